@@ -11,19 +11,26 @@ frame's 16x16 tiles are sharded over the ranks (diagonal interleave), every rank
 radiance is exchanged with ONE RCCL all_gather of the compact per-rank tile buffers per frame.  Total work is fixed, so
 scaling is "strong".
 
-`value` is K whole frames one after the other on one stream -- the same measurement for every N; for N > 1 `value_pipelined` adds the same frames
-alternating between two renderers / streams (the drain of one frame overlapping the start of the next).
+`value` is K whole frames one after the other on one stream -- the same measurement for every N; for N > 1 `--full` adds `value_pipelined`, the same
+frames alternating between two renderers / streams (the drain of one frame overlapping the start of the next).
 
 `python bench.py --gpus N --host sharded [--devices a,b,...]` measures the PRODUCT's multi-GPU host instead (include/volren_amd.h vr_sharded_*,
 csrc/sharded.cpp: ONE process, N renderers on N devices, one grouped ncclAllGather per frame through librccl) and prints the same line with
-`host: "sharded"`, `rccl_ranks: N`, `frame_crc32`.  Under the driver's torchrun command for N > 1 rank 0 also runs that mode as a child process once the
+`host: "sharded"`, `rccl_ranks: N`, `frame_crc32`.  With --full, for N > 1 rank 0 also runs that mode as a child process once the
 ranks have finished (they have left the GPUs by then) and reports it as `value_sharded` / `sharded` beside the torch.distributed `value`.
 
-Adds to the JSON line:
+A plain run does only what `value` needs: set-up, warm-up, the --steps timed steps, the outputs and the JSON line, which holds `ms_per_step` (wall
+time of one timed step) and
+  frame_crc32  -- CRC-32 of rank 0's RGBA32F frame after the last step: the same for every N (and equal to the oracle's frame).
+`--dump-outputs DIR` writes that frame (what vr_framebuffer hands a caller) as DIR/framebuffer.npy, or -- a frame larger than MAX_DUMP_BYTES -- a fixed
+seeded sample of its pixels as DIR/framebuffer_sample.npy.  The inputs are the committed fixtures and fixed seeds: the same arguments give the same inputs.
+
+With --full the run also measures, and adds to the JSON line:
+  value_pipelined -- (N > 1, or VOLREN_PIPELINE=1) the timed frames once more, alternating between two renderers / streams.
+  sharded      -- (N > 1) the product's one-process host, see above.
   value_trace_loop -- (N=1) the same frame driven the way the reference drives it, `while (sample < sppx) trace();` (src/main.cpp:533-537,
                   src/bindings.cpp:124-132): spp x vr_trace + one vr_synchronize per step.  Consecutive trace() calls are coalesced into fused launches
                   (csrc/renderer.h), so this is expected within a few per cent of `value`.
-  frame_crc32  -- CRC-32 of rank 0's RGBA32F frame after the last step: the same for every N (and equal to the oracle's frame).
   roofline     -- algorithmic HBM bytes (SURVEY.md 8d formula; event counts from the oracle's instrumented counters on the same config, 8
                   batches of one sample per pixel, their spread = bytes_per_sample_stderr) / HIP-event duration of the path-tracing kernel,
                   vs 8 TB/s; `traffic` from the committed PMC profile of the same configuration at the same frame (profiles/r4_hbm_traffic.json,
@@ -76,7 +83,31 @@ def parse_args(argv=None):
     ap.add_argument("--host", default="dist", choices=("dist", "sharded"), help="dist: one process per GPU under torch.distributed (the contract's launcher); sharded: ONE process, the product's ShardedRenderer (vr_sharded_*) on --gpus devices")
     ap.add_argument("--devices", default=None, help="--host sharded: comma list of device ordinals, one per part (repeats = logical shards of one device); default 0..gpus-1")
     ap.add_argument("--launch-check", action="store_true", help="only start the ranks, rendezvous and exchange one tile buffer (no rendering): checks the launcher path")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline: trace-loop protocol, roofline, CPU baselines, tolerance-mode kernels, "
+                    "--extra-configs, pipelined frames (N > 1) and the sharded host (N > 1); --cpu-budget and --extra-configs apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step to DIR/framebuffer.npy (float32 RGBA [H][W][4]; a sample of its pixels above MAX_DUMP_BYTES)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+MAX_DUMP_BYTES = 48 << 20   # --dump-outputs stays under 64 MB: a larger frame is written as a sample of its pixels
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: `frame` (RGBA32F [H][W][4]) as DIR/framebuffer.npy, or, above MAX_DUMP_BYTES, the pixels at fixed seeded positions (sorted, the
+    same for every run at that frame size) as DIR/framebuffer_sample.npy [n][4]."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= MAX_DUMP_BYTES:
+        np.save(os.path.join(directory, "framebuffer.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = MAX_DUMP_BYTES // px[0].nbytes
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(directory, "framebuffer_sample.npy"), px[idx])
 
 
 def free_port():
@@ -486,6 +517,8 @@ def run_sharded(args):
         step()
     s.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, s.framebuffer())
     samples = float(w) * h * spp
     parts = []
     for i, p in enumerate(s.parts):
@@ -511,7 +544,7 @@ def run_sharded(args):
         "config": {"workload": workload_name(args.config, w, h, spp),
                    "parallelism": "ONE process, ShardedRenderer (vr_sharded_*): tiles16x16 diagonal-interleaved over %d part(s) on devices %s, 1 gather/frame by %s" % (len(devices), devices, transport)},
         "rccl_ranks": len(devices) if transport == "rccl" else 0, "parts": parts,
-        "roofline": roofline_of(args.config, w, h, spp, m, event_counters(args.config, aspect=w / h)) if args.cpu_budget > 0 else None,
+        "roofline": roofline_of(args.config, w, h, spp, m, event_counters(args.config, aspect=w / h)) if args.full and args.cpu_budget > 0 else None,
     }
     print(json.dumps(out), flush=True)
     return 0
@@ -607,11 +640,13 @@ def main():
             dist.init_process_group(backend)
 
     w, h, spp = args.width, args.height, args.spp
-    b = Bench(args.config, w, h, spp, world, rank, local_rank, dist)
+    b = Bench(args.config, w, h, spp, world, rank, local_rank, dist, pipelined=None if args.full else False)
     m = b.measure(args.steps, args.warmup)
     crc = b.frame_crc32() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, b.last_renderer().framebuffer())
     trace_loop = None
-    if world == 1 and dist is None:
+    if args.full and world == 1 and dist is None:
         try:
             trace_loop = b.measure_trace_loop(args.steps)
             trace_loop["same_frame"] = bool(trace_loop["frame_crc32"] == crc)
@@ -622,29 +657,32 @@ def main():
     out = None
     if rank == 0:
         use_tf = args.config == "c3"
-        cpu = None
-        if world == 1 and dist is None and args.cpu_budget > 0:
-            cpu = cpu_baseline(args.config, args.cpu_budget, aspect=w / h)
-        counted = event_counters(args.config, aspect=w / h)
         out = {
             "metric": "Msamples/s (pixels x spp / s), volume path tracing",
             "value": m["value"], "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "strong",
-            # `value`: K frames one after the other on one stream, for every N; value_pipelined (N > 1): the same frames alternating between two renderers
-            # on two streams, the drain of frame i overlapping the start of frame i+1
-            "value_pipelined": m["value_pipelined"], "pipelined": False,
-            # the reference's protocol, `while (sample < sppx) trace();`: spp x vr_trace + one vr_synchronize per frame (coalesced into fused launches)
-            "value_trace_loop": (trace_loop or {}).get("value"), "trace_loop": trace_loop,
+            # `value`: K frames one after the other on one stream, for every N
+            "pipelined": False,
             "host": "dist",
             "frame_crc32": crc,                                # of the RGBA32F frame on rank 0 after the last step: the same for every N
             "vs_baseline": None, "dtype": "f32", "data": ("synthetic grid (tests/scenes.py generator) + reference envmap" if args.config[:2] in ("c4", "c5") else
                                       "reference fixtures (smoke.brick, table_mountain_2_puresky_1k.hdr)" + (", lut.txt" if use_tf else "")),
             "config": {"workload": workload_name(args.config, w, h, spp),
                        "parallelism": ("tiles16x16 diagonal-interleaved over %d GPU(s), 1 all_gather/frame%s" % (world, "; value_pipelined: consecutive frames over 2 streams" if b.pipelined else "")) if world > 1 else "1 GPU, %d fused launch(es)/frame (sample pool budget %d GiB)%s%s" % (m["launches"], b.r.sample_pool_mb >> 10, "; value_pipelined: consecutive frames over 2 streams" if b.pipelined else "", ", one-rank process group: pack_tiles -> all_gather -> unpack_tiles per frame" if dist is not None else "")},
-            "roofline": b.roofline(m, counted),
             "rccl_ranks": int(dist.get_world_size()) if dist is not None else 1,
             "dist_backend": (dist.get_backend() if dist is not None else None),
         }
+    if rank == 0 and args.full:
+        out.update({
+            # value_pipelined (N > 1): the same frames alternating between two renderers on two streams, the drain of frame i overlapping the start of frame i+1
+            "value_pipelined": m["value_pipelined"],
+            # the reference's protocol, `while (sample < sppx) trace();`: spp x vr_trace + one vr_synchronize per frame (coalesced into fused launches)
+            "value_trace_loop": (trace_loop or {}).get("value"), "trace_loop": trace_loop,
+        })
+        cpu = None
+        if world == 1 and dist is None and args.cpu_budget > 0:
+            cpu = cpu_baseline(args.config, args.cpu_budget, aspect=w / h)
+        out["roofline"] = b.roofline(m, event_counters(args.config, aspect=w / h))
         if cpu is not None:
             out["cpu_baseline"] = cpu
             for key, fn in (("cpu_baseline_raymarch", lambda: cpu_baseline(args.config, min(args.cpu_budget, 6.0), integrator=3, kind="raymarch-64", aspect=w / h)),
@@ -658,7 +696,7 @@ def main():
                     out[key] = {"error": str(e)}
 
     # tolerance-mode kernels (v_log/v_rcp/v_sin hardware math): speed and distance from the bit-exact default, same frame
-    if world == 1 and dist is None and args.extra_configs != "none" and getattr(b.r, "has_fast_math", lambda: False)():
+    if args.full and world == 1 and dist is None and args.extra_configs != "none" and getattr(b.r, "has_fast_math", lambda: False)():
         ref = b.r.framebuffer().copy()
         bf = Bench(args.config, w, h, spp, world, rank, local_rank, dist, fast_math=True)
         mf = bf.measure(max(1, args.steps - 1), 1)
@@ -676,7 +714,7 @@ def main():
         del bf
 
     # the other single-GPU BASELINE configs at the resolution north_star quotes (driver-run, not builder-only)
-    extra = args.extra_configs
+    extra = args.extra_configs if args.full else "none"
     if extra is None:
         extra = "c3,c4,c4@1920x1080x4096,c5full@2048x2048x4096,c5cloud@2048x2048x4096" if (args.config == "c2" and world == 1 and dist is None) else "none"
     if rank == 0 and world == 1 and extra != "none":
@@ -701,7 +739,7 @@ def main():
     if rank == 0:
         # N > 1: the product's own multi-GPU host (vr_sharded_*, one process, RCCL through librccl) on the same devices, beside the torch.distributed value.
         # The ranks have finished their collectives; this process gives its device memory back first.  VOLREN_SHARDED_LEG=0 skips it.
-        if world > 1 and os.environ.get("VOLREN_SHARDED_LEG", "1") != "0":
+        if args.full and world > 1 and os.environ.get("VOLREN_SHARDED_LEG", "1") != "0":
             import gc
             b = None
             gc.collect()

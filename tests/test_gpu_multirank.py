@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, SPP = 256, 192, 8
 
 
-def run_bench(n, backend=None, extra=(), config="c2", w=W, h=H, spp=SPP, steps=2, timeout=900):
+def run_bench(n, backend=None, extra=(), config="c2", w=W, h=H, spp=SPP, steps=2, timeout=900, full=True):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "LOCAL_WORLD_SIZE", "GROUP_RANK", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
@@ -38,7 +38,7 @@ def run_bench(n, backend=None, extra=(), config="c2", w=W, h=H, spp=SPP, steps=2
         env.pop("VOLREN_DIST_BACKEND", None)
     env["VOLREN_SAMPLE_POOL_MB"] = "1024"               # several ranks x two pipelined renderers share one GPU
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--config", config, "--width", str(w), "--height", str(h), "--spp", str(spp),
-           "--steps", str(steps), "--warmup", "1", "--cpu-budget", "0", "--extra-configs", "none"] + list(extra)
+           "--steps", str(steps), "--warmup", "1", "--cpu-budget", "0", "--extra-configs", "none"] + (["--full"] if full else []) + list(extra)
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, "bench.py --gpus %d failed (rc %d)\n%s\n%s" % (n, out.returncode, out.stdout[-2000:], out.stderr[-4000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -73,6 +73,17 @@ def test_bench_multirank_frames_equal_the_single_gpu_frame(oracle_crc):
         assert j["value_pipelined"] > 0 and j["scaling"] == "strong"    # N > 1: also the frames pipelined over two renderers / streams
         assert j["frame_crc32"] == oracle_crc, "N=%d frame differs from the N=1 frame" % n
         assert j["roofline"]["samples_per_launch"] < W * H * SPP          # a rank rendered its share, not the frame
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_dumps_the_frame_of_the_last_step(oracle_crc, tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the frame the last timed step left -- the oracle's frame."""
+    j = run_bench(1, full=False, extra=["--dump-outputs", str(tmp_path)])
+    assert j["steps"] == 2 and j["value"] > 0 and j["ms_per_step"] > 0 and j["frame_crc32"] == oracle_crc
+    assert not {"value_pipelined", "trace_loop", "value_trace_loop", "roofline", "cpu_baseline", "fast_math", "configs", "sharded"} & set(j), sorted(j)
+    fb = np.load(tmp_path / "framebuffer.npy")
+    assert fb.dtype == np.float32 and fb.shape == (H, W, 4)
+    assert zlib.crc32(fb.tobytes()) & 0xFFFFFFFF == oracle_crc
 
 
 @pytest.mark.timeout(900)

@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 
 if [ "$what" = bench ] || [ "$what" = all ]; then
   rm -rf $OUT/bench_trace
-  rocprofv3 --kernel-trace --stats -d $OUT/bench_trace -o out --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 1 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+  rocprofv3 --kernel-trace --stats -d $OUT/bench_trace -o out --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
   f=$(find $OUT/bench_trace -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/bench_kernel_stats.csv
   echo "bench under rocprofv3: rc=$? stats=$f"

@@ -10,7 +10,7 @@ export VOLREN_SAMPLE_POOL_MB=2048
 run() {   # name, then the bench arguments
     local name=$1; shift
     echo "== $name: python bench.py $* (VOLREN_DIST_BACKEND=${VOLREN_DIST_BACKEND:-nccl})" | tee $OUT/$name.log
-    python bench.py "$@" --cpu-budget 0 --extra-configs none >> $OUT/$name.log 2>&1
+    python bench.py "$@" --full --cpu-budget 0 --extra-configs none >> $OUT/$name.log 2>&1
     grep '^{' $OUT/$name.log | tail -1 > $OUT/$name.json
     python - "$OUT/$name.json" <<'PY'
 import json, sys

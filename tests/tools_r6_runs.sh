@@ -9,7 +9,7 @@ call1() {
 O=gpurun_out/r6a; mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?" | tee -a $O/summary.txt
 tail -n 3 $O/pytest.log | tee -a $O/summary.txt
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
 for c in "c2 1024 128" "c3 1024 128" "c4:512 1024 32" "c5full 2048 16" "c5cloud 2048 8"; do
   timeout -k 10 200 python tests/tools_sched_stats.py $c >> $O/sched_stats.txt 2>&1
 done
@@ -225,7 +225,7 @@ python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?" | 
 tail -n 4 $O/pytest.log | tee -a $O/summary.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?" | tee -a $O/summary.txt
 grep -E "smoke" $O/smoke.log | tail -3 | tee -a $O/summary.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
 grep "^{" $O/bench.json | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
