@@ -87,6 +87,7 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     "gpu_encoder" (dense grids are bricked on the device, default 1)
  *     "integrator" (0 DDA tracking = both reference kernels, 1 global-majorant tracking = common.glsl:333-394, 2 direct volume rendering
  *     = common.glsl:571-591, needs a transfer function, 3 trace_path around the 64-step ray-marching trackers = common.glsl:506-566)
+ *     "variance" (default 0; 1 = every accumulation pass also keeps the per-pixel second moments of the samples: vr_variance)
  *     "fast_math" (0 = the specified, bit-reproducible arithmetic; 1 = opt-in tolerance mode: hardware log/sin/cos/rcp, within 1e-3
  *     relative L2 of the default -- refused with VR_ERR while a transfer function is bound, where it misses that bound)
  *     "tf_float_atlas" (default 1: transfer-function renders of brick grids decode the atlas to floats once, 4x its size; 0 = read the bytes)
@@ -143,6 +144,23 @@ int vr_last_pathtrace_ms(vr_renderer* r, double* ms);
  *     vr_save_png = tonemap + Texture2D::save_ldr of the offline loop (src/main.cpp:540-555): RGBA8 PNG, top row first. */
 int vr_framebuffer(vr_renderer* r, float* rgba_out);
 int vr_framebuffer_device(vr_renderer* r, void** device_ptr);
+/* --- denoiser data (no reference counterpart; the reference's scripts/datagen_denoise.py exports colour only).
+ *     vr_render_features: for every pixel of the tile set, the first scattering event of colour samples 1..spp -- same seed, jitter and camera
+ *     ray as colour sample s, then the first segment of the DDA tracker (common.glsl:458-501) with the same draws, whatever "integrator" is and
+ *     always in the specified arithmetic ("fast_math" does not apply).  Per pixel, over the samples that collide (H of spp): albedo (vol_albedo
+ *     [x the LUT's rgb]), normal (-normalize(transpose(Minv3) g), g the central difference of the trilinear density, not renormalised after
+ *     averaging) and depth (distance along the unit camera ray) averaged, and coverage = H / spp; zeros where H = 0.  Not progressive: each call
+ *     computes samples 1..spp afresh.  Asynchronous on the renderer's stream; a flush point like vr_render.  Bounded like the path tracer: a
+ *     segment whose ray parameter can no longer advance (a camera very far from the volume for its voxel size) ends without a collision, and
+ *     a pixel whose segment exceeds a step budget stops there, which the next vr_synchronize reports as an error.
+ *     vr_features waits and writes W*H*8 floats (albedo.rgb, coverage, normal.xyz, depth), row 0 at the bottom; VR_ERR before the first
+ *     vr_render_features since the last resize.
+ *     vr_variance waits and writes W*H*4 floats: the unbiased per-channel variance of the samples 1..n behind the framebuffer (0 for n = 1),
+ *     kept when vr_set_int "variance" is 1 (default 0; the buffer is allocated only then).  VR_ERR unless "variance" was on for every one of
+ *     samples 1..n (switched on mid-frame: vr_reset and render again). */
+int vr_render_features(vr_renderer* r, int spp);
+int vr_features(vr_renderer* r, float* out);
+int vr_variance(vr_renderer* r, float* rgba_out);
 int vr_draw(vr_renderer* r);
 int vr_display(vr_renderer* r, float* rgba_out);
 int vr_save_png(vr_renderer* r, const char* path);

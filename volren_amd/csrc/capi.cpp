@@ -285,6 +285,7 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
         else if (n == "tonemapping") R.tonemapping = v != 0;
         else if (n == "integrator") R.integrator = v;
         else if (n == "fast_math") R.fast_math = v != 0;
+        else if (n == "variance") { if (v < 0 || v > 1) throw std::runtime_error("variance: 0 (off) or 1 (keep the per-pixel second moments)"); R.variance = v; }
         else if (n == "coalesce_trace") { R.flush_pending(); R.coalesce_trace = v != 0; }
         else if (n == "majorant_layout") { if (v < -1 || v > 1) throw std::runtime_error("majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)"); R.majorant_layout = v; }
         else if (n == "tf_float_atlas") R.tf_float_atlas = v != 0;
@@ -313,6 +314,7 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
         else if (n == "tonemapping") *v = R.tonemapping ? 1 : 0;
         else if (n == "integrator") *v = R.integrator;
         else if (n == "fast_math") *v = R.fast_math ? 1 : 0;
+        else if (n == "variance") *v = R.variance;
         else if (n == "coalesce_trace") *v = R.coalesce_trace ? 1 : 0;
         else if (n == "majorant_layout") *v = R.majorant_layout;
         else if (n == "majorant_blocked") {          // what the current frame's next launch will use
@@ -406,7 +408,9 @@ int vr_synchronize(vr_renderer* r) {
     return guard([&] {
         use_device(r);
         r->impl.synchronize();
-        if (r->impl.watchdog_status() != 0) throw std::runtime_error("path-tracing kernel watchdog tripped (a wavefront exceeded its step budget)");
+        const uint32_t st = r->impl.watchdog_status();
+        if (st & vr::kFeatureLostStatus) throw std::runtime_error("feature pass: a camera segment exceeded its step budget (vr_render_features); the pixels concerned cover only their samples before it");
+        if (st != 0) throw std::runtime_error("path-tracing kernel watchdog tripped (a wavefront exceeded its step budget)");
     });
 }
 
@@ -426,6 +430,24 @@ int vr_framebuffer(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
     return guard([&] { use_device(r); r->impl.download(out); });
+}
+// denoiser data: the device is checked before the renderer is touched
+int vr_render_features(vr_renderer* r, int spp) {
+    NEED(r);
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.render_features(spp); });
+}
+int vr_features(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.download_features(out); });
+}
+int vr_variance(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.download_variance(out); });
 }
 int vr_framebuffer_device(vr_renderer* r, void** p) {
     NEED(r);

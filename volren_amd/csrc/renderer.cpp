@@ -55,6 +55,8 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     resolution = { (int)w, (int)h };
     color = make_device_buffer((size_t)w * h * 4 * sizeof(float));
     display.reset();
+    features_.reset();
+    moments_.reset(); moments_n_ = -1;
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
 }
@@ -502,7 +504,7 @@ bool RendererHIP::LaunchInputs::same_launch_as(const LaunchInputs& o) const {
     return memcmp(&P, &o.P, sizeof P) == 0 && frame == o.frame && maj.density_scale == o.maj.density_scale && maj.tf_version == o.maj.tf_version &&
            maj.wl == o.maj.wl && maj.ww == o.maj.ww && maj.blocked == o.maj.blocked && memcmp(tuning.thr, o.tuning.thr, sizeof tuning.thr) == 0 && tuning.stats == o.tuning.stats &&
            tuning.samples_per_unit == o.tuning.samples_per_unit && tuning.blocks_per_cu == o.tuning.blocks_per_cu && order_tiles == o.order_tiles &&
-           launch_target_ms == o.launch_target_ms && fast_math == o.fast_math && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
+           launch_target_ms == o.launch_target_ms && fast_math == o.fast_math && variance == o.variance && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
 }
 
 // What a launch reads from the renderer's public, freely mutable state -- taken when trace() / render() is CALLED (the reference issues its dispatch at that
@@ -555,7 +557,7 @@ void RendererHIP::capture(LaunchInputs& in) {
     in.maj.frame = in.frame;
     in.maj.blocked = in.P.density.maj_blocked;
     in.tuning = tuning;
-    in.order_tiles = order_tiles; in.launch_target_ms = launch_target_ms; in.fast_math = fast_math ? 1 : 0;
+    in.order_tiles = order_tiles; in.launch_target_ms = launch_target_ms; in.fast_math = fast_math ? 1 : 0; in.variance = variance != 0 ? 1 : 0;
     in.sample_pool_bytes = sample_pool_bytes;
     in.stream = stream;
     in.env = environment; in.tf = transferfunc;
@@ -647,6 +649,20 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n) {
             probe = std::min(probe, n);
         } else per_launch = cap_by_rate(per_launch);
     }
+    // second moments: valid while every launch since sample 1 has kept them (a launch from sample 1 starts them afresh)
+    float* moments = nullptr;
+    if (in.variance) {
+        const size_t bytes = color->size_bytes();
+        if (!moments_ || moments_->size_bytes() != bytes) {
+            moments_ = make_device_buffer(bytes);
+            VR_HIP(hipMemsetAsync(moments_->get(), 0, bytes, stream));
+            if (first > 0) moments_n_ = -1;
+        }
+        moments = moments_->as<float>();
+        moments_n_ = first == 0 ? n : (moments_n_ == first ? first + n : -1);
+    } else {
+        moments_n_ = -1;
+    }
     VR_HIP(hipEventRecord(ev0_, stream));
     last_launches = 0;
     pt_events_used_ = 0;
@@ -659,7 +675,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n) {
             eb = pt_events_[pt_events_used_]; ee = pt_events_[pt_events_used_ + 1];
             pt_events_used_ += 2;
         }
-        launch_pathtrace(in.tuning, P, color->as<float>(), pool_->as<float>(), workspace_->as<float>(), status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m, status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee);
+        launch_pathtrace(in.tuning, P, color->as<float>(), pool_->as<float>(), workspace_->as<float>(), status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m, status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments);
         VR_HIP(hipGetLastError());
         done += m;
         if (pt_kernel) { rate_pending_samples_ = px_samples * (double)m; rate_pending_key_ = key; }
@@ -790,8 +806,51 @@ void RendererHIP::download_display(float* rgba) const {
     display->download(rgba, display->size_bytes(), stream);
 }
 
+// The feature pass reads the scene as a render() would: capture() (which also decodes the float atlas under a transfer function) and the majorant
+// table of the current density scale and LUT.  It runs the lane code of the run-time kernel variant, which reads every grid from its own atlas:
+// the views of a frame whose grids share a paired atlas are made again without it (the majorant layout stays the one the table is built in).
+void RendererHIP::render_features(int spp) {
+    if (spp <= 0) throw std::runtime_error("render_features: spp must be positive");
+    flush_pending();
+    LaunchInputs in;
+    capture(in);
+    update_majorants(in, density_grids.at(in.frame));
+    SceneParams P = in.P;
+    if (P.paired) {
+        P.density = make_view(density_grids.at(in.frame), false, P.density.maj_blocked != 0);
+        P.emission = make_view(emission_grids.at(in.frame), false);
+        P.paired = 0;
+    }
+    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : ((resolution.x + 15) / 16) * ((resolution.y + 15) / 16);
+    const size_t bytes = (size_t)resolution.x * resolution.y * 8 * sizeof(float);
+    if (!features_ || features_->size_bytes() != bytes) {
+        features_ = make_device_buffer(bytes);
+        VR_HIP(hipMemsetAsync(features_->get(), 0, bytes, stream));
+    }
+    launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, features_->as<float>(), status_->as<uint32_t>(), stream);
+    VR_HIP(hipGetLastError());
+}
+
+void RendererHIP::download_features(float* out) {
+    if (!features_) throw std::runtime_error("features: no feature pass since the last resize (call render_features first)");
+    flush_pending();
+    features_->download(out, features_->size_bytes(), stream);
+}
+
+void RendererHIP::download_variance(float* rgba) {
+    flush_pending();
+    if (sample < 1 || !moments_ || moments_n_ != sample)
+        throw std::runtime_error("variance: the moments do not cover samples 1.." + std::to_string(sample) +
+                                 " (variance was off for some of them, e.g. switched on mid-frame): reset() and render with variance = 1");
+    moments_->download(rgba, moments_->size_bytes(), stream);
+    const size_t n = (size_t)resolution.x * resolution.y * 4;
+    const float f = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;
+    for (size_t i = 0; i < n; ++i) rgba[i] = sample >= 2 ? rgba[i] * f : 0.0f;
+}
+
 uint32_t RendererHIP::watchdog_status() {
-    // bit 0: a wavefront gave up (iteration / shader-clock budget), bit 1: a path ended in an impossible state.
+    // bit 0: a wavefront gave up (iteration / shader-clock budget), bit 1: a path ended in an impossible state, bit 2 (kFeatureLostStatus): a feature
+    // sample's tracker exceeded its step budget.
     // Read-and-clear, so that one bad launch does not poison the renderer.
     flush_pending();
     uint32_t s = 0;

@@ -131,6 +131,7 @@ struct RendererHIP {
                                                       // commit() (blocked when more than kBlockedMajorantBricks bricks carry voxels: the large, well filled sparse grids of
                                                       // BASELINE configs[4], +3 % there, -2 % on small or thinly filled ones: profiles/r4d_*, r5_*), 0 = linear, 1 = blocked.
                                                       // Results never depend on it
+    int variance = 0;                                 // 1: every accumulation pass also keeps the per-channel second moments of the samples (download_variance)
     bool fast_math = false;                           // opt-in tolerance mode: hardware log/sin/cos/rcp instead of the specified arithmetic
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
                                                       // with one bound the renderer refuses it: DESIGN.md 3)
@@ -147,6 +148,12 @@ struct RendererHIP {
     void set_tiles(const std::vector<int32_t>& tile_ids);     // empty = whole frame
     void fill_params(SceneParams& P);                          // renderer.cpp:88-138
     void download(float* rgba);                                // color -> host
+    // Denoiser data.  render_features(spp): the first-scatter features of samples 1..spp of every pixel of the tile set (vr_trace.h feature_pixel),
+    // computed afresh into their own W*H*8 buffer (asynchronous; flushes recorded samples first).  download_features: that buffer, W*H*8 floats.
+    // download_variance: the unbiased per-channel variance of samples 1..sample, W*H*4 floats -- needs `variance` on for all of them.
+    void render_features(int spp);
+    void download_features(float* out);
+    void download_variance(float* rgba);
     void download_display(float* rgba) const;
     void synchronize();
     // Launches the samples that coalesced trace() calls have recorded (no-op without any).  Every member function that reads or replaces the
@@ -177,7 +184,7 @@ private:
         MajKey maj;
         size_t frame = 0;
         PathtraceTuning tuning;
-        int order_tiles = 0, launch_target_ms = 0, fast_math = 0;
+        int order_tiles = 0, launch_target_ms = 0, fast_math = 0, variance = 0;
         size_t sample_pool_bytes = 0;
         hipStream_t stream = nullptr;
         std::shared_ptr<Environment> env;
@@ -201,6 +208,9 @@ private:
     DeviceBufferPtr pool_;
     DeviceBufferPtr workspace_;
     DeviceBufferPtr stats_;                            // 32 counters of the instrumented kernels (sched_stats)
+    DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
+    DeviceBufferPtr moments_;                          // W*H*4 second moments, allocated by the first launch with `variance` on
+    int moments_n_ = -1;                               // the moments cover samples 1..moments_n_ (-1: they do not start at sample 1)
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     std::vector<hipEvent_t> pt_events_;                // (begin, end) around the path-tracing kernel of every sub-launch
     size_t pt_events_used_ = 0;

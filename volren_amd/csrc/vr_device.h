@@ -28,7 +28,13 @@ size_t pathtrace_pool_floats(const PathtraceTuning& T, int32_t n_tiles, int32_t 
 size_t pathtrace_workspace_floats();      // cold path state of all resident wavefronts
 void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
                       int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math = false,
-                      hipEvent_t ev_kernel_begin = nullptr, hipEvent_t ev_kernel_end = nullptr);      // optional: bracket the path-tracing kernel alone
+                      hipEvent_t ev_kernel_begin = nullptr, hipEvent_t ev_kernel_end = nullptr,      // optional: bracket the path-tracing kernel alone
+                      float* moments = nullptr);      // optional: W*H*4 per-channel second moments S = M2 / n, folded in the same pass (vr_set_int "variance")
+// Denoiser features of samples 1..spp for every pixel of the listed tiles (tiles == nullptr: all n_tiles of the frame): out = W*H*8 floats,
+// (albedo.rgb, coverage, normal.xyz, depth) per pixel, row 0 at the bottom (vr_trace.h feature_pixel).  Pixels of other tiles are not written.
+// status: the renderer's status word; a pixel whose tracker exceeded its step budget sets kFeatureLostStatus there (its remaining samples are not run).
+constexpr uint32_t kFeatureLostStatus = 4u;
+void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream);
 // which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
 // what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
 enum PathtraceVariantReason : int {

@@ -11,7 +11,7 @@
 //
 // Also here: the environment importance pyramid + warp table (env_setup.glsl, environment.cpp), the dense->brick encoder
 // (voldata to_brick_grid at commit()), majorant remap, tonemap.glsl, direct volume rendering (common.glsl:571-591),
-// tile pack/unpack for the multi-GPU gather, and a math probe for the tests.
+// tile pack/unpack for the multi-GPU gather, the denoiser feature pass and a math probe for the tests.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -59,6 +59,7 @@ raymarch_kernel(const SceneParams P, float* __restrict__ sbuf, const LaunchDesc 
 }
 
 // Running mean over the samples of one launch, in sample order (pathtracer_brick.glsl:36): one thread per pixel.
+// (accumulate_moments_kernel below is this kernel plus the second moments: its pixel mapping and sample-pool indexing must change with these)
 __global__ void __launch_bounds__(256)
 accumulate_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, const int32_t* __restrict__ tiles, int32_t n_tiles,
                   int32_t W, int32_t H, int32_t first_sample, int32_t n_samples, int32_t spu) {
@@ -80,6 +81,66 @@ accumulate_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, const 
         accumulate_sample(acc, L, first_sample + k);
     }
     *texel = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+// accumulate_kernel -- same pixel mapping, same sample-pool indexing: keep the two in step -- with the per-channel second moments (variance = 1): Welford in the running-mean form, S_k = M2_k / k, in a W*H*4 buffer beside
+// the colour.  The mean is the same mix_ as accumulate_sample's, bit for bit.
+__global__ void __launch_bounds__(256)
+accumulate_moments_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, float* __restrict__ moments, const int32_t* __restrict__ tiles, int32_t n_tiles,
+                          int32_t W, int32_t H, int32_t first_sample, int32_t n_samples, int32_t spu) {
+    const int32_t tiles_x = (W + 15) >> 4;
+    const int32_t tile = tiles ? tiles[blockIdx.x] : (int32_t)blockIdx.x;
+    const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
+    const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
+    const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
+    if (px >= W || py >= H) return;
+    float4* texel = reinterpret_cast<float4*>(fb) + (size_t)py * W + px;
+    float4* mtexel = reinterpret_cast<float4*>(moments) + (size_t)py * W + px;
+    float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, S[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if (first_sample > 1) {
+        const float4 c = *texel, m = *mtexel;
+        acc[0] = c.x; acc[1] = c.y; acc[2] = c.z; acc[3] = c.w;
+        S[0] = m.x; S[1] = m.y; S[2] = m.z; S[3] = m.w;
+    }
+    const float4* sb = reinterpret_cast<const float4*>(sbuf);
+    for (int32_t k = 0; k < n_samples; ++k) {
+        const int32_t chunk = k / spu, sl = k - chunk * spu;
+        const size_t unit = ((size_t)chunk * n_tiles + blockIdx.x) * 4u + (uint32_t)wave;
+        const float4 v = sb[unit * (size_t)(spu * 64) + (size_t)sl * 64u + (uint32_t)p];
+        const float L[4] = { v.x, v.y, v.z, v.w };
+        const float a = 1.0f / (float)(first_sample + k);
+        for (int32_t c = 0; c < 4; ++c) {
+            const float x = sanitize(L[c]);
+            const float mu = acc[c], mu1 = mix_(mu, x, a);
+            S[c] = mix_(S[c], (x - mu) * (x - mu1), a);
+            acc[c] = mu1;
+        }
+    }
+    *texel = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *mtexel = make_float4(S[0], S[1], S[2], S[3]);
+}
+
+// Denoiser features (vr_trace.h feature_pixel): one thread per pixel of the renderer's tiles, all `spp` samples in a loop, laid out like accumulate_kernel.
+// out: W*H*8 floats.  The first segment of the DDA tracker only, so a few registers' worth of state: no scheduler, no sample pool.
+template <bool TF>
+__global__ void __launch_bounds__(256)
+features_kernel(const SceneParams P, const int32_t* __restrict__ tiles, int32_t spp, float* __restrict__ out, uint32_t* __restrict__ status) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const int32_t tiles_x = (W + 15) >> 4;
+    const int32_t tile = tiles ? tiles[blockIdx.x] : (int32_t)blockIdx.x;
+    const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
+    const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
+    const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
+    if (px >= W || py >= H) return;
+    float f[8];
+    if (!feature_pixel<TF>(P, px, py, spp, f)) atomicOr(status, kFeatureLostStatus);      // a sample over its step budget (vr_trace.h feature_sample)
+    float4* o = reinterpret_cast<float4*>(out) + 2u * ((size_t)py * W + px);
+    o[0] = make_float4(f[0], f[1], f[2], f[3]);
+    o[1] = make_float4(f[4], f[5], f[6], f[7]);
+}
+void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream) {
+    if (n_tiles <= 0 || spp <= 0) return;
+    if (P.u.use_tf) hipLaunchKernelGGL(features_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
+    else hipLaunchKernelGGL(features_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
 }
 
 // Units of 8 samples x 64 pixels, except on the dense-grid kernel, whose long paths (128 bounces, every camera ray scatters) fill
@@ -191,7 +252,8 @@ static int resident_blocks(const PathtraceTuning& T, int mode, int variant, bool
 size_t pathtrace_workspace_floats() { return kColdMainFloats + (size_t)kMaxWorkgroups * 4u * (size_t)kColdSideWaveFloats; }      // cold state of 4 wavefronts per resident workgroup: main slots, then the side array
 
 void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
-                      int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math, hipEvent_t ev_kernel_begin, hipEvent_t ev_kernel_end) {
+                      int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math, hipEvent_t ev_kernel_begin, hipEvent_t ev_kernel_end,
+                      float* moments) {
     if (n_tiles <= 0 || n_samples <= 0) return;
     SchedParams S;
     for (int i = 0; i < ST_COUNT; ++i) S.thr[i] = T.thr[i];
@@ -230,8 +292,12 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
         kPtLaunch[mode][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats);
         if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
     }
-    hipLaunchKernelGGL(accumulate_kernel, dim3((unsigned)n_tiles), block, 0, stream, sample_pool, fb, tiles, n_tiles,
-                       P.u.resolution[0], P.u.resolution[1], first_sample, n_samples, D.spu);
+    if (moments)
+        hipLaunchKernelGGL(accumulate_moments_kernel, dim3((unsigned)n_tiles), block, 0, stream, sample_pool, fb, moments, tiles, n_tiles,
+                           P.u.resolution[0], P.u.resolution[1], first_sample, n_samples, D.spu);
+    else
+        hipLaunchKernelGGL(accumulate_kernel, dim3((unsigned)n_tiles), block, 0, stream, sample_pool, fb, tiles, n_tiles,
+                           P.u.resolution[0], P.u.resolution[1], first_sample, n_samples, D.spu);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -1669,6 +1669,92 @@ VR_HD void dvr_sample(const SceneParams& P, int32_t px, int32_t py, int32_t smp,
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Denoiser features: the first scattering event of colour sample `smp`'s camera ray.  Same seed, jitter and ray as the colour sample,
+// then the first segment of sample_volumeDDA (common.glsl:458-501) driven through the lane code's own helpers on a private Hot -- the DDA
+// tracker whatever the integrator, with every draw of the colour path's camera segment (transfer-function lookup, emission taps) in the
+// same order.  Result: FEAT_HIT (real collision), FEAT_MISS, or FEAT_LOST.  On a hit, t = distance along the unit camera ray, albedo = the
+// throughput after the collision (vol_albedo [* the LUT's rgb]), normal = -normalize(transpose(Minv3) g), g the central difference of the
+// trilinear density at the collision (one voxel each way), 0 where g vanishes.  Nothing is written otherwise.
+// The tracker runs outside the path scheduler and its watchdog, so it is bounded here:
+//   * a march step that changes nothing -- t, tau and the (saturated) mip level as they were: t so large that t + dt rounds back to t, in an
+//     empty cell -- is a fixed point the reference's loop never leaves; the segment ends there without a collision (FEAT_MISS).  Wherever the
+//     reference's loop ends, it never meets such a step, so results are unchanged;
+//   * any other segment that takes more than kFeatureMaxSteps march steps and collisions (a few thousand is the most a real one needs) is
+//     given up: FEAT_LOST, which the kernel reports in the renderer's status word (vr_synchronize fails).
+enum FeatureResult : int32_t { FEAT_MISS = 0, FEAT_HIT = 1, FEAT_LOST = 2 };
+constexpr uint32_t kFeatureMaxSteps = 1u << 20;
+struct FeatureCold {
+    float v[C_COUNT];
+    VR_HD float ld(int32_t f) const { return v[f]; }
+    VR_HD void st(int32_t f, float x) { v[f] = x; }
+};
+template <bool TF>
+VR_HD int32_t feature_sample(const SceneParams& P, int32_t px, int32_t py, int32_t smp, float& t, v3& albedo, v3& normal) {
+    using K = TraceCfg<TF, 0, 2, 2, 2>;
+    const Uniforms& u = P.u;
+    const int32_t W = u.resolution[0], H = u.resolution[1];
+    Hot h;
+    hot_init(h);
+    h.seed = tea32((uint32_t)u.seed * (uint32_t)(py * W + px), (uint32_t)smp);
+    const float jx = rng(h.seed), jy = rng(h.seed);
+    const float fx = (((float)px + jx) - (float)W * 0.5f) / (float)H;
+    const float fy = (((float)py + jy) - (float)H * 0.5f) / (float)H;
+    const v3 dir = normalize(mat3_mul(u.cam_transform, normalize(v3{ fx, fy, P.cam_z })));
+    const v3 pos = v3{ u.cam_pos[0], u.cam_pos[1], u.cam_pos[2] };
+    if (!begin_segment<K>(h, P, pos, dir, 0)) return FEAT_MISS;
+    FeatureCold c;
+    for (int32_t i = 0; i < C_COUNT; ++i) c.v[i] = 0.0f;       // throughput 1 is not needed: the emission radiance it weighs is discarded
+    for (uint32_t steps = 0u; h.state == ST_MARCH || h.state == ST_COLLIDE; ++steps) {
+        if (steps >= kFeatureMaxSteps) return FEAT_LOST;
+        if (h.state == ST_MARCH) {
+            const float t0 = h.t, tau0 = h.tau;
+            const int32_t mip0 = h.mipq;
+            do_march<TF, 2, 2>(h, P);
+            if (h.state == ST_MARCH && h.t == t0 && h.tau == tau0 && h.mipq == mip0) return FEAT_MISS;
+        } else {
+            do_collide<K, FeatureCold, false>(h, c, P);
+        }
+    }
+    if (h.state != ST_NEE) return FEAT_MISS;
+    t = h.t;
+    albedo = v3{ u.vol_albedo[0], u.vol_albedo[1], u.vol_albedo[2] };
+    if (TF) albedo = albedo * ld3(c, C_COL);
+    const v3 ip = axpy(h.ipos, h.t, h.idir);
+    const v3 g = v3{ density_trilinear_raw(P.density, v3{ ip.x + 1.0f, ip.y, ip.z }) - density_trilinear_raw(P.density, v3{ ip.x - 1.0f, ip.y, ip.z }),
+                     density_trilinear_raw(P.density, v3{ ip.x, ip.y + 1.0f, ip.z }) - density_trilinear_raw(P.density, v3{ ip.x, ip.y - 1.0f, ip.z }),
+                     density_trilinear_raw(P.density, v3{ ip.x, ip.y, ip.z + 1.0f }) - density_trilinear_raw(P.density, v3{ ip.x, ip.y, ip.z - 1.0f }) };
+    const float* m = u.vol_density_inv_transform;          // column-major: row i of transpose(Minv3) = column i of Minv3
+    const v3 n = v3{ (m[0] * g.x + m[1] * g.y) + m[2] * g.z, (m[4] * g.x + m[5] * g.y) + m[6] * g.z, (m[8] * g.x + m[9] * g.y) + m[10] * g.z };
+    normal = (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) ? v3{ 0, 0, 0 } : -normalize(n);
+    return FEAT_HIT;
+}
+// Per pixel over samples 1..spp, float sums in sample order: out = (albedo.rgb, coverage, normal.xyz, depth), the hit-weighted means
+// (the normal not renormalised), coverage = hits / spp; zeros where no sample hit.  Returns false when a sample was lost (feature_sample):
+// the pixel's remaining samples are not run then (its values cover the samples before), so that one thread stays bounded.
+template <bool TF>
+VR_HD bool feature_pixel(const SceneParams& P, int32_t px, int32_t py, int32_t spp, float out[8]) {
+    int32_t hits = 0;
+    v3 sa = v3{ 0, 0, 0 }, sn = v3{ 0, 0, 0 };
+    float sd = 0.0f;
+    bool ok = true;
+    for (int32_t s = 1; s <= spp; ++s) {
+        float t = 0.0f;
+        v3 a, n;
+        const int32_t r = feature_sample<TF>(P, px, py, s, t, a, n);
+        if (r == FEAT_LOST) { ok = false; break; }
+        if (r != FEAT_HIT) continue;
+        ++hits;
+        sa = sa + a; sn = sn + n; sd += t;
+    }
+    for (int32_t i = 0; i < 8; ++i) out[i] = 0.0f;
+    if (hits == 0) return ok;
+    const float fh = (float)hits;
+    out[0] = sa.x / fh; out[1] = sa.y / fh; out[2] = sa.z / fh; out[3] = fh / (float)spp;
+    out[4] = sn.x / fh; out[5] = sn.y / fh; out[6] = sn.z / fh; out[7] = sd / fh;
+    return ok;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // trace_path with the 64-step ray-marching trackers (common.glsl:506-566: transmittance_raymarch, sample_volume_raymarch;
 // RAYMARCH_STEPS 64).  Dead code in the reference -- no kernel calls them; trace_path only switches between the DDA and the
 // global-majorant pair -- offered as integrator = 3.  Every step costs a stochastic-tricubic tap (9 draws), also with a

@@ -7,7 +7,8 @@ import numpy as np
 from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
-               "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout")
+               "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
+               "variance")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
@@ -19,7 +20,10 @@ def _f32(a):
 
 
 class Renderer:
-    """`Renderer(w, h)`; set fields; `load_volume/load_envmap/load_transferfunc`; `render(spp)`; `fbo_data()`."""
+    """`Renderer(w, h)`; set fields; `load_volume/load_envmap/load_transferfunc`; `render(spp)`; `fbo_data()`.
+
+    One name is both a field and a method: `r.variance = 1` switches the per-pixel moments on (vr_set_int "variance"), `r.variance()` returns the
+    variance buffer, and `r.get_int("variance")` reads the switch back (the attribute itself is the method)."""
 
     def __init__(self, width, height, device=0, _borrowed=None):
         object.__setattr__(self, "_h", None)
@@ -48,6 +52,12 @@ class Renderer:
             pass
 
     # ---- fields ----
+    def get_int(self, name):
+        """vr_get_int: an int field by name (e.g. "variance", whose attribute name is taken by the method variance())."""
+        v = C.c_int()
+        _lib.check(self._L.vr_get_int(self._h, name.encode(), C.byref(v)))
+        return v.value
+
     def __getattr__(self, name):
         if name in _INT_FIELDS or name in ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason"):
             v = C.c_int()
@@ -216,6 +226,25 @@ class Renderer:
     def fbo_data(self):
         """float RGB of the framebuffer (bindings.cpp:141-148)."""
         return self.framebuffer()[..., :3].copy()
+
+    # ---- denoiser data ----
+    def render_features(self, spp, sync=True):
+        """First-scatter features of samples 1..spp of every pixel (include/volren_amd.h vr_render_features), computed afresh."""
+        _lib.check(self._L.vr_render_features(self._h, int(spp)))
+        if sync:
+            self.synchronize()
+
+    def features(self):
+        """[H][W][8] float32, row 0 = bottom: albedo.rgb, coverage, normal.xyz, depth."""
+        out = np.empty((self.height, self.width, 8), np.float32)
+        _lib.check(self._L.vr_features(self._h, out.ctypes.data))
+        return out
+
+    def variance(self):
+        """[H][W][4] float32, row 0 = bottom: unbiased per-channel variance of samples 1..sample (needs `variance = 1` for all of them)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _lib.check(self._L.vr_variance(self._h, out.ctypes.data))
+        return out
 
     def framebuffer_device_ptr(self):
         p = C.c_void_p()

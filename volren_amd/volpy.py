@@ -422,6 +422,8 @@ class Renderer:
 
     # -- fields ------------------------------------------------------------------------------------------------------
     def __getattr__(self, name):
+        if name == "variance":
+            return self._r.get_int("variance")
         if name in _SCALARS:
             return getattr(self._r, name)
         if name in _VEC3S:
@@ -429,7 +431,7 @@ class Renderer:
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in _SCALARS:
+        if name in _SCALARS or name == "variance":
             setattr(self._r, name, value)
         elif name in _VEC3S:
             setattr(self._r, name, np.asarray(vec3(value) if np.ndim(value) == 0 else value, np.float32).reshape(3))
@@ -528,6 +530,19 @@ class Renderer:
         """Float RGB of the accumulation buffer with the reference's declared buffer shape (w, h, 3) (bindings.cpp:69-77,143)."""
         rgb = self._r.fbo_data()
         return rgb.reshape(self._r.width, self._r.height, 3)
+
+    # -- denoiser data (no reference counterpart): same declared buffer shape as fbo_data(), so np.flip(np.array(...), axis=0) treats them alike
+    def render_features(self, spp):
+        """First-scatter features of samples 1..spp, computed afresh (`seed` as for colour: feature sample s belongs to colour sample s)."""
+        self._r.render_features(int(spp))
+
+    def feature_data(self):
+        """(w, h, 8) float: albedo.rgb, coverage, normal.xyz, depth."""
+        return self._r.features().reshape(self._r.width, self._r.height, 8)
+
+    def variance_data(self):
+        """(w, h, 3) float: per-channel variance of the colour samples behind fbo_data() (set `variance = 1` before rendering)."""
+        return self._r.variance()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
 
     def _write(self, filename, channels):
         from PIL import Image
