@@ -88,6 +88,7 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     "integrator" (0 DDA tracking = both reference kernels, 1 global-majorant tracking = common.glsl:333-394, 2 direct volume rendering
  *     = common.glsl:571-591, needs a transfer function, 3 trace_path around the 64-step ray-marching trackers = common.glsl:506-566)
  *     "variance" (default 0; 1 = every accumulation pass also keeps the per-pixel second moments of the samples: vr_variance)
+ *     "denoise_iterations" (a-trous iterations of vr_denoise, 0 .. 10, default 5; 0 = the colour unchanged)
  *     "fast_math" (0 = the specified, bit-reproducible arithmetic; 1 = opt-in tolerance mode: hardware log/sin/cos/rcp, within 1e-3
  *     relative L2 of the default -- refused with VR_ERR while a transfer function is bound, where it misses that bound)
  *     "tf_float_atlas" (default 1: transfer-function renders of brick grids decode the atlas to floats once, 4x its size; 0 = read the bytes)
@@ -100,7 +101,9 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     paths are what is left when its work queue runs empty: 0 = never (raster order), 1 = when a tile subset is set (vr_set_tiles / a sharded
  *     renderer's parts; default), 2 = always.  Results never depend on the order) (int);  "tonemap_exposure" "tonemap_gamma" "albedo"(3) "phase" "density_scale"
  *     "emission_scale" "vol_clip_min"(3) "vol_clip_max"(3) "env_strength" "env_transform"(9) "env_rot"(1, degrees about +y,
- *     main.cpp:382) "tf_window_left" "tf_window_width" "cam_pos"(3) "cam_dir"(3) "cam_up"(3) "cam_fov" "volume_transform"(16) (float) */
+ *     main.cpp:382) "tf_window_left" "tf_window_width" "cam_pos"(3) "cam_dir"(3) "cam_up"(3) "cam_fov" "volume_transform"(16)
+ *     "denoise_sigma"(5: the edge-stopping widths of vr_denoise for colour, normal, depth, coverage, albedo; each finite and > 0; default
+ *     4, 0.5, 0.1, 0.25, 0.2) (float) */
 /* read-only through vr_get_int: "kernel_variant" (the compiled path-tracing kernel the next launch uses: 0 brick grid, 1 dense fp16 grid, 2 / 4 brick grid +
  *     emission grid, 3 everything decided at run time -- correct for every scene, up to an order of magnitude slower) and "kernel_variant_reason" (what sent the
  *     scene to variant 3, a mask: 1 integrator != 0, 2 the environment's warp table has thresholds below 2^-76 ("env_div_safe" = 0), 4 density scale outside
@@ -161,6 +164,18 @@ int vr_framebuffer_device(vr_renderer* r, void** device_ptr);
 int vr_render_features(vr_renderer* r, int spp);
 int vr_features(vr_renderer* r, float* out);
 int vr_variance(vr_renderer* r, float* rgba_out);
+/* --- denoiser (no reference counterpart either: scripts/datagen_denoise.py exports the noisy colour for a denoiser of the caller's own).
+ *     vr_denoise: the edge-avoiding a-trous wavelet filter (the spatial part of SVGF, Schied et al. 2017) of the current frame, guided by the
+ *     per-pixel variance and the last vr_render_features: "denoise_iterations" passes at steps 1, 2, 4, ... of a 5x5 B3-spline kernel whose taps are
+ *     weighted down by differences in luminance (relative to the filtered standard deviation), coverage, normal, depth and albedo ("denoise_sigma";
+ *     the arithmetic is specified operation by operation in volren_amd/csrc/vr_denoise.h and reproducible bit for bit).  Asynchronous on the
+ *     renderer's stream; a flush point like vr_render_features.  VR_ERR when no feature pass has run since the last resize, when "variance" was not
+ *     on for every one of samples 1..n, when n < 1, or while a tile subset is set (the filter reads neighbours: whole frames only).  The framebuffer,
+ *     the moments, the features and what vr_draw / vr_display / vr_save_png show are left as they were.
+ *     vr_denoised waits and writes W*H*4 floats, linear (not tonemapped), row 0 at the bottom; VR_ERR before the first vr_denoise since the last
+ *     resize. */
+int vr_denoise(vr_renderer* r);
+int vr_denoised(vr_renderer* r, float* rgba_out);
 int vr_draw(vr_renderer* r);
 int vr_display(vr_renderer* r, float* rgba_out);
 int vr_save_png(vr_renderer* r, const char* path);

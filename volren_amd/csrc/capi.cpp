@@ -1,6 +1,7 @@
 // capi.cpp -- extern "C" surface of libvolren_amd.so (include/volren_amd.h) over the C++ classes.
 #include "../../include/volren_amd.h"
 
+#include <cmath>
 #include <cstring>
 #include <filesystem>
 #include <functional>
@@ -286,6 +287,10 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
         else if (n == "integrator") R.integrator = v;
         else if (n == "fast_math") R.fast_math = v != 0;
         else if (n == "variance") { if (v < 0 || v > 1) throw std::runtime_error("variance: 0 (off) or 1 (keep the per-pixel second moments)"); R.variance = v; }
+        else if (n == "denoise_iterations") {
+            if (v < 0 || v > vr::kDenoiseMaxIterations) throw std::runtime_error("denoise_iterations must be in [0, 10]");
+            R.denoise_iterations = v;
+        }
         else if (n == "coalesce_trace") { R.flush_pending(); R.coalesce_trace = v != 0; }
         else if (n == "majorant_layout") { if (v < -1 || v > 1) throw std::runtime_error("majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)"); R.majorant_layout = v; }
         else if (n == "tf_float_atlas") R.tf_float_atlas = v != 0;
@@ -315,6 +320,7 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
         else if (n == "integrator") *v = R.integrator;
         else if (n == "fast_math") *v = R.fast_math ? 1 : 0;
         else if (n == "variance") *v = R.variance;
+        else if (n == "denoise_iterations") *v = R.denoise_iterations;
         else if (n == "coalesce_trace") *v = R.coalesce_trace ? 1 : 0;
         else if (n == "majorant_layout") *v = R.majorant_layout;
         else if (n == "majorant_blocked") {          // what the current frame's next launch will use
@@ -362,6 +368,7 @@ FloatField float_field(vr::RendererHIP& R, const std::string& n) {
     if (n == "tf_window_left") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_left, 1 }; }
     if (n == "tf_window_width") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_width, 1 }; }
     if (n == "volume_transform") { if (!R.volume) throw std::runtime_error("no volume"); return { R.volume->transform.m, 16 }; }
+    if (n == "denoise_sigma") return { R.denoise_sigma, 5 };
     throw std::runtime_error("unknown float parameter: " + n);
 }
 }  // namespace
@@ -379,6 +386,11 @@ int vr_set_float(vr_renderer* r, const char* name, const float* values, int coun
             return;
         }
         if (n == "albedo" && count == 1) { R.albedo = vr::vec3(values[0]); return; }      // main.cpp:371-372
+        if (n == "denoise_sigma") {                 // colour, normal, depth, coverage, albedo: each finite and > 0
+            if (count != 5) throw std::runtime_error("denoise_sigma takes 5 values (colour, normal, depth, coverage, albedo)");
+            for (int i = 0; i < 5; ++i)
+                if (!(std::isfinite(values[i]) && values[i] > 0.0f)) throw std::runtime_error("denoise_sigma: every value must be finite and > 0");
+        }
         const FloatField f = float_field(R, n);
         if (count != f.count) throw std::runtime_error("wrong value count for " + n);
         memcpy(f.ptr, values, sizeof(float) * (size_t)count);
@@ -448,6 +460,17 @@ int vr_variance(vr_renderer* r, float* out) {
     if (!out) return fail(VR_ERR_ARG, "null argument");
     if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
     return guard([&] { use_device(r); r->impl.download_variance(out); });
+}
+int vr_denoise(vr_renderer* r) {
+    NEED(r);
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.denoise(); });
+}
+int vr_denoised(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.download_denoised(out); });
 }
 int vr_framebuffer_device(vr_renderer* r, void** p) {
     NEED(r);

@@ -6,11 +6,14 @@
 // Not provided: the interactive window/GUI, Python scripts (.py arguments: `python -m volren_amd.run_script` runs them) and the tinycolormap presets.
 // Addition: --gpus N [--devices a,b,...] renders every frame on N devices (sharded.h: scene replicated, 16x16 tiles dealt diagonally, one
 // grouped ncclAllGather per frame; a device named more than once = logical shards of one GPU, exchanged by device-to-device copies).
+// Addition: --denoise keeps the per-pixel variance, runs the feature pass (min(spp, 16) samples) and the a-trous denoiser (vr_denoise.h) after every
+// frame and writes the tonemapped denoised frame instead of the raw one (one device only).
 //
 //   volren data/smoke.brick data/table_mountain_2_puresky_1k.hdr -w 1024 -h 1024 --render --spp 4096 --bounces 128 \
 //          --albedo 0.8 --phase 0.3 --density 100 --env_strength 3 --env_rot 270 --exposure 3 --gamma 2.0 --cam_fov 40
 #include <sys/wait.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstdio>
@@ -80,7 +83,7 @@ static void parse_cmd(int argc, char** argv) {
     Args a{ argc, argv, 0 };
     for (a.i = 1; a.i < argc; ++a.i) {
         const std::string arg = argv[a.i];
-        if (arg == "--render") {
+        if (arg == "--render" || arg == "--denoise") {          // --denoise: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
@@ -157,6 +160,7 @@ int main(int argc, char** argv) {
         if (arg.size() > 3 && arg.compare(arg.size() - 3, 3, ".py") == 0 && fs::is_regular_file(arg)) return run_python_script(argc, argv);
     }
     int width = 1280, height = 720, device = 0, gpus = 0;        // cppgl ContextParameters defaults (unverified): always pass -w/-h
+    bool denoise = false;
     std::vector<int> devices;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -166,7 +170,10 @@ int main(int argc, char** argv) {
             else if (arg == "--device" && i + 1 < argc) device = std::stoi(argv[++i]);
             else if (arg == "--gpus" && i + 1 < argc) gpus = std::stoi(argv[++i]);
             else if (arg == "--devices" && i + 1 < argc) devices = parse_int_list(argv[++i]);
+            else if (arg == "--denoise") denoise = true;
         }
+        if (denoise && (gpus > 0 || devices.size() > 1))
+            throw std::runtime_error("--denoise renders on one device only: drop --gpus / --devices (the sharded renderer has no denoiser)");
         // one renderer per part; without --gpus / --devices: one part on --device, the reference's single-context loop
         if (devices.empty()) {
             if (gpus <= 1) devices = { device };
@@ -191,6 +198,7 @@ int main(int argc, char** argv) {
                 renderer->commit();
             }
             renderer->reset();
+            if (denoise) renderer->variance = 1;        // the denoiser's variance input: kept from sample 1 of every frame
             parts.push_back(renderer);
         }
         renderer = parts[0];                            // holds the whole frame after the gather
@@ -220,7 +228,15 @@ int main(int argc, char** argv) {
                       << (double)width * height * renderer->sppx / sec / 1e6 << " Msamples/s)" << std::endl;
             VR_HIP(hipSetDevice(devices[0]));
             renderer->tonemapping = true;               // the offline loop always tonemaps (main.cpp:540-550)
-            renderer->draw();
+            if (denoise) {
+                renderer->render_features(std::min(renderer->sppx, 16));
+                renderer->denoise();
+                renderer->synchronize();
+                if (renderer->watchdog_status()) throw std::runtime_error("feature pass: a camera segment exceeded its step budget");
+                renderer->draw_from(*renderer->denoised());
+            } else {
+                renderer->draw();
+            }
             std::vector<float> fb((size_t)width * height * 4);
             renderer->download_display(fb.data());
             std::vector<uint8_t> rgba;

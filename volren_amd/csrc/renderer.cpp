@@ -57,6 +57,7 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     display.reset();
     features_.reset();
     moments_.reset(); moments_n_ = -1;
+    dn_guide_.reset(); dn_var_[0].reset(); dn_var_[1].reset(); dn_color_[0].reset(); dn_color_[1].reset(); denoised_.reset();
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
 }
@@ -743,8 +744,12 @@ void RendererHIP::render(int n) {
 void RendererHIP::draw() {
     flush_pending();
     if (!color) return;
-    if (!display || display->size_bytes() != color->size_bytes()) display = make_device_buffer(color->size_bytes());
-    VR_HIP(hipMemcpyAsync(display->get(), color->get(), color->size_bytes(), hipMemcpyDeviceToDevice, stream));
+    draw_from(*color);
+}
+
+void RendererHIP::draw_from(const DeviceBuffer& src) {
+    if (!display || display->size_bytes() != src.size_bytes()) display = make_device_buffer(src.size_bytes());
+    VR_HIP(hipMemcpyAsync(display->get(), src.get(), src.size_bytes(), hipMemcpyDeviceToDevice, stream));
     if (tonemapping) {
         launch_tonemap(display->as<float>(), resolution.x, resolution.y, tonemap_exposure, tonemap_gamma, stream);
         VR_HIP(hipGetLastError());
@@ -837,15 +842,61 @@ void RendererHIP::download_features(float* out) {
     features_->download(out, features_->size_bytes(), stream);
 }
 
+void RendererHIP::check_moments(const char* who) {
+    if (sample < 1 || !moments_ || moments_n_ != sample)
+        throw std::runtime_error(std::string(who) + ": the moments do not cover samples 1.." + std::to_string(sample) +
+                                 " (variance was off for some of them, e.g. switched on mid-frame): reset() and render with variance = 1");
+}
+
 void RendererHIP::download_variance(float* rgba) {
     flush_pending();
-    if (sample < 1 || !moments_ || moments_n_ != sample)
-        throw std::runtime_error("variance: the moments do not cover samples 1.." + std::to_string(sample) +
-                                 " (variance was off for some of them, e.g. switched on mid-frame): reset() and render with variance = 1");
+    check_moments("variance");
     moments_->download(rgba, moments_->size_bytes(), stream);
     const size_t n = (size_t)resolution.x * resolution.y * 4;
     const float f = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;
     for (size_t i = 0; i < n; ++i) rgba[i] = sample >= 2 ? rgba[i] * f : 0.0f;
+}
+
+// The a-trous denoiser (vr_denoise.h) on whole frames: prepare (variance of the mean, guide) once, then `denoise_iterations` passes at steps
+// 1, 2, 4, ...  Iteration 0 reads the framebuffer itself; colour and variance ping-pong between buffers of their own, and the last iteration
+// writes `denoised_` (N = 0: a copy of the framebuffer).
+void RendererHIP::denoise() {
+    flush_pending();
+    if (!tiles_host_.empty()) throw std::runtime_error("denoise: a tile subset is set (set_tiles); the filter needs every pixel's neighbours and runs on whole frames only");
+    if (!features_) throw std::runtime_error("denoise: no feature pass since the last resize (call render_features first)");
+    if (sample < 1) throw std::runtime_error("denoise: the framebuffer holds no samples (sample < 1)");
+    check_moments("denoise");
+    const int32_t W = resolution.x, H = resolution.y, N = denoise_iterations;
+    if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error("denoise: frame too large (32-bit pixel indices)");
+    if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error("denoise: denoise_iterations out of range");
+    const size_t px = (size_t)W * H;
+    auto ensure = [&](DeviceBufferPtr& b, size_t bytes) { if (!b || b->size_bytes() != bytes) b = make_device_buffer(bytes); };
+    ensure(dn_guide_, px * 8 * sizeof(float));
+    ensure(dn_var_[0], px * sizeof(float));
+    ensure(denoised_, px * 4 * sizeof(float));
+    if (N >= 2) { ensure(dn_var_[1], px * sizeof(float)); ensure(dn_color_[0], px * 4 * sizeof(float)); }
+    if (N >= 3) ensure(dn_color_[1], px * 4 * sizeof(float));
+    const float vscale = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;      // download_variance's factor
+    launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
+    VR_HIP(hipGetLastError());
+    if (N == 0) {
+        VR_HIP(hipMemcpyAsync(denoised_->get(), color->get(), color->size_bytes(), hipMemcpyDeviceToDevice, stream));
+        return;
+    }
+    const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
+    for (int32_t k = 0; k < N; ++k) {
+        const float* cin = k == 0 ? color->as<float>() : dn_color_[(k - 1) & 1]->as<float>();
+        float* cout = k == N - 1 ? denoised_->as<float>() : dn_color_[k & 1]->as<float>();
+        float* vout = k == N - 1 ? nullptr : dn_var_[(k + 1) & 1]->as<float>();
+        launch_denoise_atrous(cin, dn_var_[k & 1]->as<float>(), dn_guide_->as<float>(), W, H, 1 << k, sg, cout, vout, stream);
+        VR_HIP(hipGetLastError());
+    }
+}
+
+void RendererHIP::download_denoised(float* rgba) {
+    if (!denoised_) throw std::runtime_error("denoised: no denoise since the last resize (call denoise first)");
+    flush_pending();
+    denoised_->download(rgba, denoised_->size_bytes(), stream);
 }
 
 uint32_t RendererHIP::watchdog_status() {

@@ -132,6 +132,9 @@ struct RendererHIP {
                                                       // BASELINE configs[4], +3 % there, -2 % on small or thinly filled ones: profiles/r4d_*, r5_*), 0 = linear, 1 = blocked.
                                                       // Results never depend on it
     int variance = 0;                                 // 1: every accumulation pass also keeps the per-channel second moments of the samples (download_variance)
+    int denoise_iterations = kDenoiseDefaultIterations;   // a-trous iterations of denoise() (0..kDenoiseMaxIterations; 0 = the colour unchanged)
+    float denoise_sigma[5] = { kDenoiseDefaultSigma[0], kDenoiseDefaultSigma[1], kDenoiseDefaultSigma[2], kDenoiseDefaultSigma[3], kDenoiseDefaultSigma[4] };
+                                                      // edge-stopping widths: colour, normal, depth, coverage, albedo (vr_denoise.h)
     bool fast_math = false;                           // opt-in tolerance mode: hardware log/sin/cos/rcp instead of the specified arithmetic
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
                                                       // with one bound the renderer refuses it: DESIGN.md 3)
@@ -154,6 +157,14 @@ struct RendererHIP {
     void render_features(int spp);
     void download_features(float* out);
     void download_variance(float* rgba);
+    // Denoiser (vr_denoise.h).  denoise(): the a-trous filter of the current frame, guided by the variance and the last feature pass, into its own W*H*4
+    // buffer (asynchronous; flushes recorded samples first).  Needs render_features since the last resize, `variance` on for samples 1..sample, sample >= 1
+    // and no tile subset.  download_denoised: that buffer, W*H*4 floats.  The framebuffer, moments, features and display are not touched.
+    void denoise();
+    void download_denoised(float* rgba);
+    const DeviceBuffer* denoised() const { return denoised_.get(); }
+    // copy + tonemap of a W*H*4 buffer into `display` (draw() = draw_from(*color) after the flush)
+    void draw_from(const DeviceBuffer& src);
     void download_display(float* rgba) const;
     void synchronize();
     // Launches the samples that coalesced trace() calls have recorded (no-op without any).  Every member function that reads or replaces the
@@ -211,6 +222,9 @@ private:
     DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
     DeviceBufferPtr moments_;                          // W*H*4 second moments, allocated by the first launch with `variance` on
     int moments_n_ = -1;                               // the moments cover samples 1..moments_n_ (-1: they do not start at sample 1)
+    void check_moments(const char* who);               // throws unless the moments cover samples 1..sample
+    DeviceBufferPtr dn_guide_, dn_var_[2], dn_color_[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4 (dropped by resize)
+    DeviceBufferPtr denoised_;                         // W*H*4: the last denoise()'s result (dropped by resize)
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     std::vector<hipEvent_t> pt_events_;                // (begin, end) around the path-tracing kernel of every sub-launch
     size_t pt_events_used_ = 0;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vr_denoise.h"
 #include "vr_scene.h"
 
 namespace vr {
@@ -35,6 +36,13 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
 // status: the renderer's status word; a pixel whose tracker exceeded its step budget sets kFeatureLostStatus there (its remaining samples are not run).
 constexpr uint32_t kFeatureLostStatus = 4u;
 void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream);
+// Denoiser (vr_denoise.h), whole W x H frames.  prepare: moments = W*H*4 Welford second moments S of n samples (the variance is S * vscale, 0 for
+// n = 1: vr_variance's arithmetic), features = W*H*8 (vr_render_features) -> v = W*H variances of the mean's luminance, guide = W*H*8.
+// atrous: one iteration of step `step` from (cin W*H*4, vin W*H, guide) into cout (W*H*4) and vout (W*H; nullptr: not written); the
+// inputs and outputs must not overlap.
+void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, float* v, float* guide, hipStream_t stream);
+void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
+                           float* cout, float* vout, hipStream_t stream);
 // which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
 // what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
 enum PathtraceVariantReason : int {

@@ -11,7 +11,7 @@
 //
 // Also here: the environment importance pyramid + warp table (env_setup.glsl, environment.cpp), the dense->brick encoder
 // (voldata to_brick_grid at commit()), majorant remap, tonemap.glsl, direct volume rendering (common.glsl:571-591),
-// tile pack/unpack for the multi-GPU gather, the denoiser feature pass and a math probe for the tests.
+// tile pack/unpack for the multi-GPU gather, the denoiser feature pass, the a-trous denoiser and a math probe for the tests.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "vr_denoise.h"
 #include "vr_device.h"
 #include "vr_pathtrace.h"
 
@@ -141,6 +142,72 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
     if (n_tiles <= 0 || spp <= 0) return;
     if (P.u.use_tf) hipLaunchKernelGGL(features_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
     else hipLaunchKernelGGL(features_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
+}
+
+// Denoiser (vr_denoise.h): one thread per pixel, laid out like accumulate_kernel (16x16 tiles of four 8x8 wavefronts) for 2-D locality of
+// the 5x5 footprint.  No LDS: from step 4 on the footprint leaves the tile, and the working set fits the Infinity Cache.  Per tap: the
+// colour (one dwordx4), the variance (one dword) and the guide (two dwordx4).
+struct DenoiseSrcDev {
+    const float4* __restrict__ c;
+    const float* __restrict__ v;
+    const float4* __restrict__ g;
+    __device__ __forceinline__ void color(int32_t i, float o[4]) const { const float4 x = c[i]; o[0] = x.x; o[1] = x.y; o[2] = x.z; o[3] = x.w; }
+    __device__ __forceinline__ float var(int32_t i) const { return v[i]; }
+    __device__ __forceinline__ void guide(int32_t i, float o[8]) const {
+        const float4 a = g[2 * i], b = g[2 * i + 1];
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    }
+};
+// prepare: moments S (W*H*4, Welford's M2 / n) -> the unbiased variance var = S * vscale exactly as vr_variance forms it (0 for n = 1), then
+// the variance of the mean's luminance v (W*H) and the guide (W*H*8) from the features
+__global__ void __launch_bounds__(256)
+denoise_prepare_kernel(const float4* __restrict__ moments, const float4* __restrict__ features, int32_t W, int32_t H, int32_t n, float vscale,
+                       float* __restrict__ v, float4* __restrict__ guide) {
+    const int32_t tiles_x = (W + 15) >> 4;
+    const int32_t tile = (int32_t)blockIdx.x;
+    const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
+    const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
+    const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
+    if (px >= W || py >= H) return;
+    const int32_t i = py * W + px;
+    const float4 m = moments[i];
+    const float var[4] = { n >= 2 ? m.x * vscale : 0.0f, n >= 2 ? m.y * vscale : 0.0f, n >= 2 ? m.z * vscale : 0.0f, n >= 2 ? m.w * vscale : 0.0f };
+    const float4 fa = features[2 * i], fb = features[2 * i + 1];
+    const float f[8] = { fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w };
+    float g[8];
+    denoise_guide(f, g);
+    v[i] = denoise_mean_variance(var, n);
+    guide[2 * i] = make_float4(g[0], g[1], g[2], g[3]);
+    guide[2 * i + 1] = make_float4(g[4], g[5], g[6], g[7]);
+}
+// one a-trous iteration; vout == nullptr: the variance is not written (the last iteration)
+__global__ void __launch_bounds__(256)
+denoise_atrous_kernel(const float4* __restrict__ cin, const float* __restrict__ vin, const float4* __restrict__ guide, int32_t W, int32_t H,
+                      int32_t step, const DenoiseSigma sg, float4* __restrict__ cout, float* __restrict__ vout) {
+    const int32_t tiles_x = (W + 15) >> 4;
+    const int32_t tile = (int32_t)blockIdx.x;
+    const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
+    const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
+    const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
+    if (px >= W || py >= H) return;
+    const DenoiseSrcDev src{ cin, vin, guide };
+    float o[4], ov;
+    denoise_atrous_pixel(src, W, H, px, py, step, sg, o, ov);
+    const int32_t i = py * W + px;
+    cout[i] = make_float4(o[0], o[1], o[2], o[3]);
+    if (vout) vout[i] = ov;
+}
+static unsigned denoise_blocks(int32_t W, int32_t H) { return (unsigned)(((W + 15) / 16) * ((H + 15) / 16)); }
+void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, float* v, float* guide, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(denoise_prepare_kernel, dim3(denoise_blocks(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(moments),
+                       reinterpret_cast<const float4*>(features), W, H, n, vscale, v, reinterpret_cast<float4*>(guide));
+}
+void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
+                           float* cout, float* vout, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(denoise_atrous_kernel, dim3(denoise_blocks(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(cin), vin,
+                       reinterpret_cast<const float4*>(guide), W, H, step, sg, reinterpret_cast<float4*>(cout), vout);
 }
 
 // Units of 8 samples x 64 pixels, except on the dense-grid kernel, whose long paths (128 bounces, every camera ray scatters) fill

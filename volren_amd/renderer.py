@@ -8,11 +8,11 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance")
+               "variance", "denoise_iterations")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
-                 "volume_transform": 16}
+                 "volume_transform": 16, "denoise_sigma": 5}
 
 
 def _f32(a):
@@ -244,6 +244,20 @@ class Renderer:
         """[H][W][4] float32, row 0 = bottom: unbiased per-channel variance of samples 1..sample (needs `variance = 1` for all of them)."""
         out = np.empty((self.height, self.width, 4), np.float32)
         _lib.check(self._L.vr_variance(self._h, out.ctypes.data))
+        return out
+
+    # ---- denoiser ----
+    def denoise(self, sync=True):
+        """The a-trous filter of the current frame (include/volren_amd.h vr_denoise): needs `variance = 1` for all its samples and a render_features
+        since the last resize; `denoise_iterations` / `denoise_sigma` set it up."""
+        _lib.check(self._L.vr_denoise(self._h))
+        if sync:
+            self.synchronize()
+
+    def denoised(self):
+        """[H][W][4] float32, row 0 = bottom: the last denoise()'s result, linear (not tonemapped)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _lib.check(self._L.vr_denoised(self._h, out.ctypes.data))
         return out
 
     def framebuffer_device_ptr(self):

@@ -544,6 +544,15 @@ class Renderer:
         """(w, h, 3) float: per-channel variance of the colour samples behind fbo_data() (set `variance = 1` before rendering)."""
         return self._r.variance()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
 
+    # -- denoiser (no reference counterpart): render with `variance = 1`, render_features, then denoise()
+    def denoise(self):
+        """The a-trous filter of the current frame, guided by its variance and the last render_features (volren_amd.Renderer.denoise)."""
+        self._r.denoise()
+
+    def denoised_data(self):
+        """(w, h, 3) float: the denoised colour, in fbo_data()'s shape."""
+        return self._r.denoised()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
+
     def _write(self, filename, channels):
         from PIL import Image
         self._r.draw()
