@@ -102,8 +102,8 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     renderer's parts; default), 2 = always.  Results never depend on the order) (int);  "tonemap_exposure" "tonemap_gamma" "albedo"(3) "phase" "density_scale"
  *     "emission_scale" "vol_clip_min"(3) "vol_clip_max"(3) "env_strength" "env_transform"(9) "env_rot"(1, degrees about +y,
  *     main.cpp:382) "tf_window_left" "tf_window_width" "cam_pos"(3) "cam_dir"(3) "cam_up"(3) "cam_fov" "volume_transform"(16)
- *     "denoise_sigma"(5: the edge-stopping widths of vr_denoise for colour, normal, depth, coverage, albedo; each finite and > 0; default
- *     4, 0.5, 0.1, 0.25, 0.2) (float) */
+ *     "denoise_sigma"(5: the edge-stopping widths of vr_denoise for colour, normal, depth, coverage, albedo; each in [2^-60, 2^60], about
+ *     [8.7e-19, 1.15e18]: VR_ERR otherwise, the old values kept; default 4, 0.5, 0.1, 0.25, 0.2) (float) */
 /* read-only through vr_get_int: "kernel_variant" (the compiled path-tracing kernel the next launch uses: 0 brick grid, 1 dense fp16 grid, 2 / 4 brick grid +
  *     emission grid, 3 everything decided at run time -- correct for every scene, up to an order of magnitude slower) and "kernel_variant_reason" (what sent the
  *     scene to variant 3, a mask: 1 integrator != 0, 2 the environment's warp table has thresholds below 2^-76 ("env_div_safe" = 0), 4 density scale outside

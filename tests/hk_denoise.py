@@ -34,6 +34,13 @@ def lib():
     return _lib
 
 
+def sigma_range():
+    """(smallest, largest) value of each sigma that vr_set_float "denoise_sigma" accepts (vr_denoise.h kDenoiseSigmaMin / Max)"""
+    r = np.zeros(2, np.float32)
+    lib().hk_denoise_sigma_range(_p(r))
+    return float(r[0]), float(r[1])
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -132,7 +139,7 @@ def spec_atrous(color, v, guide, step, sigma=DEFAULT_SIGMA):
                 wt = wt * np.exp(-np.abs(L - Lq) / dc) * np.exp(-np.abs(kp - gq[..., 3]) / sk)
                 both = (kp > 0) & (gq[..., 3] > 0)
                 nq = gq[..., 4:7]
-                d = np.maximum(0.0, (gp * nq).sum(axis=-1))
+                d = np.minimum(1.0, np.maximum(0.0, (gp * nq).sum(axis=-1)))
                 wn = np.where(gp0 | (nq == 0).all(axis=-1), 1.0, np.where(d > 0, d, 0.0) ** sn)
                 wd = np.exp(-np.abs(dp - gq[..., 7]) / (sd * np.maximum(dp, gq[..., 7]) + 1e-6))
                 da = ap - gq[..., 0:3]

@@ -43,6 +43,9 @@ void hk_denoise_atrous(int W, int H, int step, const float* c, const float* v, c
         }
 }
 
+// the accepted range of every sigma: out[0] = smallest, out[1] = largest
+void hk_denoise_sigma_range(float* out) { out[0] = kDenoiseSigmaMin; out[1] = kDenoiseSigmaMax; }
+
 // the whole filter as RendererHIP::denoise runs it: prepare, then N iterations at steps 1, 2, 4, ... (N = 0: the colour copied)
 void hk_denoise(int W, int H, int n, const float* color, const float* var, const float* feat, int N, const float* sigma, float* out) {
     const size_t px = (size_t)W * H;

@@ -62,3 +62,15 @@ def test_denoise_settings_range_checks():
     v = np.ones(4, np.float32)
     assert lib.vr_set_float(r._h, b"denoise_sigma", v.ctypes.data_as(C.POINTER(C.c_float)), 4) == 1
     assert np.array_equal(r.denoise_sigma, np.arange(1, 6, dtype=np.float32))       # refused values leave the old ones
+    # [2^-60, 2^60]: sigma_a^2 stays a normal float (sigma_a = 1e-23 gave 0 / 0 = NaN for equal albedos); the ends themselves are accepted
+    lo, hi = np.float32(2.0 ** -60), np.float32(2.0 ** 60)
+    for i in range(5):
+        for bad in (np.nextafter(lo, np.float32(0)), np.float32(1e-23), np.float32(2.0 ** -100), np.nextafter(hi, np.float32(np.inf)), np.float32(1e30)):
+            v = np.arange(1, 6, dtype=np.float32)
+            v[i] = bad
+            assert lib.vr_set_float(r._h, b"denoise_sigma", v.ctypes.data_as(C.POINTER(C.c_float)), 5) == 1, (i, bad)
+            assert b"2^-60" in lib.vr_last_error()
+            assert np.array_equal(r.denoise_sigma, np.arange(1, 6, dtype=np.float32))
+    for v in ((lo,) * 5, (hi,) * 5, (lo, hi, lo, hi, lo)):
+        r.denoise_sigma = v
+        assert np.array_equal(r.denoise_sigma, np.asarray(v, np.float32))

@@ -180,3 +180,94 @@ def test_cli_render_denoise_writes_the_tonemapped_denoised_frame(tmp_path):
     assert (tmp_path / "raw_000000.png").read_bytes() != (tmp_path / "dn_000000.png").read_bytes()
     bad = subprocess.run([exe, scenes.SMOKE, scenes.HDR, "--gpus", "2"] + args + ["--denoise"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "--denoise" in bad.stderr
+
+
+# ---- shapes, HDR input, the limits of denoise_sigma, flush points -----------------------------------------------------------------------------------
+def _same_denoised(r, what, iterations=None, sigma=None):
+    if iterations is not None:
+        r.denoise_iterations = iterations
+    if sigma is not None:
+        r.denoise_sigma = sigma
+    r.denoise()
+    got = r.denoised()
+    ref = _host(r)
+    bad = (_bits(got) != _bits(ref)).any(axis=2)
+    assert not bad.any(), (what, int(bad.sum()))
+    assert np.isfinite(got).all(), what
+    return got
+
+
+def _nontrivial(r):
+    assert (r.features()[..., 3] > 0).any() and (r.variance()[..., :3] > 0).any()
+
+
+@pytest.mark.parametrize("w,h", ((1, 1), (1, 37), (37, 1), (15, 9), (16, 16), (17, 16), (33, 31)))
+def test_denoised_on_small_and_thin_frames(w, h):
+    """frames one pixel wide or tall, narrower than a tile, one tile, one tile and a column, two tiles and a ragged row and column"""
+    r = _ready("c1", w, h, 6)
+    _nontrivial(r)
+    for it in (0, 1, 5):
+        got = _same_denoised(r, (w, h, it), it)
+        if it == 0:
+            assert np.array_equal(_bits(got), _bits(r.framebuffer()))
+        elif w * h > 1:
+            assert not np.array_equal(_bits(got), _bits(r.framebuffer()))
+
+
+@pytest.mark.parametrize("w,h,it", ((1030, 770, 10), (1920, 1080, 5)))
+def test_denoised_on_large_frames(w, h, it):
+    """1030 x 770 at N = 10: the step-512 taps of the last iteration land inside the frame; 1920 x 1080 at N = 5"""
+    r = _ready("c1", w, h, 2, 1)
+    _nontrivial(r)
+    got = _same_denoised(r, (w, h, it), it)
+    assert not np.array_equal(_bits(got), _bits(r.framebuffer()))
+
+
+def test_denoised_on_hdr_input():
+    """c1 under an environment 1e4 times as strong, 2 spp"""
+    r = scenes.hip_scene("c1", 48, 32)
+    r.env_strength = 1e4
+    r.variance = 1
+    r.render(2)
+    r.render_features(2)
+    _nontrivial(r)
+    assert r.framebuffer()[..., :3].max() > 1e3 and r.variance()[..., :3].max() > 1e6
+    got = _same_denoised(r, "hdr")
+    assert not np.array_equal(_bits(got), _bits(r.framebuffer()))
+
+
+def test_denoised_at_the_limits_of_each_sigma():
+    """Each sigma alone at the smallest and the largest value the API accepts (2^-60 and 2^60: sigma_a^2 down to 2^-120, where a device that
+    flushed subnormals would still agree): finite, and the device equal to the host"""
+    lo, hi = hk_denoise.sigma_range()
+    r = _ready("c1", 64, 48, 8)
+    _nontrivial(r)
+    for i in range(5):
+        for v in (lo, hi):
+            sg = list(hk_denoise.DEFAULT_SIGMA)
+            sg[i] = v
+            _same_denoised(r, ("sigma", i, v), 5, tuple(sg))
+
+
+def test_every_flush_point_sees_the_pending_samples():
+    """trace() x n, then variance(), features(), render_features() or denoise(): each gives what it gives after render(n)"""
+    n = 5
+    ref = _ready("c1", 40, 32, n)
+    ref.denoise()
+    want_fb, want_var, want_feat, want_den = ref.framebuffer(), ref.variance(), ref.features(), ref.denoised()
+    r = _ready("c1", 40, 32, 1, n)
+    for step in ("variance", "features", "render_features", "denoise"):
+        r.reset()
+        for _ in range(n):
+            r.trace()
+        if step == "variance":
+            assert np.array_equal(_bits(r.variance()), _bits(want_var))
+        elif step == "features":
+            assert np.array_equal(_bits(r.features()), _bits(want_feat))
+        elif step == "render_features":
+            r.render_features(n)
+            assert np.array_equal(_bits(r.features()), _bits(want_feat))
+        else:
+            r.denoise()
+            assert np.array_equal(_bits(r.denoised()), _bits(want_den))
+        assert r.sample == n and np.array_equal(_bits(r.framebuffer()), _bits(want_fb)), step

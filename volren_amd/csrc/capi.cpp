@@ -386,10 +386,11 @@ int vr_set_float(vr_renderer* r, const char* name, const float* values, int coun
             return;
         }
         if (n == "albedo" && count == 1) { R.albedo = vr::vec3(values[0]); return; }      // main.cpp:371-372
-        if (n == "denoise_sigma") {                 // colour, normal, depth, coverage, albedo: each finite and > 0
+        if (n == "denoise_sigma") {                 // colour, normal, depth, coverage, albedo: each in [2^-60, 2^60] (vr_denoise.h)
             if (count != 5) throw std::runtime_error("denoise_sigma takes 5 values (colour, normal, depth, coverage, albedo)");
             for (int i = 0; i < 5; ++i)
-                if (!(std::isfinite(values[i]) && values[i] > 0.0f)) throw std::runtime_error("denoise_sigma: every value must be finite and > 0");
+                if (!(values[i] >= vr::kDenoiseSigmaMin && values[i] <= vr::kDenoiseSigmaMax))
+                    throw std::runtime_error("denoise_sigma: every value must be in [2^-60, 2^60]");
         }
         const FloatField f = float_field(R, n);
         if (count != f.count) throw std::runtime_error("wrong value count for " + n);

@@ -17,13 +17,16 @@
 //     w_c = exp(-|L_p - L_q| / (sigma_c sqrt(vbar_p) + 1e-6))                      L = luma of the current colour
 //     w_k = exp(-|k_p - k_q| / sigma_k)                                             k = coverage
 //     and, only where k_p > 0 and k_q > 0 (1 otherwise):
-//     w_n = pow(max(0, dot(g_p, g_q)), sigma_n)   (1 when either g is 0; exactly 0 for dot <= 0)
+//     w_n = pow(min(1, max(0, dot(g_p, g_q))), sigma_n)   (1 when either g is 0; exactly 0 for dot <= 0; the float32 dot of two unit
+//                                                  vectors can be 1 + 2^-22, and without the clamp w_n > 1 overflows for large sigma_n)
 //     w_d = exp(-|d_p - d_q| / (sigma_d max(d_p, d_q) + 1e-6))                     relative depth difference
 //     w_a = exp(-|a_p - a_q|^2 / sigma_a^2)
 //   The centre tap's edge-stopping factors are 1 by definition: its weight is exactly (3/8)^2 > 0.
 //   c'_p = sum w c_q / sum w (all four channels, the same weights), v'_p = sum w^2 v_q / (sum w)^2.
 // N = 0 returns the colour bit for bit.  No albedo demodulation, no temporal accumulation.
 //
+// Every sigma lies in [2^-60, 2^60] (vr_set_float "denoise_sigma" refuses the rest): sigma_a^2 stays a normal float, so two equal albedos give
+// 0 / sigma_a^2 = 0 and not 0 / 0, and a device that flushes subnormals computes what the host does.
 // Defaults: N = 5, (sigma_c, sigma_n, sigma_d, sigma_k, sigma_a) = (4, 0.5, 0.1, 0.25, 0.2), chosen from a sweep of 80 settings (DESIGN.md 5
 // "Denoiser": relative L2 to a 1024-spp frame on c2 / c3 / c4 at 256^2, 16 and 64 spp).  The averaged first-scatter normals of a volume are
 // noisy, so a sharp normal weight (sigma_n = 16, the starting point) stops the filter on c2 / c3: 0.66 / 0.65 of the raw error at 16 spp,
@@ -38,6 +41,7 @@ struct DenoiseSigma { float c, n, d, k, a; };          // colour, normal, depth,
 constexpr int32_t kDenoiseDefaultIterations = 5;
 constexpr int32_t kDenoiseMaxIterations = 10;
 constexpr float kDenoiseDefaultSigma[5] = { 4.0f, 0.5f, 0.1f, 0.25f, 0.2f };
+constexpr float kDenoiseSigmaMin = 0x1p-60f, kDenoiseSigmaMax = 0x1p60f;      // the accepted range of every sigma
 
 // variance of the mean's luminance from the unbiased per-channel variance of n >= 1 samples
 VR_HD float denoise_mean_variance(const float var[4], int32_t n) {
@@ -106,7 +110,7 @@ VR_HD void denoise_atrous_pixel(const Src& src, int32_t W, int32_t H, int32_t px
                 if (gp[3] > 0.0f && gq[3] > 0.0f) {
                     const v3 nq = v3{ gq[4], gq[5], gq[6] }, da = ap - v3{ gq[0], gq[1], gq[2] };
                     const bool nq0 = nq.x == 0.0f && nq.y == 0.0f && nq.z == 0.0f;
-                    const float wn = (np0 || nq0) ? 1.0f : pow_(max_(0.0f, dot(np, nq)), sg.n);
+                    const float wn = (np0 || nq0) ? 1.0f : pow_(min_(1.0f, max_(0.0f, dot(np, nq))), sg.n);
                     const float wd = exp_(-abs_(gp[7] - gq[7]) / (sg.d * max_(gp[7], gq[7]) + 1e-6f));
                     const float wa = exp_(-dot(da, da) / sa2);
                     w = w * wn;
