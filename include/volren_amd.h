@@ -176,6 +176,37 @@ int vr_variance(vr_renderer* r, float* rgba_out);
  *     resize. */
 int vr_denoise(vr_renderer* r);
 int vr_denoised(vr_renderer* r, float* rgba_out);
+/* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
+ *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
+ *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the
+ *     tile's pixels inside the frame (NaN if any e_p is).  The arithmetic is specified in volren_amd/csrc/vr_adaptive.h and reproducible bit for bit.
+ *     vr_render_adaptive: the tiles of the tile set (vr_set_tiles; none = every tile) below min_spp are brought to min_spp; then, while some
+ *     tile of the set has fewer than max_spp samples, one round evaluates e_t of those tiles, retires the ones with e_t < threshold (strict: a
+ *     threshold of 0 never retires a tile) and takes each other tile from n_t to min(2 n_t, max_spp) samples.  It starts from the uniform frame
+ *     of "sample" samples or from the counts a previous call left, keeps the per-pixel moments for all its launches whatever "variance" says
+ *     (the setting is left as it was) and ends with "sample" = the largest count of any tile.  A tile brought to k samples is bit for bit the
+ *     tile of a k-spp vr_render, moments included.  Asynchronous like vr_render, except that each round waits for its error values (one small
+ *     copy) and reports a tripped watchdog as vr_synchronize would; vr_get_int "adaptive_rounds" counts the rounds of the last call.
+ *     VR_ERR when "sample" > 0 and the moments do not cover samples 1..sample ("variance" off for some of them: vr_reset and render again).
+ *     vr_tile_samples / vr_tile_error wait and write one value per raster tile of the frame (t = ty * ceil(W/16) + tx, row 0 = bottom).
+ *     Ragged frames: a call that leaves tiles at different counts leaves a "ragged" frame.  While "sample" keeps the value that call left:
+ *     vr_trace and vr_render refuse it (VR_ERR, frame untouched: vr_reset, or continue with vr_render_adaptive), vr_variance applies each
+ *     tile's own n / (n - 1) (0 for n < 2), vr_denoise takes each tile's own n (VR_ERR if a tile holds no samples), and vr_last_kernel_ms /
+ *     vr_last_pathtrace_ms cover the whole vr_render_adaptive call: all its launches, and the sum of all its path-tracing kernels.  Anything
+ *     that changes "sample" ends the ragged state (vr_reset, vr_resize, the loaders, vr_set_int "sample" -- even to the same value): the frame
+ *     counts as uniform again.  A call that ends with every tile at one count leaves an ordinary uniform frame.
+ *     Bias: the decision to stop uses the variance estimated from the very samples it judges, so tiles whose estimate came out low stop early
+ *     and the result is biased towards them -- as in the adaptive samplers of production renderers; there is no second sample buffer here.
+ *     A tile whose pixels saw no collision in its first min_spp samples (the volume is thin there) has zero estimated variance and retires at
+ *     once: keep min_spp at 16 or more.  Not available on the sharded renderer. */
+/* render until every tile of the tile set has e_t < threshold or max_spp samples (the schedule above); 2 <= min_spp <= max_spp,
+   threshold finite and >= 0, else VR_ERR_ARG; VR_ERR for missing moments or a tripped watchdog */
+int vr_render_adaptive(vr_renderer* r, int min_spp, int max_spp, float threshold);
+/* samples behind each raster tile (row 0 = bottom, t = ty * ceil(W/16) + tx); a uniform frame gives `sample` everywhere;
+   n_tiles must be ceil(W/16) * ceil(H/16) (VR_ERR_ARG otherwise); waits */
+int vr_tile_samples(vr_renderer* r, int32_t* out, int n_tiles);
+/* e_t of every tile at its current count (same kernel as the schedule); needs the moments to cover the frame; waits */
+int vr_tile_error(vr_renderer* r, float* out, int n_tiles);
 int vr_draw(vr_renderer* r);
 int vr_display(vr_renderer* r, float* rgba_out);
 int vr_save_png(vr_renderer* r, const char* path);

@@ -1,6 +1,7 @@
 // capi.cpp -- extern "C" surface of libvolren_amd.so (include/volren_amd.h) over the C++ classes.
 #include "../../include/volren_amd.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <filesystem>
@@ -278,7 +279,7 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
     return guard([&] {
         auto& R = r->impl;
         const std::string n = name;
-        if (n == "sample") R.sample = v;
+        if (n == "sample") { R.sample = v; R.drop_tile_samples(); }      // a count set by hand is a uniform frame's (include/volren_amd.h: ragged frames)
         else if (n == "sppx") R.sppx = v;
         else if (n == "seed") R.seed = v;
         else if (n == "bounces") R.bounces = v;
@@ -342,6 +343,7 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
         else if (n == "grid_frame_counter") *v = R.volume ? (int)R.volume->grid_frame_counter : 0;
         else if (n == "n_grid_frames") *v = R.volume ? (int)R.volume->n_grid_frames() : 0;
         else if (n == "last_launches") *v = R.last_launches;
+        else if (n == "adaptive_rounds") *v = R.adaptive_rounds;
         else if (n == "width") *v = R.resolution.x;
         else if (n == "height") *v = R.resolution.y;
         else throw std::runtime_error("unknown int parameter: " + n);
@@ -421,9 +423,7 @@ int vr_synchronize(vr_renderer* r) {
     return guard([&] {
         use_device(r);
         r->impl.synchronize();
-        const uint32_t st = r->impl.watchdog_status();
-        if (st & vr::kFeatureLostStatus) throw std::runtime_error("feature pass: a camera segment exceeded its step budget (vr_render_features); the pixels concerned cover only their samples before it");
-        if (st != 0) throw std::runtime_error("path-tracing kernel watchdog tripped (a wavefront exceeded its step budget)");
+        r->impl.check_watchdog();
     });
 }
 
@@ -472,6 +472,41 @@ int vr_denoised(vr_renderer* r, float* out) {
     if (!out) return fail(VR_ERR_ARG, "null argument");
     if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
     return guard([&] { use_device(r); r->impl.download_denoised(out); });
+}
+// adaptive sampling: the arguments, then the device, are checked before the renderer is touched
+int vr_render_adaptive(vr_renderer* r, int min_spp, int max_spp, float threshold) {
+    NEED(r);
+    if (min_spp < 2 || min_spp > max_spp || !(threshold >= 0.0f) || !std::isfinite(threshold))
+        return fail(VR_ERR_ARG, "vr_render_adaptive: needs 2 <= min_spp <= max_spp and a finite threshold >= 0");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.render_adaptive(min_spp, max_spp, threshold); });
+}
+static int tile_count_arg(vr_renderer* r, int n_tiles) {
+    const auto& res = r->impl.resolution;
+    return n_tiles == ((res.x + 15) / 16) * ((res.y + 15) / 16) ? VR_OK : fail(VR_ERR_ARG, "n_tiles must be ceil(W / 16) * ceil(H / 16)");
+}
+int vr_tile_samples(vr_renderer* r, int32_t* out, int n_tiles) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    if (tile_count_arg(r, n_tiles) != VR_OK) return VR_ERR_ARG;
+    return guard([&] {
+        use_device(r);
+        r->impl.synchronize();
+        const std::vector<int32_t> c = r->impl.tile_samples();
+        std::copy(c.begin(), c.end(), out);
+    });
+}
+int vr_tile_error(vr_renderer* r, float* out, int n_tiles) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    if (tile_count_arg(r, n_tiles) != VR_OK) return VR_ERR_ARG;
+    return guard([&] {
+        use_device(r);
+        const std::vector<float> e = r->impl.tile_error();
+        std::copy(e.begin(), e.end(), out);
+    });
 }
 int vr_framebuffer_device(vr_renderer* r, void** p) {
     NEED(r);

@@ -8,6 +8,8 @@
 // grouped ncclAllGather per frame; a device named more than once = logical shards of one GPU, exchanged by device-to-device copies).
 // Addition: --denoise keeps the per-pixel variance, runs the feature pass (min(spp, 16) samples) and the a-trous denoiser (vr_denoise.h) after every
 // frame and writes the tonemapped denoised frame instead of the raw one (one device only).
+// Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
+// the mean samples per pixel; combines with --denoise (one device only).
 //
 //   volren data/smoke.brick data/table_mountain_2_puresky_1k.hdr -w 1024 -h 1024 --render --spp 4096 --bounces 128 \
 //          --albedo 0.8 --phase 0.3 --density 100 --env_strength 3 --env_rot 270 --exposure 3 --gamma 2.0 --cam_fov 40
@@ -15,6 +17,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <filesystem>
@@ -83,7 +86,7 @@ static void parse_cmd(int argc, char** argv) {
     Args a{ argc, argv, 0 };
     for (a.i = 1; a.i < argc; ++a.i) {
         const std::string arg = argv[a.i];
-        if (arg == "--render" || arg == "--denoise") {          // --denoise: main()
+        if (arg == "--render" || arg == "--denoise") {          // --denoise, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
@@ -119,7 +122,7 @@ static void parse_cmd(int argc, char** argv) {
         } else if (arg == "--vol_crop_min") { renderer->vol_clip_min.x = a.nextf(); renderer->vol_clip_min.y = a.nextf(); renderer->vol_clip_min.z = a.nextf(); }
         else if (arg == "--vol_crop_max") { renderer->vol_clip_max.x = a.nextf(); renderer->vol_clip_max.y = a.nextf(); renderer->vol_clip_max.z = a.nextf(); }
         else if (arg == "--seed") renderer->seed = a.nexti();                        // addition
-        else if (arg == "--device" || arg == "--gpus" || arg == "--devices") a.next();  // consumed earlier
+        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive") a.next();  // consumed earlier
         else if (fs::is_regular_file(arg) || fs::is_directory(arg)) handle_path(arg);
     }
 }
@@ -160,7 +163,8 @@ int main(int argc, char** argv) {
         if (arg.size() > 3 && arg.compare(arg.size() - 3, 3, ".py") == 0 && fs::is_regular_file(arg)) return run_python_script(argc, argv);
     }
     int width = 1280, height = 720, device = 0, gpus = 0;        // cppgl ContextParameters defaults (unverified): always pass -w/-h
-    bool denoise = false;
+    bool denoise = false, adaptive = false;
+    float threshold = 0.f;
     std::vector<int> devices;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -171,7 +175,15 @@ int main(int argc, char** argv) {
             else if (arg == "--gpus" && i + 1 < argc) gpus = std::stoi(argv[++i]);
             else if (arg == "--devices" && i + 1 < argc) devices = parse_int_list(argv[++i]);
             else if (arg == "--denoise") denoise = true;
+            else if (arg == "--adaptive") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --adaptive");
+                adaptive = true;
+                threshold = std::stof(argv[++i]);
+                if (!(threshold >= 0.f) || !std::isfinite(threshold)) throw std::runtime_error("--adaptive: the threshold must be finite and >= 0");
+            }
         }
+        if (adaptive && (gpus > 0 || devices.size() > 1))
+            throw std::runtime_error("--adaptive renders on one device only: drop --gpus / --devices (the sharded renderer has no adaptive sampling)");
         if (denoise && (gpus > 0 || devices.size() > 1))
             throw std::runtime_error("--denoise renders on one device only: drop --gpus / --devices (the sharded renderer has no denoiser)");
         // one renderer per part; without --gpus / --devices: one part on --device, the reference's single-context loop
@@ -218,14 +230,30 @@ int main(int argc, char** argv) {
             if (shards) {
                 shards->render(renderer->sppx);
                 shards->synchronize();
+            } else if (adaptive) {
+                renderer->render_adaptive(std::min(16, renderer->sppx), renderer->sppx, threshold);
+                renderer->synchronize();
+                if (renderer->watchdog_status()) throw std::runtime_error("path-tracing kernel watchdog tripped");
             } else {
                 renderer->render(renderer->sppx);          // == while (sample < sppx) trace();
                 renderer->synchronize();
                 if (renderer->watchdog_status()) throw std::runtime_error("path-tracing kernel watchdog tripped");
             }
             const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            std::cout << renderer->sample << " / " << renderer->sppx << "  (" << sec << " s, "
-                      << (double)width * height * renderer->sppx / sec / 1e6 << " Msamples/s)" << std::endl;
+            if (adaptive) {
+                const std::vector<int32_t> n = renderer->tile_samples();
+                double px_samples = 0.0;                   // partial edge tiles count their pixels inside the frame
+                const int tiles_x = (width + 15) / 16;
+                for (size_t t = 0; t < n.size(); ++t) {
+                    const int tx = (int)(t % tiles_x), ty = (int)(t / tiles_x);
+                    px_samples += (double)n[t] * std::min(16, width - 16 * tx) * std::min(16, height - 16 * ty);
+                }
+                std::cout << "adaptive: " << px_samples / ((double)width * height) << " spp mean, " << renderer->sample << " max / " << renderer->sppx
+                          << ", " << renderer->adaptive_rounds << " rounds  (" << sec << " s, " << px_samples / sec / 1e6 << " Msamples/s)" << std::endl;
+            } else {
+                std::cout << renderer->sample << " / " << renderer->sppx << "  (" << sec << " s, "
+                          << (double)width * height * renderer->sppx / sec / 1e6 << " Msamples/s)" << std::endl;
+            }
             VR_HIP(hipSetDevice(devices[0]));
             renderer->tonemapping = true;               // the offline loop always tonemaps (main.cpp:540-550)
             if (denoise) {

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <iostream>
 
+#include "vr_adaptive.h"
 #include "vr_device.h"
 #include "vr_math.h"
 
@@ -58,11 +59,12 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     features_.reset();
     moments_.reset(); moments_n_ = -1;
     dn_guide_.reset(); dn_var_[0].reset(); dn_var_[1].reset(); dn_color_[0].reset(); dn_color_[1].reset(); denoised_.reset();
+    drop_tile_samples(); tile_n_dev_.reset(); adaptive_lists_.reset(); adaptive_err_.reset();
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
 }
 
-void RendererHIP::reset() { sample = 0; }
+void RendererHIP::reset() { sample = 0; drop_tile_samples(); }
 
 // ---------------------------------------------------------------------------------------------------
 static void check_grid_bytes(size_t bytes, const char* what, const int32_t nb[3]);
@@ -456,18 +458,12 @@ void RendererHIP::set_tiles(const std::vector<int32_t>& tile_ids) {
 // the launch ends with its deepest path (4-5 ms on the bench scene: 2 % of a frame on one GPU, 15 % of a rank's share on eight).  With the costly tiles --
 // long chords through the volume's box -- at the FRONT of every segment and the tiles whose rays miss the box at its end, what is left at that point are
 // camera rays that escape at once.  Cost estimate: the longest chord of five rays of the tile (corners and centre, no jitter) through the clipped box.
-// Sorted (stably) inside each eighth of the list, so that an XCD keeps its band of tile rows.  Cached per (camera, box, frame size, tile set).
-const int32_t* RendererHIP::tile_order(const SceneParams& P, int n_tiles) {
+// Sorted (stably) inside each eighth of the list, so that an XCD keeps its band of tile rows.  tile_order caches the device list per (camera, box,
+// frame size, tile list); ids empty = the n_tiles tiles of the whole frame.
+std::vector<int32_t> RendererHIP::costliest_first(const SceneParams& P, const std::vector<int32_t>& tile_ids, int n_tiles) const {
     const Uniforms& u = P.u;
-    uint64_t key = 1469598103934665603ull;
-    auto mix = [&key](const void* p, size_t nbytes) { const uint8_t* b = static_cast<const uint8_t*>(p); for (size_t i = 0; i < nbytes; ++i) { key ^= b[i]; key *= 1099511628211ull; } };
-    mix(u.cam_pos, sizeof u.cam_pos); mix(u.cam_transform, sizeof u.cam_transform); mix(&P.cam_z, sizeof P.cam_z);
-    mix(u.vol_bb_min, sizeof u.vol_bb_min); mix(u.vol_bb_max, sizeof u.vol_bb_max); mix(u.resolution, sizeof u.resolution); mix(&n_tiles, sizeof n_tiles);
-    if (!tiles_host_.empty()) mix(tiles_host_.data(), tiles_host_.size() * sizeof(int32_t));
-    key = key ? key : 1;
-    if (order_dev_ && order_key_ == key && order_dev_->size_bytes() == (size_t)n_tiles * sizeof(int32_t)) return order_dev_->as<int32_t>();
     const int W = u.resolution[0], H = u.resolution[1], tiles_x = (W + 15) / 16;
-    std::vector<int32_t> ids(tiles_host_);
+    std::vector<int32_t> ids(tile_ids);
     if (ids.empty()) { ids.resize((size_t)n_tiles); for (int i = 0; i < n_tiles; ++i) ids[(size_t)i] = i; }
     auto chord = [&](float px, float py) {
         float d[3] = { (px - 0.5f * (float)W) / (float)H, (py - 0.5f * (float)H) / (float)H, P.cam_z };
@@ -495,6 +491,19 @@ const int32_t* RendererHIP::tile_order(const SceneParams& P, int n_tiles) {
         std::stable_sort(perm.begin() + (ptrdiff_t)b, perm.begin() + (ptrdiff_t)std::min(ids.size(), b + seg), [&](int32_t x, int32_t y) { return cost[(size_t)x] > cost[(size_t)y]; });
     std::vector<int32_t> ordered(ids.size());
     for (size_t k = 0; k < ids.size(); ++k) ordered[k] = ids[(size_t)perm[k]];
+    return ordered;
+}
+
+const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) {
+    const Uniforms& u = P.u;
+    uint64_t key = 1469598103934665603ull;
+    auto mix = [&key](const void* p, size_t nbytes) { const uint8_t* b = static_cast<const uint8_t*>(p); for (size_t i = 0; i < nbytes; ++i) { key ^= b[i]; key *= 1099511628211ull; } };
+    mix(u.cam_pos, sizeof u.cam_pos); mix(u.cam_transform, sizeof u.cam_transform); mix(&P.cam_z, sizeof P.cam_z);
+    mix(u.vol_bb_min, sizeof u.vol_bb_min); mix(u.vol_bb_max, sizeof u.vol_bb_max); mix(u.resolution, sizeof u.resolution); mix(&n_tiles, sizeof n_tiles);
+    if (!ids.empty()) mix(ids.data(), ids.size() * sizeof(int32_t));
+    key = key ? key : 1;
+    if (order_dev_ && order_key_ == key && order_dev_->size_bytes() == (size_t)n_tiles * sizeof(int32_t)) return order_dev_->as<int32_t>();
+    const std::vector<int32_t> ordered = costliest_first(P, ids, n_tiles);
     if (!order_dev_ || order_dev_->size_bytes() != ordered.size() * sizeof(int32_t)) order_dev_ = make_device_buffer(ordered.size() * sizeof(int32_t));
     order_dev_->upload(ordered.data(), ordered.size() * sizeof(int32_t), stream);
     order_key_ = key;
@@ -580,16 +589,21 @@ int RendererHIP::samples_per_launch(const LaunchInputs& in, int n_tiles) const {
     return per_launch;
 }
 
-void RendererHIP::submit(const LaunchInputs& in, int first, int n) {
+void RendererHIP::submit_tile_set(const LaunchInputs& in, int first, int n) {
+    if (n <= 0) return;
+    const int tiles_x = (in.P.u.resolution[0] + 15) / 16, tiles_y = (in.P.u.resolution[1] + 15) / 16;
+    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tiles_x * tiles_y;
+    const bool ordered = in.order_tiles >= 2 || (in.order_tiles == 1 && tiles_dev_);
+    const int32_t* tiles = ordered ? tile_order(in.P, tiles_host_, n_tiles) : (tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr);
+    submit(in, first, n, tiles, n_tiles);
+}
+
+void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles) {
     if (n <= 0) return;
     const SceneParams& P = in.P;
     hipStream_t stream = in.stream;                              // (shadows the member: the launch goes where it was recorded for)
     const bool has_tf = P.u.use_tf != 0;
     update_majorants(in, density_grids.at(in.frame));
-    const int tiles_x = (P.u.resolution[0] + 15) / 16, tiles_y = (P.u.resolution[1] + 15) / 16;
-    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tiles_x * tiles_y;
-    const bool ordered = in.order_tiles >= 2 || (in.order_tiles == 1 && tiles_dev_);
-    const int32_t* tiles = ordered ? tile_order(P, n_tiles) : (tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr);
     // per-sample radiances live in a device pool; split the request so that one sub-launch fits the pool
     int per_launch = std::min(samples_per_launch(in, n_tiles), n);
     for (;;) {                                                   // a pool that does not fit the free HBM: halve the sub-launch, never fail for it
@@ -664,9 +678,11 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n) {
     } else {
         moments_n_ = -1;
     }
-    VR_HIP(hipEventRecord(ev0_, stream));
-    last_launches = 0;
-    pt_events_used_ = 0;
+    if (!keep_timing_) {
+        VR_HIP(hipEventRecord(ev0_, stream));
+        last_launches = 0;
+        pt_events_used_ = 0;
+    }
     for (int done = 0; done < n;) {
         ++last_launches;
         const int m = probe > 0 ? probe : std::min(per_launch, n - done);
@@ -707,7 +723,9 @@ void RendererHIP::harvest_rate(bool wait) {
 // record the same bytes are launched together (renderer.h).  What a caller can observe is unchanged: `sample` advances by one per call, invalid
 // state throws at the call, and every way of looking at the frame launches the recorded samples first -- with the values they were recorded with.
 void RendererHIP::trace() {
-    if (!coalesce_trace) { flush_pending(); LaunchInputs in; capture(in); submit(in, sample, 1); sample += 1; return; }
+    if (ragged())
+        throw std::runtime_error("trace: the frame holds per-tile sample counts of render_adaptive (a ragged frame): reset(), or continue with render_adaptive");
+    if (!coalesce_trace) { flush_pending(); LaunchInputs in; capture(in); submit_tile_set(in, sample, 1); sample += 1; return; }
     LaunchInputs now;
     capture(now);
     if (pending_n_ > 0 && (sample != pending_first_ + pending_n_ || !now.same_launch_as(pending_))) flush_pending();
@@ -728,16 +746,17 @@ void RendererHIP::flush_pending() {
     pending_n_ = 0;                                              // (first: submit may throw, and must not be retried with half of it enqueued)
     LaunchInputs in = std::move(pending_);
     pending_ = LaunchInputs{};
-    submit(in, first, n);
+    submit_tile_set(in, first, n);
 }
 
 void RendererHIP::render(int n) {
     flush_pending();
+    if (ragged()) throw std::runtime_error("render: the frame holds per-tile sample counts of render_adaptive (a ragged frame): reset(), or continue with render_adaptive");
     if (n <= 0) n = sppx - sample;
     if (n <= 0) return;
     LaunchInputs in;
     capture(in);
-    submit(in, sample, n);
+    submit_tile_set(in, sample, n);
     sample += n;
 }
 
@@ -843,6 +862,7 @@ void RendererHIP::download_features(float* out) {
 }
 
 void RendererHIP::check_moments(const char* who) {
+    if (ragged() && moments_) return;                 // render_adaptive keeps the moments of every launch: they cover each tile's own count
     if (sample < 1 || !moments_ || moments_n_ != sample)
         throw std::runtime_error(std::string(who) + ": the moments do not cover samples 1.." + std::to_string(sample) +
                                  " (variance was off for some of them, e.g. switched on mid-frame): reset() and render with variance = 1");
@@ -853,6 +873,17 @@ void RendererHIP::download_variance(float* rgba) {
     check_moments("variance");
     moments_->download(rgba, moments_->size_bytes(), stream);
     const size_t n = (size_t)resolution.x * resolution.y * 4;
+    if (ragged()) {                                   // each tile's own factor
+        const int W = resolution.x, H = resolution.y, tiles_x = (W + 15) / 16;
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                const int32_t c = tile_n_[(size_t)((y >> 4) * tiles_x + (x >> 4))];
+                const float f = c >= 2 ? (float)c / (float)(c - 1) : 0.0f;
+                float* px = rgba + 4 * ((size_t)y * W + x);
+                for (int k = 0; k < 4; ++k) px[k] = c >= 2 ? px[k] * f : 0.0f;
+            }
+        return;
+    }
     const float f = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;
     for (size_t i = 0; i < n; ++i) rgba[i] = sample >= 2 ? rgba[i] * f : 0.0f;
 }
@@ -866,6 +897,15 @@ void RendererHIP::denoise() {
     if (!features_) throw std::runtime_error("denoise: no feature pass since the last resize (call render_features first)");
     if (sample < 1) throw std::runtime_error("denoise: the framebuffer holds no samples (sample < 1)");
     check_moments("denoise");
+    const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
+    if (ragged()) {
+        for (int32_t c : tile_n_)
+            if (c < 1) throw std::runtime_error("denoise: a tile of the frame holds no samples (sample < 1 there: render_adaptive over a tile subset from sample 0)");
+        const size_t bytes = tile_n_.size() * sizeof(int32_t);
+        if (!tile_n_dev_ || tile_n_dev_->size_bytes() != bytes) tile_n_dev_ = make_device_buffer(bytes);
+        tile_n_dev_->upload(tile_n_.data(), bytes, stream);
+        counts = tile_n_dev_->as<int32_t>();
+    }
     const int32_t W = resolution.x, H = resolution.y, N = denoise_iterations;
     if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error("denoise: frame too large (32-bit pixel indices)");
     if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error("denoise: denoise_iterations out of range");
@@ -877,7 +917,7 @@ void RendererHIP::denoise() {
     if (N >= 2) { ensure(dn_var_[1], px * sizeof(float)); ensure(dn_color_[0], px * 4 * sizeof(float)); }
     if (N >= 3) ensure(dn_color_[1], px * 4 * sizeof(float));
     const float vscale = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;      // download_variance's factor
-    launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
+    launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, counts, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
     VR_HIP(hipGetLastError());
     if (N == 0) {
         VR_HIP(hipMemcpyAsync(denoised_->get(), color->get(), color->size_bytes(), hipMemcpyDeviceToDevice, stream));
@@ -897,6 +937,130 @@ void RendererHIP::download_denoised(float* rgba) {
     if (!denoised_) throw std::runtime_error("denoised: no denoise since the last resize (call denoise first)");
     flush_pending();
     denoised_->download(rgba, denoised_->size_bytes(), stream);
+}
+
+// ---- adaptive sampling (vr_adaptive.h) -----------------------------------------------------------------------------------------------------------
+bool RendererHIP::ragged() {
+    if (!tile_n_.empty() && sample != tile_n_sample_) drop_tile_samples();
+    return !tile_n_.empty();
+}
+
+void RendererHIP::drop_tile_samples() { tile_n_.clear(); tile_n_sample_ = -1; }
+
+std::vector<int32_t> RendererHIP::tile_samples() {
+    flush_pending();
+    if (ragged()) return tile_n_;
+    return std::vector<int32_t>((size_t)(((resolution.x + 15) / 16) * ((resolution.y + 15) / 16)), sample);
+}
+
+std::vector<float> RendererHIP::tile_error() {
+    flush_pending();
+    if (!color) throw std::runtime_error("tile_error: no framebuffer");
+    check_moments("tile_error");
+    const std::vector<int32_t> counts = tile_samples();
+    const int n_all = (int)counts.size();
+    std::vector<int32_t> lists((size_t)n_all * 2);
+    for (int t = 0; t < n_all; ++t) { lists[(size_t)t] = t; lists[(size_t)(n_all + t)] = counts[(size_t)t]; }
+    if (!adaptive_lists_ || adaptive_lists_->size_bytes() < lists.size() * sizeof(int32_t)) adaptive_lists_ = make_device_buffer(lists.size() * sizeof(int32_t));
+    if (!adaptive_err_ || adaptive_err_->size_bytes() < (size_t)n_all * sizeof(float)) adaptive_err_ = make_device_buffer((size_t)n_all * sizeof(float));
+    adaptive_lists_->upload(lists.data(), lists.size() * sizeof(int32_t), stream);
+    launch_adaptive_error(color->as<float>(), moments_->as<float>(), adaptive_lists_->as<int32_t>(), adaptive_lists_->as<int32_t>() + n_all, n_all, resolution.x,
+                          resolution.y, adaptive_err_->as<float>(), stream);
+    VR_HIP(hipGetLastError());
+    std::vector<float> e((size_t)n_all);
+    adaptive_err_->download(e.data(), e.size() * sizeof(float), stream);
+    return e;
+}
+
+// The schedule of vr_adaptive.h.  Per round: the live tiles and their counts go up in one copy, the error kernel runs, its values come back
+// (the round's one wait), then one submit per group of equal counts, each group's tiles costliest first (unless order_tiles is 0) and all
+// groups' lists in one more copy.  The tile counts are the bookkeeping of what has been enqueued; `sample` follows at the end (or on a throw).
+void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
+    if (min_spp < 2 || min_spp > max_spp || !(threshold >= 0.0f) || !std::isfinite(threshold))
+        throw std::invalid_argument("render_adaptive: needs 2 <= min_spp <= max_spp and a finite threshold >= 0");
+    flush_pending();
+    if (!color) throw std::runtime_error("render_adaptive: no framebuffer (call resize first)");
+    const bool was_ragged = ragged();
+    if (sample > 0 && !was_ragged && !(moments_ && moments_n_ == sample))
+        throw std::runtime_error("render_adaptive: the moments do not cover samples 1.." + std::to_string(sample) +
+                                 " (variance was off for some of them): reset() and render with variance = 1");
+    LaunchInputs in;
+    capture(in);
+    in.variance = 1;                                  // the error estimate needs the moments of every launch
+    const int W = resolution.x, H = resolution.y, n_all = ((W + 15) / 16) * ((H + 15) / 16);
+    if (!was_ragged) tile_n_.assign((size_t)n_all, std::max(sample, 0));
+    std::vector<int32_t> set(tiles_host_);
+    if (set.empty()) { set.resize((size_t)n_all); for (int t = 0; t < n_all; ++t) set[(size_t)t] = t; }
+    if (!adaptive_lists_ || adaptive_lists_->size_bytes() < (size_t)n_all * 2 * sizeof(int32_t)) adaptive_lists_ = make_device_buffer((size_t)n_all * 2 * sizeof(int32_t));
+    if (!adaptive_err_ || adaptive_err_->size_bytes() < (size_t)n_all * sizeof(float)) adaptive_err_ = make_device_buffer((size_t)n_all * sizeof(float));
+    const bool ordered = in.order_tiles >= 1;
+    VR_HIP(hipEventRecord(ev0_, in.stream));
+    last_launches = 0;
+    pt_events_used_ = 0;
+    adaptive_rounds = 0;
+    keep_timing_ = true;
+    // every group of `ids` from its count n to to(n), as one submit each
+    auto launch_groups = [&](const std::vector<int32_t>& ids, const auto& to) {
+        const auto groups = adaptive_groups(ids, tile_n_);
+        std::vector<int32_t> packed;
+        for (const auto& g : groups) {
+            const std::vector<int32_t> o = ordered ? costliest_first(in.P, g.second, (int)g.second.size()) : g.second;
+            packed.insert(packed.end(), o.begin(), o.end());
+        }
+        if (packed.empty()) return;
+        adaptive_lists_->upload(packed.data(), packed.size() * sizeof(int32_t), in.stream);
+        size_t off = 0;
+        for (const auto& g : groups) {
+            const int32_t n = g.first, next = to(n);
+            submit(in, n, next - n, adaptive_lists_->as<int32_t>() + off, (int)g.second.size());
+            for (int32_t t : g.second) tile_n_[(size_t)t] = next;
+            off += g.second.size();
+        }
+    };
+    auto finish = [&] {
+        keep_timing_ = false;
+        VR_HIP(hipEventRecord(ev1_, in.stream));
+        timing_pending_ = true;
+        const auto mm = std::minmax_element(tile_n_.begin(), tile_n_.end());
+        sample = *mm.second;
+        if (*mm.first == *mm.second) { drop_tile_samples(); moments_n_ = sample; }      // every tile at one count: an ordinary uniform frame
+        else { tile_n_sample_ = sample; moments_n_ = -1; }
+    };
+    try {
+        std::vector<int32_t> low;                     // step 1: the set to min_spp
+        for (int32_t t : set) if (tile_n_[(size_t)t] < min_spp) low.push_back(t);
+        launch_groups(low, [&](int32_t) { return min_spp; });
+        std::vector<int32_t> live, go;
+        for (int32_t t : set) if (tile_n_[(size_t)t] < max_spp) live.push_back(t);
+        while (!live.empty()) {                       // step 2: rounds
+            ++adaptive_rounds;
+            const size_t m = live.size();
+            std::vector<int32_t> lists(live);
+            for (int32_t t : live) lists.push_back(tile_n_[(size_t)t]);
+            adaptive_lists_->upload(lists.data(), lists.size() * sizeof(int32_t), in.stream);
+            launch_adaptive_error(color->as<float>(), moments_->as<float>(), adaptive_lists_->as<int32_t>(), adaptive_lists_->as<int32_t>() + m, (int32_t)m, W, H,
+                                  adaptive_err_->as<float>(), in.stream);
+            VR_HIP(hipGetLastError());
+            std::vector<float> e(m);
+            adaptive_err_->download(e.data(), m * sizeof(float), in.stream);
+            check_watchdog();
+            go.clear();
+            for (size_t k = 0; k < m; ++k) if (!adaptive_converged(e[k], threshold)) go.push_back(live[k]);
+            launch_groups(go, [&](int32_t n) { return adaptive_next_count(n, max_spp); });
+            live.clear();
+            for (int32_t t : go) if (tile_n_[(size_t)t] < max_spp) live.push_back(t);
+        }
+    } catch (...) {
+        finish();
+        throw;
+    }
+    finish();
+}
+
+void RendererHIP::check_watchdog() {
+    const uint32_t st = watchdog_status();
+    if (st & kFeatureLostStatus) throw std::runtime_error("feature pass: a camera segment exceeded its step budget (vr_render_features); the pixels concerned cover only their samples before it");
+    if (st != 0) throw std::runtime_error("path-tracing kernel watchdog tripped (a wavefront exceeded its step budget)");
 }
 
 uint32_t RendererHIP::watchdog_status() {

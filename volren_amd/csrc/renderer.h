@@ -71,6 +71,20 @@ struct RendererHIP {
 
     // all of `n` further samples in one launch (n <= 0: up to sppx)
     void render(int n = 0);
+    // Adaptive sampling (vr_adaptive.h): every tile of the tile set (set_tiles; empty = the whole frame) to min_spp, then rounds that evaluate
+    // the error e_t of the tiles below max_spp, retire those with e_t < threshold and double the others' counts (at most max_spp).  Starts from
+    // a uniform frame of `sample` samples (whose moments cover it, unless sample = 0) or from the counts a previous call left.  Keeps the moments
+    // for all its launches whatever `variance` says (the field is left unchanged).  Afterwards sample = the largest count of any tile; a frame
+    // whose tiles hold different counts is "ragged" (tile_samples) until sample changes.  Asynchronous like render(), except that every round
+    // waits for its error values (one small copy) and throws on a tripped watchdog.  2 <= min_spp <= max_spp, threshold finite and >= 0.
+    void render_adaptive(int min_spp, int max_spp, float threshold);
+    // samples behind every raster tile (tiles_x * tiles_y, row 0 = bottom): `sample` everywhere on a uniform frame
+    std::vector<int32_t> tile_samples();
+    // e_t of every raster tile at its current count (the schedule's kernel); needs moments that cover the frame.  Waits
+    std::vector<float> tile_error();
+    bool ragged();                                     // the frame holds the per-tile counts of a render_adaptive (drops them once `sample` has moved)
+    void drop_tile_samples();                          // forget them (vr_set_int "sample": a value set back by hand does not revive them)
+    void check_watchdog();                             // throws (as vr_synchronize reports it) if the status word is set; reads and clears it
 
     // helper to convert brick grid to device arrays
     BrickGridHIP brick_grid_to_device(const std::shared_ptr<BrickGrid>& grid);
@@ -139,7 +153,8 @@ struct RendererHIP {
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
                                                       // with one bound the renderer refuses it: DESIGN.md 3)
     PathtraceTuning tuning = default_tuning();        // scheduler thresholds, work-unit size, statistics buffer of THIS renderer's launches
-    int last_launches = 0;                            // path-tracing sub-launches of the last trace()/render()
+    int last_launches = 0;                            // path-tracing sub-launches of the last trace()/render()/render_adaptive()
+    int adaptive_rounds = 0;                          // error evaluations (rounds) of the last render_adaptive()
     int launch_target_ms = 2000;                      // a sub-launch is planned to take at most this long, from the rate the renderer measured on its last launch (a short
                                                       // probe launch when it has none for the current settings and the request is large); 0 = plan by the sample pool alone.
                                                       // Correctness does not depend on it (the kernel's watchdog is progress-based): it bounds how long one launch holds the GPU
@@ -204,17 +219,25 @@ private:
         bool same_launch_as(const LaunchInputs& o) const;
     };
     void capture(LaunchInputs& in);            // validates, builds the decoded float atlas when a LUT needs it, fills `in` from the current fields
-    void submit(const LaunchInputs& in, int first, int n);      // samples first+1 .. first+n
+    // samples first+1 .. first+n of the `n_tiles` tiles of the device list `tiles` in that order (nullptr: the whole frame in raster order)
+    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles);
+    void submit_tile_set(const LaunchInputs& in, int first, int n);      // submit over the renderer's tile set (set_tiles), ordered as order_tiles says
     int samples_per_launch(const LaunchInputs& in, int n_tiles) const;
     LaunchInputs pending_;
     int pending_n_ = 0, pending_first_ = 0, pending_cap_ = 0;
     void update_majorants(const LaunchInputs& in, BrickGridHIP& g);
     std::vector<int32_t> tiles_host_;
     DeviceBufferPtr tiles_dev_;
-    // the launch's own order of those tiles: the costliest first (launch(): tile_order)
+    // the launch's own order of those tiles: the costliest first (tile_order; ids empty = the whole frame)
     DeviceBufferPtr order_dev_;
     uint64_t order_key_ = 0;
-    const int32_t* tile_order(const SceneParams& P, int n_tiles);
+    std::vector<int32_t> costliest_first(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const;
+    const int32_t* tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles);
+    // adaptive sampling: samples behind each raster tile, meaningful while `sample` == tile_n_sample_ (ragged()); device copy for the denoiser
+    std::vector<int32_t> tile_n_;
+    int tile_n_sample_ = -1;
+    DeviceBufferPtr tile_n_dev_, adaptive_lists_, adaptive_err_;
+    bool keep_timing_ = false;                         // submit() adds to the timing window of the call in progress instead of opening its own
     DeviceBufferPtr status_;
     DeviceBufferPtr pool_;
     DeviceBufferPtr workspace_;
@@ -222,7 +245,7 @@ private:
     DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
     DeviceBufferPtr moments_;                          // W*H*4 second moments, allocated by the first launch with `variance` on
     int moments_n_ = -1;                               // the moments cover samples 1..moments_n_ (-1: they do not start at sample 1)
-    void check_moments(const char* who);               // throws unless the moments cover samples 1..sample
+    void check_moments(const char* who);               // throws unless the moments cover samples 1..sample (of every tile, on a ragged frame)
     DeviceBufferPtr dn_guide_, dn_var_[2], dn_color_[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4 (dropped by resize)
     DeviceBufferPtr denoised_;                         // W*H*4: the last denoise()'s result (dropped by resize)
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;

@@ -40,9 +40,15 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
 // n = 1: vr_variance's arithmetic), features = W*H*8 (vr_render_features) -> v = W*H variances of the mean's luminance, guide = W*H*8.
 // atrous: one iteration of step `step` from (cin W*H*4, vin W*H, guide) into cout (W*H*4) and vout (W*H; nullptr: not written); the
 // inputs and outputs must not overlap.
-void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, float* v, float* guide, hipStream_t stream);
+// counts: one sample count per raster tile (a frame of adaptive sampling), which replaces n and vscale per pixel; nullptr = the scalars.
+void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, const int32_t* counts, float* v, float* guide,
+                            hipStream_t stream);
 void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
                            float* cout, float* vout, hipStream_t stream);
+// Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
+// and the W*H*4 moments (device arrays, ids in range).
+void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,
+                           hipStream_t stream);
 // which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
 // what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
 enum PathtraceVariantReason : int {

@@ -11,7 +11,8 @@
 //
 // Also here: the environment importance pyramid + warp table (env_setup.glsl, environment.cpp), the dense->brick encoder
 // (voldata to_brick_grid at commit()), majorant remap, tonemap.glsl, direct volume rendering (common.glsl:571-591),
-// tile pack/unpack for the multi-GPU gather, the denoiser feature pass, the a-trous denoiser and a math probe for the tests.
+// tile pack/unpack for the multi-GPU gather, the denoiser feature pass, the a-trous denoiser, the error estimate of adaptive sampling and a math
+// probe for the tests.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "vr_adaptive.h"
 #include "vr_denoise.h"
 #include "vr_device.h"
 #include "vr_pathtrace.h"
@@ -159,16 +161,19 @@ struct DenoiseSrcDev {
     }
 };
 // prepare: moments S (W*H*4, Welford's M2 / n) -> the unbiased variance var = S * vscale exactly as vr_variance forms it (0 for n = 1), then
-// the variance of the mean's luminance v (W*H) and the guide (W*H*8) from the features
+// the variance of the mean's luminance v (W*H) and the guide (W*H*8) from the features.  counts (a frame of adaptive sampling: one count per
+// raster tile) replaces the scalar n and vscale with the tile's own, formed as the host forms vscale; nullptr = the scalars
 __global__ void __launch_bounds__(256)
-denoise_prepare_kernel(const float4* __restrict__ moments, const float4* __restrict__ features, int32_t W, int32_t H, int32_t n, float vscale,
-                       float* __restrict__ v, float4* __restrict__ guide) {
+denoise_prepare_kernel(const float4* __restrict__ moments, const float4* __restrict__ features, int32_t W, int32_t H, int32_t n_all, float vscale_all,
+                       const int32_t* __restrict__ counts, float* __restrict__ v, float4* __restrict__ guide) {
     const int32_t tiles_x = (W + 15) >> 4;
     const int32_t tile = (int32_t)blockIdx.x;
     const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
     const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
     const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
     if (px >= W || py >= H) return;
+    const int32_t n = counts ? counts[tile] : n_all;
+    const float vscale = counts ? (n >= 2 ? (float)n / (float)(n - 1) : 0.0f) : vscale_all;
     const int32_t i = py * W + px;
     const float4 m = moments[i];
     const float var[4] = { n >= 2 ? m.x * vscale : 0.0f, n >= 2 ? m.y * vscale : 0.0f, n >= 2 ? m.z * vscale : 0.0f, n >= 2 ? m.w * vscale : 0.0f };
@@ -198,10 +203,42 @@ denoise_atrous_kernel(const float4* __restrict__ cin, const float* __restrict__ 
     if (vout) vout[i] = ov;
 }
 static unsigned denoise_blocks(int32_t W, int32_t H) { return (unsigned)(((W + 15) / 16) * ((H + 15) / 16)); }
-void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, float* v, float* guide, hipStream_t stream) {
+void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, const int32_t* counts, float* v, float* guide,
+                            hipStream_t stream) {
     if (W <= 0 || H <= 0) return;
     hipLaunchKernelGGL(denoise_prepare_kernel, dim3(denoise_blocks(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(moments),
-                       reinterpret_cast<const float4*>(features), W, H, n, vscale, v, reinterpret_cast<float4*>(guide));
+                       reinterpret_cast<const float4*>(features), W, H, n, vscale, counts, v, reinterpret_cast<float4*>(guide));
+}
+
+// Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile with accumulate_kernel's pixel mapping (four 8x8
+// wavefronts); each lane forms e_p of its pixel (-inf outside the frame: the identity of the max), a wave64 max by xor shuffles, the four
+// waves' maxima through LDS, and lane 0 writes the tile's value.  Max is exact, so the order of the reduction does not matter.
+__global__ void __launch_bounds__(256)
+adaptive_error_kernel(const float4* __restrict__ fb, const float4* __restrict__ moments, const int32_t* __restrict__ tiles, const int32_t* __restrict__ counts,
+                      int32_t W, int32_t H, float* __restrict__ out) {
+    __shared__ float wave_max[4];
+    const int32_t tiles_x = (W + 15) >> 4;
+    const int32_t tile = tiles[blockIdx.x], n = counts[blockIdx.x];
+    const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
+    const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
+    const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
+    float e = -inf_();
+    if (px < W && py < H) {
+        const size_t i = (size_t)py * W + px;
+        const float4 c = fb[i], m = moments[i];
+        const float mu[4] = { c.x, c.y, c.z, c.w }, S[4] = { m.x, m.y, m.z, m.w };
+        e = adaptive_pixel_error(mu, S, n);
+    }
+    for (int32_t d = 32; d > 0; d >>= 1) e = adaptive_max(e, __shfl_xor(e, d, 64));
+    if (p == 0) wave_max[wave] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = adaptive_max(adaptive_max(wave_max[0], wave_max[1]), adaptive_max(wave_max[2], wave_max[3]));
+}
+void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,
+                           hipStream_t stream) {
+    if (n_tiles <= 0 || W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(adaptive_error_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, reinterpret_cast<const float4*>(fb),
+                       reinterpret_cast<const float4*>(moments), tiles, counts, W, H, out);
 }
 void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
                            float* cout, float* vout, hipStream_t stream) {

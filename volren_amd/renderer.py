@@ -59,7 +59,8 @@ class Renderer:
         return v.value
 
     def __getattr__(self, name):
-        if name in _INT_FIELDS or name in ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason"):
+        if name in _INT_FIELDS or name in ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
+                                              "adaptive_rounds"):
             v = C.c_int()
             _lib.check(self._L.vr_get_int(self._h, name.encode(), C.byref(v)))
             return bool(v.value) if name in ("show_environment", "tonemapping") else v.value
@@ -258,6 +259,29 @@ class Renderer:
         """[H][W][4] float32, row 0 = bottom: the last denoise()'s result, linear (not tonemapped)."""
         out = np.empty((self.height, self.width, 4), np.float32)
         _lib.check(self._L.vr_denoised(self._h, out.ctypes.data))
+        return out
+
+    # ---- adaptive sampling ----
+    def render_adaptive(self, min_spp, max_spp, threshold, sync=True):
+        """Per 16x16 tile: min_spp samples, then doubling until the tile's error e_t is below `threshold` or it has max_spp samples
+        (include/volren_amd.h vr_render_adaptive).  Keeps the moments whatever `variance` says; `sample` becomes the largest tile count."""
+        _lib.check(self._L.vr_render_adaptive(self._h, int(min_spp), int(max_spp), float(threshold)))
+        if sync:
+            self.synchronize()
+
+    def _tiles(self):
+        return (self.height + 15) // 16, (self.width + 15) // 16
+
+    def tile_samples(self):
+        """[tiles_y][tiles_x] int32, row 0 = bottom: the samples behind each tile (`sample` everywhere on a uniform frame)."""
+        out = np.empty(self._tiles(), np.int32)
+        _lib.check(self._L.vr_tile_samples(self._h, out.ctypes.data, out.size))
+        return out
+
+    def tile_error(self):
+        """[tiles_y][tiles_x] float32, row 0 = bottom: e_t of each tile at its current count (needs moments that cover the frame)."""
+        out = np.empty(self._tiles(), np.float32)
+        _lib.check(self._L.vr_tile_error(self._h, out.ctypes.data, out.size))
         return out
 
     def framebuffer_device_ptr(self):

@@ -553,6 +553,19 @@ class Renderer:
         """(w, h, 3) float: the denoised colour, in fbo_data()'s shape."""
         return self._r.denoised()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
 
+    # -- adaptive sampling (no reference counterpart): like render(), from sample 0
+    def render_adaptive(self, min_spp, max_spp, threshold):
+        """Renders the frame afresh (as render() does), per 16x16 tile from min_spp up to max_spp samples, doubling until the tile's error is
+        below `threshold` (volren_amd.Renderer.render_adaptive)."""
+        self._r.sample = 0
+        self._r.render_adaptive(int(min_spp), int(max_spp), float(threshold))
+
+    def sample_count_data(self):
+        """(w, h) int32: the samples behind every pixel, in fbo_data()'s shape (an input of a learned denoiser)."""
+        t = self._r.tile_samples()
+        per_px = np.repeat(np.repeat(t, 16, axis=0), 16, axis=1)[:self._r.height, :self._r.width]
+        return np.ascontiguousarray(per_px).reshape(self._r.width, self._r.height)
+
     def _write(self, filename, channels):
         from PIL import Image
         self._r.draw()
