@@ -268,6 +268,10 @@ int vr_wave_timeline(vr_renderer* r, unsigned long long* out, int n_words);
 int vr_test_alloc_cap_mb(long long mb);
 /* unit-test probe of the device math (volren_amd/csrc/vr_math.h): host arrays in/out */
 int vr_math_probe(int fn, const float* a, const float* b, float* out, int n);
+/* test hook: unit-test probe of the scene-data lookups (volren_amd/csrc/vr_probe.h): n items of probe `what` (0 voxel, 1 trilinear, 2 majorant, 3 importance,
+ * 4 texel, 5 sky, 6 light sample, 7 transfer function) in compile-time form `form`, on the scene as the renderer's next launch would read it.  in: 4 32-bit words per
+ * item; out: 1, 1, 1, 1, 3, 3, 7, 4 floats per item; host arrays.  VR_ERR_RUNTIME for a form the scene cannot serve (the message says why). */
+int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, long long n);
 /* voldata::Volume::to_brick_grid + BrickGrid serialisation: encode a dense float grid (x fastest) and write it as a .brick
  * container (SURVEY.md 2.3 layout); transform may be NULL (identity).  Host only, needs no device. */
 int vr_write_brick_from_dense(const float* voxels, int nx, int ny, int nz, const float* transform, const char* path);

@@ -123,6 +123,13 @@ def lib():
     L.orc_phase_hg.restype = c_f
     L.orc_transmittance.argtypes = [C.POINTER(Params), C.POINTER(Scene), P_f, P_f, P_u32]
     L.orc_transmittance.restype = c_f
+    c_i64 = C.c_int64
+    L.orc_batch_voxel.argtypes = [C.POINTER(Scene), C.c_void_p, C.c_void_p, c_i64]
+    L.orc_batch_importance.argtypes = [C.POINTER(Scene), C.c_void_p, C.c_void_p, c_i64]
+    L.orc_batch_texel.argtypes = [C.POINTER(Scene), C.c_void_p, C.c_void_p, c_i64]
+    for name in ("trilinear", "majorant", "sky", "tf"):
+        getattr(L, "orc_batch_" + name).argtypes = [C.POINTER(Params), C.POINTER(Scene), C.c_void_p, C.c_void_p, c_i64]
+    L.orc_batch_light.argtypes = [C.POINTER(Params), C.POINTER(Scene), C.c_void_p, C.c_void_p, C.c_void_p, c_i64]
     L.orc_math.argtypes = [c_i, c_f, c_f]
     L.orc_math.restype = c_f
     L.orc_num_threads.restype = c_i
@@ -411,6 +418,30 @@ class OracleRenderer:
                          self.sample + 1, int(spp), int(threads), C.byref(self.counters))
         self.sample += int(spp)
         return self.fb
+
+    # --- batch lookups (orc_batch_*): the probes of volren_amd/csrc/vr_probe.h, same item layout ---
+    PROBES = ("voxel", "trilinear", "majorant", "importance", "texel", "sky", "light", "tf")
+    PROBE_OUT_WORDS = (1, 1, 1, 1, 3, 3, 7, 4)
+
+    def probe(self, what, items, texel=False):
+        """items: [n][4] 32-bit words; returns [n][k] float32 -- and, for the light probe with texel=True, also the [n][2] base-level texels."""
+        items = np.ascontiguousarray(items)
+        assert items.ndim == 2 and items.shape[1] == 4 and items.dtype.itemsize == 4
+        name = self.PROBES[what]
+        n = items.shape[0]
+        out = np.empty((n, self.PROBE_OUT_WORDS[what]), np.float32)
+        p, s = self.params(), self.scene()
+        fn = getattr(lib(), "orc_batch_" + name)
+        if name in ("voxel", "importance", "texel"):
+            fn(C.byref(s), items.ctypes.data, out.ctypes.data, n)
+        elif name == "light":
+            tx = np.empty((n, 2), np.int32) if texel else None
+            fn(C.byref(p), C.byref(s), items.ctypes.data, out.ctypes.data, tx.ctypes.data if texel else None, n)
+            if texel:
+                return out, tx
+        else:
+            fn(C.byref(p), C.byref(s), items.ctypes.data, out.ctypes.data, n)
+        return out
 
     def trace_pixel_sample(self, x, y, sample):
         p, s = self.params(), self.scene()

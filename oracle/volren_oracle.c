@@ -151,7 +151,7 @@ static v3 lookup_environment(const ctx_t* c, v3 dir) {
 }
 
 /* ref: common.glsl:100-146; returns (Le.rgb, pdf) */
-static void sample_environment(const ctx_t* c, float r0, float r1, v3* w_i, float le_pdf[4]) {
+static void sample_environment_texel(const ctx_t* c, float r0, float r1, v3* w_i, float le_pdf[4], int32_t texel[2]) {
     const orc_params* p = c->p;
     int posx = 0, posy = 0;
     float px = r0, py = r1;
@@ -188,7 +188,9 @@ static void sample_environment(const ctx_t* c, float r0, float r1, v3* w_i, floa
     le_pdf[1] = p->env_strength * rgb[1];
     le_pdf[2] = p->env_strength * rgb[2];
     le_pdf[3] = pdf * INV_4PI;
+    if (texel) { texel[0] = posx; texel[1] = posy; }
 }
+static void sample_environment(const ctx_t* c, float r0, float r1, v3* w_i, float le_pdf[4]) { sample_environment_texel(c, r0, r1, w_i, le_pdf, NULL); }
 
 /* ref: common.glsl:148-152 */
 static float pdf_environment(const ctx_t* c, v3 dir) {
@@ -334,18 +336,20 @@ static inline float lookup_density_i(const ctx_t* c, int x, int y, int z) {
     return c->p->vol_density_scale * orc_lookup_density_brick(c->s->density, x, y, z);
 }
 /* ref: common.glsl:289-297 */
-static float lookup_density_trilinear(const ctx_t* c, v3 ipos) {
+static float trilinear_raw(const orc_brickgrid* g, v3 ipos) {
     const float qx = ipos.x - 0.5f, qy = ipos.y - 0.5f, qz = ipos.z - 0.5f;
     const float fx = qx - floorf(qx), fy = qy - floorf(qy), fz = qz - floorf(qz);
     int ix = om_floor2i(qx), iy = om_floor2i(qy), iz = om_floor2i(qz);
-    const orc_brickgrid* g = c->s->density;
     /* NaN/inf: every tap reads "outside" */
     int x1 = ix == INT32_MIN ? INT32_MIN : ix + 1, y1 = iy == INT32_MIN ? INT32_MIN : iy + 1, z1 = iz == INT32_MIN ? INT32_MIN : iz + 1;
     const float lx0 = om_mix(orc_lookup_density_brick(g, ix, iy, iz), orc_lookup_density_brick(g, x1, iy, iz), fx);
     const float lx1 = om_mix(orc_lookup_density_brick(g, ix, y1, iz), orc_lookup_density_brick(g, x1, y1, iz), fx);
     const float hx0 = om_mix(orc_lookup_density_brick(g, ix, iy, z1), orc_lookup_density_brick(g, x1, iy, z1), fx);
     const float hx1 = om_mix(orc_lookup_density_brick(g, ix, y1, z1), orc_lookup_density_brick(g, x1, y1, z1), fx);
-    return c->p->vol_density_scale * om_mix(om_mix(lx0, lx1, fy), om_mix(hx0, hx1, fy), fz);
+    return om_mix(om_mix(lx0, lx1, fy), om_mix(hx0, hx1, fy), fz);
+}
+static float lookup_density_trilinear(const ctx_t* c, v3 ipos) {
+    return c->p->vol_density_scale * trilinear_raw(c->s->density, ipos);
 }
 /* ref: common.glsl:300-304 */
 static float lookup_density_stochastic(const ctx_t* c, v3 ipos, uint32_t* seed) {
@@ -846,6 +850,47 @@ void orc_sample_environment(const orc_params* p, const orc_scene* s, float r0, f
     ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s;
     v3 w; sample_environment(&c, r0, r1, &w, le_pdf);
     w_i[0] = w.x; w_i[1] = w.y; w_i[2] = w.z;
+}
+
+/* ------------------------------------------------------------------ */
+/* batch lookups for the probe tests: items of four 32-bit words in (the layout of volren_amd/csrc/vr_probe.h), floats out */
+static inline float word_f(uint32_t w) { float f; memcpy(&f, &w, 4); return f; }
+#define ORC_BATCH(BODY) \
+    _Pragma("omp parallel for schedule(static)") \
+    for (int64_t i = 0; i < n; ++i) { const uint32_t* w = in + 4 * i; BODY }
+
+void orc_batch_voxel(const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(out[i] = orc_lookup_density_brick(w[0] ? s->emission : s->density, (int32_t)w[1], (int32_t)w[2], (int32_t)w[3]);)
+}
+void orc_batch_trilinear(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(out[i] = p->vol_density_scale * trilinear_raw(w[0] ? s->emission : s->density, V3(word_f(w[1]), word_f(w[2]), word_f(w[3])));)
+}
+/* the majorant the DDA trackers use: lookup_majorant, through the LUT when one is bound (dda_majorant) */
+void orc_batch_majorant(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s;
+              out[i] = dda_majorant(&c, V3(word_f(w[0]), word_f(w[1]), word_f(w[2])), (int32_t)w[3]);)
+}
+void orc_batch_importance(const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(out[i] = imp_fetch(s, (int32_t)w[0], (int32_t)w[1], (int32_t)w[2]);)
+}
+void orc_batch_texel(const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(orc_env_texture(s->envmap, s->env_w, s->env_h, word_f(w[0]), word_f(w[1]), out + 3 * i);)
+}
+void orc_batch_sky(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s;
+              const v3 e = lookup_environment(&c, V3(word_f(w[0]), word_f(w[1]), word_f(w[2])));
+              out[3 * i] = e.x; out[3 * i + 1] = e.y; out[3 * i + 2] = e.z;)
+}
+/* out: w_i, Le, pdf (7 floats); texel (may be NULL): the base-level texel the descent ends in, 2 per item */
+void orc_batch_light(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int32_t* texel, int64_t n) {
+    ORC_BATCH(ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s;
+              v3 wi; float lp[4];
+              sample_environment_texel(&c, word_f(w[0]), word_f(w[1]), &wi, lp, texel ? texel + 2 * i : NULL);
+              float* o = out + 7 * i;
+              o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = lp[0]; o[4] = lp[1]; o[5] = lp[2]; o[6] = lp[3];)
+}
+void orc_batch_tf(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
+    ORC_BATCH(ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s; tf_lookup(&c, word_f(w[0]), out + 4 * i);)
 }
 
 /* ------------------------------------------------------------------ */

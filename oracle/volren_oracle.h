@@ -155,6 +155,19 @@ int      orc_sample_volume(const orc_params* p, const orc_scene* s, const float 
 void     orc_sample_phase_hg(const float dir[3], float g, float r0, float r1, float out[3]);
 float    orc_phase_hg(float cos_t, float g);
 float    orc_transmittance(const orc_params* p, const orc_scene* s, const float pos[3], const float dir[3], uint32_t* seed);
+/* batch forms of the lookups (arrays in, arrays out, OpenMP): item i is the four 32-bit words in[4 i ..] -- integers or float bits --
+ * voxel: grid (0 density, 1 emission), x, y, z -> lookup_density_brick; trilinear: grid, then the index-space position as float bits ->
+ * lookup_density_trilinear (density scale applied); majorant: position as float bits, mip -> the effective lookup_majorant of the DDA
+ * trackers (TF-remapped when a LUT is bound); importance: x, y, mip; texel: u, v -> 3 floats; sky: direction -> lookup_environment, 3 floats;
+ * light: r0, r1 -> sample_environment as (w_i, Le, pdf), 7 floats, and optionally the base-level texel it ends in; tf: density -> 4 floats */
+void     orc_batch_voxel(const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+void     orc_batch_trilinear(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+void     orc_batch_majorant(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+void     orc_batch_importance(const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+void     orc_batch_texel(const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+void     orc_batch_sky(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+void     orc_batch_light(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int32_t* texel, int64_t n);
+void     orc_batch_tf(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
 float    orc_math(int32_t fn, float a, float b);   /* 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin */
 int32_t  orc_num_threads(void);
 

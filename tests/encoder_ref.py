@@ -4,14 +4,16 @@ import numpy as np
 
 
 def _half_down(x):
-    h = np.float16(x)
+    with np.errstate(over="ignore"):                 # beyond 65504: inf, which is the outward rounding
+        h = np.float16(x)
     if np.float32(h) > np.float32(x):
         h = np.nextafter(h, np.float16(-np.inf))
     return h
 
 
 def _half_up(x):
-    h = np.float16(x)
+    with np.errstate(over="ignore"):
+        h = np.float16(x)
     if np.float32(h) < np.float32(x):
         h = np.nextafter(h, np.float16(np.inf))
     return h
@@ -33,7 +35,10 @@ def encode_arrays(dense_zyx, transform=None):
         for by in range(nby):
             for bx in range(nbx):
                 blk = pad[bz * 8:bz * 8 + 12, by * 8:by * 8 + 12, bx * 8:bx * 8 + 12]
-                hlo, hhi = _half_down(blk.min()), _half_up(blk.max())
+                # (a NaN voxel is left out of the range, as the encoders' `v < lo ? v : lo` leaves it out; a window of NaN only is not defined here)
+                has_nan = bool(np.isnan(blk).any())
+                # (+ 0: a zero bound is +0.0, as in both encoders -- numpy's min / max may end on either zero)
+                hlo, hhi = _half_down((np.nanmin(blk) if has_nan else blk.min()) + np.float32(0)), _half_up((np.nanmax(blk) if has_nan else blk.max()) + np.float32(0))
                 rng[bz, by, bx] = int(hlo.view(np.uint16)) | (int(hhi.view(np.uint16)) << 16)
                 lo_f[bz, by, bx], hi_f[bz, by, bx] = np.float32(hlo), np.float32(hhi)
                 if np.float32(hhi) != np.float32(hlo):
@@ -47,8 +52,10 @@ def encode_arrays(dense_zyx, transform=None):
         lo, hi = lo_f[bz, by, bx], hi_f[bz, by, bx]
         v = pad[bz * 8 + 2:bz * 8 + 10, by * 8 + 2:by * 8 + 10, bx * 8 + 2:bx * 8 + 10]
         inv = np.float32(255.0) / np.float32(hi - lo)
-        q = np.floor((v - lo) * inv + np.float32(0.5))
-        atlas[pz * 8:pz * 8 + 8, py * 8:py * 8 + 8, px * 8:px * 8 + 8] = np.clip(q, 0, 255).astype(np.uint8)
+        with np.errstate(invalid="ignore"):
+            q = np.floor((v - lo) * inv + np.float32(0.5))
+        # a NaN here -- a NaN voxel, or inf - inf / inf * 0 in a brick whose range is infinite -- quantises to a defined 0, as in both encoders
+        atlas[pz * 8:pz * 8 + 8, py * 8:py * 8 + 8, px * 8:px * 8 + 8] = np.clip(np.nan_to_num(q, nan=0.0, posinf=255.0, neginf=0.0), 0, 255).astype(np.uint8)
     mips = []
     cur_lo, cur_hi, cur_w = lo_f, hi_f, rng
     for _ in range(3):

@@ -17,7 +17,7 @@ def build(sanitize=False, fast_tap=False):
     if fast_tap:
         so = os.path.join(_DIR, "libhostkernel_fasttap.so")
     src = os.path.join(_DIR, "host_kernel.cpp")
-    deps = [src] + [os.path.join(_ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h")]
+    deps = [src, os.path.join(_DIR, "host_scene.h")] + [os.path.join(_ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h", "env_pack.h")]
     if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
         return so
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
@@ -74,6 +74,13 @@ def lib(fast_tap=False):
         L.hk_math.argtypes = [C.c_int, C.c_float, C.c_float]
         _libs[fast_tap] = L
     return _libs[fast_tap]
+
+
+def cfg_steps(reset=False, fast_tap=False):
+    """lane steps per compiled form since the last reset: (TraceCfg<false,0,0,0,2>, <false,0,0,1,2>, <false,2,2,2,2>, <true,2,2,2,2>)"""
+    out = (C.c_ulonglong * 4)()
+    lib(fast_tap).hk_cfg_steps(out, 1 if reset else 0)
+    return tuple(int(v) for v in out)
 
 
 def render(orc_renderer, spp, rect=None, fb=None, first_sample=1, fast_tap=False):

@@ -9,91 +9,11 @@
 #include <cstring>
 #include <vector>
 
-#include "../../volren_amd/csrc/vr_trace.h"
+#include "host_scene.h"
 
 using namespace vr;
+using namespace hostscene;
 
-namespace {
-struct HostGrid {
-    std::vector<BrickRec> recs;
-    std::vector<uint8_t> atlas;
-    std::vector<float> majorant, rng, atlas_f32;
-    std::vector<uint16_t> majorant16;
-    GridView view{};
-};
-
-void build_grid(HostGrid& g, const Uniforms& u, const float* lut, const uint32_t nb[3], const uint32_t* indirection, const uint32_t* range,
-                const uint32_t ad[3], const uint8_t* atlas, int n_mips, const uint32_t* const* mips, bool density, bool blocked = false) {
-    g.view.maj_blocked = blocked ? 1 : 0;
-    const size_t n = (size_t)nb[0] * nb[1] * nb[2];
-    const uint32_t sx = ad[0] / 8, sy = ad[1] / 8, sz = ad[2] / 8;
-    for (int i = 0; i < 3; ++i) { g.view.mshift[i] = ceil_log2(nb[i]) < 3 ? 3 : ceil_log2(nb[i]); g.view.mlim[i] = (float)(8u << g.view.mshift[i]); }
-    g.recs.assign(n, BrickRec{ 0u, 0.f, 0.f, 0u });
-    g.atlas.assign(g.recs.size() * (size_t)kBrickBlockBytes, 0);            // brick-linear blocks == brick_grid_to_device
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t ind = indirection[i], rg = range[i];
-        const uint32_t px = ind >> 22, py = (ind >> 12) & 1023u, pz = (ind >> 2) & 1023u;
-        const float lo = half2float(rg & 0xFFFFu), hi = half2float(rg >> 16);
-        const size_t idx = i;
-        BrickRec& r = g.recs[idx];
-        r.slot = (uint32_t)idx; r.rmin = lo; r.rdiff = hi - lo; r.range = rg;
-        uint8_t* dst = &g.atlas[idx * (size_t)kBrickBlockBytes];
-        if (VR_BRICK_HEADERS)
-            for (uint32_t l = 0; l < 5; ++l) { memcpy(dst + l * 128u, &r.rmin, 4); memcpy(dst + l * 128u + 4u, &r.rdiff, 4); }
-        if (r.rdiff != 0.f && px < sx && py < sy && pz < sz)
-            for (uint32_t z = 0; z < 8; ++z) for (uint32_t y = 0; y < 8; ++y) {
-                const uint8_t* src = atlas + (((size_t)(pz * 8 + z) * ad[1] + (py * 8 + y)) * ad[0] + px * 8);
-                for (uint32_t x = 0; x < 8; ++x) dst[brick_voxel_byte(z * 64 + y * 8 + x)] = src[x];
-            }
-    }
-    std::vector<uint32_t> words(range, range + n);
-    uint32_t mip_off[4] = { 0u, 0u, 0u, 0u };
-    for (int m = 1; m <= n_mips; ++m) {
-        const uint32_t rnd = (1u << m) - 1u;
-        const size_t cnt = (size_t)((nb[0] + rnd) >> m) * ((nb[1] + rnd) >> m) * ((nb[2] + rnd) >> m);
-        mip_off[m] = (uint32_t)words.size();
-        words.insert(words.end(), mips[m - 1], mips[m - 1] + cnt);
-    }
-    const uint32_t k = (uint32_t)(g.view.mshift[0] + g.view.mshift[1] + g.view.mshift[2]);
-    g.majorant.assign(majorant_table_cells(k), 0.0f);
-    g.majorant16.assign(majorant_table_cells(k), 0);
-    g.view.maj_outside = (int32_t)majorant_padded_cells(k);
-    if (density) {
-        SceneParams P{}; P.u = u; P.tf_lut = lut;
-        {   // == majorant_kernel: every cell without a range word (beyond the real extent, missing level, the "outside" cell) holds density_scale * 0, TF-remapped
-            float m0 = u.vol_density_scale * half2float(0u);
-            if (u.use_tf) { float rgba[4]; tf_lookup(P, m0 * u.vol_inv_majorant, rgba); m0 = u.vol_majorant * rgba[3]; }
-            g.majorant.assign(majorant_table_cells(k), m0);
-        }
-        for (int mip = 0; mip <= n_mips; ++mip) {            // == majorant_kernel of vr_kernels.hip
-            const uint32_t rnd = (1u << mip) - 1u;
-            const uint32_t dx = (nb[0] + rnd) >> mip, dy = (nb[1] + rnd) >> mip, dz = (nb[2] + rnd) >> mip;
-            const uint32_t sxm = (uint32_t)g.view.mshift[0] - mip, sym = (uint32_t)g.view.mshift[1] - mip;
-            for (uint32_t cz = 0; cz < dz; ++cz) for (uint32_t cy = 0; cy < dy; ++cy) for (uint32_t cx = 0; cx < dx; ++cx) {
-                const uint32_t hw = words[mip_off[mip] + ((size_t)cz * dy + cy) * dx + cx] >> 16;
-                const uint32_t cell = majorant_level_offset(k, mip) + majorant_cell_index(cx, cy, cz, sxm, sym, (uint32_t)mip, blocked);
-                g.majorant16[cell] = (uint16_t)hw;
-                float m = u.vol_density_scale * half2float(hw);
-                if (u.use_tf) { float rgba[4]; tf_lookup(P, m * u.vol_inv_majorant, rgba); m = u.vol_majorant * rgba[3]; }
-                g.majorant[cell] = m;
-            }
-        }
-    }
-    g.rng.resize(g.recs.size() * 2);
-    for (size_t i = 0; i < g.recs.size(); ++i) { g.rng[2 * i] = g.recs[i].rmin; g.rng[2 * i + 1] = g.recs[i].rdiff; }
-    g.view.bricks = g.recs.data(); g.view.atlas = g.atlas.data(); g.view.majorant = g.majorant.data();
-    g.view.majorant16 = g.majorant16.data(); g.view.rng = g.rng.data();
-    g.view.atlas_f32 = nullptr;
-    if (density && u.use_tf) {                  // == RendererHIP::launch: decoded float atlas for transfer-function renders
-        g.atlas_f32.resize(g.recs.size() * 512);
-        for (size_t i = 0; i < g.atlas_f32.size(); ++i)
-            g.atlas_f32[i] = g.rng[2 * (i >> 9)] + unorm8(g.atlas[(i >> 9) * (size_t)kBrickBlockBytes + brick_voxel_byte((uint32_t)(i & 511u))]) * g.rng[2 * (i >> 9) + 1];
-        g.view.atlas_f32 = g.atlas_f32.data();
-    }
-    for (int i = 0; i < 3; ++i) g.view.nb[i] = (int32_t)nb[i];
-    g.view.n_mips = n_mips;
-}
-}  // namespace
 
 // ---- access trace (tests/tools_coherence_by_scope.py): which 128-byte line of the majorant table a marching path's next DDA step reads, which
 // 4x4x4-voxel block (one line of the dense grid) / 8^3 brick a path at a tentative collision stands in.  One 32-bit word per lane-step:
@@ -117,77 +37,14 @@ static void trace_access(const Hot& h, const SceneParams& P) {
     }
 }
 
+// lane steps per compiled form since the last hk_cfg_steps(reset): [0] TraceCfg<false, 0, 0, 0, 2>, [1] <false, 0, 0, 1, 2>, [2] <false, 2, 2, 2, 2>, [3] <true, 2, 2, 2, 2>
+static unsigned long long g_cfg_steps[4] = { 0, 0, 0, 0 };
+
 extern "C" {
 
-struct hk_grid_desc {
-    uint32_t nb[3]; uint32_t atlas_dim[3]; int32_t n_mips;
-    const uint32_t* indirection; const uint32_t* range; const uint8_t* atlas; const uint32_t* mips[3];
-    const uint16_t* dense; uint32_t dim[3];
-};
-
 int hk_uniforms_size() { return (int)sizeof(Uniforms); }
-
-// the scene as the lane code sees it (SceneParams + the arrays its views point into), built from the oracle's arrays exactly as the product builds its device copies
-struct HostScene {
-    SceneParams P{};
-    HostGrid dg, eg;
-    std::vector<uint16_t> blocked;
-    std::vector<float> env, cdf;
-};
-static void build_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
-                        const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim) {
-    SceneParams& P = S.P;
-    HostGrid& dg = S.dg; HostGrid& eg = S.eg;
-    std::vector<uint16_t>& blocked = S.blocked;
-    std::vector<float>& env = S.env; std::vector<float>& cdf = S.cdf;
-    const Uniforms& u = *up;
-    P.u = u;
-    build_grid(dg, u, lut, density->nb, density->indirection, density->range, density->atlas_dim, density->atlas, density->n_mips, density->mips, true,
-               // the majorant table's levels 0-1 in 4x4x4-cell blocks (a per-grid choice of the product since round 5; the lane code reads the view's flag at run time here)
-               std::getenv("VR_HOST_MAJ_BLOCKED") != nullptr && std::getenv("VR_HOST_MAJ_BLOCKED")[0] == '1');
-    P.density = dg.view;
-    // (blocked: == dense_grid_to_device: 4x4x4 blocks)
-    if (density->dense) {
-        const uint32_t dx = density->dim[0], dy = density->dim[1], dz = density->dim[2];
-        const uint32_t bx = (dx + 3u) / 4u, by = (dy + 3u) / 4u, bz = (dz + 3u) / 4u;
-        blocked.assign((size_t)bx * by * bz * 64u, 0);
-        for (uint32_t z = 0; z < dz; ++z) for (uint32_t y = 0; y < dy; ++y) for (uint32_t x = 0; x < dx; ++x)
-            blocked[dense_blocked_index(x, y, z, bx, by)] = density->dense[((size_t)z * dy + y) * dx + x];
-        P.density.dense = blocked.data();
-        P.density.dblk[0] = (int32_t)bx; P.density.dblk[1] = (int32_t)by;
-    }
-    for (int i = 0; i < 3; ++i) P.density.dim[i] = (int32_t)density->dim[i];
-    if (emission && u.has_emission) {
-        build_grid(eg, u, lut, emission->nb, emission->indirection, emission->range, emission->atlas_dim, emission->atlas, emission->n_mips, emission->mips, false);
-        P.emission = eg.view;
-        // emission_from_density = vol_emission_inv_transform * vol_density_transform (same product as hostmath.h)
-        const float* a = u.vol_emission_inv_transform; const float* b = u.vol_density_transform;
-        for (int c = 0; c < 4; ++c) for (int r = 0; r < 4; ++r)
-            P.emission_from_density[4 * c + r] = a[r] * b[4 * c] + a[4 + r] * b[4 * c + 1] + a[8 + r] * b[4 * c + 2] + a[12 + r] * b[4 * c + 3];
-    }
-    P.tf_lut = lut;
-    env.assign((size_t)env_w * env_h * kEnvTexelFloats, 0.0f);
-    for (size_t i = 0; i < (size_t)env_w * env_h; ++i) for (int k = 0; k < 3; ++k) env[kEnvTexelFloats * i + k] = env_rgb[3 * i + k];
-    P.envmap = env.data(); P.env_w = env_w; P.env_h = env_h;
-    P.impmap = impmap; P.imp_dim = imp_dim;
-    int base = 0; while ((1 << base) < imp_dim) ++base;
-    cdf.assign(env_cdf_table_floats(base - 1), 0.0f);
-    {   // == env_cdf_kernel of vr_kernels.hip
-        for (int mip = base - 1; mip >= 0; --mip) {
-            const int d = imp_dim >> mip, hd = d >> 1;
-            const float* level = impmap + imp_level_offset(imp_dim, mip);
-            for (int y = 0; y < hd; ++y) for (int x = 0; x < hd; ++x) {
-                const float w0 = level[(size_t)(2 * y) * d + 2 * x], w1 = level[(size_t)(2 * y) * d + 2 * x + 1];
-                const float w2 = level[(size_t)(2 * y + 1) * d + 2 * x], w3 = level[(size_t)(2 * y + 1) * d + 2 * x + 1];
-                const float q0 = w0 + w2, q1 = w1 + w3;
-                float* o = cdf.data() + env_cdf_index(base - 1, base - 1 - mip, (uint32_t)x, (uint32_t)y);
-                o[0] = q0 / max_(1e-8f, q0 + q1); o[1] = w0 / q0; o[2] = w1 / q1;
-                if (mip == 0) { o[3] = w0; o[4] = w1; o[5] = w2; o[6] = w3; }
-            }
-        }
-    }
-    P.env_cdf = cdf.data();
-    P.cam_z = -0.5f / tan_(0.5f * kPi * u.cam_fov / 180.f);
+void hk_cfg_steps(unsigned long long out[4], int reset) {
+    for (int i = 0; i < 4; ++i) { if (out) out[i] = g_cfg_steps[i]; if (reset) g_cfg_steps[i] = 0; }
 }
 
 // env_rgb: texture order (row 0 bottom), 3 floats per texel.  Returns the number of lane steps executed.
@@ -245,14 +102,16 @@ long long hk_render(const Uniforms* up, const hk_grid_desc* density, const hk_gr
                         if (l.state == ST_NEW) for (float& v : cold[i].v) v = nan_();         // a new path must not depend on what its cold line held
                         if (g_trace && (l.state == ST_MARCH || l.state == ST_COLLIDE)) trace_access(l, P);
 #if VR_WORLD_SLOT
-                        // a build with -DVR_WORLD_SLOT=1 (tests/test_host_kernel.py::test_world_slot_*): the kernels of one scene kind that carry the experiment -- DDA trackers,
-                        // no transfer function, no emission grid (the paired atlas of the emission kernels is not built here)
+                        // VR_WORLD_SLOT (vr_trace.h; on by default since round 6): the kernels of one scene kind that keep a parked path's world ray in its slot -- DDA
+                        // trackers, no transfer function, no emission grid (the lane code of the emission kernels, which read the paired atlas, is not run here; their
+                        // lookups are: probe_host.cpp).  tests/test_host_kernel.py::test_state_machine_matches_oracle asserts that these two forms ran (hk_cfg_steps)
                         if (!u.use_tf && u.integrator == 0 && !u.has_emission) {
-                            if (P.density.dense) lane_step<TraceCfg<false, 0, 0, 1, 2>>(l, cold[i], P, wu, next_item, stash[i]);
-                            else lane_step<TraceCfg<false, 0, 0, 0, 2>>(l, cold[i], P, wu, next_item, stash[i]);
+                            if (P.density.dense) { lane_step<TraceCfg<false, 0, 0, 1, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[1]; }
+                            else { lane_step<TraceCfg<false, 0, 0, 0, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[0]; }
                         } else
 #endif
-                        if (u.use_tf) lane_step<TraceCfg<true, 2, 2, 2, 2>>(l, cold[i], P, wu, next_item, stash[i]); else lane_step<TraceCfg<false, 2, 2, 2, 2>>(l, cold[i], P, wu, next_item, stash[i]);
+                        if (u.use_tf) { lane_step<TraceCfg<true, 2, 2, 2, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[3]; }
+                        else { lane_step<TraceCfg<false, 2, 2, 2, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[2]; }
                         if (++steps > (1ll << 40)) return -1;
                     }
                 }

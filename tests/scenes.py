@@ -209,6 +209,33 @@ def _range_mips(lo, hi):
     return mips
 
 
+def crop_bricks(a, nbc):
+    """Centred sub-block nbc = (cx, cy, cz) of an encode_arrays() brick grid: indirection/range cropped (the atlas pointers stay
+    valid), range mips rebuilt with the ceil(n / 2) rule (min of mins, max of maxes over the existing children)."""
+    nbx, nby, nbz = a["n_bricks"]
+    cx, cy, cz = nbc
+    ox, oy, oz = (nbx - cx) // 2, (nby - cy) // 2, (nbz - cz) // 2          # centred: the synthetic cloud is densest there
+    ind = a["indirection"].reshape(nbz, nby, nbx)[oz:oz + cz, oy:oy + cy, ox:ox + cx].copy()
+    rng = a["rng"].reshape(nbz, nby, nbx)[oz:oz + cz, oy:oy + cy, ox:ox + cx].copy()
+    lo = (rng & 0xFFFF).astype(np.uint16).view(np.float16).astype(np.float32)
+    hi = (rng >> 16).astype(np.uint16).view(np.float16).astype(np.float32)
+    mips = []
+    for _ in range(3):
+        z, y, x = lo.shape
+        z2, y2, x2 = (z + 1) // 2, (y + 1) // 2, (x + 1) // 2
+        plo = np.full((z2 * 2, y2 * 2, x2 * 2), np.inf, np.float32)
+        phi = np.full((z2 * 2, y2 * 2, x2 * 2), -np.inf, np.float32)
+        plo[:z, :y, :x] = lo
+        phi[:z, :y, :x] = hi
+        lo = plo.reshape(z2, 2, y2, 2, x2, 2).min((1, 3, 5))
+        hi = phi.reshape(z2, 2, y2, 2, x2, 2).max((1, 3, 5))
+        w = lo.astype(np.float16).view(np.uint16).astype(np.uint32) | (hi.astype(np.float16).view(np.uint16).astype(np.uint32) << 16)
+        mips.append(((x2, y2, z2), w.reshape(-1)))
+    out = dict(a)
+    out.update(n_bricks=(cx, cy, cz), indirection=ind.reshape(-1), rng=rng.reshape(-1), mips=mips)
+    return out
+
+
 _SPARSE_FULL = {}
 
 
@@ -466,3 +493,50 @@ def _configure_brick_pair(r, is_oracle, ad, at):
     r.density_scale = 100.0
     r.emission_scale = 100.0
     return r
+
+
+# ---- hostile inputs of the dense -> brick encoders (tests/test_gpu_lookups.py) -------------------------------------------------------------------
+HOSTILE_EXTENTS = ((1, 1, 1), (3, 70, 1), (65, 9, 8), (129, 8, 8))       # (nx, ny, nz); 129 x 8 x 8: the bricks from x = 136 on lie fully outside (x0 >= nx)
+HOSTILE_CASES = tuple([("random", e) for e in HOSTILE_EXTENTS] +
+                      [(k, (65, 9, 8)) for k in ("constant", "negative", "above_half_max", "1e-7", "1e-9", "denormal", "spikes", "ties", "inf")] +
+                      [("constant", (1, 1, 1)), ("negative", (3, 70, 1)), ("spikes", (129, 8, 8)), ("inf", (129, 8, 8))])
+
+
+def hostile_dense(kind, extent, seed=2027):
+    """A dense float32 grid [z][y][x] of extent (nx, ny, nz) that is hard on a dense -> brick encoder; fixed seed.  kinds: random (uniform 0..5), constant,
+    negative (-3..1), above_half_max (values beyond fp16's 65504: the range maximum rounds up to inf), 1e-7 / 1e-9 (ranges at and below fp16's smallest
+    denormal 6e-8), denormal (float32 denormals), spikes (zero but for a few isolated voxels), ties (values whose quantisation lands exactly on .5),
+    inf (+inf voxels among finite ones), minus_zero (-0.0 among the zeros), nan (NaN voxels among finite ones, no 12^3 window of NaN only)."""
+    nx, ny, nz = extent
+    rs = np.random.RandomState(seed + 131 * nx + 17 * ny + nz + sum(map(ord, kind)))
+    u = rs.uniform(0, 1, (nz, ny, nx)).astype(np.float32)
+    if kind == "random":
+        d = u * np.float32(5)
+    elif kind == "constant":
+        d = np.full((nz, ny, nx), 2.5, np.float32)
+    elif kind == "negative":
+        d = u * np.float32(4) - np.float32(3)
+    elif kind == "above_half_max":
+        d = u * np.float32(1e5)
+    elif kind in ("1e-7", "1e-9"):
+        d = u * np.float32(float(kind))
+    elif kind == "denormal":
+        d = (rs.randint(0, 1 << 22, (nz, ny, nx)).astype(np.uint32)).view(np.float32).copy()
+    elif kind == "spikes":
+        d = np.where(u > 0.985, u * np.float32(40), np.float32(0)).astype(np.float32)
+        d.flat[0] = 7.0
+    elif kind == "ties":
+        d = ((rs.randint(0, 255, (nz, ny, nx)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 / 255.0)).astype(np.float32)
+        d.flat[0], d.flat[-1] = 0.0, 2.0                       # a [0, 2] range where nothing is dilated away: (v - lo) * 255 / 2 = k + .5
+    elif kind == "inf":
+        d = u * np.float32(5)
+        d[u > 0.97] = np.inf
+    elif kind == "minus_zero":
+        d = np.where(u > 0.5, u, np.float32(0)).astype(np.float32)
+        d[u < 0.25] = -0.0
+    elif kind == "nan":
+        d = u * np.float32(5)
+        d[u > 0.97] = np.nan
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(d, np.float32)

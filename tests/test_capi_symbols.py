@@ -45,6 +45,10 @@ def test_no_device_fails_loudly():
         volren_amd.Renderer(32, 32)
     with pytest.raises(volren_amd.VolrenError):
         volren_amd.math_probe(0, [1.0])
+    words, out = (C.c_uint32 * 4)(), (C.c_float * 1)()
+    assert lib.vr_probe(C.c_void_p(1), 0, 2, words, out, 1) == 2 and b"no HIP device" in lib.vr_last_error()      # (the handle is not touched before the device check)
+    assert lib.vr_probe(None, 0, 2, words, out, 1) == 3                                       # VR_ERR_ARG: there is no renderer to probe without a device ...
+    assert lib.vr_probe(C.c_void_p(1), 0, 2, None, out, 1) == 3 and lib.vr_probe(C.c_void_p(1), 0, 2, words, out, -1) == 3      # ... and the arguments are checked first
     hs = C.c_void_p()
     devs = (C.c_int * 2)(0, 0)
     assert lib.vr_sharded_create(C.byref(hs), devs, 2, 64, 64) == 2 and not hs.value      # the sharded renderer has no CPU path either

@@ -440,31 +440,7 @@ def test_emission_grid_with_a_different_brick_layout():
     _assert_same(r.framebuffer(), ref, "emission grid of another layout, trace() x 6")
 
 
-def _crop_bricks(a, nbc):
-    """Centred sub-block nbc = (cx, cy, cz) of an encode_arrays() brick grid: indirection/range cropped (the atlas pointers stay
-    valid), range mips rebuilt with the ceil(n / 2) rule (min of mins, max of maxes over the existing children)."""
-    nbx, nby, nbz = a["n_bricks"]
-    cx, cy, cz = nbc
-    ox, oy, oz = (nbx - cx) // 2, (nby - cy) // 2, (nbz - cz) // 2          # centred: the synthetic cloud is densest there
-    ind = a["indirection"].reshape(nbz, nby, nbx)[oz:oz + cz, oy:oy + cy, ox:ox + cx].copy()
-    rng = a["rng"].reshape(nbz, nby, nbx)[oz:oz + cz, oy:oy + cy, ox:ox + cx].copy()
-    lo = (rng & 0xFFFF).astype(np.uint16).view(np.float16).astype(np.float32)
-    hi = (rng >> 16).astype(np.uint16).view(np.float16).astype(np.float32)
-    mips = []
-    for _ in range(3):
-        z, y, x = lo.shape
-        z2, y2, x2 = (z + 1) // 2, (y + 1) // 2, (x + 1) // 2
-        plo = np.full((z2 * 2, y2 * 2, x2 * 2), np.inf, np.float32)
-        phi = np.full((z2 * 2, y2 * 2, x2 * 2), -np.inf, np.float32)
-        plo[:z, :y, :x] = lo
-        phi[:z, :y, :x] = hi
-        lo = plo.reshape(z2, 2, y2, 2, x2, 2).min((1, 3, 5))
-        hi = phi.reshape(z2, 2, y2, 2, x2, 2).max((1, 3, 5))
-        w = lo.astype(np.float16).view(np.uint16).astype(np.uint32) | (hi.astype(np.float16).view(np.uint16).astype(np.uint32) << 16)
-        mips.append(((x2, y2, z2), w.reshape(-1)))
-    out = dict(a)
-    out.update(n_bricks=(cx, cy, cz), indirection=ind.reshape(-1), rng=rng.reshape(-1), mips=mips)
-    return out
+_crop_bricks = scenes.crop_bricks
 
 
 def test_dense_fp16_density_with_emission_grid():

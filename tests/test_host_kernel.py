@@ -18,9 +18,14 @@ def _same(a, b):
 def test_state_machine_matches_oracle(name, w, h, spp):
     r = scenes.oracle_scene(name, w, h)
     want = r.render(spp).copy()
+    hk.cfg_steps(reset=True)
     got, steps = hk.render(r, spp)
     assert steps > 0
     assert _same(got, want), "relative L2 %.3e" % scenes.rel_l2(got[..., :3], want[..., :3])
+    # which compiled form of the lane code ran (host_kernel.cpp hk_cfg_steps): smoke.brick without a LUT is served by the brick kernel's own form
+    # TraceCfg<false, 0, 0, 0, 2> (VR_WORLD_SLOT, on by default), with one by the run-time form <true, 2, 2, 2, 2> -- a changed default must not drop either silently
+    brick, dense, general, general_tf = hk.cfg_steps()
+    assert (brick, dense, general, general_tf) == ((0, 0, 0, steps) if name == "c3" else (steps, 0, 0, 0))
 
 
 @pytest.mark.parametrize("name,w,h,spp", [("c1", 64, 64, 16), ("c2", 48, 48, 16)])
@@ -142,9 +147,11 @@ def test_dense_fp16_grid():
     o.cam_fov = 40.0
     o.bounces = 8
     want = o.render(8).copy()
-    got, _ = hk.render(o, 8)
+    hk.cfg_steps(reset=True)
+    got, steps = hk.render(o, 8)
     assert want[..., 3].max() > 0
     assert _same(got, want)
+    assert hk.cfg_steps() == (0, steps, 0, 0)                # the dense kernel's own form, TraceCfg<false, 0, 0, 1, 2>
 
 
 def test_degenerate_inputs_do_not_diverge():

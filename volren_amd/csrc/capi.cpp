@@ -701,6 +701,13 @@ int vr_math_probe(int fn, const float* a, const float* b, float* out, int n) {
     });
 }
 
+int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, long long n) {
+    NEED(r);
+    if (!in || !out || n < 0) return fail(VR_ERR_ARG, "bad arguments");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.probe(what, form, static_cast<const uint32_t*>(in), out, (size_t)n); });
+}
+
 int vr_write_brick_from_dense(const float* voxels, int nx, int ny, int nz, const float* transform, const char* path) {
     if (!voxels || !path || nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_ARG, "bad arguments");
     return guard([&] {

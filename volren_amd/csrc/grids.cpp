@@ -336,6 +336,10 @@ std::shared_ptr<BrickGrid> Volume::to_brick_grid(const GridPtr& grid) {
                                 const float v = at(x, y, z);
                                 lo = std::min(lo, v); hi = std::max(hi, v);
                             }
+                // a zero bound is +0.0: -0.0 and +0.0 compare equal, so which of them a minimum / maximum search ends on depends on the order of the search
+                // (this loop and the device encoder's wavefront reduction differ in it); the range words must not
+                if (lo == 0.f) lo = 0.f;
+                if (hi == 0.f) hi = 0.f;
                 const uint16_t hlo = float_to_half_round_down(lo), hhi = float_to_half_round_up(hi);
                 out->range(bx, by, bz) = (uint32_t)hlo | ((uint32_t)hhi << 16);
                 const float flo = half2float(hlo), fhi = half2float(hhi);
@@ -365,7 +369,7 @@ std::shared_ptr<BrickGrid> Volume::to_brick_grid(const GridPtr& grid) {
                         for (uint32_t x = 0; x < 8; ++x) {
                             const float v = at((int64_t)bx * 8 + x, (int64_t)by * 8 + y, (int64_t)bz * 8 + z);
                             float q = std::floor((v - lo) * inv + 0.5f);
-                            q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);
+                            q = q > 0.f ? (q > 255.f ? 255.f : q) : 0.f;      // clamp to [0, 255]; a NaN (a NaN voxel, or inf in a brick whose range is infinite) becomes a defined 0
                             out->atlas(px * 8 + x, py * 8 + y, pz * 8 + z) = (uint8_t)q;
                         }
             }

@@ -12,6 +12,7 @@
 #include "vr_adaptive.h"
 #include "vr_device.h"
 #include "vr_math.h"
+#include "vr_probe.h"
 
 namespace vr {
 
@@ -853,6 +854,33 @@ void RendererHIP::render_features(int spp) {
     }
     launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, features_->as<float>(), status_->as<uint32_t>(), stream);
     VR_HIP(hipGetLastError());
+}
+
+// Test hook (vr_probe.h).  The scene as the next launch reads it: capture() and the majorant table as submit() / render_features() bring them up to date.  A PAIR form
+// reads the views of the kernel compiled for the paired atlas; every other form the grids' own atlases, as the run-time variant and the feature pass do.
+void RendererHIP::probe(int what, int form, const uint32_t* in, float* out, size_t n) {
+    if (!in || !out) throw std::runtime_error("probe: null array");
+    if (n > (size_t)1 << 28) throw std::runtime_error("probe: more than 2^28 items");
+    flush_pending();
+    LaunchInputs li;
+    capture(li);
+    update_majorants(li, density_grids.at(li.frame));
+    SceneParams P = li.P;
+    if (const char* why = probe_form_error(P, what, form)) throw std::runtime_error(std::string("probe: this scene cannot serve that form: ") + why);
+    if (const char* why = probe_items_error(P, what, form, in, n)) throw std::runtime_error(std::string("probe: bad item: ") + why);
+    if (P.paired && probe_decode_form(what, form).pair == 0) {
+        P.density = make_view(density_grids.at(li.frame), false, P.density.maj_blocked != 0);
+        P.emission = make_view(emission_grids.at(li.frame), false);
+        P.paired = 0;
+    }
+    if (n == 0) return;
+    const size_t in_bytes = n * kProbeInWords * sizeof(uint32_t), out_bytes = n * (size_t)probe_out_words(what) * sizeof(float);
+    DeviceBuffer din(in_bytes), dout(out_bytes);
+    din.upload(in, in_bytes, stream);
+    launch_probe(P, what, form, din.as<uint32_t>(), dout.as<float>(), (uint32_t)n, stream);
+    VR_HIP(hipGetLastError());
+    dout.download(out, out_bytes, stream);
+    VR_HIP(hipStreamSynchronize(stream));
 }
 
 void RendererHIP::download_features(float* out) {

@@ -170,6 +170,10 @@ struct RendererHIP {
     // computed afresh into their own W*H*8 buffer (asynchronous; flushes recorded samples first).  download_features: that buffer, W*H*8 floats.
     // download_variance: the unbiased per-channel variance of samples 1..sample, W*H*4 floats -- needs `variance` on for all of them.
     void render_features(int spp);
+    // test hook (vr_probe.h): n items of probe `what` in compile-time form `form`, host arrays in (4 words per item) and out (probe_out_words floats per item), run by
+    // probe_kernel on the SceneParams the next launch would get -- after capture() (float atlas) and update_majorants, with the paired atlas where a kernel reads it.
+    // Throws for a form the scene cannot serve.  Synchronous; touches no framebuffer.
+    void probe(int what, int form, const uint32_t* in, float* out, size_t n);
     void download_features(float* out);
     void download_variance(float* rgba);
     // Denoiser (vr_denoise.h).  denoise(): the a-trous filter of the current frame, guided by the variance and the last feature pass, into its own W*H*4

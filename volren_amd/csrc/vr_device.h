@@ -97,5 +97,7 @@ void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_ti
 // fn: 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin 9 a/b 10 sqrt 11 fma(a,b,a) 12 float(u8)/255 13 sincos 14 a*b+a 15 half->float
 //     16 rcp_exact(a) 17 rcp3_exact((a, b, a)).y
 void launch_math_probe(int32_t fn, const float* a, const float* b, float* out, int32_t n, hipStream_t stream);
+// unit-test probe of the scene-data lookups (vr_probe.h, vr_probe.hip): n items of 4 words in, probe_out_words(what) floats out
+void launch_probe(const SceneParams& P, int32_t what, int32_t form, const uint32_t* in, float* out, uint32_t n, hipStream_t stream);
 
 }  // namespace vr

@@ -508,6 +508,9 @@ encode_range_kernel(const float* __restrict__ dense, int32_t nx, int32_t ny, int
         lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi;
     }
     if (lane == 0) {
+        // a zero bound is +0.0, as in the host encoder (grids.cpp): which of -0.0 and +0.0 the reduction ends on depends on its order
+        if (lo == 0.0f) lo = 0.0f;
+        if (hi == 0.0f) hi = 0.0f;
         const uint32_t hlo = float_to_half_down(lo), hhi = float_to_half_up(hi);
         range[brick] = hlo | (hhi << 16);
         flag[brick] = half2float(hhi) != half2float(hlo) ? 1u : 0u;
@@ -533,7 +536,7 @@ encode_brick_kernel(const float* __restrict__ dense, int32_t nx, int32_t ny, int
         float v = 0.0f;
         if (x < nx && y < ny && z < nz) v = dense[((size_t)z * ny + y) * nx + x];
         float qv = floor_((v - lo) * inv + 0.5f);
-        qv = qv < 0.0f ? 0.0f : (qv > 255.0f ? 255.0f : qv);
+        qv = qv > 0.0f ? (qv > 255.0f ? 255.0f : qv) : 0.0f;      // clamp to [0, 255]; NaN becomes a defined 0, as in the host encoder (grids.cpp)
         dst[brick_voxel_byte((uint32_t)i)] = (uint8_t)qv;
     }
 }

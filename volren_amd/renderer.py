@@ -228,6 +228,18 @@ class Renderer:
         """float RGB of the framebuffer (bindings.cpp:141-148)."""
         return self.framebuffer()[..., :3].copy()
 
+    # ---- test hook ----
+    PROBE_OUT_WORDS = (1, 1, 1, 1, 3, 3, 7, 4)      # voxel, trilinear, majorant, importance, texel, sky, light sample, transfer function
+
+    def probe(self, what, form, items):
+        """Test hook (include/volren_amd.h vr_probe, volren_amd/csrc/vr_probe.h): `items` is [n][4] 32-bit words (int32, uint32 or float32 -- the bits are passed
+        as they are); returns [n][k] float32 from the device's own accessors in compile-time form `form`, on the scene as the next launch would read it."""
+        items = np.ascontiguousarray(items)
+        assert items.ndim == 2 and items.shape[1] == 4 and items.dtype.itemsize == 4, "items: [n][4] 32-bit words"
+        out = np.empty((items.shape[0], self.PROBE_OUT_WORDS[int(what)]), np.float32)
+        _lib.check(self._L.vr_probe(self._h, int(what), int(form), items.ctypes.data, out.ctypes.data, items.shape[0]))
+        return out
+
     # ---- denoiser data ----
     def render_features(self, spp, sync=True):
         """First-scatter features of samples 1..spp of every pixel (include/volren_amd.h vr_render_features), computed afresh."""
