@@ -176,6 +176,27 @@ int vr_variance(vr_renderer* r, float* rgba_out);
  *     resize. */
 int vr_denoise(vr_renderer* r);
 int vr_denoised(vr_renderer* r, float* rgba_out);
+/* --- temporal accumulation in front of the filter (no reference counterpart; the temporal part of SVGF, reprojected by depth).
+ *     vr_denoise_temporal: as vr_denoise -- the same inputs, the same refusals, whatever vr_denoise accepts -- but the frame is first blended into a
+ *     history of the frames before it, and the filter starts from the blended colour and variance.  The history of a pixel is read where the pixel's
+ *     first-scatter point (the centre ray at the guide's depth; the ray's direction where the pixel shows the environment only) lay on the screen
+ *     of the call before, from up to four bilinear taps that pass a coverage and depth test (relative depth difference <= 0.1); a pixel without such a
+ *     tap starts afresh.  While "cam_pos", the camera's orientation and "cam_fov" are what they were at the call before, every pixel reads its own
+ *     history, unresampled.  Blend: N = min(N + 1, 2^20) frames behind the pixel, a = max("denoise_alpha", 1 / N), C = (1 - a) history + a frame,
+ *     V = (1 - a)^2 V_history + a^2 v.  The arithmetic is specified operation by operation in volren_amd/csrc/vr_temporal.h and reproducible bit for bit.
+ *     Call it once per frame (a second call on the same frame blends the frame with itself), on frames of equal samples per pixel: the blend
+ *     treats frames as equals.  Meant for fixed cameras (animations, progressive refinement) and slow camera paths; see README.md for where it stops paying.
+ *     The history is created by the first call, dropped by vr_resize and vr_denoise_history_reset, and KEPT across vr_reset, vr_set_*, the loaders and
+ *     vr_commit: a sequence is reset, render, render_features, denoise_temporal per frame, and what no longer matches is for the depth and coverage test
+ *     to reject.  vr_denoise neither reads nor writes it.  A device allocation that fails makes the call fail and leaves the last result and the history
+ *     as they were.  The first call gives what vr_denoise gives.  vr_denoised returns the result of whichever of the two calls ran last.
+ *     vr_denoise_history waits and writes the history: the blended colour (W*H*4), the blended variance of the mean's luminance (W*H) and the number of
+ *     frames behind each pixel (W*H), row 0 at the bottom; any pointer may be NULL; VR_ERR while there is no history.
+ *     vr_set_float / vr_get_float "denoise_alpha"(1: the smallest weight of the current frame, in [2^-20, 1]: VR_ERR otherwise, the old value kept;
+ *     default 0.1). */
+int vr_denoise_temporal(vr_renderer* r);
+int vr_denoise_history_reset(vr_renderer* r);
+int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* length_out);
 /* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
  *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
  *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the

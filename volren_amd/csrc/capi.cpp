@@ -371,6 +371,7 @@ FloatField float_field(vr::RendererHIP& R, const std::string& n) {
     if (n == "tf_window_width") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_width, 1 }; }
     if (n == "volume_transform") { if (!R.volume) throw std::runtime_error("no volume"); return { R.volume->transform.m, 16 }; }
     if (n == "denoise_sigma") return { R.denoise_sigma, 5 };
+    if (n == "denoise_alpha") return { &R.denoise_alpha, 1 };
     throw std::runtime_error("unknown float parameter: " + n);
 }
 }  // namespace
@@ -394,6 +395,8 @@ int vr_set_float(vr_renderer* r, const char* name, const float* values, int coun
                 if (!(values[i] >= vr::kDenoiseSigmaMin && values[i] <= vr::kDenoiseSigmaMax))
                     throw std::runtime_error("denoise_sigma: every value must be in [2^-60, 2^60]");
         }
+        if (n == "denoise_alpha" && count == 1 && !(values[0] >= vr::kTemporalAlphaMin && values[0] <= vr::kTemporalAlphaMax))      // vr_temporal.h
+            throw std::runtime_error("denoise_alpha must be in [2^-20, 1]");
         const FloatField f = float_field(R, n);
         if (count != f.count) throw std::runtime_error("wrong value count for " + n);
         memcpy(f.ptr, values, sizeof(float) * (size_t)count);
@@ -466,6 +469,21 @@ int vr_denoise(vr_renderer* r) {
     NEED(r);
     if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
     return guard([&] { use_device(r); r->impl.denoise(); });
+}
+int vr_denoise_temporal(vr_renderer* r) {
+    NEED(r);
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.denoise_temporal(); });
+}
+int vr_denoise_history_reset(vr_renderer* r) {
+    NEED(r);
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.flush_pending(); r->impl.drop_history(); });
+}
+int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* length_out) {
+    NEED(r);
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.download_history(rgba_out, var_out, length_out); });
 }
 int vr_denoised(vr_renderer* r, float* out) {
     NEED(r);

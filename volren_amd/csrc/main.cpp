@@ -7,7 +7,8 @@
 // Addition: --gpus N [--devices a,b,...] renders every frame on N devices (sharded.h: scene replicated, 16x16 tiles dealt diagonally, one
 // grouped ncclAllGather per frame; a device named more than once = logical shards of one GPU, exchanged by device-to-device copies).
 // Addition: --denoise keeps the per-pixel variance, runs the feature pass (min(spp, 16) samples) and the a-trous denoiser (vr_denoise.h) after every
-// frame and writes the tonemapped denoised frame instead of the raw one (one device only).
+// frame and writes the tonemapped denoised frame instead of the raw one (one device only).  --denoise-temporal does the same through
+// denoise_temporal (vr_temporal.h): the history is kept across the frames of the run, so every frame after the first is blended with the ones before it.
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
 // the mean samples per pixel; combines with --denoise (one device only).
 //
@@ -86,7 +87,7 @@ static void parse_cmd(int argc, char** argv) {
     Args a{ argc, argv, 0 };
     for (a.i = 1; a.i < argc; ++a.i) {
         const std::string arg = argv[a.i];
-        if (arg == "--render" || arg == "--denoise") {          // --denoise, --adaptive: main()
+        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal") {      // --denoise, --denoise-temporal, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
@@ -163,7 +164,7 @@ int main(int argc, char** argv) {
         if (arg.size() > 3 && arg.compare(arg.size() - 3, 3, ".py") == 0 && fs::is_regular_file(arg)) return run_python_script(argc, argv);
     }
     int width = 1280, height = 720, device = 0, gpus = 0;        // cppgl ContextParameters defaults (unverified): always pass -w/-h
-    bool denoise = false, adaptive = false;
+    bool denoise = false, temporal = false, adaptive = false;      // temporal: --denoise with the history kept across the frames of the run
     float threshold = 0.f;
     std::vector<int> devices;
     try {
@@ -175,6 +176,7 @@ int main(int argc, char** argv) {
             else if (arg == "--gpus" && i + 1 < argc) gpus = std::stoi(argv[++i]);
             else if (arg == "--devices" && i + 1 < argc) devices = parse_int_list(argv[++i]);
             else if (arg == "--denoise") denoise = true;
+            else if (arg == "--denoise-temporal") denoise = temporal = true;
             else if (arg == "--adaptive") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --adaptive");
                 adaptive = true;
@@ -185,7 +187,7 @@ int main(int argc, char** argv) {
         if (adaptive && (gpus > 0 || devices.size() > 1))
             throw std::runtime_error("--adaptive renders on one device only: drop --gpus / --devices (the sharded renderer has no adaptive sampling)");
         if (denoise && (gpus > 0 || devices.size() > 1))
-            throw std::runtime_error("--denoise renders on one device only: drop --gpus / --devices (the sharded renderer has no denoiser)");
+            throw std::runtime_error(std::string(temporal ? "--denoise-temporal" : "--denoise") + " renders on one device only: drop --gpus / --devices (the sharded renderer has no denoiser)");
         // one renderer per part; without --gpus / --devices: one part on --device, the reference's single-context loop
         if (devices.empty()) {
             if (gpus <= 1) devices = { device };
@@ -258,7 +260,8 @@ int main(int argc, char** argv) {
             renderer->tonemapping = true;               // the offline loop always tonemaps (main.cpp:540-550)
             if (denoise) {
                 renderer->render_features(std::min(renderer->sppx, 16));
-                renderer->denoise();
+                if (temporal) renderer->denoise_temporal();      // the first frame: what denoise() gives
+                else renderer->denoise();
                 renderer->synchronize();
                 if (renderer->watchdog_status()) throw std::runtime_error("feature pass: a camera segment exceeded its step budget");
                 renderer->draw_from(*renderer->denoised());

@@ -60,6 +60,7 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     features_.reset();
     moments_.reset(); moments_n_ = -1;
     dn_guide_.reset(); dn_var_[0].reset(); dn_var_[1].reset(); dn_color_[0].reset(); dn_color_[1].reset(); denoised_.reset();
+    drop_history();
     drop_tile_samples(); tile_n_dev_.reset(); adaptive_lists_.reset(); adaptive_err_.reset();
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
@@ -349,6 +350,9 @@ static GridView make_view(const BrickGridHIP& g, bool paired = false, bool maj_b
     return v;
 }
 
+// cam_z of the uniform block (common.glsl:78); the temporal denoiser compares cameras byte for byte, so there is one expression for it
+static float camera_z(float fov_degree) { return -0.5f / tan_(0.5f * kPi * fov_degree / 180.f); }
+
 void RendererHIP::fill_params(SceneParams& P) {
     if (!volume || volume->grids.empty() || density_grids.empty())
         throw std::runtime_error("RendererHIP::trace: no volume committed");
@@ -364,7 +368,7 @@ void RendererHIP::fill_params(SceneParams& P) {
     u.cam_fov = camera.fov_degree;
     const mat3 ct = camera.view_inverse();
     memcpy(u.cam_transform, ct.m, sizeof ct.m);
-    P.cam_z = -0.5f / tan_(0.5f * kPi * camera.fov_degree / 180.f);
+    P.cam_z = camera_z(camera.fov_degree);
     // volume
     const auto [bb_min, bb_max] = volume->AABB();
     const auto [mn, maj] = volume->minorant_majorant();
@@ -919,26 +923,35 @@ void RendererHIP::download_variance(float* rgba) {
 // The a-trous denoiser (vr_denoise.h) on whole frames: prepare (variance of the mean, guide) once, then `denoise_iterations` passes at steps
 // 1, 2, 4, ...  Iteration 0 reads the framebuffer itself; colour and variance ping-pong between buffers of their own, and the last iteration
 // writes `denoised_` (N = 0: a copy of the framebuffer).
-void RendererHIP::denoise() {
+// temporal (denoise_temporal, vr_temporal.h): between prepare and the iterations the frame is blended with the history, and the iterations start
+// from the new history's colour and variance instead.  Every buffer the call needs is allocated before its first launch, so a failed allocation
+// leaves the last result and the history as they were.
+void RendererHIP::denoise() { run_denoise("denoise", false); }
+void RendererHIP::denoise_temporal() { run_denoise("denoise_temporal", true); }
+
+void RendererHIP::run_denoise(const char* who, bool temporal) {
     flush_pending();
-    if (!tiles_host_.empty()) throw std::runtime_error("denoise: a tile subset is set (set_tiles); the filter needs every pixel's neighbours and runs on whole frames only");
-    if (!features_) throw std::runtime_error("denoise: no feature pass since the last resize (call render_features first)");
-    if (sample < 1) throw std::runtime_error("denoise: the framebuffer holds no samples (sample < 1)");
-    check_moments("denoise");
+    const std::string me = std::string(who) + ": ";
+    if (!tiles_host_.empty()) throw std::runtime_error(me + "a tile subset is set (set_tiles); the filter needs every pixel's neighbours and runs on whole frames only");
+    if (!features_) throw std::runtime_error(me + "no feature pass since the last resize (call render_features first)");
+    if (sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
+    check_moments(who);
     const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
     if (ragged()) {
         for (int32_t c : tile_n_)
-            if (c < 1) throw std::runtime_error("denoise: a tile of the frame holds no samples (sample < 1 there: render_adaptive over a tile subset from sample 0)");
+            if (c < 1) throw std::runtime_error(me + "a tile of the frame holds no samples (sample < 1 there: render_adaptive over a tile subset from sample 0)");
         const size_t bytes = tile_n_.size() * sizeof(int32_t);
         if (!tile_n_dev_ || tile_n_dev_->size_bytes() != bytes) tile_n_dev_ = make_device_buffer(bytes);
         tile_n_dev_->upload(tile_n_.data(), bytes, stream);
         counts = tile_n_dev_->as<int32_t>();
     }
     const int32_t W = resolution.x, H = resolution.y, N = denoise_iterations;
-    if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error("denoise: frame too large (32-bit pixel indices)");
-    if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error("denoise: denoise_iterations out of range");
+    if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error(me + "frame too large (32-bit pixel indices)");
+    if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error(me + "denoise_iterations out of range");
     const size_t px = (size_t)W * H;
     auto ensure = [&](DeviceBufferPtr& b, size_t bytes) { if (!b || b->size_bytes() != bytes) b = make_device_buffer(bytes); };
+    const int to = hist_cur_ < 0 ? 0 : 1 - hist_cur_;      // the half of the history pair this call writes
+    if (temporal) { ensure(hist_color_[to], px * 4 * sizeof(float)); ensure(hist_record_[to], px * 4 * sizeof(float)); }
     ensure(dn_guide_, px * 8 * sizeof(float));
     ensure(dn_var_[0], px * sizeof(float));
     ensure(denoised_, px * 4 * sizeof(float));
@@ -947,17 +960,54 @@ void RendererHIP::denoise() {
     const float vscale = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;      // download_variance's factor
     launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, counts, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
     VR_HIP(hipGetLastError());
+    const DeviceBuffer* first = color.get();          // what iteration 0 reads
+    if (temporal) {
+        TemporalCamera cur;
+        memset(&cur, 0, sizeof cur);
+        copy3(cur.pos, camera.pos);
+        const mat3 ct = camera.view_inverse();
+        memcpy(cur.m, ct.m, sizeof ct.m);
+        cur.cam_z = camera_z(camera.fov_degree);
+        const bool have = hist_cur_ >= 0;
+        const bool same = have && memcmp(&cur, &hist_cam_, sizeof cur) == 0;
+        launch_denoise_temporal(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), have ? hist_color_[hist_cur_]->as<float>() : nullptr,
+                                have ? hist_record_[hist_cur_]->as<float>() : nullptr, same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha,
+                                hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
+        VR_HIP(hipGetLastError());
+        hist_cur_ = to;
+        hist_cam_ = cur;
+        first = hist_color_[to].get();
+    }
     if (N == 0) {
-        VR_HIP(hipMemcpyAsync(denoised_->get(), color->get(), color->size_bytes(), hipMemcpyDeviceToDevice, stream));
+        VR_HIP(hipMemcpyAsync(denoised_->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
         return;
     }
     const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
     for (int32_t k = 0; k < N; ++k) {
-        const float* cin = k == 0 ? color->as<float>() : dn_color_[(k - 1) & 1]->as<float>();
+        const float* cin = k == 0 ? first->as<float>() : dn_color_[(k - 1) & 1]->as<float>();
         float* cout = k == N - 1 ? denoised_->as<float>() : dn_color_[k & 1]->as<float>();
         float* vout = k == N - 1 ? nullptr : dn_var_[(k + 1) & 1]->as<float>();
         launch_denoise_atrous(cin, dn_var_[k & 1]->as<float>(), dn_guide_->as<float>(), W, H, 1 << k, sg, cout, vout, stream);
         VR_HIP(hipGetLastError());
+    }
+}
+
+void RendererHIP::drop_history() {
+    hist_color_[0].reset(); hist_color_[1].reset(); hist_record_[0].reset(); hist_record_[1].reset();
+    hist_cur_ = -1;
+}
+
+void RendererHIP::download_history(float* rgba, float* var, float* length) {
+    if (hist_cur_ < 0) throw std::runtime_error("denoise_history: no history (no denoise_temporal since the last resize or history reset)");
+    flush_pending();
+    if (rgba) hist_color_[hist_cur_]->download(rgba, hist_color_[hist_cur_]->size_bytes(), stream);
+    if (!var && !length) return;
+    const size_t px = (size_t)resolution.x * resolution.y;
+    std::vector<float> rec(px * 4);
+    hist_record_[hist_cur_]->download(rec.data(), rec.size() * sizeof(float), stream);
+    for (size_t i = 0; i < px; ++i) {
+        if (var) var[i] = rec[4 * i];
+        if (length) length[i] = rec[4 * i + 1];
     }
 }
 

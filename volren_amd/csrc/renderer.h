@@ -149,6 +149,7 @@ struct RendererHIP {
     int denoise_iterations = kDenoiseDefaultIterations;   // a-trous iterations of denoise() (0..kDenoiseMaxIterations; 0 = the colour unchanged)
     float denoise_sigma[5] = { kDenoiseDefaultSigma[0], kDenoiseDefaultSigma[1], kDenoiseDefaultSigma[2], kDenoiseDefaultSigma[3], kDenoiseDefaultSigma[4] };
                                                       // edge-stopping widths: colour, normal, depth, coverage, albedo (vr_denoise.h)
+    float denoise_alpha = kTemporalDefaultAlpha;      // smallest weight of the current frame in denoise_temporal()'s blend, in [2^-20, 1] (vr_temporal.h)
     bool fast_math = false;                           // opt-in tolerance mode: hardware log/sin/cos/rcp instead of the specified arithmetic
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
                                                       // with one bound the renderer refuses it: DESIGN.md 3)
@@ -179,7 +180,14 @@ struct RendererHIP {
     // Denoiser (vr_denoise.h).  denoise(): the a-trous filter of the current frame, guided by the variance and the last feature pass, into its own W*H*4
     // buffer (asynchronous; flushes recorded samples first).  Needs render_features since the last resize, `variance` on for samples 1..sample, sample >= 1
     // and no tile subset.  download_denoised: that buffer, W*H*4 floats.  The framebuffer, moments, features and display are not touched.
+    // denoise_temporal() (vr_temporal.h): the same, with the frame first blended into a history of the frames before it, reprojected by the guide's
+    // depth from the camera of the call before (once per frame; frames of equal spp).  Whatever denoise() accepts, this accepts.  The history is created
+    // by the first call, dropped by resize and drop_history, and kept across everything else; denoise() neither reads nor writes it.
+    // download_history: integrated colour W*H*4, integrated variance W*H, length W*H (any may be null); throws while there is no history.
     void denoise();
+    void denoise_temporal();
+    void drop_history();
+    void download_history(float* rgba, float* var, float* length);
     void download_denoised(float* rgba);
     const DeviceBuffer* denoised() const { return denoised_.get(); }
     // copy + tonemap of a W*H*4 buffer into `display` (draw() = draw_from(*color) after the flush)
@@ -251,7 +259,11 @@ private:
     int moments_n_ = -1;                               // the moments cover samples 1..moments_n_ (-1: they do not start at sample 1)
     void check_moments(const char* who);               // throws unless the moments cover samples 1..sample (of every tile, on a ragged frame)
     DeviceBufferPtr dn_guide_, dn_var_[2], dn_color_[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4 (dropped by resize)
-    DeviceBufferPtr denoised_;                         // W*H*4: the last denoise()'s result (dropped by resize)
+    DeviceBufferPtr denoised_;                         // W*H*4: the last denoise()'s or denoise_temporal()'s result (dropped by resize)
+    void run_denoise(const char* who, bool temporal);  // the body of both
+    DeviceBufferPtr hist_color_[2], hist_record_[2];   // denoise_temporal(): the history, a ping-pong pair of W*H*4 colours and W*H*4 (V, N, K, D) records
+    int hist_cur_ = -1;                                // the half that holds the history (-1: none)
+    TemporalCamera hist_cam_{};                        // the camera of the frame that wrote it
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     std::vector<hipEvent_t> pt_events_;                // (begin, end) around the path-tracing kernel of every sub-launch
     size_t pt_events_used_ = 0;

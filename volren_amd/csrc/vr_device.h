@@ -6,6 +6,7 @@
 
 #include "vr_denoise.h"
 #include "vr_scene.h"
+#include "vr_temporal.h"
 
 namespace vr {
 
@@ -45,6 +46,12 @@ void launch_denoise_prepare(const float* moments, const float* features, int32_t
                             hipStream_t stream);
 void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
                            float* cout, float* vout, hipStream_t stream);
+// Temporal accumulation (vr_temporal.h), between prepare and the iterations: blends (color W*H*4, v W*H, guide) with the history (hist_color W*H*4,
+// hist_record W*H*4 = (V, N, K, D); both nullptr: no history yet) seen from camera `prev`, writes the new history into out_color / out_record
+// (not the buffers read) and the integrated variance over v.  same_cam: `cur` equals `prev` byte for byte (no reprojection).
+void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
+                             const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
+                             hipStream_t stream);
 // Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,

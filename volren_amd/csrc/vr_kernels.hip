@@ -24,6 +24,7 @@
 
 #include "vr_adaptive.h"
 #include "vr_denoise.h"
+#include "vr_temporal.h"
 #include "vr_device.h"
 #include "vr_pathtrace.h"
 
@@ -208,6 +209,46 @@ void launch_denoise_prepare(const float* moments, const float* features, int32_t
     if (W <= 0 || H <= 0) return;
     hipLaunchKernelGGL(denoise_prepare_kernel, dim3(denoise_blocks(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(moments),
                        reinterpret_cast<const float4*>(features), W, H, n, vscale, counts, v, reinterpret_cast<float4*>(guide));
+}
+
+// Temporal accumulation (vr_temporal.h temporal_pixel), between prepare and the iterations: one thread per pixel, laid out like the kernels above.
+// Reads the pixel's colour, v and the guide's coverage and depth (52 B), gathers up to four taps of the previous history -- a tap is two dwordx4:
+// the colour and (V, N, K, D), fetched only after the tap was found inside the frame -- and writes the pixel's new history (32 B) into the other
+// half of the ping-pong pair, plus V over the pixel's own v, where the iterations read it.  No LDS, no atomics; the only loops are the 2 x 2 taps.
+struct TemporalHistDev {
+    const float4* __restrict__ c;
+    const float4* __restrict__ s;
+    __device__ __forceinline__ void color(int32_t i, float o[4]) const { const float4 x = c[i]; o[0] = x.x; o[1] = x.y; o[2] = x.z; o[3] = x.w; }
+    __device__ __forceinline__ void record(int32_t i, float o[4]) const { const float4 x = s[i]; o[0] = x.x; o[1] = x.y; o[2] = x.z; o[3] = x.w; }
+};
+__global__ void __launch_bounds__(256)
+denoise_temporal_kernel(const float4* __restrict__ color, float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ hc,
+                        const float4* __restrict__ hs, int32_t have, int32_t same_cam, const TemporalCamera cur, const TemporalCamera prev, int32_t W, int32_t H,
+                        float alpha, float4* __restrict__ oc, float4* __restrict__ os) {
+    const int32_t tiles_x = (W + 15) >> 4;
+    const int32_t tile = (int32_t)blockIdx.x;
+    const int32_t wave = threadIdx.x >> 6, p = threadIdx.x & 63;
+    const int32_t px = (tile % tiles_x) * 16 + ((wave & 1) << 3) + (p & 7);
+    const int32_t py = (tile / tiles_x) * 16 + ((wave >> 1) << 3) + (p >> 3);
+    if (px >= W || py >= H) return;
+    const int32_t i = py * W + px;
+    const float4 c4 = color[i];
+    const float c[4] = { c4.x, c4.y, c4.z, c4.w };
+    const TemporalHistDev hist{ hc, hs };
+    float C[4], S[4];
+    temporal_pixel(hist, have != 0, same_cam != 0, cur, prev, W, H, px, py, c, v[i], guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S);
+    oc[i] = make_float4(C[0], C[1], C[2], C[3]);
+    os[i] = make_float4(S[0], S[1], S[2], S[3]);
+    v[i] = S[0];
+}
+void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
+                             const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
+                             hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    const bool have = hist_color && hist_record;
+    hipLaunchKernelGGL(denoise_temporal_kernel, dim3(denoise_blocks(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
+                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
+                       have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
 }
 
 // Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile with accumulate_kernel's pixel mapping (four 8x8

@@ -12,7 +12,7 @@ _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemap
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
-                 "volume_transform": 16, "denoise_sigma": 5}
+                 "volume_transform": 16, "denoise_sigma": 5, "denoise_alpha": 1}
 
 
 def _f32(a):
@@ -267,8 +267,27 @@ class Renderer:
         if sync:
             self.synchronize()
 
+    def denoise_temporal(self, sync=True):
+        """denoise() with the frame first blended into the history of the frames before it, reprojected by depth (include/volren_amd.h
+        vr_denoise_temporal): once per frame, frames of equal spp; `denoise_alpha` is the smallest weight of the current frame."""
+        _lib.check(self._L.vr_denoise_temporal(self._h))
+        if sync:
+            self.synchronize()
+
+    def denoise_history(self):
+        """(colour [H][W][4], variance [H][W], length [H][W]) float32, row 0 = bottom: the history denoise_temporal() keeps."""
+        c = np.empty((self.height, self.width, 4), np.float32)
+        v = np.empty((self.height, self.width), np.float32)
+        n = np.empty((self.height, self.width), np.float32)
+        _lib.check(self._L.vr_denoise_history(self._h, c.ctypes.data, v.ctypes.data, n.ctypes.data))
+        return c, v, n
+
+    def denoise_history_reset(self):
+        """Drops the history: the next denoise_temporal() starts afresh."""
+        _lib.check(self._L.vr_denoise_history_reset(self._h))
+
     def denoised(self):
-        """[H][W][4] float32, row 0 = bottom: the last denoise()'s result, linear (not tonemapped)."""
+        """[H][W][4] float32, row 0 = bottom: the last denoise()'s or denoise_temporal()'s result, linear (not tonemapped)."""
         out = np.empty((self.height, self.width, 4), np.float32)
         _lib.check(self._L.vr_denoised(self._h, out.ctypes.data))
         return out

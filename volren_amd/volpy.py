@@ -549,8 +549,17 @@ class Renderer:
         """The a-trous filter of the current frame, guided by its variance and the last render_features (volren_amd.Renderer.denoise)."""
         self._r.denoise()
 
+    def denoise_temporal(self):
+        """denoise() with the frame first blended into the history of the frames before it, reprojected by depth: once per frame, frames of
+        equal spp (volren_amd.Renderer.denoise_temporal)."""
+        self._r.denoise_temporal()
+
+    def denoise_history_reset(self):
+        """Drops the history of denoise_temporal(): the next call starts afresh."""
+        self._r.denoise_history_reset()
+
     def denoised_data(self):
-        """(w, h, 3) float: the denoised colour, in fbo_data()'s shape."""
+        """(w, h, 3) float: the colour of the last denoise() or denoise_temporal(), in fbo_data()'s shape."""
         return self._r.denoised()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
 
     # -- adaptive sampling (no reference counterpart): like render(), from sample 0
