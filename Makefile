@@ -10,7 +10,7 @@ HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 OBJDIR   := build
 SRCS_CPP := grids.cpp imageio.cpp environment.cpp transferfunc.cpp renderer.cpp sharded.cpp capi.cpp
 PT_VARIANTS := 0 1 2 3 4
-OBJS     := $(OBJDIR)/vr_kernels.o $(OBJDIR)/vr_probe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
+OBJS     := $(OBJDIR)/vr_kernels.o $(OBJDIR)/vr_probe.o $(OBJDIR)/vr_fastprobe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
 # tolerance-mode kernels (opt-in, vr_math.h VR_FAST_MATH): hardware transcendentals, reciprocal division, contraction allowed
 FASTFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-hip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Wno-unused-result -Iinclude -DVR_FAST_MATH=1
 # path-tracing kernels: no SLP vectorisation.  On gfx950 a packed fp32 instruction (v_pk_mul/add/fma_f32) occupies the SIMD for
@@ -29,6 +29,11 @@ $(OBJDIR)/vr_kernels.o: $(CSRC)/vr_kernels.hip $(HDRS)
 $(OBJDIR)/vr_probe.o: $(CSRC)/vr_probe.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# test hook: the tolerance-mode forms of vr_math.h as functions (vr_fastprobe.hip), built like the vr_ptfast_* objects
+$(OBJDIR)/vr_fastprobe.o: $(CSRC)/vr_fastprobe.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(FASTFLAGS) -c $< -o $@
 
 # the path-tracing kernel, one compilation per variant (vr_pathtrace.hip); resource usage goes to build/*.resources.txt
 $(OBJDIR)/vr_pathtrace_%.o: $(CSRC)/vr_pathtrace.hip $(HDRS)

@@ -289,6 +289,9 @@ int vr_wave_timeline(vr_renderer* r, unsigned long long* out, int n_words);
 int vr_test_alloc_cap_mb(long long mb);
 /* unit-test probe of the device math (volren_amd/csrc/vr_math.h): host arrays in/out */
 int vr_math_probe(int fn, const float* a, const float* b, float* out, int n);
+/* test hook: the same probe over a range of bit patterns, out[i] = f(bits(first + i), b) (first + i wraps modulo 2^32); one launch, count <= 2^26.
+ * fn: volren_amd/csrc/vr_math_probe.h (17 has no sweep form); 100..103: the tolerance-mode forms of neg_log_1m (of the draw (first + i) 2^-24), sincos_ (sine, cosine), unorm8 (of (first + i) & 255) */
+int vr_math_sweep(int fn, uint32_t first, long long count, float b, float* out);
 /* test hook: unit-test probe of the scene-data lookups (volren_amd/csrc/vr_probe.h): n items of probe `what` (0 voxel, 1 trilinear, 2 majorant, 3 importance,
  * 4 texel, 5 sky, 6 light sample, 7 transfer function) in compile-time form `form`, on the scene as the renderer's next launch would read it.  in: 4 32-bit words per
  * item; out: 1, 1, 1, 1, 3, 3, 7, 4 floats per item; host arrays.  VR_ERR_RUNTIME for a form the scene cannot serve (the message says why). */

@@ -133,6 +133,12 @@ def lib():
     L.orc_math.argtypes = [c_i, c_f, c_f]
     L.orc_math.restype = c_f
     L.orc_num_threads.restype = c_i
+    L.orc_math_is_int.argtypes = L.orc_math_known.argtypes = [c_i]
+    L.orc_math_batch.argtypes = [c_i, C.c_void_p, C.c_void_p, C.c_void_p, c_i64]
+    L.orc_math_compare.argtypes = [c_i, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]
+    L.orc_math_compare.restype = c_i64
+    L.orc_math_sweep_compare.argtypes = [c_i, c_u, c_i64, c_u, C.c_void_p, C.c_void_p]
+    L.orc_math_sweep_compare.restype = c_i64
     _lib = L
     return L
 
@@ -453,3 +459,66 @@ class OracleRenderer:
         out = self.fb.copy()
         lib().orc_tonemap(fptr(out), self.w, self.h, self.tonemap_exposure, self.tonemap_gamma)
         return out
+
+
+# ---- the math probe table (volren_oracle.h): operands and results are float32 arrays whose BITS matter (integer ones viewed as float32) ---------
+def _u32(a):
+    a = np.ascontiguousarray(a)
+    assert a.dtype.itemsize == 4, a.dtype
+    return a.view(np.uint32).reshape(-1)
+
+
+def _pair(a, b):
+    a = _u32(a)
+    if b is None:
+        return a, None
+    b = _u32(b)
+    if b.size == 1 and a.size != 1:
+        b = np.full(a.size, b[0], np.uint32)
+    assert b.size == a.size
+    return a, b
+
+
+class MathMismatch(object):
+    """count mismatches and (index or input bits, got bits, want bits) of the first eight"""
+
+    def __init__(self, fn, count, bad, what):
+        self.fn, self.count, self.what = fn, int(count), what
+        self.examples = [tuple(int(v) for v in bad[3 * k:3 * k + 3]) for k in range(min(self.count, 8))]
+
+    def __bool__(self):
+        return self.count != 0
+
+    def __str__(self):
+        return "math fn %d: %d results differ from the oracle; first %s, got, want: %s" % (
+            self.fn, self.count, self.what, ", ".join("(0x%08x, 0x%08x, 0x%08x)" % e for e in self.examples))
+
+
+def math_batch(fn, a, b=None):
+    a, b = _pair(a, b)
+    out = np.empty(a.size, np.uint32)
+    if lib().orc_math_batch(int(fn), a.ctypes.data, b.ctypes.data if b is not None else None, out.ctypes.data, a.size) != 0:
+        raise ValueError("the oracle has no math function %d" % fn)
+    return out
+
+
+def math_compare(fn, a, b, got):
+    a, b = _pair(a, b)
+    got = _u32(got)
+    assert got.size == a.size
+    bad = np.zeros(24, np.int64)
+    n = lib().orc_math_compare(int(fn), a.ctypes.data, b.ctypes.data if b is not None else None, got.ctypes.data, a.size, bad.ctypes.data)
+    if n < 0:
+        raise ValueError("the oracle has no math function %d" % fn)
+    return MathMismatch(fn, n, bad, "index")
+
+
+def math_sweep_compare(fn, first, count, got, b=0.0):
+    got = _u32(got)
+    assert got.size >= count
+    bad = np.zeros(24, np.int64)
+    bbits = int(np.array([b], np.float32).view(np.uint32)[0])
+    n = lib().orc_math_sweep_compare(int(fn), int(first) & 0xFFFFFFFF, int(count), bbits, got.ctypes.data, bad.ctypes.data)
+    if n < 0:
+        raise ValueError("the oracle has no math function %d" % fn)
+    return MathMismatch(fn, n, bad, "input bits")

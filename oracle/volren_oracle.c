@@ -1171,3 +1171,138 @@ float orc_math(int32_t fn, float a, float b) {
     default: return NAN;
     }
 }
+
+/* ---- the math probe table (volren_amd/csrc/vr_math_probe.h), stated from oracle_math.h and plain C ---------------------------------------
+ * Integer operands travel as the bit pattern of a float, integer results as the returned bit pattern.  Where oracle_math.h has no function of
+ * the same name the identity the product's header states is the reference: sincos_ = (om_sin, om_cos), neg_log_1m(xi) = -om_log(1 - xi),
+ * log_unit_ = om_log, round_mip / round_mip_q = om_round_half_even. */
+static uint32_t half_towards(float f, int up_in_magnitude) {          /* binary16 neighbour of a finite f, by floor / ceil of the scaled magnitude */
+    const uint32_t sign = (om_f2u(f) >> 16) & 0x8000u;
+    const float a = fabsf(f);
+    if (a > 65504.0f) return sign | (up_in_magnitude ? 0x7C00u : 0x7BFFu);
+    float q; uint32_t base;
+    if (a < 6.103515625e-05f) { q = a * 16777216.0f; base = 0u; }                  /* below 2^-14: multiples of 2^-24 */
+    else {
+        const int e = (int)(om_f2u(a) >> 23) - 127;                                 /* -14 .. 15 */
+        q = a * om_u2f((uint32_t)(10 - e + 127) << 23) - 1024.0f; base = (uint32_t)(e + 15) << 10;
+    }
+    q = up_in_magnitude ? ceilf(q) : floorf(q);
+    return sign | (base + (uint32_t)q);                                              /* q == 1024 carries into the exponent */
+}
+static uint32_t half_rne(float f) {
+    const uint32_t sign = (om_f2u(f) >> 16) & 0x8000u;
+    const float a = fabsf(f);
+    if (f != f) return sign | 0x7E00u;
+    if (a >= 65520.0f) return sign | 0x7C00u;
+    if (a < 6.103515625e-05f) return sign | (uint32_t)rintf(a * 16777216.0f);        /* rintf: to nearest, ties to even (default rounding mode) */
+    const int e = (int)(om_f2u(a) >> 23) - 127;
+    return sign | (((uint32_t)(e + 15) << 10) + (uint32_t)(rintf(a * om_u2f((uint32_t)(10 - e + 127) << 23)) - 1024.0f));
+}
+static uint32_t half_dir(float f, int up) {                           /* largest half <= f (up = 0) or smallest half >= f (up = 1) */
+    if (f != f) return half_rne(f);
+    if (fabsf(f) == INFINITY) return f > 0.0f ? 0x7C00u : 0xFC00u;
+    const int negative = (int)(om_f2u(f) >> 31);
+    return half_towards(f, up ? !negative : negative);
+}
+int32_t orc_math_is_int(int32_t fn) { return (fn >= 22 && fn <= 26) || (fn >= 33 && fn <= 36); }
+int32_t orc_math_known(int32_t fn) { return fn >= 0 && fn <= 37 && fn != 12 && fn != 17; }
+static inline uint32_t math_bits(int32_t fn, float a, float b) {
+    const int32_t ib = (int32_t)om_f2u(b);
+    switch (fn) {
+    case 0: return om_f2u(om_log(a));
+    case 1: return om_f2u(om_sin(a));
+    case 2: return om_f2u(om_cos(a));
+    case 3: return om_f2u(om_tan(a));
+    case 4: return om_f2u(om_acos(a));
+    case 5: return om_f2u(om_atan2(a, b));
+    case 6: return om_f2u(om_exp(a));
+    case 7: return om_f2u(om_pow(a, b));
+    case 8: return om_f2u(om_asin(a));
+    case 9: return om_f2u(a / b);
+    case 10: return om_f2u(sqrtf(a));
+    case 11: return om_f2u(fmaf(a, b, a));
+    case 13: return om_f2u(om_sin(a) * b + om_cos(a));
+    case 14: return om_f2u(a * b + a);
+    case 15: return om_f2u(om_half2float((uint16_t)om_f2u(a)));
+    case 16: return om_f2u(1.0f / a);
+    case 18: return om_f2u(om_sin(a));
+    case 19: return om_f2u(om_cos(a));
+    case 20: return om_f2u(-om_log(1.0f - a));
+    case 21: return om_f2u(om_log(a));
+    case 22: return (uint32_t)om_floor2i(a);
+    case 23: { const int32_t v = (!(a >= -2147483648.0f && a < 2147483648.0f)) ? INT32_MIN : (int32_t)a;
+               return v == INT32_MIN ? (uint32_t)INT32_MIN : (uint32_t)v + (uint32_t)ib; }
+    case 24: return (uint32_t)om_round_half_even(a);
+    case 25: return (uint32_t)om_round_half_even((float)(int32_t)om_f2u(a) * 0.25f);
+    case 26: return (uint32_t)om_round_half_even(a);
+    case 27: return om_f2u(om_scale2(a, ib));
+    case 28: return om_f2u((isnan(a) || isinf(a)) ? 0.0f : a);
+    case 29: return om_f2u(om_min(a, b));
+    case 30: return om_f2u(om_max(a, b));
+    case 31: return om_f2u(om_clamp(a, b, 1.0f));
+    case 32: return om_f2u(om_clamp(a, 0.0f, b));
+    case 33: return half_rne(a);
+    case 34: return half_dir(a, 0);
+    case 35: return half_dir(a, 1);
+    case 36: return om_f2u(a) * om_f2u(b);
+    case 37: return om_f2u((float)(om_f2u(a) & 255u) / 255.0f);
+    default: return 0x7FC00000u;
+    }
+}
+/* does `got` count as the oracle's `want`?  floats: same bits, or both NaN; integers: same bits.  voxel_index (23) is held to the property its
+ * header states: the host's index wherever that lies in [0, 2^30), any negative or >= 2^30 value elsewhere; a NaN coordinate is the caller's. */
+static inline int math_same(int32_t fn, float a, uint32_t got, uint32_t want) {
+    if (fn == 23) {
+        if (a != a) return 1;
+        if ((int32_t)want >= 0 && want < (1u << 30)) return got == want;
+        return (int32_t)got < 0 || got >= (1u << 30);
+    }
+    if (got == want) return 1;
+    if (orc_math_is_int(fn)) return 0;
+    return (got & 0x7FFFFFFFu) > 0x7F800000u && (want & 0x7FFFFFFFu) > 0x7F800000u;
+}
+int32_t orc_math_batch(int32_t fn, const uint32_t* a, const uint32_t* b, uint32_t* out, int64_t n) {
+    if (!orc_math_known(fn)) return -1;
+    _Pragma("omp parallel for schedule(static)")
+    for (int64_t i = 0; i < n; ++i) out[i] = math_bits(fn, om_u2f(a[i]), om_u2f(b ? b[i] : 0u));
+    return 0;
+}
+/* got[i] against f(a[i], b[i]) (b may be NULL: 0).  Returns the number of mismatches, -1 for an unknown code; bad[3 k ..]: index, got, want of the first eight */
+int64_t orc_math_compare(int32_t fn, const uint32_t* a, const uint32_t* b, const uint32_t* got, int64_t n, int64_t* bad) {
+    if (!orc_math_known(fn)) return -1;
+    int64_t count = 0;
+    _Pragma("omp parallel for schedule(static) reduction(+:count)")
+    for (int64_t i = 0; i < n; ++i) {
+        const float x = om_u2f(a[i]);
+        count += !math_same(fn, x, got[i], math_bits(fn, x, om_u2f(b ? b[i] : 0u)));
+    }
+    if (count && bad) {
+        int k = 0;
+        for (int64_t i = 0; i < n && k < 8; ++i) {
+            const float x = om_u2f(a[i]);
+            const uint32_t want = math_bits(fn, x, om_u2f(b ? b[i] : 0u));
+            if (!math_same(fn, x, got[i], want)) { bad[3 * k] = i; bad[3 * k + 1] = got[i]; bad[3 * k + 2] = want; ++k; }
+        }
+    }
+    return count;
+}
+/* the same in place over a range of bit patterns: got[i] against f(bits(first + i), bits(b)); bad[3 k ..]: input bits, got, want */
+int64_t orc_math_sweep_compare(int32_t fn, uint32_t first, int64_t n, uint32_t b, const uint32_t* got, int64_t* bad) {
+    if (!orc_math_known(fn)) return -1;
+    const float y = om_u2f(b);
+    int64_t count = 0;
+    _Pragma("omp parallel for schedule(static) reduction(+:count)")
+    for (int64_t i = 0; i < n; ++i) {
+        const float x = om_u2f(first + (uint32_t)i);
+        count += !math_same(fn, x, got[i], math_bits(fn, x, y));
+    }
+    if (count && bad) {
+        int k = 0;
+        for (int64_t i = 0; i < n && k < 8; ++i) {
+            const float x = om_u2f(first + (uint32_t)i);
+            const uint32_t want = math_bits(fn, x, y);
+            if (!math_same(fn, x, got[i], want)) { bad[3 * k] = (int64_t)(first + (uint32_t)i); bad[3 * k + 1] = got[i]; bad[3 * k + 2] = want; ++k; }
+        }
+    }
+    return count;
+}

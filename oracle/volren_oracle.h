@@ -170,6 +170,15 @@ void     orc_batch_light(const orc_params* p, const orc_scene* s, const uint32_t
 void     orc_batch_tf(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
 float    orc_math(int32_t fn, float a, float b);   /* 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin */
 int32_t  orc_num_threads(void);
+/* the product's math probe table (volren_amd/csrc/vr_math_probe.h, codes 0..37 without 12 and 17) from oracle_math.h; operands and results as bit
+ * patterns; b may be NULL (0).  The compare forms return the number of elements of got[] that differ from the oracle (floats: any NaN equals any
+ * NaN; integer results: never; voxel_index: the property its header states), -1 for an unknown code, and fill bad[24] with
+ * (index or input bits, got, want) of the first eight. */
+int32_t  orc_math_is_int(int32_t fn);
+int32_t  orc_math_known(int32_t fn);
+int32_t  orc_math_batch(int32_t fn, const uint32_t* a, const uint32_t* b, uint32_t* out, int64_t n);
+int64_t  orc_math_compare(int32_t fn, const uint32_t* a, const uint32_t* b, const uint32_t* got, int64_t n, int64_t* bad);
+int64_t  orc_math_sweep_compare(int32_t fn, uint32_t first, int64_t n, uint32_t b, const uint32_t* got, int64_t* bad);
 
 #ifdef __cplusplus
 }

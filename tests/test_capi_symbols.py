@@ -45,6 +45,13 @@ def test_no_device_fails_loudly():
         volren_amd.Renderer(32, 32)
     with pytest.raises(volren_amd.VolrenError):
         volren_amd.math_probe(0, [1.0])
+    with pytest.raises(volren_amd.VolrenError):
+        volren_amd.math_sweep(6, 0, 4)
+    res = (C.c_float * 4)()
+    assert lib.vr_math_sweep(6, 0, 4, 0.0, res) == 2 and b"no HIP device" in lib.vr_last_error()
+    assert lib.vr_math_sweep(6, 0, (1 << 26) + 1, 0.0, res) == 3 and b"2^26" in lib.vr_last_error()      # VR_ERR_ARG: the arguments are checked first
+    assert lib.vr_math_sweep(6, 0, 0, 0.0, res) == 3 and lib.vr_math_sweep(6, 0, 4, 0.0, None) == 3
+    assert lib.vr_math_sweep(17, 0, 4, 0.0, res) == 3 and lib.vr_math_sweep(38, 0, 4, 0.0, res) == 3 and lib.vr_math_sweep(104, 0, 4, 0.0, res) == 3
     words, out = (C.c_uint32 * 4)(), (C.c_float * 1)()
     assert lib.vr_probe(C.c_void_p(1), 0, 2, words, out, 1) == 2 and b"no HIP device" in lib.vr_last_error()      # (the handle is not touched before the device check)
     assert lib.vr_probe(None, 0, 2, words, out, 1) == 3                                       # VR_ERR_ARG: there is no renderer to probe without a device ...

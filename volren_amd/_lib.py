@@ -18,7 +18,7 @@ SYMBOLS = [
     "vr_commit", "vr_reset", "vr_scale_and_move_to_unit_cube", "vr_trace", "vr_flush", "vr_render", "vr_synchronize",
     "vr_last_kernel_ms", "vr_last_pathtrace_ms", "vr_framebuffer", "vr_framebuffer_device", "vr_draw", "vr_display", "vr_save_png",
     "vr_set_tiles", "vr_set_stream", "vr_pack_tiles", "vr_unpack_tiles", "vr_get_uniforms", "vr_uniforms_size",
-    "vr_volume_add_grid_frame_dense", "vr_volume_update_grid_frame_dense", "vr_volume_n_grid_frames", "vr_impmap_floats", "vr_get_impmap", "vr_test_alloc_cap_mb", "vr_set_sched", "vr_sched_stats", "vr_grid_checksums", "vr_math_probe", "vr_probe", "vr_encode_dense_stats", "vr_write_brick_from_dense", "vr_write_dense",
+    "vr_volume_add_grid_frame_dense", "vr_volume_update_grid_frame_dense", "vr_volume_n_grid_frames", "vr_impmap_floats", "vr_get_impmap", "vr_test_alloc_cap_mb", "vr_set_sched", "vr_sched_stats", "vr_grid_checksums", "vr_math_probe", "vr_math_sweep", "vr_probe", "vr_encode_dense_stats", "vr_write_brick_from_dense", "vr_write_dense",
     "vr_sharded_create", "vr_sharded_destroy", "vr_sharded_parts", "vr_sharded_part", "vr_sharded_transport", "vr_sharded_collective", "vr_sharded_reset", "vr_sharded_render", "vr_sharded_synchronize", "vr_tile_owners", "vr_wave_timeline",
     "vr_render_features", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
     "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history",
@@ -101,6 +101,7 @@ def load():
     L.vr_sched_stats.argtypes = [vp, ci, vp]
     L.vr_grid_checksums.argtypes = [vp, vp]
     L.vr_math_probe.argtypes = [ci, vp, vp, vp, ci]
+    L.vr_math_sweep.argtypes = [ci, C.c_uint32, C.c_longlong, C.c_float, vp]
     L.vr_probe.argtypes = [vp, ci, ci, vp, vp, C.c_longlong]
     L.vr_write_brick_from_dense.argtypes = [vp, ci, ci, ci, vp, C.c_char_p]
     L.vr_write_dense.argtypes = [vp, ci, ci, ci, cf, cf, vp, C.c_char_p]

@@ -16,6 +16,7 @@
 #include "renderer.h"
 #include "sharded.h"
 #include "vr_device.h"
+#include "vr_math_probe.h"
 
 struct vr_renderer {
     vr::RendererHIP impl;
@@ -716,6 +717,21 @@ int vr_math_probe(int fn, const float* a, const float* b, float* out, int n) {
         vr::launch_math_probe(fn, da.as<float>(), db.as<float>(), dout.as<float>(), n, nullptr);
         VR_HIP(hipGetLastError());
         dout.download(out, (size_t)n * 4);
+    });
+}
+
+// bit-pattern sweep: out[i] = f(bits(first + i), b) for i < count, one launch; fn >= 100: the tolerance-mode form fn - 100 (vr_fastprobe.hip)
+int vr_math_sweep(int fn, uint32_t first, long long count, float b, float* out) {
+    if (!out || count <= 0) return fail(VR_ERR_ARG, "bad arguments");
+    if (count > (1ll << 26)) return fail(VR_ERR_ARG, "vr_math_sweep: at most 2^26 bit patterns per call");
+    if (fn < 0 || fn == 17 || (fn >= vr::kMathProbeCodes && (fn < 100 || fn > 103))) return fail(VR_ERR_ARG, "vr_math_sweep: no such function code");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available");
+    return guard([&] {
+        vr::DeviceBuffer dout((size_t)count * 4);
+        if (fn >= 100) vr::launch_fast_math_sweep(fn - 100, first, dout.as<float>(), (int32_t)count, nullptr);
+        else vr::launch_math_sweep(fn, first, b, dout.as<float>(), (int32_t)count, nullptr);
+        VR_HIP(hipGetLastError());
+        dout.download(out, (size_t)count * 4);
     });
 }
 

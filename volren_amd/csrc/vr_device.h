@@ -102,8 +102,12 @@ void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_ti
 
 // unit-test probe: out[i] = f(a[i], b[i]) with the device build of vr_math.h
 // fn: 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin 9 a/b 10 sqrt 11 fma(a,b,a) 12 float(u8)/255 13 sincos 14 a*b+a 15 half->float
-//     16 rcp_exact(a) 17 rcp3_exact((a, b, a)).y
+//     16 rcp_exact(a) 17 rcp3_exact((a, b, a)).y; 18.. : vr_math_probe.h
 void launch_math_probe(int32_t fn, const float* a, const float* b, float* out, int32_t n, hipStream_t stream);
+// the same over bit patterns: out[i] = f(bits(first + i), b), one launch, n <= 2^26 (fn 17 has no sweep form)
+void launch_math_sweep(int32_t fn, uint32_t first, float b, float* out, int32_t n, hipStream_t stream);
+// the VR_FAST_MATH forms (vr_fastprobe.hip, built with the tolerance-mode flags): 0 neg_log_1m(k 2^-24) 1 sincos_(bits(k)): s 2 the same: c 3 unorm8(k & 255), k = first + i
+void launch_fast_math_sweep(int32_t fn, uint32_t first, float* out, int32_t n, hipStream_t stream);
 // unit-test probe of the scene-data lookups (vr_probe.h, vr_probe.hip): n items of 4 words in, probe_out_words(what) floats out
 void launch_probe(const SceneParams& P, int32_t what, int32_t form, const uint32_t* in, float* out, uint32_t n, hipStream_t stream);
 

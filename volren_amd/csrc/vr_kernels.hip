@@ -26,6 +26,7 @@
 #include "vr_denoise.h"
 #include "vr_temporal.h"
 #include "vr_device.h"
+#include "vr_math_probe.h"
 #include "vr_pathtrace.h"
 
 namespace vr {
@@ -758,32 +759,24 @@ math_probe_kernel(int32_t fn, const float* __restrict__ a, const float* __restri
     if (i >= n) return;
     const float x = a[i], y = b[i];
     float r;
-    switch (fn) {
-    case 0: r = log_(x); break;
-    case 1: r = sin_(x); break;
-    case 2: r = cos_(x); break;
-    case 3: r = tan_(x); break;
-    case 4: r = acos_(x); break;
-    case 5: r = atan2_(x, y); break;
-    case 6: r = exp_(x); break;
-    case 7: r = pow_(x, y); break;
-    case 8: r = asin_(x); break;
-    case 9: r = x / y; break;
-    case 10: r = sqrt_(x); break;
-    case 11: r = fma_(x, y, x); break;
-    case 12: r = (float)((uint32_t)x & 255u) / 255.0f; break;
-    case 13: { float s, c; sincos_(x, s, c); r = s * y + c; break; }
-    case 14: r = x * y + x; break;     // must stay two roundings (-ffp-contract=off)
-    case 15: r = half2float(f2u(x)); break;     // bit pattern of x: low 16 bits = binary16
-    case 16: r = rcp_exact(x); break;
-    case 17: { const v3 q = rcp3_exact(v3{ x, y, x }); r = q.y; break; }      // the three-at-once form: y's reciprocal, range test shared with x
-    default: r = nan_(); break;
-    }
+    if (fn == 17) { const v3 q = rcp3_exact(v3{ x, y, x }); r = q.y; }      // the three-at-once form: y's reciprocal, range test shared with x
+    else r = math_probe_eval(fn, x, y);
     out[i] = r;
+}
+// the same over a range of bit patterns: x = bits(first + i) (wrapping), y one value; only the results leave the device
+__global__ void __launch_bounds__(256)
+math_sweep_kernel(int32_t fn, uint32_t first, float y, float* __restrict__ out, int32_t n) {
+    const int32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = math_probe_eval(fn, u2f(first + (uint32_t)i), y);
 }
 void launch_math_probe(int32_t fn, const float* a, const float* b, float* out, int32_t n, hipStream_t stream) {
     if (n <= 0) return;
     hipLaunchKernelGGL(math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, a, b, out, n);
+}
+void launch_math_sweep(int32_t fn, uint32_t first, float b, float* out, int32_t n, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(math_sweep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, first, b, out, n);
 }
 
 }  // namespace vr

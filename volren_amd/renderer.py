@@ -464,4 +464,13 @@ def math_probe(fn, a, b=None):
     return out
 
 
+def math_sweep(fn, first, count, b=0.0, out=None):
+    """f(bits(first + i), b) for i < count (at most 2^26) on the device: float32 results, integer ones as their bit pattern."""
+    if out is None:
+        out = np.empty(int(count), np.float32)
+    assert out.dtype == np.float32 and out.size >= count and out.flags.c_contiguous
+    _lib.check(_lib.load().vr_math_sweep(int(fn), int(first) & 0xFFFFFFFF, int(count), float(b), out.ctypes.data))
+    return out[:int(count)]
+
+
 STATE_NAMES = ("new", "begin", "march", "collide", "nee", "postnee", "escape")
