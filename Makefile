@@ -10,7 +10,9 @@ HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 OBJDIR   := build
 SRCS_CPP := grids.cpp imageio.cpp environment.cpp transferfunc.cpp renderer.cpp sharded.cpp capi.cpp
 PT_VARIANTS := 0 1 2 3 4
-OBJS     := $(OBJDIR)/vr_kernels.o $(OBJDIR)/vr_probe.o $(OBJDIR)/vr_fastprobe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
+# default-flag HIP objects, one per subsystem (vr_device.h lists their launchers in this order)
+HIP_OBJS := vr_launch.o vr_filters.o vr_setup.o vr_probe.o
+OBJS     := $(HIP_OBJS:%=$(OBJDIR)/%) $(OBJDIR)/vr_fastprobe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
 # tolerance-mode kernels (opt-in, vr_math.h VR_FAST_MATH): hardware transcendentals, reciprocal division, contraction allowed
 FASTFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-hip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Wno-unused-result -Iinclude -DVR_FAST_MATH=1
 # path-tracing kernels: no SLP vectorisation.  On gfx950 a packed fp32 instruction (v_pk_mul/add/fma_f32) occupies the SIMD for
@@ -21,12 +23,8 @@ HDRS     := $(wildcard $(CSRC)/*.h) include/volren_amd.h
 
 all: volren_amd/libvolren_amd.so volren_amd/volren oracle
 
-$(OBJDIR)/vr_kernels.o: $(CSRC)/vr_kernels.hip $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# the test hook's probe kernel (vr_probe.h)
-$(OBJDIR)/vr_probe.o: $(CSRC)/vr_probe.hip $(HDRS)
+# the default-flag HIP objects (HIP_OBJS)
+$(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -60,7 +58,7 @@ volren_amd/volren: $(CSRC)/main.cpp volren_amd/libvolren_amd.so $(HDRS)
 # A caller written against the reference's src/renderer.h builds with: hipcc -I<p>/include caller.cpp -L<p>/lib -lvolren_amd
 PREFIX ?= /usr/local
 # what volren_amd.hpp pulls in (host-side class headers; the kernel headers vr_trace.h / vr_pathtrace.h / vr_math.h stay private)
-INSTALL_HDRS := renderer.h environment.h transferfunc.h grids.h sharded.h devmem.h hostmath.h vr_math.h vr_device.h vr_denoise.h vr_temporal.h vr_scene.h
+INSTALL_HDRS := renderer.h environment.h transferfunc.h grids.h sharded.h devmem.h hostmath.h vr_math.h vr_device.h vr_denoise.h vr_temporal.h vr_tiles.h vr_scene.h
 install: all
 	install -d $(DESTDIR)$(PREFIX)/include/volren_amd $(DESTDIR)$(PREFIX)/lib $(DESTDIR)$(PREFIX)/bin
 	install -m 644 include/volren_amd.h include/volren_amd.hpp $(DESTDIR)$(PREFIX)/include/

@@ -64,7 +64,7 @@ inline void build_grid(HostGrid& g, const Uniforms& u, const float* lut, const u
             if (u.use_tf) { float rgba[4]; tf_lookup(P, m0 * u.vol_inv_majorant, rgba); m0 = u.vol_majorant * rgba[3]; }
             g.majorant.assign(majorant_table_cells(k), m0);
         }
-        for (int mip = 0; mip <= n_mips; ++mip) {            // == majorant_kernel of vr_kernels.hip
+        for (int mip = 0; mip <= n_mips; ++mip) {            // == majorant_kernel of vr_setup.hip
             const uint32_t rnd = (1u << mip) - 1u;
             const uint32_t dx = (nb[0] + rnd) >> mip, dy = (nb[1] + rnd) >> mip, dz = (nb[2] + rnd) >> mip;
             const uint32_t sxm = (uint32_t)g.view.mshift[0] - mip, sym = (uint32_t)g.view.mshift[1] - mip;
@@ -173,7 +173,7 @@ inline void build_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* de
     P.env_avg_w = impmap[imp_level_offset(imp_dim, base)]; P.env_avg_w_set = 1;
     bool div_safe = true;
     cdf.assign(env_cdf_table_floats(base - 1), 0.0f);
-    {   // == env_cdf_kernel of vr_kernels.hip
+    {   // == env_cdf_kernel of vr_setup.hip
         for (int mip = base - 1; mip >= 0; --mip) {
             const int d = imp_dim >> mip, hd = d >> 1;
             const float* level = impmap + imp_level_offset(imp_dim, mip);

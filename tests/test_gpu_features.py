@@ -553,6 +553,41 @@ def test_variance_of_a_tile_subset(order):
     assert (got[mask] > 0).any()
 
 
+def test_ragged_frame_partial_chunk_and_tile_subset_with_and_without_moments():
+    """Every index rule of the accumulation pass at once (vr_tiles.h: pixel mapping, sample-pool slots): a frame ragged on both axes (40x24: 3 x 2
+    tiles), 11 samples (the last chunk of a work unit partial at 8 and at 4 samples per unit), the tile list [0, 2, 5], variance off and on.  The two
+    colour buffers bit for bit each other's and the oracle's, the moments bit for bit the host Welford replay's, unlisted tiles untouched."""
+    w, h, spp, tiles = 40, 24, 11, [0, 2, 5]
+    o = scenes.oracle_scene("c1", w, h)                      # smoke.brick
+    L = _oracle_radiance(o, spp)
+    mu, S = _replay(L)
+    assert np.array_equal(_bits(mu), _bits(scenes.oracle_scene("c1", w, h).render(spp)))
+    mask = np.zeros((h, w), bool)
+    for t in tiles:
+        ty, tx = divmod(t, 3)
+        mask[ty * 16:ty * 16 + 16, tx * 16:tx * 16 + 16] = True
+    assert 0 < mask.sum() < mask.size
+    fbs = []
+    for variance in (0, 1):
+        r = scenes.hip_scene("c1", w, h)
+        r.variance = variance
+        r.set_tiles(tiles)
+        r.render(spp)
+        fb = r.framebuffer()
+        print("variance", variance, "colour words off the oracle:", int((_bits(fb[mask]) != _bits(mu[mask])).sum()))
+        assert np.array_equal(_bits(fb[mask]), _bits(mu[mask]))
+        assert not fb[~mask].any()
+        fbs.append(fb)
+        if variance:
+            var = r.variance()
+            expect = (S * (np.float32(spp) / np.float32(spp - 1))).astype(np.float32)
+            print("largest distance of the moments from the replay, ulps:", int(_ulps(var[mask], expect[mask]).max()))
+            assert np.array_equal(_bits(var[mask]), _bits(expect[mask]))
+            assert not var[~mask].any()
+            assert (var[mask] > 0).any()
+    assert np.array_equal(_bits(fbs[0]), _bits(fbs[1]))
+
+
 def test_variance_in_the_tolerance_mode():
     """fast_math = 1 (no transfer function): variance on leaves the frame bit for bit, and the variance does not depend on the launch split"""
     r = scenes.hip_scene("c1", 256, 256)

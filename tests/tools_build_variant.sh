@@ -5,6 +5,8 @@
 #   VARIANTS: the kernel variants to recompile with the flags (default: all five, bit-exact and tolerance mode); the others, and everything else when VARIANTS is set,
 #   are taken from the default build in build/ (run `make` first)
 set -e
+# the default-flag HIP objects (Makefile HIP_OBJS) and the tolerance-mode probe
+SMALL="build/vr_launch.o build/vr_filters.o build/vr_setup.o build/vr_probe.o build/vr_fastprobe.o"
 name=$1; shift
 out=build/exp_$name; mkdir -p $out
 if [ -n "$VARIANTS" ]; then
@@ -22,7 +24,7 @@ if [ -n "$VARIANTS" ]; then
     objs="$objs build/vr_ptfast_$v.o"
   done
   for p in $pids; do wait $p; done
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $out/libvolren_amd.so build/vr_kernels.o $objs build/grids.o build/imageio.o build/environment.o build/transferfunc.o build/renderer.o build/sharded.o build/capi.o -lz -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $out/libvolren_amd.so $SMALL $objs build/grids.o build/imageio.o build/environment.o build/transferfunc.o build/renderer.o build/sharded.o build/capi.o -lz -ldl
   for v in $VARIANTS; do grep -h -A8 "pathtrace_kernel" $out/res_$v.txt | grep -E "Function Name|VGPRs:|SGPRs Spill|VGPRs Spill|ScratchSize" | sed 's/.*remark: [^ ]* *//; s/ \[-R.*//' | paste - - - - - | sed "s/^/v$v: /"; done
   exit 0
 fi
@@ -32,8 +34,10 @@ for v in 0 1 2 3 4; do
   /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize -DVR_PT_VARIANT=$v "$@" -Rpass-analysis=kernel-resource-usage -c volren_amd/csrc/vr_pathtrace.hip -o $out/vr_pathtrace_$v.o 2> $out/res_$v.txt &
   pids="$pids $!"
 done
-/opt/rocm/bin/hipcc $FLAGS "$@" -c volren_amd/csrc/vr_kernels.hip -o $out/vr_kernels.o 2>/dev/null &
-pids="$pids $!"
+for f in vr_launch vr_filters vr_setup; do
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c volren_amd/csrc/$f.hip -o $out/$f.o 2>/dev/null &
+  pids="$pids $!"
+done
 /opt/rocm/bin/hipcc $FLAGS "$@" -x hip -c volren_amd/csrc/renderer.cpp -o $out/renderer.o 2>/dev/null &
 pids="$pids $!"
 /opt/rocm/bin/hipcc $FLAGS "$@" -x hip -c volren_amd/csrc/environment.cpp -o $out/environment.o 2>/dev/null &
@@ -43,5 +47,5 @@ for v in 0 1 2 3 4; do
   pids="$pids $!"
 done
 for p in $pids; do wait $p; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $out/libvolren_amd.so $out/vr_kernels.o $out/vr_pathtrace_0.o $out/vr_pathtrace_1.o $out/vr_pathtrace_2.o $out/vr_pathtrace_3.o $out/vr_pathtrace_4.o $out/vr_pathtrace_fast_0.o $out/vr_pathtrace_fast_1.o $out/vr_pathtrace_fast_2.o $out/vr_pathtrace_fast_3.o $out/vr_pathtrace_fast_4.o build/grids.o build/imageio.o $out/environment.o build/transferfunc.o $out/renderer.o build/sharded.o build/capi.o -lz -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $out/libvolren_amd.so $out/vr_launch.o $out/vr_filters.o $out/vr_setup.o build/vr_probe.o build/vr_fastprobe.o $out/vr_pathtrace_0.o $out/vr_pathtrace_1.o $out/vr_pathtrace_2.o $out/vr_pathtrace_3.o $out/vr_pathtrace_4.o $out/vr_pathtrace_fast_0.o $out/vr_pathtrace_fast_1.o $out/vr_pathtrace_fast_2.o $out/vr_pathtrace_fast_3.o $out/vr_pathtrace_fast_4.o build/grids.o build/imageio.o $out/environment.o build/transferfunc.o $out/renderer.o build/sharded.o build/capi.o -lz -ldl
 grep -h -A8 "TraceCfgILb0ELi0ELi0ELi[01]EEELb0E" $out/res_0.txt $out/res_1.txt | grep -E "VGPRs:|ScratchSize|Occupancy|LDS" | sed 's/.*remark: [^ ]* *//; s/ \[-R.*//' | paste - - - - 

@@ -1,6 +1,6 @@
-"""Diagnostic: instruction histogram of the path-tracing kernels from the device assembly (build/asm/vr_kernels.s)."""
+"""Diagnostic: instruction histogram of the path-tracing kernels from the device assembly (default: build/asm/vr_pathtrace_0.s, from vr_pathtrace.hip)."""
 import re, collections, sys
-txt = open(sys.argv[1] if len(sys.argv) > 1 else "build/asm/vr_kernels.s").read()
+txt = open(sys.argv[1] if len(sys.argv) > 1 else "build/asm/vr_pathtrace_0.s").read()
 for m in re.finditer(r"\n(_ZN2vr16pathtrace_kernelINS_8TraceCfgILb([01])E[A-Za-z0-9]*EELb0E[^\n:]*):[^\n]*\n", txt):
     body = txt[m.end():]
     body = body[:body.index(".Lfunc_end")]

@@ -1,5 +1,5 @@
 // Diagnostic (not part of the product): checks on the device that workgroups are dealt round-robin to the 8 XCDs, i.e. that
-// blockIdx.x & 7 == HW_REG_XCC_ID, the assumption behind the XCD-aware work queue of vr_kernels.hip.
+// blockIdx.x & 7 == HW_REG_XCC_ID, the assumption behind the XCD-aware work queue of vr_pathtrace.h.
 //   hipcc --offload-arch=gfx950 -O2 -o build/xcc tests/tools_xcc_probe.hip && ./build/xcc      (MI355X: 4096 of 4096 blocks match)
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -502,7 +502,7 @@ int vr_render_adaptive(vr_renderer* r, int min_spp, int max_spp, float threshold
 }
 static int tile_count_arg(vr_renderer* r, int n_tiles) {
     const auto& res = r->impl.resolution;
-    return n_tiles == ((res.x + 15) / 16) * ((res.y + 15) / 16) ? VR_OK : fail(VR_ERR_ARG, "n_tiles must be ceil(W / 16) * ceil(H / 16)");
+    return n_tiles == vr::tile_count(res.x, res.y) ? VR_OK : fail(VR_ERR_ARG, "n_tiles must be ceil(W / 16) * ceil(H / 16)");
 }
 int vr_tile_samples(vr_renderer* r, int32_t* out, int n_tiles) {
     NEED(r);
@@ -647,7 +647,7 @@ int vr_sharded_synchronize(vr_sharded* s) {
 
 int vr_tile_owners(int width, int height, int n_parts, int32_t* owner_out, int n_tiles) {
     if (!owner_out || width <= 0 || height <= 0 || n_parts <= 0) return fail(VR_ERR_ARG, "vr_tile_owners: bad arguments");
-    if (n_tiles != ((width + 15) / 16) * ((height + 15) / 16)) return fail(VR_ERR_ARG, "vr_tile_owners: n_tiles must be ceil(width / 16) * ceil(height / 16)");
+    if (n_tiles != vr::tile_count(width, height)) return fail(VR_ERR_ARG, "vr_tile_owners: n_tiles must be ceil(width / 16) * ceil(height / 16)");
     return guard([&] {
         const auto lists = vr::tile_owner_lists(width, height, n_parts);
         for (size_t p = 0; p < lists.size(); ++p)

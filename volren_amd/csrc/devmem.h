@@ -65,5 +65,8 @@ private:
 };
 using DeviceBufferPtr = std::shared_ptr<DeviceBuffer>;
 inline DeviceBufferPtr make_device_buffer(size_t bytes) { return std::make_shared<DeviceBuffer>(bytes); }
+// (re)allocate `b` unless it holds exactly `bytes` / at least `bytes`.  true: `b` is new, contents undefined; a failed allocation throws and leaves `b` as it was
+inline bool ensure_buffer(DeviceBufferPtr& b, size_t bytes) { if (b && b->size_bytes() == bytes) return false; b = make_device_buffer(bytes); return true; }
+inline bool ensure_buffer_at_least(DeviceBufferPtr& b, size_t bytes) { return b && b->size_bytes() >= bytes ? false : ensure_buffer(b, bytes); }
 
 }  // namespace vr

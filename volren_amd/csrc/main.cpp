@@ -245,7 +245,7 @@ int main(int argc, char** argv) {
             if (adaptive) {
                 const std::vector<int32_t> n = renderer->tile_samples();
                 double px_samples = 0.0;                   // partial edge tiles count their pixels inside the frame
-                const int tiles_x = (width + 15) / 16;
+                const int tiles_x = vr::tiles_x(width);
                 for (size_t t = 0; t < n.size(); ++t) {
                     const int tx = (int)(t % tiles_x), ty = (int)(t / tiles_x);
                     px_samples += (double)n[t] * std::min(16, width - 16 * tx) * std::min(16, height - 16 * ty);

@@ -345,7 +345,7 @@ static GridView make_view(const BrickGridHIP& g, bool paired = false, bool maj_b
     for (int i = 0; i < 3; ++i) v.nb[i] = g.nb[i];
     for (int i = 0; i < 3; ++i) { v.mshift[i] = g.mshift[i]; v.mlim[i] = (float)(8u << g.mshift[i]); }
     v.n_mips = g.n_mips;
-    v.maj_blocked = maj_blocked ? 1 : 0;         // the layout the majorant table is (re)built in and the kernel variant reads (vr_kernels.hip pathtrace_variant)
+    v.maj_blocked = maj_blocked ? 1 : 0;         // the layout the majorant table is (re)built in and the kernel variant reads (vr_launch.hip pathtrace_variant)
     v.maj_outside = (int32_t)majorant_padded_cells((uint32_t)(g.mshift[0] + g.mshift[1] + g.mshift[2]));
     return v;
 }
@@ -399,7 +399,7 @@ void RendererHIP::fill_params(SceneParams& P) {
         const mat4 efd = eti * dt;
         memcpy(P.emission_from_density, efd.m, sizeof efd.m);
         // the kernel compiled for two brick grids (DDA trackers) reads them from their paired atlas; every other kernel reads each grid's own
-        // (an environment that fails the warp table's check is rendered by the run-time variant, from the grids' own atlases: vr_kernels.hip pathtrace_variant)
+        // (an environment that fails the warp table's check is rendered by the run-time variant, from the grids' own atlases: vr_launch.hip pathtrace_variant)
         const bool scale_ok = u.vol_density_scale >= 1.0f / 65536.0f && u.vol_density_scale <= 16777216.0f;      // (the same goes for a density scale the fixed kernels' march does not divide by)
         P.paired = (integrator == 0 && environment->cdf_div_safe && scale_ok && density.atlas_paired && density.atlas_paired == emission.atlas_paired) ? 1 : 0;
         // ... and is the one kernel compiled for both layouts of the majorant table's fine levels: blocked for the grids commit() marked (or as majorant_layout says)
@@ -450,7 +450,7 @@ void RendererHIP::set_tiles(const std::vector<int32_t>& tile_ids) {
     tiles_dev_.reset();
     if (tile_ids.empty()) return;
     if (resolution.x > 0) {
-        const int n_all = ((resolution.x + 15) / 16) * ((resolution.y + 15) / 16);
+        const int n_all = tile_count(resolution.x, resolution.y);
         for (int32_t t : tile_ids)
             if (t < 0 || t >= n_all) throw std::runtime_error("set_tiles: tile id out of range");   // never launch out-of-bounds tiles
     }
@@ -467,7 +467,7 @@ void RendererHIP::set_tiles(const std::vector<int32_t>& tile_ids) {
 // frame size, tile list); ids empty = the n_tiles tiles of the whole frame.
 std::vector<int32_t> RendererHIP::costliest_first(const SceneParams& P, const std::vector<int32_t>& tile_ids, int n_tiles) const {
     const Uniforms& u = P.u;
-    const int W = u.resolution[0], H = u.resolution[1], tiles_x = (W + 15) / 16;
+    const int W = u.resolution[0], H = u.resolution[1], tiles_x = vr::tiles_x(W);
     std::vector<int32_t> ids(tile_ids);
     if (ids.empty()) { ids.resize((size_t)n_tiles); for (int i = 0; i < n_tiles; ++i) ids[(size_t)i] = i; }
     auto chord = [&](float px, float py) {
@@ -509,7 +509,7 @@ const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<i
     key = key ? key : 1;
     if (order_dev_ && order_key_ == key && order_dev_->size_bytes() == (size_t)n_tiles * sizeof(int32_t)) return order_dev_->as<int32_t>();
     const std::vector<int32_t> ordered = costliest_first(P, ids, n_tiles);
-    if (!order_dev_ || order_dev_->size_bytes() != ordered.size() * sizeof(int32_t)) order_dev_ = make_device_buffer(ordered.size() * sizeof(int32_t));
+    ensure_buffer(order_dev_, ordered.size() * sizeof(int32_t));
     order_dev_->upload(ordered.data(), ordered.size() * sizeof(int32_t), stream);
     order_key_ = key;
     return order_dev_->as<int32_t>();
@@ -596,8 +596,7 @@ int RendererHIP::samples_per_launch(const LaunchInputs& in, int n_tiles) const {
 
 void RendererHIP::submit_tile_set(const LaunchInputs& in, int first, int n) {
     if (n <= 0) return;
-    const int tiles_x = (in.P.u.resolution[0] + 15) / 16, tiles_y = (in.P.u.resolution[1] + 15) / 16;
-    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tiles_x * tiles_y;
+    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(in.P.u.resolution[0], in.P.u.resolution[1]);
     const bool ordered = in.order_tiles >= 2 || (in.order_tiles == 1 && tiles_dev_);
     const int32_t* tiles = ordered ? tile_order(in.P, tiles_host_, n_tiles) : (tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr);
     submit(in, first, n, tiles, n_tiles);
@@ -673,8 +672,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     float* moments = nullptr;
     if (in.variance) {
         const size_t bytes = color->size_bytes();
-        if (!moments_ || moments_->size_bytes() != bytes) {
-            moments_ = make_device_buffer(bytes);
+        if (ensure_buffer(moments_, bytes)) {
             VR_HIP(hipMemsetAsync(moments_->get(), 0, bytes, stream));
             if (first > 0) moments_n_ = -1;
         }
@@ -737,7 +735,7 @@ void RendererHIP::trace() {
     if (pending_n_ == 0) {
         pending_ = std::move(now);
         pending_first_ = sample;
-        const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : ((resolution.x + 15) / 16) * ((resolution.y + 15) / 16);
+        const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y);
         pending_cap_ = samples_per_launch(pending_, n_tiles);      // a full sub-launch goes out at once: the GPU works while the caller keeps calling
     }
     ++pending_n_;
@@ -772,7 +770,7 @@ void RendererHIP::draw() {
 }
 
 void RendererHIP::draw_from(const DeviceBuffer& src) {
-    if (!display || display->size_bytes() != src.size_bytes()) display = make_device_buffer(src.size_bytes());
+    ensure_buffer(display, src.size_bytes());
     VR_HIP(hipMemcpyAsync(display->get(), src.get(), src.size_bytes(), hipMemcpyDeviceToDevice, stream));
     if (tonemapping) {
         launch_tonemap(display->as<float>(), resolution.x, resolution.y, tonemap_exposure, tonemap_gamma, stream);
@@ -850,10 +848,9 @@ void RendererHIP::render_features(int spp) {
         P.emission = make_view(emission_grids.at(in.frame), false);
         P.paired = 0;
     }
-    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : ((resolution.x + 15) / 16) * ((resolution.y + 15) / 16);
+    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y);
     const size_t bytes = (size_t)resolution.x * resolution.y * 8 * sizeof(float);
-    if (!features_ || features_->size_bytes() != bytes) {
-        features_ = make_device_buffer(bytes);
+    if (ensure_buffer(features_, bytes)) {
         VR_HIP(hipMemsetAsync(features_->get(), 0, bytes, stream));
     }
     launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, features_->as<float>(), status_->as<uint32_t>(), stream);
@@ -904,20 +901,15 @@ void RendererHIP::download_variance(float* rgba) {
     flush_pending();
     check_moments("variance");
     moments_->download(rgba, moments_->size_bytes(), stream);
-    const size_t n = (size_t)resolution.x * resolution.y * 4;
-    if (ragged()) {                                   // each tile's own factor
-        const int W = resolution.x, H = resolution.y, tiles_x = (W + 15) / 16;
-        for (int y = 0; y < H; ++y)
-            for (int x = 0; x < W; ++x) {
-                const int32_t c = tile_n_[(size_t)((y >> 4) * tiles_x + (x >> 4))];
-                const float f = c >= 2 ? (float)c / (float)(c - 1) : 0.0f;
-                float* px = rgba + 4 * ((size_t)y * W + x);
-                for (int k = 0; k < 4; ++k) px[k] = c >= 2 ? px[k] * f : 0.0f;
-            }
-        return;
-    }
-    const float f = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;
-    for (size_t i = 0; i < n; ++i) rgba[i] = sample >= 2 ? rgba[i] * f : 0.0f;
+    const bool per_tile = ragged();                   // each tile's own count and factor
+    const int W = resolution.x, H = resolution.y;
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const int32_t c = per_tile ? tile_n_[(size_t)tile_of_pixel(x, y, W)] : sample;
+            const float f = variance_scale(c);
+            float* px = rgba + 4 * ((size_t)y * W + x);
+            for (int k = 0; k < 4; ++k) px[k] = c >= 2 ? px[k] * f : 0.0f;
+        }
 }
 
 // The a-trous denoiser (vr_denoise.h) on whole frames: prepare (variance of the mean, guide) once, then `denoise_iterations` passes at steps
@@ -941,7 +933,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal) {
         for (int32_t c : tile_n_)
             if (c < 1) throw std::runtime_error(me + "a tile of the frame holds no samples (sample < 1 there: render_adaptive over a tile subset from sample 0)");
         const size_t bytes = tile_n_.size() * sizeof(int32_t);
-        if (!tile_n_dev_ || tile_n_dev_->size_bytes() != bytes) tile_n_dev_ = make_device_buffer(bytes);
+        ensure_buffer(tile_n_dev_, bytes);
         tile_n_dev_->upload(tile_n_.data(), bytes, stream);
         counts = tile_n_dev_->as<int32_t>();
     }
@@ -949,15 +941,14 @@ void RendererHIP::run_denoise(const char* who, bool temporal) {
     if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error(me + "frame too large (32-bit pixel indices)");
     if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error(me + "denoise_iterations out of range");
     const size_t px = (size_t)W * H;
-    auto ensure = [&](DeviceBufferPtr& b, size_t bytes) { if (!b || b->size_bytes() != bytes) b = make_device_buffer(bytes); };
     const int to = hist_cur_ < 0 ? 0 : 1 - hist_cur_;      // the half of the history pair this call writes
-    if (temporal) { ensure(hist_color_[to], px * 4 * sizeof(float)); ensure(hist_record_[to], px * 4 * sizeof(float)); }
-    ensure(dn_guide_, px * 8 * sizeof(float));
-    ensure(dn_var_[0], px * sizeof(float));
-    ensure(denoised_, px * 4 * sizeof(float));
-    if (N >= 2) { ensure(dn_var_[1], px * sizeof(float)); ensure(dn_color_[0], px * 4 * sizeof(float)); }
-    if (N >= 3) ensure(dn_color_[1], px * 4 * sizeof(float));
-    const float vscale = sample >= 2 ? (float)sample / (float)(sample - 1) : 0.0f;      // download_variance's factor
+    if (temporal) { ensure_buffer(hist_color_[to], px * 4 * sizeof(float)); ensure_buffer(hist_record_[to], px * 4 * sizeof(float)); }
+    ensure_buffer(dn_guide_, px * 8 * sizeof(float));
+    ensure_buffer(dn_var_[0], px * sizeof(float));
+    ensure_buffer(denoised_, px * 4 * sizeof(float));
+    if (N >= 2) { ensure_buffer(dn_var_[1], px * sizeof(float)); ensure_buffer(dn_color_[0], px * 4 * sizeof(float)); }
+    if (N >= 3) ensure_buffer(dn_color_[1], px * 4 * sizeof(float));
+    const float vscale = variance_scale(sample);      // download_variance's factor
     launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, counts, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
     VR_HIP(hipGetLastError());
     const DeviceBuffer* first = color.get();          // what iteration 0 reads
@@ -1028,7 +1019,7 @@ void RendererHIP::drop_tile_samples() { tile_n_.clear(); tile_n_sample_ = -1; }
 std::vector<int32_t> RendererHIP::tile_samples() {
     flush_pending();
     if (ragged()) return tile_n_;
-    return std::vector<int32_t>((size_t)(((resolution.x + 15) / 16) * ((resolution.y + 15) / 16)), sample);
+    return std::vector<int32_t>((size_t)tile_count(resolution.x, resolution.y), sample);
 }
 
 std::vector<float> RendererHIP::tile_error() {
@@ -1039,8 +1030,8 @@ std::vector<float> RendererHIP::tile_error() {
     const int n_all = (int)counts.size();
     std::vector<int32_t> lists((size_t)n_all * 2);
     for (int t = 0; t < n_all; ++t) { lists[(size_t)t] = t; lists[(size_t)(n_all + t)] = counts[(size_t)t]; }
-    if (!adaptive_lists_ || adaptive_lists_->size_bytes() < lists.size() * sizeof(int32_t)) adaptive_lists_ = make_device_buffer(lists.size() * sizeof(int32_t));
-    if (!adaptive_err_ || adaptive_err_->size_bytes() < (size_t)n_all * sizeof(float)) adaptive_err_ = make_device_buffer((size_t)n_all * sizeof(float));
+    ensure_buffer_at_least(adaptive_lists_, lists.size() * sizeof(int32_t));
+    ensure_buffer_at_least(adaptive_err_, (size_t)n_all * sizeof(float));
     adaptive_lists_->upload(lists.data(), lists.size() * sizeof(int32_t), stream);
     launch_adaptive_error(color->as<float>(), moments_->as<float>(), adaptive_lists_->as<int32_t>(), adaptive_lists_->as<int32_t>() + n_all, n_all, resolution.x,
                           resolution.y, adaptive_err_->as<float>(), stream);
@@ -1065,12 +1056,12 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
     LaunchInputs in;
     capture(in);
     in.variance = 1;                                  // the error estimate needs the moments of every launch
-    const int W = resolution.x, H = resolution.y, n_all = ((W + 15) / 16) * ((H + 15) / 16);
+    const int W = resolution.x, H = resolution.y, n_all = tile_count(W, H);
     if (!was_ragged) tile_n_.assign((size_t)n_all, std::max(sample, 0));
     std::vector<int32_t> set(tiles_host_);
     if (set.empty()) { set.resize((size_t)n_all); for (int t = 0; t < n_all; ++t) set[(size_t)t] = t; }
-    if (!adaptive_lists_ || adaptive_lists_->size_bytes() < (size_t)n_all * 2 * sizeof(int32_t)) adaptive_lists_ = make_device_buffer((size_t)n_all * 2 * sizeof(int32_t));
-    if (!adaptive_err_ || adaptive_err_->size_bytes() < (size_t)n_all * sizeof(float)) adaptive_err_ = make_device_buffer((size_t)n_all * sizeof(float));
+    ensure_buffer_at_least(adaptive_lists_, (size_t)n_all * 2 * sizeof(int32_t));
+    ensure_buffer_at_least(adaptive_err_, (size_t)n_all * sizeof(float));
     const bool ordered = in.order_tiles >= 1;
     VR_HIP(hipEventRecord(ev0_, in.stream));
     last_launches = 0;

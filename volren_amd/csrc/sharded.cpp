@@ -18,7 +18,7 @@ namespace vr {
 
 std::vector<std::vector<int32_t>> tile_owner_lists(int width, int height, int n_parts) {
     if (width <= 0 || height <= 0 || n_parts <= 0) throw std::runtime_error("tile_owner_lists: bad arguments");
-    const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
+    const int tiles_x = vr::tiles_x(width), tiles_y = vr::tiles_y(height);
     std::vector<std::vector<int32_t>> lists((size_t)n_parts);
     for (int ty = 0; ty < tiles_y; ++ty)
         for (int tx = 0; tx < tiles_x; ++tx) lists[(size_t)((tx + ty) % n_parts)].push_back(ty * tiles_x + tx);

@@ -1,9 +1,9 @@
 // vr_adaptive.h -- adaptive sampling per 16x16 tile: the error estimate (host + device lane code) and the schedule (host).
 //
-// The error kernel (vr_kernels.hip adaptive_error_kernel) and the host build of the tests (tests/hostkernel/adaptive_host.cpp) run the same
+// The error kernel (vr_filters.hip adaptive_error_kernel) and the host build of the tests (tests/hostkernel/adaptive_host.cpp) run the same
 // code, so the two agree bit for bit.  The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division, sqrt_, luma).
 // For a pixel with n samples, framebuffer mean mu (RGBA) and moments S (Welford's M2 / n, what the renderer's moments hold):
-//   var_c = n >= 2 ? S_c * ((float)n / (float)(n - 1)) : 0        vr_variance's and denoise_prepare_kernel's formation
+//   var_c = n >= 2 ? S_c * variance_scale(n) : 0                  vr_variance's and denoise_prepare_kernel's formation (vr_tiles.h)
 //   e_p   = n < 2 ? +inf : sqrt_(denoise_mean_variance(var, n)) / (luma(mu.rgb) + kAdaptiveFloor)
 //   e_t   = the max of e_p over the tile's pixels inside the frame; a NaN e_p makes e_t NaN
 // e_t is the worst relative standard error of a pixel mean's luminance in the tile.  Tile t has converged iff e_t < threshold (strict:
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "vr_denoise.h"
+#include "vr_tiles.h"
 
 namespace vr {
 
@@ -34,7 +35,7 @@ VR_HD float adaptive_error_of_variance(const float mu[4], const float var[4], in
 // e_p of one pixel: mu = the framebuffer texel, S = the moments texel, n = the samples behind both
 VR_HD float adaptive_pixel_error(const float mu[4], const float S[4], int32_t n) {
     if (n < 2) return inf_();
-    const float f = (float)n / (float)(n - 1);
+    const float f = variance_scale(n);
     const float var[4] = { S[0] * f, S[1] * f, S[2] * f, S[3] * f };
     return adaptive_error_of_variance(mu, var, n);
 }

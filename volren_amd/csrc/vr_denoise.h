@@ -1,7 +1,7 @@
 // vr_denoise.h -- the edge-avoiding a-trous wavelet filter of the denoiser (host + device lane code).
 //
 // The spatial part of SVGF (Schied et al. 2017, after Dammertz et al. 2010), guided by the renderer's per-pixel variance and first-scatter
-// features (vr_trace.h feature_pixel).  Per-pixel functions only: the HIP kernels (vr_kernels.hip denoise_prepare_kernel /
+// features (vr_trace.h feature_pixel).  Per-pixel functions only: the HIP kernels (vr_filters.hip denoise_prepare_kernel /
 // denoise_atrous_kernel) and the host build of the tests (tests/hostkernel/denoise_host.cpp) run the same code, so the two agree bit for bit.
 // The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division, the project's exp_ / pow_ / sqrt_ / luma),
 // and every sum runs in one order: dy outer, dx inner, from -r to r.  n = the samples behind the framebuffer; row 0 is the bottom row.

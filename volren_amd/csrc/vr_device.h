@@ -1,4 +1,5 @@
-// vr_device.h -- host-callable launchers of the HIP kernels in vr_kernels.hip (all asynchronous on `stream`).
+// vr_device.h -- the host-callable launchers of every HIP kernel (all asynchronous on `stream`), in sections, one per source file:
+// vr_launch.hip (path tracing, features), vr_filters.hip (image space), vr_setup.hip (scene and environment), vr_probe.hip / vr_fastprobe.hip (test hooks).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,9 +8,11 @@
 #include "vr_denoise.h"
 #include "vr_scene.h"
 #include "vr_temporal.h"
+#include "vr_tiles.h"
 
 namespace vr {
 
+// ---- vr_launch.hip ---------------------------------------------------------------------------------------------------------------------------
 // Path tracing: runs samples first_sample .. first_sample+n_samples-1 (1-based, the reference's current_sample)
 // for every pixel of the listed 16x16 tiles (kernel 1: per-sample radiances into `sample_pool`) and folds them in
 // sample order into the RGBA32F running mean `fb` (kernel 2; W*H texels, row 0 at the bottom).
@@ -37,6 +40,18 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
 // status: the renderer's status word; a pixel whose tracker exceeded its step budget sets kFeatureLostStatus there (its remaining samples are not run).
 constexpr uint32_t kFeatureLostStatus = 4u;
 void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream);
+// which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
+// what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
+enum PathtraceVariantReason : int {
+    VR_VARIANT_INTEGRATOR = 1,        // a global-majorant / ray-marching integrator was asked for
+    VR_VARIANT_ENV_DIVISION = 2,      // the environment's warp table failed env_cdf_kernel's check (thresholds below 2^-76: vr_math.h div_core does not apply)
+    VR_VARIANT_DENSITY_SCALE = 4,     // density scale outside [2^-16, 2^24] (the clean march divides by majorants without rescaling)
+    VR_VARIANT_GRID_FORMS = 8         // emission grid with a dense grid on either side, or brick grids of different layouts (no paired atlas)
+};
+int pathtrace_variant_of(const SceneParams& P, int* why);
+// fast_math: the opt-in tolerance-mode kernels (hardware transcendentals, reciprocal division; vr_math.h VR_FAST_MATH); the default
+// kernels are bit-identical to the CPU oracle
+// ---- vr_filters.hip --------------------------------------------------------------------------------------------------------------------------
 // Denoiser (vr_denoise.h), whole W x H frames.  prepare: moments = W*H*4 Welford second moments S of n samples (the variance is S * vscale, 0 for
 // n = 1: vr_variance's arithmetic), features = W*H*8 (vr_render_features) -> v = W*H variances of the mean's luminance, guide = W*H*8.
 // atrous: one iteration of step `step` from (cin W*H*4, vin W*H, guide) into cout (W*H*4) and vout (W*H; nullptr: not written); the
@@ -56,18 +71,14 @@ void launch_denoise_temporal(const float* color, float* v, const float* guide, c
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,
                            hipStream_t stream);
-// which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
-// what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
-enum PathtraceVariantReason : int {
-    VR_VARIANT_INTEGRATOR = 1,        // a global-majorant / ray-marching integrator was asked for
-    VR_VARIANT_ENV_DIVISION = 2,      // the environment's warp table failed env_cdf_kernel's check (thresholds below 2^-76: vr_math.h div_core does not apply)
-    VR_VARIANT_DENSITY_SCALE = 4,     // density scale outside [2^-16, 2^24] (the clean march divides by majorants without rescaling)
-    VR_VARIANT_GRID_FORMS = 8         // emission grid with a dense grid on either side, or brick grids of different layouts (no paired atlas)
-};
-int pathtrace_variant_of(const SceneParams& P, int* why);
-// fast_math: the opt-in tolerance-mode kernels (hardware transcendentals, reciprocal division; vr_math.h VR_FAST_MATH); the default
-// kernels are bit-identical to the CPU oracle
 
+// tonemap.glsl:29-36 in place
+void launch_tonemap(float* fb, int32_t w, int32_t h, float exposure, float gamma, hipStream_t stream);
+
+// multi-GPU shard helpers: copy owned 16x16 tiles frame <-> compact tile-major buffer (256 texels per tile)
+void launch_pack_tiles(const float* fb, int32_t w, int32_t h, const int32_t* tiles, int32_t n_tiles, float* packed, hipStream_t stream);
+void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_tiles, float* fb, int32_t w, int32_t h, hipStream_t stream);
+// ---- vr_setup.hip ----------------------------------------------------------------------------------------------------------------------------
 // env_setup.glsl:18-34 + glGenerateMipmap (environment.cpp:27-31): importance pyramid of a dim x dim map
 void launch_build_impmap(const float* envmap_rgba, int32_t env_w, int32_t env_h, int32_t dim, float* pyramid, hipStream_t stream);
 
@@ -80,7 +91,7 @@ void launch_build_env_cdf(const float* pyramid, int32_t dim, float* table, uint3
 void launch_majorants(const SceneParams& P, const uint32_t* range_words_all_mips, const int32_t nb[3], const int32_t mip_off[4], int32_t n_mips,
                       const int32_t mshift[3], float* out_padded, uint16_t* out16_padded, hipStream_t stream);      // out16: the raw fp16 range maxima, same layout
 
-// Dense -> brick encoder on the device (Volume::to_brick_grid / commit(), src/renderer.cpp:63); see vr_kernels.hip.
+// Dense -> brick encoder on the device (Volume::to_brick_grid / commit(), src/renderer.cpp:63); see vr_setup.hip.
 // ranges: range[nb] (fp16x2 words), flag[nb] (range is not a single value: the voxels matter)
 void launch_encode_ranges(const float* dense, const int32_t dim[3], const int32_t nb[3], uint32_t* range, uint32_t* flag, hipStream_t stream);
 void launch_encode_bricks(const float* dense, const int32_t dim[3], const int32_t nb[3], const uint32_t* range, const uint32_t* flag,
@@ -92,14 +103,7 @@ void launch_pair_atlas(const uint8_t* atlas_density, const uint8_t* atlas_emissi
 
 // decoded float atlas (one float per atlas byte: rmin + unorm8(b) * rdiff of its brick), used by transfer-function renders
 void launch_decode_atlas(const float* rng, const uint8_t* atlas, float* out, size_t n_records, hipStream_t stream);
-
-// tonemap.glsl:29-36 in place
-void launch_tonemap(float* fb, int32_t w, int32_t h, float exposure, float gamma, hipStream_t stream);
-
-// multi-GPU shard helpers: copy owned 16x16 tiles frame <-> compact tile-major buffer (256 texels per tile)
-void launch_pack_tiles(const float* fb, int32_t w, int32_t h, const int32_t* tiles, int32_t n_tiles, float* packed, hipStream_t stream);
-void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_tiles, float* fb, int32_t w, int32_t h, hipStream_t stream);
-
+// ---- vr_probe.hip, vr_fastprobe.hip ---------------------------------------------------------------------------------------------------------
 // unit-test probe: out[i] = f(a[i], b[i]) with the device build of vr_math.h
 // fn: 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin 9 a/b 10 sqrt 11 fma(a,b,a) 12 float(u8)/255 13 sincos 14 a*b+a 15 half->float
 //     16 rcp_exact(a) 17 rcp3_exact((a, b, a)).y; 18.. : vr_math_probe.h

@@ -1,0 +1,186 @@
+// vr_filters.hip -- the image-space kernels (gfx950): everything that reads or writes whole frames or tiles of them after the path tracer.
+// The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h), the error estimate of adaptive
+// sampling (vr_adaptive.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
+// the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
+#include <hip/hip_runtime.h>
+
+#include "vr_adaptive.h"
+#include "vr_denoise.h"
+#include "vr_device.h"
+#include "vr_temporal.h"
+
+namespace vr {
+
+// Denoiser (vr_denoise.h).  No LDS: from step 4 on the 5x5 footprint leaves the tile, and the working set fits the Infinity Cache.  Per tap: the
+// colour (one dwordx4), the variance (one dword) and the guide (two dwordx4).
+struct DenoiseSrcDev {
+    const float4* __restrict__ c;
+    const float* __restrict__ v;
+    const float4* __restrict__ g;
+    __device__ __forceinline__ void color(int32_t i, float o[4]) const { unpack4(c[i], o); }
+    __device__ __forceinline__ float var(int32_t i) const { return v[i]; }
+    __device__ __forceinline__ void guide(int32_t i, float o[8]) const { const float4 a = g[2 * i], b = g[2 * i + 1]; unpack4(a, o); unpack4(b, o + 4); }
+};
+// prepare: moments S (W*H*4, Welford's M2 / n) -> the unbiased variance var = S * vscale exactly as vr_variance forms it (0 for n = 1), then
+// the variance of the mean's luminance v (W*H) and the guide (W*H*8) from the features.  counts (a frame of adaptive sampling: one count per
+// raster tile) replaces the scalar n and vscale with the tile's own, formed as the host forms vscale; nullptr = the scalars
+__global__ void __launch_bounds__(256)
+denoise_prepare_kernel(const float4* __restrict__ moments, const float4* __restrict__ features, int32_t W, int32_t H, int32_t n_all, float vscale_all,
+                       const int32_t* __restrict__ counts, float* __restrict__ v, float4* __restrict__ guide) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const int32_t n = counts ? counts[q.tile] : n_all;
+    const float vscale = counts ? variance_scale(n) : vscale_all;
+    const int32_t i = q.py * W + q.px;
+    const float4 m = moments[i];
+    const float var[4] = { n >= 2 ? m.x * vscale : 0.0f, n >= 2 ? m.y * vscale : 0.0f, n >= 2 ? m.z * vscale : 0.0f, n >= 2 ? m.w * vscale : 0.0f };
+    const float4 fa = features[2 * i], fb = features[2 * i + 1];
+    float f[8], g[8];
+    unpack4(fa, f); unpack4(fb, f + 4);
+    denoise_guide(f, g);
+    v[i] = denoise_mean_variance(var, n);
+    guide[2 * i] = pack4(g);
+    guide[2 * i + 1] = pack4(g + 4);
+}
+// one a-trous iteration; vout == nullptr: the variance is not written (the last iteration)
+__global__ void __launch_bounds__(256)
+denoise_atrous_kernel(const float4* __restrict__ cin, const float* __restrict__ vin, const float4* __restrict__ guide, int32_t W, int32_t H,
+                      int32_t step, const DenoiseSigma sg, float4* __restrict__ cout, float* __restrict__ vout) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const DenoiseSrcDev src{ cin, vin, guide };
+    float o[4], ov;
+    denoise_atrous_pixel(src, W, H, q.px, q.py, step, sg, o, ov);
+    const int32_t i = q.py * W + q.px;
+    cout[i] = pack4(o);
+    if (vout) vout[i] = ov;
+}
+void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, const int32_t* counts, float* v, float* guide,
+                            hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(moments),
+                       reinterpret_cast<const float4*>(features), W, H, n, vscale, counts, v, reinterpret_cast<float4*>(guide));
+}
+void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
+                           float* cout, float* vout, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(denoise_atrous_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(cin), vin,
+                       reinterpret_cast<const float4*>(guide), W, H, step, sg, reinterpret_cast<float4*>(cout), vout);
+}
+
+// Temporal accumulation (vr_temporal.h temporal_pixel), between prepare and the iterations.
+// Reads the pixel's colour, v and the guide's coverage and depth (52 B), gathers up to four taps of the previous history -- a tap is two dwordx4:
+// the colour and (V, N, K, D), fetched only after the tap was found inside the frame -- and writes the pixel's new history (32 B) into the other
+// half of the ping-pong pair, plus V over the pixel's own v, where the iterations read it.  No LDS, no atomics; the only loops are the 2 x 2 taps.
+struct TemporalHistDev {
+    const float4* __restrict__ c;
+    const float4* __restrict__ s;
+    __device__ __forceinline__ void color(int32_t i, float o[4]) const { unpack4(c[i], o); }
+    __device__ __forceinline__ void record(int32_t i, float o[4]) const { unpack4(s[i], o); }
+};
+__global__ void __launch_bounds__(256)
+denoise_temporal_kernel(const float4* __restrict__ color, float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ hc,
+                        const float4* __restrict__ hs, int32_t have, int32_t same_cam, const TemporalCamera cur, const TemporalCamera prev, int32_t W, int32_t H,
+                        float alpha, float4* __restrict__ oc, float4* __restrict__ os) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float c[4];
+    unpack4(color[i], c);
+    const TemporalHistDev hist{ hc, hs };
+    float C[4], S[4];
+    temporal_pixel(hist, have != 0, same_cam != 0, cur, prev, W, H, q.px, q.py, c, v[i], guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S);
+    oc[i] = pack4(C);
+    os[i] = pack4(S);
+    v[i] = S[0];
+}
+void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
+                             const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
+                             hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    const bool have = hist_color && hist_record;
+    hipLaunchKernelGGL(denoise_temporal_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
+                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
+                       have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
+}
+
+// Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile; each lane forms e_p of its pixel (-inf outside
+// the frame: the identity of the max), a wave64 max by xor shuffles, the four waves' maxima through LDS, and lane 0 writes the tile's value.
+// Max is exact, so the order of the reduction does not matter.
+__global__ void __launch_bounds__(256)
+adaptive_error_kernel(const float4* __restrict__ fb, const float4* __restrict__ moments, const int32_t* __restrict__ tiles, const int32_t* __restrict__ counts,
+                      int32_t W, int32_t H, float* __restrict__ out) {
+    __shared__ float wave_max[4];
+    const int32_t tile = tiles[blockIdx.x], n = counts[blockIdx.x];
+    const TilePixel q = wave_tiled_pixel(tile, threadIdx.x, W);
+    float e = -inf_();
+    if (q.px < W && q.py < H) {
+        const size_t i = (size_t)q.py * W + q.px;
+        float mu[4], S[4];
+        unpack4(fb[i], mu); unpack4(moments[i], S);
+        e = adaptive_pixel_error(mu, S, n);
+    }
+    for (int32_t d = 32; d > 0; d >>= 1) e = adaptive_max(e, __shfl_xor(e, d, 64));
+    if (q.lane == 0) wave_max[q.sub] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = adaptive_max(adaptive_max(wave_max[0], wave_max[1]), adaptive_max(wave_max[2], wave_max[3]));
+}
+void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,
+                           hipStream_t stream) {
+    if (n_tiles <= 0 || W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(adaptive_error_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, reinterpret_cast<const float4*>(fb),
+                       reinterpret_cast<const float4*>(moments), tiles, counts, W, H, out);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// tonemap.glsl:13-36
+__device__ __forceinline__ float hable(float x) {
+    const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f;
+    return ((x * (A * x + C * B) + D * E) / (x * (A * x + B) + D * F)) - E / F;
+}
+__global__ void __launch_bounds__(256)
+tonemap_kernel(float* __restrict__ fb, int32_t n, float exposure, float inv_gamma) {
+    const int32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float4* p = reinterpret_cast<float4*>(fb) + i;
+    float4 c = *p;
+    const float hw = hable(11.2f);
+    c.x = sanitize(pow_(hable(exposure * c.x) / hw, inv_gamma));
+    c.y = sanitize(pow_(hable(exposure * c.y) / hw, inv_gamma));
+    c.z = sanitize(pow_(hable(exposure * c.z) / hw, inv_gamma));
+    c.w = sanitize(c.w);
+    *p = c;
+}
+void launch_tonemap(float* fb, int32_t w, int32_t h, float exposure, float gamma, hipStream_t stream) {
+    const int32_t n = w * h;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(tonemap_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fb, n, exposure, 1.0f / gamma);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// tile <-> frame copies for the sharded framebuffer
+__global__ void __launch_bounds__(256)
+pack_tiles_kernel(const float* __restrict__ fb, int32_t w, int32_t h, const int32_t* __restrict__ tiles, float* __restrict__ packed) {
+    const TilePixel q = raster_in_tile_pixel(tiles[blockIdx.x], threadIdx.x, w);
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q.px < w && q.py < h) c = reinterpret_cast<const float4*>(fb)[(size_t)q.py * w + q.px];
+    reinterpret_cast<float4*>(packed)[(size_t)blockIdx.x * 256 + threadIdx.x] = c;
+}
+__global__ void __launch_bounds__(256)
+unpack_tiles_kernel(const float* __restrict__ packed, const int32_t* __restrict__ tiles, float* __restrict__ fb, int32_t w, int32_t h) {
+    const int32_t tile = tiles[blockIdx.x];
+    if (tile < 0) return;             // padding entry
+    const TilePixel q = raster_in_tile_pixel(tile, threadIdx.x, w);
+    if (q.px < w && q.py < h)
+        reinterpret_cast<float4*>(fb)[(size_t)q.py * w + q.px] = reinterpret_cast<const float4*>(packed)[(size_t)blockIdx.x * 256 + threadIdx.x];
+}
+void launch_pack_tiles(const float* fb, int32_t w, int32_t h, const int32_t* tiles, int32_t n_tiles, float* packed, hipStream_t stream) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(pack_tiles_kernel, dim3(n_tiles), dim3(256), 0, stream, fb, w, h, tiles, packed);
+}
+void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_tiles, float* fb, int32_t w, int32_t h, hipStream_t stream) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(unpack_tiles_kernel, dim3(n_tiles), dim3(256), 0, stream, packed, tiles, fb, w, h);
+}
+
+}  // namespace vr

@@ -1,0 +1,251 @@
+// vr_launch.hip -- launch of the volume path tracer (gfx950): launch_pathtrace and launch_features.
+//
+// pathtrace_kernel (the hot path): the per-path code -- the reference's trace_path and everything it calls, restated as a state
+// machine -- is in vr_trace.h, its scheduler (persistent wavefronts that pull work units of 8x8 pixels x 8 samples) in vr_pathtrace.h and
+// its compiled variants in vr_pathtrace.hip; this file chooses the variant, sizes the launch and launches it.
+// Radiance per (pixel, sample) goes to a sample pool; accumulate_kernel folds it into the RGBA32F running mean in sample
+// order, which makes the result bit-identical to the reference's one-dispatch-per-sample loop (renderer.cpp:138-140,
+// pathtracer_brick.glsl:36).  MFMA is not used: there is no dense contraction on this path.
+//
+// Also here: the integrators that run one thread per (pixel, sample) item -- direct volume rendering (common.glsl:571-591)
+// and ray marching --, which fill the same sample pool, and the denoiser's feature pass.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <map>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+
+#include "vr_device.h"
+#include "vr_pathtrace.h"
+
+namespace vr {
+
+// INTEGRATOR 2 (direct volume rendering, dvr_sample) and 3 (trace_path with the ray-marching trackers, raymarch_path_sample): one thread per
+// (pixel, sample) item in queue position order, same sample-pool layout as the path-tracing kernel
+template <int INTEGRATOR>
+__global__ void __launch_bounds__(256)
+item_kernel(const SceneParams P, float* __restrict__ sbuf, const LaunchDesc D) {
+    const uint32_t per_unit = (uint32_t)(D.spu * 64);
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t u = g / per_unit, item = g - u * per_unit;
+    if (u >= D.n_units) return;
+    const WorkUnit wu = make_unit(D, P.u.resolution[0], u, sbuf);
+    if ((int32_t)item >= wu.n_items) return;
+    const int32_t px = wu.px0 + (int32_t)(item & 7u), py = wu.py0 + (int32_t)((item >> 3) & 7u);
+    if (px >= P.u.resolution[0] || py >= P.u.resolution[1]) return;
+    float L[4];
+    if (INTEGRATOR == 2) dvr_sample(P, px, py, wu.first_sample + (int32_t)(item >> 6), L);
+    else raymarch_path_sample(P, px, py, wu.first_sample + (int32_t)(item >> 6), L);
+    reinterpret_cast<float4*>(sbuf)[wu.base + item] = pack4(L);
+}
+
+// Running mean over the samples of one launch, in sample order (pathtracer_brick.glsl:36): one workgroup per listed tile (tiles == nullptr: all
+// tiles), one thread per pixel.  The mean is accumulate_sample's arithmetic (vr_trace.h).  MOMENTS (variance = 1): also the per-channel second
+// moments, Welford in the running-mean form, S_k = M2_k / k, in a W*H*4 buffer beside the colour.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256)
+accumulate_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, float* __restrict__ moments, const int32_t* __restrict__ tiles, int32_t n_tiles,
+                  int32_t W, int32_t H, int32_t first_sample, int32_t n_samples, int32_t spu) {
+    const TilePixel q = wave_tiled_pixel(tiles ? tiles[blockIdx.x] : (int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    float4* texel = reinterpret_cast<float4*>(fb) + (size_t)q.py * W + q.px;
+    float4* mtexel = MOMENTS ? reinterpret_cast<float4*>(moments) + (size_t)q.py * W + q.px : nullptr;
+    float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, S[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if (first_sample > 1) {
+        unpack4(*texel, acc);
+        if (MOMENTS) unpack4(*mtexel, S);
+    }
+    const float4* sb = reinterpret_cast<const float4*>(sbuf);
+    for (int32_t k = 0; k < n_samples; ++k) {
+        const int32_t chunk = k / spu, sl = k - chunk * spu;
+        float L[4];
+        unpack4(sb[pool_slot<size_t>((size_t)chunk, n_tiles, (size_t)blockIdx.x, (uint32_t)q.sub, spu, (size_t)sl, (uint32_t)q.lane)], L);
+        const float a = 1.0f / (float)(first_sample + k);
+        for (int32_t c = 0; c < 4; ++c) {
+            const float x = sanitize(L[c]);
+            const float mu = acc[c], mu1 = mix_(mu, x, a);
+            if (MOMENTS) S[c] = mix_(S[c], (x - mu) * (x - mu1), a);
+            acc[c] = mu1;
+        }
+    }
+    *texel = pack4(acc);
+    if (MOMENTS) *mtexel = pack4(S);
+}
+
+// Denoiser features (vr_trace.h feature_pixel): one thread per pixel of the renderer's tiles (tiles == nullptr: all tiles), all `spp` samples in a loop,
+// laid out like accumulate_kernel.
+// out: W*H*8 floats.  The first segment of the DDA tracker only, so a few registers' worth of state: no scheduler, no sample pool.
+template <bool TF>
+__global__ void __launch_bounds__(256)
+features_kernel(const SceneParams P, const int32_t* __restrict__ tiles, int32_t spp, float* __restrict__ out, uint32_t* __restrict__ status) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const TilePixel q = wave_tiled_pixel(tiles ? tiles[blockIdx.x] : (int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    float f[8];
+    if (!feature_pixel<TF>(P, q.px, q.py, spp, f)) atomicOr(status, kFeatureLostStatus);      // a sample over its step budget (vr_trace.h feature_sample)
+    float4* o = reinterpret_cast<float4*>(out) + 2u * ((size_t)q.py * W + q.px);
+    o[0] = pack4(f);
+    o[1] = pack4(f + 4);
+}
+void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream) {
+    if (n_tiles <= 0 || spp <= 0) return;
+    if (P.u.use_tf) hipLaunchKernelGGL(features_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
+    else hipLaunchKernelGGL(features_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
+}
+
+// Units of 8 samples x 64 pixels, except on the dense-grid kernel, whose long paths (128 bounces, every camera ray scatters) fill
+// the pools better from units of 4: c4 +1.3 %, c2 +-0, c3 -1 % (profiles/r2x_occupancy_recheck.txt) -- and, round 4, on the emission kernel:
+// c5cloud +1 %, c5full +0.5 % (profiles/r4d_*)
+constexpr int32_t kMaxSamplesPerUnit = 8;
+static int32_t samples_per_unit(const PathtraceTuning& T, int variant) { return T.samples_per_unit > 0 ? T.samples_per_unit : ((variant == 1 || variant == 2 || variant == 4) ? 4 : kMaxSamplesPerUnit); }
+constexpr int kPtVariants = 5;
+
+PathtraceTuning default_tuning() {
+    static std::once_flag once;
+    static int32_t env_spu = 0, env_blocks = 0;       // diagnostics only
+    std::call_once(once, [] {
+        if (const char* e = getenv("VR_SPU")) env_spu = std::max(1, atoi(e));
+        if (const char* e = getenv("VR_BLOCKS_PER_CU")) env_blocks = std::max(0, atoi(e));
+    });
+    PathtraceTuning T;
+    T.samples_per_unit = env_spu;
+    T.blocks_per_cu = env_blocks;
+    return T;
+}
+
+size_t pathtrace_pool_floats(const PathtraceTuning& T, int32_t n_tiles, int32_t n_samples) {
+    // the samples are rounded up to whole units: sized for whichever unit size a variant may use (samples_per_unit)
+    size_t padded = 0;
+    for (int variant = 0; variant < kPtVariants; ++variant) {
+        const int32_t spu = std::min(n_samples, samples_per_unit(T, variant));
+        padded = std::max(padded, (size_t)((n_samples + spu - 1) / spu) * (size_t)spu);
+    }
+    return padded * (size_t)n_tiles * 4u * 64u * 4u;
+}
+
+// the kernel variants live in vr_pathtrace.hip, one compilation each, in two arithmetic modes (bit-exact / tolerance)
+extern "C" {
+#define VR_PT_DECL(N) \
+    int vr_pt_occupancy_##N(int tf, int stats); \
+    void vr_pt_launch_##N(int tf, int stats, unsigned grid, hipStream_t stream, const void* P, float* sbuf, float* cold_ws, const void* D, const void* S, uint32_t* status, unsigned long long* stats_buf);
+VR_PT_DECL(0) VR_PT_DECL(1) VR_PT_DECL(2) VR_PT_DECL(3) VR_PT_DECL(4) VR_PT_DECL(0_fast) VR_PT_DECL(1_fast) VR_PT_DECL(2_fast) VR_PT_DECL(3_fast) VR_PT_DECL(4_fast)
+#undef VR_PT_DECL
+}
+typedef int (*PtOccupancy)(int, int);
+typedef void (*PtLaunch)(int, int, unsigned, hipStream_t, const void*, float*, float*, const void*, const void*, uint32_t*, unsigned long long*);
+static const PtOccupancy kPtOccupancy[2][kPtVariants] = { { vr_pt_occupancy_0, vr_pt_occupancy_1, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 },
+                                                          { vr_pt_occupancy_0_fast, vr_pt_occupancy_1_fast, vr_pt_occupancy_2_fast, vr_pt_occupancy_3_fast, vr_pt_occupancy_4_fast } };
+static const PtLaunch kPtLaunch[2][kPtVariants] = { { vr_pt_launch_0, vr_pt_launch_1, vr_pt_launch_2, vr_pt_launch_3, vr_pt_launch_4 },
+                                                    { vr_pt_launch_0_fast, vr_pt_launch_1_fast, vr_pt_launch_2_fast, vr_pt_launch_3_fast, vr_pt_launch_4_fast } };
+
+// which compiled variant serves a scene (see vr_pathtrace.hip), and why -- `why` is a mask of PathtraceVariantReason (vr_device.h): the run-time variant (3) is an
+// order of magnitude slower than the kernels of one scene kind on some scenes (one copy of the hot pair, general forms only, everything decided per wavefront), so a
+// scene that lands there for a reason its caller did not ask for is told so (launch_pathtrace, vr_get_int "kernel_variant_reason")
+int pathtrace_variant_of(const SceneParams& P, int* why) {
+    // (an environment whose warp table failed the check of env_cdf_kernel -- thresholds below 2^-76: the kernels of one scene kind divide by vr_math.h div_core there --
+    // goes to the run-time variant, which divides in full; RendererHIP::fill_params pairs no atlases for it)
+    // -- and so does a density scale outside [2^-16, 2^24]: the CLEAN form of the march divides by majorants = density_scale x an fp16 number (vr_trace.h march_finish)
+    const bool scale_ok = P.u.vol_density_scale >= 1.0f / 65536.0f && P.u.vol_density_scale <= 16777216.0f;
+    int reason = 0;
+    if (P.u.integrator != 0) reason |= VR_VARIANT_INTEGRATOR;
+    if (!P.env_div_safe) reason |= VR_VARIANT_ENV_DIVISION;
+    if (!scale_ok) reason |= VR_VARIANT_DENSITY_SCALE;
+    int variant;
+    if (reason) variant = 3;
+    // variant 2: both grids in brick form -- and, when the kernels are built for the paired atlas, sharing one (same brick layout: RendererHIP::commit)
+    // (4 = 2 compiled for majorant levels 0-1 in 4x4x4-cell blocks; every other kernel of a fixed layout reads linear tables: RendererHIP::fill_params only
+    // sets maj_blocked on the views of frames this variant -- or the run-time variant -- serves)
+    else if (P.u.has_emission) {
+        const bool mixed = P.density.dense || P.emission.dense || (VR_PAIRED_ATLAS && !P.paired);
+        if (mixed) reason |= VR_VARIANT_GRID_FORMS;
+        variant = mixed ? 3 : (P.density.maj_blocked ? 4 : 2);
+    } else variant = P.density.dense ? 1 : 0;
+    if (why) *why = reason;
+    return variant;
+}
+static int pathtrace_variant(const SceneParams& P) {
+    int why = 0;
+    const int variant = pathtrace_variant_of(P, &why);
+    // the two reasons a caller cannot see coming: said once per process, on stderr
+    if (why & (VR_VARIANT_ENV_DIVISION | VR_VARIANT_DENSITY_SCALE)) {
+        static std::once_flag once;
+        std::call_once(once, [&] {
+            fprintf(stderr, "volren_amd: note: this scene is rendered by the run-time kernel variant (slower; results unchanged):%s%s\n",
+                    (why & VR_VARIANT_ENV_DIVISION) ? " the environment's warp table has thresholds below 2^-76 (vr_get_int env_div_safe = 0);" : "",
+                    (why & VR_VARIANT_DENSITY_SCALE) ? " the density scale lies outside [2^-16, 2^24];" : "");
+        });
+    }
+    return variant;
+}
+
+// resident workgroups of a kernel instance on the CURRENT device: occupancy query x CU count, cached per (device, instance)
+static int resident_blocks(const PathtraceTuning& T, int mode, int variant, bool tf, bool stats) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 1024;
+    static std::mutex mu;
+    static std::map<uint32_t, std::pair<int, int>> cache;            // key -> (CUs, workgroups per CU)
+    const uint32_t key = ((uint32_t)dev << 8) | ((uint32_t)mode << 5) | ((uint32_t)variant << 2) | (tf ? 2u : 0u) | (stats ? 1u : 0u);
+    std::pair<int, int> v;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = cache.find(key);
+        if (it == cache.end()) {
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+            it = cache.emplace(key, std::make_pair(cus, kPtOccupancy[mode][variant](tf, stats))).first;
+        }
+        v = it->second;
+    }
+    const int per_cu = T.blocks_per_cu > 0 ? T.blocks_per_cu : v.second;
+    return std::min(v.first * per_cu, kMaxWorkgroups * 4 / kWgWaves);
+}
+
+size_t pathtrace_workspace_floats() { return kColdMainFloats + (size_t)kMaxWorkgroups * 4u * (size_t)kColdSideWaveFloats; }      // cold state of 4 wavefronts per resident workgroup: main slots, then the side array
+
+void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
+                      int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math, hipEvent_t ev_kernel_begin, hipEvent_t ev_kernel_end,
+                      float* moments) {
+    if (n_tiles <= 0 || n_samples <= 0) return;
+    SchedParams S;
+    for (int i = 0; i < ST_COUNT; ++i) S.thr[i] = T.thr[i];
+    LaunchDesc D;
+    D.tiles = tiles; D.n_tiles = n_tiles; D.first_sample = first_sample; D.n_samples = n_samples;
+    const int variant = pathtrace_variant(P);
+    D.spu = std::min(n_samples, samples_per_unit(T, variant));
+    const int32_t chunks = (n_samples + D.spu - 1) / D.spu;
+    // item indices are 32-bit (WorkUnit::base, the sample pool's slots): RendererHIP::samples_per_launch sizes sub-launches below that; anything else is a caller's bug
+    if ((uint64_t)chunks * (uint64_t)n_tiles * 4u * (uint64_t)(D.spu * 64) > 0xFFFFFFFFull)
+        throw std::runtime_error("launch_pathtrace: " + std::to_string(n_tiles) + " tiles x " + std::to_string(n_samples) + " samples do not fit the 32-bit item index of one launch");
+    D.n_units = (uint32_t)chunks * (uint32_t)n_tiles * 4u;
+    D.chunks = (uint32_t)chunks;
+    D.seg_len = (D.n_units + kQueueSegments - 1u) / kQueueSegments;
+    D.unit_counter = unit_counter;
+    S.max_iters = kMaxIdleIters;
+    // lanes that must stand at a tentative collision before the collision code runs while others still march (vr_pathtrace.h):
+    // measured optimum 24 (smoke.brick +0.5 %, dense +0.7 %, sparse + emission +2...3.5 %), 32 with a transfer function, whose
+    // collision code (8 corner taps + LUT) is the dearest (+4.4 %); profiles/r2ab_collide_threshold.txt
+    // (round 4: 32 also with an emission grid, whose collision code carries two stochastic taps: c5cloud +0.8 %, c5full +1 %, profiles/r4a_*)
+    if (S.thr[ST_COLLIDE] <= 0) S.thr[ST_COLLIDE] = (P.u.use_tf || P.u.has_emission) ? 32 : 24;
+    const bool tf = P.u.use_tf != 0, stats = T.stats != nullptr;
+    const int mode = fast_math ? 1 : 0;
+    const int blocks = resident_blocks(T, mode, variant, tf, stats);
+    const uint32_t groups_needed = (D.n_units + (uint32_t)kWgWaves - 1u) / (uint32_t)kWgWaves;      // a wavefront per unit at least
+    const dim3 grid((unsigned)std::min<uint32_t>((uint32_t)blocks, groups_needed > 0 ? groups_needed : 1u)), block(256);
+    if (P.u.integrator == 3 || (P.u.integrator == 2 && P.u.use_tf)) {
+        const uint64_t items = (uint64_t)D.n_units * (uint64_t)(D.spu * 64);
+        const auto integrate = P.u.integrator == 2 ? item_kernel<2> : item_kernel<3>;
+        hipLaunchKernelGGL(integrate, dim3((unsigned)((items + 255) / 256)), block, 0, stream, P, sample_pool, D);
+    } else {
+        (void)hipMemsetAsync(unit_counter, 0, kQueueSegments * sizeof(uint32_t), stream);
+        if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
+        kPtLaunch[mode][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats);
+        if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
+    }
+    const auto accumulate = moments ? accumulate_kernel<true> : accumulate_kernel<false>;
+    hipLaunchKernelGGL(accumulate, dim3((unsigned)n_tiles), block, 0, stream, sample_pool, fb, moments, tiles, n_tiles, P.u.resolution[0], P.u.resolution[1],
+                       first_sample, n_samples, D.spu);
+}
+
+}  // namespace vr

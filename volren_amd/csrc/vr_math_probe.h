@@ -1,10 +1,10 @@
-// vr_math_probe.h -- TEST HOOK: one numbered entry per function of vr_math.h, for the device probe kernels (vr_kernels.hip) and for the host build of
+// vr_math_probe.h -- TEST HOOK: one numbered entry per function of vr_math.h, for the device probe kernels (vr_probe.hip) and for the host build of
 // the same header (tests/hostkernel/math_host.cpp).  No render includes this file.
 //
 // r = f(x, y).  Integer arguments travel as the BIT PATTERN of a float operand ("bits(y)"), integer results as the bit pattern of the returned float, so
 // that no entry converts an unchecked float to an integer.  Codes (the tests' CPU reference states the same table independently, in C):
 //    0 log_  1 sin_  2 cos_  3 tan_  4 acos_  5 atan2_(x, y)  6 exp_  7 pow_(x, y)  8 asin_  9 x / y  10 sqrt_  11 fma_(x, y, x)  12 float(u8) / 255
-//   13 sincos_: s * y + c  14 x * y + x (two roundings)  15 half2float(bits(x))  16 rcp_exact  17 rcp3_exact((x, y, x)).y (vr_kernels.hip only)
+//   13 sincos_: s * y + c  14 x * y + x (two roundings)  15 half2float(bits(x))  16 rcp_exact  17 rcp3_exact((x, y, x)).y (vr_probe.hip only)
 //   18 sincos_: s   19 sincos_: c   20 neg_log_1m   21 log_unit_
 //   22 floor2i -> int   23 voxel_index(x, bits(y)) -> int   24 round_mip -> int   25 round_mip_q(bits(x)) -> int   26 round_half_even -> int
 //   27 scale2(x, bits(y))   28 sanitize   29 min_(x, y)   30 max_(x, y)   31 clamp_(x, y, 1)   32 clamp_(x, 0, y)

@@ -11,6 +11,7 @@
 
 #include <type_traits>
 
+#include "vr_tiles.h"
 #include "vr_trace.h"
 
 namespace vr {
@@ -22,7 +23,7 @@ struct SchedParams {
 
 // Persistent wavefronts.  The frame's work is cut into units = one 8x8 pixel tile x `spu` consecutive samples
 // (64*spu items); unit u = ((chunk * n_tiles + tile_slot) * 4 + sub_tile) and its items occupy slots
-// [u*64*spu, (u+1)*64*spu) of the sample buffer.  Every wavefront pulls units from a global queue and refills
+// [u*64*spu, (u+1)*64*spu) of the sample buffer (vr_tiles.h: pool_slot, and the sub-tile's place in the frame).  Every wavefront pulls units from a global queue and refills
 // idle lanes item by item, WITHOUT waiting for its other lanes to finish: the only drain is at the end of the launch.
 // The queue is XCD-aware: queue position j enumerates the units tile-major (all sample chunks of a sub-tile are adjacent) and
 // the positions are cut into 8 contiguous segments, one per XCD (workgroups are dealt round-robin to the 8 XCDs, so
@@ -42,19 +43,18 @@ struct LaunchDesc {
     uint32_t* unit_counter;   // kQueueSegments counters, zeroed before the launch
 };
 
+// The unit at queue position j.  Where its sub-tile lies in the frame and where its items lie in the sample pool are vr_tiles.h's to say (the
+// accumulate kernel reads the pool by the same functions); the order of the queue is this file's.
 __device__ __forceinline__ WorkUnit make_unit(const LaunchDesc& D, int32_t W, uint32_t j, float* sbuf) {
     const uint32_t rem = j / D.chunks, chunk = j - rem * D.chunks;        // queue position -> (tile slot, sub-tile), sample chunk
-    const uint32_t u = chunk * ((uint32_t)D.n_tiles * 4u) + rem;
     const uint32_t slot = rem >> 2, sub = rem & 3u;
-    const int32_t tiles_x = (W + 15) >> 4;
-    const int32_t tile = D.tiles ? D.tiles[slot] : (int32_t)slot;
-    const int32_t tx = tile % tiles_x, ty = tile / tiles_x;
+    const TilePixel q = wave_tiled_pixel(D.tiles ? D.tiles[slot] : (int32_t)slot, sub * 64u, W);      // lane 0 of the sub-tile
     WorkUnit wu;
-    wu.px0 = tx * 16 + (int32_t)((sub & 1u) << 3);
-    wu.py0 = ty * 16 + (int32_t)((sub >> 1) << 3);
+    wu.px0 = q.px;
+    wu.py0 = q.py;
     wu.first_sample = D.first_sample + (int32_t)chunk * D.spu;
     wu.n_items = min(D.spu, D.n_samples - (int32_t)chunk * D.spu) * 64;
-    wu.base = u * (uint32_t)(D.spu * 64);
+    wu.base = pool_slot<uint32_t>(chunk, D.n_tiles, slot, sub, D.spu, 0u, 0u);
     wu.out = sbuf;
     return wu;
 }

@@ -2,7 +2,7 @@
 //
 // The temporal part of SVGF (Schied et al. 2017): before the spatial filter of vr_denoise.h runs, the current frame is blended with a history
 // of the frames before it, fetched where the pixel's first-scatter point lay on the screen of the frame that wrote the history.  Per-pixel
-// functions only: the HIP kernel (vr_kernels.hip denoise_temporal_kernel) and the host build of the tests (tests/hostkernel/temporal_host.cpp)
+// functions only: the HIP kernel (vr_filters.hip denoise_temporal_kernel) and the host build of the tests (tests/hostkernel/temporal_host.cpp)
 // run the same code, so the two agree bit for bit.  The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division,
 // sqrt_, floor_); a * b + c below is two roundings unless it is written as one of vr_math.h's dot / mat3_mul / axpy, which are fma chains.
 // A participating medium has no surface: the "depth" is the mean first-scatter distance along the pixel's centre ray.

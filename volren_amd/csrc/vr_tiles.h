@@ -1,0 +1,54 @@
+// vr_tiles.h -- the one definition of how a frame is cut into tiles, and of what follows from it (host + device).
+// A W x H frame (row 0 at the bottom) is cut into 16x16 tiles in raster order, tile = ty * tiles_x + tx.  A workgroup's 256 threads lie in a tile
+//   wave-tiled : as four 8x8 sub-tiles, one per wavefront (sub-tile s at (8 (s & 1), 8 (s >> 1)), lane l at (l & 7, l >> 3) in it) -- every per-pixel
+//                kernel, and the path tracer's work units (vr_pathtrace.h make_unit: a unit is one sub-tile x spu samples); or
+//   raster     : thread t at (t & 15, t >> 4) -- the packed tiles of the sharded framebuffer only, whose texel order is wire format.
+// tests/hostkernel/tiles_host.cpp builds this header for the host.
+#pragma once
+
+#include "vr_math.h"
+
+namespace vr {
+
+// tile grid of a W x H frame
+VR_HD int32_t tiles_x(int32_t W) { return (W + 15) >> 4; }
+VR_HD int32_t tiles_y(int32_t H) { return (H + 15) >> 4; }
+VR_HD int32_t tile_count(int32_t W, int32_t H) { return tiles_x(W) * tiles_y(H); }
+VR_HD int32_t tile_of_pixel(int32_t px, int32_t py, int32_t W) { return (py >> 4) * tiles_x(W) + (px >> 4); }
+
+struct TilePixel {
+    int32_t tile, sub, lane;      // raster tile id, 8x8 sub-tile 0..3, lane 0..63 in the sub-tile (wave-tiled layout only: sub = lane = 0 in the raster one)
+    int32_t px, py;               // may lie outside a frame whose size is no multiple of 16: the caller tests px < W && py < H
+};
+
+// wave-tiled layout: thread t (0..255) of the workgroup that serves `tile`
+VR_HD TilePixel wave_tiled_pixel(int32_t tile, uint32_t t, int32_t W) {
+    const int32_t nx = tiles_x(W), sub = (int32_t)(t >> 6), lane = (int32_t)(t & 63u);
+    return TilePixel{ tile, sub, lane, (tile % nx) * 16 + ((sub & 1) << 3) + (lane & 7), (tile / nx) * 16 + ((sub >> 1) << 3) + (lane >> 3) };
+}
+// the OTHER layout, raster in the tile -- pack_tiles_kernel / unpack_tiles_kernel only
+VR_HD TilePixel raster_in_tile_pixel(int32_t tile, uint32_t t, int32_t W) {
+    const int32_t nx = tiles_x(W);
+    return TilePixel{ tile, 0, 0, (tile % nx) * 16 + (int32_t)(t & 15u), (tile / nx) * 16 + (int32_t)(t >> 4) };
+}
+
+// Sample pool, one RGBA32F item per (pixel, sample) of a launch, written by the integrator kernels and read back by the accumulate kernel: the slot
+// of lane `lane` of sub-tile `sub` of the launch's tile_slot-th tile, sample `sample` (0-based) of sample chunk `chunk`.  Work unit u = chunk * (n_tiles * 4) + (tile_slot * 4 + sub) owns the spu * 64 slots from u * spu * 64, sample-major.  I: the index
+// type of the caller -- 32-bit in the path tracer (launch_pathtrace refuses a launch whose slots do not fit), size_t in the accumulate kernel
+template <class I>
+VR_HD I pool_slot(I chunk, int32_t n_tiles, I tile_slot, uint32_t sub, int32_t spu, I sample, uint32_t lane) {
+    const I unit = chunk * ((I)n_tiles * 4u) + (tile_slot * 4u + sub);
+    return unit * (I)(spu * 64) + sample * 64u + lane;
+}
+
+// unbiased variance = S * variance_scale(n) for n >= 2 samples, where S = Welford's M2 / n (the renderer's moments); 0 below (the callers give
+// the variance itself as 0 there, not S * 0: S may be NaN)
+VR_HD float variance_scale(int32_t n) { return n >= 2 ? (float)n / (float)(n - 1) : 0.0f; }
+
+#if defined(__HIPCC__)
+// a texel as the lane code takes it, float[4], and back: one dwordx4 either way
+__device__ __forceinline__ void unpack4(const float4 t, float o[4]) { o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w; }
+__device__ __forceinline__ float4 pack4(const float o[4]) { return make_float4(o[0], o[1], o[2], o[3]); }
+#endif
+
+}  // namespace vr

@@ -6,7 +6,7 @@
 // recursive/looping formulation.  How it is organised is different on purpose: the GLSL runs one dispatch per
 // sample with nested data-dependent loops, which on a 64-wide wavefront leaves most lanes idle most of the
 // time.  Here each lane carries an explicit state and the wavefront repeatedly executes ONE state's code for
-// all lanes that are in it (scheduler in vr_kernels.hip), so that
+// all lanes that are in it (scheduler in vr_pathtrace.h), so that
 //   * the DDA march step is shared by camera/scatter segments (sample_volumeDDA, :458-501) and shadow
 //     segments (transmittanceDDA, :412-455): both are "mode" flags of one loop body,
 //   * lanes are not tied to pixels: a wavefront owns a pool of (pixel, sample) items (one 8x8 tile x a chunk of
@@ -349,7 +349,7 @@ VR_HD int32_t majorant_index(const GridView& g, v3 ipos, int32_t mip) {
     const uint32_t sx = (uint32_t)g.mshift[0] - (uint32_t)mip, sy = (uint32_t)g.mshift[1] - (uint32_t)mip;
     const uint32_t off = majorant_level_offset((uint32_t)(g.mshift[0] + g.mshift[1] + g.mshift[2]), (uint32_t)mip);
     // the layout majorant_kernel wrote the table in (GridView::maj_blocked, a property of the grid since round 5): known at compile time in the kernels built
-    // for one layout -- a kernel is only launched on grids of its layout (vr_kernels.hip pathtrace_variant) -- read from the view otherwise (wave-uniform)
+    // for one layout -- a kernel is only launched on grids of its layout (vr_launch.hip pathtrace_variant) -- read from the view otherwise (wave-uniform)
     const bool blocked = MAJB == 2 ? g.maj_blocked != 0 : MAJB == 1;
     if (CLEAN && VR_MAJ_OUTSIDE_CELL) {
         const uint32_t bx = (uint32_t)cvt_flr(ipos.x) >> sh, by = (uint32_t)cvt_flr(ipos.y) >> sh, bz = (uint32_t)cvt_flr(ipos.z) >> sh;
@@ -358,7 +358,7 @@ VR_HD int32_t majorant_index(const GridView& g, v3 ipos, int32_t mip) {
         return inside ? (int32_t)(off + majorant_cell_index(bx, by, bz, sx, sy, (uint32_t)mip, blocked)) : g.maj_outside;
     }
     // (a level the grid does not have -- mip > n_mips -- needs no test: the table has all four levels and the cells of a missing one hold the "outside" value,
-    // vr_kernels.hip majorant_kernel; VR_MAJ_LEVEL_TEST=1 brings the compare back)
+    // vr_setup.hip majorant_kernel; VR_MAJ_LEVEL_TEST=1 brings the compare back)
     const bool inside = (VR_MAJ_LEVEL_TEST ? (mip <= g.n_mips) : true) & (ipos.x >= 0.0f) & (ipos.x < g.mlim[0]) & (ipos.y >= 0.0f) & (ipos.y < g.mlim[1]) & (ipos.z >= 0.0f) & (ipos.z < g.mlim[2]);
     const uint32_t bx = (uint32_t)(int32_t)ipos.x >> sh, by = (uint32_t)(int32_t)ipos.y >> sh, bz = (uint32_t)(int32_t)ipos.z >> sh;
     return inside ? (int32_t)(off + majorant_cell_index(bx, by, bz, sx, sy, (uint32_t)mip, blocked)) : (VR_MAJ_OUTSIDE_CELL ? g.maj_outside : -1);
@@ -825,7 +825,7 @@ VR_HD v3 lookup_environment(const SceneParams& P, v3 dir) {
 // one level of the descent (common.glsl:118-131: "if (r < p) r /= p; else { pos += 1; r = (r - p) / (1 - p); }" per axis, written
 // as operand selects + ONE division so that a wavefront whose lanes go both ways does not execute two); returns the child 0..3
 // SAFE: the two quotients by vr_math.h div_core -- in the kernels compiled for one scene kind, which are only launched with an environment whose table passed the check
-// when it was built (SceneParams::env_div_safe; vr_kernels.hip pathtrace_variant sends every other environment to the run-time variant, which divides in full).  The
+// when it was built (SceneParams::env_div_safe; vr_launch.hip pathtrace_variant sends every other environment to the run-time variant, which divides in full).  The
 // domain holds by induction over the levels: a threshold is NaN, 0 or in [2^-76, 1]; a coordinate p starts as k 2^-24 and stays +0, NaN or in [2^-99, 1] -- "left"
 // (p < d, so d >= 2^-76) gives p / d in [p, 1); "right" gives (p - d) / (1 - d) with 1 - d >= 2^-24 (d <= p < 1) and p - d zero or at least an ulp of d, >= 2^-99,
 // at most 1 - d.  The exceptions are NaN either way and nothing but their NaN-ness is used afterwards: a NaN threshold (an empty block's 0 / 0), and 0 / 0 when p has
@@ -1091,7 +1091,7 @@ VR_HD bool begin_segment(Hot& h, const SceneParams& P, v3 pos, v3 d, int32_t sha
         const bool clean = (int)(abs_(h.ipos.x) < kCleanBound) & (int)(abs_(h.ipos.y) < kCleanBound) & (int)(abs_(h.ipos.z) < kCleanBound) &
                            (int)(ax * tfar < kCleanBound) & (int)(ay * tfar < kCleanBound) & (int)(az * tfar < kCleanBound) &
                            // ... and for the quotient by div_core (march_finish): DDA steps of moderate length.  (The largest component: a NaN one drops out of the
-                           // maximum and has failed its test above.  The majorants' size is the launch's business: vr_kernels.hip pathtrace_variant.)
+                           // maximum and has failed its test above.  The majorants' size is the launch's business: vr_launch.hip pathtrace_variant.)
                            (int)(amax < kCleanBound) & (int)(amax >= 1.0f / kCleanBound);
         h.far = clean ? tfar : -tfar;
     }
@@ -1201,7 +1201,7 @@ VR_HD void march_load_lds(const SceneParams& P, MarchIO& io, const T* lds, int32
     io.maj2 = majorant_fetch_lds<TF, T>(P.density, io.i2, lds, first, all_resident);
 }
 // CLEAN (and no transfer function): the step back to the collision point, tau / majorant, by vr_math.h div_core.  Its domain: the majorant is density_scale x an fp16
-// range maximum, in [2^-40, 2^40] for the scales the kernels with a CLEAN form are launched with (2^-16 ... 2^24: vr_kernels.hip pathtrace_variant); tau = (what was left) - majorant x dt <= 0 with dt in [2^-22, 2^27] (a clean
+// range maximum, in [2^-40, 2^40] for the scales the kernels with a CLEAN form are launched with (2^-16 ... 2^24: vr_launch.hip pathtrace_variant); tau = (what was left) - majorant x dt <= 0 with dt in [2^-22, 2^27] (a clean
 // segment's |idir| lies in [2^-20, 2^20] on one axis at least and below 2^20 on all: step_dda's bracket is between 0.5 and 65), so tau is +0 or has a modulus of at
 // least an ulp of the smaller operand, >= 2^-25 majorant dt >= 2^-87, and at most majorant dt: the quotient lies in [2^-48, 2^28].  A majorant of 0 only meets a
 // tau of -0 (a free-flight draw of exactly 0 in an empty cell): NaN by either form, and only its NaN-ness is used.
@@ -1404,7 +1404,7 @@ VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const ScenePara
         }
     } else {
         if (rng(h.seed) * h.majorant < d) {
-            // (kernels of one scene kind without a transfer function: both majorants are density_scale x an fp16 number, density_scale in [2^-16, 2^24] -- vr_kernels.hip
+            // (kernels of one scene kind without a transfer function: both majorants are density_scale x an fp16 number, density_scale in [2^-16, 2^24] -- vr_launch.hip
             // pathtrace_variant --, the quotient in [1, 2^40]: div_core's domain.  The lane of a NaN collision point, whose cell majorant is 0, does not get here: 0 < 0.)
             const float ratio = (K::global == 0 && !K::tf) ? div_core(u.vol_majorant, h.majorant) : u.vol_majorant / h.majorant;
             h.Tr *= max_(0.0f, 1.0f - ratio);
