@@ -10,9 +10,11 @@ HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 OBJDIR   := build
 SRCS_CPP := grids.cpp imageio.cpp environment.cpp transferfunc.cpp renderer.cpp sharded.cpp capi.cpp
 PT_VARIANTS := 0 1 2 3 4
+# the kernels that form 32-bit gather offsets once more with 64-bit addresses (vr_pathtrace.hip VR_PT_WIDE: scenes with a table of 4 GiB or more)
+PT_WIDE_VARIANTS := 0 1
 # default-flag HIP objects, one per subsystem (vr_device.h lists their launchers in this order)
 HIP_OBJS := vr_launch.o vr_filters.o vr_setup.o vr_probe.o
-OBJS     := $(HIP_OBJS:%=$(OBJDIR)/%) $(OBJDIR)/vr_fastprobe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
+OBJS     := $(HIP_OBJS:%=$(OBJDIR)/%) $(OBJDIR)/vr_fastprobe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(PT_WIDE_VARIANTS:%=$(OBJDIR)/vr_ptwide_%.o) $(PT_WIDE_VARIANTS:%=$(OBJDIR)/vr_ptwf_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
 # tolerance-mode kernels (opt-in, vr_math.h VR_FAST_MATH): hardware transcendentals, reciprocal division, contraction allowed
 FASTFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-hip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Wno-unused-result -Iinclude -DVR_FAST_MATH=1
 # path-tracing kernels: no SLP vectorisation.  On gfx950 a packed fp32 instruction (v_pk_mul/add/fma_f32) occupies the SIMD for
@@ -42,6 +44,15 @@ $(OBJDIR)/vr_pathtrace_%.o: $(CSRC)/vr_pathtrace.hip $(HDRS)
 $(OBJDIR)/vr_ptfast_%.o: $(CSRC)/vr_pathtrace.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(FASTFLAGS) $(PTFLAGS) -DVR_PT_VARIANT=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(OBJDIR)/vr_ptfast_$*.resources.txt || (cat $(OBJDIR)/vr_ptfast_$*.resources.txt; false)
+
+# ... and the wide builds of both modes
+$(OBJDIR)/vr_ptwide_%.o: $(CSRC)/vr_pathtrace.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(PTFLAGS) -DVR_PT_VARIANT=$* -DVR_PT_WIDE=1 -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(OBJDIR)/vr_ptwide_$*.resources.txt || (cat $(OBJDIR)/vr_ptwide_$*.resources.txt; false)
+
+$(OBJDIR)/vr_ptwf_%.o: $(CSRC)/vr_pathtrace.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(FASTFLAGS) $(PTFLAGS) -DVR_PT_VARIANT=$* -DVR_PT_WIDE=1 -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(OBJDIR)/vr_ptwf_$*.resources.txt || (cat $(OBJDIR)/vr_ptwf_$*.resources.txt; false)
 
 $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)

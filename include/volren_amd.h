@@ -109,7 +109,9 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     scene to variant 3, a mask: 1 integrator != 0, 2 the environment's warp table has thresholds below 2^-76 ("env_div_safe" = 0), 4 density scale outside
  *     [2^-16, 2^24], 8 emission grid with a dense grid / brick grids of different layouts; 0: the scene has a kernel of its own kind).  Reasons 2 and 4 are also
  *     said once per process on stderr: a caller cannot see them coming;  "env_compact" (1: every texel of the environment map is exactly an RGBE number -- a
- *     Radiance file's always are -- and the path tracer fetches them as one dword each; the values are the float map's, bit for bit) */
+ *     Radiance file's always are -- and the path tracer fetches them as one dword each; the values are the float map's, bit for bit);  "kernel_wide" (1: the next
+ *     launch's path-tracing kernel forms 64-bit gather addresses -- a grid table of 4 GiB or more, kernel variants 2 to 4, or "wide_addressing" -- 0: 32-bit byte
+ *     offsets from the tables' bases).  Diagnostic, through vr_set_int: "wide_addressing" (default 0 = by the tables' sizes; 1 = always the 64-bit kernels.  Same results) */
 int vr_set_int(vr_renderer* r, const char* name, int value);
 int vr_get_int(vr_renderer* r, const char* name, int* value);
 int vr_set_float(vr_renderer* r, const char* name, const float* values, int count);

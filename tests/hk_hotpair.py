@@ -1,0 +1,54 @@
+"""ctypes binding of tests/hostkernel/libhotpair_host*.so: collide_finish (vr_trace.h) built for the host, with and without the shortcut for blocked
+shadow rays; the gathers' two addressing forms and the rule that chooses between them.  TEST HARNESS ONLY."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import hk_binding
+
+_DIR = hk_binding._DIR
+_libs = {}
+
+
+def build(shortcut=True):
+    so = os.path.join(_DIR, "libhotpair_host.so" if shortcut else "libhotpair_host_noshortcut.so")
+    src = os.path.join(_DIR, "hotpair_host.cpp")
+    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h")]
+    if not (os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps)):
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2", "-Wno-unknown-pragmas", "-o", so, src]
+        if not shortcut:
+            cmd[1:1] = ["-DVR_SHADOW_BLOCKED_SHORTCUT=0"]
+        subprocess.check_call(cmd)
+    return so
+
+
+def lib(shortcut=True):
+    if shortcut not in _libs:
+        L = C.CDLL(build(shortcut))
+        L.hc_shadow_collide.argtypes = [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
+        L.hc_largest_table_bytes.restype = C.c_ulonglong
+        L.hc_largest_table_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.hc_addressing_forms_differ.restype = C.c_longlong
+        assert L.hc_shortcut_compiled() == (1 if shortcut else 0)
+        _libs[shortcut] = L
+    return _libs[shortcut]
+
+
+def shadow_collide(form, states, shortcut=True):
+    """states: [n][5] uint32 = RNG state, cell majorant, vol_majorant, Tr, density (floats as bits) -> [n][5] = Tr, state, RNG state, tau, mipq"""
+    states = np.ascontiguousarray(states, np.uint32).reshape(-1, 5)
+    out = np.zeros_like(states)
+    assert lib(shortcut).hc_shadow_collide(int(form), states.shape[0], states.ctypes.data, out.ctypes.data) == 0
+    return out
+
+
+def largest_table_bytes(nb=(1, 1, 1), mshift=(3, 3, 3), dim=(0, 0, 0), float_atlas=False, paired=False, tf=False):
+    """vr_scene.h grid_largest_table_bytes of a brick grid of nb bricks, or -- dim given -- of a dense grid of dim voxels"""
+    a, b, c = (np.array(v, np.int32) for v in (nb, mshift, dim))
+    return int(lib().hc_largest_table_bytes(a.ctypes.data, b.ctypes.data, c.ctypes.data, 1 if any(dim) else 0, int(float_atlas), int(paired), int(tf)))
+
+
+def addressing_forms_differ(records, cells):
+    return int(lib().hc_addressing_forms_differ(int(records), int(cells)))

@@ -296,6 +296,7 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
         else if (n == "coalesce_trace") { R.flush_pending(); R.coalesce_trace = v != 0; }
         else if (n == "majorant_layout") { if (v < -1 || v > 1) throw std::runtime_error("majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)"); R.majorant_layout = v; }
         else if (n == "tf_float_atlas") R.tf_float_atlas = v != 0;
+        else if (n == "wide_addressing") { if (v < 0 || v > 1) throw std::runtime_error("wide_addressing: 0 (by the tables' sizes), 1 (always the kernels with 64-bit gather addresses)"); R.tuning.wide_addressing = v; }
         else if (n == "gpu_encoder") R.gpu_encoder = v != 0;
         else if (n == "sample_pool_mb") { if (v < 16 || v > 65536) throw std::runtime_error("sample_pool_mb must be in [16, 65536] (item indices of a sub-launch are 32-bit: < 2^32 RGBA32F items)"); R.sample_pool_bytes = (size_t)v << 20; }
         else if (n == "launch_target_ms") { if (v < 0) throw std::runtime_error("launch_target_ms must be >= 0 (0 = no sizing by time)"); R.launch_target_ms = v; }
@@ -332,6 +333,11 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
             vr::SceneParams P; R.fill_params(P);
             int why = 0; const int variant = vr::pathtrace_variant_of(P, &why);
             *v = n == "kernel_variant" ? variant : why;
+        }
+        else if (n == "wide_addressing") *v = R.tuning.wide_addressing;
+        else if (n == "kernel_wide") {               // the next launch's kernel forms 64-bit gather addresses: forced, a table of 4 GiB or more, or a variant that always does (2, 3, 4)
+            vr::SceneParams P; R.fill_params(P);
+            *v = (vr::pathtrace_wide_of(R.tuning, P) || vr::pathtrace_variant_of(P, nullptr) >= 2) ? 1 : 0;
         }
         else if (n == "env_div_safe") *v = R.environment && R.environment->cdf_div_safe ? 1 : 0;      // the environment's warp table passed env_cdf_kernel's check (vr_math.h div_core)
         else if (n == "env_compact") *v = R.environment && R.environment->envmap_rgbe ? 1 : 0;      // the path tracer fetches the map's texels as RGBE dwords (vr_scene.h SceneParams::env_rgbe)

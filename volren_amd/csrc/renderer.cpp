@@ -518,7 +518,7 @@ const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<i
 bool RendererHIP::LaunchInputs::same_launch_as(const LaunchInputs& o) const {
     return memcmp(&P, &o.P, sizeof P) == 0 && frame == o.frame && maj.density_scale == o.maj.density_scale && maj.tf_version == o.maj.tf_version &&
            maj.wl == o.maj.wl && maj.ww == o.maj.ww && maj.blocked == o.maj.blocked && memcmp(tuning.thr, o.tuning.thr, sizeof tuning.thr) == 0 && tuning.stats == o.tuning.stats &&
-           tuning.samples_per_unit == o.tuning.samples_per_unit && tuning.blocks_per_cu == o.tuning.blocks_per_cu && order_tiles == o.order_tiles &&
+           tuning.samples_per_unit == o.tuning.samples_per_unit && tuning.blocks_per_cu == o.tuning.blocks_per_cu && tuning.wide_addressing == o.tuning.wide_addressing && order_tiles == o.order_tiles &&
            launch_target_ms == o.launch_target_ms && fast_math == o.fast_math && variance == o.variance && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
 }
 

@@ -27,6 +27,7 @@ struct PathtraceTuning {
     unsigned long long* stats = nullptr;      // device buffer of 32 counters: the launch uses the instrumented (STATS) kernels; or null
     int32_t samples_per_unit = 0;             // samples of a work unit; 0 = per kernel variant
     int32_t blocks_per_cu = 0;                // resident workgroups per CU; 0 = from the occupancy query (cached per device)
+    int32_t wide_addressing = 0;              // diagnostic (vr_set_int "wide_addressing"): 1 = the kernels with 64-bit gather addresses whatever the tables' sizes (pathtrace_wide_of)
 };
 PathtraceTuning default_tuning();             // the defaults, with the diagnostic overrides VR_SPU / VR_BLOCKS_PER_CU of the environment (read once)
 size_t pathtrace_pool_floats(const PathtraceTuning& T, int32_t n_tiles, int32_t n_samples);
@@ -49,6 +50,9 @@ enum PathtraceVariantReason : int {
     VR_VARIANT_GRID_FORMS = 8         // emission grid with a dense grid on either side, or brick grids of different layouts (no paired atlas)
 };
 int pathtrace_variant_of(const SceneParams& P, int* why);
+// Kernel variants 0 and 1 form the byte offsets of their gathers into the grids' tables in 32 bits (vr_trace.h table_load) and exist a second time with 64-bit
+// addresses: true when a table such a kernel would index on this scene holds 4 GiB or more -- or when the tuning forces it.  (Variants 2, 3 and 4 are always wide.)
+bool pathtrace_wide_of(const PathtraceTuning& T, const SceneParams& P);
 // fast_math: the opt-in tolerance-mode kernels (hardware transcendentals, reciprocal division; vr_math.h VR_FAST_MATH); the default
 // kernels are bit-identical to the CPU oracle
 // ---- vr_filters.hip --------------------------------------------------------------------------------------------------------------------------

@@ -132,14 +132,20 @@ extern "C" {
     int vr_pt_occupancy_##N(int tf, int stats); \
     void vr_pt_launch_##N(int tf, int stats, unsigned grid, hipStream_t stream, const void* P, float* sbuf, float* cold_ws, const void* D, const void* S, uint32_t* status, unsigned long long* stats_buf);
 VR_PT_DECL(0) VR_PT_DECL(1) VR_PT_DECL(2) VR_PT_DECL(3) VR_PT_DECL(4) VR_PT_DECL(0_fast) VR_PT_DECL(1_fast) VR_PT_DECL(2_fast) VR_PT_DECL(3_fast) VR_PT_DECL(4_fast)
+VR_PT_DECL(0w) VR_PT_DECL(1w) VR_PT_DECL(0w_fast) VR_PT_DECL(1w_fast)      // 64-bit gather addresses (VR_PT_WIDE)
 #undef VR_PT_DECL
 }
 typedef int (*PtOccupancy)(int, int);
 typedef void (*PtLaunch)(int, int, unsigned, hipStream_t, const void*, float*, float*, const void*, const void*, uint32_t*, unsigned long long*);
-static const PtOccupancy kPtOccupancy[2][kPtVariants] = { { vr_pt_occupancy_0, vr_pt_occupancy_1, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 },
-                                                          { vr_pt_occupancy_0_fast, vr_pt_occupancy_1_fast, vr_pt_occupancy_2_fast, vr_pt_occupancy_3_fast, vr_pt_occupancy_4_fast } };
-static const PtLaunch kPtLaunch[2][kPtVariants] = { { vr_pt_launch_0, vr_pt_launch_1, vr_pt_launch_2, vr_pt_launch_3, vr_pt_launch_4 },
-                                                    { vr_pt_launch_0_fast, vr_pt_launch_1_fast, vr_pt_launch_2_fast, vr_pt_launch_3_fast, vr_pt_launch_4_fast } };
+// [arithmetic mode][wide][variant]; variants 2, 3 and 4 have one build each, which is wide
+static const PtOccupancy kPtOccupancy[2][2][kPtVariants] = { { { vr_pt_occupancy_0, vr_pt_occupancy_1, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 },
+                                                               { vr_pt_occupancy_0w, vr_pt_occupancy_1w, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 } },
+                                                             { { vr_pt_occupancy_0_fast, vr_pt_occupancy_1_fast, vr_pt_occupancy_2_fast, vr_pt_occupancy_3_fast, vr_pt_occupancy_4_fast },
+                                                               { vr_pt_occupancy_0w_fast, vr_pt_occupancy_1w_fast, vr_pt_occupancy_2_fast, vr_pt_occupancy_3_fast, vr_pt_occupancy_4_fast } } };
+static const PtLaunch kPtLaunch[2][2][kPtVariants] = { { { vr_pt_launch_0, vr_pt_launch_1, vr_pt_launch_2, vr_pt_launch_3, vr_pt_launch_4 },
+                                                         { vr_pt_launch_0w, vr_pt_launch_1w, vr_pt_launch_2, vr_pt_launch_3, vr_pt_launch_4 } },
+                                                       { { vr_pt_launch_0_fast, vr_pt_launch_1_fast, vr_pt_launch_2_fast, vr_pt_launch_3_fast, vr_pt_launch_4_fast },
+                                                         { vr_pt_launch_0w_fast, vr_pt_launch_1w_fast, vr_pt_launch_2_fast, vr_pt_launch_3_fast, vr_pt_launch_4_fast } } };
 
 // which compiled variant serves a scene (see vr_pathtrace.hip), and why -- `why` is a mask of PathtraceVariantReason (vr_device.h): the run-time variant (3) is an
 // order of magnitude slower than the kernels of one scene kind on some scenes (one copy of the hot pair, general forms only, everything decided per wavefront), so a
@@ -166,6 +172,13 @@ int pathtrace_variant_of(const SceneParams& P, int* why) {
     if (why) *why = reason;
     return variant;
 }
+// a kernel's 32-bit byte offsets reach every byte of a table smaller than 2^32 bytes (vr_scene.h grid_largest_table_bytes)
+bool pathtrace_wide_of(const PathtraceTuning& T, const SceneParams& P) {
+    if (T.wide_addressing) return true;
+    uint64_t m = grid_largest_table_bytes(P.density, P.paired != 0, P.u.use_tf != 0);
+    if (P.u.has_emission) m = std::max(m, grid_largest_table_bytes(P.emission, P.paired != 0, false));
+    return m >= (1ull << 32);
+}
 static int pathtrace_variant(const SceneParams& P) {
     int why = 0;
     const int variant = pathtrace_variant_of(P, &why);
@@ -182,19 +195,19 @@ static int pathtrace_variant(const SceneParams& P) {
 }
 
 // resident workgroups of a kernel instance on the CURRENT device: occupancy query x CU count, cached per (device, instance)
-static int resident_blocks(const PathtraceTuning& T, int mode, int variant, bool tf, bool stats) {
+static int resident_blocks(const PathtraceTuning& T, int mode, int wide, int variant, bool tf, bool stats) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 1024;
     static std::mutex mu;
     static std::map<uint32_t, std::pair<int, int>> cache;            // key -> (CUs, workgroups per CU)
-    const uint32_t key = ((uint32_t)dev << 8) | ((uint32_t)mode << 5) | ((uint32_t)variant << 2) | (tf ? 2u : 0u) | (stats ? 1u : 0u);
+    const uint32_t key = ((uint32_t)dev << 8) | ((uint32_t)wide << 6) | ((uint32_t)mode << 5) | ((uint32_t)variant << 2) | (tf ? 2u : 0u) | (stats ? 1u : 0u);
     std::pair<int, int> v;
     {
         std::lock_guard<std::mutex> lock(mu);
         auto it = cache.find(key);
         if (it == cache.end()) {
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            it = cache.emplace(key, std::make_pair(cus, kPtOccupancy[mode][variant](tf, stats))).first;
+            it = cache.emplace(key, std::make_pair(cus, kPtOccupancy[mode][wide][variant](tf, stats))).first;
         }
         v = it->second;
     }
@@ -229,8 +242,8 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     // (round 4: 32 also with an emission grid, whose collision code carries two stochastic taps: c5cloud +0.8 %, c5full +1 %, profiles/r4a_*)
     if (S.thr[ST_COLLIDE] <= 0) S.thr[ST_COLLIDE] = (P.u.use_tf || P.u.has_emission) ? 32 : 24;
     const bool tf = P.u.use_tf != 0, stats = T.stats != nullptr;
-    const int mode = fast_math ? 1 : 0;
-    const int blocks = resident_blocks(T, mode, variant, tf, stats);
+    const int mode = fast_math ? 1 : 0, wide = pathtrace_wide_of(T, P) ? 1 : 0;
+    const int blocks = resident_blocks(T, mode, wide, variant, tf, stats);
     const uint32_t groups_needed = (D.n_units + (uint32_t)kWgWaves - 1u) / (uint32_t)kWgWaves;      // a wavefront per unit at least
     const dim3 grid((unsigned)std::min<uint32_t>((uint32_t)blocks, groups_needed > 0 ? groups_needed : 1u)), block(256);
     if (P.u.integrator == 3 || (P.u.integrator == 2 && P.u.use_tf)) {
@@ -240,7 +253,7 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     } else {
         (void)hipMemsetAsync(unit_counter, 0, kQueueSegments * sizeof(uint32_t), stream);
         if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
-        kPtLaunch[mode][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats);
+        kPtLaunch[mode][wide][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats);
         if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
     }
     const auto accumulate = moments ? accumulate_kernel<true> : accumulate_kernel<false>;

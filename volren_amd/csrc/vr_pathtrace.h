@@ -780,9 +780,9 @@ pathtrace_kernel(const KernelArgs A) {
             else {
             march_idle(mio);
             if (is_m) march_prep<K::dense, K::majb, CLEAN>(l, P, mio);
-            if constexpr (kMajCells > 0) march_load_lds<K::tf, MajT>(P, mio, lds_maj, maj_first);
-            else if constexpr (K::maj_reuse) march_load_reuse<K::tf>(P, mio, l);
-            else march_load<K::tf>(P, mio);
+            if constexpr (kMajCells > 0) march_load_lds<K::tf, MajT, K::a32>(P, mio, lds_maj, maj_first);
+            else if constexpr (K::maj_reuse) march_load_reuse<K::tf, K::a32>(P, mio, l);
+            else march_load<K::tf, K::a32>(P, mio);
 #if VR_MARCH_LOADS_PINNED
             // Both majorants must have been REQUESTED before the first is used.  Left alone, the compiler sinks each load into the
             // conditional block of march_finish that consumes it (load, wait, test, load, wait: two dependent round trips); an
@@ -838,7 +838,7 @@ pathtrace_kernel(const KernelArgs A) {
                     ls.mipq = spec ? (l.mipq > 8 ? l.mipq - 8 : 0) : l.mipq;             // collide_finish: mip = max(0, mip - 2)
                     march_idle(pre);
                     if (slot >= 0 && (l.state == ST_MARCH || spec)) march_prep<K::dense, K::majb, CLEAN>(ls, P, pre);
-                    march_load<K::tf>(P, pre);
+                    march_load<K::tf, K::a32>(P, pre);
                     // the tap is used from HERE on as far as the compiler is concerned: left alone it hoists the tap's decode (a conversion and a select) up to the
                     // tap's load -- and waits for it there, before the majorants above have been requested
                     if (VR_EARLY_MARCH == 1) asm volatile("" : "+v"(cio.d.raw), "+v"(cio.d.rmin), "+v"(cio.d.rdiff));

@@ -7,9 +7,13 @@
 //      filled sparse grids of BASELINE configs[4], whose DDA walks then touch a quarter fewer cache lines)
 //   3  everything decided at run time: the global-majorant trackers (common.glsl:333-394, the code the reference compiles out with
 //      USE_DDA) and the one remaining combination, a dense fp16 density grid with an emission grid
+// Variants 0 and 1 form the byte offsets of their gathers into the grids' tables in 32 bits (TraceCfg::a32, vr_trace.h table_load) and are also built with
+// -DVR_PT_WIDE=1: the same kernel with 64-bit gather addresses, for a scene with a table of 4 GiB or more (vr_launch.hip pathtrace_wide_of); those symbols carry a
+// `w` after the variant.  The others always form 64-bit addresses: the emission kernels (2, 4) pay for the 32-bit form with five more scalar spills
+// (profiles/r7a_gather_addressing.txt).
 // Each is built twice: bit-exact arithmetic (the default and the parity target) and, with -DVR_FAST_MATH=1, the opt-in
 // tolerance mode (hardware transcendentals, reciprocal division, contraction; vr_math.h).  A compilation exports two C symbols,
-// vr_pt_occupancy_<variant>[_fast] and vr_pt_launch_<variant>[_fast], for {no TF, TF} x {plain, STATS}.
+// vr_pt_occupancy_<variant>[w][_fast] and vr_pt_launch_<variant>[w][_fast], for {no TF, TF} x {plain, STATS}.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,6 +25,16 @@
 #define VR_PT_SUFFIX _fast
 #else
 #define VR_PT_SUFFIX
+#endif
+#if defined(VR_PT_WIDE) && VR_PT_WIDE
+#if VR_PT_VARIANT >= 2
+#error "variants 2, 3 and 4 have no wide build: they always form 64-bit addresses"
+#endif
+#define VR_PT_WIDTH w
+#define VR_PT_A32 false
+#else
+#define VR_PT_WIDTH
+#define VR_PT_A32 (VR_PT_VARIANT < 2)
 #endif
 
 #if VR_PT_VARIANT == 3 && !defined(VR_BATCH_REGS)
@@ -42,15 +56,15 @@
 namespace vr {
 
 #if VR_PT_VARIANT == 0
-template <bool TF> using Cfg = TraceCfg<TF, 0, 0, 0>;
+template <bool TF> using Cfg = TraceCfg<TF, 0, 0, 0, 0, VR_PT_A32>;
 #elif VR_PT_VARIANT == 1
-template <bool TF> using Cfg = TraceCfg<TF, 0, 0, 1>;
+template <bool TF> using Cfg = TraceCfg<TF, 0, 0, 1, 0, VR_PT_A32>;
 #elif VR_PT_VARIANT == 2
-template <bool TF> using Cfg = TraceCfg<TF, 0, 1, 0>;
+template <bool TF> using Cfg = TraceCfg<TF, 0, 1, 0, 0, VR_PT_A32>;
 #elif VR_PT_VARIANT == 4
-template <bool TF> using Cfg = TraceCfg<TF, 0, 1, 0, 1>;
+template <bool TF> using Cfg = TraceCfg<TF, 0, 1, 0, 1, VR_PT_A32>;
 #else
-template <bool TF> using Cfg = TraceCfg<TF, 2, 2, 2, 2>;
+template <bool TF> using Cfg = TraceCfg<TF, 2, 2, 2, 2, false>;
 #endif
 
 typedef void (*PtKernel)(const KernelArgs);
@@ -61,8 +75,9 @@ static PtKernel pick(bool tf, bool stats) {
 
 }  // namespace vr
 
-#define VR_PT_CAT3(a, b, c) a##b##c
-#define VR_PT_CAT(a, b, c) VR_PT_CAT3(a, b, c)
+#define VR_PT_CAT4(a, b, c, d) a##b##c##d
+#define VR_PT_CAT5(a, b, c, d) VR_PT_CAT4(a, b, c, d)
+#define VR_PT_CAT(a, b, c) VR_PT_CAT5(a, b, VR_PT_WIDTH, c)
 
 extern "C" int VR_PT_CAT(vr_pt_occupancy_, VR_PT_VARIANT, VR_PT_SUFFIX)(int tf, int stats) {
     int per_cu = 0;

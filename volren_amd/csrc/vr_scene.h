@@ -147,6 +147,21 @@ struct GridView {
     int32_t dblk[2];             // blocks per axis (x, y) = ceil(dim / 4)
 };
 
+// Bytes of the largest table of a grid that a path-tracing kernel gathers from: the atlas (bricks: kBrickBlockBytes per record of the grid's box, kPairBlockBytes in a
+// paired atlas; dense: 128 bytes per 4x4x4 block), the decoded float atlas (2 KiB per record) when there is one, and the majorant table (fp16; float under a transfer
+// function).  What decides between a kernel's 32-bit gather offsets and its 64-bit form (vr_launch.hip pathtrace_wide_of).
+VR_SCENE_HD uint64_t grid_largest_table_bytes(const GridView& g, bool paired, bool tf) {
+    uint64_t m = (uint64_t)majorant_table_cells((uint32_t)(g.mshift[0] + g.mshift[1] + g.mshift[2])) * (tf ? 4u : 2u);
+    uint64_t a;
+    if (g.dense) a = (uint64_t)g.dblk[0] * (uint64_t)g.dblk[1] * (uint64_t)((g.dim[2] + 3) / 4) * 128u;
+    else {
+        const uint64_t records = (uint64_t)g.nb[0] * (uint64_t)g.nb[1] * (uint64_t)g.nb[2];
+        a = records * (paired ? kPairBlockBytes : kBrickBlockBytes);
+        if (g.atlas_f32 && records * 2048u > a) a = records * 2048u;
+    }
+    return a > m ? a : m;
+}
+
 struct Uniforms {                // names follow the GLSL uniforms
     int32_t bounces, seed, show_environment;
     float cam_pos[3], cam_fov, cam_transform[9];

@@ -62,9 +62,11 @@ enum LaneState : int32_t {
 #ifndef VR_MAJ_REUSE
 #define VR_MAJ_REUSE 0       /* build-time experiment (round 5, profiles/r5f_*): 0 never (default: c5cloud +-0, c2 -0.6 %), 1 in the kernel for blocked majorant tables (variant 4), 2 in every kernel */
 #endif
-template <bool TF, int GLOBAL, int EMISSION, int DENSE, int MAJB = 0>
+//   A32       the kernel's gathers into the grids' tables form their byte offsets in 32 bits (table_load: every table below 4 GiB, checked per launch) or -- false --
+//             64-bit addresses
+template <bool TF, int GLOBAL, int EMISSION, int DENSE, int MAJB = 0, bool A32 = true>
 struct TraceCfg {
-    static constexpr bool tf = TF;
+    static constexpr bool tf = TF, a32 = A32;
     static constexpr int global = GLOBAL, emission = EMISSION, dense = DENSE, majb = MAJB;
     static constexpr int edense = EMISSION == 1 ? DENSE : 2;      // a kernel with a compiled-in emission grid takes it in the same form as the density grid
     // that kernel, on brick grids, reads both grids from one paired atlas (vr_scene.h): component 1 = density, 2 = emission, 0 = a grid's own atlas
@@ -204,6 +206,23 @@ VR_HD void rng_skip9(uint32_t& s) {
 // (block of brick record i = bytes [640 i, 640 i + 640), vr_scene.h): range and voxel come from one cache line, no dependent pointer chase.
 template <int DENSE>
 VR_HD bool grid_is_dense(const GridView& g) { return DENSE == 2 ? g.dense != nullptr : DENSE == 1; }
+// ---- gather addressing (round 7) -------------------------------------------------------------------------------------------------------------------------------
+// The tables' bases are kernel arguments: wave-uniform, in scalar registers.  A32: the table is smaller than 4 GiB (decided per launch, vr_launch.hip
+// pathtrace_wide_of: the kernels of one scene kind exist in both forms), so a gather's BYTE offset is formed in 32 bits and the load adds it to the base itself --
+// global_load v, v_offset, s[base:base+1] -- instead of the kernel forming a 64-bit address in a vector register pair first: per copy of the hot pair that was a
+// move and two v_lshl_add_u64 for the march's two majorants, and a v_mad_u64_u32, a v_lshlrev_b64, two v_lshl_add_u64 and two fix-ups for the tap's range and voxel
+// (profiles/r7a_gather_addressing.txt).  !A32: the 64-bit address, as before -- what every caller outside the path-tracing kernels' scheduler uses (the lookups
+// of the feature pass, the probes and the other integrators run on grids of any size).  Same element either way.
+template <bool A32, class T>
+VR_HD T table_load(const T* base, uint32_t i) {          // base[i]
+    if (A32) return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (uint32_t)(i * (uint32_t)sizeof(T)));
+    return base[(size_t)i];
+}
+template <bool A32, class T>
+VR_HD T line_load(const uint8_t* base, uint32_t line, uint32_t byte) {      // the T at byte `byte` of the table's 128-byte line `line`
+    if (A32) return *reinterpret_cast<const T*>(base + (uint32_t)((line << 7) + byte));
+    return *reinterpret_cast<const T*>(base + ((size_t)line << 7) + byte);
+}
 struct TapAddr { uint32_t cell, off; bool in; };      // bricks: record index, byte inside the 8^3 block; dense: 4x4x4 block index, voxel inside it
 struct TapData { float rmin, rdiff; uint32_t raw; };  // bricks: range of the brick + the u8; dense: the fp16 bits
 template <int DENSE = 2>
@@ -232,10 +251,28 @@ VR_HD TapAddr tap_addr(const GridView& g, int32_t x, int32_t y, int32_t z) {
 #ifndef VR_TAP_LINE_INDEX
 #define VR_TAP_LINE_INDEX 1
 #endif
-template <int DENSE = 2, int PAIR = 0>
+// A32: the loads in the 32-bit form of table_load / line_load (default builds of the layouts; the build-time experiments keep the 64-bit form)
+#if VR_TAP_LINE_INDEX && VR_BRICK_HEADERS && !defined(VR_TAP_NT) && !defined(VR_DENSE_TAP_NT)
+#define VR_TAP_A32(A32) (A32)
+#else
+#define VR_TAP_A32(A32) false
+#endif
+template <int DENSE = 2, int PAIR = 0, bool A32 = false>
 VR_HD TapData tap_load(const GridView& g, TapAddr a) {
     TapData d;
     VR_TRACE(1, g.atlas ? (const void*)g.atlas : (const void*)g.dense, a.cell, a.off);
+    static_assert(!(A32 && PAIR != 0), "the kernels that read a paired atlas form 64-bit addresses (vr_pathtrace.hip)");
+    if (VR_TAP_A32(A32)) {
+        if (grid_is_dense<DENSE>(g)) {
+            d.rmin = 0.0f; d.rdiff = 0.0f;
+            d.raw = table_load<true>(g.dense, a.cell * 64u + a.off);
+        } else {
+            const uint32_t line = brick_voxel_line(a.off), ln = a.cell * (kBrickBlockBytes / 128u) + line;
+            d.rmin = line_load<true, float>(g.atlas, ln, 0u); d.rdiff = line_load<true, float>(g.atlas, ln, 4u);
+            d.raw = line_load<true, uint8_t>(g.atlas, ln, kBrickLineHeader + a.off - line * kBrickLineVoxels);
+        }
+        return d;
+    }
     if (PAIR != 0) {
         // paired atlas: ten lines of [rmin_d, rdiff_d, rmin_e, rdiff_e | 56 x (density, emission)] per brick
         const uint32_t line = pair_voxel_line(a.off);
@@ -365,14 +402,14 @@ VR_HD int32_t majorant_index(const GridView& g, v3 ipos, int32_t mip) {
 }
 // Unconditional load (cell 0 when outside; the caller discards it then).  TF kernels read the float table (TF-remapped
 // majorants); the others read the raw fp16 range maximum -- half the cache lines -- and scale it themselves (majorant_value).
-template <bool TF>
+template <bool TF, bool A32 = false>
 VR_HD uint32_t majorant_fetch(const GridView& g, int32_t idx) {
     const int32_t i = VR_MAJ_OUTSIDE_CELL ? idx : (idx < 0 ? 0 : idx);
 #if VR_MAJ_OUTSIDE_CELL && defined(__clang__)
     __builtin_assume(i >= 0);                        // a table index (at most 73/64 x 2^30 cells, vr_scene.h): zero- instead of sign-extended into the 64-bit address
 #endif
     VR_TRACE(0, g.majorant16, i, TF ? 4 : 2);
-    return TF ? f2u(g.majorant[i]) : (uint32_t)g.majorant16[i];
+    return TF ? f2u(table_load<A32>(g.majorant, (uint32_t)i)) : (uint32_t)table_load<A32>(g.majorant16, (uint32_t)i);
 }
 template <bool TF>
 VR_HD float majorant_value(const SceneParams& P, uint32_t raw) { return TF ? u2f(raw) : P.u.vol_density_scale * half2float(raw); }
@@ -452,15 +489,15 @@ VR_HD void trilinear_prep(const GridView& g, v3 ipos, TriIO& io) {
 }
 // The 8 corner loads.  With a decoded float atlas (GridView::atlas_f32, brick grids under a transfer function) a corner is ONE
 // 4-byte load of the value the byte path would compute (rmin + unorm8(b) * rdiff, evaluated once when the atlas is decoded).
-template <int DENSE = 2, int PAIR = 0>
+template <int DENSE = 2, int PAIR = 0, bool A32 = false>
 VR_HD void trilinear_load(const GridView& g, TriIO& io) {
     if (!grid_is_dense<DENSE>(g) && g.atlas_f32) {
 #pragma unroll
-        for (int n = 0; n < 8; ++n) { io.d[n].rmin = 0.0f; io.d[n].rdiff = 0.0f; io.d[n].raw = f2u(g.atlas_f32[(size_t)io.a[n].cell * 512u + io.a[n].off]); }
+        for (int n = 0; n < 8; ++n) { io.d[n].rmin = 0.0f; io.d[n].rdiff = 0.0f; io.d[n].raw = f2u(A32 ? table_load<true>(g.atlas_f32, io.a[n].cell * 512u + io.a[n].off) : g.atlas_f32[(size_t)io.a[n].cell * 512u + io.a[n].off]); }
         return;
     }
 #pragma unroll
-    for (int n = 0; n < 8; ++n) io.d[n] = tap_load<DENSE, PAIR>(g, io.a[n]);
+    for (int n = 0; n < 8; ++n) io.d[n] = tap_load<DENSE, PAIR, A32>(g, io.a[n]);
 }
 VR_HD void trilinear_idle(TriIO& io) {           // addresses of a lane without a lookup: cell 0
 #pragma unroll
@@ -1168,37 +1205,37 @@ VR_HD void march_prep(const Hot& h, const SceneParams& P, MarchIO& io) {
 }
 // the loads: unconditional and for every lane of the wavefront (an idle lane reads cell 0), so that they sit in straight-line
 // code and the compiler's wait counts are exact
-template <bool TF>
+template <bool TF, bool A32 = false>
 VR_HD void march_load(const SceneParams& P, MarchIO& io) {
-    io.maj1 = majorant_fetch<TF>(P.density, io.i1);
-    io.maj2 = majorant_fetch<TF>(P.density, io.i2);
+    io.maj1 = majorant_fetch<TF, A32>(P.density, io.i1);
+    io.maj2 = majorant_fetch<TF, A32>(P.density, io.i2);
 }
 // the same with the lane's remembered (index, word) pair (Hot::maj_idx): a first step into the remembered cell loads nothing new
-template <bool TF>
+template <bool TF, bool A32 = false>
 VR_HD void march_load_reuse(const SceneParams& P, MarchIO& io, const Hot& h) {
     const bool same = io.i1 == h.maj_idx;                        // (-1 = outside never equals a remembered index: those are >= 0 or -2)
-    const uint32_t m1 = majorant_fetch<TF>(P.density, same ? 0 : io.i1);
+    const uint32_t m1 = majorant_fetch<TF, A32>(P.density, same ? 0 : io.i1);
     io.maj1 = same ? h.maj_raw : m1;
-    io.maj2 = majorant_fetch<TF>(P.density, io.i2);
+    io.maj2 = majorant_fetch<TF, A32>(P.density, io.i2);
 }
 // The same loads when the tail of the majorant table -- cells [first, end): the coarse levels, or the whole table of a small grid -- has been copied
 // to LDS (vr_pathtrace.h): a lane whose cell lies there reads the copy and sends its global load to cell 0, which all such lanes share (one
 // line); when the whole table is resident (first == 0, wave-uniform) no global load is issued at all.  T: uint16_t (raw fp16) or float (TF).
-template <bool TF, class T>
+template <bool TF, class T, bool A32 = false>
 VR_HD uint32_t majorant_fetch_lds(const GridView& g, int32_t idx, const T* lds, int32_t first, bool all_resident) {
     const int32_t i = idx < 0 ? 0 : idx;
     const bool in_lds = i >= first;
     const T s = lds[in_lds ? i - first : 0];
     const uint32_t sv = TF ? f2u((float)s) : (uint32_t)s;
     if (all_resident) return sv;
-    const uint32_t gv = majorant_fetch<TF>(g, in_lds ? 0 : i);
+    const uint32_t gv = majorant_fetch<TF, A32>(g, in_lds ? 0 : i);
     return in_lds ? sv : gv;
 }
-template <bool TF, class T>
+template <bool TF, class T, bool A32 = false>
 VR_HD void march_load_lds(const SceneParams& P, MarchIO& io, const T* lds, int32_t first) {
     const bool all_resident = first == 0;
-    io.maj1 = majorant_fetch_lds<TF, T>(P.density, io.i1, lds, first, all_resident);
-    io.maj2 = majorant_fetch_lds<TF, T>(P.density, io.i2, lds, first, all_resident);
+    io.maj1 = majorant_fetch_lds<TF, T, A32>(P.density, io.i1, lds, first, all_resident);
+    io.maj2 = majorant_fetch_lds<TF, T, A32>(P.density, io.i2, lds, first, all_resident);
 }
 // CLEAN (and no transfer function): the step back to the collision point, tau / majorant, by vr_math.h div_core.  Its domain: the majorant is density_scale x an fp16
 // range maximum, in [2^-40, 2^40] for the scales the kernels with a CLEAN form are launched with (2^-16 ... 2^24: vr_launch.hip pathtrace_variant); tau = (what was left) - majorant x dt <= 0 with dt in [2^-22, 2^27] (a clean
@@ -1257,15 +1294,15 @@ VR_HD void march_prep(const Hot& h, const SceneParams& P, MarchIO& io) {
 }
 // the loads: unconditional and for every lane of the wavefront (an idle lane reads cell 0), so that they sit in straight-line
 // code and the compiler's wait counts are exact
-template <bool TF>
+template <bool TF, bool A32 = false>
 VR_HD void march_load(const SceneParams& P, MarchIO& io) {
 #pragma unroll
-    for (int k = 0; k < kMarchSteps; ++k) io.maj[k] = majorant_fetch<TF>(P.density, io.idx[k]);
+    for (int k = 0; k < kMarchSteps; ++k) io.maj[k] = majorant_fetch<TF, A32>(P.density, io.idx[k]);
 }
-template <bool TF, class T>
+template <bool TF, class T, bool A32 = false>
 VR_HD void march_load_lds(const SceneParams&, MarchIO&, const T*, int32_t) { static_assert(sizeof(T) == 0, "VR_MAJ_LDS is written for VR_MARCH_STEPS == 2"); }
-template <bool TF>
-VR_HD void march_load_reuse(const SceneParams& P, MarchIO& io, const Hot&) { march_load<TF>(P, io); }      // (majorant reuse is written for VR_MARCH_STEPS == 2)
+template <bool TF, bool A32 = false>
+VR_HD void march_load_reuse(const SceneParams& P, MarchIO& io, const Hot&) { march_load<TF, A32>(P, io); }      // (majorant reuse is written for VR_MARCH_STEPS == 2)
 template <bool TF, bool REUSE = false, bool CLEAN = false>
 VR_HD void march_finish(Hot& h, const SceneParams& P, const MarchIO& io) {
     static_assert(!REUSE, "majorant reuse is written for VR_MARCH_STEPS == 2");
@@ -1355,12 +1392,17 @@ template <class K, bool CLEAN = false>
 VR_HD void collide_prep(Hot& h, const SceneParams& P, CollideIO<K>& io) { collide_prep<K, CLEAN>(h, P, P, io); }
 template <class K>
 VR_HD void collide_load(const SceneParams& P, const SceneParams& PE, CollideIO<K>& io) {      // unconditional, like march_load
-    if (K::tf) trilinear_load<K::dense, K::pair_d>(P.density, io.tri);
-    else io.d = tap_load<K::dense, K::pair_d>(P.density, io.a);
-    if (K::emission == 2 ? P.u.has_emission != 0 : K::emission == 1) io.ed = tap_load<K::edense, K::pair_e>(PE.emission, io.ea);
+    if (K::tf) trilinear_load<K::dense, K::pair_d, K::a32>(P.density, io.tri);
+    else io.d = tap_load<K::dense, K::pair_d, K::a32>(P.density, io.a);
+    if (K::emission == 2 ? P.u.has_emission != 0 : K::emission == 1) io.ed = tap_load<K::edense, K::pair_e, K::a32>(PE.emission, io.ea);
 }
 template <class K>
 VR_HD void collide_load(const SceneParams& P, CollideIO<K>& io) { collide_load<K>(P, P, io); }
+#ifndef VR_SHADOW_BLOCKED_SHORTCUT
+// round 7: a blocked shadow ray of the DDA trackers ends without the division and the roulette whose outcome is fixed (0: the A/B).  Not in the tolerance-mode kernels:
+// their quotient is a reciprocal and a multiply, and the test cost the smoke.brick one a vector register and six scalar spills (profiles/r7a_shadow_shortcut.txt)
+#define VR_SHADOW_BLOCKED_SHORTCUT (!VR_FAST_DEVICE)
+#endif
 // CACHED: throughput and radiance of the marching path are in h.ethr / h.eL (device scheduler, see Hot); otherwise on the cold line
 template <class K, class Cold, bool CACHED = false>
 VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const SceneParams& PE, const CollideIO<K>& io, const float* tf_lut) {
@@ -1404,6 +1446,23 @@ VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const ScenePara
         }
     } else {
         if (rng(h.seed) * h.majorant < d) {
+#if VR_SHADOW_BLOCKED_SHORTCUT
+            // Round 7.  The reference's tail below has ONE outcome wherever the cell's majorant does not exceed the volume's -- every cell of every scene the product
+            // builds: vol_majorant is the grid's maximum x density_scale (renderer.cpp), a cell's majorant a range maximum x the same scale.  With 0 < majorant <=
+            // vol_majorant the correctly rounded quotient is >= 1 (rounding is monotone, 1 is representable; +inf for an infinite vol_majorant, NaN for inf / inf; div_core
+            // equals that quotient on its domain), so 1 - ratio is <= 0 or NaN and max_(0, .) returns its first argument, +0; a finite Tr times +0 is a zero, which is
+            // < 0.1; prob = 1 - 0 = 1; and a draw is at most (2^24 - 1) / 2^24 < 1.  So the tail always ends as {one LCG advance; Tr = 0; POSTNEE}, which is what this
+            // does -- per lane, behind a test of exactly those premises, so that it holds whatever the scene: a majorant above vol_majorant, of zero, negative or NaN,
+            // a NaN vol_majorant (the compare fails) or a Tr that has overflowed (inf x 0 = NaN, and the reference marches on) take the code below.  Out of the collision
+            // block with it: a division (IEEE in the transfer-function kernels) and a roulette, 21 vector instructions in three nested exec regions, that the
+            // wavefront ran whenever one of its colliding lanes was a shadow ray at a real collision (profiles/r7a_shadow_shortcut.txt).
+            if ((h.majorant > 0.0f) & (h.majorant <= u.vol_majorant) & (abs_(h.Tr) < inf_())) {
+                (void)rng(h.seed);
+                h.Tr = 0.0f;
+                h.state = ST_POSTNEE;
+                return;
+            }
+#endif
             // (kernels of one scene kind without a transfer function: both majorants are density_scale x an fp16 number, density_scale in [2^-16, 2^24] -- vr_launch.hip
             // pathtrace_variant --, the quotient in [1, 2^40]: div_core's domain.  The lane of a NaN collision point, whose cell majorant is 0, does not get here: 0 < 0.)
             const float ratio = (K::global == 0 && !K::tf) ? div_core(u.vol_majorant, h.majorant) : u.vol_majorant / h.majorant;
@@ -1690,7 +1749,7 @@ struct FeatureCold {
 };
 template <bool TF>
 VR_HD int32_t feature_sample(const SceneParams& P, int32_t px, int32_t py, int32_t smp, float& t, v3& albedo, v3& normal) {
-    using K = TraceCfg<TF, 0, 2, 2, 2>;
+    using K = TraceCfg<TF, 0, 2, 2, 2, false>;      // (64-bit gather addresses: the feature pass runs on grids of any size)
     const Uniforms& u = P.u;
     const int32_t W = u.resolution[0], H = u.resolution[1];
     Hot h;
@@ -1877,7 +1936,7 @@ VR_HD void lane_step(Hot& h, Cold& c, const SceneParams& P, const WorkUnit& wu, 
         if (h.first) { stash.dir = h.ipos; stash.item = f2u(h.Tr); first_resume(h, P); }      // = HotStore::save_new + load_resume
         break;
     // two DDA steps, as on the device; a path on a clean segment in the forms the device runs for a wavefront of such paths
-    case ST_MARCH: { MarchIO io; if (seg_clean(h)) march_prep<K::dense, K::majb, true>(h, P, io); else march_prep<K::dense, K::majb, false>(h, P, io); march_load<K::tf>(P, io); if (seg_clean(h)) march_finish<K::tf, false, true>(h, P, io); else march_finish<K::tf, false, false>(h, P, io); break; }
+    case ST_MARCH: { MarchIO io; if (seg_clean(h)) march_prep<K::dense, K::majb, true>(h, P, io); else march_prep<K::dense, K::majb, false>(h, P, io); march_load<K::tf, K::a32>(P, io); if (seg_clean(h)) march_finish<K::tf, false, true>(h, P, io); else march_finish<K::tf, false, false>(h, P, io); break; }
     case ST_COLLIDE: if (seg_clean(h)) do_collide<K, Cold, true>(h, c, P); else do_collide<K, Cold, false>(h, c, P); break;
     case ST_NEE: do_nee<K>(h, c, c, P); break;
     case ST_POSTNEE: do_postnee<K>(h, c, P, wu); break;
