@@ -221,7 +221,7 @@ int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* l
  *     Bias: the decision to stop uses the variance estimated from the very samples it judges, so tiles whose estimate came out low stop early
  *     and the result is biased towards them -- as in the adaptive samplers of production renderers; there is no second sample buffer here.
  *     A tile whose pixels saw no collision in its first min_spp samples (the volume is thin there) has zero estimated variance and retires at
- *     once: keep min_spp at 16 or more.  Not available on the sharded renderer. */
+ *     once: keep min_spp at 16 or more.  Not available on the sharded renderer (the parts would end at different "sample" values). */
 /* render until every tile of the tile set has e_t < threshold or max_spp samples (the schedule above); 2 <= min_spp <= max_spp,
    threshold finite and >= 0, else VR_ERR_ARG; VR_ERR for missing moments or a tripped watchdog */
 int vr_render_adaptive(vr_renderer* r, int min_spp, int max_spp, float threshold);
@@ -253,7 +253,20 @@ int vr_unpack_tiles(vr_renderer* r, const int32_t* tile_ids_device, int n_tiles,
  *     devices = {0, 0, 0}) exchange their tiles with device-to-device copies instead -- vr_sharded_transport says which: "rccl", "copy", or
  *     "none" for one part; environment VR_SHARDED_TRANSPORT=copy|rccl overrides (rccl also with ONE part: a one-rank communicator).
  *     Asynchronous like vr_render; vr_sharded_synchronize waits for every part and reports a tripped watchdog.  The parts belong to the
- *     sharded renderer: never vr_destroy one, never vr_set_stream / vr_set_tiles on one. */
+ *     sharded renderer: never vr_destroy one, never vr_set_stream / vr_set_tiles on one.
+ *     Denoising: set "variance" to 1 on every part before the frame's first sample.  vr_sharded_render_features runs vr_render_features(spp) on every
+ *     part that owns tiles, over its tiles, on its own stream (no exchange).  vr_sharded_gather_guides packs every part's per-pixel moments and
+ *     features of its own tiles (three float4 per pixel), moves them to part 0 in ONE exchange on the transport above (3x the colour's size; its
+ *     buffers are allocated by the first call, a caller that only renders pays nothing) and scatters them into part 0's moments and features.
+ *     vr_sharded_denoise / vr_sharded_denoise_temporal do that and then run vr_denoise / vr_denoise_temporal's filter on part 0 over the whole frame,
+ *     with part 0's "denoise_iterations", "denoise_sigma", "denoise_alpha" and camera: bit-identical to the single-device calls.  Results are read
+ *     from part 0: vr_denoised, vr_features, vr_variance (both after a gather), vr_denoise_history on vr_sharded_part(s, 0); the temporal history lives
+ *     in part 0 and vr_denoise_history_reset on part 0 drops it.  All three are asynchronous, and a sequence reset, render, render_features, denoise per
+ *     frame needs no synchronisation between frames.  VR_ERR, before anything is launched and with a message that names the part, unless all parts agree
+ *     on the resolution and "sample", "sample" >= 1, and every part that owns tiles has moments that cover samples 1..n, a feature pass since the last
+ *     resize and no ragged frame; the last result and the history are then left as they were.  vr_denoise on a part itself keeps refusing the part's
+ *     tile subset, and vr_render_adaptive stays a single-device call.  Like the colour gather, the guide exchange has run between logical shards of
+ *     one device and on a one-rank communicator only. */
 typedef struct vr_sharded vr_sharded;
 int vr_sharded_create(vr_sharded** out, const int* devices, int n_parts, int width, int height);
 void vr_sharded_destroy(vr_sharded* s);
@@ -263,6 +276,10 @@ const char* vr_sharded_transport(vr_sharded* s);
 const char* vr_sharded_collective(vr_sharded* s);         /* "gather" | "allgather": what the rccl transport runs per frame */
 int vr_sharded_reset(vr_sharded* s);                      /* vr_reset on every part */
 int vr_sharded_render(vr_sharded* s, int spp);
+int vr_sharded_render_features(vr_sharded* s, int spp);   /* spp >= 1, as vr_render_features */
+int vr_sharded_gather_guides(vr_sharded* s);
+int vr_sharded_denoise(vr_sharded* s);
+int vr_sharded_denoise_temporal(vr_sharded* s);
 int vr_sharded_synchronize(vr_sharded* s);
 /* the tile deal itself (host only, needs no device): owner_out[t] = the part (0 .. n_parts-1) that renders raster tile t of a width x height frame,
  * t = ty * ceil(width / 16) + tx, row 0 = bottom; n_tiles must be ceil(width / 16) * ceil(height / 16) */

@@ -23,6 +23,7 @@ SYMBOLS = [
     "vr_render_features", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
     "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history",
     "vr_render_adaptive", "vr_tile_samples", "vr_tile_error",
+    "vr_sharded_render_features", "vr_sharded_gather_guides", "vr_sharded_denoise", "vr_sharded_denoise_temporal",
 ]
 
 _lib = None
@@ -119,6 +120,10 @@ def load():
     L.vr_sharded_reset.argtypes = [vp]
     L.vr_sharded_render.argtypes = [vp, ci]
     L.vr_sharded_synchronize.argtypes = [vp]
+    L.vr_sharded_render_features.argtypes = [vp, ci]
+    L.vr_sharded_gather_guides.argtypes = [vp]
+    L.vr_sharded_denoise.argtypes = [vp]
+    L.vr_sharded_denoise_temporal.argtypes = [vp]
     L.vr_tile_owners.argtypes = [ci, ci, ci, vp, ci]
     L.vr_wave_timeline.argtypes = [vp, vp, ci]
     _lib = L

@@ -646,6 +646,22 @@ int vr_sharded_render(vr_sharded* s, int spp) {
     if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
     return guard([&] { s->impl->render(spp); });
 }
+int vr_sharded_render_features(vr_sharded* s, int spp) {
+    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    return guard([&] { s->impl->render_features(spp); });
+}
+int vr_sharded_gather_guides(vr_sharded* s) {
+    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    return guard([&] { s->impl->gather_guides(); });
+}
+int vr_sharded_denoise(vr_sharded* s) {
+    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    return guard([&] { s->impl->denoise(); });
+}
+int vr_sharded_denoise_temporal(vr_sharded* s) {
+    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    return guard([&] { s->impl->denoise_temporal(); });
+}
 int vr_sharded_synchronize(vr_sharded* s) {
     if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
     return guard([&] { s->impl->synchronize(); });

@@ -921,10 +921,10 @@ void RendererHIP::download_variance(float* rgba) {
 void RendererHIP::denoise() { run_denoise("denoise", false); }
 void RendererHIP::denoise_temporal() { run_denoise("denoise_temporal", true); }
 
-void RendererHIP::run_denoise(const char* who, bool temporal) {
+void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_gathered) {
     flush_pending();
     const std::string me = std::string(who) + ": ";
-    if (!tiles_host_.empty()) throw std::runtime_error(me + "a tile subset is set (set_tiles); the filter needs every pixel's neighbours and runs on whole frames only");
+    if (!tiles_host_.empty() && !whole_frame_gathered) throw std::runtime_error(me + "a tile subset is set (set_tiles); the filter needs every pixel's neighbours and runs on whole frames only");
     if (!features_) throw std::runtime_error(me + "no feature pass since the last resize (call render_features first)");
     if (sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
     check_moments(who);

@@ -184,6 +184,7 @@ struct RendererHIP {
     // depth from the camera of the call before (once per frame; frames of equal spp).  Whatever denoise() accepts, this accepts.  The history is created
     // by the first call, dropped by resize and drop_history, and kept across everything else; denoise() neither reads nor writes it.
     // download_history: integrated colour W*H*4, integrated variance W*H, length W*H (any may be null); throws while there is no history.
+    // Several devices: ShardedRenderer::denoise / denoise_temporal (sharded.h); called on a part directly, these refuse the part's tile subset.
     void denoise();
     void denoise_temporal();
     void drop_history();
@@ -260,7 +261,9 @@ private:
     void check_moments(const char* who);               // throws unless the moments cover samples 1..sample (of every tile, on a ragged frame)
     DeviceBufferPtr dn_guide_, dn_var_[2], dn_color_[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4 (dropped by resize)
     DeviceBufferPtr denoised_;                         // W*H*4: the last denoise()'s or denoise_temporal()'s result (dropped by resize)
-    void run_denoise(const char* who, bool temporal);  // the body of both
+    void run_denoise(const char* who, bool temporal, bool whole_frame_gathered = false);  // the body of both; whole_frame_gathered: part 0 of a ShardedRenderer,
+                                                       // whose moments and features hold every part's tiles (gather_guides) -- the tile subset is no obstacle then
+    friend struct ShardedRenderer;                     // sharded.h: packs moments_ / features_ of every part, unpacks into part 0's, runs part 0's filter
     DeviceBufferPtr hist_color_[2], hist_record_[2];   // denoise_temporal(): the history, a ping-pong pair of W*H*4 colours and W*H*4 (V, N, K, D) records
     int hist_cur_ = -1;                                // the half that holds the history (-1: none)
     TemporalCamera hist_cam_{};                        // the camera of the frame that wrote it

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <iostream>
 #include <exception>
+#include <functional>
 #include <mutex>
 #include <set>
 #include <thread>
@@ -144,7 +145,7 @@ void ShardedRenderer::release() {
     for (size_t i = 0; i < parts_.size(); ++i) {
         (void)hipSetDevice(devices_[i]);
         if (buf_[i].stream && parts_[i]->stream == buf_[i].stream) parts_[i]->stream = prev_streams_[i];
-        buf_[i].pack_ids.reset(); buf_[i].packed.reset(); buf_[i].gathered.reset();
+        buf_[i].pack_ids.reset(); buf_[i].packed.reset(); buf_[i].gathered.reset(); buf_[i].guides_packed.reset(); buf_[i].guides_gathered.reset();
         if (i == 0) unpack_ids_.reset();
         if (buf_[i].packed_ready) (void)hipEventDestroy(buf_[i].packed_ready);
         if (buf_[i].stream) (void)hipStreamDestroy(buf_[i].stream);
@@ -175,6 +176,7 @@ void ShardedRenderer::setup(int width, int height) {
     std::vector<int32_t> unpack;
     for (size_t i = 0; i < n; ++i) {
         VR_HIP(hipSetDevice(devices_[i]));
+        buf_[i].guides_packed.reset(); buf_[i].guides_gathered.reset();      // sized by the resolution: made again by the next gather_guides, if there is one
         parts_[i]->set_tiles(lists[i]);
         buf_[i].n_own = (int)lists[i].size();        // 0 (more parts than tile diagonals): the part renders nothing -- an empty list would mean the WHOLE frame to set_tiles
         // pack list: own tiles, padded by repeating the last one (any valid tile: its slot is ignored on unpack)
@@ -196,19 +198,85 @@ void ShardedRenderer::reset() {
     for (RendererHIP* p : parts_) p->reset();
 }
 
-void ShardedRenderer::render(int spp) {
+// the parts must agree on what frame they hold; the tile deal and the buffers follow the resolution
+void ShardedRenderer::prepare(const char* who) {
     RendererHIP& first = *parts_[0];
     for (RendererHIP* p : parts_)
         if (p->resolution.x != first.resolution.x || p->resolution.y != first.resolution.y || p->sample != first.sample)
-            throw std::runtime_error("ShardedRenderer::render: the parts disagree on resolution or sample count");
+            throw std::runtime_error(std::string("ShardedRenderer::") + who + ": the parts disagree on resolution or sample count");
     if (first.resolution.x != width_ || first.resolution.y != height_) setup(first.resolution.x, first.resolution.y);
+}
+
+// issue(i) for every part, from one host thread per part (part 0 on the caller's); the first exception is rethrown once all have returned
+void ShardedRenderer::issue_on_parts(const std::function<void(size_t)>& issue) {
+    const size_t n = parts_.size();
+    if (n == 1) { issue(0); return; }
+    std::vector<std::exception_ptr> errors(n);
+    std::vector<std::thread> threads;
+    for (size_t i = 1; i < n; ++i) threads.emplace_back([&, i] { try { issue(i); } catch (...) { errors[i] = std::current_exception(); } });
+    try { issue(0); } catch (...) { errors[0] = std::current_exception(); }
+    for (std::thread& t : threads) t.join();
+    for (const std::exception_ptr& e : errors) if (e) std::rethrow_exception(e);
+}
+
+// ONE exchange: every part's `packed` buffer of `count` floats into part 0's `gathered` buffer, part i's at float i * count, enqueued on the parts' streams after
+// whatever filled the packed buffers; part 0's stream continues once all of it has arrived.  The colour gather of render() and the guide gather of
+// gather_guides() differ in the buffers and the count only.
+void ShardedRenderer::exchange(DeviceBufferPtr PartBuffers::*packed, DeviceBufferPtr PartBuffers::*gathered_of, size_t count) {
+    const size_t n = parts_.size();
+    if (transport_ == "rccl" && collective_ == "allgather") {
+        Rccl& R = rccl();
+        RcclGroup group;
+        for (size_t i = 0; i < n; ++i) {
+            VR_HIP(hipSetDevice(devices_[i]));
+            rccl_check(R.AllGather((buf_[i].*packed)->get(), (buf_[i].*gathered_of)->get(), count, ncclFloat, (ncclComm_t)comms_[i], buf_[i].stream), "ncclAllGather");
+        }
+        group.end();
+    } else if (transport_ == "rccl") {
+        // gather to part 0: its own buffer moves on its stream, every other part sends its buffer and part 0 posts the matching receives -- ONE group, so the
+        // N - 1 transfers over the N - 1 xGMI links into device 0 run concurrently.  Stream order does the rest: a part's send follows its pack, part 0's
+        // receives follow its unpack of the exchange before (which reads the buffer they fill) and precede this one's.
+        Rccl& R = rccl();
+        float* gathered = (buf_[0].*gathered_of)->as<float>();
+        VR_HIP(hipSetDevice(devices_[0]));
+        VR_HIP(hipMemcpyAsync(gathered, (buf_[0].*packed)->get(), count * sizeof(float), hipMemcpyDeviceToDevice, buf_[0].stream));
+        RcclGroup group;
+        for (size_t i = 1; i < n; ++i) {
+            VR_HIP(hipSetDevice(devices_[0]));
+            rccl_check(R.Recv(gathered + i * count, count, ncclFloat, (int)i, (ncclComm_t)comms_[0], buf_[0].stream), "ncclRecv");
+            VR_HIP(hipSetDevice(devices_[i]));
+            rccl_check(R.Send((buf_[i].*packed)->get(), count, ncclFloat, 0, (ncclComm_t)comms_[i], buf_[i].stream), "ncclSend");
+        }
+        group.end();
+    } else {
+        // logical shards of one device (or VR_SHARDED_TRANSPORT=copy): every part copies its buffer into part 0's gathered buffer on its
+        // own stream, and part 0's stream waits for all of them.  The copies of exchange k+1 must not overtake part 0's unpack of exchange k,
+        // which reads that buffer: they wait for an event part 0 records after its pack -- in stream order after the unpack before it.
+        VR_HIP(hipSetDevice(devices_[0]));
+        VR_HIP(hipEventRecord(buf_[0].packed_ready, buf_[0].stream));       // part 0 has packed (and, in stream order, finished the unpack before)
+        float* gathered = (buf_[0].*gathered_of)->as<float>();
+        for (size_t i = 0; i < n; ++i) {
+            VR_HIP(hipSetDevice(devices_[i]));
+            if (i > 0) VR_HIP(hipStreamWaitEvent(buf_[i].stream, buf_[0].packed_ready, 0));
+            if (devices_[i] == devices_[0]) VR_HIP(hipMemcpyAsync(gathered + i * count, (buf_[i].*packed)->get(), count * sizeof(float), hipMemcpyDeviceToDevice, buf_[i].stream));
+            else VR_HIP(hipMemcpyPeerAsync(gathered + i * count, devices_[0], (buf_[i].*packed)->get(), devices_[i], count * sizeof(float), buf_[i].stream));
+            if (i > 0) VR_HIP(hipEventRecord(buf_[i].packed_ready, buf_[i].stream));
+        }
+        VR_HIP(hipSetDevice(devices_[0]));
+        for (size_t i = 1; i < n; ++i) VR_HIP(hipStreamWaitEvent(buf_[0].stream, buf_[i].packed_ready, 0));
+    }
+}
+
+void ShardedRenderer::render(int spp) {
+    prepare("render");
+    RendererHIP& first = *parts_[0];
     const int n_samples = spp <= 0 ? first.sppx - first.sample : spp;
     if (n_samples <= 0) return;
     const size_t n = parts_.size();
     const size_t count = (size_t)n_max_ * 256u * 4u;             // floats a part contributes
     // Every part: all samples of its tiles, then its compact tile buffer -- issued from one host thread per part.  A part's first render() on new settings
     // waits for its probe launch (RendererHIP::submit, launch_target_ms); issued one after the other the parts' first frames ran staggered (round 4).
-    auto issue = [&](size_t i) {
+    issue_on_parts([&](size_t i) {
         VR_HIP(hipSetDevice(devices_[i]));
         RendererHIP& p = *parts_[i];
         if (p.stream != buf_[i].stream) throw std::runtime_error("ShardedRenderer::render: a part's stream was changed behind the sharded renderer");
@@ -217,62 +285,87 @@ void ShardedRenderer::render(int spp) {
         if (transport_ == "none") return;
         launch_pack_tiles(p.color->as<float>(), width_, height_, buf_[i].pack_ids->as<int32_t>(), n_max_, buf_[i].packed->as<float>(), buf_[i].stream);
         VR_HIP(hipGetLastError());
-    };
-    if (n == 1) issue(0);
-    else {
-        std::vector<std::exception_ptr> errors(n);
-        std::vector<std::thread> threads;
-        for (size_t i = 1; i < n; ++i) threads.emplace_back([&, i] { try { issue(i); } catch (...) { errors[i] = std::current_exception(); } });
-        try { issue(0); } catch (...) { errors[0] = std::current_exception(); }
-        for (std::thread& t : threads) t.join();
-        for (const std::exception_ptr& e : errors) if (e) std::rethrow_exception(e);
-    }
+    });
     if (transport_ == "none") return;
-    if (transport_ == "rccl" && collective_ == "allgather") {
-        Rccl& R = rccl();
-        RcclGroup group;
-        for (size_t i = 0; i < n; ++i) {
-            VR_HIP(hipSetDevice(devices_[i]));
-            rccl_check(R.AllGather(buf_[i].packed->get(), buf_[i].gathered->get(), count, ncclFloat, (ncclComm_t)comms_[i], buf_[i].stream), "ncclAllGather");
-        }
-        group.end();
-    } else if (transport_ == "rccl") {
-        // gather to part 0: its own buffer moves on its stream, every other part sends its buffer and part 0 posts the matching receives -- ONE group, so the
-        // N - 1 transfers over the N - 1 xGMI links into device 0 run concurrently.  Stream order does the rest: a part's send follows its pack, part 0's
-        // receives follow its unpack of the frame before (which reads the buffer they fill) and precede this frame's.
-        Rccl& R = rccl();
-        float* gathered = buf_[0].gathered->as<float>();
-        VR_HIP(hipSetDevice(devices_[0]));
-        VR_HIP(hipMemcpyAsync(gathered, buf_[0].packed->get(), count * sizeof(float), hipMemcpyDeviceToDevice, buf_[0].stream));
-        RcclGroup group;
-        for (size_t i = 1; i < n; ++i) {
-            VR_HIP(hipSetDevice(devices_[0]));
-            rccl_check(R.Recv(gathered + i * count, count, ncclFloat, (int)i, (ncclComm_t)comms_[0], buf_[0].stream), "ncclRecv");
-            VR_HIP(hipSetDevice(devices_[i]));
-            rccl_check(R.Send(buf_[i].packed->get(), count, ncclFloat, 0, (ncclComm_t)comms_[i], buf_[i].stream), "ncclSend");
-        }
-        group.end();
-    } else {
-        // logical shards of one device (or VR_SHARDED_TRANSPORT=copy): every part copies its buffer into part 0's gathered buffer on its
-        // own stream, and part 0's stream waits for all of them.  The copies of frame k+1 must not overtake part 0's unpack of frame k,
-        // which reads that buffer: they wait for an event part 0 records after its pack -- in stream order after the unpack before it.
-        VR_HIP(hipSetDevice(devices_[0]));
-        VR_HIP(hipEventRecord(buf_[0].packed_ready, buf_[0].stream));       // part 0 has packed (and, in stream order, finished last frame's unpack)
-        float* gathered = buf_[0].gathered->as<float>();
-        for (size_t i = 0; i < n; ++i) {
-            VR_HIP(hipSetDevice(devices_[i]));
-            if (i > 0) VR_HIP(hipStreamWaitEvent(buf_[i].stream, buf_[0].packed_ready, 0));
-            if (devices_[i] == devices_[0]) VR_HIP(hipMemcpyAsync(gathered + i * count, buf_[i].packed->get(), count * sizeof(float), hipMemcpyDeviceToDevice, buf_[i].stream));
-            else VR_HIP(hipMemcpyPeerAsync(gathered + i * count, devices_[0], buf_[i].packed->get(), devices_[i], count * sizeof(float), buf_[i].stream));
-            if (i > 0) VR_HIP(hipEventRecord(buf_[i].packed_ready, buf_[i].stream));
-        }
-        VR_HIP(hipSetDevice(devices_[0]));
-        for (size_t i = 1; i < n; ++i) VR_HIP(hipStreamWaitEvent(buf_[0].stream, buf_[i].packed_ready, 0));
-    }
+    exchange(&PartBuffers::packed, &PartBuffers::gathered, count);
     VR_HIP(hipSetDevice(devices_[0]));
     launch_unpack_tiles(buf_[0].gathered->as<float>(), unpack_ids_->as<int32_t>(), (int32_t)(n * (size_t)n_max_), first.color->as<float>(), width_, height_, buf_[0].stream);
     VR_HIP(hipGetLastError());
 }
+
+// ---- denoising (renderer.h render_features / denoise / denoise_temporal on several devices) --------------------------------------------------------
+void ShardedRenderer::render_features(int spp) {
+    if (spp <= 0) throw std::runtime_error("ShardedRenderer::render_features: spp must be positive");
+    prepare("render_features");
+    issue_on_parts([&](size_t i) {
+        VR_HIP(hipSetDevice(devices_[i]));
+        RendererHIP& p = *parts_[i];
+        if (p.stream != buf_[i].stream) throw std::runtime_error("ShardedRenderer::render_features: a part's stream was changed behind the sharded renderer");
+        if (transport_ == "none" || buf_[i].n_own > 0) p.render_features(spp);      // no tile of its own: no features either (an empty tile set would mean the whole frame)
+    });
+}
+
+// What the guide gather and the filter need of every part, asked before anything is launched: a call that throws here has changed nothing.
+void ShardedRenderer::check_guides(const char* who) {
+    prepare(who);
+    const std::string me = std::string("ShardedRenderer::") + who + ": ";
+    if (parts_[0]->sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
+    for (size_t i = 0; i < parts_.size(); ++i) {
+        if (transport_ != "none" && buf_[i].n_own == 0) continue;             // renders nothing, contributes nothing
+        const std::string part = me + "part " + std::to_string(i) + ": ";
+        VR_HIP(hipSetDevice(devices_[i]));
+        RendererHIP& p = *parts_[i];
+        if (p.stream != buf_[i].stream) throw std::runtime_error(part + "its stream was changed behind the sharded renderer");
+        p.flush_pending();                                                    // recorded trace() calls: their launch brings the moments up to `sample`
+        if (p.ragged()) throw std::runtime_error(part + "its frame is ragged (render_adaptive): adaptive sampling is not available on several devices");
+        try { p.check_moments(who); } catch (const std::exception& e) { throw std::runtime_error(part + e.what()); }
+        if (!p.features_) throw std::runtime_error(part + "no feature pass since the last resize (call render_features first)");
+    }
+}
+
+void ShardedRenderer::gather_guides() {
+    check_guides("gather_guides");
+    exchange_guides();
+}
+
+void ShardedRenderer::exchange_guides() {
+    if (transport_ == "none") return;
+    const size_t n = parts_.size();
+    const size_t count = (size_t)n_max_ * kGuidePlanes * 256u * 4u;           // floats a part contributes: 3x the colour's
+    for (size_t i = 0; i < n; ++i) {                                          // first use at this resolution: every allocation before the first launch
+        const bool gathers = i == 0 || (transport_ == "rccl" && collective_ == "allgather");
+        if (buf_[i].guides_packed && (!gathers || buf_[i].guides_gathered)) continue;
+        VR_HIP(hipSetDevice(devices_[i]));
+        DeviceBufferPtr packed = make_device_buffer(count * sizeof(float)), gathered = gathers ? make_device_buffer(count * sizeof(float) * n) : nullptr;
+        VR_HIP(hipMemsetAsync(packed->get(), 0, count * sizeof(float), buf_[i].stream));      // a part without tiles never packs: it sends zeros, which nobody unpacks
+        buf_[i].guides_packed = packed; buf_[i].guides_gathered = gathered;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (buf_[i].n_own == 0) continue;
+        VR_HIP(hipSetDevice(devices_[i]));
+        RendererHIP& p = *parts_[i];
+        launch_pack_guides(p.moments_->as<float>(), p.features_->as<float>(), width_, height_, buf_[i].pack_ids->as<int32_t>(), n_max_,
+                           buf_[i].guides_packed->as<float>(), buf_[i].stream);
+        VR_HIP(hipGetLastError());
+    }
+    exchange(&PartBuffers::guides_packed, &PartBuffers::guides_gathered, count);
+    // part 0's moments and features now take every part's tiles (its own among them, unchanged).  In stream order before its filter, and before its next
+    // accumulate and feature pass, which write its own tiles only; the other parts' passes touch their own buffers and need no ordering against this.
+    VR_HIP(hipSetDevice(devices_[0]));
+    RendererHIP& first = *parts_[0];
+    launch_unpack_guides(buf_[0].guides_gathered->as<float>(), unpack_ids_->as<int32_t>(), (int32_t)(n * (size_t)n_max_), first.moments_->as<float>(),
+                         first.features_->as<float>(), width_, height_, buf_[0].stream);
+    VR_HIP(hipGetLastError());
+}
+
+void ShardedRenderer::run_denoise(const char* who, bool temporal) {
+    check_guides(who);
+    exchange_guides();
+    VR_HIP(hipSetDevice(devices_[0]));
+    parts_[0]->run_denoise(who, temporal, transport_ != "none");
+}
+void ShardedRenderer::denoise() { run_denoise("denoise", false); }
+void ShardedRenderer::denoise_temporal() { run_denoise("denoise_temporal", true); }
 
 void ShardedRenderer::synchronize() {
     uint32_t tripped = 0;

@@ -7,7 +7,7 @@
 // ncclAllGather, still there behind VR_SHARDED_COLLECTIVE=allgather) of the compact
 // per-part tile buffers puts the accumulated radiance together; part 0 scatters it back into its framebuffer, which then holds the
 // whole frame -- bit-identical to a single-device render, because a pixel-sample depends on (seed, pixel, sample) only
-// (pathtracer_brick.glsl:28-36).
+// (pathtracer_brick.glsl:28-36).  The denoiser's guide buffers (per-pixel moments, features) travel the same way on request, and part 0 filters the frame.
 //
 // Transport: "rccl" when the parts sit on distinct devices (librccl.so.1 is opened at run time: the library has no link-time
 // dependency on it), "copy" when two parts share a device (logical shards of one GPU: device-to-device copies ordered by events
@@ -15,6 +15,7 @@
 // (peer copies across devices).  VR_SHARDED_TRANSPORT=rccl forces the collective also for a single part.
 #pragma once
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -48,11 +49,34 @@ struct ShardedRenderer {
     // synchronize() returns.  More parts than the frame has tile diagonals: the surplus parts own no tile and render nothing.
     void render(int spp = 0);
     void synchronize();                   // waits for all parts; throws if a kernel watchdog tripped
+    // Denoising on several devices (renderer.h render_features / denoise / denoise_temporal): bit for bit what one device gives, because the filter is
+    // deterministic per pixel and part 0 runs it on the gathered whole frame.  Asynchronous like render(); no host synchronisation is needed anywhere in
+    // reset, render, render_features, denoise, reset, render, ... (stream order and the exchange's events keep the frames apart).
+    // render_features: every part that owns tiles runs its feature pass over them on its own stream (one host thread per part); no exchange.
+    void render_features(int spp);
+    // gather_guides: every part's moments and features of its own tiles -> part 0's moments and features, which then cover the whole frame
+    // (part(0).download_variance / download_features): one pack per part, ONE exchange of 3x the colour's size through the transport render() uses,
+    // one unpack on part 0.  The buffers are allocated by the first call at a resolution: a caller that only renders pays nothing.
+    void gather_guides();
+    // denoise / denoise_temporal: gather_guides(), then part 0's filter on the whole frame, with part 0's settings (denoise_iterations, denoise_sigma,
+    // denoise_alpha) and -- temporal -- part 0's camera and history: the history lives in part 0 and is read and dropped there (part(0).download_history,
+    // part(0).drop_history), as is the result (part(0).download_denoised).  Refused before anything is launched, with a message that names the part, unless
+    // all parts agree on resolution and sample, sample >= 1, and every part that owns tiles has moments covering samples 1..sample (`variance` on for all of
+    // them), a feature pass since the last resize and no ragged frame (render_adaptive: adaptive sampling stays a single-device feature).  A refused call
+    // leaves the last result and the history as they were.  One part without a forced transport: the plain renderer's calls.
+    // (RendererHIP::denoise() on a part keeps refusing the part's tile subset.)
+    void denoise();
+    void denoise_temporal();
     const std::string& transport() const { return transport_; }      // "rccl" | "copy" | "none" (one part, nothing to exchange)
     const std::string& collective() const { return collective_; }    // of the rccl transport: "gather" (ncclSend / ncclRecv to part 0) | "allgather"
 
 private:
     void setup(int width, int height);   // tile deal + buffers for the current resolution
+    void prepare(const char* who);        // throws unless the parts agree on resolution and sample; setup() on a new resolution
+    void issue_on_parts(const std::function<void(size_t)>& issue);
+    void check_guides(const char* who);   // what gather_guides and the filter need of every part, before the first launch
+    void exchange_guides();               // gather_guides after the checks
+    void run_denoise(const char* who, bool temporal);
     void release();                       // everything this object created; the parts get their previous streams back
     std::vector<RendererHIP*> parts_;
     std::vector<int> devices_;
@@ -63,8 +87,11 @@ private:
         hipEvent_t packed_ready = nullptr;
         int n_own = 0;                    // tiles this part renders
         DeviceBufferPtr pack_ids, packed, gathered;      // gathered: on part 0 (every part under VR_SHARDED_COLLECTIVE=allgather)
+        DeviceBufferPtr guides_packed, guides_gathered;  // the same pair for the denoiser's guides, kGuidePlanes x as large; made by the first gather_guides
     };
     std::vector<PartBuffers> buf_;
+    // every part's `packed` (count floats) into part 0's `gathered`, on the transport: rccl gather, rccl allgather, or copies ordered by events
+    void exchange(DeviceBufferPtr PartBuffers::*packed, DeviceBufferPtr PartBuffers::*gathered, size_t count);
     DeviceBufferPtr unpack_ids_;          // on part 0's device: every part's tile ids in part order, -1 = padding
     std::vector<void*> comms_;            // ncclComm_t per part (rccl transport)
     std::vector<hipStream_t> prev_streams_;      // what the parts' `stream` fields held before this object took them

@@ -82,6 +82,10 @@ void launch_tonemap(float* fb, int32_t w, int32_t h, float exposure, float gamma
 // multi-GPU shard helpers: copy owned 16x16 tiles frame <-> compact tile-major buffer (256 texels per tile)
 void launch_pack_tiles(const float* fb, int32_t w, int32_t h, const int32_t* tiles, int32_t n_tiles, float* packed, hipStream_t stream);
 void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_tiles, float* fb, int32_t w, int32_t h, hipStream_t stream);
+// the same for the denoiser's guides: moments (W*H*4) and features (W*H*8) <-> kGuidePlanes * 256 float4 per tile slot (vr_tiles.h guide_slot: wire format).
+// pack: every tiles[k] a tile of the frame; unpack: tiles[k] < 0 = padding, the slot is not read
+void launch_pack_guides(const float* moments, const float* features, int32_t w, int32_t h, const int32_t* tiles, int32_t n_tiles, float* packed, hipStream_t stream);
+void launch_unpack_guides(const float* packed, const int32_t* tiles, int32_t n_tiles, float* moments, float* features, int32_t w, int32_t h, hipStream_t stream);
 // ---- vr_setup.hip ----------------------------------------------------------------------------------------------------------------------------
 // env_setup.glsl:18-34 + glGenerateMipmap (environment.cpp:27-31): importance pyramid of a dim x dim map
 void launch_build_impmap(const float* envmap_rgba, int32_t env_w, int32_t env_h, int32_t dim, float* pyramid, hipStream_t stream);

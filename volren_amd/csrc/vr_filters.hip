@@ -182,5 +182,45 @@ void launch_unpack_tiles(const float* packed, const int32_t* tiles, int32_t n_ti
     if (n_tiles <= 0) return;
     hipLaunchKernelGGL(unpack_tiles_kernel, dim3(n_tiles), dim3(256), 0, stream, packed, tiles, fb, w, h);
 }
+// The same for the denoiser's guide buffers, three float4 planes per pixel in one kernel (vr_tiles.h guide_slot): the moments texel and the two
+// float4 of the pixel's features.  One workgroup per tile slot, raster in the tile; a pixel is three dwordx4 loads and three dwordx4 stores, each
+// plane of a slot one contiguous 4 KiB run.  Pixels outside the frame pack as zeros and are not written on unpack.
+__global__ void __launch_bounds__(256)
+pack_guides_kernel(const float4* __restrict__ moments, const float4* __restrict__ features, int32_t w, int32_t h, const int32_t* __restrict__ tiles,
+                   float4* __restrict__ packed) {
+    const TilePixel q = raster_in_tile_pixel(tiles[blockIdx.x], threadIdx.x, w);
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f), fa = m, fb = m;
+    if (q.px < w && q.py < h) {
+        const size_t i = (size_t)q.py * w + q.px;
+        m = moments[i];
+        fa = features[2 * i];
+        fb = features[2 * i + 1];
+    }
+    packed[guide_slot(blockIdx.x, 0u, threadIdx.x)] = m;
+    packed[guide_slot(blockIdx.x, 1u, threadIdx.x)] = fa;
+    packed[guide_slot(blockIdx.x, 2u, threadIdx.x)] = fb;
+}
+__global__ void __launch_bounds__(256)
+unpack_guides_kernel(const float4* __restrict__ packed, const int32_t* __restrict__ tiles, float4* __restrict__ moments, float4* __restrict__ features,
+                     int32_t w, int32_t h) {
+    const int32_t tile = tiles[blockIdx.x];
+    if (tile < 0) return;             // padding entry
+    const TilePixel q = raster_in_tile_pixel(tile, threadIdx.x, w);
+    if (q.px >= w || q.py >= h) return;
+    const size_t i = (size_t)q.py * w + q.px;
+    moments[i] = packed[guide_slot(blockIdx.x, 0u, threadIdx.x)];
+    features[2 * i] = packed[guide_slot(blockIdx.x, 1u, threadIdx.x)];
+    features[2 * i + 1] = packed[guide_slot(blockIdx.x, 2u, threadIdx.x)];
+}
+void launch_pack_guides(const float* moments, const float* features, int32_t w, int32_t h, const int32_t* tiles, int32_t n_tiles, float* packed, hipStream_t stream) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(pack_guides_kernel, dim3(n_tiles), dim3(256), 0, stream, reinterpret_cast<const float4*>(moments),
+                       reinterpret_cast<const float4*>(features), w, h, tiles, reinterpret_cast<float4*>(packed));
+}
+void launch_unpack_guides(const float* packed, const int32_t* tiles, int32_t n_tiles, float* moments, float* features, int32_t w, int32_t h, hipStream_t stream) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(unpack_guides_kernel, dim3(n_tiles), dim3(256), 0, stream, reinterpret_cast<const float4*>(packed), tiles,
+                       reinterpret_cast<float4*>(moments), reinterpret_cast<float4*>(features), w, h);
+}
 
 }  // namespace vr

@@ -2,9 +2,11 @@
 // A W x H frame (row 0 at the bottom) is cut into 16x16 tiles in raster order, tile = ty * tiles_x + tx.  A workgroup's 256 threads lie in a tile
 //   wave-tiled : as four 8x8 sub-tiles, one per wavefront (sub-tile s at (8 (s & 1), 8 (s >> 1)), lane l at (l & 7, l >> 3) in it) -- every per-pixel
 //                kernel, and the path tracer's work units (vr_pathtrace.h make_unit: a unit is one sub-tile x spu samples); or
-//   raster     : thread t at (t & 15, t >> 4) -- the packed tiles of the sharded framebuffer only, whose texel order is wire format.
-// tests/hostkernel/tiles_host.cpp builds this header for the host.
+//   raster     : thread t at (t & 15, t >> 4) -- the packed tiles of the sharded framebuffer and of its denoiser guides only, whose texel order is wire format.
+// tests/hostkernel/tiles_host.cpp and guides_host.cpp build this header for the host.
 #pragma once
+
+#include <stddef.h>
 
 #include "vr_math.h"
 
@@ -31,6 +33,12 @@ VR_HD TilePixel raster_in_tile_pixel(int32_t tile, uint32_t t, int32_t W) {
     const int32_t nx = tiles_x(W);
     return TilePixel{ tile, 0, 0, (tile % nx) * 16 + (int32_t)(t & 15u), (tile / nx) * 16 + (int32_t)(t >> 4) };
 }
+// The packed denoiser guides of the sharded renderer (pack_guides_kernel / unpack_guides_kernel): kGuidePlanes float4 planes per pixel -- 0 the moments
+// texel, 1 and 2 the two float4 of the pixel's eight features -- plane-major inside a tile slot, thread t in raster_in_tile_pixel order.  The float4
+// index below is WIRE FORMAT: the parts of a sharded renderer exchange these buffers, n_max * kGuidePlanes * 256 float4 per part.
+// tests/hostkernel/guides_host.cpp builds it for the host.
+constexpr uint32_t kGuidePlanes = 3u;
+VR_HD size_t guide_slot(size_t tile_slot, uint32_t plane, uint32_t t) { return (tile_slot * kGuidePlanes + plane) * 256u + t; }
 
 // Sample pool, one RGBA32F item per (pixel, sample) of a launch, written by the integrator kernels and read back by the accumulate kernel: the slot
 // of lane `lane` of sub-tile `sub` of the launch's tile_slot-th tile, sample `sample` (0-based) of sample chunk `chunk`.  Work unit u = chunk * (n_tiles * 4) + (tile_slot * 4 + sub) owns the spu * 64 slots from u * spu * 64, sample-major.  I: the index

@@ -455,6 +455,49 @@ class ShardedRenderer:
     def save(self, path):
         self.parts[0].save(path)
 
+    # ---- denoiser: every part computes the guides of its own tiles, part 0 gathers them and filters the whole frame ----
+    def render_features(self, spp, sync=True):
+        """Renderer.render_features on every part that owns tiles, over its tiles (vr_sharded_render_features); no exchange."""
+        _lib.check(self._L.vr_sharded_render_features(self._h, int(spp)))
+        if sync:
+            self.synchronize()
+
+    def gather_guides(self):
+        """Every part's moments and features of its tiles into `parts[0]` (vr_sharded_gather_guides): one exchange, asynchronous."""
+        _lib.check(self._L.vr_sharded_gather_guides(self._h))
+
+    def denoise(self, sync=True):
+        """gather_guides(), then Renderer.denoise's filter on `parts[0]` over the whole frame, with that part's `denoise_*` settings
+        (vr_sharded_denoise): bit for bit the single-device result.  Needs `variance = 1` on every part for all the frame's samples."""
+        _lib.check(self._L.vr_sharded_denoise(self._h))
+        if sync:
+            self.synchronize()
+
+    def denoise_temporal(self, sync=True):
+        """The same with Renderer.denoise_temporal's blend in front (vr_sharded_denoise_temporal); the history lives in `parts[0]`."""
+        _lib.check(self._L.vr_sharded_denoise_temporal(self._h))
+        if sync:
+            self.synchronize()
+
+    def denoised(self):
+        return self.parts[0].denoised()
+
+    def features(self):
+        """[H][W][8] of the whole frame: gathers first."""
+        self.gather_guides()
+        return self.parts[0].features()
+
+    def variance(self):
+        """[H][W][4] of the whole frame: gathers first."""
+        self.gather_guides()
+        return self.parts[0].variance()
+
+    def denoise_history(self):
+        return self.parts[0].denoise_history()
+
+    def denoise_history_reset(self):
+        self.parts[0].denoise_history_reset()
+
 
 def math_probe(fn, a, b=None):
     a = _f32(a).reshape(-1)
