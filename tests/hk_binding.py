@@ -76,15 +76,32 @@ def lib(fast_tap=False):
     return _libs[fast_tap]
 
 
-def cfg_steps(reset=False, fast_tap=False):
-    """lane steps per compiled form since the last reset: (TraceCfg<false,0,0,0,2>, <false,0,0,1,2>, <false,2,2,2,2>, <true,2,2,2,2>)"""
-    out = (C.c_ulonglong * 4)()
-    lib(fast_tap).hk_cfg_steps(out, 1 if reset else 0)
-    return tuple(int(v) for v in out)
+# The forms of the lane code the harness compiles: exactly the 14 configurations the device ships (host_kernel.cpp FormCfg, vr_pathtrace.hip Cfg), in the
+# harness's order: (kernel variant, 64-bit gather addresses, transfer function)
+FORMS = tuple((variant, wide, tf) for variant, wide in ((0, False), (0, True), (1, False), (1, True), (2, True), (4, True), (3, True)) for tf in (False, True))
+COUNTERS = ("steps", "clean_march", "clean_collide", "general_march", "general_collide")
+HS_MAJ_BLOCKED = 1            # host_scene.h
 
 
-def render(orc_renderer, spp, rect=None, fb=None, first_sample=1, fast_tap=False):
-    """Run the host-compiled product kernel on the scene held by an oracle.binding.OracleRenderer."""
+def form_steps(reset=False, fast_tap=False):
+    """{form: {counter: n}} since the last reset, forms as in FORMS: all lane steps, and the steps of the hot pair by what the path stood on -- a clean segment
+    (vr_trace.h seg_clean) or not, which is where lane_step takes the general forms -- counted by the harness before each step."""
+    L = lib(fast_tap)
+    assert L.hk_form_count() == len(FORMS)
+    out = (C.c_ulonglong * (len(FORMS) * len(COUNTERS)))()
+    L.hk_form_steps(out, 1 if reset else 0)
+    return {f: {c: int(out[i * len(COUNTERS) + k]) for k, c in enumerate(COUNTERS)} for i, f in enumerate(FORMS)}
+
+
+def forms_that_ran(fast_tap=False):
+    """{form: lane steps} of the forms with a step since the last reset"""
+    return {f: c["steps"] for f, c in form_steps(fast_tap=fast_tap).items() if any(c.values())}
+
+
+def render(orc_renderer, spp, rect=None, fb=None, first_sample=1, fast_tap=False, wide=False, blocked=False):
+    """Run the host-compiled product kernel on the scene held by an oracle.binding.OracleRenderer, in the form the product's launch would pick for it
+    (vr_launch.hip pathtrace_variant_of / pathtrace_wide_of).  wide: the 64-bit form of variants 0 and 1 (the product's wide_addressing = 1);
+    blocked: majorant levels 0-1 in 4x4x4-cell blocks where the product has a kernel for them (majorant_layout = 1: variant 4 instead of 2)."""
     L = lib(fast_tap)
     p = orc_renderer.params()
     assert C.sizeof(p) == L.hk_uniforms_size(), (C.sizeof(p), L.hk_uniforms_size())
@@ -100,6 +117,6 @@ def render(orc_renderer, spp, rect=None, fb=None, first_sample=1, fast_tap=False
                         lut.ctypes.data_as(C.c_void_p) if lut is not None else None,
                         env.ctypes.data_as(C.c_void_p), env.shape[1], env.shape[0],
                         orc_renderer.impmap.ctypes.data_as(C.c_void_p), 512,
-                        fb.ctypes.data_as(C.c_void_p), x0, y0, x1, y1, first_sample, spp)
+                        fb.ctypes.data_as(C.c_void_p), x0, y0, x1, y1, first_sample, spp, 1 if wide else 0, HS_MAJ_BLOCKED if blocked else 0)
     assert steps >= 0
     return fb, steps

@@ -37,26 +37,133 @@ static void trace_access(const Hot& h, const SceneParams& P) {
     }
 }
 
-// lane steps per compiled form since the last hk_cfg_steps(reset): [0] TraceCfg<false, 0, 0, 0, 2>, [1] <false, 0, 0, 1, 2>, [2] <false, 2, 2, 2, 2>, [3] <true, 2, 2, 2, 2>
-static unsigned long long g_cfg_steps[4] = { 0, 0, 0, 0 };
+// ---- the compiled forms of the lane code: exactly the 14 configurations the device ships (volren_amd/csrc/vr_pathtrace.hip Cfg) -----------------------------------
+// form = 2 * slot + (transfer function ? 1 : 0); slots: 0 variant 0 with 32-bit gather offsets, 1 variant 0 with 64-bit addresses ("wide"), 2 and 3 the same for variant 1,
+// 4 variant 2, 5 variant 4, 6 variant 3 (the last three always form 64-bit addresses).  What stays out is what only the device's scheduler has: the emission
+// state cached in the hot registers (collide_finish's CACHED) and the LDS stores.
+enum { HK_SLOTS = 7, HK_FORMS = 2 * HK_SLOTS, HK_COUNTERS = 5 };
+template <int SLOT, bool TF> struct FormCfg;
+template <bool TF> struct FormCfg<0, TF> { using type = TraceCfg<TF, 0, 0, 0, 0, true>; };
+template <bool TF> struct FormCfg<1, TF> { using type = TraceCfg<TF, 0, 0, 0, 0, false>; };
+template <bool TF> struct FormCfg<2, TF> { using type = TraceCfg<TF, 0, 0, 1, 0, true>; };
+template <bool TF> struct FormCfg<3, TF> { using type = TraceCfg<TF, 0, 0, 1, 0, false>; };
+template <bool TF> struct FormCfg<4, TF> { using type = TraceCfg<TF, 0, 1, 0, 0, false>; };
+template <bool TF> struct FormCfg<5, TF> { using type = TraceCfg<TF, 0, 1, 0, 1, false>; };
+template <bool TF> struct FormCfg<6, TF> { using type = TraceCfg<TF, 2, 2, 2, 2, false>; };
+// per form since the last hk_form_steps(reset): [0] lane steps, then the steps of the hot pair by the segment's kind, counted before each lane_step from seg_clean(l)
+// and l.state: [1] march on a clean segment, [2] collide on a clean one, [3] march on a segment that is not clean (the general forms), [4] collide on such a one
+static unsigned long long g_form_steps[HK_FORMS][HK_COUNTERS] = {};
+
+struct ColdHost {
+    float v[C_COUNT];
+    float ld(int32_t f) const { return v[f]; }
+    void st(int32_t f, float x) { v[f] = x; }
+};
+
+// Which form serves a scene: vr_launch.hip pathtrace_variant_of / pathtrace_wide_of, restated (that file is device code).  `paired`: the scene's two brick grids
+// share a paired atlas (build_lane_scene below, as RendererHIP::fill_params decides it).
+static int form_of(const SceneParams& P, bool paired, bool force_wide) {
+    const Uniforms& u = P.u;
+    const bool scale_ok = u.vol_density_scale >= 1.0f / 65536.0f && u.vol_density_scale <= 16777216.0f;
+    int slot;
+    if (u.integrator != 0 || !P.env_div_safe || !scale_ok) slot = 6;
+    else if (u.has_emission) slot = (P.density.dense || P.emission.dense || (VR_PAIRED_ATLAS && !paired)) ? 6 : (P.density.maj_blocked ? 5 : 4);
+    else {
+        uint64_t m = grid_largest_table_bytes(P.density, false, u.use_tf != 0);
+        const bool wide = force_wide || m >= (1ull << 32);
+        slot = (P.density.dense ? 2 : 0) + (wide ? 1 : 0);
+    }
+    return 2 * slot + (u.use_tf ? 1 : 0);
+}
+
+// The scene with the views the serving kernel gets (RendererHIP::fill_params): two brick grids of one brick layout under the DDA trackers, with a warp table that
+// passed the division check and a density scale the fixed kernels take, are read from ONE paired atlas -- and only that kernel reads a majorant table whose
+// levels 0-1 are in 4x4x4-cell blocks; for every other scene the table is built linear, whatever the caller asked for.
+static bool build_lane_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
+                             const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim, int flags) {
+    build_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
+    SceneParams& P = S.P;
+    const bool scale_ok = P.u.vol_density_scale >= 1.0f / 65536.0f && P.u.vol_density_scale <= 16777216.0f;
+    const bool paired = VR_PAIRED_ATLAS && P.u.has_emission && emission && !P.density.dense && !P.emission.dense && P.u.integrator == 0 && P.env_div_safe && scale_ok &&
+                        P.density.nb[0] == P.emission.nb[0] && P.density.nb[1] == P.emission.nb[1] && P.density.nb[2] == P.emission.nb[2];
+    if (!paired && P.density.maj_blocked) build_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags | HS_MAJ_LINEAR);
+    if (paired) {
+        build_paired_atlas(S.dg, S.eg, S.paired);
+        P.density.atlas = S.paired.data();
+        P.emission.atlas = S.paired.data();
+        P.paired = 1;
+    }
+    return paired;
+}
+
+// wave-sized work units exactly like the HIP kernel: 8x8 tile x chunk of samples -> sample buffer -> running mean
+template <class K>
+static long long render_units(const SceneParams& P, int form, float* fb, int x0, int y0, int x1, int y1, int first_sample, int n_samples) {
+    const Uniforms& u = P.u;
+    const int W = u.resolution[0], H = u.resolution[1];
+    long long steps = 0;
+    unsigned long long* count = g_form_steps[form];
+    const int spu = n_samples < 32 ? n_samples : 32;
+    std::vector<float> sbuf((size_t)spu * 64 * 4);
+    for (int ty = y0 & ~7; ty < y1; ty += 8)
+        for (int tx = x0 & ~7; tx < x1; tx += 8)
+            for (int c0 = 0; c0 < n_samples; c0 += spu) {
+                WorkUnit wu;
+                wu.px0 = tx; wu.py0 = ty; wu.first_sample = first_sample + c0;
+                const int sc = (n_samples - c0) < spu ? (n_samples - c0) : spu;
+                wu.n_items = sc * 64; wu.base = 0u; wu.out = sbuf.data();
+                // 64 lanes advanced round-robin: exercises the item hand-out in a different order than the GPU does
+                Hot lanes[64];
+                ColdHost cold[64] = {};
+                FirstStash stash[64] = {};
+                for (auto& l : lanes) hot_init(l);
+                uint32_t next_item = 0;
+                bool live = true;
+                while (live) {
+                    live = false;
+                    for (int i = 0; i < 64; ++i) {
+                        Hot& l = lanes[i];
+                        if (l.state == ST_DONE) continue;
+                        live = true;
+                        if (l.state == ST_NEW) for (float& v : cold[i].v) v = nan_();         // a new path must not depend on what its cold line held
+                        if (l.state == ST_MARCH || l.state == ST_COLLIDE) {
+                            if (g_trace) trace_access(l, P);
+                            ++count[(seg_clean(l) ? 1 : 3) + (l.state == ST_COLLIDE ? 1 : 0)];
+                        }
+                        lane_step<K>(l, cold[i], P, wu, next_item, stash[i]);
+                        ++count[0];
+                        if (++steps > (1ll << 40)) return -1;
+                    }
+                }
+                for (int p = 0; p < 64; ++p) {
+                    const int x = tx + (p & 7), y = ty + (p >> 3);
+                    if (x < x0 || x >= x1 || y < y0 || y >= y1 || x >= W || y >= H) continue;
+                    float* px = fb + 4 * ((size_t)y * W + x);
+                    for (int k = 0; k < sc; ++k) accumulate_sample(px, &sbuf[4 * ((size_t)k * 64 + p)], first_sample + c0 + k);
+                }
+            }
+    return steps;
+}
 
 extern "C" {
 
 int hk_uniforms_size() { return (int)sizeof(Uniforms); }
-void hk_cfg_steps(unsigned long long out[4], int reset) {
-    for (int i = 0; i < 4; ++i) { if (out) out[i] = g_cfg_steps[i]; if (reset) g_cfg_steps[i] = 0; }
+int hk_form_count() { return HK_FORMS; }
+void hk_form_steps(unsigned long long out[HK_FORMS * HK_COUNTERS], int reset) {
+    for (int f = 0; f < HK_FORMS; ++f) for (int k = 0; k < HK_COUNTERS; ++k) { if (out) out[f * HK_COUNTERS + k] = g_form_steps[f][k]; if (reset) g_form_steps[f][k] = 0; }
 }
 
-// env_rgb: texture order (row 0 bottom), 3 floats per texel.  Returns the number of lane steps executed.
+// env_rgb: texture order (row 0 bottom), 3 floats per texel.  force_wide: the 64-bit form of variants 0 and 1 whatever the tables' sizes (the product's
+// "wide_addressing"); flags: host_scene.h HS_*.  Returns the number of lane steps executed.
 long long hk_render(const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
                     const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim,
-                    float* fb, int x0, int y0, int x1, int y1, int first_sample, int n_samples) {
+                    float* fb, int x0, int y0, int x1, int y1, int first_sample, int n_samples, int force_wide, int flags) {
     HostScene S;
-    build_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim);
+    const bool paired = build_lane_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
     const SceneParams& P = S.P;
     const Uniforms& u = P.u;
     long long steps = 0;
-    const int W = u.resolution[0], H = u.resolution[1];
+    const int W = u.resolution[0];
     if (u.integrator == 2 && u.use_tf) {       // direct volume rendering: one call per (pixel, sample)
         for (int y = y0; y < y1; ++y) for (int x = x0; x < x1; ++x) {
             float* px = fb + 4 * ((size_t)y * W + x);
@@ -71,58 +178,15 @@ long long hk_render(const Uniforms* up, const hk_grid_desc* density, const hk_gr
         }
         return steps;
     }
-    // wave-sized work units exactly like the HIP kernel: 8x8 tile x chunk of samples -> sample buffer -> running mean
-    const int spu = n_samples < 32 ? n_samples : 32;
-    std::vector<float> sbuf((size_t)spu * 64 * 4);
-    for (int ty = y0 & ~7; ty < y1; ty += 8)
-        for (int tx = x0 & ~7; tx < x1; tx += 8)
-            for (int c0 = 0; c0 < n_samples; c0 += spu) {
-                WorkUnit wu;
-                wu.px0 = tx; wu.py0 = ty; wu.first_sample = first_sample + c0;
-                const int sc = (n_samples - c0) < spu ? (n_samples - c0) : spu;
-                wu.n_items = sc * 64; wu.base = 0u; wu.out = sbuf.data();
-                // 64 lanes advanced round-robin: exercises the item hand-out in a different order than the GPU does
-                struct ColdHost {
-                    float v[C_COUNT];
-                    float ld(int32_t f) const { return v[f]; }
-                    void st(int32_t f, float x) { v[f] = x; }
-                };
-                Hot lanes[64];
-                ColdHost cold[64] = {};
-                FirstStash stash[64] = {};
-                for (auto& l : lanes) hot_init(l);
-                uint32_t next_item = 0;
-                bool live = true;
-                while (live) {
-                    live = false;
-                    for (int i = 0; i < 64; ++i) {
-                        Hot& l = lanes[i];
-                        if (l.state == ST_DONE) continue;
-                        live = true;
-                        if (l.state == ST_NEW) for (float& v : cold[i].v) v = nan_();         // a new path must not depend on what its cold line held
-                        if (g_trace && (l.state == ST_MARCH || l.state == ST_COLLIDE)) trace_access(l, P);
-#if VR_WORLD_SLOT
-                        // VR_WORLD_SLOT (vr_trace.h; on by default since round 6): the kernels of one scene kind that keep a parked path's world ray in its slot -- DDA
-                        // trackers, no transfer function, no emission grid (the lane code of the emission kernels, which read the paired atlas, is not run here; their
-                        // lookups are: probe_host.cpp).  tests/test_host_kernel.py::test_state_machine_matches_oracle asserts that these two forms ran (hk_cfg_steps)
-                        if (!u.use_tf && u.integrator == 0 && !u.has_emission) {
-                            if (P.density.dense) { lane_step<TraceCfg<false, 0, 0, 1, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[1]; }
-                            else { lane_step<TraceCfg<false, 0, 0, 0, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[0]; }
-                        } else
-#endif
-                        if (u.use_tf) { lane_step<TraceCfg<true, 2, 2, 2, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[3]; }
-                        else { lane_step<TraceCfg<false, 2, 2, 2, 2>>(l, cold[i], P, wu, next_item, stash[i]); ++g_cfg_steps[2]; }
-                        if (++steps > (1ll << 40)) return -1;
-                    }
-                }
-                for (int p = 0; p < 64; ++p) {
-                    const int x = tx + (p & 7), y = ty + (p >> 3);
-                    if (x < x0 || x >= x1 || y < y0 || y >= y1 || x >= W || y >= H) continue;
-                    float* px = fb + 4 * ((size_t)y * W + x);
-                    for (int k = 0; k < sc; ++k) accumulate_sample(px, &sbuf[4 * ((size_t)k * 64 + p)], first_sample + c0 + k);
-                }
-            }
-    return steps;
+    const int form = form_of(P, paired, force_wide != 0);
+    switch (form) {
+#define HK_FORM(SLOT) \
+    case 2 * SLOT: return render_units<FormCfg<SLOT, false>::type>(P, form, fb, x0, y0, x1, y1, first_sample, n_samples); \
+    case 2 * SLOT + 1: return render_units<FormCfg<SLOT, true>::type>(P, form, fb, x0, y0, x1, y1, first_sample, n_samples);
+    HK_FORM(0) HK_FORM(1) HK_FORM(2) HK_FORM(3) HK_FORM(4) HK_FORM(5) HK_FORM(6)
+#undef HK_FORM
+    default: return -1;
+    }
 }
 
 #if defined(VR_HOST_TRACE)
@@ -223,11 +287,6 @@ long long hk_l2_breakdown(const Uniforms* up, const hk_grid_desc* density, const
     sink.density_table = P.density.atlas; sink.emission_table = u.has_emission ? P.emission.atlas : nullptr; sink.maj_table = P.density.majorant16;
     sink.maj_coarse_from = majorant_level_offset((uint32_t)(P.density.mshift[0] + P.density.mshift[1] + P.density.mshift[2]), 2u);
     sink.paired = paired != 0;
-    struct ColdHost {
-        float v[C_COUNT];
-        float ld(int32_t f) const { return v[f]; }
-        void st(int32_t f, float x) { v[f] = x; }
-    };
     struct Path { Hot h; ColdHost c; FirstStash stash; uint64_t last[SC_COUNT]; bool scattered; };
     std::vector<Path> paths((size_t)population);
     for (Path& p : paths) { hot_init(p.h); p.h.state = ST_NEW; memset(p.last, 0, sizeof p.last); p.scattered = false; memset(&p.c, 0, sizeof p.c); p.stash = FirstStash{}; }

@@ -130,7 +130,8 @@ struct HostScene {
     std::vector<uint8_t> paired;          // the paired atlas (build_paired_atlas); the views of P do not point into it
 };
 // flags of build_scene
-enum { HS_MAJ_BLOCKED = 1, HS_NO_FLOAT_ATLAS = 2, HS_NO_COMPACT_ENV = 4 };
+// (8 belongs to probe_host.cpp: pair the atlases.)  HS_MAJ_LINEAR: a linear majorant table whatever HS_MAJ_BLOCKED and VR_HOST_MAJ_BLOCKED say
+enum { HS_MAJ_BLOCKED = 1, HS_NO_FLOAT_ATLAS = 2, HS_NO_COMPACT_ENV = 4, HS_MAJ_LINEAR = 16 };
 inline void build_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
                         const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim, int flags = 0) {
     SceneParams& P = S.P;
@@ -141,7 +142,8 @@ inline void build_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* de
     P.u = u;
     build_grid(dg, u, lut, density->nb, density->indirection, density->range, density->atlas_dim, density->atlas, density->n_mips, density->mips, true,
                // the majorant table's levels 0-1 in 4x4x4-cell blocks (a per-grid choice of the product since round 5; the lane code reads the view's flag at run time here)
-               (flags & HS_MAJ_BLOCKED) != 0 || (std::getenv("VR_HOST_MAJ_BLOCKED") != nullptr && std::getenv("VR_HOST_MAJ_BLOCKED")[0] == '1'), (flags & HS_NO_FLOAT_ATLAS) == 0);
+               (flags & HS_MAJ_LINEAR) == 0 && ((flags & HS_MAJ_BLOCKED) != 0 || (std::getenv("VR_HOST_MAJ_BLOCKED") != nullptr && std::getenv("VR_HOST_MAJ_BLOCKED")[0] == '1')),
+               (flags & HS_NO_FLOAT_ATLAS) == 0);
     P.density = dg.view;
     // (blocked: == dense_grid_to_device: 4x4x4 blocks)
     if (density->dense) {

@@ -1776,6 +1776,55 @@ def test_random_parameter_sets_match_oracle():
         _assert_same(r.framebuffer(), o.render(spp), "random set %d: %s %dx%d %d spp %s" % (i, base, w, h, spp, fields))
 
 
+def test_random_parameter_sets_match_oracle_on_the_other_scene_kinds():
+    """The same on the scene kinds smoke.brick does not reach: the dense fp16 grid (variant 1, in both addressing forms), two brick grids with emission (variant 2) and
+    the same with majorant levels 0-1 in blocks (variant 4), each with and without a transfer function, the camera in about a third of the draws so far away that
+    its segments are not clean (FLAG_VARIANTS "camera_very_far": the general copy of the hot pair).  The density scale stays within [2^-16, 2^24], so the kernel of
+    the scene kind serves the frame -- asserted -- and not the run-time variant."""
+    rs = np.random.RandomState(20291)      # (a seed whose ten draws hold every base with and without a LUT, the wide form, and the far camera on variants 1, 1 + LUT and 4)
+    far = FLAG_VARIANTS["camera_very_far"][1]
+    oracles = {}
+    for i in range(10):
+        base, blocked = (("c4:64", False), ("c5:64", False), ("c5:64", True))[int(rs.randint(3))]
+        lut = bool(rs.rand() < 0.5)
+        variant = 1 if base == "c4:64" else (4 if blocked else 2)
+        wide = int(variant == 1 and rs.rand() < 0.5)
+        w, h, spp = int(rs.randint(3, 71)), int(rs.randint(3, 61)), int(rs.randint(1, 7))
+        fields = dict(bounces=int(rs.randint(1, 24)), albedo=tuple(float(x) for x in rs.uniform(0.0, 1.0, 3)), phase=float(rs.uniform(-0.9, 0.9)),
+                      density_scale=float(10.0 ** rs.uniform(0.0, 3.0)), env_strength=float(rs.uniform(0.1, 5.0)), show_environment=bool(rs.rand() < 0.7),
+                      cam_fov=float(rs.uniform(15.0, 110.0)), seed=int(rs.randint(-1000, 1000)))
+        assert 2.0 ** -16 <= fields["density_scale"] <= 2.0 ** 24
+        d = rs.normal(size=3)
+        d /= np.linalg.norm(d)
+        dist = float(rs.uniform(0.2, 2.5))
+        fields["cam_pos"] = tuple(float(x) for x in (-d * dist))
+        fields["cam_dir"] = tuple(float(x) for x in (d + rs.normal(scale=0.15, size=3)))
+        if rs.rand() < 1.0 / 3.0:
+            fields.update(far)
+        rot = float(rs.uniform(0.0, 360.0))
+        if (base, lut) not in oracles:                     # the oracle's copy of a scene is encoded once; every field below is set anew in each draw
+            oracles[(base, lut)] = scenes.oracle_scene(base, w, h)
+            if lut:
+                oracles[(base, lut)].load_transferfunc(scenes.LUT)
+        o = oracles[(base, lut)]
+        o.resize(w, h)
+        r = scenes.hip_scene(base, w, h)
+        if lut:
+            r.load_transferfunc(scenes.LUT)
+        r.majorant_layout = 1 if blocked else 0
+        r.wide_addressing = wide
+        o.set_env_rot(rot)
+        r.env_rot = rot
+        for k, v in fields.items():
+            setattr(o, k, v)
+            setattr(r, k, v)
+        what = "random set %d: %s%s%s%s %dx%d %d spp %s" % (i, base, " blocked" if blocked else "", " lut" if lut else "", " wide" if wide else "", w, h, spp, fields)
+        assert r.kernel_variant == variant and r.kernel_variant_reason == 0, what
+        assert r.kernel_wide == (1 if (wide or variant >= 2) else 0), what
+        r.render(spp)
+        _assert_same(r.framebuffer(), o.render(spp), what)
+
+
 @pytest.mark.gpu
 def test_nan_ray_parameter_on_a_clean_segment():
     """A free-flight draw of exactly 0 (one in 2^24 segments) that meets an empty first cell makes the reference's step back to the collision point 0 / 0: the ray

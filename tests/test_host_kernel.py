@@ -18,14 +18,13 @@ def _same(a, b):
 def test_state_machine_matches_oracle(name, w, h, spp):
     r = scenes.oracle_scene(name, w, h)
     want = r.render(spp).copy()
-    hk.cfg_steps(reset=True)
+    hk.form_steps(reset=True)
     got, steps = hk.render(r, spp)
     assert steps > 0
     assert _same(got, want), "relative L2 %.3e" % scenes.rel_l2(got[..., :3], want[..., :3])
-    # which compiled form of the lane code ran (host_kernel.cpp hk_cfg_steps): smoke.brick without a LUT is served by the brick kernel's own form
-    # TraceCfg<false, 0, 0, 0, 2> (VR_WORLD_SLOT, on by default), with one by the run-time form <true, 2, 2, 2, 2> -- a changed default must not drop either silently
-    brick, dense, general, general_tf = hk.cfg_steps()
-    assert (brick, dense, general, general_tf) == ((0, 0, 0, steps) if name == "c3" else (steps, 0, 0, 0))
+    # which compiled form of the lane code ran (host_kernel.cpp hk_form_steps), and that no other did: smoke.brick is served by the brick kernel, variant 0 with
+    # 32-bit gather offsets -- TraceCfg<false, 0, 0, 0, 0, true> without a LUT, <true, 0, 0, 0, 0, true> with one -- a changed default must not drop either silently
+    assert hk.forms_that_ran() == {(0, False, name == "c3"): steps}
 
 
 @pytest.mark.parametrize("name,w,h,spp", [("c1", 64, 64, 16), ("c2", 48, 48, 16)])
@@ -127,14 +126,19 @@ def test_emission_grid():
 
 
 def test_blocked_majorant_layout(monkeypatch):
-    """Round 5: the majorant table's levels 0-1 in 4x4x4-cell blocks (vr_scene.h majorant_cell_index), a per-grid layout choice of the product.  The lane code
-    compiled for the host reads the layout flag at run time; the frame must not depend on it (the table is a permutation of the same cells)."""
+    """Round 5: the majorant table's levels 0-1 in 4x4x4-cell blocks (vr_scene.h majorant_cell_index), a per-grid layout choice of the product.  The frame must
+    not depend on it (the table is a permutation of the same cells).  As in the product (RendererHIP::fill_params) only the kernel of two paired brick grids
+    reads a blocked table -- variant 4, the form compiled for it --; a single grid's table stays linear whatever is asked for."""
     monkeypatch.setenv("VR_HOST_MAJ_BLOCKED", "1")
     o = scenes.oracle_scene("c1", 40, 32)
     want = o.render(4).copy()
-    got, _ = hk.render(o, 4)
+    hk.form_steps(reset=True)
+    got, steps = hk.render(o, 4)
     assert _same(got, want)
+    assert hk.forms_that_ran() == {(0, False, False): steps}
+    hk.form_steps(reset=True)
     test_emission_grid()
+    assert list(hk.forms_that_ran()) == [(4, True, False)]
 
 
 def test_dense_fp16_grid():
@@ -147,11 +151,11 @@ def test_dense_fp16_grid():
     o.cam_fov = 40.0
     o.bounces = 8
     want = o.render(8).copy()
-    hk.cfg_steps(reset=True)
+    hk.form_steps(reset=True)
     got, steps = hk.render(o, 8)
     assert want[..., 3].max() > 0
     assert _same(got, want)
-    assert hk.cfg_steps() == (0, steps, 0, 0)                # the dense kernel's own form, TraceCfg<false, 0, 0, 1, 2>
+    assert hk.forms_that_ran() == {(1, False, False): steps}         # the dense kernel's own form and no other: variant 1, TraceCfg<false, 0, 0, 1, 0, true>
 
 
 def test_degenerate_inputs_do_not_diverge():
@@ -268,3 +272,103 @@ def test_segments_that_are_not_clean():
         got, steps = hk.render(r, 6, fast_tap=fast_tap)
         assert steps > 0
         assert _same(got, want), "relative L2 %.3e" % scenes.rel_l2(got[..., :3], want[..., :3])
+
+
+# ---- every shipped form of the lane code, general and clean copies of the hot pair --------------------------------------------------------------------------------
+# form (hk_binding.FORMS) -> the scene that the product's launch serves with it: (config, transfer function, integrator, majorant levels 0-1 blocked)
+FORM_SCENES = {}
+for _tf in (False, True):
+    for _wide in (False, True):
+        FORM_SCENES[(0, _wide, _tf)] = ("c3" if _tf else "c2", False, 0, False)
+        FORM_SCENES[(1, _wide, _tf)] = ("c4:64", _tf, 0, False)
+    FORM_SCENES[(2, True, _tf)] = ("c5:64", _tf, 0, False)
+    FORM_SCENES[(4, True, _tf)] = ("c5:64", _tf, 0, True)
+    FORM_SCENES[(3, True, _tf)] = ("c3" if _tf else "c2", False, 1, False)      # the global-majorant trackers: served by the run-time variant
+FW, FH, FSPP = 40, 40, 4
+_far = {}
+
+
+def _far_scene(config, lut, integrator, shadow_tail=False):
+    """(oracle renderer with the far camera, its frame): rendered once, shared by the forms that serve the scene"""
+    key = (config, lut, integrator, shadow_tail)
+    if key not in _far:
+        r = _far_camera(scenes.oracle_scene(config, FW, FH))
+        if lut:
+            r.load_transferfunc(scenes.LUT)
+        r.integrator = integrator
+        if shadow_tail:
+            r.bounces, r.albedo = 1000, (1.0, 1.0, 1.0)
+        ipos = np.array(r.params().vol_density_inv_transform, np.float32).reshape(4, 4).T @ np.array([*r.cam_pos, 1.0], np.float32)
+        assert np.abs(ipos[:3]).max() > 2.0 ** 20                       # the camera segments are not clean ...
+        want = r.render(FSPP).copy()
+        assert want[..., 3].max() == 1.0 and want[..., 3].mean() > 0.01      # ... and they do march: the volume is hit
+        _far[key] = (r, want)
+    return _far[key]
+
+
+def _check_form(form, r, want, fast_tap):
+    variant, wide, _ = form
+    blocked = FORM_SCENES[form][3]
+    hk.form_steps(reset=True, fast_tap=fast_tap)
+    got, steps = hk.render(r, FSPP, fast_tap=fast_tap, wide=wide and variant < 2, blocked=blocked)
+    assert steps > 0
+    assert _same(got, want), "form %s: relative L2 %.3e" % (form, scenes.rel_l2(got[..., :3], want[..., :3]))
+    assert hk.forms_that_ran(fast_tap=fast_tap) == {form: steps}       # the intended form served the scene, and no other
+    c = hk.form_steps(fast_tap=fast_tap)[form]
+    print("form", form, "fast_tap", fast_tap, c)
+    assert c["general_collide"] > 0
+    if FORM_SCENES[form][2] != 0:
+        # the global-majorant trackers go from collision to collision (begin_segment, collide_finish: no DDA march) and none of their segments is clean
+        assert c["general_march"] == 0 and c["clean_march"] == 0 and c["clean_collide"] == 0
+    else:
+        assert c["general_march"] > 0
+        assert c["clean_march"] > 0 and c["clean_collide"] > 0         # the scatter and shadow segments begin inside the volume
+    return c
+
+
+@pytest.mark.parametrize("form", hk.FORMS, ids=lambda f: "v%d%s%s" % (f[0], "w" if f[1] and f[0] < 2 else "", "_lut" if f[2] else ""))
+def test_shipped_forms_on_segments_that_are_not_clean(form):
+    """Each of the 14 configurations of the lane code that the device ships (vr_pathtrace.hip Cfg; host_kernel.cpp FormCfg), compiled for the host, renders a frame
+    whose camera segments are not clean (test_segments_that_are_not_clean) on the scene kind its kernel serves: bit for bit the oracle's, with the reference's
+    filter tests and with the device's (VR_TAP_FAST), the general forms of march and collision AND the clean ones having run in that form and no step in another."""
+    config, lut, integrator, _ = FORM_SCENES[form]
+    r, want = _far_scene(config, lut, integrator)
+    for fast_tap in (False, True):
+        _check_form(form, r, want, fast_tap)
+
+
+@pytest.mark.parametrize("form", [f for f in hk.FORMS if not f[2]], ids=lambda f: "v%d%s" % (f[0], "w" if f[1] and f[0] < 2 else ""))
+def test_shipped_forms_shadow_tail_on_segments_that_are_not_clean(form):
+    """1000 bounces at albedo 1: the paths live until they leave, and most of their shadow rays end blocked -- collide_finish's shadow tail and its shortcut, in the
+    forms without a transfer function, on a frame with segments that are not clean."""
+    config, lut, integrator, _ = FORM_SCENES[form]
+    r, want = _far_scene(config, lut, integrator, shadow_tail=True)
+    _check_form(form, r, want, False)
+
+
+@pytest.mark.parametrize("lut", [False, True], ids=["plain", "lut"])
+def test_runtime_form_with_the_dda_trackers_on_segments_that_are_not_clean(lut):
+    """The run-time variant also serves the one grid combination without a kernel of its own, a dense fp16 density grid with a brick emission grid, with the DDA
+    trackers: the general march of TraceCfg<TF, 2, 2, 2, 2, false>, which the global trackers of the test above never reach."""
+    import encoder_ref
+    n = 40
+    dens = scenes.synthetic_density(n)
+    temp = np.clip(dens * 0.2 + 0.1 * scenes.synthetic_density(n, seed=99), 0, None).astype(np.float32)
+    gt = encoder_ref.encode(temp)
+    o = ob.OracleRenderer(FW, FH)
+    o.load_envmap(scenes.HDR)
+    o.set_volume(encoder_ref.encode_dense_fp16(dens), emission=gt, majorant_emission=gt.min_maj[1])
+    if lut:
+        o.load_transferfunc(scenes.LUT)
+    o.bounces, o.albedo, o.emission_scale = 8, (0.7, 0.8, 0.9), 50.0
+    _far_camera(o)
+    ipos = np.array(o.params().vol_density_inv_transform, np.float32).reshape(4, 4).T @ np.array([*o.cam_pos, 1.0], np.float32)
+    assert np.abs(ipos[:3]).max() > 2.0 ** 20
+    want = o.render(FSPP).copy()
+    assert want[..., 3].max() == 1.0 and want[..., 3].mean() > 0.01
+    hk.form_steps(reset=True)
+    got, steps = hk.render(o, FSPP)
+    assert _same(got, want)
+    assert hk.forms_that_ran() == {(3, True, lut): steps}
+    c = hk.form_steps()[(3, True, lut)]
+    assert c["general_march"] > 0 and c["general_collide"] > 0 and c["clean_march"] > 0 and c["clean_collide"] > 0
