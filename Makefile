@@ -6,7 +6,8 @@ ARCH     ?= gfx950
 CSRC     := volren_amd/csrc
 # -ffp-contract=off: the renderer's fp32 arithmetic is specified operation by operation (vr_math.h)
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-unused-result -Iinclude
-HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
+# EXTRA: flags of an experiment build, which goes to an OBJDIR of its own (tests/tools_build_variant.sh); empty otherwise
+HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS) $(EXTRA)
 OBJDIR   := build
 SRCS_CPP := grids.cpp imageio.cpp environment.cpp transferfunc.cpp renderer.cpp sharded.cpp capi.cpp
 PT_VARIANTS := 0 1 2 3 4
@@ -16,7 +17,7 @@ PT_WIDE_VARIANTS := 0 1
 HIP_OBJS := vr_launch.o vr_filters.o vr_setup.o vr_probe.o
 OBJS     := $(HIP_OBJS:%=$(OBJDIR)/%) $(OBJDIR)/vr_fastprobe.o $(PT_VARIANTS:%=$(OBJDIR)/vr_pathtrace_%.o) $(PT_VARIANTS:%=$(OBJDIR)/vr_ptfast_%.o) $(PT_WIDE_VARIANTS:%=$(OBJDIR)/vr_ptwide_%.o) $(PT_WIDE_VARIANTS:%=$(OBJDIR)/vr_ptwf_%.o) $(SRCS_CPP:%.cpp=$(OBJDIR)/%.o)
 # tolerance-mode kernels (opt-in, vr_math.h VR_FAST_MATH): hardware transcendentals, reciprocal division, contraction allowed
-FASTFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-hip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Wno-unused-result -Iinclude -DVR_FAST_MATH=1
+FASTFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-hip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Wno-unused-result -Iinclude -DVR_FAST_MATH=1 $(EXTRA)
 # path-tracing kernels: no SLP vectorisation.  On gfx950 a packed fp32 instruction (v_pk_mul/add/fma_f32) occupies the SIMD for
 # 4.2 cycles against 1.8 for the plain one (profiles/r2_valu_issue_rate.txt) and needs extra moves to pair its operands: the
 # scalar form of the same arithmetic is 4 % (c2) / 2 % (c3) / 1 % (c4) faster (profiles/r2p_compiler_flags.txt); results identical.
@@ -58,7 +59,8 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-volren_amd/libvolren_amd.so: $(OBJS)
+# (the second target: the library of an experiment build, beside its objects)
+volren_amd/libvolren_amd.so $(OBJDIR)/libvolren_amd.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS) -lz -ldl
 
 volren_amd/volren: $(CSRC)/main.cpp volren_amd/libvolren_amd.so $(HDRS)

@@ -31,7 +31,7 @@ COST = {"simple": 1.75, "fma": 1.85, "vop3": 2.75, "cvt": 2.65, "cmp": 3.2, "cnd
         "mul24": 2.6, "u64": 2.86, "pk": 2.86, "sgpr_src": 0.9}
 TOP = {   # innermost function / section -> top-level block (None: inherit from the block before)
     "march": ("march_prep", "step_dda", "majorant_index", "march_finish", "majorant_fetch", "majorant_value", "march_load", "march_idle", "majorant_cell_index", "majorant_level_offset", "round_mip_q",
-              "cvt_flr", "seg_far", "majorant_of"),
+              "cvt_flr", "seg_far"),
     "collide": ("tricubic_tap", "tricubic_tap_t", "tricubic_axis_fast", "tricubic_fast_test", "tricubic_axis_weights", "tap_addr", "tap_load", "tap_value", "collide_prep", "collide_finish", "collide_load",
                 "collide_idle", "nan_guard", "rng_skip9", "trilinear_prep", "trilinear_load", "trilinear_value", "axis_cells", "tf_lookup_at", "brick_voxel_line", "pair_voxel_line", "voxel_index"),
     "new": ("do_new", "tea32", "make_unit"),

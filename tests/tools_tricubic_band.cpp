@@ -1,8 +1,8 @@
 // Verifier for the fast decision of the stochastic-tricubic filter tests (vr_trace.h: tricubic_axis_fast / tricubic_fast_test).
 // TEST TOOL -- compiles the product's lane code for the host, like tests/hostkernel.
 //
-// (Round 5: the product's test is x = RN(k s' - W') against -G / +G with W' = 2^24 w' and an absolute band G, VR_TAP_ABS_BAND in vr_trace.h; this tool
-// searches the product's own tricubic_fast_test, so it checks whichever form the header compiles.  The comparisons named below are round 2's.)
+// (The product's test is x = RN(k s' - W') against -G / +G with W' = 2^24 w' and an absolute band G, round 5's form in vr_trace.h; this tool searches the
+// product's own tricubic_fast_test.  The comparisons named below are round 2's, whose relative band that form replaced.)
 // Claim checked: for every fractional coordinate t a float can take in [0, 1] and EVERY one of the 2^24 values a draw can take,
 // a test that the fast path decides ("yes" / "no") is decided the same way by the reference's code
 //     r < w / s,   r = k * 2^-24,   w, s from tricubic_axis_weights (common.glsl:221-244 restated operation by operation),
@@ -22,11 +22,7 @@
 #include "../volren_amd/csrc/vr_trace.h"
 
 using namespace vr;
-#if VR_TAP_ABS_BAND
 #define VR_BAND_TEXT "absolute, 160 units of k s, round 5's form; draws and weights scaled by kTapDrawScale"
-#else
-#define VR_BAND_TEXT "2^-18 relative, round 2's form"
-#endif
 
 static const double TWO24 = 16777216.0;
 
@@ -48,11 +44,7 @@ template <class Pred> static inline int64_t first_k(double k0, Pred pred) {
     return k;
 }
 
-#if VR_TAP_ABS_BAND
-static const float KS = kTapDrawScale;                       // a draw enters the product's test as KS x k (vr_trace.h VR_TAP_PRESHIFT): exact, k < 2^24
-#else
-static const float KS = 1.0f;
-#endif
+static const float KS = kTapDrawScale;                       // a draw enters the product's test as KS x k (vr_trace.h: the state shifted left by 8): exact, k < 2^24
 static inline int decide(float k, float w, float s) {         // the product's test: 1 yes, 0 no, 2 inside the band
     bool yes, no;
     tricubic_fast_test(k * KS, w, s, yes, no);
@@ -82,11 +74,7 @@ int main(int argc, char** argv) {
             const float s = fs[j], w = fw[j];
             // both decision sets are intervals of k: the fast test's x(k) (RN(k s) against two thresholds in round 2's form, RN(k s - W) against -G / +G in
             // round 5's) is monotone in k.  The product's own test function is what is searched: first k that is NOT a yes, first k that IS a no
-#if VR_TAP_ABS_BAND
             const double g_yes = ((double)w - (double)kTapBand) / (double)s / (double)KS, g_no = ((double)w + (double)kTapBand) / (double)s / (double)KS;
-#else
-            const double g_yes = (double)fma_(w, kTapLo, -1e-20f) / (double)s, g_no = (double)fma_(w, kTapHi, 1e-20f) / (double)s;
-#endif
             const int64_t K_yes = first_k(g_yes, [w, s](float k) { bool y, n; tricubic_fast_test(k * KS, w, s, y, n); return !y; });
             const int64_t K_no = first_k(g_no, [w, s](float k) { bool y, n; tricubic_fast_test(k * KS, w, s, y, n); return n; });
             // cross-check the interval picture with the product's own test function at the boundaries
@@ -97,11 +85,7 @@ int main(int argc, char** argv) {
             if (K_yes > K_ref) { ++violations; ++decided_wrong_yes; if (std::getenv("TB_VERBOSE")) std::printf("yes>ref: q %.9g test %d K_yes %lld K_ref %lld K_no %lld  rw %.9g rs %.9g fw %.9g fs %.9g\n", q, j, (long long)K_yes, (long long)K_ref, (long long)K_no, rw[j], rs[j], fw[j], s); }
             if (K_no < K_ref) { ++violations; ++decided_wrong_no; }
             ++checked;
-#if VR_TAP_ABS_BAND
             const double T = (double)rw[j] / (double)rs[j], Tf = (double)fw[j] / (TWO24 * (double)KS) / (double)s;
-#else
-            const double T = (double)rw[j] / (double)rs[j], Tf = (double)fw[j] / (double)s;
-#endif
             if (T > 1e-30) { const double d = std::fabs(Tf / T - 1.0); if (d > max_disc) max_disc = d; }
             const double band = (double)(K_no - K_yes) / TWO24;
             if (band > max_band) max_band = band;
@@ -115,7 +99,7 @@ int main(int argc, char** argv) {
     }
     // the whole call, fast form against the reference's code (vr_trace.h tricubic_tap_t<true> / <false>): taps and RNG end state must agree for finite coordinates
     // (random points and seeds) and for coordinates that are not finite on one, two or all three axes -- a test whose x is NaN drops out of the call's min |x| and
-    // decides "no", which is what the reference's comparison against a NaN quotient decides (VR_TAP_PRESHIFT)
+    // decides "no", which is what the reference's comparison against a NaN quotient decides
     long long calls = 0, call_mismatches = 0;
     {
         uint32_t st = 0x2545F491u;

@@ -62,18 +62,6 @@ __device__ __forceinline__ WorkUnit make_unit(const LaunchDesc& D, int32_t W, ui
 #ifndef VR_WAVES_PER_SIMD
 #define VR_WAVES_PER_SIMD 4
 #endif
-#ifndef VR_MARCH_SPECULATIVE
-#define VR_MARCH_SPECULATIVE 1
-#endif
-#ifndef VR_MARCH_LOADS_PINNED
-#define VR_MARCH_LOADS_PINNED (VR_MARCH_STEPS == 2)
-#endif
-#ifndef VR_DIAG_PAD_VALU
-#define VR_DIAG_PAD_VALU 0
-#endif
-#ifndef VR_DIAG_PAD_SLEEP
-#define VR_DIAG_PAD_SLEEP 0
-#endif
 #ifndef VR_BATCH_REGS
 #define VR_BATCH_REGS 1
 #endif
@@ -86,9 +74,6 @@ __device__ __forceinline__ WorkUnit make_unit(const LaunchDesc& D, int32_t W, ui
 #endif
 #ifndef VR_PRIO_EVENTS
 #define VR_PRIO_EVENTS 0
-#endif
-#ifndef VR_EMISSION_BY_POINTER
-#define VR_EMISSION_BY_POINTER 1
 #endif
 
 // ---------------------------------------------------------------------------------------------------
@@ -107,48 +92,15 @@ __device__ __forceinline__ WorkUnit make_unit(const LaunchDesc& D, int32_t W, ui
 //     register set so the marching path stays put (VR_BATCH_REGS=0 swaps it through its LDS slot instead).
 // Everything is wave-synchronous (ballots, mbcnt ranks, scalar counters): no atomics, no barriers, no spinning; the only
 // global atomic is the work-queue head.  Which lane runs which path never changes a result.
-// Pool size = LDS share of a wavefront (10 KiB at 4 wavefronts per SIMD) / bytes per slot.  Round 3: 1/dir of a parked path is no longer kept in its slot
-// (15 dwords, 152 slots: VR_HOT_RI=1) but recomputed when the path is resumed (three exact reciprocals, vr_math.h rcp_exact): 12 dwords in 13-dword
-// slots (odd stride) = 175 slots; 12-dword slots (188, VR_HOT_STRIDE=12) measure the same (profiles/r3f_*: the pool-size elasticity is gone beyond 152).
-#ifndef VR_HOT_RI
-#define VR_HOT_RI 0
-#endif
-#ifndef VR_HOT_STRIDE
-#define VR_HOT_STRIDE (VR_HOT_RI ? 15 : 12)      /* round 5: 12-dword slots without the pad dword = 188 slots instead of 175 (13-dword, odd stride: rounds 3-4).  With the bookkeeping
-                                                    amortised over up to four passes the larger pool is worth more than the odd stride: c2 +0.6 %, c4 +0.3 %, c5cloud +-0 (profiles/r5l_*);
-                                                    150 slots: c2 -1.7 %, c4 -1.1 %; 1/dir stored again (15 dwords, 152 slots): c2 -1.2 %, c5cloud -3 % */
-#endif
-// Workgroup shape.  Default: four 4-wavefront workgroups per CU.  Build-time experiment (round 3, profiles/r3h_lds_resident_majorants.txt):
-// -DVR_WG_WAVES=16 = ONE workgroup per CU whose 16 wavefronts share nothing but read-only tables in LDS -- the transfer-function LUT once per CU
-// instead of four times and (VR_MAJ_LDS) the coarse levels of the majorant table, or all of it (smoke.brick's is 18 KiB).  Measured: the workgroup
-// shape alone +-0.5 %; serving the majorant gathers from LDS c2 +-0 (its whole table resident: 28 % of the kernel's L1 accesses gone), c3 -4 %, c4 -3 %,
-// c5full -5 % -- the select between the two sources costs what the L1-hit gathers cost.  Not adopted.
-#ifndef VR_WG_WAVES
-#define VR_WG_WAVES 4
-#endif
-#ifndef VR_MAJ_LDS
-#define VR_MAJ_LDS 0
-#endif
-constexpr int32_t kWgWaves = VR_WG_WAVES;
+// Pool size = LDS share of a wavefront (10 KiB at 4 wavefronts per SIMD) / bytes per slot.  1/dir of a parked path is not kept in its slot but recomputed when the
+// path is resumed (three exact reciprocals, vr_math.h rcp_exact): 12 dwords per slot, no pad dword = 188 slots (profiles/r3f_*, r5l_*: storing 1/dir again, 15 dwords
+// and 152 slots, c2 -1.2 %, c5cloud -3 %; the larger pool is worth more than an odd stride).
+// Workgroup shape: four 4-wavefront workgroups per CU (one 16-wavefront workgroup sharing tables in LDS, the majorant table's coarse levels among them, was not adopted:
+// profiles/r3h_lds_resident_majorants.txt).
+constexpr int32_t kWgWaves = 4;
 constexpr int32_t kLdsPerWorkgroup = 163840 / 16 * kWgWaves;      // 160 KiB per CU
 // The transfer-function kernels stage the LUT (up to kLutLdsEntries vec4 = 4 KiB) in LDS.
 constexpr int32_t kLutLdsEntries = 256;
-// cells of the majorant table's tail a kernel keeps in LDS: the brick kernel without transfer function 10 240 fp16 cells (20 KiB: all of a grid of up to
-// ~8 000 bricks), the dense-grid and emission kernels 5 120 (10 KiB: levels 2-3 of a 512^3 grid, level 3 of a 1024^3 one), the transfer-function kernels
-// 2 560 floats (10 KiB: their table holds TF-remapped floats)
-template <class K> constexpr int32_t maj_lds_cells() { return !VR_MAJ_LDS ? 0 : (K::tf ? 2560 : ((K::dense == 0 && K::emission == 0) ? 10240 : 5120)); }
-// Build-time experiment (round 3, -DVR_COLD_REGS=1; profiles/r3a_cold_state_in_registers.txt): cold path state in VECTOR REGISTERS
-// (ColdBanks below) instead of global memory, for the dense-grid kernel, whose paths scatter 3.2 times per sample (c4) and spend a
-// third of their memory-side traffic on the 64-byte cold slots.  Three wavefronts per SIMD instead of four leave each 168 registers:
-// the fourth wavefront's share of the register file holds the cold state of all 192 slots of the other three (3 banks x 20 fields =
-// 60 registers), its share of the LDS makes the pools 192 slots instead of 152.  No cold workspace, no cold traffic, bit-identical
-// images.  Measured on c4: +7 % against the same 3 x 192 configuration with the cold state in memory, but the fourth wavefront is
-// worth 10 %: 1.906 against 1.972 Gsamples/s for the default (4 x 152, cold state in memory).  Off by default.
-#ifndef VR_COLD_REGS
-#define VR_COLD_REGS 0
-#endif
-template <class K> constexpr bool cold_in_regs() { return VR_COLD_REGS != 0 && !K::tf && K::dense == 1 && K::emission == 0; }
-template <class K> constexpr int32_t waves_per_simd() { return cold_in_regs<K>() ? 3 : VR_WAVES_PER_SIMD; }
 
 enum PoolStack : int32_t { Q_READY = 0, Q_NEE = 1, Q_POST = 2, Q_ESC = 3, Q_FREE = 4, Q_COUNT = 5 };
 
@@ -156,28 +108,24 @@ enum PoolStack : int32_t { Q_READY = 0, Q_NEE = 1, Q_POST = 2, Q_ESC = 3, Q_FREE
 // path's radiance, so until round 3 do_new wrote the whole cold line up front (80 bytes per sample) and every resume / park of a camera segment moved
 // throughput and radiance through it -- also for the majority of samples that never scatter.  Now the radiance of a `first` path waits in three more dwords
 // of its LDS slot (15-dword slots, 153 of them, in the emission kernel only) and its throughput is 1: such a path touches no cold line at all.
-#ifndef VR_LAZY_EMISSION
-#define VR_LAZY_EMISSION 1
-#endif
-template <class K> constexpr bool lazy_emission() { return VR_LAZY_EMISSION != 0 && !VR_HOT_RI && K::emission == 1; }
-template <class K> constexpr int32_t hot_stride() { return lazy_emission<K>() ? 15 : VR_HOT_STRIDE; }      // dwords per slot in LDS (the parked fields, padded to an odd count)
+template <class K> constexpr bool lazy_emission() { return K::emission == 1; }
+template <class K> constexpr int32_t hot_stride() { return lazy_emission<K>() ? 15 : 12; }      // dwords per slot in LDS
 constexpr int32_t HOT_EL = 12;                           // lazy_emission kernels: radiance of a `first` path, dwords 12..14 of its slot
 // slots of a wavefront's pool: what is left of the workgroup's LDS after the shared tables, per wavefront, in slots of HOT_STRIDE dwords + Q_COUNT stack
 // bytes; at most 192 (slot ids index three register banks, ShleBanks) -- or VR_NSLOT when a build pins it
 template <class K> constexpr int32_t pool_slots() {
 #ifdef VR_NSLOT
-    return cold_in_regs<K>() ? 192 : VR_NSLOT;
+    return VR_NSLOT;
 #else
-    if (cold_in_regs<K>()) return 192;
-    const int32_t shared = maj_lds_cells<K>() * (K::tf ? 4 : 2) + (K::tf ? kLutLdsEntries * 16 + 16 : kWgWaves * 256);
+    const int32_t shared = K::tf ? kLutLdsEntries * 16 + 16 : kWgWaves * 256;
     const int32_t n = (kLdsPerWorkgroup - shared) / kWgWaves / (hot_stride<K>() * 4 + Q_COUNT);
     return n > 192 ? 192 : n;
 #endif
 }
 constexpr int32_t NSLOT = 192;             // upper bound of pool_slots (sizes the cold workspace); slot ids are bytes
-constexpr int32_t HOT_COL = VR_HOT_RI ? 12 : 4;         // where the transfer-function kernels keep the colour of a real collision until its event: in the place of
-                                                        // 1/dir (15-dword slots) or of dir (12-dword slots) -- both dead between the collision and the set-up of the next segment
-// WORLD (vr_trace.h world_slot, -DVR_WORLD_SLOT=1): dwords 1..6 hold the segment's origin and direction in WORLD space (Hot::wpos / wdir) instead of the index-space
+constexpr int32_t HOT_COL = 4;             // where the transfer-function kernels keep the colour of a real collision until its event: in the place of dir, dead between
+                                           // the collision and the set-up of the next segment
+// WORLD (vr_trace.h world_slot): dwords 1..6 hold the segment's origin and direction in WORLD space (Hot::wpos / wdir) instead of the index-space
 // ones; load_resume recomputes those with begin_segment's two transforms -- so that the collision event finds position and direction in the slot and reads no cold line
 template <int32_t HOT_STRIDE, bool WORLD = false>
 struct HotStoreT {                     // [slot][field]: a path's parked dwords are adjacent (ds_read2/ds_write2 pairs)
@@ -199,7 +147,6 @@ struct HotStoreT {                     // [slot][field]: a path's parked dwords 
         p[7] = f2u(h.t); p[8] = f2u(h.far); p[9] = f2u(h.tau);
         p[10] = f2u(h.Tr);
         p[11] = flags(h);
-        if (VR_HOT_RI) { p[12] = f2u(h.ri.x); p[13] = f2u(h.ri.y); p[14] = f2u(h.ri.z); }
     }
     // any later store: a `first` path's stash stays where it is
     __device__ __forceinline__ void save(const Hot& h, int32_t slot) const {
@@ -215,7 +162,6 @@ struct HotStoreT {                     // [slot][field]: a path's parked dwords 
         }
         p[7] = f2u(h.t); p[8] = f2u(h.far); p[9] = f2u(h.tau);
         p[11] = flags(h);
-        if (VR_HOT_RI) { p[12] = f2u(h.ri.x); p[13] = f2u(h.ri.y); p[14] = f2u(h.ri.z); }
     }
     // a path that leaves the hot pair for an event: the march / collision code only changes seed, t, tau, Tr and the flag word
     // (state, mip); ray, far and 1/dir are still in the slot from the store that preceded the path's resume
@@ -233,7 +179,7 @@ struct HotStoreT {                     // [slot][field]: a path's parked dwords 
         h.ipos = v3{ u2f(p[1]), u2f(p[2]), u2f(p[3]) };
         h.idir = v3{ u2f(p[4]), u2f(p[5]), u2f(p[6]) };
         if (WORLD) { h.wpos = h.ipos; h.wdir = h.idir; }            // (the events read wpos / wdir; a resumed path gets its index-space ray in load_resume)
-        h.ri = VR_HOT_RI ? v3{ u2f(p[12 % HOT_STRIDE]), u2f(p[13 % HOT_STRIDE]), u2f(p[14 % HOT_STRIDE]) } : v3{ 0.0f, 0.0f, 0.0f };      // events do not read it (begin_segment sets it)
+        h.ri = v3{ 0.0f, 0.0f, 0.0f };      // events do not read it (begin_segment sets it)
         h.t = u2f(p[7]); h.far = u2f(p[8]); h.tau = u2f(p[9]);
         h.Tr = u2f(p[10]);
         const uint32_t f = p[11];
@@ -252,7 +198,7 @@ struct HotStoreT {                     // [slot][field]: a path's parked dwords 
         } else
         h.ipos = v3{ first ? cam_ipos[0] : h.ipos.x, first ? cam_ipos[1] : h.ipos.y, first ? cam_ipos[2] : h.ipos.z };
         h.Tr = first ? 1.0f : h.Tr;
-        if (!VR_HOT_RI) h.ri = rcp3_exact(h.idir);             // as begin_segment computed it
+        h.ri = rcp3_exact(h.idir);             // as begin_segment computed it
     }
 };
 // Cold path state of one wavefront in global memory (vr_trace.h ColdField): a 64-byte slot per path -- half a cache line: the 16
@@ -261,26 +207,24 @@ struct HotStoreT {                     // [slot][field]: a path's parked dwords 
 // big array (159 -> 80 MB for all resident wavefronts) and dirties one of its two sectors.  Measured against one 128-byte line per
 // path with everything in it: c4 +3.3 %, c2 +1.1 %, same bytes moved (profiles/r2y_ab_cold_64_byte_slots.txt).  Earlier experiments:
 // group-major [group][slot][4] (same speed, more traffic), non-temporal accesses (-21 %), everything in LDS (-28 ... -42 %: the
-// pool slots it costs), profiles/r2j_layout_experiments.txt, r2m_cold_state_in_lds_experiments.txt.
+// pool slots it costs), profiles/r2j_layout_experiments.txt, r2m_cold_state_in_lds_experiments.txt; everything in vector registers (the dense-grid kernel, c4 -3 %:
+// the fourth wavefront per SIMD it costs is worth more), profiles/r3a_cold_state_in_registers.txt.
 constexpr uint32_t kStatsWaveBase = 32u;                 // statistics buffer: 32 counters, then (begin, queue empty, end) per wavefront of the launch
 constexpr int32_t kMaxWorkgroups = 2048;                // the cold-state workspace is sized for this many resident 4-wavefront units = 8192 wavefronts (launch_pathtrace clamps the grid to it)
-// SWAP (the kernels with VR_WORLD_SLOT, vr_trace.h world_slot): throughput and direction trade places in the slot and sh_pdf moves next to the direction -- sector 0 =
+// SWAP (vr_trace.h world_slot kernels): throughput and direction trade places in the slot and sh_pdf moves next to the direction -- sector 0 =
 // [ unused | dir, sh_pdf ], sector 1 = [ L, n_paths | thr, f_p ] -- because those kernels' collision event reads nothing and writes ITS segment's direction and sh_pdf (the
 // collision point stays with the path, the light sample's phase value is re-evaluated by the scatter event), and their scatter event writes L, n_paths, thr, f_p:
 // every event dirties exactly ONE 32-byte sector, in whole 16-byte groups (do_nee / do_postnee, vr_trace.h)
-#ifndef VR_COLD_NT_STORES
-#define VR_COLD_NT_STORES 0
-#endif
 template <bool SWAP = false>
 struct ColdGlobalT {
-    // SWAP (the kernels with VR_WORLD_SLOT): [ -, - ][ dir, sh_pdf ][ L, n_paths ][ thr, f_p ] -- the collision event writes the second 16 bytes, the scatter event the
+    // SWAP (the kernels with world_slot): [ -, - ][ dir, sh_pdf ][ L, n_paths ][ thr, f_p ] -- the collision event writes the second 16 bytes, the scatter event the
     // upper sector; pos and f_pl are not kept (vr_trace.h do_nee)
     static __device__ __forceinline__ constexpr int32_t phys(int32_t f) {
         return !SWAP ? f : ((f >= C_THR && f < C_THR + 3) ? f + (C_DIR - C_THR) : ((f >= C_DIR && f < C_DIR + 3) ? f - (C_DIR - C_THR) : (f == C_SHPDF ? C_FPL : (f == C_FPL ? C_SHPDF : f))));
     }
     float* base;                       // this slot's 16 floats in the wavefront's slice of the main array
     float* side;                       // this slot's 4 floats in the wavefront's slice of the side array
-    float* col;                        // C_COL: the three dwords of the path's parked hot state (LDS) that hold 1/dir -- dead between a real collision and
+    float* col;                        // C_COL: the three dwords of the path's parked hot state (LDS) that hold dir -- dead between a real collision and
                                        // the event that follows it, which is when the transfer-function kernels keep the collision's colour there
     __device__ __forceinline__ float ld(int32_t f) const {     // f is a compile-time constant at every call: the selection folds
         return f >= C_COL ? col[f - C_COL]
@@ -289,12 +233,7 @@ struct ColdGlobalT {
     }
     __device__ __forceinline__ void st(int32_t f, float v) {
         if (f >= C_COL) col[f - C_COL] = v;
-#if VR_COLD_NT_STORES
-        // build-time experiment (round 6): the cold slot's stores as non-temporal ones -- with VR_WORLD_SLOT nobody reads a sector back before it has left the L2 anyway
-        else if (f < C_SIDE) __builtin_nontemporal_store(v, static_cast<float*>(__builtin_assume_aligned(base, C_STRIDE * 4)) + phys(f));
-#else
-        else if (f < C_SIDE) static_cast<float*>(__builtin_assume_aligned(base, C_STRIDE * 4))[phys(f)] = v;
-#endif
+        else if (f < C_SIDE) static_cast<float*>(__builtin_assume_aligned(base, C_STRIDE * 4))[phys(f)] = v;      // (not non-temporal: profiles/r6h_non_temporal_stores.txt)
         else static_cast<float*>(__builtin_assume_aligned(side, C_SIDE_STRIDE * 4))[f - C_SIDE] = v;
     }
 };
@@ -366,72 +305,6 @@ __device__ __forceinline__ uint32_t item_fetch(const ShleBanks& B, int32_t lane,
     return k == 0 ? r0 : (k == 1 ? r1 : r2);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// The whole cold state of a wavefront's paths in vector registers (cold_in_regs kernels): field f of slot s lives in lane s & 63 of
-// register v[s >> 6][f] -- the 16 floats of a cold slot (ColdField, vr_trace.h) followed by the radiance of the pending light
-// sample and the path's slot in the sample buffer.  An event batch (lane i works on slot bs_i) pulls the fields its event reads
-// into a per-lane working copy (ColdLocal: the `Cold` the lane code of vr_trace.h is written against) with ds_bpermute -- one
-// per bank, the lane's own bank selected afterwards -- and the home lanes pull the fields the event wrote back the same way,
-// told by the LDS row of shle_park which batch lane holds "their" slot of each bank.  All of it runs with all 64 lanes active.
-constexpr int32_t kBankFields = 20;
-static_assert(C_SIDE == 16 && C_SHLE == 16 && C_ITEM == 19 && C_COL == kBankFields, "ColdLocal maps field f to v[f]");
-struct ColdBanks { float v[3][kBankFields]; };
-struct ColdLocal {
-    float v[kBankFields];
-    float* col;                        // C_COL (transfer-function kernels): the parked path's LDS slot, as in ColdGlobal
-    __device__ __forceinline__ float ld(int32_t f) const { return f >= C_COL ? col[f - C_COL] : v[f]; }      // f is a compile-time constant at every call
-    __device__ __forceinline__ void st(int32_t f, float x) { if (f >= C_COL) col[f - C_COL] = x; else v[f] = x; }
-};
-constexpr uint32_t cold_bits(int32_t first, int32_t n) { return ((1u << n) - 1u) << first; }
-// what each event reads and writes (do_nee / do_postnee / do_escape, vr_trace.h)
-constexpr uint32_t kColdNeeR = cold_bits(C_POS, 3) | cold_bits(C_THR, 3) | cold_bits(C_DIR, 3);
-constexpr uint32_t kColdNeeW = cold_bits(C_POS, 8) | cold_bits(C_SHLE, 3);                                                // pos, sh_pdf, thr, f_p of the light sample, its radiance
-constexpr uint32_t kColdNeeWFirst = cold_bits(C_L, 8) | cold_bits(C_ITEM, 1);                                             // a path's first collision: L, n_paths, dir, f_p, sample slot
-constexpr uint32_t kColdPostR = cold_bits(C_POS, 15) | cold_bits(C_SHLE, 4);                                              // everything but C_FP
-constexpr uint32_t kColdPostW = cold_bits(C_THR, 3) | cold_bits(C_L, 8);                                                  // thr (roulette), L, n_paths, dir, f_p
-constexpr uint32_t kColdEscR = cold_bits(C_THR, 3) | cold_bits(C_L, 8) | cold_bits(C_ITEM, 1);
-__device__ __forceinline__ void cold_clear(ColdLocal& c) {
-#pragma unroll
-    for (int f = 0; f < kBankFields; ++f) c.v[f] = 0.0f;
-    c.col = nullptr;
-}
-template <uint32_t MASK>
-__device__ __forceinline__ void cold_fetch(ColdLocal& c, const ColdBanks& B, int32_t lane, int32_t bs) {
-    const uint32_t home = bank_home(lane, bs);
-    const int32_t k = bs >> 6;
-#pragma unroll
-    for (int f = 0; f < kBankFields; ++f)
-        if ((MASK >> f) & 1u) {
-            const float r0 = lane_pull(home, B.v[0][f]), r1 = lane_pull(home, B.v[1][f]), r2 = lane_pull(home, B.v[2][f]);
-            c.v[f] = k == 0 ? r0 : (k == 1 ? r1 : r2);
-        }
-}
-// the row through which the home lanes learn who works on their slots: byte k of word d = 1 + the batch lane that holds slot 64 k + d
-// (bit 7: that lane's `flag`), 0 = nobody.  The fences keep a lane's read from being satisfied from its own earlier store.
-__device__ __forceinline__ uint32_t cold_stage(uint32_t* stage, int32_t lane, int32_t bs, bool flag) {
-    stage[lane] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (bs >= 0) reinterpret_cast<uint8_t*>(stage)[((bs & 63) << 2) + (bs >> 6)] = (uint8_t)((lane + 1) | (flag ? 0x80 : 0));
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    return stage[lane];
-}
-// FLAGGED: only from batch lanes that raised their flag
-template <uint32_t MASK, bool FLAGGED>
-__device__ __forceinline__ void cold_store(ColdBanks& B, uint32_t w, int32_t lane, const ColdLocal& c) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint32_t byte = (w >> (8 * k)) & 0xFFu, src = byte & 0x7Fu;
-        const uint32_t from = src ? src - 1u : (uint32_t)lane;
-        const bool take = FLAGGED ? byte > 0x80u : src != 0u;
-#pragma unroll
-        for (int f = 0; f < kBankFields; ++f)
-            if ((MASK >> f) & 1u) {
-                const float x = lane_pull(from, c.v[f]);
-                B.v[k][f] = take ? x : B.v[k][f];
-            }
-    }
-}
-
 // All kernel arguments travel as ONE struct so that the event code can address any of them through the kernarg pointer.
 // The scene parameters alone are ~1 KiB of uniforms.  The hot pair (march / collide) reads its few fields from the by-value
 // argument, which the compiler keeps in SGPRs; the event code (new sample, NEE, scatter, escape) reads everything else --
@@ -455,25 +328,13 @@ __device__ __forceinline__ const KernelArgs& event_args() {
 }
 
 template <class K, bool STATS>
-__global__ void __launch_bounds__(64 * kWgWaves, waves_per_simd<K>())
+__global__ void __launch_bounds__(64 * kWgWaves, VR_WAVES_PER_SIMD)
 pathtrace_kernel(const KernelArgs A) {
-#ifndef VR_PIN_TAP_POINTERS
-#define VR_PIN_TAP_POINTERS 0
-#endif
-#if VR_PIN_TAP_POINTERS
-    // experiment (round 5): the density grid's tap pointer as an opaque scalar value -- the register allocator treats a kernel-argument load as free to repeat and
-    // re-loaded it in the collision code of every pass (s_load + wait in front of the tap)
-    SceneParams Ppin = A.P;
-    asm volatile("" : "+s"(Ppin.density.atlas), "+s"(Ppin.density.dense));
-    const SceneParams& P = Ppin;
-#else
     const SceneParams& P = A.P;           // hot pair only; events use event_args()
-#endif
     const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     // path slots of this kernel's wavefronts (shadows the global maximum below); the instrumented instances give three of them up for their counters (lds_stat)
     constexpr int32_t NS = pool_slots<K>() - (STATS ? 3 : 0);
 
-    static_assert(!cold_in_regs<K>() || kWgWaves == 4, "the cold-state-in-registers experiment runs 3 workgroups of 4 wavefronts per CU");
     __shared__ uint8_t lds_q[kWgWaves * Q_COUNT * NS];
     uint8_t* const q = lds_q + wave * (Q_COUNT * NS);
     // per-wavefront slices of the workspace: the cold fields of its NSLOT paths
@@ -484,27 +345,18 @@ pathtrace_kernel(const KernelArgs A) {
 #define VR_COLD(SLOT) ColdT{ cold_base + (SLOT) * C_STRIDE, side_base + (SLOT) * C_SIDE_STRIDE, reinterpret_cast<float*>(hs.base + (SLOT) * HS + HOT_COL) }
     // where the radiance of a parked path's pending light sample waits: vector registers (ShleBanks), or -- in the transfer-function
     // variants, which have no registers to spare (126 of 128) -- the side array
-    constexpr bool kColdRegs = cold_in_regs<K>();            // the whole cold state in registers (ColdBanks); else:
-    constexpr bool kShleInRegs = !K::tf && !kColdRegs;
+    constexpr bool kShleInRegs = !K::tf;
     // the sample-buffer slot joins it there in the dense-grid kernel, where nearly every path scatters (c4 +1.3 %, memory-side traffic
     // 1.59x -> 1.52x); on smoke.brick two thirds of the escaping paths never scattered and the three extra ds_bpermute of every
     // escape batch cost more than the side-array accesses they save (c2 -0.7 %): profiles/r2z_*
     constexpr bool kItemInRegs = kShleInRegs && K::dense == 1;
     static_assert(!kItemInRegs || K::emission == 0, "with an emission grid do_new writes the sample-buffer slot to the side array (no stash to park it from)");
     static_assert(NS <= 192, "ShleBanks holds 3 x 64 slots");
-    static_assert(!kColdRegs || (K::emission == 0 && !K::tf), "ColdBanks: no marching-path access to the cold state (EmissionCache), C_COL not wired");
-    __shared__ uint32_t lds_stage[kShleInRegs || kColdRegs ? kWgWaves * 64 : 4];
-    uint32_t* const stage = lds_stage + (kShleInRegs || kColdRegs ? wave * 64 : 0);
+    __shared__ uint32_t lds_stage[kShleInRegs ? kWgWaves * 64 : 4];
+    uint32_t* const stage = lds_stage + (kShleInRegs ? wave * 64 : 0);
     ShleBanks banks;
     banks.b[0] = banks.b[1] = banks.b[2] = v3{ 0, 0, 0 };
     banks.item[0] = banks.item[1] = banks.item[2] = 0u;
-    ColdBanks cb;
-    if (kColdRegs) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int f = 0; f < kBankFields; ++f) cb.v[k][f] = 0.0f;
-    }
     constexpr int32_t HS = hot_stride<K>();
     constexpr bool kLazyEm = lazy_emission<K>();
     static_assert(VR_BATCH_REGS || !kLazyEm, "the VR_BATCH_REGS=0 swap path moves a marching path's radiance through its cold line: a `first` path of a lazy-emission kernel has none");
@@ -523,27 +375,9 @@ pathtrace_kernel(const KernelArgs A) {
     __shared__ float lds_lut[K::tf ? 4 * kLutLdsEntries : 4];
     const bool lut_in_lds = K::tf && P.u.tf_size <= (uint32_t)kLutLdsEntries;
     const bool emission_on = K::emission == 2 ? P.u.has_emission != 0 : K::emission == 1;
-    // the tail of the majorant table: cells [maj_first, maj_end) = the coarsest levels that fit (level offsets: vr_scene.h); maj_first = maj_end: none
-    constexpr int32_t kMajCells = maj_lds_cells<K>();
-    typedef typename std::conditional<K::tf, float, uint16_t>::type MajT;
-    __shared__ MajT lds_maj[kMajCells > 0 ? kMajCells : 1];
-    int32_t maj_first = 0x7FFFFFFF;
-    if (kMajCells > 0) {
-        const uint32_t k = (uint32_t)(P.density.mshift[0] + P.density.mshift[1] + P.density.mshift[2]);
-        const int32_t maj_end = (int32_t)majorant_table_cells(k);         // the "outside" cell included
-        maj_first = maj_end;
-#pragma unroll
-        for (int mip = 3; mip >= 0; --mip) {
-            const int32_t off = (int32_t)majorant_level_offset(k, (uint32_t)mip);
-            if (maj_end - off <= kMajCells) maj_first = off;
-        }
-        maj_first = __builtin_amdgcn_readfirstlane(maj_first);
-        for (int32_t i = (int32_t)threadIdx.x; i < maj_end - maj_first; i += 64 * kWgWaves)
-            lds_maj[i] = K::tf ? (MajT)P.density.majorant[maj_first + i] : (MajT)P.density.majorant16[maj_first + i];
-    }
     if (K::tf && lut_in_lds)
         for (uint32_t i = threadIdx.x; i < 4u * P.u.tf_size; i += 64u * (uint32_t)kWgWaves) lds_lut[i] = P.tf_lut[i];
-    if (K::tf || kMajCells > 0) __syncthreads();      // the only workgroup barrier of the kernel: before the persistent loop
+    if (K::tf) __syncthreads();      // the only workgroup barrier of the kernel: before the persistent loop
 
     // scheduler thresholds, one byte each in two scalars: batch sizes that trigger NEW / NEE / POSTNEE / ESCAPE, the low-water
     // mark of live paths ("hungry"), the slots in use (diagnostic cap)
@@ -558,9 +392,6 @@ pathtrace_kernel(const KernelArgs A) {
 #define VR_POOL ((int32_t)((thr_b >> 8) & 255u))
 #define VR_THR_COLLIDE ((int32_t)(thr_b >> 16))
     int32_t cnt_ready = 0, cnt_nee = 0, cnt_post = 0, cnt_esc = 0, cnt_free = pool;     // stack heights (wave-uniform)
-#if VR_READY_FIFO
-    int32_t rdy_head = 0;                                                               // READY ring: position of its oldest entry (wave-uniform)
-#endif
     for (int32_t i = lane; i < pool; i += 64) q[Q_FREE * NS + i] = (uint8_t)i;
     __builtin_amdgcn_wave_barrier();
 
@@ -615,21 +446,8 @@ pathtrace_kernel(const KernelArgs A) {
         if (m_) { if (COND) q[(QI) * NS + (CNT) + (int32_t)lane_rank(m_)] = (uint8_t)(SLOTV); (CNT) += popc(m_); } \
     } while (0)
 
-// READY as a queue instead of a stack (build-time experiment, round 4, -DVR_READY_FIFO=1): a ring of NS bytes, oldest entry at rdy_head.  The hypothesis was
-// that paths parked early starve at the bottom of the stack until the end of the launch and ARE its 4-5 ms fixed cost.  They are not: the per-wavefront
-// timeline (tests/tools_wave_timeline.py, profiles/r4f_*) shows EVERY wavefront taking ~1.6 ms (c2) to finish its pool once the work queue is empty -- the
-// latency of the deepest of its 175 paths, ~40 bounces x ~12 scheduler passes x ~3 us, stack or queue -- and the queue measures -0.5 % on full frames.
-#ifndef VR_READY_FIFO
-#define VR_READY_FIFO 0
-#endif
-#if VR_READY_FIFO
-#define VR_PUSH_READY(COND, SLOTV) do { \
-        const uint64_t m_ = wave_ballot(COND); \
-        if (m_) { if (COND) { int32_t p_ = rdy_head + cnt_ready + (int32_t)lane_rank(m_); p_ = p_ >= NS ? p_ - NS : p_; q[Q_READY * NS + p_] = (uint8_t)(SLOTV); } cnt_ready += popc(m_); } \
-    } while (0)
-#else
+// (READY is a stack: as a queue it measures -0.5 %, and the end of a launch is the latency of the pool's deepest path either way -- profiles/r4f_fixed_cost_of_a_launch.txt)
 #define VR_PUSH_READY(COND, SLOTV) VR_PUSH(Q_READY, cnt_ready, COND, SLOTV)
-#endif
 // route the batch paths to the stack of their new state; an impossible state is reported and the slot recycled
 #define VR_ROUTE_ST(BS, STV) do { \
         /* one integer per lane (its new state, or -1 without a batch path): every ballot below is then a single v_cmp */ \
@@ -682,12 +500,7 @@ pathtrace_kernel(const KernelArgs A) {
                 if (slot < 0) {
                     const int32_t r = (int32_t)lane_rank(idle);
                     if (r < take) {
-#if VR_READY_FIFO
-                        int32_t p_ = rdy_head + r; p_ = p_ >= NS ? p_ - NS : p_;
-                        slot = q[Q_READY * NS + p_]; hs.load_resume(l, slot, kWorld ? event_args().P.u.vol_density_inv_transform : nullptr);
-#else
                         slot = q[Q_READY * NS + cnt_ready - 1 - r]; hs.load_resume(l, slot, kWorld ? event_args().P.u.vol_density_inv_transform : nullptr);
-#endif
                         if (emission_on && !l.shadow) {              // EmissionCache (vr_trace.h Hot): the collisions of this segment add to L
                             if (kLazyEm && l.first) { l.ethr = v3{ 1.0f, 1.0f, 1.0f }; l.eL = hs.load_first_radiance(slot); }      // no cold line yet
                             else { const ColdT c = VR_COLD(slot); l.ethr = ld3(c, C_THR); l.eL = ld3(c, C_L); }
@@ -695,9 +508,6 @@ pathtrace_kernel(const KernelArgs A) {
                     }
                 }
                 cnt_ready -= take;
-#if VR_READY_FIFO
-                rdy_head += take; rdy_head = rdy_head >= NS ? rdy_head - NS : rdy_head;
-#endif
             }
         }
         VR_SECTION(0);                                                   // resume
@@ -718,96 +528,48 @@ pathtrace_kernel(const KernelArgs A) {
 #ifndef VR_HOT_PAIRS
 #define VR_HOT_PAIRS 4
 #endif
-        // ... per kernel instance (round 6): the transfer-function kernel with an emission grid -- 8 corner taps, the LUT and a stochastic emission tap in one collision
-        // block -- spills 34 scalar registers with four clean copies and the general one, 20 with VR_HOT_PAIRS_TF_EMISSION copies (profiles/r6_kernel_resources.txt)
-#ifndef VR_HOT_PAIRS_TF_EMISSION
-#define VR_HOT_PAIRS_TF_EMISSION 4
-#endif
-        constexpr int kHotPairs = (K::tf && K::emission == 1) ? (VR_HOT_PAIRS_TF_EMISSION < VR_HOT_PAIRS ? VR_HOT_PAIRS_TF_EMISSION : VR_HOT_PAIRS) : VR_HOT_PAIRS;
+        constexpr int kHotPairs = VR_HOT_PAIRS;
 
 #ifndef VR_HOT_PAIR_MIN
 #define VR_HOT_PAIR_MIN 44
 #endif
         // VR_DRAIN (round 6, build-time experiment): once the work queue is empty a wavefront's pool only shrinks, and the launch ends with the latency of the deepest
         // path (profiles/r4f_*).  1: a draining wavefront runs its further copies of the hot pair for any number of lanes and, when hungry, EVERY non-empty event batch
-        // per iteration instead of the largest only (nothing is left to fill the others up)
+        // per iteration instead of the largest only (nothing is left to fill the others up): profiles/r6b_drain_experiment.txt.  Not adopted; still a switch because
+        // taking it out changes the generated code of every instance (profiles/r8_retired_switches.txt)
 #ifndef VR_DRAIN
 #define VR_DRAIN 0
 #endif
-        // VR_BALLOT_VALID (round 5): `slot` does not change inside the hot pair, so "the lane holds a path" is ONE ballot per scheduler iteration and the pair's
-        // counts are ballots of a single compare ANDed with it on the scalar unit; a ballot of `slot >= 0 && state == X` costs a v_cndmask + v_cmp more each
-#ifndef VR_BALLOT_VALID
-#define VR_BALLOT_VALID 1
-#endif
+        // `slot` does not change inside the hot pair, so "the lane holds a path" is ONE ballot per scheduler iteration and the pair's counts are ballots of a single
+        // compare ANDed with it on the scalar unit; a ballot of `slot >= 0 && state == X` costs a v_cndmask + v_cmp more each (round 5)
         const uint64_t holds_path = wave_ballot(slot >= 0);
         // Clean segments (vr_trace.h seg_clean, round 5): while every path the wavefront holds is on one -- always, outside degenerate scenes -- the pair runs in
         // its CLEAN form (integer inside test, v_min3 in the DDA step, no NaN guard on the density tap); otherwise ONE pass in the general form.  A lane's path, and
         // with it the flag in the sign of its `far`, only changes in the resume block above: one ballot per scheduler iteration.
         // (VR_CLEAN_FORMS=0, the everything-at-run-time variant: the general form only -- a second form costs that kernel registers it does not have)
 #ifndef VR_CLEAN_FORMS
-#define VR_CLEAN_FORMS VR_CLEAN_FLAG
+#define VR_CLEAN_FORMS 1
 #endif
-        // (VR_CLEAN_FORMS_TF_EMISSION, round 6: whether the transfer-function kernel with an emission grid carries the clean form too)
-#ifndef VR_CLEAN_FORMS_TF_EMISSION
-#define VR_CLEAN_FORMS_TF_EMISSION 1
-#endif
-        constexpr bool kCleanForms = VR_CLEAN_FORMS && ((K::tf && K::emission == 1) ? VR_CLEAN_FORMS_TF_EMISSION != 0 : true);
+        constexpr bool kCleanForms = VR_CLEAN_FORMS != 0;
         const bool all_clean = kCleanForms && (holds_path & wave_ballot((int32_t)f2u(l.far) < 0)) == 0ull;
-        // VR_EARLY_MARCH (round 6, build-time experiment, profiles/r6l_*): the NEXT copy's march loads are issued between this copy's tap loads and the code that consumes
-        // the taps.  After collide_prep a path's next DDA steps are known whatever the tap says -- a null collision leaves it where it stands, one level finer
-        // (collide_finish: mip = max(0, mip - 2)); a real one takes it out of the hot pair, and its steps are dropped -- so march_prep runs on that state and both
-        // majorants travel while the tap does: one exposed round trip per pass instead of two.  The same values by the same operations (all tests green); only where
-        // the loads are issued changes.  1: as described; 2: without the pin that keeps the tap's decode below the majorant loads.  Measured: -5 % c2, -5 ... -7 % c4
-        // either way -- the pair does not run at the speed of its round trips.  Off.
-#ifndef VR_EARLY_MARCH
-#define VR_EARLY_MARCH 0
-#endif
-        constexpr bool kEarlyMarch = VR_EARLY_MARCH != 0 && VR_MARCH_SPECULATIVE && VR_MARCH_STEPS == 2 && K::global == 0 && !K::tf && K::emission == 0 && !K::maj_reuse && maj_lds_cells<K>() == 0;
-        MarchIO pre;                       // kEarlyMarch: the next copy's steps and (in flight) majorants
-        march_idle(pre); pre.maj1 = pre.maj2 = 0u;
-        auto hot_pair = [&](auto clean_tag, const int hot_rep_, const int n_copies_) __attribute__((always_inline)) -> bool {
+        // (the next copy's march loads are NOT issued under this copy's taps: -5 ... -7 %, the pair does not run at the speed of its round trips -- profiles/r6l_hot_pair_software_pipelined.txt)
+        auto hot_pair = [&](auto clean_tag, const int hot_rep_) __attribute__((always_inline)) -> bool {
             constexpr bool CLEAN = decltype(clean_tag)::value;
-#if VR_BALLOT_VALID
             if (hot_rep_ > 0 && popc_s(holds_path & wave_ballot((uint32_t)(l.state - ST_MARCH) < 2u)) < (VR_DRAIN && exhausted ? 1 : VR_HOT_PAIR_MIN)) return false;
-#else
-            if (hot_rep_ > 0 && popc(wave_ballot(slot >= 0 && (uint32_t)(l.state - ST_MARCH) < 2u)) < VR_HOT_PAIR_MIN) return false;
-#endif
             if (STATS_T) t_blk = (uint32_t)__builtin_readcyclecounter();
             const bool is_m = slot >= 0 && l.state == ST_MARCH;
-#if VR_MARCH_SPECULATIVE
             MarchIO mio;
-            if (kEarlyMarch && hot_rep_ > 0) mio = pre;      // prepared and loaded by the copy before this one (below), for every lane that is marching now
-            else {
             march_idle(mio);
             if (is_m) march_prep<K::dense, K::majb, CLEAN>(l, P, mio);
-            if constexpr (kMajCells > 0) march_load_lds<K::tf, MajT, K::a32>(P, mio, lds_maj, maj_first);
-            else if constexpr (K::maj_reuse) march_load_reuse<K::tf, K::a32>(P, mio, l);
+            if constexpr (K::maj_reuse) march_load_reuse<K::tf, K::a32>(P, mio, l);
             else march_load<K::tf, K::a32>(P, mio);
-#if VR_MARCH_LOADS_PINNED
             // Both majorants must have been REQUESTED before the first is used.  Left alone, the compiler sinks each load into the
             // conditional block of march_finish that consumes it (load, wait, test, load, wait: two dependent round trips); an
             // empty asm that takes both values as operands keeps the two loads above it, back to back.
             asm volatile("" : "+v"(mio.maj1), "+v"(mio.maj2));
-#endif
-            }
             if (is_m) march_finish<K::tf, K::maj_reuse, CLEAN>(l, P, mio);
-#else
-            for (int32_t k = 0; k < 2; ++k)            // diagnostic: two plain steps, one majorant load each, only where a step runs
-                if (slot >= 0 && l.state == ST_MARCH) do_march<K::tf, K::dense, K::majb>(l, P);
-#endif
             if (STATS) { const int32_t nm = popc(wave_ballot(is_m)); if (nm) { stat_add(2 * ST_MARCH, 1u); stat_add(2 * ST_MARCH + 1, (uint32_t)nm); } }
             if (STATS_T) { const uint32_t t_now = (uint32_t)__builtin_readcyclecounter(); stat_add(18 + ST_MARCH, t_now - t_blk); t_blk = t_now; }
-#if VR_DIAG_PAD_VALU > 0
-            {   // diagnostic: VR_DIAG_PAD_VALU extra dependent-free vector instructions per pass -> how issue-bound is the pass?
-                float pad_ = l.t;
-#pragma unroll
-                for (int k_ = 0; k_ < VR_DIAG_PAD_VALU; ++k_) asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(pad_));
-                asm volatile("" :: "v"(pad_));
-            }
-#endif
-#if VR_DIAG_PAD_SLEEP > 0
-            __builtin_amdgcn_s_sleep(VR_DIAG_PAD_SLEEP);       // diagnostic: 64 * n idle cycles per pass -> how latency-bound is the wavefront?
-#endif
             // The collision code runs when enough lanes stand at a tentative collision -- or when no lane is left marching.  In a
             // dense medium two DDA steps take most marching lanes to one (smoke.brick: 43 of 59); in a sparse grid (c5: 7.6 steps per
             // collision) a pass would otherwise run the collision code, the most expensive block of the loop, for a dozen lanes.
@@ -815,51 +577,16 @@ pathtrace_kernel(const KernelArgs A) {
             // A wavefront that is running dry (end of the launch: a handful of deep paths) must not make them wait for each other:
             // the threshold is at most half the lanes that hold a marching or colliding path.
             const bool is_c = slot >= 0 && l.state == ST_COLLIDE;
-#if VR_BALLOT_VALID
             const int32_t n_c = popc(holds_path & wave_ballot(l.state == ST_COLLIDE));
             const int32_t n_m = popc(holds_path & wave_ballot(l.state == ST_MARCH));
-#else
-            const int32_t n_c = popc(wave_ballot(is_c));
-            const int32_t n_m = popc(wave_ballot(slot >= 0 && l.state == ST_MARCH));
-#endif
             const bool run_c = n_c > 0 && n_c >= min(VR_THR_COLLIDE, (n_c + n_m + 1) >> 1);
-            if (kEarlyMarch) {
-                // the pipelined form of the block below: tap loads, then the next copy's march loads, then the code that waits for the taps
-                CollideIO<K> cio;
-                collide_idle<K>(cio);
-                if (run_c) {
-                    if (is_c) collide_prep<K, CLEAN>(l, P, P, cio);
-                    collide_load<K>(P, P, cio);
-                }
-                const bool early = hot_rep_ + 1 < n_copies_;
-                if (early) {
-                    const bool spec = run_c && is_c;                                   // the tentative collision this pass resolves: assume it is a null one
-                    Hot ls = l;
-                    ls.mipq = spec ? (l.mipq > 8 ? l.mipq - 8 : 0) : l.mipq;             // collide_finish: mip = max(0, mip - 2)
-                    march_idle(pre);
-                    if (slot >= 0 && (l.state == ST_MARCH || spec)) march_prep<K::dense, K::majb, CLEAN>(ls, P, pre);
-                    march_load<K::tf, K::a32>(P, pre);
-                    // the tap is used from HERE on as far as the compiler is concerned: left alone it hoists the tap's decode (a conversion and a select) up to the
-                    // tap's load -- and waits for it there, before the majorants above have been requested
-                    if (VR_EARLY_MARCH == 1) asm volatile("" : "+v"(cio.d.raw), "+v"(cio.d.rmin), "+v"(cio.d.rdiff));
-                }
-                if (run_c) {
-                    if (is_c) { ColdT c = VR_COLD(slot); collide_finish<K, ColdT, true>(l, c, P, P, cio, P.tf_lut); }
-                    if (STATS) { stat_add(2 * ST_COLLIDE, 1u); stat_add(2 * ST_COLLIDE + 1, (uint32_t)n_c); }
-                }
-                // (the majorants are used HERE as far as the compiler is concerned: it may neither sink the loads into the next copy's march_finish nor drop them)
-                if (early) asm volatile("" : "+v"(pre.maj1), "+v"(pre.maj2));
-            } else
             if (run_c) {
                 CollideIO<K> cio;
                 collide_idle<K>(cio);
-                const SceneParams& PE = VR_EMISSION_BY_POINTER && K::emission != 0 ? event_args().P : P;      // see collide_prep
-                // (VR_COLLIDE_BY_POINTER, round 6: the run-time variant with a transfer function evaluates its collisions on uniforms read through the kernarg pointer too --
+                const SceneParams& PE = K::emission != 0 ? event_args().P : P;      // see collide_prep
+                // (round 6: the run-time variant with a transfer function evaluates its collisions on uniforms read through the kernarg pointer too --
                 // scalar loads in the collision code instead of ~20 more scalar registers held through the whole scheduler loop)
-#ifndef VR_COLLIDE_BY_POINTER
-#define VR_COLLIDE_BY_POINTER 1
-#endif
-                const SceneParams& PF = (VR_COLLIDE_BY_POINTER && K::tf && (K::global == 2 || K::emission == 1)) ? event_args().P : P;
+                const SceneParams& PF = (K::tf && (K::global == 2 || K::emission == 1)) ? event_args().P : P;
                 if (is_c) collide_prep<K, CLEAN>(l, PF, PE, cio);
                 collide_load<K>(PF, PE, cio);
                 if (is_c) {
@@ -878,11 +605,11 @@ pathtrace_kernel(const KernelArgs A) {
         if constexpr (kCleanForms) {
             if (all_clean) {
 #pragma unroll
-                for (int hot_rep_ = 0; hot_rep_ < kHotPairs; ++hot_rep_) if (!hot_pair(std::true_type{}, hot_rep_, kHotPairs)) break;
-            } else hot_pair(std::false_type{}, 0, 1);
+                for (int hot_rep_ = 0; hot_rep_ < kHotPairs; ++hot_rep_) if (!hot_pair(std::true_type{}, hot_rep_)) break;
+            } else hot_pair(std::false_type{}, 0);
         } else {
 #pragma unroll
-            for (int hot_rep_ = 0; hot_rep_ < kHotPairs; ++hot_rep_) if (!hot_pair(std::false_type{}, hot_rep_, kHotPairs)) break;
+            for (int hot_rep_ = 0; hot_rep_ < kHotPairs; ++hot_rep_) if (!hot_pair(std::false_type{}, hot_rep_)) break;
         }
         VR_SECTION(1);                                                   // hot pair (also in st_cyc[MARCH] + st_cyc[COLLIDE])
         // (3) park paths that reached an event
@@ -944,16 +671,6 @@ pathtrace_kernel(const KernelArgs A) {
                 int32_t bs = -1;
                 if (lane < n) { bs = q[Q_ESC * NS + cnt_esc - 1 - lane]; hs.load(b, bs); if (kLazyEm && b.first) b.eL = hs.load_first_radiance(bs); }
                 if (kItemInRegs) b.item = item_fetch(banks, lane, bs);                      // all lanes
-                if constexpr (kColdRegs) {
-                    ColdLocal c;
-                    cold_clear(c);
-                    cold_fetch<kColdEscR>(c, cb, lane, bs);                                  // all lanes (a path that never scattered reads its slot's leftovers and discards them)
-                    if (lane < n) {
-                        const KernelArgs& E = event_args();
-                        WorkUnit w; w.out = E.sbuf;
-                        do_escape<ColdLocal, false>(b, c, E.P, w);
-                    }
-                } else
                 if (lane < n) {
                     // a path that never scattered carries what it needs in its stash (FirstStash): its loads go to slot 0's line, shared by the batch
                     const ColdT c = VR_COLD(b.first ? 0 : bs);
@@ -972,18 +689,6 @@ pathtrace_kernel(const KernelArgs A) {
                 if (lane < n) { bs = q[Q_POST * NS + cnt_post - 1 - lane]; hs.load(b, bs); }
                 if (kShleInRegs) b.shle = shle_fetch(banks, lane, bs);                     // all lanes: the values come from their home lanes
                 if (kItemInRegs) b.item = item_fetch(banks, lane, bs);
-                if constexpr (kColdRegs) {
-                    ColdLocal c;
-                    cold_clear(c);
-                    cold_fetch<kColdPostR>(c, cb, lane, bs);
-                    if (lane < n) {
-                        const KernelArgs& E = event_args();
-                        WorkUnit w; w.out = E.sbuf;
-                        do_postnee<K, ColdLocal, false, false>(b, c, E.P, w);
-                        hs.save(b, bs);
-                    }
-                    cold_store<kColdPostW, false>(cb, cold_stage(stage, lane, bs, false), lane, c);      // a path that has ended leaves leftovers in a free slot: harmless
-                } else
                 if (lane < n) {
                     ColdT c = VR_COLD(bs);
                     const KernelArgs& E = event_args();
@@ -1035,19 +740,6 @@ pathtrace_kernel(const KernelArgs A) {
                 bool was_first = false;
                 uint32_t first_item = 0u;
                 if (lane < n) { bs = q[Q_NEE * NS + cnt_nee - 1 - lane]; hs.load(b, bs); }
-                if constexpr (kColdRegs) {
-                    ColdLocal c;
-                    cold_clear(c);
-                    cold_fetch<kColdNeeR>(c, cb, lane, bs);
-                    if (lane < n) {
-                        was_first = b.first != 0;
-                        do_nee<K, ColdLocal, false, false>(b, c, c, event_args().P);        // a first collision writes every field (its reads are discarded)
-                        hs.save(b, bs);
-                    }
-                    const uint32_t w = cold_stage(stage, lane, bs, was_first);
-                    cold_store<kColdNeeW, false>(cb, w, lane, c);
-                    if (wave_ballot(was_first)) cold_store<kColdNeeWFirst, true>(cb, w, lane, c);
-                } else
                 if (lane < n) {
                     was_first = b.first != 0; first_item = f2u(b.Tr);      // a path's first collision: its sample-buffer slot is in the stash
                     if (kLazyEm && b.first) b.eL = hs.load_first_radiance(bs);

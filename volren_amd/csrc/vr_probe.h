@@ -121,7 +121,7 @@ template <bool TF, int DENSE, int MAJB, bool CLEAN>
 VR_HD float probe_majorant(const SceneParams& P, v3 ipos, int32_t mip) {
     if (!CLEAN) return majorant_at<TF, DENSE, MAJB>(P, ipos, mip);
     const int32_t idx = majorant_index<DENSE, MAJB, CLEAN>(P.density, ipos, mip);      // as march_prep / march_load / march_finish do on a clean segment
-    return majorant_of<TF>(P, idx, majorant_fetch<TF>(P.density, idx));
+    return majorant_value<TF>(P, majorant_fetch<TF>(P.density, idx));
 }
 
 // one item.  `P` by reference: the forms that need a changed view (byte atlas, float map, fetched average) work on a copy of the few fields they change

@@ -56,11 +56,9 @@ enum LaneState : int32_t {
 //   DENSE     0: density grid = bricks  1: dense fp16 voxels  2: run time
 //   MAJB      layout of the majorant table's levels 0-1 (vr_scene.h majorant_cell_index): 0 linear, 1 in 4x4x4-cell blocks of one cache line, 2 run time
 //             (GridView::maj_blocked, chosen per grid at commit(): round 5)
-#ifndef VR_MARCH_STEPS
-#define VR_MARCH_STEPS 2     /* DDA steps a march pass prepares and loads together (march_prep below) */
-#endif
 #ifndef VR_MAJ_REUSE
-#define VR_MAJ_REUSE 0       /* build-time experiment (round 5, profiles/r5f_*): 0 never (default: c5cloud +-0, c2 -0.6 %), 1 in the kernel for blocked majorant tables (variant 4), 2 in every kernel */
+#define VR_MAJ_REUSE 0       /* build-time experiment (round 5, profiles/r5f_*): 0 never (default: c5cloud +-0, c2 -0.6 %), 1 in the kernel for blocked majorant tables (variant 4), 2 in every kernel.
+                                Still here because taking it out changes the emission kernels' code (four more spilled vector registers in tolerance mode): profiles/r8_retired_switches.txt */
 #endif
 //   A32       the kernel's gathers into the grids' tables form their byte offsets in 32 bits (table_load: every table below 4 GiB, checked per launch) or -- false --
 //             64-bit addresses
@@ -72,21 +70,16 @@ struct TraceCfg {
     // that kernel, on brick grids, reads both grids from one paired atlas (vr_scene.h): component 1 = density, 2 = emission, 0 = a grid's own atlas
     static constexpr int pair_d = (VR_PAIRED_ATLAS && EMISSION == 1 && DENSE == 0) ? 1 : 0, pair_e = pair_d ? 2 : 0;
     // the kernel compiled for the large sparse grids (blocked majorant table: the grid whose gathers leave the caches) remembers the last majorant it used
-    static constexpr bool maj_reuse = VR_MARCH_STEPS == 2 && (VR_MAJ_REUSE == 2 || (VR_MAJ_REUSE == 1 && MAJB == 1));
+    static constexpr bool maj_reuse = (VR_MAJ_REUSE == 2 || (VR_MAJ_REUSE == 1 && MAJB == 1));
 };
 
-// VR_WORLD_SLOT (round 6, build-time experiment): a parked path keeps the WORLD origin and direction of its segment in its slot instead of the index-space ones
-// (which the resume recomputes, as begin_segment computed them), so that the collision event needs nothing from the path's cold line -- position and direction are in
-// the slot, and "throughput *= albedo" moves to the scatter event that always follows -- and reads none: one of a bounce's two cold line reads and the first dependent
-// round trip of every collision event gone, for two transforms per resume and one more sector written per bounce.  Kernels of the DDA trackers without a transfer
-// function only (a transfer function's collision colour waits in the slot's direction fields).
-#ifndef VR_WORLD_SLOT
-#define VR_WORLD_SLOT 1
-#endif
-#ifndef VR_WORLD_SLOT_EMISSION
-#define VR_WORLD_SLOT_EMISSION 0     /* the emission kernels (127 vector registers as they are) spill 6 of them with it: measured separately (profiles/r6g_*) */
-#endif
-template <class K> constexpr bool world_slot() { return VR_WORLD_SLOT != 0 && !K::tf && K::global == 0 && (K::emission == 0 || VR_WORLD_SLOT_EMISSION != 0); }
+// world_slot kernels (round 6, profiles/r6g_collision_events_without_cold_read.txt): a parked path keeps the WORLD origin and direction of its segment in its slot
+// instead of the index-space ones (which the resume recomputes, as begin_segment computed them), so that the collision event needs nothing from the path's cold line --
+// position and direction are in the slot, and "throughput *= albedo" moves to the scatter event that always follows -- and reads none: one of a bounce's two cold line
+// reads and the first dependent round trip of every collision event gone, for two transforms per resume and one more sector written per bounce.  Kernels of the DDA
+// trackers without a transfer function (its collision colour waits in the slot's direction fields) and without an emission grid (those kernels, at 127 vector
+// registers, spill 6 of them with it) only.
+template <class K> constexpr bool world_slot() { return !K::tf && K::global == 0 && K::emission == 0; }
 
 // the pool of work items of one wavefront: pixel p = item & 63 of the 8x8 tile at (px0, py0), sample
 // first_sample + (item >> 6) (1-based like the reference's current_sample)
@@ -108,7 +101,7 @@ VR_HD int32_t segment_end_state(int32_t shadow) { return ST_ESCAPE - shadow; }
 struct Hot {
     uint32_t seed;
     v3 ipos, idir, ri;       // index-space ray of the current segment
-    v3 wpos, wdir;           // the same segment's origin and direction in world space (begin_segment's arguments): what a parked path keeps under VR_WORLD_SLOT
+    v3 wpos, wdir;           // the same segment's origin and direction in world space (begin_segment's arguments): what a parked path keeps under world_slot
     float t, far, tau, majorant, Tr;
     int32_t mipq;            // 4 * mip: the DDA level moves in quarter steps (common.glsl:433,450), kept as an integer
     int32_t shadow;          // 0: sample_volumeDDA segment, 1: transmittanceDDA segment
@@ -135,7 +128,7 @@ struct Hot {
 // the box) never touches one, and the first scatter event writes the line without having to read it: for the bench scene
 // 0.7 line fetches and 0.7 partial line writes fewer per sample, from memory that sits beyond the L2.
 // On the GPU the stash is the parked path's LDS slot (HotStore, vr_pathtrace.h); the host harness keeps it in a FirstStash.
-// (Kernels with VR_WORLD_SLOT keep every path's world direction in its slot anyway -- Hot::wdir -- and their events read it from there, first path or not: for them the
+// (Kernels with world_slot keep every path's world direction in its slot anyway -- Hot::wdir -- and their events read it from there, first path or not: for them the
 // stash is the sample slot in Tr alone.)
 struct FirstStash { v3 dir; uint32_t item; };
 // Cold: path state that only the rare events (new sample, scatter, escape) read or write.  On the GPU it is parked
@@ -231,11 +224,6 @@ VR_HD TapAddr tap_addr(const GridView& g, int32_t x, int32_t y, int32_t z) {
     const bool nonneg = (x | y | z) >= 0;
     if (grid_is_dense<DENSE>(g)) {          // dense fp16 grid: one 2-byte load, no indirection
         a.in = nonneg && (uint32_t)x < (uint32_t)g.dim[0] && (uint32_t)y < (uint32_t)g.dim[1] && (uint32_t)z < (uint32_t)g.dim[2];
-#if defined(VR_WHATIF_WRAP)
-        // diagnostic build (tests/tools_whatif_wrap.py): the grid holds a field of period VR_WHATIF_WRAP voxels and the taps read its
-        // first period only -- same values, a working set that fits a cache level: what would voxel taps cost if they never missed?
-        x &= VR_WHATIF_WRAP - 1; y &= VR_WHATIF_WRAP - 1; z &= VR_WHATIF_WRAP - 1;
-#endif
         // 4x4x4 blocks (vr_scene.h): neighbouring rays and the +-2-voxel stochastic taps share 128-byte lines; block counts < 2^14 per axis
         a.cell = (mul24((uint32_t)z >> 2, (uint32_t)g.dblk[1]) + ((uint32_t)y >> 2)) * (uint32_t)g.dblk[0] + ((uint32_t)x >> 2);
         a.off = (((uint32_t)z & 3u) << 4) | (((uint32_t)y & 3u) << 2) | ((uint32_t)x & 3u);
@@ -248,11 +236,8 @@ VR_HD TapAddr tap_addr(const GridView& g, int32_t x, int32_t y, int32_t z) {
     if (!a.in) { a.cell = 0u; a.off = 0u; }       // the loads are unconditional: an outside tap reads cell 0 and is discarded
     return a;
 }
-#ifndef VR_TAP_LINE_INDEX
-#define VR_TAP_LINE_INDEX 1
-#endif
-// A32: the loads in the 32-bit form of table_load / line_load (default builds of the layouts; the build-time experiments keep the 64-bit form)
-#if VR_TAP_LINE_INDEX && VR_BRICK_HEADERS && !defined(VR_TAP_NT) && !defined(VR_DENSE_TAP_NT)
+// A32: the loads in the 32-bit form of table_load / line_load (the atlas with brick headers; the other layout keeps the 64-bit form)
+#if VR_BRICK_HEADERS
 #define VR_TAP_A32(A32) (A32)
 #else
 #define VR_TAP_A32(A32) false
@@ -276,41 +261,23 @@ VR_HD TapData tap_load(const GridView& g, TapAddr a) {
     if (PAIR != 0) {
         // paired atlas: ten lines of [rmin_d, rdiff_d, rmin_e, rdiff_e | 56 x (density, emission)] per brick
         const uint32_t line = pair_voxel_line(a.off);
-#if VR_TAP_LINE_INDEX
         const uint8_t* ln = g.atlas + ((size_t)(a.cell * (kPairBlockBytes / 128u) + line) << 7);      // see the brick atlas below
-#else
-        const uint8_t* ln = g.atlas + ((size_t)a.cell * kPairBlockBytes + (size_t)(line * 128u));
-#endif
         const float* rec = reinterpret_cast<const float*>(ln) + (PAIR == 2 ? 2 : 0);
-#if defined(VR_TAP_NT) && defined(__HIP_DEVICE_COMPILE__)
-        // build-time experiment (round 5): the paired atlas of a large grid streams through the L2 (450 MB touched on c5cloud); non-temporal taps would leave the L2
-        // to the majorant and environment tables
-        d.rmin = __builtin_nontemporal_load(rec); d.rdiff = __builtin_nontemporal_load(rec + 1);
-        d.raw = __builtin_nontemporal_load(ln + (kPairLineHeader + 2u * (a.off - line * kPairLineVoxels) + (PAIR == 2 ? 1u : 0u)));
-#else
+        // (the taps are not non-temporal loads: profiles/r5k_ab_non_temporal_taps.txt, r6k_memory_path_probes.txt)
         d.rmin = rec[0]; d.rdiff = rec[1];
         d.raw = ln[kPairLineHeader + 2u * (a.off - line * kPairLineVoxels) + (PAIR == 2 ? 1u : 0u)];
-#endif
         return d;
     }
     if (grid_is_dense<DENSE>(g)) {
         d.rmin = 0.0f; d.rdiff = 0.0f;
-#if defined(VR_DENSE_TAP_NT) && defined(__HIP_DEVICE_COMPILE__)
-        d.raw = __builtin_nontemporal_load(g.dense + ((size_t)a.cell * 64u + a.off));      // build-time experiment (round 6, profiles/r6k_*): the dense grid's taps streaming through the L2
-#else
         d.raw = g.dense[(size_t)a.cell * 64u + a.off];
-#endif
     } else {
 #if VR_BRICK_HEADERS
         // the voxel's line of the brick's block: [rmin, rdiff | 120 voxels] -- range and voxel come from one cache line
         const uint32_t line = brick_voxel_line(a.off);
-#if VR_TAP_LINE_INDEX
         // the line's index in the atlas as ONE 32-bit number (cell * 5 + line: fewer than 2^32 lines = 512 GiB, checked at upload), shifted into the 64-bit
         // address once -- instead of a 64-bit product, two 64-bit selects and two 64-bit additions (round 5; fewer instructions, no measurable gain: profiles/r5p_*)
         const uint8_t* ln = g.atlas + ((size_t)(a.cell * (kBrickBlockBytes / 128u) + line) << 7);
-#else
-        const uint8_t* ln = g.atlas + ((size_t)a.cell * kBrickBlockBytes + (size_t)(line * 128u));
-#endif
         const float* rec = reinterpret_cast<const float*>(ln);
         d.rmin = rec[0]; d.rdiff = rec[1];
         d.raw = ln[kBrickLineHeader + a.off - line * kBrickLineVoxels];
@@ -318,14 +285,6 @@ VR_HD TapData tap_load(const GridView& g, TapAddr a) {
         const float* rec = g.rng + 2u * (size_t)a.cell;          // compact (rmin, rdiff) pairs: twice as many bricks per cache line as BrickRec
         d.rmin = rec[0]; d.rdiff = rec[1];
         d.raw = g.atlas[(size_t)a.cell * 512u + a.off];
-#endif
-#if defined(VR_DIAG_EXTRA_RNG) && defined(__HIP_DEVICE_COMPILE__)
-        {   // diagnostic (profiles/r4c_*): one more gather of the old range table's kind per tap, from the record of another brick -- what does such a gather cost?
-            const uint32_t n_ = (uint32_t)g.nb[0] * (uint32_t)g.nb[1] * (uint32_t)g.nb[2];
-            uint32_t c_ = a.cell * 2654435761u; c_ = c_ % n_;
-            float x_ = g.rng[2u * (size_t)c_];
-            asm volatile("" :: "v"(x_));
-        }
 #endif
     }
     return d;
@@ -344,16 +303,9 @@ VR_HD float brick_value(const GridView& g, int32_t x, int32_t y, int32_t z) {
 // The padded layout (vr_scene.h) holds the outside value in every cell beyond the real extent of a level, so only the padded extent -- the
 // same for all levels -- is tested, on the floats (floor(x) in [0, n) <=> x in [0, n) for integer n; NaN fails), after
 // which truncation equals floor.
-// VR_MAJ_OUTSIDE_CELL (round 5, default): "outside" is the index of the table's last cell, which holds what the reference computes there (vr_scene.h
-// majorant_table_cells), instead of -1 with the loaded value replaced by 0 afterwards: the load needs no clamp and the value no compare + select.  Either way the
-// arithmetic on the value is the reference's: density_scale * 0 outside.  0: the -1 convention (kept for the A/B, profiles/r5o_*)
-#ifndef VR_MAJ_OUTSIDE_CELL
-#define VR_MAJ_OUTSIDE_CELL 1
-#endif
-#ifndef VR_MAJ_LEVEL_TEST
-#define VR_MAJ_LEVEL_TEST 0
-#endif
-// ---- "clean" segments (round 5, VR_CLEAN_FLAG) ------------------------------------------------------------------------------------------------------------
+// "Outside" is the index of the table's last cell, which holds what the reference computes there (vr_scene.h majorant_table_cells): the load needs no clamp and the
+// value no compare + select (round 5, profiles/r5o_ab_issue_items.txt).  The arithmetic on the value is the reference's: density_scale * 0 outside.
+// ---- "clean" segments (round 5, profiles/r5p_*) ------------------------------------------------------------------------------------------------------------
 // begin_segment marks a segment whose ray is finite and of moderate size -- |ipos| < 2^20, |idir| < 2^20 and |idir| * far < 2^20 per axis, |idir| >= 2^-20 on one
 // axis at least; all comparisons that fail for NaN --
 // in the sign of Hot::far (clean: far as computed, >= 0; not clean: -far; every reader takes |far|, seg_far).  On such a segment every point the trackers
@@ -366,12 +318,9 @@ VR_HD float brick_value(const GridView& g, int32_t x, int32_t y, int32_t z) {
 //     the tap lands on index -1 by itself: no NaN guard on the voxel index (argument at nan_guard).
 // The scheduler (vr_pathtrace.h) runs the hot pair in the CLEAN form while every marching path of the wavefront is clean and in the general form otherwise; the
 // host harness picks the form per path (lane_step), so both are checked against the oracle on the CPU.
-#ifndef VR_CLEAN_FLAG
-#define VR_CLEAN_FLAG 1
-#endif
 constexpr float kCleanBound = 1048576.0f;      // 2^20
-VR_HD float seg_far(const Hot& h) { return VR_CLEAN_FLAG ? abs_(h.far) : h.far; }
-VR_HD bool seg_clean(const Hot& h) { return VR_CLEAN_FLAG ? (int32_t)f2u(h.far) >= 0 : false; }
+VR_HD float seg_far(const Hot& h) { return abs_(h.far); }
+VR_HD bool seg_clean(const Hot& h) { return (int32_t)f2u(h.far) >= 0; }
 // floor(x) as an int for |x| < 2^31 (clean segments: < 2^21)
 VR_HD int32_t cvt_flr(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -388,41 +337,34 @@ VR_HD int32_t majorant_index(const GridView& g, v3 ipos, int32_t mip) {
     // the layout majorant_kernel wrote the table in (GridView::maj_blocked, a property of the grid since round 5): known at compile time in the kernels built
     // for one layout -- a kernel is only launched on grids of its layout (vr_launch.hip pathtrace_variant) -- read from the view otherwise (wave-uniform)
     const bool blocked = MAJB == 2 ? g.maj_blocked != 0 : MAJB == 1;
-    if (CLEAN && VR_MAJ_OUTSIDE_CELL) {
+    if (CLEAN) {
         const uint32_t bx = (uint32_t)cvt_flr(ipos.x) >> sh, by = (uint32_t)cvt_flr(ipos.y) >> sh, bz = (uint32_t)cvt_flr(ipos.z) >> sh;
         const uint32_t sz = (uint32_t)g.mshift[2] - (uint32_t)mip;
         const bool inside = ((bx >> sx) | (by >> sy) | (bz >> sz)) == 0u;          // a negative coordinate leaves ones above the shifted-out bits
         return inside ? (int32_t)(off + majorant_cell_index(bx, by, bz, sx, sy, (uint32_t)mip, blocked)) : g.maj_outside;
     }
     // (a level the grid does not have -- mip > n_mips -- needs no test: the table has all four levels and the cells of a missing one hold the "outside" value,
-    // vr_setup.hip majorant_kernel; VR_MAJ_LEVEL_TEST=1 brings the compare back)
-    const bool inside = (VR_MAJ_LEVEL_TEST ? (mip <= g.n_mips) : true) & (ipos.x >= 0.0f) & (ipos.x < g.mlim[0]) & (ipos.y >= 0.0f) & (ipos.y < g.mlim[1]) & (ipos.z >= 0.0f) & (ipos.z < g.mlim[2]);
+    // vr_setup.hip majorant_kernel)
+    const bool inside = (ipos.x >= 0.0f) & (ipos.x < g.mlim[0]) & (ipos.y >= 0.0f) & (ipos.y < g.mlim[1]) & (ipos.z >= 0.0f) & (ipos.z < g.mlim[2]);
     const uint32_t bx = (uint32_t)(int32_t)ipos.x >> sh, by = (uint32_t)(int32_t)ipos.y >> sh, bz = (uint32_t)(int32_t)ipos.z >> sh;
-    return inside ? (int32_t)(off + majorant_cell_index(bx, by, bz, sx, sy, (uint32_t)mip, blocked)) : (VR_MAJ_OUTSIDE_CELL ? g.maj_outside : -1);
+    return inside ? (int32_t)(off + majorant_cell_index(bx, by, bz, sx, sy, (uint32_t)mip, blocked)) : g.maj_outside;
 }
-// Unconditional load (cell 0 when outside; the caller discards it then).  TF kernels read the float table (TF-remapped
+// Unconditional load.  TF kernels read the float table (TF-remapped
 // majorants); the others read the raw fp16 range maximum -- half the cache lines -- and scale it themselves (majorant_value).
 template <bool TF, bool A32 = false>
 VR_HD uint32_t majorant_fetch(const GridView& g, int32_t idx) {
-    const int32_t i = VR_MAJ_OUTSIDE_CELL ? idx : (idx < 0 ? 0 : idx);
-#if VR_MAJ_OUTSIDE_CELL && defined(__clang__)
-    __builtin_assume(i >= 0);                        // a table index (at most 73/64 x 2^30 cells, vr_scene.h): zero- instead of sign-extended into the 64-bit address
+#if defined(__clang__)
+    __builtin_assume(idx >= 0);                      // a table index (at most 73/64 x 2^30 cells, vr_scene.h): zero- instead of sign-extended into the 64-bit address
 #endif
-    VR_TRACE(0, g.majorant16, i, TF ? 4 : 2);
-    return TF ? f2u(table_load<A32>(g.majorant, (uint32_t)i)) : (uint32_t)table_load<A32>(g.majorant16, (uint32_t)i);
+    VR_TRACE(0, g.majorant16, idx, TF ? 4 : 2);
+    return TF ? f2u(table_load<A32>(g.majorant, (uint32_t)idx)) : (uint32_t)table_load<A32>(g.majorant16, (uint32_t)idx);
 }
 template <bool TF>
 VR_HD float majorant_value(const SceneParams& P, uint32_t raw) { return TF ? u2f(raw) : P.u.vol_density_scale * half2float(raw); }
-// the majorant of a step from the word march_load fetched for cell `idx`
-template <bool TF>
-VR_HD float majorant_of(const SceneParams& P, int32_t idx, uint32_t raw) {
-    const float m = majorant_value<TF>(P, raw);
-    return VR_MAJ_OUTSIDE_CELL ? m : (idx >= 0 ? m : 0.0f);
-}
 template <bool TF, int DENSE = 2, int MAJB = 2>
 VR_HD float majorant_at(const SceneParams& P, v3 ipos, int32_t mip) {
     const int32_t idx = majorant_index<DENSE, MAJB>(P.density, ipos, mip);
-    return majorant_of<TF>(P, idx, majorant_fetch<TF>(P.density, idx));
+    return majorant_value<TF>(P, majorant_fetch<TF>(P.density, idx));
 }
 // A point of a CLEAN segment (seg_clean) needs no guard.  Its coordinates are finite with |p| < 2^21 -- or NaN on ALL THREE axes, when the ray parameter itself is NaN:
 // the reference's `t += tau / majorant` is 0 / 0 when a free-flight draw of exactly 0 meets an empty first cell (2^-24 per segment: dozens of times in a bench frame),
@@ -562,30 +504,19 @@ constexpr LcgJump lcg_jump(int j) {
     for (int i = 0; i < j; ++i) { A = A * 1664525u; C = C * 1664525u + 1013904223u; }
     return LcgJump{ A, C };
 }
-// Round 5 (VR_TAP_ABS_BAND, default on): the same decision with fewer operations.  The weights come out of the Horner forms already scaled by 2^24 (the
-// constants carry the factor: scaling by a power of two commutes with every rounding of the evaluation, so W = 2^24 x w bit for bit), the partial sums are
-// s2 = RN(2^-24 W2 + u^3), s3 = RN(2^-24 W3 + s2) (one fma each, the same single rounding as the additions they replace), and a test is ONE fma and two
-// compares: x = RN(k s - W);  yes: x < -G,  no: x > G,  with an ABSOLUTE band G = 160 (in units of k s; W <= 4 x 2^24, so G / W >= 2^-18.7 where the two
-// evaluations' thresholds differ most, 2^-21.3 relative = 26 units).  Round 2's form -- x = k s against RN(W lo - eps) and RN(W hi + eps), a relative band --
-// took a multiply and two fmas per test.  tests/tools_tricubic_band.cpp checks either form for every float t in [0, 1] and all 2^24 draws.
-#ifndef VR_TAP_ABS_BAND
-#define VR_TAP_ABS_BAND 1
-#endif
-// VR_TAP_PRESHIFT (round 5, default): the nine draws are taken from the LCG state SHIFTED LEFT BY 8 -- multiplying the recurrence by 2^8 commutes with it mod 2^32, and
-// the top 24 bits of the shifted state are the draw's 24 bits, so its conversion to float is 2^8 k exactly (24 significant bits) and the mask per draw is gone.  The
-// weights and the band carry the same factor (all of it powers of two: every rounding of the evaluation commutes with it, x' = 2^8 x bit for bit).  And a call
-// needs the exact code when the SMALLEST |x| of its nine tests lies inside the band: min(|x|) chained through the tests (min3 for two of them) and ONE compare,
+// Round 5: the same decision with fewer operations.  The weights come out of the Horner forms already scaled by 2^24 (the constants carry the factor: scaling by a
+// power of two commutes with every rounding of the evaluation, so W = 2^24 x w bit for bit), the partial sums are s2 = RN(2^-24 W2 + u^3), s3 = RN(2^-24 W3 + s2) (one
+// fma each, the same single rounding as the additions they replace), and a test is ONE fma and two compares: x = RN(k s - W);  yes: x < -G,  no: x > G,  with an
+// ABSOLUTE band G = 160 (in units of k s; W <= 4 x 2^24, so G / W >= 2^-18.7 where the two evaluations' thresholds differ most, 2^-21.3 relative = 26 units);
+// tests/tools_tricubic_band.cpp checks it for every float t in [0, 1] and all 2^24 draws (profiles/r5_tricubic_abs_band_exhaustive.txt).
+// The nine draws are taken from the LCG state SHIFTED LEFT BY 8 -- multiplying the recurrence by 2^8 commutes with it mod 2^32, and the top 24 bits of the shifted
+// state are the draw's 24 bits, so its conversion to float is 2^8 k exactly (24 significant bits) and the mask per draw is gone.  The weights and the band carry the
+// same factor (all of it powers of two: every rounding of the evaluation commutes with it, x' = 2^8 x bit for bit; profiles/r5_tricubic_preshift_exhaustive.txt).  And a
+// call needs the exact code when the SMALLEST |x| of its nine tests lies inside the band: min(|x|) chained through the tests (min3 for two of them) and ONE compare,
 // instead of a second compare per test.  A test whose x is NaN (a non-finite coordinate on that axis) drops out of the minimum and decides "no" -- what the exact
 // code's comparisons against NaN quotients decide for that axis as well.
-#ifndef VR_TAP_PRESHIFT
-#define VR_TAP_PRESHIFT 1
-#endif
-#ifndef VR_TAP_CHAIN
-#define VR_TAP_CHAIN 0
-#endif
-#if VR_TAP_ABS_BAND
-struct AxisFast { float w2, s2, w3, s3, w4, fl; };      // w*: 2^24 x 6 x the weights (2^32 x with VR_TAP_PRESHIFT); s*: 6 x the partial sums (s4 = 6)
-constexpr float kTapDrawScale = VR_TAP_PRESHIFT ? 256.0f : 1.0f;        // a draw enters its test as kTapDrawScale x k, k its 24 bits
+struct AxisFast { float w2, s2, w3, s3, w4, fl; };      // w*: 2^32 x 6 x the weights; s*: 6 x the partial sums (s4 = 6)
+constexpr float kTapDrawScale = 256.0f;        // a draw enters its test as kTapDrawScale x k, k its 24 bits
 constexpr float kTapScale = 16777216.0f * kTapDrawScale, kTapInvScale = 1.0f / kTapScale, kTapBand = 160.0f * kTapDrawScale;
 VR_HD AxisFast tricubic_axis_fast(float q) {
     AxisFast a;
@@ -604,29 +535,6 @@ VR_HD void tricubic_fast_test(float k, float w, float s, bool& yes, bool& no) {
     yes = x < -kTapBand;
     no = x > kTapBand;
 }
-#else
-struct AxisFast { float w2, s2, w3, s3, w4, fl; };      // 6 x the weights; s4 = 6
-VR_HD AxisFast tricubic_axis_fast(float q) {
-    AxisFast a;
-    a.fl = floor_(q);
-    const float t = q - a.fl, t2 = t * t, u = 1.0f - t;
-    a.w4 = t2 * t;                                                    // t^3
-    a.w2 = fma_(fma_(3.0f, t, -6.0f), t2, 4.0f);                      // 3t^3 - 6t^2 + 4
-    a.w3 = fma_(fma_(fma_(-3.0f, t, 3.0f), t, 3.0f), t, 1.0f);        // -3t^3 + 3t^2 + 3t + 1
-    a.s2 = (u * u) * u + a.w2;                                        // (1 - t)^3 + 6 w2
-    a.s3 = a.s2 + a.w3;
-    return a;
-}
-constexpr float kTapLo = 16777152.0f;       // 2^24 (1 - 2^-18)
-constexpr float kTapHi = 16777280.0f;       // 2^24 (1 + 2^-18)
-// one test: yes / no as the reference decides, or neither (inside the band).  k: the draw's 24 bits as a float
-VR_HD void tricubic_fast_test(float k, float w, float s, bool& yes, bool& no) {
-    const float x = k * s;
-    // the absolute term keeps k = 0 out of "yes" where the reference's weight has underflowed to 0 (t < 1e-9) and the fast one has not
-    yes = x < fma_(w, kTapLo, -1e-20f);
-    no = x > fma_(w, kTapHi, 1e-20f);
-}
-#endif
 #ifndef VR_TAP_FAST
 #if defined(__HIP_DEVICE_COMPILE__)
 #define VR_TAP_FAST 1
@@ -670,52 +578,19 @@ VR_HD void tricubic_tap_t(v3 ipos, uint32_t& seed, int32_t& tx, int32_t& ty, int
         const AxisFast fx = tricubic_axis_fast(ipos.x - 0.5f), fy = tricubic_axis_fast(ipos.y - 0.5f), fz = tricubic_axis_fast(ipos.z - 0.5f);
         flx = fx.fl; fly = fy.fl; flz = fz.fl;
         const uint32_t seed0 = seed;
-#if VR_TAP_ABS_BAND && VR_TAP_PRESHIFT
         const uint32_t sh8 = seed << 8;
         float amin = __builtin_inff();                               // the smallest |x| of the nine tests
-#if VR_TAP_CHAIN
-        // the nine shifted states one from the other, st_j = a st_(j-1) + 2^8 c: ONE multiplier in a scalar register instead of nine jump-ahead constants (the
-        // kernels are short of scalar registers: the brick kernel re-loaded the atlas pointer from the kernel arguments in every collision pass).  The empty asm
-        // keeps the optimiser from folding the chain back into nine constants.
-        uint32_t st_ = sh8;
-#if defined(__HIP_DEVICE_COMPILE__)
-#define VR_TAP_KEEP(X) asm("" : "+v"(X))
-#else
-#define VR_TAP_KEEP(X) do { } while (0)
-#endif
-#define VR_TAP(J, V, W, S, N) do { \
-            st_ = st_ * 1664525u + (1013904223u << 8); \
-            VR_TAP_KEEP(st_); \
-            const float x_ = fma_((float)st_, S, -(W));     /* tricubic_fast_test's x for the draw 2^8 k */ \
-            J = x_ < -kTapBand ? V : J; \
-            amin = __builtin_fminf(amin, __builtin_fabsf(x_)); \
-        } while (0)
-#else
 #define VR_TAP(J, V, W, S, N) do { \
             constexpr LcgJump g_ = lcg_jump(N); \
             const float x_ = fma_((float)(sh8 * g_.A + (g_.C << 8)), S, -(W));     /* tricubic_fast_test's x for the draw 2^8 k */ \
             J = x_ < -kTapBand ? V : J; \
             amin = __builtin_fminf(amin, __builtin_fabsf(x_)); \
         } while (0)
-#endif
-#else
-        const uint32_t lo24 = seed & 0x00FFFFFFu;
-        bool unsure = false;
-#define VR_TAP(J, V, W, S, N) do { \
-            constexpr LcgJump g_ = lcg_jump(N); \
-            bool yes_, no_; \
-            tricubic_fast_test((float)((mul24(lo24, g_.A & 0x00FFFFFFu) + g_.C) & 0x00FFFFFFu), W, S, yes_, no_); \
-            J = yes_ ? V : J; \
-            unsure = unsure | !(yes_ | no_); \
-        } while (0)
-#endif
         VR_TAP(jx, 1, fx.w2, fx.s2, 1); VR_TAP(jy, 1, fy.w2, fy.s2, 2); VR_TAP(jz, 1, fz.w2, fz.s2, 3);
         VR_TAP(jx, 2, fx.w3, fx.s3, 4); VR_TAP(jy, 2, fy.w3, fy.s3, 5); VR_TAP(jz, 2, fz.w3, fz.s3, 6);
         VR_TAP(jx, 3, fx.w4, 6.0f, 7); VR_TAP(jy, 3, fy.w4, 6.0f, 8); VR_TAP(jz, 3, fz.w4, 6.0f, 9);
 #undef VR_TAP
-#if VR_TAP_ABS_BAND && VR_TAP_PRESHIFT
         const bool unsure = !(amin > kTapBand);                      // a test inside the band, or nine NaNs
-#endif
         rng_skip9(seed);
         exact = unsure;
         if (unsure) { seed = seed0; jx = jy = jz = 0; }
@@ -895,17 +770,12 @@ __device__ __forceinline__ void env_warp_block(float4 q0, float4 q1, float4 q2, 
     env_warp_level<ENVDC>(child, px, py, posx, posy);
 }
 #endif
-#ifndef VR_ENV_BLOCK_LOADS
-#define VR_ENV_BLOCK_LOADS 1
-#endif
-// build-time experiments (round 6, profiles/r6j_*): levels 0 and 1 through the scalar cache; block loads only for the levels below VR_ENV_BLOCK_BELOW
-#ifndef VR_ENV_SCALAR_TOP
-#define VR_ENV_SCALAR_TOP 0
-#endif
+// block loads only for the levels below VR_ENV_BLOCK_BELOW (round 6, profiles/r6j_environment_warp_loads.txt: all of them; levels 0 and 1 do not go through the scalar cache)
 #ifndef VR_ENV_BLOCK_BELOW
 #define VR_ENV_BLOCK_BELOW 64
 #endif
-// BLOCK: load a pair of levels' 64-byte block at once (below); off in the everything-at-run-time kernel, which has no registers for it
+// BLOCK: load a pair of levels' 64-byte block at once (below, on the device: profiles/r5g_ab_env_warp_block_loads.txt); off in the everything-at-run-time kernel, which
+// has no registers for it
 // ENVDC: the warp's quotients by div_core (env_warp_level<true>): only for an environment whose table passed the check (SceneParams::env_div_safe)
 template <bool BLOCK = true, bool ENVDC = false>
 VR_HD void sample_environment(const SceneParams& P, float r0, float r1, v3& w_i, v3& Le, float& pdf_out) {
@@ -921,22 +791,10 @@ VR_HD void sample_environment(const SceneParams& P, float r0, float r1, v3& w_i,
         if (top == 0) w_texel = blk[3 + c];
         blk += kEnvCdfBlockFloats; k = 1;
     }
-#if VR_ENV_BLOCK_LOADS && VR_ENV_SCALAR_TOP && defined(__HIP_DEVICE_COMPILE__)
-    if (BLOCK && k == 0 && 1 < top) {
-        // levels 0 and 1: the block is the same for every lane -- read through the scalar cache (a load in the constant address space: the table is not written while
-        // the kernel runs) into scalar registers, no vector-memory round trip
-        typedef const float4 __attribute__((address_space(4))) * ConstQ;
-        uint64_t addr = reinterpret_cast<uint64_t>(blk);
-        asm("" : "+s"(addr));                                   // (keeps the optimiser from folding the pointer back into the global address space and the load into a vector one)
-        ConstQ cb = (ConstQ)(addr);
-        env_warp_block<ENVDC>(cb[0], cb[1], cb[2], cb[3], px, py, posx, posy);
-        blk += kEnvCdfBlockFloats; k = 2;
-    }
-#endif
     for (; k + 1 < top; k += 2) {                               // levels k and k + 1: parent record, then the chosen child's in the same block
         const float* b = blk + kEnvCdfBlockFloats * (size_t)((posy << k) + posx);
         VR_TRACE(2, P.env_cdf, (b - P.env_cdf) * 4, 64);
-#if VR_ENV_BLOCK_LOADS && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (BLOCK && k < VR_ENV_BLOCK_BELOW) {
         // the whole 64-byte block at once -- parent record and all four children's -- and the child picked in registers: one memory round trip per pair of
         // levels instead of two dependent ones (the second was a hit in the line the first had fetched, but a round trip all the same)
@@ -1028,16 +886,9 @@ VR_HD bool intersect_box(v3 pos, v3 dir, const float* bmin, const float* bmax, f
 }
 
 // one DDA step on mip (common.glsl:404-409)
-#ifndef VR_DDA_INT_DIM
-#define VR_DDA_INT_DIM 1
-#endif
 template <bool CLEAN = false>
 VR_HD float step_dda(v3 p, v3 ri, int32_t mip) {
-#if VR_DDA_INT_DIM
     const float dim = u2f((uint32_t)(130 + mip) << 23);        // 2^(3+mip) = (float)(8 << mip), from the exponent: shares the shift with idim (round 5: an add instead of shift + convert)
-#else
-    const float dim = (float)(8 << mip);
-#endif
     const float idim = u2f((uint32_t)(124 - mip) << 23);       // 1 / dim exactly (dim = 2^(3+mip)): no division
     const float ox = ri.x >= 0.0f ? dim + 0.5f : -0.5f;
     const float oy = ri.y >= 0.0f ? dim + 0.5f : -0.5f;
@@ -1063,20 +914,14 @@ VR_HD void hot_init(Hot& h) {
     h.maj_idx = -2; h.maj_raw = 0u;
 }
 
-// VR_SAMPLE_NT (default since round 6): the per-sample radiance is written once and read once, by the accumulation pass, long after it has left the L2: a non-temporal
-// store.  Round 4 measured +0.2 ... +0.5 % ("within the noise"), round 6 on the final kernels c2 +0.8 / +1.2 %, c4 +0.4 / +0.9 % in two rounds (profiles/r6h_*)
-#ifndef VR_SAMPLE_NT
-#define VR_SAMPLE_NT 1
-#endif
 // result of trace_path: vec4(L, clamp(n_paths, 0, 1)) -> the item's slot of the sample buffer
 VR_HD void write_sample(const WorkUnit& wu, uint32_t item, v3 L, uint32_t n_paths) {
     float* o = wu.out + 4u * (size_t)item;
-#if defined(__HIP_DEVICE_COMPILE__) && VR_SAMPLE_NT
-    // build-time experiment (profiles/r4d_*): the sample pool is written once and read once by the accumulation pass -- non-temporal stores
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the sample pool is written once and read once, by the accumulation pass, long after it has left the L2: a non-temporal store (c2 +0.8 ... +1.2 %, c4 +0.4 ...
+    // +0.9 %: profiles/r6h_non_temporal_stores.txt)
     typedef float vr_f4 __attribute__((ext_vector_type(4)));
     __builtin_nontemporal_store(vr_f4{ L.x, L.y, L.z, n_paths > 0u ? 1.0f : 0.0f }, reinterpret_cast<vr_f4*>(o));
-#elif defined(__HIP_DEVICE_COMPILE__)
-    *reinterpret_cast<float4*>(o) = make_float4(L.x, L.y, L.z, n_paths > 0u ? 1.0f : 0.0f);
 #else
     o[0] = L.x; o[1] = L.y; o[2] = L.z; o[3] = n_paths > 0u ? 1.0f : 0.0f;
 #endif
@@ -1112,7 +957,7 @@ VR_HD bool begin_segment(Hot& h, const SceneParams& P, v3 pos, v3 d, int32_t sha
         // t = near - log(1 - xi) * vol_inv_majorant, then straight to the first tentative collision
         h.ri = v3{ 0, 0, 0 };
         h.tau = 0.0f;
-        if (VR_CLEAN_FLAG) h.far = -tfar;            // these trackers' segments are never examined: not clean
+        h.far = -tfar;                               // these trackers' segments are never examined: not clean
         h.t = tnear + neg_log_1m(rng(h.seed)) * P.u.vol_inv_majorant;
         if (h.t < tfar) { h.majorant = P.u.vol_majorant; h.state = ST_COLLIDE; }
         else h.state = segment_end_state(shadow);
@@ -1122,7 +967,6 @@ VR_HD bool begin_segment(Hot& h, const SceneParams& P, v3 pos, v3 d, int32_t sha
     h.t = tnear + 1e-6f;
     h.tau = neg_log_1m(rng(h.seed));
     h.state = ST_MARCH;
-#if VR_CLEAN_FLAG
     {   // a finite ray of moderate size (see seg_clean): every comparison fails for NaN, and inf * 0 is NaN
         const float ax = abs_(h.idir.x), ay = abs_(h.idir.y), az = abs_(h.idir.z), amax = __builtin_fmaxf(ax, __builtin_fmaxf(ay, az));
         const bool clean = (int)(abs_(h.ipos.x) < kCleanBound) & (int)(abs_(h.ipos.y) < kCleanBound) & (int)(abs_(h.ipos.z) < kCleanBound) &
@@ -1132,7 +976,6 @@ VR_HD bool begin_segment(Hot& h, const SceneParams& P, v3 pos, v3 d, int32_t sha
                            (int)(amax < kCleanBound) & (int)(amax >= 1.0f / kCleanBound);
         h.far = clean ? tfar : -tfar;
     }
-#endif
     return true;
 }
 
@@ -1170,20 +1013,16 @@ VR_HD void first_resume(Hot& h, const SceneParams& P) {
     h.Tr = 1.0f;
 }
 
-// Loop body of both DDA trackers up to the collision test (common.glsl:422-435, 469-482), kMarchSteps iterations at a time and
+// Loop body of both DDA trackers up to the collision test (common.glsl:422-435, 469-482), two iterations at a time and
 // in two phases.  march_prep does everything that needs no memory -- positions, DDA levels, step lengths of this iteration AND
 // of the following ones, each taken as if its predecessors neither collide nor leave the box (step lengths do not depend on the
 // majorant) -- and march_load fetches all their majorants together; march_finish replays the reference's loop on those
 // values.  A step that an earlier one cancels costs one unused load; the arithmetic of a step that does run is the
 // reference's, operation for operation.
-#ifndef VR_MARCH_STEPS
-#define VR_MARCH_STEPS 2
-#endif
-constexpr int32_t kMarchSteps = VR_MARCH_STEPS;
-#if VR_MARCH_STEPS == 2
-// the two-step form written out (the default; the generic loop below compiles ~1 % slower for the same arithmetic)
-struct MarchIO { float dt1, dt2, t1; uint32_t maj1, maj2; int32_t i1, i2; bool go1, go2; };     // i*: majorant cell or -1 (outside: majorant 0); maj*: as loaded (majorant_fetch)
-VR_HD void march_idle(MarchIO& io) { io.i1 = io.i2 = VR_MAJ_OUTSIDE_CELL ? 0 : -1; io.dt1 = io.dt2 = io.t1 = 0.0f; io.go1 = io.go2 = false; }      // a lane that is not marching (its loads: cell 0)
+// The two steps are written out: a generic N-step loop compiles ~1 % slower for the same arithmetic, and one or three steps per pass measure no better
+// (profiles/r2w_ab_march_steps_recheck.txt, r4a_march_steps_and_collide_threshold.txt, r5h_ab_one_step_march_with_more_hot_pairs.txt).
+struct MarchIO { float dt1, dt2, t1; uint32_t maj1, maj2; int32_t i1, i2; bool go1, go2; };     // i*: majorant cell; maj*: as loaded (majorant_fetch)
+VR_HD void march_idle(MarchIO& io) { io.i1 = io.i2 = 0; io.dt1 = io.dt2 = io.t1 = 0.0f; io.go1 = io.go2 = false; }      // a lane that is not marching (its loads: cell 0)
 // CLEAN: every path the call runs for is on a clean segment (seg_clean).  The second step is prepared also when the first one leaves [near, far) (go2 false: its
 // results are discarded); its point may then lie beyond the bound, which the clean forms tolerate -- an index is only formed for cells inside the table, and a
 // discarded step's NaN is discarded with it
@@ -1213,29 +1052,10 @@ VR_HD void march_load(const SceneParams& P, MarchIO& io) {
 // the same with the lane's remembered (index, word) pair (Hot::maj_idx): a first step into the remembered cell loads nothing new
 template <bool TF, bool A32 = false>
 VR_HD void march_load_reuse(const SceneParams& P, MarchIO& io, const Hot& h) {
-    const bool same = io.i1 == h.maj_idx;                        // (-1 = outside never equals a remembered index: those are >= 0 or -2)
+    const bool same = io.i1 == h.maj_idx;                        // (hot_init's -2 never equals a cell's index)
     const uint32_t m1 = majorant_fetch<TF, A32>(P.density, same ? 0 : io.i1);
     io.maj1 = same ? h.maj_raw : m1;
     io.maj2 = majorant_fetch<TF, A32>(P.density, io.i2);
-}
-// The same loads when the tail of the majorant table -- cells [first, end): the coarse levels, or the whole table of a small grid -- has been copied
-// to LDS (vr_pathtrace.h): a lane whose cell lies there reads the copy and sends its global load to cell 0, which all such lanes share (one
-// line); when the whole table is resident (first == 0, wave-uniform) no global load is issued at all.  T: uint16_t (raw fp16) or float (TF).
-template <bool TF, class T, bool A32 = false>
-VR_HD uint32_t majorant_fetch_lds(const GridView& g, int32_t idx, const T* lds, int32_t first, bool all_resident) {
-    const int32_t i = idx < 0 ? 0 : idx;
-    const bool in_lds = i >= first;
-    const T s = lds[in_lds ? i - first : 0];
-    const uint32_t sv = TF ? f2u((float)s) : (uint32_t)s;
-    if (all_resident) return sv;
-    const uint32_t gv = majorant_fetch<TF, A32>(g, in_lds ? 0 : i);
-    return in_lds ? sv : gv;
-}
-template <bool TF, class T, bool A32 = false>
-VR_HD void march_load_lds(const SceneParams& P, MarchIO& io, const T* lds, int32_t first) {
-    const bool all_resident = first == 0;
-    io.maj1 = majorant_fetch_lds<TF, T, A32>(P.density, io.i1, lds, first, all_resident);
-    io.maj2 = majorant_fetch_lds<TF, T, A32>(P.density, io.i2, lds, first, all_resident);
 }
 // CLEAN (and no transfer function): the step back to the collision point, tau / majorant, by vr_math.h div_core.  Its domain: the majorant is density_scale x an fp16
 // range maximum, in [2^-40, 2^40] for the scales the kernels with a CLEAN form are launched with (2^-16 ... 2^24: vr_launch.hip pathtrace_variant); tau = (what was left) - majorant x dt <= 0 with dt in [2^-22, 2^27] (a clean
@@ -1245,15 +1065,15 @@ VR_HD void march_load_lds(const SceneParams& P, MarchIO& io, const T* lds, int32
 template <bool TF, bool REUSE = false, bool CLEAN = false>
 VR_HD void march_finish(Hot& h, const SceneParams& P, const MarchIO& io) {
     if (!io.go1) { h.state = segment_end_state(h.shadow); return; }
-    float t = io.t1, maj = majorant_of<TF>(P, io.i1, io.maj1);
+    float t = io.t1, maj = majorant_value<TF>(P, io.maj1);
     float tau = h.tau - maj * io.dt1;
     int32_t q = h.mipq < 12 ? h.mipq + 1 : 12;
-    // REUSE: the cell whose majorant the lane leaves the pass with (Hot::maj_idx; selects, not conditional stores)
-    if (REUSE) { const bool keep = VR_MAJ_OUTSIDE_CELL || io.i1 >= 0; h.maj_idx = keep ? io.i1 : h.maj_idx; h.maj_raw = keep ? io.maj1 : h.maj_raw; }
+    // REUSE: the cell whose majorant the lane leaves the pass with (Hot::maj_idx)
+    if (REUSE) { h.maj_idx = io.i1; h.maj_raw = io.maj1; }
     if (tau > 0.0f) {                                              // no tentative collision in the first cell: second step
         if (!io.go2) { h.t = t; h.tau = tau; h.mipq = q; h.state = segment_end_state(h.shadow); return; }
-        maj = majorant_of<TF>(P, io.i2, io.maj2);
-        if (REUSE) { const bool keep = VR_MAJ_OUTSIDE_CELL || io.i2 >= 0; h.maj_idx = keep ? io.i2 : h.maj_idx; h.maj_raw = keep ? io.maj2 : h.maj_raw; }
+        maj = majorant_value<TF>(P, io.maj2);
+        if (REUSE) { h.maj_idx = io.i2; h.maj_raw = io.maj2; }
         t = io.t1 + io.dt2;
         tau = tau - maj * io.dt2;
         q = q < 12 ? q + 1 : 12;
@@ -1265,68 +1085,6 @@ VR_HD void march_finish(Hot& h, const SceneParams& P, const MarchIO& io) {
     h.majorant = maj;
     h.state = ST_COLLIDE;
 }
-#else
-struct MarchIO {
-    float dt[kMarchSteps], t[kMarchSteps];      // step length; ray parameter after the step
-    uint32_t maj[kMarchSteps];                  // majorant of the step's cell as loaded (majorant_fetch)
-    int32_t idx[kMarchSteps];                   // its table index or -1 (outside: majorant 0)
-    bool go[kMarchSteps];                       // the step starts inside [near, far)
-};
-VR_HD void march_idle(MarchIO& io) {             // a lane that is not marching
-#pragma unroll
-    for (int k = 0; k < kMarchSteps; ++k) { io.idx[k] = VR_MAJ_OUTSIDE_CELL ? 0 : -1; io.dt[k] = io.t[k] = 0.0f; io.go[k] = false; }
-}
-template <int DENSE = 2, int MAJB = 2, bool CLEAN = false>
-VR_HD void march_prep(const Hot& h, const SceneParams& P, MarchIO& io) {
-    float t = h.t;
-    int32_t q = h.mipq;
-#pragma unroll
-    for (int k = 0; k < kMarchSteps; ++k) {
-        io.go[k] = t < seg_far(h);
-        const v3 c = axpy(h.ipos, t, h.idir);
-        const int32_t m = round_mip_q(q);
-        io.idx[k] = majorant_index<DENSE, MAJB, CLEAN>(P.density, c, m);
-        io.dt[k] = step_dda<CLEAN>(c, h.ri, m);
-        t = t + io.dt[k];
-        io.t[k] = t;
-        q = q < 12 ? q + 1 : 12;                                   // mip = min(mip + 0.25, 3)
-    }
-}
-// the loads: unconditional and for every lane of the wavefront (an idle lane reads cell 0), so that they sit in straight-line
-// code and the compiler's wait counts are exact
-template <bool TF, bool A32 = false>
-VR_HD void march_load(const SceneParams& P, MarchIO& io) {
-#pragma unroll
-    for (int k = 0; k < kMarchSteps; ++k) io.maj[k] = majorant_fetch<TF, A32>(P.density, io.idx[k]);
-}
-template <bool TF, class T, bool A32 = false>
-VR_HD void march_load_lds(const SceneParams&, MarchIO&, const T*, int32_t) { static_assert(sizeof(T) == 0, "VR_MAJ_LDS is written for VR_MARCH_STEPS == 2"); }
-template <bool TF, bool A32 = false>
-VR_HD void march_load_reuse(const SceneParams& P, MarchIO& io, const Hot&) { march_load<TF, A32>(P, io); }      // (majorant reuse is written for VR_MARCH_STEPS == 2)
-template <bool TF, bool REUSE = false, bool CLEAN = false>
-VR_HD void march_finish(Hot& h, const SceneParams& P, const MarchIO& io) {
-    static_assert(!REUSE, "majorant reuse is written for VR_MARCH_STEPS == 2");
-    float tau = h.tau, maj = 0.0f, t = h.t;
-    int32_t q = h.mipq;
-#pragma unroll
-    for (int k = 0; k < kMarchSteps; ++k) {
-        if (!io.go[k]) { h.t = t; h.tau = tau; h.mipq = q; h.state = segment_end_state(h.shadow); return; }
-        maj = majorant_of<TF>(P, io.idx[k], io.maj[k]);
-        t = io.t[k];
-        tau = tau - maj * io.dt[k];
-        q = q < 12 ? q + 1 : 12;
-        if (!(tau > 0.0f)) goto tentative_collision;
-    }
-    h.t = t; h.tau = tau; h.mipq = q;                              // still marching
-    return;
-tentative_collision:
-    t += (CLEAN && !TF) ? div_core(tau, maj) : tau / maj;
-    h.t = t; h.tau = tau; h.mipq = q;
-    if (t >= seg_far(h)) { h.state = segment_end_state(h.shadow); return; }
-    h.majorant = maj;
-    h.state = ST_COLLIDE;
-}
-#endif
 // one iteration (sequential form; the scheduler uses the two-phase form above)
 template <bool TF, int DENSE = 2, int MAJB = 2>
 VR_HD void do_march(Hot& h, const SceneParams& P) {
@@ -1612,7 +1370,7 @@ VR_HD void do_nee(Hot& h, Cold& c, const Cold& crd, const SceneParams& P) {
 // common.glsl:625-641, then the head of the next sample_volumeDDA call
 template <class K, class Cold, bool SHLE_IN_HOT = false, bool ITEM_IN_HOT = false>
 VR_HD void do_postnee(Hot& h, Cold& c, const SceneParams& P, const WorkUnit& wu) {
-    // the whole slot, as the 16-byte groups its layout puts side by side: four loads (with VR_WORLD_SLOT three -- (dir, sh_pdf), (L, n_paths), (thr, f_p); vr_pathtrace.h
+    // the whole slot, as the 16-byte groups its layout puts side by side: four loads (with world_slot three -- (dir, sh_pdf), (L, n_paths), (thr, f_p); vr_pathtrace.h
     // ColdGlobalT), all in flight at once (round 6; before: seven, the last two -- dir, pos -- issued only after the roulette)
     constexpr bool WS = world_slot<K>();
     const Quad q_l = ld4(c, C_L, C_NPATHS), q_p = WS ? Quad{ h.wpos, 0.0f } : ld4(c, C_POS, C_SHPDF);
@@ -1624,7 +1382,7 @@ VR_HD void do_postnee(Hot& h, Cold& c, const SceneParams& P, const WorkUnit& wu)
     const float fpl_kept = WS ? 0.0f : q_t.b;
     if (sh_pdf > 0.0f) {
         // common.glsl:620-626: L += throughput * mis * f_p * Tr * Le / pdf, the factors of the light sample do_nee drew
-        // (VR_WORLD_SLOT: f_p from the incoming direction and the shadow segment's, which the path still carries -- the expression do_nee's other form evaluates)
+        // (world_slot: f_p from the incoming direction and the shadow segment's, which the path still carries -- the expression do_nee's other form evaluates)
         const float f_p = WS ? phase_hg(dot(-q_d.a, h.wdir), P.u.vol_phase_g) : fpl_kept;
         const float mis = P.u.show_environment > 0 ? power_heuristic(sh_pdf, f_p) : 1.0f;
         L = L + ((((thr * mis) * f_p) * h.Tr) * (SHLE_IN_HOT ? h.shle : ld3(c, C_SHLE))) / sh_pdf;
@@ -1662,14 +1420,14 @@ VR_HD void do_escape(Hot& h, const Cold& c, const SceneParams& P, const WorkUnit
     v3 L = ld3(c, C_L), thr = ld3(c, C_THR), dir = ld3(c, C_DIR);
     uint32_t n_paths = ldu(c, C_NPATHS), item = ITEM_IN_HOT ? h.item : ldu(c, C_ITEM);
     const float f_p = c.ld(C_FP);
-    // VR_WORLD_SLOT: the lookup needs nothing of the slot -- it runs BEFORE the slot's values are touched, the line's latency under the lookup's arithmetic and texel fetch
+    // world_slot: the lookup needs nothing of the slot -- it runs BEFORE the slot's values are touched, the line's latency under the lookup's arithmetic and texel fetch
     // (round 6; before, the selects below waited for the line first: two round trips one after the other)
     v3 Le_early = v3{ 0.0f, 0.0f, 0.0f };
     if (WS && P.u.show_environment > 0) Le_early = lookup_environment(P, h.wdir);
     const v3 L_first = FIRST_L_IN_HOT ? h.eL : v3{ 0.0f, 0.0f, 0.0f };
     L = v3{ first ? L_first.x : L.x, first ? L_first.y : L.y, first ? L_first.z : L.z };
     thr = v3{ first ? 1.0f : thr.x, first ? 1.0f : thr.y, first ? 1.0f : thr.z };
-    if (WS) dir = h.wdir;        // (VR_WORLD_SLOT: the escaping segment's own direction, first path or not)
+    if (WS) dir = h.wdir;        // (world_slot: the escaping segment's own direction, first path or not)
     else dir = v3{ first ? h.ipos.x : dir.x, first ? h.ipos.y : dir.y, first ? h.ipos.z : dir.z };
     n_paths = first ? 0u : n_paths;
     item = first ? f2u(h.Tr) : item;
