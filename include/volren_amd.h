@@ -195,10 +195,21 @@ int vr_denoised(vr_renderer* r, float* rgba_out);
  *     vr_denoise_history waits and writes the history: the blended colour (W*H*4), the blended variance of the mean's luminance (W*H) and the number of
  *     frames behind each pixel (W*H), row 0 at the bottom; any pointer may be NULL; VR_ERR while there is no history.
  *     vr_set_float / vr_get_float "denoise_alpha"(1: the smallest weight of the current frame, in [2^-20, 1]: VR_ERR otherwise, the old value kept;
- *     default 0.1). */
+ *     default 0.1).
+ *     History rejection, off by default.  The tests above compare what a pixel shows, never its colour: after a change of the lighting or of the volume
+ *     the history lags by 1 / "denoise_alpha" frames.  vr_set_float / vr_get_float "denoise_reject"(1: the threshold tau; 0 = off, the default, and then
+ *     every launch and result is what it is without this paragraph; otherwise in [2^-10, 2^20]: anything else, NaN included, is VR_ERR, the old value
+ *     kept).  With tau > 0 a pixel with a history forms z2 = (luma(history) - luma(frame))^2 / (V_history + v + 1e-12), whose expectation is 1 while
+ *     nothing changed, and T = the mean of z2 over the pixels of its 5x5 neighbourhood that lie in the frame and have a history; unless T <= tau
+ *     (a NaN fails) the pixel starts afresh like one without a history: C = frame, V = v, N = 1.  3 is a good tau: under 1 % of the pixels of an unchanged
+ *     scene.  Two limits: the frames need n >= 2 samples per pixel (with n = 1 the variance v is 0 and whatever changed at all is rejected), and the floor
+ *     1e-12 assumes radiances far above 1e-6.  Costs one scratch buffer of W*H*8 floats, allocated like the others before anything is launched.
+ *     vr_denoise_reject_stat waits and writes W*H floats, row 0 at the bottom: T of the last vr_denoise_temporal, -1 where the pixel had no history;
+ *     VR_ERR unless the last vr_denoise_temporal since the resize ran with "denoise_reject" > 0. */
 int vr_denoise_temporal(vr_renderer* r);
 int vr_denoise_history_reset(vr_renderer* r);
 int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* length_out);
+int vr_denoise_reject_stat(vr_renderer* r, float* out);
 /* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
  *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
  *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the
@@ -259,8 +270,8 @@ int vr_unpack_tiles(vr_renderer* r, const int32_t* tile_ids_device, int n_tiles,
  *     features of its own tiles (three float4 per pixel), moves them to part 0 in ONE exchange on the transport above (3x the colour's size; its
  *     buffers are allocated by the first call, a caller that only renders pays nothing) and scatters them into part 0's moments and features.
  *     vr_sharded_denoise / vr_sharded_denoise_temporal do that and then run vr_denoise / vr_denoise_temporal's filter on part 0 over the whole frame,
- *     with part 0's "denoise_iterations", "denoise_sigma", "denoise_alpha" and camera: bit-identical to the single-device calls.  Results are read
- *     from part 0: vr_denoised, vr_features, vr_variance (both after a gather), vr_denoise_history on vr_sharded_part(s, 0); the temporal history lives
+ *     with part 0's "denoise_iterations", "denoise_sigma", "denoise_alpha", "denoise_reject" and camera: bit-identical to the single-device calls.  Results are read
+ *     from part 0: vr_denoised, vr_features, vr_variance (both after a gather), vr_denoise_history and vr_denoise_reject_stat on vr_sharded_part(s, 0); the temporal history lives
  *     in part 0 and vr_denoise_history_reset on part 0 drops it.  All three are asynchronous, and a sequence reset, render, render_features, denoise per
  *     frame needs no synchronisation between frames.  VR_ERR, before anything is launched and with a message that names the part, unless all parts agree
  *     on the resolution and "sample", "sample" >= 1, and every part that owns tiles has moments that cover samples 1..n, a feature pass since the last

@@ -1,0 +1,98 @@
+// tests/hostkernel/reject_host.cpp -- TEST HARNESS ONLY, never part of the product.
+//
+// The temporal accumulation with its history rejection (volren_amd/csrc/vr_temporal.h, steps 2a and 3a) compiled for the host, in the two passes the
+// HIP kernels make (vr_filters.hip denoise_temporal_fetch_kernel, denoise_temporal_resolve_kernel): tests/test_reject_host.py checks it against a
+// float64 numpy statement of the rules (tests/hk_reject.py), and tests/test_gpu_reject.py checks the kernels against it bit for bit.
+// A camera is 13 floats: cam_pos (3), cam_transform (9, column-major), cam_z.
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../volren_amd/csrc/vr_temporal.h"
+
+using namespace vr;
+
+namespace {
+// every read of the history and of the window goes through here: an index outside [0, n) is counted and not dereferenced (bad = nullptr: not checked)
+struct Range {
+    int64_t n;
+    int64_t* bad;
+    bool ok(int64_t i) const { if (!bad || (i >= 0 && i < n)) return true; ++*bad; return false; }
+};
+struct HostHist {
+    const float* c;      // W*H*4
+    const float* s;      // W*H*4: (V, N, K, D)
+    Range range;
+    void color(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? c[4 * (size_t)i + k] : 0.0f; }
+    void record(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? s[4 * (size_t)i + k] : 0.0f; }
+};
+// the window of pixel (px, py) over the whole frame's z2 / has planes (the kernel's LDS footprint holds the same words)
+struct HostWindow {
+    const float* z2;
+    const uint8_t* has;
+    int32_t W, H, px, py;
+    Range range;
+    float word(int32_t dx, int32_t dy) const {
+        const int32_t x = px + dx, y = py + dy;
+        if (x < 0 || x >= W || y < 0 || y >= H) return kTemporalNoHistory;
+        const int64_t i = (int64_t)y * W + x;
+        if (!range.ok(i)) return kTemporalNoHistory;
+        return temporal_window_word(has[i] != 0, z2[i]);
+    }
+};
+TemporalCamera camera_of(const float* p) {
+    TemporalCamera c;
+    std::memcpy(c.pos, p, 3 * sizeof(float));
+    std::memcpy(c.m, p + 3, 9 * sizeof(float));
+    c.cam_z = p[12];
+    return c;
+}
+int64_t step_frame(bool checked, int W, int H, int have, int same_cam, const float* cur, const float* prev, const float* color, const float* v, const float* k,
+                   const float* d, const float* hist_color, const float* hist_record, float alpha, float tau, float* out_color, float* out_record, float* out_stat) {
+    int64_t bad = 0;
+    const Range range{ (int64_t)W * H, checked ? &bad : nullptr };
+    const TemporalCamera cc = camera_of(cur), pc = camera_of(prev);
+    const size_t n = (size_t)W * H;
+    std::vector<float> h(4 * n), vh(n), nh(n), z2(n);
+    std::vector<uint8_t> has(n);
+    const HostHist hist{ hist_color, hist_record, range };
+    for (int y = 0; y < H; ++y)                           // the fetch
+        for (int x = 0; x < W; ++x) {
+            const size_t i = (size_t)y * W + x;
+            has[i] = temporal_fetch(hist, have != 0, same_cam != 0, cc, pc, W, H, x, y, k[i], d[i], &h[4 * i], vh[i], nh[i]) ? 1 : 0;
+            z2[i] = has[i] ? temporal_z2(&h[4 * i], vh[i], color + 4 * i, v[i]) : 0.0f;
+        }
+    for (int y = 0; y < H; ++y)                           // the resolve
+        for (int x = 0; x < W; ++x) {
+            const size_t i = (size_t)y * W + x;
+            float T = kTemporalNoHistory;
+            if (has[i]) T = temporal_pool(HostWindow{ z2.data(), has.data(), W, H, x, y, range });
+            temporal_blend(has[i] && !temporal_rejects(T, tau), &h[4 * i], vh[i], nh[i], color + 4 * i, v[i], k[i], d[i], alpha, out_color + 4 * i, out_record + 4 * i);
+            out_stat[i] = T;
+        }
+    return bad;
+}
+}  // namespace
+
+extern "C" {
+
+// out = (smallest tau, largest tau, variance floor, window radius, the statistic of a pixel without history)
+void hk_reject_constants(float* out) {
+    out[0] = kTemporalRejectMin; out[1] = kTemporalRejectMax; out[2] = kTemporalVarianceFloor; out[3] = (float)kTemporalWindow; out[4] = kTemporalNoHistory;
+}
+
+// steps 1-4 with 2a and 3a of a whole frame, tau > 0: color W*H*4, v / k / d W*H, the history (hist_color, hist_record W*H*4; read only if have) -> the
+// new history and the statistic T (W*H; -1 without history)
+void hk_reject_step(int W, int H, int have, int same_cam, const float* cur, const float* prev, const float* color, const float* v, const float* k, const float* d,
+                    const float* hist_color, const float* hist_record, float alpha, float tau, float* out_color, float* out_record, float* out_stat) {
+    step_frame(false, W, H, have, same_cam, cur, prev, color, v, k, d, hist_color, hist_record, alpha, tau, out_color, out_record, out_stat);
+}
+
+// the same with every history and window read behind a range check: returns the number of reads outside the frame (0 is the only right answer)
+int64_t hk_reject_step_checked(int W, int H, int have, int same_cam, const float* cur, const float* prev, const float* color, const float* v, const float* k,
+                               const float* d, const float* hist_color, const float* hist_record, float alpha, float tau, float* out_color, float* out_record,
+                               float* out_stat) {
+    return step_frame(true, W, H, have, same_cam, cur, prev, color, v, k, d, hist_color, hist_record, alpha, tau, out_color, out_record, out_stat);
+}
+
+}

@@ -379,6 +379,7 @@ FloatField float_field(vr::RendererHIP& R, const std::string& n) {
     if (n == "volume_transform") { if (!R.volume) throw std::runtime_error("no volume"); return { R.volume->transform.m, 16 }; }
     if (n == "denoise_sigma") return { R.denoise_sigma, 5 };
     if (n == "denoise_alpha") return { &R.denoise_alpha, 1 };
+    if (n == "denoise_reject") return { &R.denoise_reject, 1 };
     throw std::runtime_error("unknown float parameter: " + n);
 }
 }  // namespace
@@ -404,6 +405,8 @@ int vr_set_float(vr_renderer* r, const char* name, const float* values, int coun
         }
         if (n == "denoise_alpha" && count == 1 && !(values[0] >= vr::kTemporalAlphaMin && values[0] <= vr::kTemporalAlphaMax))      // vr_temporal.h
             throw std::runtime_error("denoise_alpha must be in [2^-20, 1]");
+        if (n == "denoise_reject" && count == 1 && !(values[0] == 0.0f || (values[0] >= vr::kTemporalRejectMin && values[0] <= vr::kTemporalRejectMax)))
+            throw std::runtime_error("denoise_reject must be 0 (off) or in [2^-10, 2^20]");
         const FloatField f = float_field(R, n);
         if (count != f.count) throw std::runtime_error("wrong value count for " + n);
         memcpy(f.ptr, values, sizeof(float) * (size_t)count);
@@ -491,6 +494,12 @@ int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* l
     NEED(r);
     if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
     return guard([&] { use_device(r); r->impl.download_history(rgba_out, var_out, length_out); });
+}
+int vr_denoise_reject_stat(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.download_reject_stat(out); });
 }
 int vr_denoised(vr_renderer* r, float* out) {
     NEED(r);

@@ -9,6 +9,7 @@
 // Addition: --denoise keeps the per-pixel variance, runs the feature pass (min(spp, 16) samples) and the a-trous denoiser (vr_denoise.h) after every
 // frame and writes the tonemapped denoised frame instead of the raw one (one device only).  --denoise-temporal does the same through
 // denoise_temporal (vr_temporal.h): the history is kept across the frames of the run, so every frame after the first is blended with the ones before it.
+// --denoise-reject T with it: a pixel whose history disagrees with its frame beyond the noise of the two starts afresh (vr_temporal.h 2a, 3a; refused alone).
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
 // the mean samples per pixel; combines with --denoise (one device only).
 //
@@ -123,7 +124,7 @@ static void parse_cmd(int argc, char** argv) {
         } else if (arg == "--vol_crop_min") { renderer->vol_clip_min.x = a.nextf(); renderer->vol_clip_min.y = a.nextf(); renderer->vol_clip_min.z = a.nextf(); }
         else if (arg == "--vol_crop_max") { renderer->vol_clip_max.x = a.nextf(); renderer->vol_clip_max.y = a.nextf(); renderer->vol_clip_max.z = a.nextf(); }
         else if (arg == "--seed") renderer->seed = a.nexti();                        // addition
-        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive") a.next();  // consumed earlier
+        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject") a.next();  // consumed earlier
         else if (fs::is_regular_file(arg) || fs::is_directory(arg)) handle_path(arg);
     }
 }
@@ -165,7 +166,8 @@ int main(int argc, char** argv) {
     }
     int width = 1280, height = 720, device = 0, gpus = 0;        // cppgl ContextParameters defaults (unverified): always pass -w/-h
     bool denoise = false, temporal = false, adaptive = false;      // temporal: --denoise with the history kept across the frames of the run
-    float threshold = 0.f;
+    float threshold = 0.f, reject = 0.f;      // reject: --denoise-reject, the history rejection threshold of --denoise-temporal (0 = off)
+    bool reject_given = false;
     std::vector<int> devices;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -177,13 +179,20 @@ int main(int argc, char** argv) {
             else if (arg == "--devices" && i + 1 < argc) devices = parse_int_list(argv[++i]);
             else if (arg == "--denoise") denoise = true;
             else if (arg == "--denoise-temporal") denoise = temporal = true;
-            else if (arg == "--adaptive") {
+            else if (arg == "--denoise-reject") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --denoise-reject");
+                reject_given = true;
+                reject = std::stof(argv[++i]);
+                if (!(reject == 0.f || (reject >= kTemporalRejectMin && reject <= kTemporalRejectMax)))
+                    throw std::runtime_error("--denoise-reject: the threshold must be 0 (off) or in [2^-10, 2^20]");
+            } else if (arg == "--adaptive") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --adaptive");
                 adaptive = true;
                 threshold = std::stof(argv[++i]);
                 if (!(threshold >= 0.f) || !std::isfinite(threshold)) throw std::runtime_error("--adaptive: the threshold must be finite and >= 0");
             }
         }
+        if (reject_given && !temporal) throw std::runtime_error("--denoise-reject needs --denoise-temporal: it rejects the history that only that call keeps");
         if (adaptive && (gpus > 0 || devices.size() > 1))
             throw std::runtime_error("--adaptive renders on one device only: drop --gpus / --devices (the sharded renderer has no adaptive sampling)");
         if (denoise && (gpus > 0 || devices.size() > 1))
@@ -213,6 +222,7 @@ int main(int argc, char** argv) {
             }
             renderer->reset();
             if (denoise) renderer->variance = 1;        // the denoiser's variance input: kept from sample 1 of every frame
+            renderer->denoise_reject = reject;
             parts.push_back(renderer);
         }
         renderer = parts[0];                            // holds the whole frame after the gather

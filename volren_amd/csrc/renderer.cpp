@@ -61,6 +61,7 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     moments_.reset(); moments_n_ = -1;
     dn_guide_.reset(); dn_var_[0].reset(); dn_var_[1].reset(); dn_color_[0].reset(); dn_color_[1].reset(); denoised_.reset();
     drop_history();
+    dn_reject_.reset(); reject_stat_ = false;
     drop_tile_samples(); tile_n_dev_.reset(); adaptive_lists_.reset(); adaptive_err_.reset();
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
@@ -942,7 +943,9 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error(me + "denoise_iterations out of range");
     const size_t px = (size_t)W * H;
     const int to = hist_cur_ < 0 ? 0 : 1 - hist_cur_;      // the half of the history pair this call writes
+    const bool reject = temporal && denoise_reject > 0.0f;      // vr_temporal.h steps 2a, 3a: the fetch / resolve pair instead of the one kernel
     if (temporal) { ensure_buffer(hist_color_[to], px * 4 * sizeof(float)); ensure_buffer(hist_record_[to], px * 4 * sizeof(float)); }
+    if (reject) ensure_buffer(dn_reject_, px * 8 * sizeof(float));
     ensure_buffer(dn_guide_, px * 8 * sizeof(float));
     ensure_buffer(dn_var_[0], px * sizeof(float));
     ensure_buffer(denoised_, px * 4 * sizeof(float));
@@ -961,10 +964,16 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         cur.cam_z = camera_z(camera.fov_degree);
         const bool have = hist_cur_ >= 0;
         const bool same = have && memcmp(&cur, &hist_cam_, sizeof cur) == 0;
-        launch_denoise_temporal(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), have ? hist_color_[hist_cur_]->as<float>() : nullptr,
-                                have ? hist_record_[hist_cur_]->as<float>() : nullptr, same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha,
-                                hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
+        const float* hc = have ? hist_color_[hist_cur_]->as<float>() : nullptr;
+        const float* hr = have ? hist_record_[hist_cur_]->as<float>() : nullptr;
+        if (reject)
+            launch_denoise_temporal_reject(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H,
+                                           denoise_alpha, denoise_reject, dn_reject_->as<float>(), hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
+        else
+            launch_denoise_temporal(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha,
+                                    hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
         VR_HIP(hipGetLastError());
+        reject_stat_ = reject;
         hist_cur_ = to;
         hist_cam_ = cur;
         first = hist_color_[to].get();
@@ -1000,6 +1009,16 @@ void RendererHIP::download_history(float* rgba, float* var, float* length) {
         if (var) var[i] = rec[4 * i];
         if (length) length[i] = rec[4 * i + 1];
     }
+}
+
+void RendererHIP::download_reject_stat(float* out) {
+    if (!reject_stat_) throw std::runtime_error("denoise_reject_stat: the last denoise_temporal since the resize did not run with denoise_reject > 0");
+    flush_pending();
+    const size_t px = (size_t)resolution.x * resolution.y;
+    std::vector<float> rec(px * 4);      // the scratch's second half, (T, N_h, z2, has) per pixel
+    VR_HIP(hipMemcpyAsync(rec.data(), dn_reject_->as<float>() + px * 4, rec.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < px; ++i) out[i] = rec[4 * i];
 }
 
 void RendererHIP::download_denoised(float* rgba) {

@@ -150,6 +150,7 @@ struct RendererHIP {
     float denoise_sigma[5] = { kDenoiseDefaultSigma[0], kDenoiseDefaultSigma[1], kDenoiseDefaultSigma[2], kDenoiseDefaultSigma[3], kDenoiseDefaultSigma[4] };
                                                       // edge-stopping widths: colour, normal, depth, coverage, albedo (vr_denoise.h)
     float denoise_alpha = kTemporalDefaultAlpha;      // smallest weight of the current frame in denoise_temporal()'s blend, in [2^-20, 1] (vr_temporal.h)
+    float denoise_reject = 0.0f;                      // threshold tau of denoise_temporal()'s history rejection (vr_temporal.h 2a, 3a): 0 = off, or in [2^-10, 2^20]
     bool fast_math = false;                           // opt-in tolerance mode: hardware log/sin/cos/rcp instead of the specified arithmetic
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
                                                       // with one bound the renderer refuses it: DESIGN.md 3)
@@ -184,11 +185,15 @@ struct RendererHIP {
     // depth from the camera of the call before (once per frame; frames of equal spp).  Whatever denoise() accepts, this accepts.  The history is created
     // by the first call, dropped by resize and drop_history, and kept across everything else; denoise() neither reads nor writes it.
     // download_history: integrated colour W*H*4, integrated variance W*H, length W*H (any may be null); throws while there is no history.
+    // With denoise_reject > 0 a pixel whose history disagrees with the frame beyond the noise of the two starts afresh (other kernels, one scratch buffer
+    // more; 0 is today's call exactly).  download_reject_stat: W*H statistics T of the last denoise_temporal(), -1 where the pixel had no history; throws
+    // unless the last denoise_temporal() since the resize ran with denoise_reject > 0.
     // Several devices: ShardedRenderer::denoise / denoise_temporal (sharded.h); called on a part directly, these refuse the part's tile subset.
     void denoise();
     void denoise_temporal();
     void drop_history();
     void download_history(float* rgba, float* var, float* length);
+    void download_reject_stat(float* out);
     void download_denoised(float* rgba);
     const DeviceBuffer* denoised() const { return denoised_.get(); }
     // copy + tonemap of a W*H*4 buffer into `display` (draw() = draw_from(*color) after the flush)
@@ -267,6 +272,8 @@ private:
     DeviceBufferPtr hist_color_[2], hist_record_[2];   // denoise_temporal(): the history, a ping-pong pair of W*H*4 colours and W*H*4 (V, N, K, D) records
     int hist_cur_ = -1;                                // the half that holds the history (-1: none)
     TemporalCamera hist_cam_{};                        // the camera of the frame that wrote it
+    DeviceBufferPtr dn_reject_;                        // denoise_temporal() with denoise_reject > 0: the scratch between its two kernels, W*H*8 (dropped by resize)
+    bool reject_stat_ = false;                         // dn_reject_ holds the statistic of the last denoise_temporal()
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     std::vector<hipEvent_t> pt_events_;                // (begin, end) around the path-tracing kernel of every sub-launch
     size_t pt_events_used_ = 0;

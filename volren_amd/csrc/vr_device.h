@@ -71,6 +71,12 @@ void launch_denoise_atrous(const float* cin, const float* vin, const float* guid
 void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
                              const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
                              hipStream_t stream);
+// The same with the rejection test of threshold tau > 0 (vr_temporal.h steps 2a, 3a): two kernels with `scratch` between them, W*H*8 floats that no
+// other argument overlaps: W*H*4 of h, then W*H*4 of (v_h, N_h, z2, has).  Afterwards the first word of each of the latter holds the pixel's
+// statistic T, -1 where the pixel had no history.
+void launch_denoise_temporal_reject(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
+                                    const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float tau, float* scratch,
+                                    float* out_color, float* out_record, hipStream_t stream);
 // Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,

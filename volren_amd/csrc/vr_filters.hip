@@ -104,6 +104,82 @@ void launch_denoise_temporal(const float* color, float* v, const float* guide, c
                        have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
 }
 
+// The same with the rejection test (vr_temporal.h steps 2a, 3a; tau > 0 only), as two kernels, because a pixel's decision needs the z2 of its 5 x 5
+// neighbours.  Between them lies a scratch pair of W*H float4 each: h, and (v_h, N_h, z2, has).
+// fetch: today's gather (52 B in, up to four taps), then z2; writes the two dwordx4 of the scratch.
+// resolve: stages the window words of the tile's 20 x 20 footprint (16 x 16 plus a halo of 2, one dwordx2 load per pixel, "no history" off the frame)
+// in 1600 B of LDS, one barrier -- threads outside the frame stage and wait with the others -- then sums its 25 words from LDS, blends, and writes
+// the new history and v where denoise_temporal_kernel writes them.  The statistic T (-1 without a history) goes over the pixel's v_h word, which only
+// this thread reads: the z2 and has words are read by the neighbouring tiles' staging, at no fixed time, so they stay as they are.  No atomics.
+constexpr int32_t kRejectFoot = 16 + 2 * kTemporalWindow;      // edge of a tile's footprint in pixels
+struct TemporalWindowDev {
+    const float* win;      // the staged footprint
+    int32_t at;            // the pixel's own word in it
+    __device__ __forceinline__ float word(int32_t dx, int32_t dy) const { return win[at + dy * kRejectFoot + dx]; }
+};
+__global__ void __launch_bounds__(256)
+denoise_temporal_fetch_kernel(const float4* __restrict__ color, const float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ hc,
+                              const float4* __restrict__ hs, int32_t have, int32_t same_cam, const TemporalCamera cur, const TemporalCamera prev, int32_t W,
+                              int32_t H, float4* __restrict__ sh, float4* __restrict__ sr) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float c[4];
+    unpack4(color[i], c);
+    const TemporalHistDev hist{ hc, hs };
+    float h[4], vh, nh;
+    const bool has = temporal_fetch(hist, have != 0, same_cam != 0, cur, prev, W, H, q.px, q.py, guide[2 * i].w, guide[2 * i + 1].w, h, vh, nh);
+    const float z2 = has ? temporal_z2(h, vh, c, v[i]) : 0.0f;
+    sh[i] = pack4(h);
+    sr[i] = make_float4(vh, nh, z2, has ? 1.0f : 0.0f);
+}
+__global__ void __launch_bounds__(256)
+denoise_temporal_resolve_kernel(const float4* __restrict__ color, float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ sh,
+                                float4* sr, int32_t W, int32_t H, float alpha, float tau, float4* __restrict__ oc, float4* __restrict__ os) {
+    __shared__ float win[kRejectFoot * kRejectFoot];
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    const int32_t nx = tiles_x(W);
+    const int32_t x0 = ((int32_t)blockIdx.x % nx) * 16 - kTemporalWindow, y0 = ((int32_t)blockIdx.x / nx) * 16 - kTemporalWindow;
+    for (int32_t f = (int32_t)threadIdx.x; f < kRejectFoot * kRejectFoot; f += 256) {
+        const int32_t x = x0 + f % kRejectFoot, y = y0 + f / kRejectFoot;
+        float word = kTemporalNoHistory;
+        if (x >= 0 && x < W && y >= 0 && y < H) {
+            const float2 zh = *reinterpret_cast<const float2*>(&sr[y * W + x].z);
+            word = temporal_window_word(zh.y != 0.0f, zh.x);
+        }
+        win[f] = word;
+    }
+    __syncthreads();
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float c[4], h[4];
+    unpack4(color[i], c);
+    unpack4(sh[i], h);
+    const float4 r = sr[i];
+    const bool has = r.w != 0.0f;
+    float T = kTemporalNoHistory;
+    if (has) T = temporal_pool(TemporalWindowDev{ win, (q.py - y0) * kRejectFoot + (q.px - x0) });
+    float C[4], S[4];
+    temporal_blend(has && !temporal_rejects(T, tau), h, r.x, r.y, c, v[i], guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S);
+    oc[i] = pack4(C);
+    os[i] = pack4(S);
+    v[i] = S[0];
+    sr[i].x = T;
+}
+void launch_denoise_temporal_reject(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
+                                    const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float tau, float* scratch,
+                                    float* out_color, float* out_record, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    const bool have = hist_color && hist_record;
+    float4* sh = reinterpret_cast<float4*>(scratch);
+    float4* sr = sh + (size_t)W * H;
+    hipLaunchKernelGGL(denoise_temporal_fetch_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
+                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
+                       have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, sh, sr);
+    hipLaunchKernelGGL(denoise_temporal_resolve_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
+                       reinterpret_cast<const float4*>(guide), sh, sr, W, H, alpha, tau, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
+}
+
 // Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile; each lane forms e_p of its pixel (-inf outside
 // the frame: the identity of the max), a wave64 max by xor shuffles, the four waves' maxima through LDS, and lane 0 writes the tile's value.
 // Max is exact, so the order of the reduction does not matter.

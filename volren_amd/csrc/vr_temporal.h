@@ -2,8 +2,8 @@
 //
 // The temporal part of SVGF (Schied et al. 2017): before the spatial filter of vr_denoise.h runs, the current frame is blended with a history
 // of the frames before it, fetched where the pixel's first-scatter point lay on the screen of the frame that wrote the history.  Per-pixel
-// functions only: the HIP kernel (vr_filters.hip denoise_temporal_kernel) and the host build of the tests (tests/hostkernel/temporal_host.cpp)
-// run the same code, so the two agree bit for bit.  The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division,
+// functions only: the HIP kernels (vr_filters.hip denoise_temporal_kernel; with rejection denoise_temporal_fetch_kernel and
+// denoise_temporal_resolve_kernel) and the host builds of the tests (tests/hostkernel/temporal_host.cpp, reject_host.cpp) run the same code, so the two agree bit for bit.  The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division,
 // sqrt_, floor_); a * b + c below is two roundings unless it is written as one of vr_math.h's dot / mat3_mul / axpy, which are fma chains.
 // A participating medium has no surface: the "depth" is the mean first-scatter distance along the pixel's centre ray.
 //
@@ -25,9 +25,18 @@
 //    0.1 is kDenoiseDefaultSigma's depth width used as a hard bound.  Comparisons with NaN are false, so a NaN depth has no history.
 //    sum b over the taps that count < 2^-10: no history.  Otherwise h = (sum b C_q) / sum b per channel, v_h = (sum b V_q) / sum b, each sum
 //    from 0 in tap order, and N_h = the smallest N_q of the taps that count.
+//  2a The pixel against its history (only with a rejection threshold tau > 0, off by default).  A pixel with a history gets the squared z-score
+//      dl = luma(h.rgb) - luma(c.rgb), z2 = (dl * dl) / ((v + v_h) + 1e-12)
+//    of the two estimates of its luminance: v and v_h are the variances of the two, so z2 has expectation 1 while the scene did not change.
+//    luma is vr_math.h's, the division IEEE.  A frame of n = 1 samples has v = 0 and rejects whatever changed at all: the test needs n >= 2.
+//    The floor 1e-12 assumes radiances far above 1e-6.
 //  3 Unchanged camera.  If pos, M and cam_z equal the history's byte for byte (decided by the caller from what it can see, not an option), step 1
 //    is skipped: u = px, w = py, d' = d, so the one tap with b > 0 is (px, py) with b = 1 and h = C_q exactly.  No resampling blur builds up
 //    under a fixed camera.
+//  3a Rejection (tau > 0 only), at a pixel p with a history: T = (sum z2_q) / count over the pixels q = p + (dx, dy), dx and dy in -2 .. 2, dy outer,
+//    dx inner, that lie inside the frame and have a history; the sum from 0, count a float, p itself among them.  The pixel is rejected iff
+//    !(T <= tau) -- a NaN rejects -- and is from here on a pixel without history.  One z2 is too noisy to threshold; the mean of up to 25 is not.
+//    In the window a pixel stands as one word, its z2 or -1 for "no history or off the frame": variances are >= 0, so no z2 is negative.
 //  4 Blend.  No history: C = c, V = v, N = 1.  Otherwise N = min(N_h + 1, 2^20), a = max_(alpha, 1 / N), oma = 1 - a,
 //      C = oma * h + a * c per channel, V = (oma * oma) * v_h + (a * a) * v.   (C, V, N, k, d) is the new history.
 //  5 The a-trous iterations of vr_denoise.h then run unchanged from (C, V) with the current frame's guide; with 0 iterations the result is C.
@@ -47,6 +56,10 @@ constexpr float kTemporalAlphaMin = 0x1p-20f, kTemporalAlphaMax = 1.0f;      // 
 constexpr float kTemporalDepthBound = 0.1f;           // relative depth difference a tap may have (kDenoiseDefaultSigma[2] as a hard bound)
 constexpr float kTemporalMinWeight = 0x1p-10f;        // smallest sum of bilinear weights that still is a history
 constexpr float kTemporalMaxLength = 1048576.0f;      // 2^20 frames
+constexpr float kTemporalRejectMin = 0x1p-10f, kTemporalRejectMax = 0x1p20f;      // the accepted range of "denoise_reject" besides 0 = off
+constexpr float kTemporalVarianceFloor = 1e-12f;      // added to the variance of the difference (radiances far above 1e-6)
+constexpr int32_t kTemporalWindow = 2;                // the rejection statistic pools a (2 * 2 + 1)^2 window
+constexpr float kTemporalNoHistory = -1.0f;           // the statistic, and the window word, of a pixel without a history
 
 // Step 1: where the first-scatter point of pixel (px, py) lay on the history's screen (u, w in pixels, d' its distance from that camera).
 // false: behind that camera (q.z >= 0 or NaN); u, w, d' are not written then.
@@ -74,12 +87,13 @@ VR_HD bool temporal_reproject(const TemporalCamera& cur, const TemporalCamera& p
     return true;
 }
 
-// Steps 1-4 at pixel (px, py).  Hist reads the previous history by pixel index y * W + x:
+// Steps 1-3 at pixel (px, py): the fetch.  Hist reads the previous history by pixel index y * W + x:
 //   void color(int32_t i, float c[4]) const;   void record(int32_t i, float s[4]) const;      (V, N, K, D)
-// have: a history exists; same_cam: its camera equals the current one byte for byte.  Cout / Sout: the pixel's new history.
+// have: a history exists; same_cam: its camera equals the current one byte for byte.  true: the pixel has a history, h, vh, nh are step 2's
+// h, v_h, N_h; false: they are 0.
 template <class Hist>
-VR_HD void temporal_pixel(const Hist& hist, bool have, bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H,
-                          int32_t px, int32_t py, const float c[4], float v, float k, float d, float alpha, float Cout[4], float Sout[4]) {
+VR_HD bool temporal_fetch(const Hist& hist, bool have, bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H,
+                          int32_t px, int32_t py, float k, float d, float h[4], float& vh, float& nh_out) {
     float hs[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     float bs = 0.0f, vs = 0.0f, nh = 0.0f;
     bool any = false;
@@ -114,17 +128,63 @@ VR_HD void temporal_pixel(const Hist& hist, bool have, bool same_cam, const Temp
             }
         }
     }
-    Sout[2] = k; Sout[3] = d;
     if (!any || bs < kTemporalMinWeight) {
+        for (int32_t i = 0; i < 4; ++i) h[i] = 0.0f;
+        vh = 0.0f; nh_out = 0.0f;
+        return false;
+    }
+    for (int32_t i = 0; i < 4; ++i) h[i] = hs[i] / bs;
+    vh = vs / bs;
+    nh_out = nh;
+    return true;
+}
+
+// Step 4 at a pixel: keep = the pixel has a history and it was not rejected; (h, vh, nh) its fetch.  Cout / Sout: the pixel's new history.
+VR_HD void temporal_blend(bool keep, const float h[4], float vh, float nh, const float c[4], float v, float k, float d, float alpha, float Cout[4],
+                          float Sout[4]) {
+    Sout[2] = k; Sout[3] = d;
+    if (!keep) {
         for (int32_t i = 0; i < 4; ++i) Cout[i] = c[i];
         Sout[0] = v; Sout[1] = 1.0f;
         return;
     }
     const float N = min_(nh + 1.0f, kTemporalMaxLength);
     const float a = max_(alpha, 1.0f / N), oma = 1.0f - a;
-    for (int32_t i = 0; i < 4; ++i) Cout[i] = oma * (hs[i] / bs) + a * c[i];
-    Sout[0] = (oma * oma) * (vs / bs) + (a * a) * v;
+    for (int32_t i = 0; i < 4; ++i) Cout[i] = oma * h[i] + a * c[i];
+    Sout[0] = (oma * oma) * vh + (a * a) * v;
     Sout[1] = N;
 }
+
+// Steps 1-4 at pixel (px, py), without the rejection test: the fetch, then the blend.
+template <class Hist>
+VR_HD void temporal_pixel(const Hist& hist, bool have, bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H,
+                          int32_t px, int32_t py, const float c[4], float v, float k, float d, float alpha, float Cout[4], float Sout[4]) {
+    float h[4], vh, nh;
+    const bool has = temporal_fetch(hist, have, same_cam, cur, prev, W, H, px, py, k, d, h, vh, nh);
+    temporal_blend(has, h, vh, nh, c, v, k, d, alpha, Cout, Sout);
+}
+
+// Step 2a at a pixel with a history: the squared z-score of its fetch against the frame.
+VR_HD float temporal_z2(const float h[4], float vh, const float c[4], float v) {
+    const float dl = luma(v3{ h[0], h[1], h[2] }) - luma(v3{ c[0], c[1], c[2] });
+    return (dl * dl) / ((v + vh) + kTemporalVarianceFloor);
+}
+// the word that stands for a pixel in step 3a's window: its z2, or kTemporalNoHistory (the only negative one, variances being >= 0) without a history
+VR_HD float temporal_window_word(bool has, float z2) { return has ? z2 : kTemporalNoHistory; }
+// Step 3a at a pixel with a history.  Win answers  float word(int32_t dx, int32_t dy) const:  the window word of pixel p + (dx, dy),
+// kTemporalNoHistory where that pixel lies outside the frame.  A NaN word counts, and makes T NaN.
+template <class Win>
+VR_HD float temporal_pool(const Win& win) {
+    float sum = 0.0f, count = 0.0f;
+    for (int32_t dy = -kTemporalWindow; dy <= kTemporalWindow; ++dy)
+        for (int32_t dx = -kTemporalWindow; dx <= kTemporalWindow; ++dx) {
+            const float z = win.word(dx, dy);
+            if (z < 0.0f) continue;
+            sum = sum + z;
+            count = count + 1.0f;
+        }
+    return sum / count;
+}
+VR_HD bool temporal_rejects(float T, float tau) { return !(T <= tau); }
 
 }  // namespace vr

@@ -12,7 +12,7 @@ _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemap
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
-                 "volume_transform": 16, "denoise_sigma": 5, "denoise_alpha": 1}
+                 "volume_transform": 16, "denoise_sigma": 5, "denoise_alpha": 1, "denoise_reject": 1}
 
 
 def _f32(a):
@@ -282,6 +282,13 @@ class Renderer:
         _lib.check(self._L.vr_denoise_history(self._h, c.ctypes.data, v.ctypes.data, n.ctypes.data))
         return c, v, n
 
+    def denoise_reject_stat(self):
+        """[H][W] float32, row 0 = bottom: the rejection statistic T of the last denoise_temporal() (a pixel was rejected iff not T <= `denoise_reject`),
+        -1 where the pixel had no history.  Needs `denoise_reject` > 0 at that call."""
+        out = np.empty((self.height, self.width), np.float32)
+        _lib.check(self._L.vr_denoise_reject_stat(self._h, out.ctypes.data))
+        return out
+
     def denoise_history_reset(self):
         """Drops the history: the next denoise_temporal() starts afresh."""
         _lib.check(self._L.vr_denoise_history_reset(self._h))
@@ -497,6 +504,14 @@ class ShardedRenderer:
 
     def denoise_history_reset(self):
         self.parts[0].denoise_history_reset()
+
+    @property
+    def denoise_reject(self):
+        """The rejection threshold the filter runs with: part 0's (set it on `parts[0]`, or on every part with `each`)."""
+        return self.parts[0].denoise_reject
+
+    def denoise_reject_stat(self):
+        return self.parts[0].denoise_reject_stat()
 
 
 def math_probe(fn, a, b=None):
