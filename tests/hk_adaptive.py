@@ -1,15 +1,12 @@
 """ctypes binding of tests/hostkernel/libadaptive_host.so: the adaptive-sampling lane code of the product (vr_adaptive.h) built for the host, plus an
 independent float64 numpy statement of the error estimate and a replay of the schedule.  TEST HARNESS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
+from hk_common import _f32, _p
 
-_DIR = hk_binding._DIR
-_SO = os.path.join(_DIR, "libadaptive_host.so")
 _lib = None
 
 LUMA = (0.212671, 0.715160, 0.072169)
@@ -17,12 +14,7 @@ FLOOR = 2.0 ** -10
 
 
 def build():
-    src = os.path.join(_DIR, "adaptive_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_adaptive.h", "vr_denoise.h", "vr_math.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               "-Wno-unknown-pragmas", "-Wno-subobject-linkage", "-o", _SO, src])
-    return _SO
+    return hk_common.build(__file__, "adaptive_host.cpp", "libadaptive_host.so", ("-Wno-unknown-pragmas", "-Wno-subobject-linkage"))
 
 
 def lib():
@@ -37,16 +29,6 @@ def lib():
         L.hk_adaptive_groups.restype = C.c_int
         _lib = L
     return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a, shape):
-    a = np.ascontiguousarray(a, np.float32)
-    assert a.shape == shape, (a.shape, shape)
-    return a
 
 
 def tiles_of(w, h):

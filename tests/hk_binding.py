@@ -2,43 +2,22 @@
 TEST HARNESS ONLY -- lets the CPU-only suite check the lane state machine against the oracle."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostkernel")
-_SO = os.path.join(_DIR, "libhostkernel.so")
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import hk_common
 
 
 def build(sanitize=False, fast_tap=False):
     """fast_tap: the device's decision of the stochastic-filter tests (VR_TAP_FAST, vr_trace.h) instead of the reference's loop."""
-    so = _SO if not sanitize else os.path.join(_DIR, "libhostkernel_san.so")
-    if fast_tap:
-        so = os.path.join(_DIR, "libhostkernel_fasttap.so")
-    src = os.path.join(_DIR, "host_kernel.cpp")
-    deps = [src, os.path.join(_DIR, "host_scene.h")] + [os.path.join(_ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h", "env_pack.h")]
-    if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
-        return so
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-           "-Wno-unknown-pragmas", "-o", so, src]
-    if sanitize:
-        cmd[1:1] = ["-fsanitize=undefined", "-fno-sanitize-recover=undefined", "-g"]
-    if fast_tap:
-        cmd[1:1] = ["-DVR_TAP_FAST=1"]
-    subprocess.check_call(cmd)
-    return so
+    assert not (sanitize and fast_tap), "there is no sanitizer build of the fast-tap form"
+    name, extra = ("libhostkernel_san.so", hk_common.UBSAN) if sanitize else ("libhostkernel_fasttap.so", ("-DVR_TAP_FAST=1",)) if fast_tap else ("libhostkernel.so", ())
+    return hk_common.build(__file__, "host_kernel.cpp", name, ("-Wno-unknown-pragmas",) + extra)
 
 
 def build_tricubic_band_tool():
     """tests/tools_tricubic_band.cpp: exhaustive / strided check of the fast filter tests against the reference's."""
-    exe = os.path.join(_DIR, "tricubic_band")
-    src = os.path.join(os.path.dirname(_DIR), "tools_tricubic_band.cpp")
-    deps = [src] + [os.path.join(_ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h")]
-    if not (os.path.exists(exe) and all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2", "-fopenmp",
-                               "-Wno-unknown-pragmas", "-o", exe, src])
-    return exe
+    return hk_common.build(__file__, os.path.join(hk_common.TESTS, "tools_tricubic_band.cpp"), "tricubic_band", ("-fopenmp", "-Wno-unknown-pragmas"), shared=False)
 
 
 class GridDesc(C.Structure):

@@ -1,15 +1,12 @@
 """ctypes binding of tests/hostkernel/libdenoise_host.so: the a-trous denoiser of the product's lane code (vr_denoise.h) built for the host, plus
 an independent float64 numpy statement of the same filter.  TEST HARNESS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
+from hk_common import _f32, _p
 
-_DIR = hk_binding._DIR
-_SO = os.path.join(_DIR, "libdenoise_host.so")
 _lib = None
 
 DEFAULT_SIGMA = (4.0, 0.5, 0.1, 0.25, 0.2)          # colour, normal, depth, coverage, albedo
@@ -19,12 +16,7 @@ G3 = (1 / 4, 1 / 2, 1 / 4)
 
 
 def build():
-    src = os.path.join(_DIR, "denoise_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_denoise.h", "vr_math.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               "-Wno-unknown-pragmas", "-Wno-subobject-linkage", "-o", _SO, src])
-    return _SO
+    return hk_common.build(__file__, "denoise_host.cpp", "libdenoise_host.so", ("-Wno-unknown-pragmas", "-Wno-subobject-linkage"))
 
 
 def lib():
@@ -39,16 +31,6 @@ def sigma_range():
     r = np.zeros(2, np.float32)
     lib().hk_denoise_sigma_range(_p(r))
     return float(r[0]), float(r[1])
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a, shape):
-    a = np.ascontiguousarray(a, np.float32)
-    assert a.shape == shape, (a.shape, shape)
-    return a
 
 
 def denoise(color, var, feat, n, iterations=5, sigma=DEFAULT_SIGMA):

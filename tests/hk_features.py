@@ -1,25 +1,17 @@
 """ctypes binding of tests/hostkernel/libfeatures_host.so: the denoiser feature pass of the product's lane code (vr_trace.h feature_sample /
 feature_pixel) built for the host, plus float64 numpy references.  TEST HARNESS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import hk_binding
+import hk_common
 
-_DIR = hk_binding._DIR
-_SO = os.path.join(_DIR, "libfeatures_host.so")
 _lib = None
 
 
 def build():
-    src = os.path.join(_DIR, "features_host.cpp")
-    deps = [src, os.path.join(_DIR, "host_kernel.cpp")] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               "-Wno-unknown-pragmas", "-Wno-subobject-linkage", "-o", _SO, src])
-    return _SO
+    return hk_common.build(__file__, "features_host.cpp", "libfeatures_host.so", ("-Wno-unknown-pragmas", "-Wno-subobject-linkage"))
 
 
 def lib():

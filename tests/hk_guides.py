@@ -1,25 +1,16 @@
 """ctypes binding of tests/hostkernel/libguides_host.so: the wire format of the sharded renderer's packed denoiser guides (vr_tiles.h guide_slot)
 built for the host.  TEST HARNESS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
 
-_DIR = hk_binding._DIR
-_SO = os.path.join(_DIR, "libguides_host.so")
 _lib = None
 
 
 def build():
-    src = os.path.join(_DIR, "guides_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_tiles.h", "vr_math.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               "-Wno-unknown-pragmas", "-o", _SO, src])
-    return _SO
+    return hk_common.build(__file__, "guides_host.cpp", "libguides_host.so", ("-Wno-unknown-pragmas",))
 
 
 def lib():

@@ -1,27 +1,17 @@
 """ctypes binding of tests/hostkernel/libhotpair_host*.so: collide_finish (vr_trace.h) built for the host, with and without the shortcut for blocked
 shadow rays; the gathers' two addressing forms and the rule that chooses between them.  TEST HARNESS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
 
-_DIR = hk_binding._DIR
 _libs = {}
 
 
 def build(shortcut=True):
-    so = os.path.join(_DIR, "libhotpair_host.so" if shortcut else "libhotpair_host_noshortcut.so")
-    src = os.path.join(_DIR, "hotpair_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h")]
-    if not (os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps)):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2", "-Wno-unknown-pragmas", "-o", so, src]
-        if not shortcut:
-            cmd[1:1] = ["-DVR_SHADOW_BLOCKED_SHORTCUT=0"]
-        subprocess.check_call(cmd)
-    return so
+    return hk_common.build(__file__, "hotpair_host.cpp", "libhotpair_host.so" if shortcut else "libhotpair_host_noshortcut.so",
+                           ("-Wno-unknown-pragmas",) + (() if shortcut else ("-DVR_SHADOW_BLOCKED_SHORTCUT=0",)))
 
 
 def lib(shortcut=True):

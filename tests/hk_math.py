@@ -3,16 +3,13 @@ vr_math_probe.h, a float64 libm reference for the accuracy tests, and the input 
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
 
-_DIR = hk_binding._DIR
-_SO = os.path.join(_DIR, "libmath_host.so")
 _lib = None
-ACCURACY_JSON = os.path.join(os.path.dirname(_DIR), "golden", "math_accuracy.json")
+ACCURACY_JSON = os.path.join(hk_common.TESTS, "golden", "math_accuracy.json")
 
 # probe codes (volren_amd/csrc/vr_math_probe.h)
 LOG, SIN, COS, TAN, ACOS, ATAN2, EXP, POW, ASIN = range(9)
@@ -29,12 +26,7 @@ LIVE = " on [0, 2 pi]"            # suffix of the recorded entries of sincos_ on
 
 
 def build():
-    src = os.path.join(_DIR, "math_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_math_probe.h", "vr_math.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2", "-fopenmp",
-                               "-o", _SO, src])
-    return _SO
+    return hk_common.build(__file__, "math_host.cpp", "libmath_host.so", ("-fopenmp",))
 
 
 def lib():
@@ -50,7 +42,8 @@ def lib():
 
 
 def bits(a):
-    """the uint32 view of a 4-byte array (float32 values, or integers carried as bit patterns)"""
+    """the uint32 view of a 4-byte array (float32 values, or integers carried as bit patterns).  Not hk_common.bits: integers keep their bits instead
+    of being converted to float32, and the result is flat."""
     a = np.ascontiguousarray(a)
     if a.dtype.kind == "f" and a.dtype.itemsize != 4:
         a = a.astype(np.float32)

@@ -1,36 +1,32 @@
-"""ctypes binding of tests/hostkernel/libtemporal_host.so: the temporal accumulation of the product's lane code (vr_temporal.h) built for the host,
-a replay of RendererHIP::denoise_temporal on top of it and of the host build of the filter (hk_denoise), plus an independent float64 numpy statement
-of the reprojection, the tap rules and the blend.  TEST HARNESS ONLY.
+"""ctypes binding of tests/hostkernel/libtemporal_host.so: the temporal accumulation of the product's lane code (vr_temporal.h) built for the host, without
+its history rejection and with it (steps 2a, 3a, in the two passes the HIP kernels make); a replay of RendererHIP::denoise_temporal on top of it and of
+the host build of the filter (hk_denoise); plus an independent float64 numpy statement of the reprojection, the tap rules, the blend, the rejection
+statistic and the decision.  TEST HARNESS ONLY.
 
 A camera is 13 float32: cam_pos (3), cam_transform (9, column-major), cam_z."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
 import hk_denoise
+from hk_common import _f32, _p
 
-_DIR = hk_binding._DIR
 _lib = {}
 
 DEPTH_BOUND = 0.1
 MIN_WEIGHT = 2.0 ** -10
 MAX_LENGTH = 2.0 ** 20
+VARIANCE_FLOOR = 1e-12
+WINDOW = 2
+NO_HISTORY = -1.0
+TAU_MIN, TAU_MAX = 2.0 ** -10, 2.0 ** 20
+LUMA = hk_denoise.LUMA                            # vr_math.h luma
 
 
 def build(sanitize=False):
-    so = os.path.join(_DIR, "libtemporal_host_san.so" if sanitize else "libtemporal_host.so")
-    src = os.path.join(_DIR, "temporal_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_temporal.h", "vr_math.h")]
-    if not (os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps)):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-               "-Wno-unknown-pragmas", "-Wno-subobject-linkage", "-o", so, src]
-        if sanitize:
-            cmd[1:1] = ["-fsanitize=undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-g"]
-        subprocess.check_call(cmd)
-    return so
+    return hk_common.build(__file__, "temporal_host.cpp", "libtemporal_host_san.so" if sanitize else "libtemporal_host.so", ("-Wno-unknown-pragmas", "-Wno-subobject-linkage") +
+                           (("-fsanitize=undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-g") if sanitize else ()))
 
 
 def lib(sanitize=False):
@@ -39,25 +35,22 @@ def lib(sanitize=False):
         L = C.CDLL(build(sanitize))
         L.hk_temporal_cam_z.restype = C.c_float
         L.hk_temporal_cam_z.argtypes = [C.c_float]
-        L.hk_temporal_step_checked.restype = C.c_longlong
+        L.hk_temporal_step_checked.restype = L.hk_reject_step_checked.restype = C.c_longlong
         _lib[sanitize] = L
     return _lib[sanitize]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a, shape):
-    a = np.ascontiguousarray(a, np.float32)
-    assert a.shape == shape, (a.shape, shape)
-    return a
 
 
 def constants():
     """(default alpha, smallest alpha, largest alpha, depth bound, smallest weight sum, longest history) of vr_temporal.h"""
     out = np.zeros(6, np.float32)
     lib().hk_temporal_constants(_p(out))
+    return tuple(float(x) for x in out)
+
+
+def reject_constants():
+    """(smallest tau, largest tau, variance floor, window radius, the statistic of a pixel without history) of vr_temporal.h"""
+    out = np.zeros(5, np.float32)
+    lib().hk_reject_constants(_p(out))
     return tuple(float(x) for x in out)
 
 
@@ -83,24 +76,46 @@ def reproject(cur, prev, k, d):
     return u, ww, dp, ok != 0
 
 
-def step(cur, color, v, k, d, alpha, hist=None, checked=False):
-    """Host build of steps 1-4 on a whole frame.  hist: None or (camera, colour [H][W][4], record [H][W][4] = (V, N, K, D)).  Whether the camera is
-    unchanged is decided as the renderer decides it: the 13 floats byte for byte.  -> (colour, record) of the new history.
-    checked: run the sanitizer build with every history read behind a range check; asserts that none fell outside the frame."""
+def _step(name, cur, color, v, k, d, alpha, hist, checked, tau=None):
+    """the call both steps share; T stays 0 without tau"""
     h, w = v.shape
-    fn = lib(True).hk_temporal_step_checked if checked else lib().hk_temporal_step
+    fn = getattr(lib(checked), name + ("_checked" if checked else ""))
     cur = _f32(cur, (13,))
     oc = np.zeros((h, w, 4), np.float32)
     orec = np.zeros((h, w, 4), np.float32)
+    stat = np.zeros((h, w), np.float32)
     if hist is None:
         prev, hc, hr, have, same = cur, oc, orec, 0, 0
     else:
         prev, hc, hr = _f32(hist[0], (13,)), _f32(hist[1], (h, w, 4)), _f32(hist[2], (h, w, 4))
         have, same = 1, int(prev.tobytes() == cur.tobytes())
-    bad = fn(w, h, have, same, _p(cur), _p(prev), _p(_f32(color, (h, w, 4))), _p(_f32(v, (h, w))), _p(_f32(k, (h, w))), _p(_f32(d, (h, w))),
-             _p(hc), _p(hr), C.c_float(float(alpha)), _p(oc), _p(orec))
-    assert not checked or bad == 0, "%d history reads outside the frame" % bad
-    return oc, orec
+    args = [w, h, have, same, _p(cur), _p(prev), _p(_f32(color, (h, w, 4))), _p(_f32(v, (h, w))), _p(_f32(k, (h, w))), _p(_f32(d, (h, w))),
+            _p(hc), _p(hr), C.c_float(float(alpha)), _p(oc), _p(orec)]
+    if tau is not None:                                 # hk_reject_step: tau after alpha, T at the end
+        args[13:13] = [C.c_float(float(tau))]
+        args.append(_p(stat))
+    bad = fn(*args)
+    assert not checked or bad == 0, "%d reads outside the frame" % bad
+    return oc, orec, stat
+
+
+def step(cur, color, v, k, d, alpha, hist=None, checked=False):
+    """Host build of steps 1-4 on a whole frame.  hist: None or (camera, colour [H][W][4], record [H][W][4] = (V, N, K, D)).  Whether the camera is
+    unchanged is decided as the renderer decides it: the 13 floats byte for byte.  -> (colour, record) of the new history.
+    checked: run the sanitizer build with every history read behind a range check; asserts that none fell outside the frame."""
+    return _step("hk_temporal_step", cur, color, v, k, d, alpha, hist, checked)[:2]
+
+
+def step_reject(cur, color, v, k, d, alpha, tau, hist=None, checked=False):
+    """The same with steps 2a and 3a, tau > 0.  -> (colour, record, T [H][W]) of the new history.  checked: the window's reads are range-checked too."""
+    assert tau > 0
+    return _step("hk_reject_step", cur, color, v, k, d, alpha, hist, checked, tau)
+
+
+def rejected(stat, tau):
+    """the pixels with a history that step 3a rejected: not (T <= tau)"""
+    with np.errstate(invalid="ignore"):
+        return (stat != np.float32(NO_HISTORY)) & ~(stat <= np.float32(tau))
 
 
 class Replay:
@@ -108,15 +123,19 @@ class Replay:
 
     def __init__(self):
         self.hist = None
+        self.stat = None                              # T of the last frame; None after a frame with tau = 0
 
-    def frame(self, cur, color, var, feat, n, alpha, iterations=5, sigma=hk_denoise.DEFAULT_SIGMA):
-        """n: the frame's sample count, or [H][W] counts of a ragged frame.  -> (history colour, V, N, denoised)"""
+    def frame(self, cur, color, var, feat, n, alpha, iterations=5, sigma=hk_denoise.DEFAULT_SIGMA, tau=0.0):
+        """n: the frame's sample count, or [H][W] counts of a ragged frame; tau: `denoise_reject`.  -> (history colour, V, N, denoised)"""
         if np.ndim(n) == 0:
             v, g = hk_denoise.prepare(var, feat, n)
         else:
             import hk_adaptive
             v, g = hk_adaptive.prepare(var, feat, n)
-        c, rec = step(cur, color, v, g[..., 3], g[..., 7], alpha, self.hist)
+        if tau > 0:
+            c, rec, self.stat = step_reject(cur, color, v, g[..., 3], g[..., 7], alpha, tau, self.hist)
+        else:
+            (c, rec), self.stat = step(cur, color, v, g[..., 3], g[..., 7], alpha, self.hist), None
         self.hist = (np.array(cur, np.float32), c, rec)
         out, vv = c, np.ascontiguousarray(rec[..., 0])
         for k in range(iterations):
@@ -222,3 +241,36 @@ def spec_step(cur, color, v, k, d, alpha, hist=None, given=None):
     if same:
         u, w = nan, nan
     return C_out, V_out, N_out, u, w, ratios, sum_b
+
+
+# ---- float64 statement of steps 2a and 3a, written from the formulas -----------------------------------------------------------------------------
+def spec_fetch(cur, k, d, hist, given=None):
+    """float64 (has [H][W], h [H][W][4], v_h, N_h [H][W]) of steps 1-3.  The fetch is spec_step's, so the statement is spec_step:
+    blended with a frame of zeros at an alpha below every 1 / N it returns C = (1 - 1 / N) h, V = (1 - 1 / N)^2 v_h and N = N_h + 1 >= 2 where the pixel
+    has a history, and N = 1 where it has none.  (Histories in the tests are shorter than 2^20 - 1 frames, where N stops counting.)"""
+    H, W = np.shape(k)
+    C_, V_, N_ = spec_step(cur, np.zeros((H, W, 4)), np.zeros((H, W)), k, d, 2.0 ** -40, hist, given=given)[:3]
+    has = N_ >= 2
+    oma = np.where(has, 1.0 - 1.0 / N_, 1.0)
+    return has, np.where(has[..., None], C_ / oma[..., None], 0.0), np.where(has, V_ / (oma * oma), 0.0), np.where(has, N_ - 1.0, 0.0)
+
+
+def spec_stat(color, v, has, h, vh):
+    """float64 T [H][W] (-1 without history) from the frame (colour [H][W][4], v) and the fetch"""
+    c = np.asarray(color, np.float64)
+    w = np.asarray(LUMA, np.float64)
+    dl = (h[..., :3] * w).sum(axis=-1) - (c[..., :3] * w).sum(axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z2 = np.where(has, dl * dl / ((np.asarray(v, np.float64) + vh) + VARIANCE_FLOOR), 0.0)
+    H, W = has.shape
+    zs = np.zeros((H + 2 * WINDOW, W + 2 * WINDOW))
+    ns = np.zeros_like(zs)
+    zs[WINDOW:WINDOW + H, WINDOW:WINDOW + W] = z2
+    ns[WINDOW:WINDOW + H, WINDOW:WINDOW + W] = has
+    total, count = np.zeros((H, W)), np.zeros((H, W))
+    for dy in range(2 * WINDOW + 1):
+        for dx in range(2 * WINDOW + 1):
+            total += zs[dy:dy + H, dx:dx + W]
+            count += ns[dy:dy + H, dx:dx + W]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(has, total / count, NO_HISTORY)

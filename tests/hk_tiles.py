@@ -1,24 +1,16 @@
 """ctypes binding of tests/hostkernel/libtiles_host.so: the product's tile layout (vr_tiles.h) built for the host.  TEST HARNESS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import hk_binding
+import hk_common
+from hk_common import _p
 
-_DIR = hk_binding._DIR
-_SO = os.path.join(_DIR, "libtiles_host.so")
 _lib = None
 
 
 def build():
-    src = os.path.join(_DIR, "tiles_host.cpp")
-    deps = [src] + [os.path.join(hk_binding._ROOT, "volren_amd", "csrc", f) for f in ("vr_tiles.h", "vr_math.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               "-Wno-unknown-pragmas", "-o", _SO, src])
-    return _SO
+    return hk_common.build(__file__, "tiles_host.cpp", "libtiles_host.so", ("-Wno-unknown-pragmas",))
 
 
 def lib():
@@ -30,10 +22,6 @@ def lib():
         L.hk_tiles_variance_scale.argtypes = [C.c_int]
         _lib = L
     return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def grid(w, h):

@@ -1,15 +1,11 @@
 """ctypes binding of tests/hostkernel/libprobehost.so: the lookup probes of volren_amd/csrc/vr_probe.h built for the host.
 TEST HARNESS ONLY -- lets the CPU-only suite hold every scene-data accessor of the device code to the oracle."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import hk_binding as hk
-
-_DIR = hk._DIR
-_ROOT = hk._ROOT
+import hk_common
 
 MAJ_BLOCKED, NO_FLOAT_ATLAS, NO_COMPACT_ENV, PAIR = 1, 2, 4, 8
 VOXEL, TRILINEAR, MAJORANT, IMPORTANCE, TEXEL, SKY, LIGHT, TF = range(8)
@@ -17,19 +13,8 @@ OUT_WORDS = (1, 1, 1, 1, 3, 3, 7, 4)
 
 
 def build(sanitize=False):
-    so = os.path.join(_DIR, "libprobehost_san.so" if sanitize else "libprobehost.so")
-    src = os.path.join(_DIR, "probe_host.cpp")
-    deps = [src, os.path.join(_DIR, "host_scene.h")] + [os.path.join(_ROOT, "volren_amd", "csrc", f)
-                                                          for f in ("vr_probe.h", "vr_trace.h", "vr_math.h", "vr_scene.h", "env_pack.h")]
-    if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
-        return so
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2", "-fopenmp",
-           "-Wno-unknown-pragmas", "-o", so + ".%d.tmp" % os.getpid(), src]
-    if sanitize:
-        cmd[1:1] = ["-fsanitize=undefined", "-fno-sanitize-recover=undefined", "-g"]
-    subprocess.check_call(cmd)
-    os.replace(so + ".%d.tmp" % os.getpid(), so)          # atomic: test workers that run in parallel never load a half-written library
-    return so
+    return hk_common.build(__file__, "probe_host.cpp", "libprobehost_san.so" if sanitize else "libprobehost.so",
+                           ("-fopenmp", "-Wno-unknown-pragmas") + (hk_common.UBSAN if sanitize else ()))
 
 
 _libs = {}

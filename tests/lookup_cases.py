@@ -2,15 +2,13 @@
 items of four 32-bit words, whole tables and their edges.  Every generator is deterministic (fixed seeds)."""
 import numpy as np
 
+from hk_common import bits
+
 VOXEL, TRILINEAR, MAJORANT, IMPORTANCE, TEXEL, SKY, LIGHT, TF = range(8)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def same(got, want):
-    """bit for bit, NaN equal to NaN"""
+    """bit for bit, NaN equal to NaN.  Not hk_common.same: any NaN equals any other, and the shapes must agree"""
     got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
     return got.shape == want.shape and bool(((bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))).all())
 

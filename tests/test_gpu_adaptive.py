@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import hk_adaptive as ha
+from hk_common import bits as _bits
 import scenes
 import volren_amd
 
@@ -15,10 +16,6 @@ pytestmark = pytest.mark.gpu
 
 W, H = 72, 56                                              # 5 x 4 tiles, the last column 8 wide, the top row 8 high
 COUNTS = (4, 8, 16, 32, 64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _uniform(name):

@@ -7,15 +7,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from hk_common import bits as _bits
 import hk_denoise
 import scenes
 import volren_amd
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _ready(name, w, h, spp, fspp=None):

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from hk_common import bits as _bits
 import hk_features
 import scenes
 import volren_amd
@@ -17,10 +18,6 @@ FEATURE_SCENES = ("c1", "c3", "c4_64", "c5_64")
 
 def _pair(name, w, h):
     return scenes.hip_scene(name, w, h), scenes.oracle_scene(name, w, h)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("name", FEATURE_SCENES)

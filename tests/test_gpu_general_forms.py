@@ -10,6 +10,7 @@ apart, must be the oracle's bit for bit.  tests/test_host_kernel.py runs the sam
 import numpy as np
 import pytest
 
+from hk_common import bits as _bits
 import scenes
 from test_gpu_parity import FLAG_VARIANTS
 
@@ -36,10 +37,6 @@ _ids = lambda v: "%s-%s" % (v[0], "addresses64" if v[1] else "offsets32") if isi
 SCHED_DEFAULT = [64, 0, 56, 0, 60, 60, 64, 0]
 _made = {}
 _frames = {}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _assert_same(got, want, what):

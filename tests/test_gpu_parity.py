@@ -8,13 +8,10 @@ import os
 import numpy as np
 import pytest
 
+from hk_common import bits as _bits
 import scenes
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _assert_same(hip, orc, what):

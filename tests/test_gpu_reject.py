@@ -1,5 +1,5 @@
 """GPU: the history rejection of the temporal accumulation (vr_set_float "denoise_reject", vr_denoise_reject_stat) through the C ABI: the fetch and
-resolve kernels equal the host-compiled lane code bit for bit (tests/hostkernel/reject_host.cpp, itself held to a float64 statement by
+resolve kernels equal the host-compiled lane code bit for bit (tests/hostkernel/temporal_host.cpp, itself held to a float64 statement by
 tests/test_reject_host.py), statistic included; a threshold of 0 is the call as it was; the state rules; a scratch buffer that does not fit; logical
 shards; that it follows a changing scene; the Python, volpy and CLI interfaces."""
 import subprocess
@@ -8,36 +8,21 @@ import numpy as np
 import pytest
 
 import hk_adaptive
-import hk_reject as hr
 import hk_temporal as ht
 import scenes
 import volren_amd
-from test_gpu_temporal import _bits, _camera, _frame, _orbit, _same, _scene
+from gpu_frames import _camera, _check_against_replay, _frame, _orbit, _scene
+from hk_common import same as _same
 from test_reject_capi import check_range
 from test_reject_host import CHANGE, H3, SPP, W3, change_scene, check_table, run_scenarios
 
 pytestmark = pytest.mark.gpu
 
 
-def _check_against_replay(r, replay, what, n=None):
-    """after r.denoise_temporal(): history, result and statistic equal the host lane code fed with the renderer's own buffers, camera and threshold"""
-    tau = r.denoise_reject
-    hc, hv, hn = r.denoise_history()
-    want = replay.frame(_camera(r), r.framebuffer(), r.variance(), r.features(), r.sample if n is None else n, r.denoise_alpha, tau, r.denoise_iterations,
-                        tuple(r.denoise_sigma))
-    parts = [(hc, want[0], "C"), (hv, want[1], "V"), (hn, want[2], "N"), (r.denoised(), want[3], "denoised")]
-    if tau > 0:
-        parts.append((r.denoise_reject_stat(), replay.stat, "T"))
-    for got, ref, part in parts:
-        bad = _bits(got) != _bits(ref)
-        assert not bad.any(), (what, part, int(bad.sum()))
-    return hn, replay.stat
-
-
 def _sequence(r, tau, what, frames=4, spp=5):
     """an orbit of 1 degree steps with the density scaled by 0.25 in the middle; -> (pixels kept with N >= 2, pixels rejected) over the sequence"""
     r.denoise_reject = tau
-    replay = hr.Replay()
+    replay = ht.Replay()
     kept = dropped = 0
     for i in range(frames):
         _orbit(r, 1.0 * i)
@@ -47,7 +32,7 @@ def _sequence(r, tau, what, frames=4, spp=5):
         r.denoise_temporal()
         n, stat = _check_against_replay(r, replay, (what, tau, i))
         kept += int((n >= 2).sum())
-        dropped += int(hr.rejected(stat, tau).sum())
+        dropped += int(ht.rejected(stat, tau).sum())
     return kept, dropped
 
 
@@ -74,7 +59,7 @@ def test_a_ragged_frame_as_the_second_frame():
     W, H = 64, 48
     r = _scene("c4_64", W, H)
     r.denoise_reject = 3.0
-    replay = hr.Replay()
+    replay = ht.Replay()
     _frame(r, 8, seed=1)
     r.denoise_temporal()
     _check_against_replay(r, replay, "uniform")
@@ -226,7 +211,7 @@ def test_three_logical_shards_equal_one_device():
         for a, b in zip(s.denoise_history(), one.denoise_history()):
             assert _same(a, b), frame
         assert _same(s.denoise_reject_stat(), one.denoise_reject_stat())
-        rejected += int(hr.rejected(one.denoise_reject_stat(), 3.0).sum())
+        rejected += int(ht.rejected(one.denoise_reject_stat(), 3.0).sum())
     assert rejected > 0
     one.close()
     s.close()
@@ -286,14 +271,14 @@ def test_python_and_volpy_shapes_and_row_order():
     assert vr.denoise_reject == 0.0
     vr.denoise_reject = 3.0
     assert vr.denoise_reject == 3.0 and vr._r.denoise_reject == 3.0
-    replay = hr.Replay()
+    replay = ht.Replay()
     r = vr._r
     for seed in (1, 2):                               # two frames of different samples: T is a picture, not a constant
         vr.seed = seed
         vr.render(6)
         vr.render_features(6)
         vr.denoise_temporal()
-        want = replay.frame(_camera(r), r.framebuffer(), r.variance(), r.features(), r.sample, r.denoise_alpha, 3.0)
+        want = replay.frame(_camera(r), r.framebuffer(), r.variance(), r.features(), r.sample, r.denoise_alpha, tau=3.0)
     t = r.denoise_reject_stat()
     assert t.shape == (24, 40) and t.dtype == np.float32
     assert _same(t, replay.stat) and not _same(t, replay.stat[::-1])      # row 0 = bottom, like every array the replay takes and gives

@@ -7,17 +7,10 @@ as in test_gpu_sharded.py: the guide exchange has never run between two physical
 import numpy as np
 import pytest
 
+from hk_common import same as _same
 import scenes
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 _REF = {}
@@ -108,6 +101,7 @@ def test_frames_back_to_back_without_synchronisation():
 
 
 def _orbit(r, degrees):
+    """not gpu_frames._orbit(r, degrees, 0.0): cam_dir.y is -0.0 here and +0.0 there"""
     a = np.radians(45.0 + degrees)
     pos = np.array([np.sqrt(2.0) * np.sin(a), 0.0, np.sqrt(2.0) * np.cos(a)])
     r.cam_pos = pos

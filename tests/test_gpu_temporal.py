@@ -13,60 +13,10 @@ import hk_denoise
 import hk_temporal as ht
 import scenes
 import volren_amd
+from gpu_frames import _camera, _check_against_replay, _frame, _orbit, _scene
+from hk_common import same as _same
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _scene(name, w, h):
-    r = scenes.hip_scene(name, w, h)
-    r.variance = 1
-    return r
-
-
-def _frame(r, spp, seed=None, fspp=None, fseed=None):
-    """one frame of a sequence, up to the denoise call: reset, render, render_features"""
-    if seed is not None:
-        r.seed = seed
-    r.reset()
-    r.render(spp)
-    if fseed is not None:
-        r.seed = fseed
-    r.render_features(fspp or spp)
-
-
-def _camera(r):
-    """the renderer's own camera from its uniform block (vr_get_uniforms): 3 ints, then cam_pos, cam_fov, cam_transform"""
-    f = np.frombuffer(r.uniforms_bytes(), np.float32)
-    return ht.camera(f[3:6], f[7:16], fov_degree=float(f[6]))
-
-
-def _orbit(r, degrees, yaw=0.0):
-    """cam_pos = (1, 0, 1) turned about +y, cam_dir towards the origin (yaw: turned away from it about +y, degrees)"""
-    a = np.radians(45.0 + degrees)
-    pos = np.array([np.sqrt(2.0) * np.sin(a), 0.0, np.sqrt(2.0) * np.cos(a)])
-    b = np.radians(yaw)
-    d = -pos / np.linalg.norm(pos)
-    r.cam_pos = pos
-    r.cam_dir = (np.cos(b) * d[0] + np.sin(b) * d[2], 0.0, -np.sin(b) * d[0] + np.cos(b) * d[2])
-
-
-def _check_against_replay(r, replay, what, n=None):
-    """after r.denoise_temporal(): the history and the result equal the host lane code fed with the renderer's own buffers and camera"""
-    hc, hv, hn = r.denoise_history()
-    want = replay.frame(_camera(r), r.framebuffer(), r.variance(), r.features(), r.sample if n is None else n, r.denoise_alpha, r.denoise_iterations,
-                        tuple(r.denoise_sigma))
-    for got, ref, part in ((hc, want[0], "C"), (hv, want[1], "V"), (hn, want[2], "N"), (r.denoised(), want[3], "denoised")):
-        bad = _bits(got) != _bits(ref)
-        assert not bad.any(), (what, part, int(bad.sum()))
-    return hn
 
 
 # ---- 4: the first call is vr_denoise ------------------------------------------------------------------------------------------------------------------
@@ -96,7 +46,7 @@ def test_moving_sequence_matches_the_host_lane_code(name):
         _orbit(r, 2.0 * i)
         _frame(r, 6, seed=i + 1)
         r.denoise_temporal()
-        n = _check_against_replay(r, replay, (name, i))
+        n, _ = _check_against_replay(r, replay, (name, i))
         longest = max(longest, int(n.max()))
     assert longest >= 3, longest                     # histories were found and followed, not rejected everywhere
 
@@ -110,7 +60,7 @@ def test_sequence_with_a_change_of_fov_and_a_camera_that_looks_away():
         _frame(r, 4, seed=i + 1)
         prev = replay.hist
         r.denoise_temporal()
-        n = _check_against_replay(r, replay, (fov, yaw))
+        n, _ = _check_against_replay(r, replay, (fov, yaw))
         if prev is not None:
             g = hk_denoise.prepare(r.variance(), r.features(), r.sample)[1]
             u, w, _, ok = ht.reproject(_camera(r), prev[0], g[..., 3], g[..., 7])
@@ -152,7 +102,7 @@ def test_a_ragged_frame_as_the_second_frame():
     assert sorted(set(counts.reshape(-1).tolist())) == [8, 32]
     r.render_features(8)
     r.denoise_temporal()
-    n = _check_against_replay(r, replay, "ragged", n=hk_adaptive.per_pixel(counts, W, H))
+    n, _ = _check_against_replay(r, replay, "ragged", n=hk_adaptive.per_pixel(counts, W, H))
     assert (n == 2).any()
 
 

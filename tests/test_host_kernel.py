@@ -6,12 +6,9 @@ import numpy as np
 import pytest
 
 import hk_binding as hk
+from hk_common import same as _same
 import scenes
 from oracle import binding as ob
-
-
-def _same(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
 
 
 @pytest.mark.parametrize("name,w,h,spp", [("c1", 64, 64, 16), ("c2", 40, 40, 8), ("c3", 48, 48, 8), ("readme", 40, 40, 8)])

@@ -1,5 +1,5 @@
 """CPU: the host build of the temporal accumulation's history rejection (volren_amd/csrc/vr_temporal.h steps 2a, 3a through
-tests/hostkernel/reject_host.cpp) against a float64 numpy statement of its rules (tests/hk_reject.py spec_*) on synthetic histories and guides,
+tests/hostkernel/temporal_host.cpp) against a float64 numpy statement of its rules (tests/hk_temporal.py spec_*) on synthetic histories and guides,
 thresholds that never and always reject, thin frames behind range checks in the sanitizer build, and what it is for: a scene that changes under a
 fixed camera, rendered by the oracle."""
 import numpy as np
@@ -7,17 +7,13 @@ import pytest
 
 import hk_denoise
 import hk_features
-import hk_reject as hr
 import hk_temporal as ht
 import scenes
+from hk_common import bits as _bits
 from test_temporal_host import orbit_camera, synthetic_guide, synthetic_history
 
 SIZES = ((96, 72), (1, 1), (1, 37), (37, 1), (33, 31))
 CAMERAS = (("moved", 10.0, 11.0), ("unchanged", 20.0, 20.0))      # degrees on test_temporal_host's orbit: the history's camera, the frame's
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _inputs(rng, W, H, a0, a1, smooth):
@@ -50,16 +46,16 @@ def test_statistic_and_decision_match_float64(size, camera, tau):
         cur, hist, c, v, k, d = _inputs(rng, W, H, a0, a1, smooth=True)
         same = a0 == a1
         alpha = (0.1, 2.0 ** -20, 1.0, 0.3)[seed]
-        C, R, T = hr.step(cur, c, v, k, d, alpha, tau, hist, checked=True)
-        C2, R2, T2 = hr.step(cur, c, v, k, d, alpha, tau, hist)
+        C, R, T = ht.step_reject(cur, c, v, k, d, alpha, tau, hist, checked=True)
+        C2, R2, T2 = ht.step_reject(cur, c, v, k, d, alpha, tau, hist)
         assert np.array_equal(_bits(C), _bits(C2)) and np.array_equal(_bits(R), _bits(R2)) and np.array_equal(_bits(T), _bits(T2))
         given = None if same else ht.reproject(cur, hist[0], k, d)
-        has, h, vh, nh = hr.spec_fetch(cur, k, d, hist, given=given)
-        sT = hr.spec_stat(c, v, has, h, vh)
-        assert np.array_equal(T != hr.NO_HISTORY, has)
+        has, h, vh, nh = ht.spec_fetch(cur, k, d, hist, given=given)
+        sT = ht.spec_stat(c, v, has, h, vh)
+        assert np.array_equal(T != ht.NO_HISTORY, has)
         assert np.allclose(T[has], sT[has], rtol=1e-5, atol=0)
         near = has & (np.abs(sT - tau) <= 1e-4 * tau)
-        rej = hr.rejected(T, tau)
+        rej = ht.rejected(T, tau)
         assert np.array_equal(rej[~near], (has & ~(sT <= tau))[~near])
         # C, V, N: the statement's blend where the host build kept the history, the frame where it did not
         sC, sV, sN = ht.spec_step(cur, c, v, k, d, alpha, hist, given=given)[:3]
@@ -84,7 +80,7 @@ def test_the_window_counts_only_pixels_with_a_history_inside_the_frame():
     cam = orbit_camera(0.0)
     k = np.full((H, W), 0.5, np.float32)
     d = np.ones((H, W), np.float32)
-    w = np.asarray(hr.LUMA)
+    w = np.asarray(ht.LUMA)
     c = np.zeros((H, W, 4), np.float32)
     hc = np.zeros((H, W, 4), np.float32)
     hc[..., 1] = 2.0
@@ -92,7 +88,7 @@ def test_the_window_counts_only_pixels_with_a_history_inside_the_frame():
     v = np.full((H, W), 0.25, np.float32)
     rec = np.stack([np.full((H, W), 0.25, np.float32), np.full((H, W), 3.0, np.float32), k, d], axis=-1)
     rec[:, 6, 1] = 0.0                                   # column 6: no history
-    C, R, T = hr.step(cam, c, v, k, d, 0.1, 5.0, (cam, hc, rec), checked=True)
+    C, R, T = ht.step_reject(cam, c, v, k, d, 0.1, 5.0, (cam, hc, rec), checked=True)
     z = ((hc[..., :3].astype(np.float64) * w).sum(-1)) ** 2 / 0.5
     assert (T[:, 6] == -1).all() and (R[:, 6, 1] == 1).all()
     for (x, y) in ((0, 0), (8, 6), (4, 3), (2, 3), (1, 3), (7, 0)):
@@ -111,16 +107,16 @@ def test_the_largest_threshold_is_the_step_without_rejection_and_the_smallest_re
     rng = np.random.default_rng(8000 + W * 7 + H)
     cur, hist, c, v, k, d = _inputs(rng, W, H, camera[1], camera[2], smooth=False)
     C0, R0 = ht.step(cur, c, v, k, d, 0.1, hist)
-    C, R, T = hr.step(cur, c, v, k, d, 0.1, hr.TAU_MAX, hist, checked=True)
-    assert not np.isnan(T).any() and T.max() <= hr.TAU_MAX
+    C, R, T = ht.step_reject(cur, c, v, k, d, 0.1, ht.TAU_MAX, hist, checked=True)
+    assert not np.isnan(T).any() and T.max() <= ht.TAU_MAX
     assert np.array_equal(_bits(C), _bits(C0)) and np.array_equal(_bits(R), _bits(R0))
-    has = T != hr.NO_HISTORY
+    has = T != ht.NO_HISTORY
     assert np.array_equal(has, R0[..., 1] > 1)
-    C, R, T = hr.step(cur, c, v, k, d, 0.1, hr.TAU_MIN, hist, checked=True)
-    assert np.array_equal(T != hr.NO_HISTORY, has) and (T[has] > hr.TAU_MIN).all()      # a white-noise history differs from the frame everywhere
+    C, R, T = ht.step_reject(cur, c, v, k, d, 0.1, ht.TAU_MIN, hist, checked=True)
+    assert np.array_equal(T != ht.NO_HISTORY, has) and (T[has] > ht.TAU_MIN).all()      # a white-noise history differs from the frame everywhere
     assert np.array_equal(_bits(C), _bits(c))
     assert np.array_equal(_bits(R), _bits(np.stack([v, np.ones_like(v), k, d], axis=-1)))
-    assert hr.constants() == (2.0 ** -10, 2.0 ** 20, float(np.float32(1e-12)), 2.0, -1.0)
+    assert ht.reject_constants() == (2.0 ** -10, 2.0 ** 20, float(np.float32(1e-12)), 2.0, -1.0)
 
 
 def test_a_nan_rejects_and_the_first_frame_is_the_frame():
@@ -130,12 +126,12 @@ def test_a_nan_rejects_and_the_first_frame_is_the_frame():
     k, d = synthetic_guide(rng, W, H)
     c = rng.uniform(0.0, 2.0, (H, W, 4)).astype(np.float32)
     v = rng.uniform(0.0, 0.1, (H, W)).astype(np.float32)
-    C, R, T = hr.step(cam, c, v, k, d, 0.1, 3.0, None, checked=True)
+    C, R, T = ht.step_reject(cam, c, v, k, d, 0.1, 3.0, None, checked=True)
     assert (T == -1).all() and np.array_equal(_bits(C), _bits(c)) and np.array_equal(_bits(R), _bits(np.stack([v, np.ones_like(v), k, d], axis=-1)))
     rec = np.stack([v, np.full((H, W), 2.0, np.float32), k, d], axis=-1)
     hc = c.copy()                                        # the history is the frame: z2 = 0, nothing rejected ...
     hc[10, 12, 1] = np.nan                               # ... but for the 5 x 5 pixels whose window holds the NaN
-    C, R, T = hr.step(cam, c, v, k, d, 0.1, hr.TAU_MAX, (cam, hc, rec), checked=True)
+    C, R, T = ht.step_reject(cam, c, v, k, d, 0.1, ht.TAU_MAX, (cam, hc, rec), checked=True)
     hole = np.zeros((H, W), bool)
     hole[8:13, 10:15] = True
     assert np.isnan(T[hole]).all() and (T[~hole] == 0).all()
@@ -157,8 +153,8 @@ def test_no_window_or_history_read_leaves_the_frame(size):
         v = rng.uniform(0.0, 0.1, (H, W)).astype(np.float32)
         hc, rec = synthetic_history(rng, cur, prev, k, np.nan_to_num(d, nan=1.0), W, H, smooth=False)
         for tau in (3.0, 0.5):
-            C, R, T = hr.step(cur, c, v, k, d, 0.1, tau, (prev, hc, rec), checked=True)      # asserts that no read fell outside
-            C2, R2, T2 = hr.step(cur, c, v, k, d, 0.1, tau, (prev, hc, rec))
+            C, R, T = ht.step_reject(cur, c, v, k, d, 0.1, tau, (prev, hc, rec), checked=True)      # asserts that no read fell outside
+            C2, R2, T2 = ht.step_reject(cur, c, v, k, d, 0.1, tau, (prev, hc, rec))
             assert np.array_equal(_bits(C), _bits(C2)) and np.array_equal(_bits(R), _bits(R2)) and np.array_equal(_bits(T), _bits(T2))
 
 
@@ -196,7 +192,7 @@ def run_scenarios(frame_of, reference_of, camera, denoise_spatial, replay_of):
                 if i >= CHANGE:
                     err.append(scenes.rel_l2(o[..., :3], ref))
                     outs.append(o)
-                share.append(float(hr.rejected(stat, tau).mean()) if tau > 0 and stat is not None else 0.0)
+                share.append(float(ht.rejected(stat, tau).mean()) if tau > 0 and stat is not None else 0.0)
             res[tau] = dict(err=err, out=outs, share=share)
         out[s] = res
         print("%-14s spatial %s | tau 0 %s | tau 3 %s | rejected %s" % (s, " ".join("%.4f" % e for e in res["spatial"]), " ".join("%.4f" % e for e in res[0.0]["err"]),
@@ -241,10 +237,10 @@ def table():
         return o.render(1024).copy()
 
     def replay_of(tau):
-        rp = hr.Replay()
+        rp = ht.Replay()
 
         def one(cam, color, var, feat):
-            out = rp.frame(cam, color, var, feat, SPP, 0.1, tau)[3]
+            out = rp.frame(cam, color, var, feat, SPP, 0.1, tau=tau)[3]
             return out, rp.stat
         return one
 

@@ -4,6 +4,7 @@ camera, the first frame, frames one pixel thin, cameras that look away."""
 import numpy as np
 import pytest
 
+from hk_common import bits as _bits
 import hk_temporal as ht
 
 SIZES = ((96, 72), (1, 1), (1, 37), (37, 1), (33, 31), (256, 256))
@@ -11,10 +12,6 @@ SIZES = ((96, 72), (1, 1), (1, 37), (37, 1), (33, 31), (256, 256))
 # float32 at |u| <= W (the error grows with the coordinate), not of any device.  The tolerance is 4 x the measured value.
 MEASURED_PX = {(96, 72): 1.69e-5, (1, 1): 5.26e-8, (1, 37): 3.51e-6, (37, 1): 7.87e-6, (33, 31): 5.65e-6, (256, 256): 5.54e-5}
 TOL_PX = {k: 4.0 * v for k, v in MEASURED_PX.items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def orbit_camera(angle_deg, fov=40.0, radius=np.sqrt(2.0), height=0.0, yaw_deg=0.0):

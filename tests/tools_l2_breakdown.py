@@ -17,13 +17,13 @@ usage: tools_l2_breakdown.py [cfg=c5cloud] [frame=2048] [spp=2] [bands=8] [popul
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 import time
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__))]
 import numpy as np  # noqa: E402
 import scenes  # noqa: E402
 import hk_binding  # noqa: E402
+import hk_common  # noqa: E402
 
 cfg = sys.argv[1] if len(sys.argv) > 1 else "c5cloud"
 frame = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
@@ -33,13 +33,7 @@ rows = frame // bands
 population = int(sys.argv[5]) if len(sys.argv) > 5 else 1024 * 188
 l2_mib = float(sys.argv[6]) if len(sys.argv) > 6 else 4.0
 
-here = os.path.dirname(os.path.abspath(__file__))
-so = os.path.join(here, "hostkernel", "libhostkernel_trace.so")
-src = os.path.join(here, "hostkernel", "host_kernel.cpp")
-deps = [src] + [os.path.join(os.path.dirname(here), "volren_amd", "csrc", f) for f in ("vr_trace.h", "vr_math.h", "vr_scene.h")]
-if not (os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps)):
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2", "-Wno-unknown-pragmas", "-DVR_HOST_TRACE=1", "-o", so, src])
-L = C.CDLL(so)
+L = C.CDLL(hk_common.build(__file__, "host_kernel.cpp", "libhostkernel_trace.so", ("-Wno-unknown-pragmas", "-DVR_HOST_TRACE=1")))
 L.hk_l2_breakdown.restype = C.c_longlong
 
 o = scenes.oracle_scene(cfg, frame, frame)
@@ -78,7 +72,7 @@ print("  %-30s %9.2f %13.2f %11.2f %12s %20.0f   (reads only)" % ("all reads", a
 print("  dirty lines written back by the model: %.2f per sample" % (sum(out[32 * b + 27] for b in range(bands)) / max(n, 1)))
 print("# per band (XCD): share of the frame's read misses / of its accesses:", "  ".join("%d: %.0f %% / %.0f %%" % (b, 100 * raw[b, :7, 2].sum() / max(raw[:, :7, 2].sum(), 1), 100 * raw[b, :7, 0].sum() / max(raw[:, :7, 0].sum(), 1)) for b in range(bands)))
 try:
-    pm = json.load(open(os.path.join(os.path.dirname(here), "profiles", "r5_pmc_summary.json")))
+    pm = json.load(open(os.path.join(hk_common.ROOT, "profiles", "r5_pmc_summary.json")))
     key = {"c5cloud": "c5cloud", "c4:512": "c4", "c2": "c2", "c5full": "c5full"}.get(cfg)
     if key:
         m = pm[key]

@@ -351,9 +351,6 @@ static GridView make_view(const BrickGridHIP& g, bool paired = false, bool maj_b
     return v;
 }
 
-// cam_z of the uniform block (common.glsl:78); the temporal denoiser compares cameras byte for byte, so there is one expression for it
-static float camera_z(float fov_degree) { return -0.5f / tan_(0.5f * kPi * fov_degree / 180.f); }
-
 void RendererHIP::fill_params(SceneParams& P) {
     if (!volume || volume->grids.empty() || density_grids.empty())
         throw std::runtime_error("RendererHIP::trace: no volume committed");

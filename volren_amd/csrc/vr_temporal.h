@@ -3,7 +3,7 @@
 // The temporal part of SVGF (Schied et al. 2017): before the spatial filter of vr_denoise.h runs, the current frame is blended with a history
 // of the frames before it, fetched where the pixel's first-scatter point lay on the screen of the frame that wrote the history.  Per-pixel
 // functions only: the HIP kernels (vr_filters.hip denoise_temporal_kernel; with rejection denoise_temporal_fetch_kernel and
-// denoise_temporal_resolve_kernel) and the host builds of the tests (tests/hostkernel/temporal_host.cpp, reject_host.cpp) run the same code, so the two agree bit for bit.  The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division,
+// denoise_temporal_resolve_kernel) and the host builds of the tests (tests/hostkernel/temporal_host.cpp) run the same code, so the two agree bit for bit.  The arithmetic is fixed operation by operation (vr_math.h: -ffp-contract=off, IEEE division,
 // sqrt_, floor_); a * b + c below is two roundings unless it is written as one of vr_math.h's dot / mat3_mul / axpy, which are fma chains.
 // A participating medium has no surface: the "depth" is the mean first-scatter distance along the pixel's centre ray.
 //
@@ -60,6 +60,10 @@ constexpr float kTemporalRejectMin = 0x1p-10f, kTemporalRejectMax = 0x1p20f;    
 constexpr float kTemporalVarianceFloor = 1e-12f;      // added to the variance of the difference (radiances far above 1e-6)
 constexpr int32_t kTemporalWindow = 2;                // the rejection statistic pools a (2 * 2 + 1)^2 window
 constexpr float kTemporalNoHistory = -1.0f;           // the statistic, and the window word, of a pixel without a history
+
+// cam_z of the uniform block (common.glsl:78).  Cameras are compared byte for byte (step 3), so there is one expression for it: RendererHIP::fill_params
+// and run_denoise call it, and so does the tests' host build.  No kernel does.
+VR_HD float camera_z(float fov_degree) { return -0.5f / tan_(0.5f * kPi * fov_degree / 180.f); }
 
 // Step 1: where the first-scatter point of pixel (px, py) lay on the history's screen (u, w in pixels, d' its distance from that camera).
 // false: behind that camera (q.z >= 0 or NaN); u, w, d' are not written then.
