@@ -205,11 +205,28 @@ int vr_denoised(vr_renderer* r, float* rgba_out);
  *     scene.  Two limits: the frames need n >= 2 samples per pixel (with n = 1 the variance v is 0 and whatever changed at all is rejected), and the floor
  *     1e-12 assumes radiances far above 1e-6.  Costs one scratch buffer of W*H*8 floats, allocated like the others before anything is launched.
  *     vr_denoise_reject_stat waits and writes W*H floats, row 0 at the bottom: T of the last vr_denoise_temporal, -1 where the pixel had no history;
- *     VR_ERR unless the last vr_denoise_temporal since the resize ran with "denoise_reject" > 0. */
+ *     VR_ERR unless the last vr_denoise_temporal since the resize ran with "denoise_reject" > 0.
+ *     Luminance moments, off by default.  The filter's variance above is the frames' sample variance, which a frame of one sample per pixel does not
+ *     have: at 1 spp v = 0, vr_denoise is the identity and vr_denoise_temporal a bare running mean.  vr_set_int / vr_get_int "denoise_moments" (0 or 1;
+ *     default 0, and then every launch, allocation and result is what it is without this paragraph; anything else is VR_ERR, the old value kept; a
+ *     call that changes the value drops the history: one without moment records cannot continue one with them).  With 1 the history carries a
+ *     third array, W*H*4 floats (m1, m2, E, S): the integrated first and second moments of the frame's luminance L (m1 = (1 - a) m1_history + a L,
+ *     m2 likewise from L^2, fetched from the same taps as the colour), E = (1 - a)^2 E_history + a^2 the sum of squared blend weights (1 without a
+ *     history), and S the variance of one frame's luminance: m2 - m1^2 (not below 0) where N >= 4 frames lie behind the pixel, and where fewer do --
+ *     the first frames, disoccluded pixels -- the same from m1, m2 averaged over the 7x7 neighbourhood with the filter's coverage, normal, depth and
+ *     albedo weights.  The filter starts from V = S E, and the frame's own v is not used.  The arithmetic is specified operation by operation in
+ *     volren_amd/csrc/vr_moments.h and reproducible bit for bit.  Use it for sequences of 1 to a few samples per pixel (previews, fly-throughs): at
+ *     1 spp it takes the error of the first frame to 0.42 and that of frames 10 to 15 to 0.56 of the running mean's (README.md); from 2 spp on the
+ *     sample variance is as good, and better during the first three frames, hence a setting.  The refusals stay what they are ("variance" = 1 for
+ *     every sample included).  With "denoise_moments" = 1 and "denoise_reject" > 0 vr_denoise_temporal is VR_ERR, nothing is launched and the last
+ *     result and the history stay as they were: one-sample luminances are too heavy-tailed for the rejection statistic.
+ *     vr_denoise_history_moments waits and writes W*H*4 floats (m1, m2, E, S), row 0 at the bottom; VR_ERR unless the current history was written with
+ *     "denoise_moments" = 1. */
 int vr_denoise_temporal(vr_renderer* r);
 int vr_denoise_history_reset(vr_renderer* r);
 int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* length_out);
 int vr_denoise_reject_stat(vr_renderer* r, float* out);
+int vr_denoise_history_moments(vr_renderer* r, float* out);
 /* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
  *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
  *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the
@@ -270,8 +287,8 @@ int vr_unpack_tiles(vr_renderer* r, const int32_t* tile_ids_device, int n_tiles,
  *     features of its own tiles (three float4 per pixel), moves them to part 0 in ONE exchange on the transport above (3x the colour's size; its
  *     buffers are allocated by the first call, a caller that only renders pays nothing) and scatters them into part 0's moments and features.
  *     vr_sharded_denoise / vr_sharded_denoise_temporal do that and then run vr_denoise / vr_denoise_temporal's filter on part 0 over the whole frame,
- *     with part 0's "denoise_iterations", "denoise_sigma", "denoise_alpha", "denoise_reject" and camera: bit-identical to the single-device calls.  Results are read
- *     from part 0: vr_denoised, vr_features, vr_variance (both after a gather), vr_denoise_history and vr_denoise_reject_stat on vr_sharded_part(s, 0); the temporal history lives
+ *     with part 0's "denoise_iterations", "denoise_sigma", "denoise_alpha", "denoise_reject", "denoise_moments" and camera: bit-identical to the single-device calls.  Results are read
+ *     from part 0: vr_denoised, vr_features, vr_variance (both after a gather), vr_denoise_history, vr_denoise_history_moments and vr_denoise_reject_stat on vr_sharded_part(s, 0); the temporal history lives
  *     in part 0 and vr_denoise_history_reset on part 0 drops it.  All three are asynchronous, and a sequence reset, render, render_features, denoise per
  *     frame needs no synchronisation between frames.  VR_ERR, before anything is launched and with a message that names the part, unless all parts agree
  *     on the resolution and "sample", "sample" >= 1, and every part that owns tiles has moments that cover samples 1..n, a feature pass since the last

@@ -21,7 +21,7 @@ SYMBOLS = [
     "vr_volume_add_grid_frame_dense", "vr_volume_update_grid_frame_dense", "vr_volume_n_grid_frames", "vr_impmap_floats", "vr_get_impmap", "vr_test_alloc_cap_mb", "vr_set_sched", "vr_sched_stats", "vr_grid_checksums", "vr_math_probe", "vr_math_sweep", "vr_probe", "vr_encode_dense_stats", "vr_write_brick_from_dense", "vr_write_dense",
     "vr_sharded_create", "vr_sharded_destroy", "vr_sharded_parts", "vr_sharded_part", "vr_sharded_transport", "vr_sharded_collective", "vr_sharded_reset", "vr_sharded_render", "vr_sharded_synchronize", "vr_tile_owners", "vr_wave_timeline",
     "vr_render_features", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
-    "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history", "vr_denoise_reject_stat",
+    "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history", "vr_denoise_reject_stat", "vr_denoise_history_moments",
     "vr_render_adaptive", "vr_tile_samples", "vr_tile_error",
     "vr_sharded_render_features", "vr_sharded_gather_guides", "vr_sharded_denoise", "vr_sharded_denoise_temporal",
 ]
@@ -83,6 +83,7 @@ def load():
     L.vr_denoise_history_reset.argtypes = [vp]
     L.vr_denoise_history.argtypes = [vp, vp, vp, vp]
     L.vr_denoise_reject_stat.argtypes = [vp, vp]
+    L.vr_denoise_history_moments.argtypes = [vp, vp]
     L.vr_render_adaptive.argtypes = [vp, ci, ci, cf]
     L.vr_tile_samples.argtypes = [vp, vp, ci]
     L.vr_tile_error.argtypes = [vp, vp, ci]

@@ -10,6 +10,8 @@
 // frame and writes the tonemapped denoised frame instead of the raw one (one device only).  --denoise-temporal does the same through
 // denoise_temporal (vr_temporal.h): the history is kept across the frames of the run, so every frame after the first is blended with the ones before it.
 // --denoise-reject T with it: a pixel whose history disagrees with its frame beyond the noise of the two starts afresh (vr_temporal.h 2a, 3a; refused alone).
+// --denoise-moments with it: the filter's variance comes from luminance moments kept in the history (vr_moments.h), for runs of 1 to a few spp per
+// frame (refused alone and with --denoise-reject above 0).
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
 // the mean samples per pixel; combines with --denoise (one device only).
 //
@@ -88,7 +90,7 @@ static void parse_cmd(int argc, char** argv) {
     Args a{ argc, argv, 0 };
     for (a.i = 1; a.i < argc; ++a.i) {
         const std::string arg = argv[a.i];
-        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal") {      // --denoise, --denoise-temporal, --adaptive: main()
+        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments") {      // --denoise*, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
@@ -167,7 +169,7 @@ int main(int argc, char** argv) {
     int width = 1280, height = 720, device = 0, gpus = 0;        // cppgl ContextParameters defaults (unverified): always pass -w/-h
     bool denoise = false, temporal = false, adaptive = false;      // temporal: --denoise with the history kept across the frames of the run
     float threshold = 0.f, reject = 0.f;      // reject: --denoise-reject, the history rejection threshold of --denoise-temporal (0 = off)
-    bool reject_given = false;
+    bool reject_given = false, moments = false;      // moments: --denoise-moments, the filter's variance from the history's luminance moments (low-spp sequences)
     std::vector<int> devices;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -179,6 +181,7 @@ int main(int argc, char** argv) {
             else if (arg == "--devices" && i + 1 < argc) devices = parse_int_list(argv[++i]);
             else if (arg == "--denoise") denoise = true;
             else if (arg == "--denoise-temporal") denoise = temporal = true;
+            else if (arg == "--denoise-moments") moments = true;
             else if (arg == "--denoise-reject") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --denoise-reject");
                 reject_given = true;
@@ -193,6 +196,8 @@ int main(int argc, char** argv) {
             }
         }
         if (reject_given && !temporal) throw std::runtime_error("--denoise-reject needs --denoise-temporal: it rejects the history that only that call keeps");
+        if (moments && !temporal) throw std::runtime_error("--denoise-moments needs --denoise-temporal: the moments live in the history that only that call keeps");
+        if (moments && reject > 0.f) throw std::runtime_error("--denoise-moments and --denoise-reject do not go together: the rejection statistic needs the frames' sample variance");
         if (adaptive && (gpus > 0 || devices.size() > 1))
             throw std::runtime_error("--adaptive renders on one device only: drop --gpus / --devices (the sharded renderer has no adaptive sampling)");
         if (denoise && (gpus > 0 || devices.size() > 1))
@@ -223,6 +228,7 @@ int main(int argc, char** argv) {
             renderer->reset();
             if (denoise) renderer->variance = 1;        // the denoiser's variance input: kept from sample 1 of every frame
             renderer->denoise_reject = reject;
+            renderer->denoise_moments = moments ? 1 : 0;
             parts.push_back(renderer);
         }
         renderer = parts[0];                            // holds the whole frame after the gather

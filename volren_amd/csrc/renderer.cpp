@@ -926,6 +926,8 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (!features_) throw std::runtime_error(me + "no feature pass since the last resize (call render_features first)");
     if (sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
     check_moments(who);
+    if (temporal && denoise_moments != 0 && denoise_reject > 0.0f)
+        throw std::runtime_error(me + "denoise_moments = 1 and denoise_reject > 0 do not go together: the rejection statistic needs the frames' sample variance, and the moment variance of 1-spp frames is too heavy-tailed for it (DESIGN.md 5)");
     const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
     if (ragged()) {
         for (int32_t c : tile_n_)
@@ -939,8 +941,12 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error(me + "frame too large (32-bit pixel indices)");
     if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error(me + "denoise_iterations out of range");
     const size_t px = (size_t)W * H;
+    // a history without moment records cannot continue one with them, nor the other way round (denoise_moments set as a field, past set_denoise_moments)
+    if (temporal && hist_cur_ >= 0 && (hist_moments_[hist_cur_] != nullptr) != (denoise_moments != 0)) drop_history();
     const int to = hist_cur_ < 0 ? 0 : 1 - hist_cur_;      // the half of the history pair this call writes
     const bool reject = temporal && denoise_reject > 0.0f;      // vr_temporal.h steps 2a, 3a: the fetch / resolve pair instead of the one kernel
+    const bool moments = temporal && denoise_moments != 0;      // vr_moments.h: the temporal kernel with the moment records, then the variance kernel
+    if (moments) ensure_buffer(hist_moments_[to], px * 4 * sizeof(float));
     if (temporal) { ensure_buffer(hist_color_[to], px * 4 * sizeof(float)); ensure_buffer(hist_record_[to], px * 4 * sizeof(float)); }
     if (reject) ensure_buffer(dn_reject_, px * 8 * sizeof(float));
     ensure_buffer(dn_guide_, px * 8 * sizeof(float));
@@ -963,7 +969,12 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         const bool same = have && memcmp(&cur, &hist_cam_, sizeof cur) == 0;
         const float* hc = have ? hist_color_[hist_cur_]->as<float>() : nullptr;
         const float* hr = have ? hist_record_[hist_cur_]->as<float>() : nullptr;
-        if (reject)
+        const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
+        if (moments)
+            launch_denoise_temporal_moments(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, have ? hist_moments_[hist_cur_]->as<float>() : nullptr,
+                                            same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha, sg, hist_color_[to]->as<float>(), hist_record_[to]->as<float>(),
+                                            hist_moments_[to]->as<float>(), stream);
+        else if (reject)
             launch_denoise_temporal_reject(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H,
                                            denoise_alpha, denoise_reject, dn_reject_->as<float>(), hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
         else
@@ -991,7 +1002,23 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
 
 void RendererHIP::drop_history() {
     hist_color_[0].reset(); hist_color_[1].reset(); hist_record_[0].reset(); hist_record_[1].reset();
+    hist_moments_[0].reset(); hist_moments_[1].reset();
     hist_cur_ = -1;
+}
+
+void RendererHIP::set_denoise_moments(int v) {
+    if (v != 0 && v != 1) throw std::runtime_error("denoise_moments: 0 (the frames' sample variance) or 1 (luminance moments kept in the history)");
+    if (v == denoise_moments) return;
+    flush_pending();
+    drop_history();
+    denoise_moments = v;
+}
+
+void RendererHIP::download_history_moments(float* out) {
+    if (hist_cur_ < 0 || !hist_moments_[hist_cur_])
+        throw std::runtime_error("denoise_history_moments: no history with moment records (no denoise_temporal with denoise_moments = 1 since the last resize, history reset or change of the setting)");
+    flush_pending();
+    hist_moments_[hist_cur_]->download(out, hist_moments_[hist_cur_]->size_bytes(), stream);
 }
 
 void RendererHIP::download_history(float* rgba, float* var, float* length) {

@@ -150,6 +150,7 @@ struct RendererHIP {
     float denoise_sigma[5] = { kDenoiseDefaultSigma[0], kDenoiseDefaultSigma[1], kDenoiseDefaultSigma[2], kDenoiseDefaultSigma[3], kDenoiseDefaultSigma[4] };
                                                       // edge-stopping widths: colour, normal, depth, coverage, albedo (vr_denoise.h)
     float denoise_alpha = kTemporalDefaultAlpha;      // smallest weight of the current frame in denoise_temporal()'s blend, in [2^-20, 1] (vr_temporal.h)
+    int denoise_moments = 0;                          // 1: denoise_temporal() takes the filter's variance from luminance moments kept in the history (vr_moments.h); set it with set_denoise_moments
     float denoise_reject = 0.0f;                      // threshold tau of denoise_temporal()'s history rejection (vr_temporal.h 2a, 3a): 0 = off, or in [2^-10, 2^20]
     bool fast_math = false;                           // opt-in tolerance mode: hardware log/sin/cos/rcp instead of the specified arithmetic
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
@@ -188,12 +189,19 @@ struct RendererHIP {
     // With denoise_reject > 0 a pixel whose history disagrees with the frame beyond the noise of the two starts afresh (other kernels, one scratch buffer
     // more; 0 is today's call exactly).  download_reject_stat: W*H statistics T of the last denoise_temporal(), -1 where the pixel had no history; throws
     // unless the last denoise_temporal() since the resize ran with denoise_reject > 0.
+    // With denoise_moments = 1 the history carries a third array, the moment record (m1, m2, E, S) of the frames' luminance, and the variance the
+    // iterations start from is S * E instead of the blend of the frames' sample variances: frames of 1 spp, which have none, are filtered (other kernels;
+    // 0 is today's call exactly).  set_denoise_moments: 0 or 1, throws otherwise; a change drops the history (one without moment records cannot continue
+    // one with them).  Together with denoise_reject > 0 denoise_temporal() throws before anything is launched: the rejection statistic needs a sample
+    // variance.  download_history_moments: W*H*4 floats; throws unless the current history was written with denoise_moments = 1.
     // Several devices: ShardedRenderer::denoise / denoise_temporal (sharded.h); called on a part directly, these refuse the part's tile subset.
     void denoise();
     void denoise_temporal();
     void drop_history();
     void download_history(float* rgba, float* var, float* length);
     void download_reject_stat(float* out);
+    void set_denoise_moments(int v);
+    void download_history_moments(float* out);
     void download_denoised(float* rgba);
     const DeviceBuffer* denoised() const { return denoised_.get(); }
     // copy + tonemap of a W*H*4 buffer into `display` (draw() = draw_from(*color) after the flush)
@@ -270,6 +278,7 @@ private:
                                                        // whose moments and features hold every part's tiles (gather_guides) -- the tile subset is no obstacle then
     friend struct ShardedRenderer;                     // sharded.h: packs moments_ / features_ of every part, unpacks into part 0's, runs part 0's filter
     DeviceBufferPtr hist_color_[2], hist_record_[2];   // denoise_temporal(): the history, a ping-pong pair of W*H*4 colours and W*H*4 (V, N, K, D) records
+    DeviceBufferPtr hist_moments_[2];                  // with denoise_moments = 1: the pair's W*H*4 moment records (m1, m2, E, S); the current half exists iff the history has them
     int hist_cur_ = -1;                                // the half that holds the history (-1: none)
     TemporalCamera hist_cam_{};                        // the camera of the frame that wrote it
     DeviceBufferPtr dn_reject_;                        // denoise_temporal() with denoise_reject > 0: the scratch between its two kernels, W*H*8 (dropped by resize)

@@ -23,7 +23,8 @@
 //     w_a = exp(-|a_p - a_q|^2 / sigma_a^2)
 //   The centre tap's edge-stopping factors are 1 by definition: its weight is exactly (3/8)^2 > 0.
 //   c'_p = sum w c_q / sum w (all four channels, the same weights), v'_p = sum w^2 v_q / (sum w)^2.
-// N = 0 returns the colour bit for bit.  No albedo demodulation.  The temporal half of SVGF is vr_temporal.h: it runs in front of these iterations.
+// N = 0 returns the colour bit for bit.  No albedo demodulation.  The temporal half of SVGF is vr_temporal.h, with vr_moments.h
+// for its variance estimate: it runs in front of these iterations.
 //
 // Every sigma lies in [2^-60, 2^60] (vr_set_float "denoise_sigma" refuses the rest): sigma_a^2 stays a normal float, so two equal albedos give
 // 0 / sigma_a^2 = 0 and not 0 / 0, and a device that flushes subnormals computes what the host does.

@@ -71,6 +71,12 @@ void launch_denoise_atrous(const float* cin, const float* vin, const float* guid
 void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
                              const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
                              hipStream_t stream);
+// The same with the luminance moments of vr_moments.h ("denoise_moments" = 1), as two kernels: pass 1 also gathers and blends the moment records
+// (hist_moments / out_moments, W*H*4 = (m1, m2, E, S); nullptr with the other two: no history yet), pass 2 forms S and V = S * E with the guide
+// weights of sigma `sg` and writes V into out_record and over v.  The frame's own v is not read.
+void launch_denoise_temporal_moments(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, const float* hist_moments,
+                                     bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, const DenoiseSigma& sg,
+                                     float* out_color, float* out_record, float* out_moments, hipStream_t stream);
 // The same with the rejection test of threshold tau > 0 (vr_temporal.h steps 2a, 3a): two kernels with `scratch` between them, W*H*8 floats that no
 // other argument overlaps: W*H*4 of h, then W*H*4 of (v_h, N_h, z2, has).  Afterwards the first word of each of the latter holds the pixel's
 // statistic T, -1 where the pixel had no history.

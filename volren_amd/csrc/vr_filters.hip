@@ -1,5 +1,5 @@
 // vr_filters.hip -- the image-space kernels (gfx950): everything that reads or writes whole frames or tiles of them after the path tracer.
-// The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h), the error estimate of adaptive
+// The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h, vr_moments.h), the error estimate of adaptive
 // sampling (vr_adaptive.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
 // the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include "vr_adaptive.h"
 #include "vr_denoise.h"
 #include "vr_device.h"
+#include "vr_moments.h"
 #include "vr_temporal.h"
 
 namespace vr {
@@ -78,10 +79,17 @@ struct TemporalHistDev {
     __device__ __forceinline__ void color(int32_t i, float o[4]) const { unpack4(c[i], o); }
     __device__ __forceinline__ void record(int32_t i, float o[4]) const { unpack4(s[i], o); }
 };
+// MOMENTS (vr_moments.h pass 1, "denoise_moments" = 1): every tap that counts also gives its moment record (a third dwordx4), the pixel's new moment
+// record goes to om (16 B more), and v is left alone: denoise_moments_variance_kernel writes it.  false: hm, om are not touched.
+struct MomentsHistDev {
+    const float4* __restrict__ m;
+    __device__ __forceinline__ void moments(int32_t i, float o[4]) const { unpack4(m[i], o); }
+};
+template <bool MOMENTS>
 __global__ void __launch_bounds__(256)
 denoise_temporal_kernel(const float4* __restrict__ color, float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ hc,
-                        const float4* __restrict__ hs, int32_t have, int32_t same_cam, const TemporalCamera cur, const TemporalCamera prev, int32_t W, int32_t H,
-                        float alpha, float4* __restrict__ oc, float4* __restrict__ os) {
+                        const float4* __restrict__ hs, const float4* __restrict__ hm, int32_t have, int32_t same_cam, const TemporalCamera cur,
+                        const TemporalCamera prev, int32_t W, int32_t H, float alpha, float4* __restrict__ oc, float4* __restrict__ os, float4* __restrict__ om) {
     const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
     if (q.px >= W || q.py >= H) return;
     const int32_t i = q.py * W + q.px;
@@ -89,19 +97,78 @@ denoise_temporal_kernel(const float4* __restrict__ color, float* __restrict__ v,
     unpack4(color[i], c);
     const TemporalHistDev hist{ hc, hs };
     float C[4], S[4];
-    temporal_pixel(hist, have != 0, same_cam != 0, cur, prev, W, H, q.px, q.py, c, v[i], guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S);
+    if constexpr (MOMENTS) {
+        float M[4];
+        moments_pixel(hist, MomentsHistDev{ hm }, have != 0, same_cam != 0, cur, prev, W, H, q.px, q.py, c, guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S, M);
+        om[i] = pack4(M);
+    } else {
+        temporal_pixel(hist, have != 0, same_cam != 0, cur, prev, W, H, q.px, q.py, c, v[i], guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S);
+    }
     oc[i] = pack4(C);
     os[i] = pack4(S);
-    v[i] = S[0];
+    if constexpr (!MOMENTS) v[i] = S[0];
 }
 void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
                              const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
                              hipStream_t stream) {
     if (W <= 0 || H <= 0) return;
     const bool have = hist_color && hist_record;
-    hipLaunchKernelGGL(denoise_temporal_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
+    hipLaunchKernelGGL(denoise_temporal_kernel<false>, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
                        reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
-                       have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
+                       (const float4*)nullptr, have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color),
+                       reinterpret_cast<float4*>(out_record), (float4*)nullptr);
+}
+
+// Pass 2 of vr_moments.h: the variance of the filter's input from the moments pass 1 blended.  Stages (m1, m2) of the tile's 22 x 22 footprint (16 x 16
+// plus a halo of 3; one dwordx2 load per pixel, m2 = -1 "off the frame") in 3872 B of LDS, one barrier -- threads outside the frame stage and wait with
+// the others -- then a pixel with N >= 4 reads its own pair back, and only a pixel with a shorter history runs the 49 taps.  The guide taps come straight
+// from global memory, as the a-trous kernel reads them, not from LDS: after the first frames only disoccluded pixels pool, and staging 22 x 22 x 32 B of
+// guide per tile would charge every tile of every frame 15 KiB of loads for taps that almost none of its pixels make; on the first frame, where all do,
+// the 49 x 32 B of a pixel are its neighbours' too and hit the L2.  Writes S into the pixel's moment record, V = S * E into its history record and over
+// its v: words of its own pixel that no other thread reads (the staging of the neighbouring tiles reads m1, m2 only, at no fixed time).  No atomics.
+constexpr int32_t kMomentsFoot = 16 + 2 * kMomentsWindow;      // edge of a tile's footprint in pixels
+struct MomentsWindowDev {
+    const float2* win;     // the staged footprint
+    int32_t at;            // the pixel's own pair in it
+    __device__ __forceinline__ void moments(int32_t dx, int32_t dy, float m[2]) const { const float2 p = win[at + dy * kMomentsFoot + dx]; m[0] = p.x; m[1] = p.y; }
+};
+struct MomentsGuideDev {
+    const float4* __restrict__ g;
+    __device__ __forceinline__ void guide(int32_t i, float o[8]) const { const float4 a = g[2 * i], b = g[2 * i + 1]; unpack4(a, o); unpack4(b, o + 4); }
+};
+__global__ void __launch_bounds__(256)
+denoise_moments_variance_kernel(const float4* __restrict__ guide, int32_t W, int32_t H, const DenoiseSigma sg, float4* os, float4* om, float* __restrict__ v) {
+    __shared__ float2 win[kMomentsFoot * kMomentsFoot];
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    const int32_t nx = tiles_x(W);
+    const int32_t x0 = ((int32_t)blockIdx.x % nx) * 16 - kMomentsWindow, y0 = ((int32_t)blockIdx.x / nx) * 16 - kMomentsWindow;
+    for (int32_t f = (int32_t)threadIdx.x; f < kMomentsFoot * kMomentsFoot; f += 256) {
+        const int32_t x = x0 + f % kMomentsFoot, y = y0 + f / kMomentsFoot;
+        float2 pair = make_float2(0.0f, kMomentsOffFrame);
+        if (x >= 0 && x < W && y >= 0 && y < H) pair = *reinterpret_cast<const float2*>(&om[y * W + x].x);
+        win[f] = pair;
+    }
+    __syncthreads();
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    const float N = os[i].y, E = om[i].z;
+    const float S = moments_variance(MomentsWindowDev{ win, (q.py - y0) * kMomentsFoot + (q.px - x0) }, MomentsGuideDev{ guide }, W, q.px, q.py, N, sg);
+    const float V = S * E;
+    om[i].w = S;
+    os[i].x = V;
+    v[i] = V;
+}
+void launch_denoise_temporal_moments(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, const float* hist_moments,
+                                     bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, const DenoiseSigma& sg,
+                                     float* out_color, float* out_record, float* out_moments, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    const bool have = hist_color && hist_record && hist_moments;
+    hipLaunchKernelGGL(denoise_temporal_kernel<true>, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
+                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
+                       reinterpret_cast<const float4*>(hist_moments), have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color),
+                       reinterpret_cast<float4*>(out_record), reinterpret_cast<float4*>(out_moments));
+    hipLaunchKernelGGL(denoise_moments_variance_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(guide), W, H, sg,
+                       reinterpret_cast<float4*>(out_record), reinterpret_cast<float4*>(out_moments), v);
 }
 
 // The same with the rejection test (vr_temporal.h steps 2a, 3a; tau > 0 only), as two kernels, because a pixel's decision needs the z2 of its 5 x 5

@@ -11,6 +11,8 @@
 // mean's luminance, N the number of frames behind the pixel (a float, exact up to 2^24; 0 = none), K and D the coverage and depth of the frame
 // that wrote it.  With it goes the camera of that frame (pos', M' = cam_transform, cam_z' as RendererHIP::fill_params forms them).
 //
+// With "denoise_moments" = 1 the history also carries luminance moments, and V comes from them instead of from v: vr_moments.h.
+//
 // Pixel (px, py) of the current frame; c = its framebuffer colour, v = denoise_mean_variance of it, (k, d) = coverage and depth of its guide:
 //  1 Where it was.  The centre ray is feature_sample's expression with both jitters 0.5:
 //      f = (((px + 0.5) - W * 0.5) / H, ((py + 0.5) - H * 0.5) / H, cam_z), dir = normalize(mat3_mul(M, normalize(f)))
@@ -94,10 +96,12 @@ VR_HD bool temporal_reproject(const TemporalCamera& cur, const TemporalCamera& p
 // Steps 1-3 at pixel (px, py): the fetch.  Hist reads the previous history by pixel index y * W + x:
 //   void color(int32_t i, float c[4]) const;   void record(int32_t i, float s[4]) const;      (V, N, K, D)
 // have: a history exists; same_cam: its camera equals the current one byte for byte.  true: the pixel has a history, h, vh, nh are step 2's
-// h, v_h, N_h; false: they are 0.
-template <class Hist>
+// h, v_h, N_h; false: they are 0.  extra.tap(iq, b) is called for every tap that counts, in tap order, with its pixel index and bilinear weight: what
+// else the history carries per pixel is gathered from the same taps (vr_moments.h).
+struct TemporalNoExtra { VR_HD void tap(int32_t, float) {} };
+template <class Hist, class Extra>
 VR_HD bool temporal_fetch(const Hist& hist, bool have, bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H,
-                          int32_t px, int32_t py, float k, float d, float h[4], float& vh, float& nh_out) {
+                          int32_t px, int32_t py, float k, float d, float h[4], float& vh, float& nh_out, Extra& extra) {
     float hs[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     float bs = 0.0f, vs = 0.0f, nh = 0.0f;
     bool any = false;
@@ -129,6 +133,7 @@ VR_HD bool temporal_fetch(const Hist& hist, bool have, bool same_cam, const Temp
                 bs = bs + b;
                 nh = any ? min_(nh, s[1]) : s[1];
                 any = true;
+                extra.tap(iq, b);
             }
         }
     }
@@ -141,6 +146,12 @@ VR_HD bool temporal_fetch(const Hist& hist, bool have, bool same_cam, const Temp
     vh = vs / bs;
     nh_out = nh;
     return true;
+}
+template <class Hist>
+VR_HD bool temporal_fetch(const Hist& hist, bool have, bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H,
+                          int32_t px, int32_t py, float k, float d, float h[4], float& vh, float& nh_out) {
+    TemporalNoExtra none;
+    return temporal_fetch(hist, have, same_cam, cur, prev, W, H, px, py, k, d, h, vh, nh_out, none);
 }
 
 // Step 4 at a pixel: keep = the pixel has a history and it was not rejected; (h, vh, nh) its fetch.  Cout / Sout: the pixel's new history.

@@ -8,7 +8,7 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "wide_addressing")
+               "variance", "denoise_iterations", "denoise_moments", "wide_addressing")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
@@ -289,6 +289,14 @@ class Renderer:
         _lib.check(self._L.vr_denoise_reject_stat(self._h, out.ctypes.data))
         return out
 
+    def denoise_history_moments(self):
+        """[H][W][4] float32, row 0 = bottom: the history's moment records (m1, m2, E, S) -- integrated first and second moments of the frames' luminance,
+        the sum of squared blend weights, the variance of one frame's luminance.  Needs a history written with `denoise_moments = 1` (a change of that
+        field drops the history)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _lib.check(self._L.vr_denoise_history_moments(self._h, out.ctypes.data))
+        return out
+
     def denoise_history_reset(self):
         """Drops the history: the next denoise_temporal() starts afresh."""
         _lib.check(self._L.vr_denoise_history_reset(self._h))
@@ -512,6 +520,14 @@ class ShardedRenderer:
 
     def denoise_reject_stat(self):
         return self.parts[0].denoise_reject_stat()
+
+    @property
+    def denoise_moments(self):
+        """Whether the filter takes its variance from the history's luminance moments: part 0's field (set it on `parts[0]`, or on every part with `each`)."""
+        return self.parts[0].denoise_moments
+
+    def denoise_history_moments(self):
+        return self.parts[0].denoise_history_moments()
 
 
 def math_probe(fn, a, b=None):

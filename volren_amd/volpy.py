@@ -424,8 +424,8 @@ class Renderer:
     def __getattr__(self, name):
         if name == "variance":
             return self._r.get_int("variance")
-        if name == "denoise_reject":
-            return self._r.denoise_reject
+        if name in ("denoise_reject", "denoise_moments"):
+            return getattr(self._r, name)
         if name in _SCALARS:
             return getattr(self._r, name)
         if name in _VEC3S:
@@ -433,7 +433,7 @@ class Renderer:
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in _SCALARS or name in ("variance", "denoise_reject"):
+        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments"):
             setattr(self._r, name, value)
         elif name in _VEC3S:
             setattr(self._r, name, np.asarray(vec3(value) if np.ndim(value) == 0 else value, np.float32).reshape(3))
@@ -554,7 +554,9 @@ class Renderer:
     def denoise_temporal(self):
         """denoise() with the frame first blended into the history of the frames before it, reprojected by depth: once per frame, frames of
         equal spp (volren_amd.Renderer.denoise_temporal).  `denoise_reject` > 0 (3 is a good value; 0 = off, the default) makes a pixel whose history
-        disagrees with the frame beyond the noise of the two start afresh: a changing scene under a fixed camera no longer lags."""
+        disagrees with the frame beyond the noise of the two start afresh: a changing scene under a fixed camera no longer lags.  `denoise_moments = 1`
+        (default 0; a change drops the history; not together with `denoise_reject`) takes the filter's variance from luminance moments kept in the
+        history instead of the frames' sample variance: for sequences of 1 to a few spp, which have none."""
         self._r.denoise_temporal()
 
     def denoise_history_reset(self):
@@ -565,6 +567,11 @@ class Renderer:
         """(w, h) float: the rejection statistic of the last denoise_temporal() run with `denoise_reject` > 0 (-1: the pixel had no history), in
         fbo_data()'s shape (volren_amd.Renderer.denoise_reject_stat)."""
         return self._r.denoise_reject_stat().reshape(self._r.width, self._r.height)
+
+    def denoise_history_moments_data(self):
+        """(w, h, 4) float: the history's moment records (m1, m2, E, S) after a denoise_temporal() with `denoise_moments = 1`, in fbo_data()'s shape
+        (volren_amd.Renderer.denoise_history_moments)."""
+        return self._r.denoise_history_moments().reshape(self._r.width, self._r.height, 4)
 
     def denoised_data(self):
         """(w, h, 3) float: the colour of the last denoise() or denoise_temporal(), in fbo_data()'s shape."""
