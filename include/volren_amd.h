@@ -158,12 +158,25 @@ int vr_framebuffer_device(vr_renderer* r, void** device_ptr);
  *     computes samples 1..spp afresh.  Asynchronous on the renderer's stream; a flush point like vr_render.  Bounded like the path tracer: a
  *     segment whose ray parameter can no longer advance (a camera very far from the volume for its voxel size) ends without a collision, and
  *     a pixel whose segment exceeds a step budget stops there, which the next vr_synchronize reports as an error.
+ *     vr_render_features_expected fills the same buffer with the EXPECTED VALUES of those features instead of a sample mean: per pixel rays x rays
+ *     deterministic sub-rays (rays in 1..4, else VR_ERR_ARG; sub-ray (i, j) takes the jitters ((i + 0.5) / rays, (j + 0.5) / rays) in the camera
+ *     expression above), each marched through the volume's box in m = clamp(ceil(length in voxels), 1, 4096) equal steps of length h.  A step at
+ *     its midpoint t looks up the trilinear density, sigma = density_scale x it (with a LUT: sigma = LUT alpha x majorant, albedo x LUT rgb), and
+ *     weighs w = T (1 - exp(-sigma h)), T *= exp(-sigma h), until T <= 2^-10; the normal is -normalize(transpose(Minv3) g) with g the analytic
+ *     gradient of the trilinear interpolant.  With K = sum w: albedo = sum(w a) / K, coverage = K / rays^2, normal = sum(w n) / K, depth =
+ *     sum(w t) / K, zeros where K = 0 -- the limit of vr_render_features for spp -> infinity (without a LUT up to the tracker's smoother
+ *     stochastic-tricubic field), free of noise, independent of "seed", "integrator" and the emission grid, and bit-identical from call to call
+ *     under the same camera and scene.  All in float32 as volren_amd/csrc/vr_expected.h states it.  Asynchronous on the renderer's stream and a
+ *     flush point like vr_render_features; it counts as a feature pass for every call that needs one, and every reader of the feature buffer
+ *     (vr_features, vr_denoise, vr_denoise_temporal, vr_sharded_gather_guides, vr_render_adaptive's frames) reads it unchanged.  Bounded by
+ *     construction (at most 16 x 4096 steps per pixel): it never sets the status word.
  *     vr_features waits and writes W*H*8 floats (albedo.rgb, coverage, normal.xyz, depth), row 0 at the bottom; VR_ERR before the first
  *     vr_render_features since the last resize.
  *     vr_variance waits and writes W*H*4 floats: the unbiased per-channel variance of the samples 1..n behind the framebuffer (0 for n = 1),
  *     kept when vr_set_int "variance" is 1 (default 0; the buffer is allocated only then).  VR_ERR unless "variance" was on for every one of
  *     samples 1..n (switched on mid-frame: vr_reset and render again). */
 int vr_render_features(vr_renderer* r, int spp);
+int vr_render_features_expected(vr_renderer* r, int rays);
 int vr_features(vr_renderer* r, float* out);
 int vr_variance(vr_renderer* r, float* rgba_out);
 /* --- denoiser (no reference counterpart either: scripts/datagen_denoise.py exports the noisy colour for a denoiser of the caller's own).
@@ -305,6 +318,7 @@ const char* vr_sharded_collective(vr_sharded* s);         /* "gather" | "allgath
 int vr_sharded_reset(vr_sharded* s);                      /* vr_reset on every part */
 int vr_sharded_render(vr_sharded* s, int spp);
 int vr_sharded_render_features(vr_sharded* s, int spp);   /* spp >= 1, as vr_render_features */
+int vr_sharded_render_features_expected(vr_sharded* s, int rays);   /* rays in 1..4: vr_render_features_expected on every part that owns tiles, over its tiles */
 int vr_sharded_gather_guides(vr_sharded* s);
 int vr_sharded_denoise(vr_sharded* s);
 int vr_sharded_denoise_temporal(vr_sharded* s);

@@ -465,6 +465,12 @@ int vr_render_features(vr_renderer* r, int spp) {
     if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
     return guard([&] { use_device(r); r->impl.render_features(spp); });
 }
+int vr_render_features_expected(vr_renderer* r, int rays) {
+    NEED(r);
+    if (rays < 1 || rays > vr::kExpectedMaxRays) return fail(VR_ERR_ARG, "vr_render_features_expected: rays must be 1..4");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.render_features_expected(rays); });
+}
 int vr_features(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
@@ -666,6 +672,11 @@ int vr_sharded_render(vr_sharded* s, int spp) {
 int vr_sharded_render_features(vr_sharded* s, int spp) {
     if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
     return guard([&] { s->impl->render_features(spp); });
+}
+int vr_sharded_render_features_expected(vr_sharded* s, int rays) {
+    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    if (rays < 1 || rays > vr::kExpectedMaxRays) return fail(VR_ERR_ARG, "vr_sharded_render_features_expected: rays must be 1..4");
+    return guard([&] { s->impl->render_features_expected(rays); });
 }
 int vr_sharded_gather_guides(vr_sharded* s) {
     if (!s) return fail(VR_ERR_ARG, "null sharded renderer");

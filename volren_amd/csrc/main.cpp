@@ -12,6 +12,8 @@
 // --denoise-reject T with it: a pixel whose history disagrees with its frame beyond the noise of the two starts afresh (vr_temporal.h 2a, 3a; refused alone).
 // --denoise-moments with it: the filter's variance comes from luminance moments kept in the history (vr_moments.h), for runs of 1 to a few spp per
 // frame (refused alone and with --denoise-reject above 0).
+// --expected-features N with any of them: the guide is the noise-free expected-value pass of N x N rays per pixel (vr_expected.h; N in 1..4) instead of
+// the sampled feature pass (refused without a denoise flag).
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
 // the mean samples per pixel; combines with --denoise (one device only).
 //
@@ -126,7 +128,7 @@ static void parse_cmd(int argc, char** argv) {
         } else if (arg == "--vol_crop_min") { renderer->vol_clip_min.x = a.nextf(); renderer->vol_clip_min.y = a.nextf(); renderer->vol_clip_min.z = a.nextf(); }
         else if (arg == "--vol_crop_max") { renderer->vol_clip_max.x = a.nextf(); renderer->vol_clip_max.y = a.nextf(); renderer->vol_clip_max.z = a.nextf(); }
         else if (arg == "--seed") renderer->seed = a.nexti();                        // addition
-        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject") a.next();  // consumed earlier
+        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject" || arg == "--expected-features") a.next();  // consumed earlier
         else if (fs::is_regular_file(arg) || fs::is_directory(arg)) handle_path(arg);
     }
 }
@@ -169,6 +171,7 @@ int main(int argc, char** argv) {
     int width = 1280, height = 720, device = 0, gpus = 0;        // cppgl ContextParameters defaults (unverified): always pass -w/-h
     bool denoise = false, temporal = false, adaptive = false;      // temporal: --denoise with the history kept across the frames of the run
     float threshold = 0.f, reject = 0.f;      // reject: --denoise-reject, the history rejection threshold of --denoise-temporal (0 = off)
+    int expected_rays = 0;      // --expected-features N: the denoise flags take their guide from render_features_expected(N) instead of render_features(min(spp, 16))
     bool reject_given = false, moments = false;      // moments: --denoise-moments, the filter's variance from the history's luminance moments (low-spp sequences)
     std::vector<int> devices;
     try {
@@ -188,6 +191,10 @@ int main(int argc, char** argv) {
                 reject = std::stof(argv[++i]);
                 if (!(reject == 0.f || (reject >= kTemporalRejectMin && reject <= kTemporalRejectMax)))
                     throw std::runtime_error("--denoise-reject: the threshold must be 0 (off) or in [2^-10, 2^20]");
+            } else if (arg == "--expected-features") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-features");
+                expected_rays = std::stoi(argv[++i]);
+                if (expected_rays < 1 || expected_rays > kExpectedMaxRays) throw std::runtime_error("--expected-features: the rays per pixel axis must be 1..4");
             } else if (arg == "--adaptive") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --adaptive");
                 adaptive = true;
@@ -196,6 +203,7 @@ int main(int argc, char** argv) {
             }
         }
         if (reject_given && !temporal) throw std::runtime_error("--denoise-reject needs --denoise-temporal: it rejects the history that only that call keeps");
+        if (expected_rays > 0 && !denoise) throw std::runtime_error("--expected-features needs --denoise or --denoise-temporal: it chooses the guide of their filter");
         if (moments && !temporal) throw std::runtime_error("--denoise-moments needs --denoise-temporal: the moments live in the history that only that call keeps");
         if (moments && reject > 0.f) throw std::runtime_error("--denoise-moments and --denoise-reject do not go together: the rejection statistic needs the frames' sample variance");
         if (adaptive && (gpus > 0 || devices.size() > 1))
@@ -275,7 +283,8 @@ int main(int argc, char** argv) {
             VR_HIP(hipSetDevice(devices[0]));
             renderer->tonemapping = true;               // the offline loop always tonemaps (main.cpp:540-550)
             if (denoise) {
-                renderer->render_features(std::min(renderer->sppx, 16));
+                if (expected_rays > 0) renderer->render_features_expected(expected_rays);
+                else renderer->render_features(std::min(renderer->sppx, 16));
                 if (temporal) renderer->denoise_temporal();      // the first frame: what denoise() gives
                 else renderer->denoise();
                 renderer->synchronize();

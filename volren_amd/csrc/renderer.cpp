@@ -834,13 +834,14 @@ void RendererHIP::download_display(float* rgba) const {
 // The feature pass reads the scene as a render() would: capture() (which also decodes the float atlas under a transfer function) and the majorant
 // table of the current density scale and LUT.  It runs the lane code of the run-time kernel variant, which reads every grid from its own atlas:
 // the views of a frame whose grids share a paired atlas are made again without it (the majorant layout stays the one the table is built in).
-void RendererHIP::render_features(int spp) {
-    if (spp <= 0) throw std::runtime_error("render_features: spp must be positive");
+// begin_feature_pass: what both feature passes do before their launch -- P = that scene; the feature buffer exists (zero-filled when it is new); returns the
+// number of tiles of the tile set.
+int RendererHIP::begin_feature_pass(SceneParams& P) {
     flush_pending();
     LaunchInputs in;
     capture(in);
     update_majorants(in, density_grids.at(in.frame));
-    SceneParams P = in.P;
+    P = in.P;
     if (P.paired) {
         P.density = make_view(density_grids.at(in.frame), false, P.density.maj_blocked != 0);
         P.emission = make_view(emission_grids.at(in.frame), false);
@@ -851,7 +852,23 @@ void RendererHIP::render_features(int spp) {
     if (ensure_buffer(features_, bytes)) {
         VR_HIP(hipMemsetAsync(features_->get(), 0, bytes, stream));
     }
+    return n_tiles;
+}
+
+void RendererHIP::render_features(int spp) {
+    if (spp <= 0) throw std::runtime_error("render_features: spp must be positive");
+    SceneParams P;
+    const int n_tiles = begin_feature_pass(P);
     launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, features_->as<float>(), status_->as<uint32_t>(), stream);
+    VR_HIP(hipGetLastError());
+}
+
+// The expected values of the same features (vr_expected.h), into the same buffer: whatever reads the feature buffer reads either pass's output.
+void RendererHIP::render_features_expected(int rays) {
+    if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("render_features_expected: rays must be 1.." + std::to_string(kExpectedMaxRays));
+    SceneParams P;
+    const int n_tiles = begin_feature_pass(P);
+    launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, features_->as<float>(), stream);
     VR_HIP(hipGetLastError());
 }
 

@@ -172,7 +172,11 @@ struct RendererHIP {
     // Denoiser data.  render_features(spp): the first-scatter features of samples 1..spp of every pixel of the tile set (vr_trace.h feature_pixel),
     // computed afresh into their own W*H*8 buffer (asynchronous; flushes recorded samples first).  download_features: that buffer, W*H*8 floats.
     // download_variance: the unbiased per-channel variance of samples 1..sample, W*H*4 floats -- needs `variance` on for all of them.
+    // render_features_expected(rays): the expected values of the same features from rays x rays deterministic ray marches per pixel (vr_expected.h
+    // expected_pixel; rays in 1..4) into the same buffer -- the limit of render_features for spp -> infinity, without noise, at a cost independent of spp.
+    // Counts as a feature pass for everything that needs one.
     void render_features(int spp);
+    void render_features_expected(int rays);
     // test hook (vr_probe.h): n items of probe `what` in compile-time form `form`, host arrays in (4 words per item) and out (probe_out_words floats per item), run by
     // probe_kernel on the SceneParams the next launch would get -- after capture() (float atlas) and update_majorants, with the paired atlas where a kernel reads it.
     // Throws for a form the scene cannot serve.  Synchronous; touches no framebuffer.
@@ -215,6 +219,7 @@ struct RendererHIP {
     // calls need no flush by the caller: the next trace() sees bytes that differ from the recorded ones and launches the recorded samples first,
     // with the values they were recorded with.
     void flush_pending();
+    int begin_feature_pass(SceneParams& P);      // the common head of render_features / render_features_expected (renderer.cpp)
     int pending_samples() const { return pending_n_; }         // samples recorded by trace() and not launched yet
     bool coalesce_trace = true;                                // false: every trace() is its own launch (round 4's behaviour; A/B and tests)
     double last_kernel_ms();                                    // HIP-event time of the last launch (a render(), or the trace() calls coalesced into one): all sub-launches, path tracing + accumulation (waits for it)

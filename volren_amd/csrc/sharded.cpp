@@ -294,15 +294,22 @@ void ShardedRenderer::render(int spp) {
 }
 
 // ---- denoising (renderer.h render_features / denoise / denoise_temporal on several devices) --------------------------------------------------------
-void ShardedRenderer::render_features(int spp) {
-    if (spp <= 0) throw std::runtime_error("ShardedRenderer::render_features: spp must be positive");
-    prepare("render_features");
+void ShardedRenderer::feature_pass_on_parts(const char* who, const std::function<void(RendererHIP&)>& pass) {
+    prepare(who);
     issue_on_parts([&](size_t i) {
         VR_HIP(hipSetDevice(devices_[i]));
         RendererHIP& p = *parts_[i];
-        if (p.stream != buf_[i].stream) throw std::runtime_error("ShardedRenderer::render_features: a part's stream was changed behind the sharded renderer");
-        if (transport_ == "none" || buf_[i].n_own > 0) p.render_features(spp);      // no tile of its own: no features either (an empty tile set would mean the whole frame)
+        if (p.stream != buf_[i].stream) throw std::runtime_error(std::string("ShardedRenderer::") + who + ": a part's stream was changed behind the sharded renderer");
+        if (transport_ == "none" || buf_[i].n_own > 0) pass(p);      // no tile of its own: no features either (an empty tile set would mean the whole frame)
     });
+}
+void ShardedRenderer::render_features(int spp) {
+    if (spp <= 0) throw std::runtime_error("ShardedRenderer::render_features: spp must be positive");
+    feature_pass_on_parts("render_features", [spp](RendererHIP& p) { p.render_features(spp); });
+}
+void ShardedRenderer::render_features_expected(int rays) {
+    if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("ShardedRenderer::render_features_expected: rays must be 1.." + std::to_string(kExpectedMaxRays));
+    feature_pass_on_parts("render_features_expected", [rays](RendererHIP& p) { p.render_features_expected(rays); });
 }
 
 // What the guide gather and the filter need of every part, asked before anything is launched: a call that throws here has changed nothing.

@@ -53,7 +53,9 @@ struct ShardedRenderer {
     // deterministic per pixel and part 0 runs it on the gathered whole frame.  Asynchronous like render(); no host synchronisation is needed anywhere in
     // reset, render, render_features, denoise, reset, render, ... (stream order and the exchange's events keep the frames apart).
     // render_features: every part that owns tiles runs its feature pass over them on its own stream (one host thread per part); no exchange.
+    // render_features_expected: the same with every part's render_features_expected(rays), rays in 1..4.
     void render_features(int spp);
+    void render_features_expected(int rays);
     // gather_guides: every part's moments and features of its own tiles -> part 0's moments and features, which then cover the whole frame
     // (part(0).download_variance / download_features): one pack per part, ONE exchange of 3x the colour's size through the transport render() uses,
     // one unpack on part 0.  The buffers are allocated by the first call at a resolution: a caller that only renders pays nothing.
@@ -74,6 +76,7 @@ private:
     void setup(int width, int height);   // tile deal + buffers for the current resolution
     void prepare(const char* who);        // throws unless the parts agree on resolution and sample; setup() on a new resolution
     void issue_on_parts(const std::function<void(size_t)>& issue);
+    void feature_pass_on_parts(const char* who, const std::function<void(RendererHIP&)>& pass);      // `pass` on every part that owns tiles, on its device
     void check_guides(const char* who);   // what gather_guides and the filter need of every part, before the first launch
     void exchange_guides();               // gather_guides after the checks
     void run_denoise(const char* who, bool temporal);

@@ -41,6 +41,10 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
 // status: the renderer's status word; a pixel whose tracker exceeded its step budget sets kFeatureLostStatus there (its remaining samples are not run).
 constexpr uint32_t kFeatureLostStatus = 4u;
 void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream);
+// The same buffer, same tiles, filled with the expected values of those features instead: rays x rays deterministic ray marches per pixel (vr_expected.h
+// expected_pixel), rays in 1..kExpectedMaxRays.  Bounded by construction: no status word.
+constexpr int32_t kExpectedMaxRays = 4;
+void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream);
 // which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
 // what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
 enum PathtraceVariantReason : int {

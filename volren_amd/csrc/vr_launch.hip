@@ -1,4 +1,4 @@
-// vr_launch.hip -- launch of the volume path tracer (gfx950): launch_pathtrace and launch_features.
+// vr_launch.hip -- launch of the volume path tracer (gfx950): launch_pathtrace, launch_features and launch_features_expected.
 //
 // pathtrace_kernel (the hot path): the per-path code -- the reference's trace_path and everything it calls, restated as a state
 // machine -- is in vr_trace.h, its scheduler (persistent wavefronts that pull work units of 8x8 pixels x 8 samples) in vr_pathtrace.h and
@@ -19,6 +19,7 @@
 #include <string>
 
 #include "vr_device.h"
+#include "vr_expected.h"
 #include "vr_pathtrace.h"
 
 namespace vr {
@@ -94,6 +95,28 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
     if (n_tiles <= 0 || spp <= 0) return;
     if (P.u.use_tf) hipLaunchKernelGGL(features_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
     else hipLaunchKernelGGL(features_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, spp, out, status);
+}
+
+// The same buffer filled with expected values instead of sample means (vr_expected.h expected_pixel): one thread per pixel on the same tiles, rays x rays
+// deterministic marches of at most kExpectedMaxSteps steps each -- a bounded loop, so no status word.  An 8x8 patch of neighbouring rays walks the same bricks
+// nearly in lockstep: a step's eight corner taps mostly hit lines a neighbouring lane has just loaded, and trip counts differ only at silhouettes.  The LUT is read
+// from global memory: its two rows per step are shared by neighbouring lanes too, and the kernel keeps its registers and LDS for occupancy.
+template <bool TF>
+__global__ void __launch_bounds__(256)
+features_expected_kernel(const SceneParams P, const int32_t* __restrict__ tiles, int32_t rays, float* __restrict__ out) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const TilePixel q = wave_tiled_pixel(tiles ? tiles[blockIdx.x] : (int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    float f[8];
+    expected_pixel<TF>(P, q.px, q.py, rays, f);
+    float4* o = reinterpret_cast<float4*>(out) + 2u * ((size_t)q.py * W + q.px);
+    o[0] = pack4(f);
+    o[1] = pack4(f + 4);
+}
+void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream) {
+    if (n_tiles <= 0 || rays < 1 || rays > kExpectedMaxRays) return;
+    if (P.u.use_tf) hipLaunchKernelGGL(features_expected_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, rays, out);
+    else hipLaunchKernelGGL(features_expected_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, rays, out);
 }
 
 // Units of 8 samples x 64 pixels, except on the dense-grid kernel, whose long paths (128 bounces, every camera ray scatters) fill

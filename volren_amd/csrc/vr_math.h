@@ -52,6 +52,7 @@ VR_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
 
 VR_HD float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 VR_HD float floor_(float x) { return __builtin_floorf(x); }
+VR_HD float ceil_(float x) { return __builtin_ceilf(x); }
 VR_HD float sqrt_(float x) { return __builtin_sqrtf(x); }
 VR_HD float abs_(float x) { return __builtin_fabsf(x); }
 // 1.0f / x, correctly rounded.  On the device: v_rcp_f32 (1 ulp) + one Newton step + v_div_fixup_f32 -- 4 instructions instead of the 10 of

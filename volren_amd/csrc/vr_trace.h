@@ -462,6 +462,24 @@ VR_HD float trilinear_value(const GridView& g, const TriIO& io) {
     const float hx1 = mix_(v[6], v[7], io.fx);
     return mix_(mix_(lx0, lx1, io.fy), mix_(hx0, hx1, io.fy), io.fz);
 }
+// The gradient of the same interpolant, from the same eight corner values and weights (no further loads): per axis the difference along it, mixed over
+// the two others.  In voxel units, piecewise constant along its own axis.
+template <int DENSE = 2>
+VR_HD v3 trilinear_gradient(const GridView& g, const TriIO& io) {
+    float v[8];
+    if (!grid_is_dense<DENSE>(g) && g.atlas_f32) {
+#pragma unroll
+        for (int n = 0; n < 8; ++n) v[n] = ((io.in_mask >> n) & 1u) ? u2f(io.d[n].raw) : 0.0f;
+    } else {
+#pragma unroll
+        for (int n = 0; n < 8; ++n) v[n] = tap_value<DENSE>(g, io.d[n], (io.in_mask >> n) & 1u);
+    }
+    v3 r;
+    r.x = mix_(mix_(v[1] - v[0], v[3] - v[2], io.fy), mix_(v[5] - v[4], v[7] - v[6], io.fy), io.fz);
+    r.y = mix_(mix_(v[2] - v[0], v[3] - v[1], io.fx), mix_(v[6] - v[4], v[7] - v[5], io.fx), io.fz);
+    r.z = mix_(mix_(v[4] - v[0], v[5] - v[1], io.fx), mix_(v[6] - v[2], v[7] - v[3], io.fx), io.fy);
+    return r;
+}
 template <int DENSE = 2>
 VR_HD float density_trilinear_raw(const GridView& g, v3 ipos) {
     TriIO io;

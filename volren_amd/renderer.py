@@ -247,6 +247,13 @@ class Renderer:
         if sync:
             self.synchronize()
 
+    def render_features_expected(self, rays=2, sync=True):
+        """The expected values of the same features from rays x rays deterministic ray marches per pixel, rays in 1..4 (include/volren_amd.h
+        vr_render_features_expected): no noise, no dependence on spp or seed; fills the buffer features() and the denoiser read."""
+        _lib.check(self._L.vr_render_features_expected(self._h, int(rays)))
+        if sync:
+            self.synchronize()
+
     def features(self):
         """[H][W][8] float32, row 0 = bottom: albedo.rgb, coverage, normal.xyz, depth."""
         out = np.empty((self.height, self.width, 8), np.float32)
@@ -474,6 +481,12 @@ class ShardedRenderer:
     def render_features(self, spp, sync=True):
         """Renderer.render_features on every part that owns tiles, over its tiles (vr_sharded_render_features); no exchange."""
         _lib.check(self._L.vr_sharded_render_features(self._h, int(spp)))
+        if sync:
+            self.synchronize()
+
+    def render_features_expected(self, rays=2, sync=True):
+        """Renderer.render_features_expected on every part that owns tiles, over its tiles (vr_sharded_render_features_expected); no exchange."""
+        _lib.check(self._L.vr_sharded_render_features_expected(self._h, int(rays)))
         if sync:
             self.synchronize()
 

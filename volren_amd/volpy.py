@@ -538,6 +538,10 @@ class Renderer:
         """First-scatter features of samples 1..spp, computed afresh (`seed` as for colour: feature sample s belongs to colour sample s)."""
         self._r.render_features(int(spp))
 
+    def render_features_expected(self, rays=2):
+        """The same features as expected values: rays x rays deterministic ray marches per pixel (1..4), noise-free and independent of `seed`."""
+        self._r.render_features_expected(int(rays))
+
     def feature_data(self):
         """(w, h, 8) float: albedo.rgb, coverage, normal.xyz, depth."""
         return self._r.features().reshape(self._r.width, self._r.height, 8)
