@@ -94,6 +94,15 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     "tf_float_atlas" (default 1: transfer-function renders of brick grids decode the atlas to floats once, 4x its size; 0 = read the bytes)
  *     "grid_frame_counter"
  *     "sample_pool_mb" (HBM budget of the per-sample radiance pool, 16 .. 65536, default 65536: allocated only as large as a launch needs)
+ *     "seed_table_mb" (HBM budget of the renderer's path-seed table, 0 .. 8192, 0 = no table, -1 = back to the default min(4096, "sample_pool_mb" / 4), which
+ *     vr_get_int reports as that number.  A new path's RNG state is a 32-round hash of (seed, width, pixel, sample number) only; the renderer keeps the hashes of
+ *     the whole frame's first samples, 4 bytes per pixel of the 16x16-tile grid and sample, and the path-tracing kernel reads them instead of hashing.  The table is
+ *     keyed by (seed, width, height): vr_reset keeps it, a change of one of the three drops it; it grows to the samples the launches have asked for, up to the
+ *     budget, and the samples beyond are hashed as before, as are all samples of scenes whose kernel is no faster with the table (dense grids, emission grids,
+ *     "kernel_variant" != 0: their launches make none).  A table that cannot be allocated is given up with one note on stderr: no render fails for it.  The parts
+ *     of a sharded renderer hold a table each, indexed by the whole frame's tiles, so parts that share a device cover the same samples once per part.
+ *     Results never depend on the table)
+ *     "seed_table_max_samples" (default 0 = as many samples per pixel as "seed_table_mb" holds; > 0: at most this many, the samples beyond hash in the kernel)
  *     "launch_target_ms" (default 2000: a vr_render is split into sub-launches planned to take at most this long each, from the rate this
  *     renderer measured last -- a short probe launch, one synchronisation, when it has none for the current settings and the request is
  *     large; 0 = split by the sample pool alone.  Results never depend on the split)
@@ -104,7 +113,8 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     main.cpp:382) "tf_window_left" "tf_window_width" "cam_pos"(3) "cam_dir"(3) "cam_up"(3) "cam_fov" "volume_transform"(16)
  *     "denoise_sigma"(5: the edge-stopping widths of vr_denoise for colour, normal, depth, coverage, albedo; each in [2^-60, 2^60], about
  *     [8.7e-19, 1.15e18]: VR_ERR otherwise, the old values kept; default 4, 0.5, 0.1, 0.25, 0.2) (float) */
-/* read-only through vr_get_int: "kernel_variant" (the compiled path-tracing kernel the next launch uses: 0 brick grid, 1 dense fp16 grid, 2 / 4 brick grid +
+/* read-only through vr_get_int: "seed_table_samples" (samples 1 .. this of every pixel have their seeds in the table now; 0 = no table) and "seed_table_fills"
+ *     (fill launches of this renderer so far: a frame that repeats the last one's seed, size and samples adds none);  "kernel_variant" (the compiled path-tracing kernel the next launch uses: 0 brick grid, 1 dense fp16 grid, 2 / 4 brick grid +
  *     emission grid, 3 everything decided at run time -- correct for every scene, up to an order of magnitude slower) and "kernel_variant_reason" (what sent the
  *     scene to variant 3, a mask: 1 integrator != 0, 2 the environment's warp table has thresholds below 2^-76 ("env_div_safe" = 0), 4 density scale outside
  *     [2^-16, 2^24], 8 emission grid with a dense grid / brick grids of different layouts; 0: the scene has a kernel of its own kind).  Reasons 2 and 4 are also
@@ -326,6 +336,10 @@ int vr_sharded_synchronize(vr_sharded* s);
 /* the tile deal itself (host only, needs no device): owner_out[t] = the part (0 .. n_parts-1) that renders raster tile t of a width x height frame,
  * t = ty * ceil(width / 16) + tx, row 0 = bottom; n_tiles must be ceil(width / 16) * ceil(height / 16) */
 int vr_tile_owners(int width, int height, int n_parts, int32_t* owner_out, int n_tiles);
+/* the seed table's arithmetic (host only, needs no device): the default "seed_table_mb" of a renderer whose "sample_pool_mb" is sample_pool_mb, and the
+ * samples per pixel a budget of mb MiB covers on a width x height frame (4 bytes x 256 x ceil(width / 16) x ceil(height / 16) per sample) */
+int vr_seed_table_default_mb(int sample_pool_mb);
+int vr_seed_table_samples_for(int mb, int width, int height);
 /* the uniform block the next launch would use (struct vr::Uniforms of volren_amd/csrc/vr_scene.h, `bytes` must match) */
 int vr_get_uniforms(vr_renderer* r, void* out, int bytes);
 int vr_uniforms_size(void);

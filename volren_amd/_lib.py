@@ -23,6 +23,7 @@ SYMBOLS = [
     "vr_render_features", "vr_render_features_expected", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
     "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history", "vr_denoise_reject_stat", "vr_denoise_history_moments",
     "vr_render_adaptive", "vr_tile_samples", "vr_tile_error",
+    "vr_seed_table_default_mb", "vr_seed_table_samples_for",
     "vr_sharded_render_features", "vr_sharded_render_features_expected", "vr_sharded_gather_guides", "vr_sharded_denoise", "vr_sharded_denoise_temporal",
 ]
 
@@ -129,6 +130,8 @@ def load():
     L.vr_sharded_denoise.argtypes = [vp]
     L.vr_sharded_denoise_temporal.argtypes = [vp]
     L.vr_tile_owners.argtypes = [ci, ci, ci, vp, ci]
+    L.vr_seed_table_default_mb.argtypes = [ci]
+    L.vr_seed_table_samples_for.argtypes = [ci, ci, ci]
     L.vr_wave_timeline.argtypes = [vp, vp, ci]
     _lib = L
     return L

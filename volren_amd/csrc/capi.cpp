@@ -300,6 +300,11 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
         else if (n == "wide_addressing") { if (v < 0 || v > 1) throw std::runtime_error("wide_addressing: 0 (by the tables' sizes), 1 (always the kernels with 64-bit gather addresses)"); R.tuning.wide_addressing = v; }
         else if (n == "gpu_encoder") R.gpu_encoder = v != 0;
         else if (n == "sample_pool_mb") { if (v < 16 || v > 65536) throw std::runtime_error("sample_pool_mb must be in [16, 65536] (item indices of a sub-launch are 32-bit: < 2^32 RGBA32F items)"); R.sample_pool_bytes = (size_t)v << 20; }
+        else if (n == "seed_table_mb") {
+            if (v < -1 || v > vr::RendererHIP::kSeedTableMaxMb) throw std::runtime_error("seed_table_mb must be in [0, 8192] (0 = no table), or -1 for the default min(4096, sample_pool_mb / 4)");
+            R.seed_table_mb = v;
+        }
+        else if (n == "seed_table_max_samples") { if (v < 0) throw std::runtime_error("seed_table_max_samples must be >= 0 (0 = as many as seed_table_mb holds)"); R.seed_table_max_samples = v; }
         else if (n == "launch_target_ms") { if (v < 0) throw std::runtime_error("launch_target_ms must be >= 0 (0 = no sizing by time)"); R.launch_target_ms = v; }
         else if (n == "order_tiles") { if (v < 0 || v > 2) throw std::runtime_error("order_tiles: 0 (never), 1 (tile subsets), 2 (always)"); R.order_tiles = v; }
         else if (n == "grid_frame_counter") {
@@ -347,6 +352,10 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
         else if (n == "tf_float_atlas") *v = R.tf_float_atlas ? 1 : 0;
         else if (n == "gpu_encoder") *v = R.gpu_encoder ? 1 : 0;
         else if (n == "sample_pool_mb") *v = (int)(R.sample_pool_bytes >> 20);
+        else if (n == "seed_table_mb") *v = R.seed_table_budget_mb();
+        else if (n == "seed_table_max_samples") *v = R.seed_table_max_samples;
+        else if (n == "seed_table_samples") *v = R.seed_table_samples();
+        else if (n == "seed_table_fills") *v = R.seed_table_fills();
         else if (n == "launch_target_ms") *v = R.launch_target_ms;
         else if (n == "order_tiles") *v = R.order_tiles;
         else if (n == "grid_frame_counter") *v = R.volume ? (int)R.volume->grid_frame_counter : 0;
@@ -704,6 +713,10 @@ int vr_tile_owners(int width, int height, int n_parts, int32_t* owner_out, int n
             for (int32_t t : lists[p]) owner_out[t] = (int32_t)p;
     });
 }
+
+// seed table (renderer.h): the default budget for a sample pool of `sample_pool_mb`, and the sample numbers a budget of `mb` covers on a frame (host only)
+int vr_seed_table_default_mb(int sample_pool_mb) { return sample_pool_mb < 0 ? 0 : vr::RendererHIP::seed_table_default_mb(sample_pool_mb); }
+int vr_seed_table_samples_for(int mb, int width, int height) { return vr::RendererHIP::seed_table_samples_for(mb, width, height); }
 
 int vr_uniforms_size(void) { return (int)sizeof(vr::Uniforms); }
 int vr_get_uniforms(vr_renderer* r, void* out, int bytes) {

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <mutex>
 
 #include "vr_adaptive.h"
 #include "vr_device.h"
@@ -32,6 +33,7 @@ RendererHIP::~RendererHIP() {
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     for (hipEvent_t e : pt_events_) (void)hipEventDestroy(e);
+    if (seed_event_) (void)hipEventDestroy(seed_event_);
 }
 
 void RendererHIP::init() {
@@ -63,6 +65,7 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     drop_history();
     dn_reject_.reset(); reject_stat_ = false;
     drop_tile_samples(); tile_n_dev_.reset(); adaptive_lists_.reset(); adaptive_err_.reset();
+    drop_seed_table();                                           // keyed by the frame size
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
 }
@@ -693,7 +696,10 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
             eb = pt_events_[pt_events_used_]; ee = pt_events_[pt_events_used_ + 1];
             pt_events_used_ += 2;
         }
-        launch_pathtrace(in.tuning, P, color->as<float>(), pool_->as<float>(), workspace_->as<float>(), status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m, status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments);
+        int seed_samples = 0;
+        const uint32_t* seed_table = pathtrace_reads_seed_table(in.tuning, P) ? seed_table_for(P, first + done, m, stream, &seed_samples) : nullptr;
+        launch_pathtrace(in.tuning, P, color->as<float>(), pool_->as<float>(), workspace_->as<float>(), status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m, status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments,
+                         seed_table, seed_samples);
         VR_HIP(hipGetLastError());
         done += m;
         if (pt_kernel) { rate_pending_samples_ = px_samples * (double)m; rate_pending_key_ = key; }
@@ -705,6 +711,68 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     }
     VR_HIP(hipEventRecord(ev1_, stream));
     timing_pending_ = true;
+}
+
+// ---- seed table (renderer.h) ------------------------------------------------------------------------------------------------------------------
+int RendererHIP::seed_table_samples_for(long long mb, int w, int h) {
+    if (mb <= 0 || w <= 0 || h <= 0) return 0;
+    const long long per_sample = (long long)tile_count(w, h) * 256 * (long long)sizeof(uint32_t);
+    return (int)std::min<long long>((mb << 20) / per_sample, 1 << 24);
+}
+
+void RendererHIP::drop_seed_table() {
+    seed_table_.reset();                               // (freeing device memory waits for the work that reads it)
+    seed_cap_ = seed_filled_ = 0;
+    seed_failed_ = false;
+}
+
+const uint32_t* RendererHIP::seed_table_for(const SceneParams& P, int s0, int n, hipStream_t stream, int* samples) {
+    *samples = 0;
+    const int W = P.u.resolution[0], H = P.u.resolution[1], budget_mb = seed_table_budget_mb();
+    if (seed_key_[0] != P.u.seed || seed_key_[1] != W || seed_key_[2] != H || seed_budget_mb_ != budget_mb || seed_max_samples_ != seed_table_max_samples) {
+        drop_seed_table();
+        seed_key_[0] = P.u.seed; seed_key_[1] = W; seed_key_[2] = H; seed_budget_mb_ = budget_mb; seed_max_samples_ = seed_table_max_samples;
+    }
+    int max_samples = seed_table_samples_for(budget_mb, W, H);
+    if (seed_table_max_samples > 0) max_samples = std::min(max_samples, seed_table_max_samples);
+    if (max_samples <= 0 || (seed_failed_ && !seed_table_) || s0 < 0 || n <= 0) return nullptr;
+    const size_t per_sample = (size_t)tile_count(W, H) * 256u * sizeof(uint32_t);
+    const int want = (int)std::min<long long>((long long)s0 + n, max_samples);
+    if (!seed_event_) VR_HIP(hipEventCreateWithFlags(&seed_event_, hipEventDisableTiming));
+    // a launch on another stream than the last fill's: ordered behind that fill
+    if (seed_table_ && seed_filled_ > 0 && stream != seed_stream_) { VR_HIP(hipStreamWaitEvent(stream, seed_event_, 0)); seed_stream_ = stream; }
+    if (want > seed_cap_ && !seed_failed_) {
+        // grow: at least double (a caller that asks for one sample more per call does not pay an allocation per call), the filled prefix moves over
+        const int cap = (int)std::min<long long>(max_samples, std::max<long long>(want, 2ll * seed_cap_));
+        DeviceBufferPtr grown;
+        try { grown = make_device_buffer((size_t)cap * per_sample); }
+        catch (const std::exception& e) {
+            (void)hipGetLastError();
+            seed_failed_ = true;
+            static std::once_flag once;
+            std::call_once(once, [&] { fprintf(stderr, "volren_amd: note: no memory for the path-seed table (%zu MiB: %s); new paths hash their seeds (slower; results unchanged)\n", ((size_t)cap * per_sample) >> 20, e.what()); });
+            if (!seed_table_) return nullptr;
+        }
+        if (grown) {
+            // test hook (see submit): no launch may depend on what an entry held before its fill
+            if (const char* e = std::getenv("VR_TEST_POISON_WORKSPACE"); e && *e == '2') VR_HIP(hipMemsetAsync(grown->get(), 0xFF, grown->size_bytes(), stream));
+            if (seed_filled_ > 0) VR_HIP(hipMemcpyAsync(grown->get(), seed_table_->get(), (size_t)seed_filled_ * per_sample, hipMemcpyDeviceToDevice, stream));
+            if (seed_table_) VR_HIP(hipStreamSynchronize(stream));      // the copy has left the old buffer before it goes
+            seed_table_ = grown;
+            seed_cap_ = cap;
+        }
+    }
+    const int upto = std::min(want, seed_cap_);
+    if (upto > seed_filled_) {
+        launch_seed_fill(seed_table_->as<uint32_t>(), (uint32_t)P.u.seed, W, H, seed_filled_, upto, stream);
+        VR_HIP(hipGetLastError());
+        VR_HIP(hipEventRecord(seed_event_, stream));
+        seed_stream_ = stream;
+        seed_filled_ = upto;
+        ++seed_fills_;
+    }
+    *samples = seed_filled_;
+    return seed_filled_ > 0 ? seed_table_->as<uint32_t>() : nullptr;
 }
 
 // rate of the last path-tracing sub-launch that was enqueued, if it has finished (wait: block until it has)

@@ -14,6 +14,7 @@
 //   * set_tiles(): restrict a renderer to a subset of 16x16 framebuffer tiles (multi-GPU sharding).
 #pragma once
 
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -166,6 +167,25 @@ struct RendererHIP {
                                                       // a 2048^2 x 4096-spp frame is 5 sub-launches instead of 16 and each one's drain (4-8 ms) is paid that much less often: c5full +2.2 %,
                                                       // c4 at 1920x1080x4096 +0.9 % (tests/tools_pool_ab.py)
 
+    // Path-seed table.  A new path's RNG state is a 32-round hash of (seed, W, pixel, sample number) and of nothing else, and those stay the same from frame to
+    // frame -- progressive refinement starts over at sample 1 after every camera move, a script renders frame after frame at one seed and size -- so the renderer
+    // keeps the hashes of the whole frame's first samples in a device table (vr_tiles.h seed_table_index; 4 bytes per pixel of the tile grid and sample) and the
+    // path-tracing kernel reads a seed where it would compute it.  The table is keyed by (seed, W, H): reset() keeps it, a change of any of the three drops it.  It
+    // grows to the sample numbers launches have asked for, up to the budget; before a launch the part of its sample range that is not covered yet is filled on the
+    // launch's stream.  Samples beyond the budget hash in the kernel, as do the feature passes, the other integrators and the kernels that measured no faster with
+    // it (dense grids, emission grids, the run-time variant: vr_pathtrace.h seed_request_point) always -- their launches make no table; a table that cannot be
+    // allocated is given up (said once) and the renderer hashes as before: no render fails for it.  Results do not depend on any of this.
+    // seed_table_mb: the budget in MiB, 0 = no table, -1 = min(4096, sample_pool_mb / 4) -- a 1024^2 frame of 1024 spp is covered in full, and a renderer whose
+    // pool was made small stays small.  The parts of a ShardedRenderer each hold a table of their own, indexed by the whole frame's tiles: n parts on one device
+    // cover the frame's samples n times over within n budgets (left so: parts on a device of their own are the case the sharded renderer is for).
+    int seed_table_mb = -1;
+    int seed_table_max_samples = 0;                         // > 0: the table covers at most this many samples per pixel, whatever the budget allows (0: the budget alone decides)
+    static constexpr int kSeedTableMaxMb = 8192;            // 2^31 entries: the kernels index the table in 32 bits
+    static int seed_table_default_mb(long long sample_pool_mb) { return (int)std::min<long long>(4096, sample_pool_mb / 4); }
+    static int seed_table_samples_for(long long mb, int w, int h);      // sample numbers a budget covers on a w x h frame
+    int seed_table_budget_mb() const { return seed_table_mb >= 0 ? seed_table_mb : seed_table_default_mb((long long)(sample_pool_bytes >> 20)); }
+    int seed_table_samples() const { return seed_filled_; }    // sample numbers 1..this of the current (seed, W, H) are in the table now
+    int seed_table_fills() const { return seed_fills_; }       // fill launches so far (diagnostics, tests)
     void set_tiles(const std::vector<int32_t>& tile_ids);     // empty = whole frame
     void fill_params(SceneParams& P);                          // renderer.cpp:88-138
     void download(float* rgba);                                // color -> host
@@ -272,6 +292,16 @@ private:
     DeviceBufferPtr status_;
     DeviceBufferPtr pool_;
     DeviceBufferPtr workspace_;
+    // seed table: the buffer, its capacity and its filled prefix in sample numbers, its key, the stream of the last fill and an event recorded after it
+    DeviceBufferPtr seed_table_;
+    int seed_cap_ = 0, seed_filled_ = 0, seed_fills_ = 0, seed_budget_mb_ = -1, seed_max_samples_ = 0;      // (the last two: the settings the table was made under)
+    int seed_key_[3] = { 0, 0, 0 };                    // (seed, W, H) the entries were hashed for
+    bool seed_failed_ = false;                         // an allocation failed: the table stays as large as it is (none: the renderer hashes) until the key or the budget changes
+    hipStream_t seed_stream_ = nullptr;
+    hipEvent_t seed_event_ = nullptr;
+    void drop_seed_table();
+    // the table for a launch of the 0-based sample numbers [s0, s0 + n) on `stream`, filled as far as it reaches: *samples = the numbers it covers (0: no table)
+    const uint32_t* seed_table_for(const SceneParams& P, int s0, int n, hipStream_t stream, int* samples);
     DeviceBufferPtr stats_;                            // 32 counters of the instrumented kernels (sched_stats)
     DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
     DeviceBufferPtr moments_;                          // W*H*4 second moments, allocated by the first launch with `variance` on

@@ -35,7 +35,10 @@ size_t pathtrace_workspace_floats();      // cold path state of all resident wav
 void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
                       int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math = false,
                       hipEvent_t ev_kernel_begin = nullptr, hipEvent_t ev_kernel_end = nullptr,      // optional: bracket the path-tracing kernel alone
-                      float* moments = nullptr);      // optional: W*H*4 per-channel second moments S = M2 / n, folded in the same pass (vr_set_int "variance")
+                      float* moments = nullptr,       // optional: W*H*4 per-channel second moments S = M2 / n, folded in the same pass (vr_set_int "variance")
+                      // optional: the path seeds of samples 1..seed_samples of every pixel of the WHOLE frame (launch_seed_fill); the path-tracing kernel reads a
+                      // new path's seed there instead of hashing it, and hashes for the samples beyond.  The other integrators hash always.
+                      const uint32_t* seed_table = nullptr, int32_t seed_samples = 0);
 // Denoiser features of samples 1..spp for every pixel of the listed tiles (tiles == nullptr: all n_tiles of the frame): out = W*H*8 floats,
 // (albedo.rgb, coverage, normal.xyz, depth) per pixel, row 0 at the bottom (vr_trace.h feature_pixel).  Pixels of other tiles are not written.
 // status: the renderer's status word; a pixel whose tracker exceeded its step budget sets kFeatureLostStatus there (its remaining samples are not run).
@@ -54,6 +57,9 @@ enum PathtraceVariantReason : int {
     VR_VARIANT_GRID_FORMS = 8         // emission grid with a dense grid on either side, or brick grids of different layouts (no paired atlas)
 };
 int pathtrace_variant_of(const SceneParams& P, int* why);
+// true when the kernel instance that serves the scene reads a seed table (vr_pathtrace.h seed_request_point: the brick kernels without an emission grid, not
+// their instrumented forms): for every other launch the renderer neither fills nor passes one
+bool pathtrace_reads_seed_table(const PathtraceTuning& T, const SceneParams& P);
 // Kernel variants 0 and 1 form the byte offsets of their gathers into the grids' tables in 32 bits (vr_trace.h table_load) and exist a second time with 64-bit
 // addresses: true when a table such a kernel would index on this scene holds 4 GiB or more -- or when the tuning forces it.  (Variants 2, 3 and 4 are always wide.)
 bool pathtrace_wide_of(const PathtraceTuning& T, const SceneParams& P);
@@ -127,6 +133,9 @@ void launch_pair_atlas(const uint8_t* atlas_density, const uint8_t* atlas_emissi
 
 // decoded float atlas (one float per atlas byte: rmin + unorm8(b) * rdiff of its brick), used by transfer-function renders
 void launch_decode_atlas(const float* rng, const uint8_t* atlas, float* out, size_t n_records, hipStream_t stream);
+// Path-seed table (vr_tiles.h seed_table_index): the entries of the 0-based sample numbers [s_begin, s_end) of every pixel of the W x H frame's tiles, each
+// vr_trace.h path_seed(seed, W, px, py, s + 1) -- what do_new hashes for that sample.  table holds s_end * tile_count(W, H) * 256 entries at least.
+void launch_seed_fill(uint32_t* table, uint32_t seed, int32_t W, int32_t H, int32_t s_begin, int32_t s_end, hipStream_t stream);
 // ---- vr_probe.hip, vr_fastprobe.hip ---------------------------------------------------------------------------------------------------------
 // unit-test probe: out[i] = f(a[i], b[i]) with the device build of vr_math.h
 // fn: 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin 9 a/b 10 sqrt 11 fma(a,b,a) 12 float(u8)/255 13 sincos 14 a*b+a 15 half->float

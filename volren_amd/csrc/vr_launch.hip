@@ -153,13 +153,13 @@ size_t pathtrace_pool_floats(const PathtraceTuning& T, int32_t n_tiles, int32_t 
 extern "C" {
 #define VR_PT_DECL(N) \
     int vr_pt_occupancy_##N(int tf, int stats); \
-    void vr_pt_launch_##N(int tf, int stats, unsigned grid, hipStream_t stream, const void* P, float* sbuf, float* cold_ws, const void* D, const void* S, uint32_t* status, unsigned long long* stats_buf);
+    void vr_pt_launch_##N(int tf, int stats, unsigned grid, hipStream_t stream, const void* P, float* sbuf, float* cold_ws, const void* D, const void* S, uint32_t* status, unsigned long long* stats_buf, const void* seeds);
 VR_PT_DECL(0) VR_PT_DECL(1) VR_PT_DECL(2) VR_PT_DECL(3) VR_PT_DECL(4) VR_PT_DECL(0_fast) VR_PT_DECL(1_fast) VR_PT_DECL(2_fast) VR_PT_DECL(3_fast) VR_PT_DECL(4_fast)
 VR_PT_DECL(0w) VR_PT_DECL(1w) VR_PT_DECL(0w_fast) VR_PT_DECL(1w_fast)      // 64-bit gather addresses (VR_PT_WIDE)
 #undef VR_PT_DECL
 }
 typedef int (*PtOccupancy)(int, int);
-typedef void (*PtLaunch)(int, int, unsigned, hipStream_t, const void*, float*, float*, const void*, const void*, uint32_t*, unsigned long long*);
+typedef void (*PtLaunch)(int, int, unsigned, hipStream_t, const void*, float*, float*, const void*, const void*, uint32_t*, unsigned long long*, const void*);
 // [arithmetic mode][wide][variant]; variants 2, 3 and 4 have one build each, which is wide
 static const PtOccupancy kPtOccupancy[2][2][kPtVariants] = { { { vr_pt_occupancy_0, vr_pt_occupancy_1, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 },
                                                                { vr_pt_occupancy_0w, vr_pt_occupancy_1w, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 } },
@@ -202,6 +202,10 @@ bool pathtrace_wide_of(const PathtraceTuning& T, const SceneParams& P) {
     if (P.u.has_emission) m = std::max(m, grid_largest_table_bytes(P.emission, P.paired != 0, false));
     return m >= (1ull << 32);
 }
+bool pathtrace_reads_seed_table(const PathtraceTuning& T, const SceneParams& P) {
+    const bool item_kernel_serves = P.u.integrator == 3 || (P.u.integrator == 2 && P.u.use_tf);
+    return !item_kernel_serves && T.stats == nullptr && pathtrace_variant_of(P, nullptr) == 0;
+}
 static int pathtrace_variant(const SceneParams& P) {
     int why = 0;
     const int variant = pathtrace_variant_of(P, &why);
@@ -242,7 +246,7 @@ size_t pathtrace_workspace_floats() { return kColdMainFloats + (size_t)kMaxWorkg
 
 void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
                       int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math, hipEvent_t ev_kernel_begin, hipEvent_t ev_kernel_end,
-                      float* moments) {
+                      float* moments, const uint32_t* seed_table, int32_t seed_samples) {
     if (n_tiles <= 0 || n_samples <= 0) return;
     SchedParams S;
     for (int i = 0; i < ST_COUNT; ++i) S.thr[i] = T.thr[i];
@@ -258,6 +262,10 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     D.chunks = (uint32_t)chunks;
     D.seg_len = (D.n_units + kQueueSegments - 1u) / kQueueSegments;
     D.unit_counter = unit_counter;
+    SeedTable seeds;
+    seeds.table = seed_samples > 0 ? seed_table : nullptr;
+    seeds.cap = seed_samples;
+    seeds.n_tiles = tile_count(P.u.resolution[0], P.u.resolution[1]);
     S.max_iters = kMaxIdleIters;
     // lanes that must stand at a tentative collision before the collision code runs while others still march (vr_pathtrace.h):
     // measured optimum 24 (smoke.brick +0.5 %, dense +0.7 %, sparse + emission +2...3.5 %), 32 with a transfer function, whose
@@ -276,7 +284,7 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     } else {
         (void)hipMemsetAsync(unit_counter, 0, kQueueSegments * sizeof(uint32_t), stream);
         if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
-        kPtLaunch[mode][wide][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats);
+        kPtLaunch[mode][wide][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats, &seeds);
         if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
     }
     const auto accumulate = moments ? accumulate_kernel<true> : accumulate_kernel<false>;

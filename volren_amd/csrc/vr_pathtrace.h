@@ -42,6 +42,12 @@ struct LaunchDesc {
     uint32_t n_units, chunks, seg_len;
     uint32_t* unit_counter;   // kQueueSegments counters, zeroed before the launch
 };
+// the renderer's path-seed table (vr_tiles.h seed_table_index over the n_tiles = tile_count(W, H) tiles of the whole frame) or nullptr = every path hashes its seed;
+// samples whose 0-based number is `cap` or more hash too
+struct SeedTable {
+    const uint32_t* table;
+    int32_t cap, n_tiles;
+};
 
 // The unit at queue position j.  Where its sub-tile lies in the frame and where its items lie in the sample pool are vr_tiles.h's to say (the
 // accumulate kernel reads the pool by the same functions); the order of the queue is this file's.
@@ -75,6 +81,28 @@ __device__ __forceinline__ WorkUnit make_unit(const LaunchDesc& D, int32_t W, ui
 #ifndef VR_PRIO_EVENTS
 #define VR_PRIO_EVENTS 0
 #endif
+
+// Where a NEW batch asks for its lanes' entries of the seed table (KernelArgs::seeds).  The entries are read once, so every read comes from beyond the L2, and
+// vector loads return in order: asked for where do_new needs it (0), the seed's latency stands exposed in front of the batch -- about what the 384 instructions of
+// the hash it replaces were worth.  1: at the top of the event section, before the escape and scatter batches -- the work unit is pulled there when the cursor stands
+// at its end, each lane's entry is computed and the load issued into ONE vector register that lives to the end of the section; the NEW batch runs last of the four,
+// so the miss returns together with the cold-line misses the other batches open with.  2: at the end of the previous NEW batch, into one vector register carried
+// around the scheduler loop (the load is as good as free, the register is not: only for instances with registers to spare).  Measured: profiles/r10_seed_table.txt.
+// VR_SEED_REQ pins one point for every instance (experiment builds).
+typedef __attribute__((address_space(1))) uint32_t SeedGlobal;      // the table is global memory: global_load, not the flat form a pointer read through event_args() gets
+template <class K, bool STATS> constexpr int seed_request_point() {
+#ifdef VR_SEED_REQ
+    return VR_SEED_REQ;
+#else
+    // By measurement (profiles/r10_seed_table.txt; c2 / c3 / c4 against hashing): the brick kernel without a transfer function carries the register, +1.3 % on c2
+    // (at use +0.7 %, top of the section +0.3 %); with a transfer function it asks at use, +1.3 % on c3 (the carried register would cost it seven more spilled
+    // scalar registers).  -1 = the instance does not read the table at all and hashes as before: the dense-grid kernels (c4 -0.6 ... -0.9 % at every request
+    // point: 119 -> 127 vector registers), the kernels with an emission grid and the everything-at-run-time variant (127-128 vector registers, 9-26 spilled scalar
+    // ones: two more with the table) and every instrumented instance (all 128, spilling to scratch as they are).
+    if (K::emission != 0 || K::global != 0 || K::dense != 0 || STATS) return -1;
+    return K::tf ? 0 : 2;
+#endif
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Wave-private path pool.
@@ -319,6 +347,7 @@ struct KernelArgs {
     float* cold_ws;              // cold path state of all resident wavefronts
     uint32_t* status;            // [0] bit 0: watchdog tripped, bit 1: a path ended in an impossible state
     unsigned long long* stats;   // STATS kernels only
+    SeedTable seeds;             // (last: the arguments before it lie where they lay before the table existed, and the instances that do not read it compile as they did)
 };
 typedef const __attribute__((address_space(4))) KernelArgs* KernargPtr;
 __device__ __forceinline__ const KernelArgs& event_args() {
@@ -404,6 +433,8 @@ pathtrace_kernel(const KernelArgs A) {
     Hot l;
     hot_init(l);
     int32_t slot = -1;                // path held in this lane's registers (-1: none)
+    uint32_t seed_next = 0u;          // seed_request_point 2 only: the table entry of the item the NEXT NEW batch gives this lane, asked for at the end of the last one
+    bool seed_next_valid = false;
 
     // VR_STATS_LEVEL (round 6): what the instrumented (STATS) instances carry.  2 (default): everything -- executions and lanes per block, cycles per block, pool
     // occupancy, the wavefront's timeline; those instances spill 3-28 vector registers to scratch and run ~25 % slower than the production kernels.  1: executions and
@@ -665,6 +696,79 @@ pathtrace_kernel(const KernelArgs A) {
             Hot& b = l;
 #endif
             if (VR_PRIO_EVENTS != VR_PRIO_HOT) __builtin_amdgcn_s_setprio(VR_PRIO_EVENTS);
+            constexpr int kSeedReq = seed_request_point<K, STATS>();
+            // the unit the next NEW batch takes its items from: pulled when the cursor stands at the current one's end
+            auto pull_unit = [&]() __attribute__((always_inline)) {
+                if (cursor != (uint32_t)wu.n_items) return;
+                const KernelArgs& E = event_args();
+                uint32_t j = 0xFFFFFFFFu;
+                while (seg_tries < kQueueSegments) {                    // own segment first, then the following ones
+                    const uint32_t k = ((blockIdx.x & (kQueueSegments - 1u)) + seg_tries) & (kQueueSegments - 1u);
+                    const uint32_t lo = k * E.D.seg_len, hi = min(lo + E.D.seg_len, E.D.n_units);
+                    uint32_t v = 0xFFFFFFFFu;
+                    if (lo < hi) { if (lane == 0) v = atomicAdd(E.D.unit_counter + k, 1u); v = __builtin_amdgcn_readfirstlane(v); }
+                    if (lo < hi && v < hi - lo) { j = lo + v; break; }
+                    ++seg_tries;                                        // this segment is used up for good
+                }
+                if (j == 0xFFFFFFFFu) { exhausted = true; if (STATS_T) t_exhausted = __builtin_amdgcn_s_memrealtime(); }
+                else { wu = make_unit(E.D, E.P.u.resolution[0], j, nullptr); cursor = 0u; idle_iters = 0u; t_elapsed = 0u; }
+            };
+            // Seed table (seed_request_point above).  A NEW batch gives lane i item cursor + i, whatever its size turns out to be, so a lane's entry is known as soon as
+            // the unit is: seed_entry is that entry's index and whether the lane has one (an item of the unit, a sample below the cap -- a unit may straddle it);
+            // seed_load issues the read -- unconditional where there is a table (a lane without an entry reads one of the table's first 64, and drops it), and followed by
+            // an empty asm that may touch memory, past which the compiler sinks no load: left alone it would move this one to its use at the far end of the section.
+            // (Not volatile: a volatile load is waited for where it stands.)
+            // Table, cap and tile count are read through event_args() here; nothing but request point 2's one vector register (seed_next, with its wave-uniform
+            // flag) is carried around the scheduler loop.
+            auto seed_entry = [&](const KernelArgs& E, bool& have) __attribute__((always_inline)) -> uint32_t {
+                const uint32_t item = cursor + (uint32_t)lane;
+                const uint32_t s = (uint32_t)(wu.first_sample - 1) + (item >> 6);
+                have = kSeedReq >= 0 && E.seeds.table != nullptr && item < (uint32_t)wu.n_items && s < (uint32_t)E.seeds.cap;
+                return seed_table_index<uint32_t>(s, E.seeds.n_tiles, (uint32_t)tile_of_pixel(wu.px0, wu.py0, E.P.u.resolution[0]), sub_of_pixel(wu.px0, wu.py0), item & 63u);
+            };
+            auto seed_load = [&](const KernelArgs& E) __attribute__((always_inline)) -> uint32_t {
+                uint32_t v = 0u;
+                if (kSeedReq >= 0 && E.seeds.table != nullptr) {             // wave-uniform
+                    bool have;
+                    const uint32_t i = seed_entry(E, have);
+                    v = *(const SeedGlobal*)(E.seeds.table + (size_t)(have ? i : (uint32_t)lane));
+                    asm volatile("" ::: "memory");
+                }
+                return v;
+            };
+            uint32_t seed_early = 0u;     // the table entry asked for at the top of the section (request point 1)
+            // the NEW batch.  At request points 1 and 2 it runs last of the four; otherwise where it always ran, between the scatter and the collision events
+            auto new_batch = [&]() __attribute__((always_inline)) {
+                if (want_new) {
+                    if (kSeedReq != 1) pull_unit();
+                    n = min(min(64, cnt_free), (int32_t)((uint32_t)wu.n_items - cursor));
+                    if (n > 0) {
+                        VR_STAT(ST_NEW, n);
+                        int32_t bs = -1;
+                        const KernelArgs& E = event_args();
+                        bool have_seed;
+                        seed_entry(E, have_seed);
+                        uint32_t table_seed;
+                        if (kSeedReq == 1) table_seed = seed_early;
+                        else if (kSeedReq == 2) { table_seed = seed_next; have_seed = have_seed && seed_next_valid; }
+                        else table_seed = seed_load(E);
+                        if (lane < n) {
+                            bs = q[Q_FREE * NS + cnt_free - 1 - lane];
+                            hot_init(b);
+                            ColdT c = VR_COLD(bs);
+                            do_new<K, ColdT, kLazyEm>(b, c, E.P, wu, cursor + (uint32_t)lane, have_seed, table_seed);
+                            hs.save_new(b, bs);
+                            if (kLazyEm) hs.save_first_radiance(v3{ 0.0f, 0.0f, 0.0f }, bs);
+                        }
+                        cnt_free -= n;
+                        cursor += (uint32_t)n;
+                        VR_ROUTE_B(bs);                                        // ST_NEW = pixel outside a ragged frame
+                        VR_STAT_END(ST_NEW);
+                    }
+                    if (kSeedReq == 2) { pull_unit(); seed_next = seed_load(event_args()); seed_next_valid = true; }
+                }
+            };
+            if (kSeedReq == 1 && want_new) { pull_unit(); seed_early = seed_load(event_args()); }
             if (want_esc) {
                 n = min(64, cnt_esc);
                 VR_STAT(ST_ESCAPE, n);
@@ -700,39 +804,43 @@ pathtrace_kernel(const KernelArgs A) {
                 VR_ROUTE_B(bs);                                            // ST_NEW = path ended (bounce cap / roulette)
                 VR_STAT_END(ST_POSTNEE);
             }
-            if (want_new) {
-                if (cursor == (uint32_t)wu.n_items) {
-                    const KernelArgs& E = event_args();
-                    uint32_t j = 0xFFFFFFFFu;
-                    while (seg_tries < kQueueSegments) {                    // own segment first, then the following ones
-                        const uint32_t k = ((blockIdx.x & (kQueueSegments - 1u)) + seg_tries) & (kQueueSegments - 1u);
-                        const uint32_t lo = k * E.D.seg_len, hi = min(lo + E.D.seg_len, E.D.n_units);
-                        uint32_t v = 0xFFFFFFFFu;
-                        if (lo < hi) { if (lane == 0) v = atomicAdd(E.D.unit_counter + k, 1u); v = __builtin_amdgcn_readfirstlane(v); }
-                        if (lo < hi && v < hi - lo) { j = lo + v; break; }
-                        ++seg_tries;                                        // this segment is used up for good
+            // The kernels that do not read the table (seed_request_point -1) keep the NEW batch as it was written before the table existed, text and all: any
+            // restatement of it -- the shared pull_unit, the batch as a lambda -- costs them two to eight more spilled scalar registers.
+            if constexpr (kSeedReq < 0) {
+                if (want_new) {
+                    if (cursor == (uint32_t)wu.n_items) {
+                        const KernelArgs& E = event_args();
+                        uint32_t j = 0xFFFFFFFFu;
+                        while (seg_tries < kQueueSegments) {                    // own segment first, then the following ones
+                            const uint32_t k = ((blockIdx.x & (kQueueSegments - 1u)) + seg_tries) & (kQueueSegments - 1u);
+                            const uint32_t lo = k * E.D.seg_len, hi = min(lo + E.D.seg_len, E.D.n_units);
+                            uint32_t v = 0xFFFFFFFFu;
+                            if (lo < hi) { if (lane == 0) v = atomicAdd(E.D.unit_counter + k, 1u); v = __builtin_amdgcn_readfirstlane(v); }
+                            if (lo < hi && v < hi - lo) { j = lo + v; break; }
+                            ++seg_tries;                                        // this segment is used up for good
+                        }
+                        if (j == 0xFFFFFFFFu) { exhausted = true; if (STATS_T) t_exhausted = __builtin_amdgcn_s_memrealtime(); }
+                        else { wu = make_unit(E.D, E.P.u.resolution[0], j, nullptr); cursor = 0u; idle_iters = 0u; t_elapsed = 0u; }
                     }
-                    if (j == 0xFFFFFFFFu) { exhausted = true; if (STATS_T) t_exhausted = __builtin_amdgcn_s_memrealtime(); }
-                    else { wu = make_unit(E.D, E.P.u.resolution[0], j, nullptr); cursor = 0u; idle_iters = 0u; t_elapsed = 0u; }
-                }
-                n = min(min(64, cnt_free), (int32_t)((uint32_t)wu.n_items - cursor));
-                if (n > 0) {
-                    VR_STAT(ST_NEW, n);
-                    int32_t bs = -1;
-                    if (lane < n) {
-                        bs = q[Q_FREE * NS + cnt_free - 1 - lane];
-                        hot_init(b);
-                        ColdT c = VR_COLD(bs);
-                        do_new<K, ColdT, kLazyEm>(b, c, event_args().P, wu, cursor + (uint32_t)lane);
-                        hs.save_new(b, bs);
-                        if (kLazyEm) hs.save_first_radiance(v3{ 0.0f, 0.0f, 0.0f }, bs);
+                    n = min(min(64, cnt_free), (int32_t)((uint32_t)wu.n_items - cursor));
+                    if (n > 0) {
+                        VR_STAT(ST_NEW, n);
+                        int32_t bs = -1;
+                        if (lane < n) {
+                            bs = q[Q_FREE * NS + cnt_free - 1 - lane];
+                            hot_init(b);
+                            ColdT c = VR_COLD(bs);
+                            do_new<K, ColdT, kLazyEm>(b, c, event_args().P, wu, cursor + (uint32_t)lane);
+                            hs.save_new(b, bs);
+                            if (kLazyEm) hs.save_first_radiance(v3{ 0.0f, 0.0f, 0.0f }, bs);
+                        }
+                        cnt_free -= n;
+                        cursor += (uint32_t)n;
+                        VR_ROUTE_B(bs);                                        // ST_NEW = pixel outside a ragged frame
+                        VR_STAT_END(ST_NEW);
                     }
-                    cnt_free -= n;
-                    cursor += (uint32_t)n;
-                    VR_ROUTE_B(bs);                                        // ST_NEW = pixel outside a ragged frame
-                    VR_STAT_END(ST_NEW);
                 }
-            }
+            } else if (kSeedReq < 1) new_batch();
             if (want_nee) {
                 n = min(64, cnt_nee);
                 VR_STAT(ST_NEE, n);
@@ -753,6 +861,9 @@ pathtrace_kernel(const KernelArgs A) {
                 VR_ROUTE_B(bs);
                 VR_STAT_END(ST_NEE);
             }
+            // (last of the four: a seed asked for at the top of the section has had the other batches' round trips to arrive; request point 2 was measured in
+            // this order too)
+            if (kSeedReq >= 1) new_batch();
 #if !VR_BATCH_REGS
             __builtin_amdgcn_wave_barrier();
             if (my_slot >= 0) { hs.load_resume(l, my_slot); l.majorant = my_majorant; if (emission_on && !l.shadow) { const ColdT c = VR_COLD(my_slot); l.ethr = ld3(c, C_THR); l.eL = ld3(c, C_L); } }

@@ -84,13 +84,14 @@ extern "C" int VR_PT_CAT(vr_pt_occupancy_, VR_PT_VARIANT, VR_PT_SUFFIX)(int tf, 
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vr::pick(tf != 0, stats != 0), 64 * vr::kWgWaves, 0) != hipSuccess || per_cu <= 0) per_cu = 16 / vr::kWgWaves;
     return per_cu;
 }
-// P, D, S: SceneParams, LaunchDesc, SchedParams (plain data, same layout in both builds)
+// P, D, S, seeds: SceneParams, LaunchDesc, SchedParams, SeedTable (plain data, same layout in both builds)
 extern "C" void VR_PT_CAT(vr_pt_launch_, VR_PT_VARIANT, VR_PT_SUFFIX)(int tf, int stats, unsigned grid, hipStream_t stream, const void* P, float* sbuf, float* cold_ws,
-                                                                       const void* D, const void* S, uint32_t* status, unsigned long long* stats_buf) {
+                                                                       const void* D, const void* S, uint32_t* status, unsigned long long* stats_buf, const void* seeds) {
     vr::KernelArgs A;
     A.P = *static_cast<const vr::SceneParams*>(P);
     A.D = *static_cast<const vr::LaunchDesc*>(D);
     A.S = *static_cast<const vr::SchedParams*>(S);
     A.sbuf = sbuf; A.cold_ws = cold_ws; A.status = status; A.stats = stats_buf;
+    A.seeds = *static_cast<const vr::SeedTable*>(seeds);
     hipLaunchKernelGGL(vr::pick(tf != 0, stats != 0), dim3(grid), dim3(64 * vr::kWgWaves), 0, stream, A);
 }

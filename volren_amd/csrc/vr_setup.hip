@@ -259,4 +259,21 @@ void launch_majorants(const SceneParams& P, const uint32_t* range_words_all_mips
     hipLaunchKernelGGL(majorant_kernel, dim3((n + 256u) / 256u), dim3(256), 0, stream, P, range_words_all_mips, L, n, out_padded, out16_padded);      // n + 1 cells
 }
 
+// Path-seed table: one thread per entry of the sample numbers [s_begin, s_begin + n) (vr_device.h launch_seed_fill).  Consecutive threads write consecutive entries.
+__global__ void __launch_bounds__(256)
+seed_fill_kernel(uint32_t* __restrict__ table, uint32_t seed, int32_t W, int32_t n_tiles, uint32_t s_begin, size_t n_entries) {
+    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (g >= n_entries) return;
+    const size_t per_sample = (size_t)n_tiles * 256u;
+    const uint32_t s = s_begin + (uint32_t)(g / per_sample), r = (uint32_t)(g % per_sample);
+    const TilePixel q = wave_tiled_pixel((int32_t)(r >> 8), r & 255u, W);
+    table[seed_table_index<size_t>(s, n_tiles, (size_t)q.tile, (uint32_t)q.sub, (uint32_t)q.lane)] = path_seed(seed, W, q.px, q.py, (int32_t)s + 1);
+}
+void launch_seed_fill(uint32_t* table, uint32_t seed, int32_t W, int32_t H, int32_t s_begin, int32_t s_end, hipStream_t stream) {
+    if (s_end <= s_begin || s_begin < 0) return;
+    const int32_t n_tiles = tile_count(W, H);
+    const size_t n_entries = (size_t)(s_end - s_begin) * (size_t)n_tiles * 256u;
+    hipLaunchKernelGGL(seed_fill_kernel, dim3((unsigned)((n_entries + 255u) / 256u)), dim3(256), 0, stream, table, seed, W, n_tiles, (uint32_t)s_begin, n_entries);
+}
+
 }  // namespace vr

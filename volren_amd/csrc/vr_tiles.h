@@ -49,6 +49,18 @@ VR_HD I pool_slot(I chunk, int32_t n_tiles, I tile_slot, uint32_t sub, int32_t s
     return unit * (I)(spu * 64) + sample * 64u + lane;
 }
 
+// Path-seed table of a renderer (renderer.h seed table; written by seed_fill_kernel, read by the path-tracing kernel's NEW batches): one uint32 per (sample
+// number, pixel of the WHOLE frame in wave-tiled order).  s: the sample number as do_new hands it to the hash, minus the 1 a frame starts from; tile: the raster
+// tile id of the whole frame (n_frame_tiles = tile_count(W, H)), so a launch over a tile subset reads the same entries as one over the frame.  The 64 lanes of a
+// sub-tile are adjacent: a NEW batch, whose lanes take consecutive items, reads one or two contiguous 256-byte runs.  Pixels outside a ragged frame have entries
+// (nobody reads them).  I: the caller's index type, as in pool_slot -- 32 bits in the kernels (the table is capped below 2^32 entries), size_t on the host
+template <class I>
+VR_HD I seed_table_index(I s, int32_t n_frame_tiles, I tile, uint32_t sub, uint32_t lane) {
+    return ((s * (I)n_frame_tiles + tile) * 4u + sub) * 64u + lane;
+}
+// the sub-tile (0..3) of its 16x16 tile that holds pixel (px, py) -- the inverse of wave_tiled_pixel's sub
+VR_HD uint32_t sub_of_pixel(int32_t px, int32_t py) { return (uint32_t)(((px >> 3) & 1) | (((py >> 3) & 1) << 1)); }
+
 // unbiased variance = S * variance_scale(n) for n >= 2 samples, where S = Welford's M2 / n (the renderer's moments); 0 below (the callers give
 // the variance itself as 0 there, not S * 0: S may be NaN)
 VR_HD float variance_scale(int32_t n) { return n >= 2 ? (float)n / (float)(n - 1) : 0.0f; }

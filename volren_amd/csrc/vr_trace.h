@@ -178,6 +178,9 @@ VR_HD uint32_t tea32(uint32_t v0, uint32_t v1) {
     }
     return v0;
 }
+// the RNG state a path of pixel (px, py) of a frame W wide starts sample `smp` (1-based) with, uint32 wrap-around included: what do_new evaluates and what
+// seed_fill_kernel (vr_setup.hip) stores in the renderer's seed table
+VR_HD uint32_t path_seed(uint32_t seed, int32_t W, int32_t px, int32_t py, int32_t smp) { return tea32(seed * (uint32_t)(py * W + px), (uint32_t)smp); }
 VR_HD float rng(uint32_t& s) {
     s = s * 1664525u + 1013904223u;
     return (float)(s & 0x00FFFFFFu) * (1.0f / 16777216.0f);   // exact: same value as / float(0x01000000)
@@ -999,13 +1002,16 @@ VR_HD bool begin_segment(Hot& h, const SceneParams& P, v3 pos, v3 d, int32_t sha
 
 // pathtracer_brick.glsl:27-30 + common.glsl:76-80; the lane has just been given `item` (< n_items)
 // LAZY_EM: also with an emission grid no cold line is written (the scheduler keeps the radiance of a `first` path in its parked hot state: vr_pathtrace.h)
+// have_seed: `table_seed` is this item's entry of the renderer's seed table (vr_tiles.h seed_table_index) -- the value the hash below would return, read instead of
+// computed; the lanes of a batch without one hash, in one branch
 template <class K, class Cold, bool LAZY_EM = false>
-VR_HD void do_new(Hot& h, Cold& c, const SceneParams& P, const WorkUnit& wu, uint32_t item) {
+VR_HD void do_new(Hot& h, Cold& c, const SceneParams& P, const WorkUnit& wu, uint32_t item, bool have_seed = false, uint32_t table_seed = 0u) {
     const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
     const int32_t px = wu.px0 + (int32_t)(item & 7u), py = wu.py0 + (int32_t)((item >> 3) & 7u);
     const int32_t smp = wu.first_sample + (int32_t)(item >> 6);
     if (px >= W || py >= H) return;                 // pixel outside a ragged frame: stay in ST_NEW, take the next item
-    h.seed = tea32((uint32_t)P.u.seed * (uint32_t)(py * W + px), (uint32_t)smp);
+    if (have_seed) h.seed = table_seed;
+    else h.seed = path_seed((uint32_t)P.u.seed, W, px, py, smp);
     const float jx = rng(h.seed), jy = rng(h.seed);
     const float fx = (((float)px + jx) - (float)W * 0.5f) / (float)H;
     const float fy = (((float)py + jy) - (float)H * 0.5f) / (float)H;

@@ -8,7 +8,7 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "denoise_moments", "wide_addressing")
+               "variance", "denoise_iterations", "denoise_moments", "wide_addressing", "seed_table_mb", "seed_table_max_samples")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
@@ -60,7 +60,7 @@ class Renderer:
 
     def __getattr__(self, name):
         if name in _INT_FIELDS or name in ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason", "kernel_wide",
-                                              "adaptive_rounds"):
+                                              "adaptive_rounds", "seed_table_samples", "seed_table_fills"):
             v = C.c_int()
             _lib.check(self._L.vr_get_int(self._h, name.encode(), C.byref(v)))
             return bool(v.value) if name in ("show_environment", "tonemapping") else v.value
