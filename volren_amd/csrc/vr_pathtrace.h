@@ -104,6 +104,20 @@ template <class K, bool STATS> constexpr int seed_request_point() {
 #endif
 }
 
+// Whether an instance's hot pair evaluates the state-determined tail of a tentative collision before it waits for the tap (vr_trace.h collide_finish EARLY).
+// By measurement (profiles/r11_load_order.txt): the brick kernel without a transfer function, +0.7 ... +1.2 % on c2.  Every other instance keeps the reference's
+// order, text and all: the dense kernel (c4 +0.1 %: inside the noise), the tolerance-mode kernels (their neg_log_1m is five instructions: nothing to move; c2
+// +-0), the kernels with a transfer function (three more spilled scalar registers), the ones with an emission grid (one more in tolerance mode; not measured),
+// the wide form (not measured), the global-majorant trackers (another tail) and every instrumented instance (128 vector registers, spilling as they are).
+// VR_COLLIDE_EARLY pins one answer for every instance of the DDA trackers (experiment builds).
+template <class K, bool STATS> constexpr bool collide_tail_early() {
+#ifdef VR_COLLIDE_EARLY
+    return K::global == 0 && VR_COLLIDE_EARLY != 0;
+#else
+    return !K::tf && K::global == 0 && K::emission == 0 && K::dense == 0 && K::a32 && !VR_FAST_DEVICE && !STATS;
+#endif
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Wave-private path pool.
 //
@@ -622,8 +636,9 @@ pathtrace_kernel(const KernelArgs A) {
                 collide_load<K>(PF, PE, cio);
                 if (is_c) {
                     ColdT c = VR_COLD(slot);
-                    if (lut_in_lds) collide_finish<K, ColdT, true>(l, c, PF, PE, cio, lds_lut);      // two instances: LDS reads need the address space at compile time
-                    else collide_finish<K, ColdT, true>(l, c, PF, PE, cio, PF.tf_lut);
+                    constexpr bool kEarly = collide_tail_early<K, STATS>();
+                    if (lut_in_lds) collide_finish<K, ColdT, true, kEarly>(l, c, PF, PE, cio, lds_lut);      // two instances: LDS reads need the address space at compile time
+                    else collide_finish<K, ColdT, true, kEarly>(l, c, PF, PE, cio, PF.tf_lut);
                 }
                 if (STATS) { stat_add(2 * ST_COLLIDE, 1u); stat_add(2 * ST_COLLIDE + 1, (uint32_t)n_c); }
             }

@@ -18,6 +18,8 @@
 // The order in which lanes run their states never changes a result: every lane owns its RNG state.
 #pragma once
 
+#include <type_traits>
+
 #include "vr_math.h"
 #include "vr_scene.h"
 
@@ -1185,12 +1187,46 @@ VR_HD void collide_load(const SceneParams& P, CollideIO<K>& io) { collide_load<K
 // their quotient is a reciprocal and a multiply, and the test cost the smoke.brick one a vector register and six scalar spills (profiles/r7a_shadow_shortcut.txt)
 #define VR_SHADOW_BLOCKED_SHORTCUT (!VR_FAST_DEVICE)
 #endif
+// The values the taps' loads return, tied to the state-determined tail of an EARLY collide_finish: an empty asm that takes both keeps the tail's arithmetic in front
+// of the wait for the loads and every use of a loaded value behind it; vol_majorant, which the shortcut's premises and the tail behind it compare with, is a
+// uniform read through the kernel-argument pointer: taken by the same asm, its scalar load is requested beside the tap's loads and has returned under them
+// (device only; the host runs the same text without the pin)
+template <class K>
+VR_HD void collide_tail_pin(CollideIO<K>& io, uint32_t& s1, uint32_t& s2, float& r1, float& tau2, float& vol_majorant) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (K::tf) {
+        asm volatile("" : "+v"(io.tri.d[0].raw), "+v"(io.tri.d[1].raw), "+v"(io.tri.d[2].raw), "+v"(io.tri.d[3].raw), "+v"(io.tri.d[4].raw), "+v"(io.tri.d[5].raw),
+                          "+v"(io.tri.d[6].raw), "+v"(io.tri.d[7].raw), "+v"(s1), "+v"(s2), "+v"(r1), "+v"(tau2), "+s"(vol_majorant));
+    } else {
+        asm volatile("" : "+v"(io.d.raw), "+v"(s1), "+v"(s2), "+v"(r1), "+v"(tau2), "+s"(vol_majorant));
+    }
+#endif
+}
 // CACHED: throughput and radiance of the marching path are in h.ethr / h.eL (device scheduler, see Hot); otherwise on the cold line
-template <class K, class Cold, bool CACHED = false>
-VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const SceneParams& PE, const CollideIO<K>& io, const float* tf_lut) {
+// EARLY (DDA trackers of the kernels compiled for one scene kind): what the collision does with the path's state alone -- both LCG advances, the draw behind the
+// second, its neg_log_1m and the premises of the blocked-shadow shortcut -- is evaluated BEFORE the first use of a loaded value, so behind the loads' issue
+// instead of behind their wait, and the outcome is committed afterwards.  The same operations on the same values in the same draw order: a real collision of a
+// camera / scatter segment keeps the seed after one draw, the shortcut and a null collision the seed after two (the same advance), a null collision alone takes
+// tau and the mip step; the reference tail behind the shortcut starts from the seed after the first draw, as it did.
+template <class K, class Cold, bool CACHED = false, bool EARLY = false>
+VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const SceneParams& PE, const CollideIO<K>& io_in, const float* tf_lut) {
+    static_assert(!EARLY || K::global == 0, "the early tail is the DDA trackers'");
     constexpr bool USE_TF = K::tf;
     const Uniforms& u = P.u;
     const bool global = K::global == 2 ? u.integrator != 0 : K::global == 1;
+    std::conditional_t<EARLY, CollideIO<K>, const CollideIO<K>&> io = io_in;
+    uint32_t s1 = h.seed, s2 = 0u;
+    float r1 = 0.0f, tau2 = 0.0f, vm = u.vol_majorant;
+    bool premises = false;
+    if constexpr (EARLY) {
+        r1 = rng(s1);
+        s2 = s1;
+        tau2 = neg_log_1m(rng(s2));
+        collide_tail_pin<K>(io, s1, s2, r1, tau2, vm);
+#if VR_SHADOW_BLOCKED_SHORTCUT
+        premises = (h.majorant > 0.0f) & (h.majorant <= vm) & (abs_(h.Tr) < inf_());
+#endif
+    }
     float d;
     float rgba[4] = { 0, 0, 0, 0 };
     if (USE_TF) {
@@ -1212,7 +1248,15 @@ VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const ScenePara
             const v3 L1 = global ? L0 + ((thr * oma) * em) * P_real : L0 + (((thr * oma) * em) * d) * u.vol_inv_majorant;
             if (CACHED) h.eL = L1; else st3(c, C_L, L1);
         }
-        if (global ? rng(h.seed) < P_real : rng(h.seed) * h.majorant < d) {
+        if (EARLY) {
+            // real collision: as below, on the draw made above
+            if (r1 * h.majorant < d) {
+                if (USE_TF) st3(c, C_COL, v3{ rgba[0], rgba[1], rgba[2] });
+                h.seed = s1;
+                h.state = ST_NEE;
+                return;
+            }
+        } else if (global ? rng(h.seed) < P_real : rng(h.seed) * h.majorant < d) {
             // real collision.  "throughput *= albedo [* rgba.rgb]" is applied by do_nee (the one event that follows): the
             // hot pair then never touches the path's cold state in global memory; a transfer-function colour travels there in C_COL
             if (USE_TF) st3(c, C_COL, v3{ rgba[0], rgba[1], rgba[2] });
@@ -1225,6 +1269,28 @@ VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const ScenePara
             const float prob = 1.0f - h.Tr;
             if (rng(h.seed) < prob) { h.Tr = 0.0f; h.state = ST_POSTNEE; return; }
             h.Tr /= 1.0f - prob;
+        }
+    } else if (EARLY) {
+        if (r1 * h.majorant < d) {
+            if (premises) {                  // the shortcut below
+                h.seed = s2;
+                h.Tr = 0.0f;
+                h.state = ST_POSTNEE;
+                return;
+            }
+            // the reference's tail, from the seed after the first draw (see below)
+            h.seed = s1;
+            const float ratio = !K::tf ? div_core(vm, h.majorant) : vm / h.majorant;
+            h.Tr *= max_(0.0f, 1.0f - ratio);
+            if (h.Tr < 0.1f) {
+                const float prob = 1.0f - h.Tr;
+                if (rng(h.seed) < prob) { h.Tr = 0.0f; h.state = ST_POSTNEE; return; }
+                h.Tr /= 1.0f - prob;
+            }
+            h.tau = neg_log_1m(rng(h.seed));
+            h.mipq = h.mipq > 8 ? h.mipq - 8 : 0;
+            h.state = ST_MARCH;
+            return;
         }
     } else {
         if (rng(h.seed) * h.majorant < d) {
@@ -1262,12 +1328,13 @@ VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const ScenePara
         if (!(h.t < seg_far(h))) h.state = segment_end_state(h.shadow);
         return;
     }
-    h.tau = neg_log_1m(rng(h.seed));
+    if (EARLY) { h.seed = s2; h.tau = tau2; }              // null collision: the second advance and its draw were made above
+    else h.tau = neg_log_1m(rng(h.seed));
     h.mipq = h.mipq > 8 ? h.mipq - 8 : 0;                  // mip = max(0, mip - 2)
     h.state = ST_MARCH;
 }
-template <class K, class Cold, bool CACHED = false>
-VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const CollideIO<K>& io, const float* tf_lut) { collide_finish<K, Cold, CACHED>(h, c, P, P, io, tf_lut); }
+template <class K, class Cold, bool CACHED = false, bool EARLY = false>
+VR_HD void collide_finish(Hot& h, Cold& c, const SceneParams& P, const CollideIO<K>& io, const float* tf_lut) { collide_finish<K, Cold, CACHED, EARLY>(h, c, P, P, io, tf_lut); }
 template <class K, class Cold, bool CLEAN = false>
 VR_HD void do_collide(Hot& h, Cold& c, const SceneParams& P) {
     CollideIO<K> io;
