@@ -180,6 +180,18 @@ int vr_framebuffer_device(vr_renderer* r, void** device_ptr);
  *     flush point like vr_render_features; it counts as a feature pass for every call that needs one, and every reader of the feature buffer
  *     (vr_features, vr_denoise, vr_denoise_temporal, vr_sharded_gather_guides, vr_render_adaptive's frames) reads it unchanged.  Bounded by
  *     construction (at most 16 x 4096 steps per pixel): it never sets the status word.
+ *     Empty space: with vr_set_int "expected_skip" 1 (the default; 0 = every step runs; other values VR_ERR) the march reads a clear-distance table
+ *     of the density grid -- one byte per cell of 8^3 voxels (the bricks; ceil(dim / 8) cells per axis of a dense grid): 0 when some voxel of the
+ *     cell's box grown by one voxel does not decode to +0.0f, else min(255, Chebyshev distance in cells to the nearest such cell) -- and drops, with
+ *     their eight loads, the steps whose midpoint lies in a cell with a byte >= 1, leaping 7 (byte - 1) further steps where a step is at most a
+ *     voxel long (volren_amd/csrc/vr_clear.h, vr_expected.h).  Results never depend on the setting: a dropped step is one that adds nothing.  Under
+ *     a LUT whose alpha at density 0 is positive empty space is not empty and every step runs.  The table (2 MiB for 1024^3 voxels) is built on the
+ *     device by the first such pass after the grid was committed, once per frame of an animation; renders that never ask for the pass pay nothing.
+ *     The default is 1 for every grid kind: on no measured scene was 1 slower than 0 (profiles/r12_expected_skip.txt).
+ *     vr_set_int "expected_stats" 1 (default 0) makes the following passes count their work in an instrumented twin of the kernel; vr_expected_stats
+ *     waits and writes the last pass's totals: out[0] sub-rays marched, [1] steps reached (dropped ones included), [2] steps that fetched their
+ *     corners, [3] reads of the table; VR_ERR when "expected_stats" was off for that pass.  vr_expected_clear_table (test hook) writes the table of
+ *     the current density grid, built if need be, x fastest, and its extent in cells; out may be NULL (the extent alone).
  *     vr_features waits and writes W*H*8 floats (albedo.rgb, coverage, normal.xyz, depth), row 0 at the bottom; VR_ERR before the first
  *     vr_render_features since the last resize.
  *     vr_variance waits and writes W*H*4 floats: the unbiased per-channel variance of the samples 1..n behind the framebuffer (0 for n = 1),
@@ -187,6 +199,8 @@ int vr_framebuffer_device(vr_renderer* r, void** device_ptr);
  *     samples 1..n (switched on mid-frame: vr_reset and render again). */
 int vr_render_features(vr_renderer* r, int spp);
 int vr_render_features_expected(vr_renderer* r, int rays);
+int vr_expected_stats(vr_renderer* r, uint64_t out[4]);
+int vr_expected_clear_table(vr_renderer* r, uint8_t* out, int cells[3]);
 int vr_features(vr_renderer* r, float* out);
 int vr_variance(vr_renderer* r, float* rgba_out);
 /* --- denoiser (no reference counterpart either: scripts/datagen_denoise.py exports the noisy colour for a denoiser of the caller's own).

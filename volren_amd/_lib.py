@@ -20,7 +20,7 @@ SYMBOLS = [
     "vr_set_tiles", "vr_set_stream", "vr_pack_tiles", "vr_unpack_tiles", "vr_get_uniforms", "vr_uniforms_size",
     "vr_volume_add_grid_frame_dense", "vr_volume_update_grid_frame_dense", "vr_volume_n_grid_frames", "vr_impmap_floats", "vr_get_impmap", "vr_test_alloc_cap_mb", "vr_set_sched", "vr_sched_stats", "vr_grid_checksums", "vr_math_probe", "vr_math_sweep", "vr_probe", "vr_encode_dense_stats", "vr_write_brick_from_dense", "vr_write_dense",
     "vr_sharded_create", "vr_sharded_destroy", "vr_sharded_parts", "vr_sharded_part", "vr_sharded_transport", "vr_sharded_collective", "vr_sharded_reset", "vr_sharded_render", "vr_sharded_synchronize", "vr_tile_owners", "vr_wave_timeline",
-    "vr_render_features", "vr_render_features_expected", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
+    "vr_render_features", "vr_render_features_expected", "vr_expected_stats", "vr_expected_clear_table", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
     "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history", "vr_denoise_reject_stat", "vr_denoise_history_moments",
     "vr_render_adaptive", "vr_tile_samples", "vr_tile_error",
     "vr_seed_table_default_mb", "vr_seed_table_samples_for",
@@ -77,6 +77,8 @@ def load():
     L.vr_framebuffer_device.argtypes = [vp, C.POINTER(vp)]
     L.vr_render_features.argtypes = [vp, ci]
     L.vr_render_features_expected.argtypes = [vp, ci]
+    L.vr_expected_stats.argtypes = [vp, vp]
+    L.vr_expected_clear_table.argtypes = [vp, vp, vp]
     L.vr_features.argtypes = [vp, vp]
     L.vr_variance.argtypes = [vp, vp]
     L.vr_denoise.argtypes = [vp]

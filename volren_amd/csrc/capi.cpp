@@ -306,6 +306,8 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
         }
         else if (n == "seed_table_max_samples") { if (v < 0) throw std::runtime_error("seed_table_max_samples must be >= 0 (0 = as many as seed_table_mb holds)"); R.seed_table_max_samples = v; }
         else if (n == "launch_target_ms") { if (v < 0) throw std::runtime_error("launch_target_ms must be >= 0 (0 = no sizing by time)"); R.launch_target_ms = v; }
+        else if (n == "expected_skip") { if (v < 0 || v > 1) throw std::runtime_error("expected_skip: 0 (march every step) or 1 (drop the steps of empty space by the clear-distance table)"); R.expected_skip = v; }
+        else if (n == "expected_stats") { if (v < 0 || v > 1) throw std::runtime_error("expected_stats: 0 (off) or 1 (the expected-value passes count their work)"); R.expected_stats = v; }
         else if (n == "order_tiles") { if (v < 0 || v > 2) throw std::runtime_error("order_tiles: 0 (never), 1 (tile subsets), 2 (always)"); R.order_tiles = v; }
         else if (n == "grid_frame_counter") {
             if (!R.volume || v < 0 || (size_t)v >= R.volume->n_grid_frames()) throw std::runtime_error("grid_frame_counter out of range");
@@ -357,6 +359,8 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
         else if (n == "seed_table_samples") *v = R.seed_table_samples();
         else if (n == "seed_table_fills") *v = R.seed_table_fills();
         else if (n == "launch_target_ms") *v = R.launch_target_ms;
+        else if (n == "expected_skip") *v = R.expected_skip;
+        else if (n == "expected_stats") *v = R.expected_stats;
         else if (n == "order_tiles") *v = R.order_tiles;
         else if (n == "grid_frame_counter") *v = R.volume ? (int)R.volume->grid_frame_counter : 0;
         else if (n == "n_grid_frames") *v = R.volume ? (int)R.volume->n_grid_frames() : 0;
@@ -479,6 +483,18 @@ int vr_render_features_expected(vr_renderer* r, int rays) {
     if (rays < 1 || rays > vr::kExpectedMaxRays) return fail(VR_ERR_ARG, "vr_render_features_expected: rays must be 1..4");
     if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
     return guard([&] { use_device(r); r->impl.render_features_expected(rays); });
+}
+int vr_expected_stats(vr_renderer* r, uint64_t out[4]) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.expected_stats_read(out); });
+}
+int vr_expected_clear_table(vr_renderer* r, uint8_t* out, int cells[3]) {
+    NEED(r);
+    if (!cells) return fail(VR_ERR_ARG, "null argument");
+    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    return guard([&] { use_device(r); r->impl.expected_clear_table(out, cells); });
 }
 int vr_features(vr_renderer* r, float* out) {
     NEED(r);

@@ -14,6 +14,8 @@
 // frame (refused alone and with --denoise-reject above 0).
 // --expected-features N with any of them: the guide is the noise-free expected-value pass of N x N rays per pixel (vr_expected.h; N in 1..4) instead of
 // the sampled feature pass (refused without a denoise flag).
+// --expected-skip 0|1 with --expected-features: whether that pass skips empty space by the clear-distance table (default 1; the frame is the same either
+// way; refused without --expected-features).
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
 // the mean samples per pixel; combines with --denoise (one device only).
 //
@@ -128,7 +130,7 @@ static void parse_cmd(int argc, char** argv) {
         } else if (arg == "--vol_crop_min") { renderer->vol_clip_min.x = a.nextf(); renderer->vol_clip_min.y = a.nextf(); renderer->vol_clip_min.z = a.nextf(); }
         else if (arg == "--vol_crop_max") { renderer->vol_clip_max.x = a.nextf(); renderer->vol_clip_max.y = a.nextf(); renderer->vol_clip_max.z = a.nextf(); }
         else if (arg == "--seed") renderer->seed = a.nexti();                        // addition
-        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject" || arg == "--expected-features") a.next();  // consumed earlier
+        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject" || arg == "--expected-features" || arg == "--expected-skip") a.next();  // consumed earlier
         else if (fs::is_regular_file(arg) || fs::is_directory(arg)) handle_path(arg);
     }
 }
@@ -172,6 +174,7 @@ int main(int argc, char** argv) {
     bool denoise = false, temporal = false, adaptive = false;      // temporal: --denoise with the history kept across the frames of the run
     float threshold = 0.f, reject = 0.f;      // reject: --denoise-reject, the history rejection threshold of --denoise-temporal (0 = off)
     int expected_rays = 0;      // --expected-features N: the denoise flags take their guide from render_features_expected(N) instead of render_features(min(spp, 16))
+    int expected_skip = -1;     // --expected-skip 0|1 (with --expected-features): whether that pass drops the steps of empty space (same frame either way); -1: the renderer's default
     bool reject_given = false, moments = false;      // moments: --denoise-moments, the filter's variance from the history's luminance moments (low-spp sequences)
     std::vector<int> devices;
     try {
@@ -195,6 +198,11 @@ int main(int argc, char** argv) {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-features");
                 expected_rays = std::stoi(argv[++i]);
                 if (expected_rays < 1 || expected_rays > kExpectedMaxRays) throw std::runtime_error("--expected-features: the rays per pixel axis must be 1..4");
+            } else if (arg == "--expected-skip") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-skip");
+                const std::string v = argv[++i];
+                if (v != "0" && v != "1") throw std::runtime_error("--expected-skip: 0 (march every step) or 1 (skip empty space)");
+                expected_skip = v == "1" ? 1 : 0;
             } else if (arg == "--adaptive") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --adaptive");
                 adaptive = true;
@@ -204,6 +212,7 @@ int main(int argc, char** argv) {
         }
         if (reject_given && !temporal) throw std::runtime_error("--denoise-reject needs --denoise-temporal: it rejects the history that only that call keeps");
         if (expected_rays > 0 && !denoise) throw std::runtime_error("--expected-features needs --denoise or --denoise-temporal: it chooses the guide of their filter");
+        if (expected_skip >= 0 && expected_rays == 0) throw std::runtime_error("--expected-skip needs --expected-features: it is a setting of that pass");
         if (moments && !temporal) throw std::runtime_error("--denoise-moments needs --denoise-temporal: the moments live in the history that only that call keeps");
         if (moments && reject > 0.f) throw std::runtime_error("--denoise-moments and --denoise-reject do not go together: the rejection statistic needs the frames' sample variance");
         if (adaptive && (gpus > 0 || devices.size() > 1))
@@ -237,6 +246,7 @@ int main(int argc, char** argv) {
             if (denoise) renderer->variance = 1;        // the denoiser's variance input: kept from sample 1 of every frame
             renderer->denoise_reject = reject;
             renderer->denoise_moments = moments ? 1 : 0;
+            if (expected_skip >= 0) renderer->expected_skip = expected_skip;
             parts.push_back(renderer);
         }
         renderer = parts[0];                            // holds the whole frame after the gather

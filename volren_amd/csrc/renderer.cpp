@@ -936,8 +936,53 @@ void RendererHIP::render_features_expected(int rays) {
     if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("render_features_expected: rays must be 1.." + std::to_string(kExpectedMaxRays));
     SceneParams P;
     const int n_tiles = begin_feature_pass(P);
-    launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, features_->as<float>(), stream);
+    ClearTable clear = { nullptr, { 0, 0, 0 } };
+    if (expected_skip) clear = clear_table_of(density_grids.at(volume->grid_frame_counter), P.density);
+    expected_stats_valid_ = false;
+    unsigned long long* counters = nullptr;
+    if (expected_stats) {
+        ensure_buffer(expected_stats_, 4 * sizeof(unsigned long long));
+        VR_HIP(hipMemsetAsync(expected_stats_->get(), 0, expected_stats_->size_bytes(), stream));
+        counters = expected_stats_->as<unsigned long long>();
+    }
+    launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, features_->as<float>(), stream, &clear, counters);
     VR_HIP(hipGetLastError());
+    expected_stats_valid_ = counters != nullptr;
+}
+
+// The clear-distance table of a density grid (vr_clear.h), made by the first pass that asks for it: the table lives with the grid's device arrays, so
+// commit() -- which every change of the volume goes through -- leaves the new grids without one, and each frame of an animation keeps its own.
+ClearTable RendererHIP::clear_table_of(BrickGridHIP& g, const GridView& view) {
+    ClearTable t;
+    clear_cells(view, t.n);
+    const size_t cells = (size_t)t.n[0] * (size_t)t.n[1] * (size_t)t.n[2];
+    if (!g.clear_table && cells > 0) {
+        auto table = make_device_buffer(cells);
+        DeviceBuffer scratch(cells);
+        launch_clear_table(view, table->as<uint8_t>(), scratch.as<uint8_t>(), stream);
+        VR_HIP(hipGetLastError());
+        VR_HIP(hipStreamSynchronize(stream));                   // the scratch half goes with this scope
+        g.clear_table = table;
+    }
+    t.d = g.clear_table ? g.clear_table->as<uint8_t>() : nullptr;
+    return t;
+}
+
+void RendererHIP::expected_stats_read(uint64_t out[4]) {
+    if (!expected_stats_valid_ || !expected_stats_) throw std::runtime_error("expected_stats: the last expected-value pass did not count (set expected_stats 1 before it)");
+    unsigned long long v[4];
+    expected_stats_->download(v, sizeof v, stream);
+    for (int i = 0; i < 4; ++i) out[i] = (uint64_t)v[i];
+}
+
+void RendererHIP::expected_clear_table(uint8_t* out, int cells[3]) {
+    flush_pending();
+    LaunchInputs in;
+    capture(in);                                                 // the scene as the pass reads it (the decoded float atlas under a transfer function)
+    BrickGridHIP& g = density_grids.at(in.frame);
+    const ClearTable t = clear_table_of(g, make_view(g, false, in.P.density.maj_blocked != 0));
+    for (int i = 0; i < 3; ++i) cells[i] = t.n[i];
+    if (out && g.clear_table) g.clear_table->download(out, g.clear_table->size_bytes(), stream);
 }
 
 // Test hook (vr_probe.h).  The scene as the next launch reads it: capture() and the majorant table as submit() / render_features() bring them up to date.  A PAIR form

@@ -48,6 +48,8 @@ struct BrickGridHIP {
     bool atlas_f32_failed = false; // its allocation failed once: not retried until commit() or a tf_float_atlas toggle (the byte atlas serves)
     DeviceBufferPtr atlas_paired;  // this grid's voxels interleaved with those of the frame's other grid (density + emission grids of one brick layout: vr_scene.h);
                                    // one buffer, held by both grids of the frame; built by commit()
+    DeviceBufferPtr clear_table;   // clear-distance table (vr_clear.h), one byte per cell, built by the first expected-value pass that reads this grid; a grid
+                                   // that commit() uploads anew starts without one
     DeviceBufferPtr dense;         // dense fp16 voxels in 4x4x4 blocks (DenseGridF16), then bricks/atlas are empty
     int32_t dim[3] = { 0, 0, 0 };
     int32_t dblk[2] = { 0, 0 };            // 4x4x4 blocks per axis (x, y) of the dense layout
@@ -195,8 +197,18 @@ struct RendererHIP {
     // render_features_expected(rays): the expected values of the same features from rays x rays deterministic ray marches per pixel (vr_expected.h
     // expected_pixel; rays in 1..4) into the same buffer -- the limit of render_features for spp -> infinity, without noise, at a cost independent of spp.
     // Counts as a feature pass for everything that needs one.
+    // expected_skip = 1: the march reads the density grid's clear-distance table (vr_clear.h) and drops the steps of empty space with their loads -- the
+    // same bits as 0, which runs every step.  The table is built on the device when the first such pass reads a grid (each frame of an animation has its
+    // own; commit() drops them all): renders that never ask for the pass pay nothing.  expected_stats = 1: the passes count their work in the
+    // instrumented twin of the kernel; expected_stats_read waits and returns the last pass's totals (sub-rays marched, steps reached, steps that fetched
+    // their corners, table reads), and throws when that pass did not count.  expected_clear_table: test hook, the current density grid's table (built if
+    // need be) and its extent in cells; out may be null.
     void render_features(int spp);
     void render_features_expected(int rays);
+    int expected_skip = 1;
+    int expected_stats = 0;
+    void expected_stats_read(uint64_t out[4]);
+    void expected_clear_table(uint8_t* out, int cells[3]);
     // test hook (vr_probe.h): n items of probe `what` in compile-time form `form`, host arrays in (4 words per item) and out (probe_out_words floats per item), run by
     // probe_kernel on the SceneParams the next launch would get -- after capture() (float atlas) and update_majorants, with the paired atlas where a kernel reads it.
     // Throws for a form the scene cannot serve.  Synchronous; touches no framebuffer.
@@ -304,6 +316,9 @@ private:
     const uint32_t* seed_table_for(const SceneParams& P, int s0, int n, hipStream_t stream, int* samples);
     DeviceBufferPtr stats_;                            // 32 counters of the instrumented kernels (sched_stats)
     DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
+    DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
+    bool expected_stats_valid_ = false;                // ... which that pass filled
+    ClearTable clear_table_of(BrickGridHIP& g, const GridView& view);      // the grid's table, built on `stream` if it has none
     DeviceBufferPtr moments_;                          // W*H*4 second moments, allocated by the first launch with `variance` on
     int moments_n_ = -1;                               // the moments cover samples 1..moments_n_ (-1: they do not start at sample 1)
     void check_moments(const char* who);               // throws unless the moments cover samples 1..sample (of every tile, on a ragged frame)

@@ -46,8 +46,12 @@ constexpr uint32_t kFeatureLostStatus = 4u;
 void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t spp, float* out, uint32_t* status, hipStream_t stream);
 // The same buffer, same tiles, filled with the expected values of those features instead: rays x rays deterministic ray marches per pixel (vr_expected.h
 // expected_pixel), rays in 1..kExpectedMaxRays.  Bounded by construction: no status word.
+// clear: the clear-distance table of P.density (launch_clear_table), by which the march drops the steps of empty space -- same bits; nullptr, or a table without
+// bytes: every step runs.  stats: 4 device counters that the launch ADDS to, in the instrumented twin of the kernel (sub-rays marched, steps reached, steps
+// that fetched their corners, reads of the table); nullptr: the plain kernel.
 constexpr int32_t kExpectedMaxRays = 4;
-void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream);
+void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream,
+                              const ClearTable* clear = nullptr, unsigned long long* stats = nullptr);
 // which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
 // what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
 enum PathtraceVariantReason : int {
@@ -133,6 +137,8 @@ void launch_pair_atlas(const uint8_t* atlas_density, const uint8_t* atlas_emissi
 
 // decoded float atlas (one float per atlas byte: rmin + unorm8(b) * rdiff of its brick), used by transfer-function renders
 void launch_decode_atlas(const float* rng, const uint8_t* atlas, float* out, size_t n_records, hipStream_t stream);
+// Clear-distance table of the grid behind view g (vr_clear.h): table and scratch hold one byte per cell of clear_cells(g) each (vr_scene.h); the result is in table.
+void launch_clear_table(const GridView& g, uint8_t* table, uint8_t* scratch, hipStream_t stream);
 // Path-seed table (vr_tiles.h seed_table_index): the entries of the 0-based sample numbers [s_begin, s_end) of every pixel of the W x H frame's tiles, each
 // vr_trace.h path_seed(seed, W, px, py, s + 1) -- what do_new hashes for that sample.  table holds s_end * tile_count(W, H) * 256 entries at least.
 void launch_seed_fill(uint32_t* table, uint32_t seed, int32_t W, int32_t H, int32_t s_begin, int32_t s_end, hipStream_t stream);

@@ -28,10 +28,25 @@
 //   Sums      float32, in step order, then sub-ray order: K += w, D += w * t, A += w * a, N += w * n^ (each product rounded, then the sum).
 //   Output    albedo = A / K, coverage = K / (float)(n * n), normal = N / K (not renormalised, as in feature_pixel), depth = D / K; all eight
 //             zero when !(K > 0).  t is the distance along the unit camera ray, as in feature_sample.
-// The emission grid, the integrator setting and the majorant table play no part; nothing is skipped: a step in empty space loads its eight corners and
-// adds nothing.
+// The emission grid, the integrator setting and the majorant table play no part.
+//
+// Empty space (SKIP, with the clear-distance table of vr_clear.h; without one the march is the text above, step by step).  A step whose eight corners
+// are all +0 has raw = +0 whatever its weights, so its sigma is the value s0 of the Density line at raw = +0.0f; when !(s0 > 0) -- always without a LUT:
+// vol_density_scale * (+0) is +-0 or NaN; with one unless the LUT's alpha at density 0 is positive -- such a step contributes nothing and may be
+// dropped with its loads.  s0 is evaluated once per pixel; when it is > 0 the pixel marches every step.  Otherwise step k, before it loads anything,
+// reads the byte d of the cell that holds its midpoint ip, cell floor(ip / 8) per axis:
+//   ip outside the table (NaN included) or d == 0: the step runs as above.
+//   d >= 1: the cell is clear, the corners -- floor(ip - 0.5) and one more per axis -- lie in its grown box: the step is dropped.  And it leaps: the
+//           midpoints of a sub-ray whose m is not capped move h |idir_i| <= h L <= 1 voxel per step and axis, so the next 7 (d - 1) of them lie
+//           less than 8 (d - 1) voxels from this one, within d - 1 cells of its cell, which are all clear (or outside the grid): k += 1 + 7 (d - 1),
+//           and the table is read again where that lands.  The eighth of a cell per cell is the margin against rounding, which is why a sub-ray
+//           leaps only while max |ipos_i| + tfar max |idir_i| < 2^16 (kExpectedLeapBound): there a midpoint is computed to within 0.02 voxels.
+//           Every other sub-ray -- m capped at kExpectedMaxSteps, or coordinates beyond that bound -- drops one step at a time.
+// The frame is the same bits with and without the table.  ExpectedRayInfo::steps stays the step index the sub-ray reached, dropped steps included
+// (a leap past the last step ends at m).
 #pragma once
 
+#include "vr_clear.h"
 #include "vr_trace.h"
 
 namespace vr {
@@ -43,10 +58,49 @@ struct ExpectedSums { float K, D; v3 A, N; };
 // what a test harness may want to know of one sub-ray: its step count (0: it contributed nothing), the steps it ran, and the transmittance it ended with
 struct ExpectedRayInfo { int32_t m, steps; float T; };
 
+// what an instrumented pass counts, summed over the sub-rays it is handed to: sub-rays marched (m > 0), the step indices they reached
+// (ExpectedRayInfo::steps), the steps that fetched their corners, the reads of the clear-distance table; audit (host harness only): dropped steps
+// that, evaluated in full, have sigma > 0 -- none, if the table is what vr_clear.h says
+struct ExpectedWork { uint32_t rays, steps, fetched, reads, audit; };
+constexpr float kExpectedLeapBound = 65536.0f;
+
 VR_HD bool expected_finite(float x) { return abs_(x) < inf_(); }
 
-template <bool TF, bool INFO = false>
-VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t i, int32_t j, int32_t n, ExpectedSums& S, ExpectedRayInfo* info = nullptr) {
+// the Density line: sigma and albedo of the step at ip, its corners left in io for the normal
+template <bool TF>
+VR_HD float expected_sigma(const SceneParams& P, v3 ip, v3 alb, TriIO& io, v3& a) {
+    const Uniforms& u = P.u;
+    trilinear_prep(P.density, ip, io);
+    trilinear_load(P.density, io);
+    const float raw = trilinear_value(P.density, io);
+    float sigma = u.vol_density_scale * raw;
+    a = alb;
+    if (TF) {
+        float rgba[4];
+        tf_lookup(P, sigma * u.vol_inv_majorant, rgba);
+        sigma = rgba[3] * u.vol_majorant;
+        a = alb * v3{ rgba[0], rgba[1], rgba[2] };
+    }
+    return sigma;
+}
+// the same line at raw = +0.0f: the sigma of every step whose eight corners are +0
+template <bool TF>
+VR_HD float expected_sigma_of_zero(const SceneParams& P) {
+    const Uniforms& u = P.u;
+    float sigma = u.vol_density_scale * 0.0f;
+    if (TF) {
+        float rgba[4];
+        tf_lookup(P, sigma * u.vol_inv_majorant, rgba);
+        sigma = rgba[3] * u.vol_majorant;
+    }
+    return sigma;
+}
+
+// SKIP: with clear (its table not null) and skip (the pixel's !(expected_sigma_of_zero > 0)) steps in clear cells are dropped; WORK: work counts;
+// AUDIT (host only, with WORK): every dropped step is evaluated all the same and counted in work->audit when its sigma > 0
+template <bool TF, bool INFO = false, bool SKIP = false, bool WORK = false, bool AUDIT = false>
+VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t i, int32_t j, int32_t n, ExpectedSums& S, ExpectedRayInfo* info = nullptr,
+                           const ClearTable* clear = nullptr, bool skip = false, ExpectedWork* work = nullptr) {
     const Uniforms& u = P.u;
     const int32_t W = u.resolution[0], H = u.resolution[1];
     if (INFO) { info->m = 0; info->steps = 0; info->T = 1.0f; }
@@ -66,22 +120,40 @@ VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t
     const float h = len / (float)m;
     const v3 alb = v3{ u.vol_albedo[0], u.vol_albedo[1], u.vol_albedo[2] };
     const float* mi = u.vol_density_inv_transform;         // column-major: row i of transpose(Minv3) = column i of Minv3
+    bool leap = false;
+    float lim[3] = { 0.0f, 0.0f, 0.0f };
+    if (SKIP && skip) {
+        const float reach = max_(max_(abs_(ipos.x), abs_(ipos.y)), abs_(ipos.z)) + tfar * max_(max_(abs_(idir.x), abs_(idir.y)), abs_(idir.z));
+        leap = m < kExpectedMaxSteps && reach < kExpectedLeapBound;
+        for (int c = 0; c < 3; ++c) lim[c] = (float)(clear->n[c] << 3);
+    }
     float T = 1.0f;
     int32_t k = 0;
     for (; k < m; ++k) {
         const float t = tnear + ((float)k + 0.5f) * h;
+        const v3 ip = axpy(ipos, t, idir);
         TriIO io;
-        trilinear_prep(P.density, axpy(ipos, t, idir), io);
-        trilinear_load(P.density, io);
-        const float raw = trilinear_value(P.density, io);
-        float sigma = u.vol_density_scale * raw;
-        v3 a = alb;
-        if (TF) {
-            float rgba[4];
-            tf_lookup(P, sigma * u.vol_inv_majorant, rgba);
-            sigma = rgba[3] * u.vol_majorant;
-            a = alb * v3{ rgba[0], rgba[1], rgba[2] };
+        v3 a;
+        if (SKIP && skip) {
+            // (One loop over fetched and dropped steps alike: neighbouring rays cross the same cells nearly in lockstep, so a wavefront mostly drops or fetches as
+            // one.  A loop of its own that runs each lane ahead to its next fetching step measured slower: profiles/r12_expected_skip.txt.)
+            // inside the table on the floats (NaN fails), after which truncation is floor
+            if ((ip.x >= 0.0f) & (ip.x < lim[0]) & (ip.y >= 0.0f) & (ip.y < lim[1]) & (ip.z >= 0.0f) & (ip.z < lim[2])) {
+                const uint32_t cx = (uint32_t)(int32_t)ip.x >> 3, cy = (uint32_t)(int32_t)ip.y >> 3, cz = (uint32_t)(int32_t)ip.z >> 3;
+                const uint32_t d = clear->d[(cz * (uint32_t)clear->n[1] + cy) * (uint32_t)clear->n[0] + cx];
+                if (WORK) ++work->reads;
+                if (d != 0u) {
+                    const int32_t more = leap ? 7 * ((int32_t)d - 1) : 0;
+                    if (AUDIT)
+                        for (int32_t kk = k; kk <= k + more && kk < m; ++kk)
+                            if (expected_sigma<TF>(P, axpy(ipos, tnear + ((float)kk + 0.5f) * h, idir), alb, io, a) > 0.0f) ++work->audit;
+                    k += more;
+                    continue;
+                }
+            }
         }
+        if (WORK) ++work->fetched;
+        const float sigma = expected_sigma<TF>(P, ip, alb, io, a);
         if (!(sigma > 0.0f)) continue;
         const float e = exp_(-(sigma * h));
         const float w = T * (1.0f - e);
@@ -95,16 +167,20 @@ VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t
         S.N = S.N + nh * w;
         if (T <= kExpectedMinT) { ++k; break; }
     }
+    if (SKIP && k > m) k = m;                              // a leap past the last step
     if (INFO) { info->m = m; info->steps = k; info->T = T; }
+    if (WORK) { ++work->rays; work->steps += (uint32_t)k; }
 }
 
 // info (INFO only): n * n entries, sub-ray j * n + i
-template <bool TF, bool INFO = false>
-VR_HD void expected_pixel(const SceneParams& P, int32_t px, int32_t py, int32_t n, float out[8], ExpectedRayInfo* info = nullptr) {
+template <bool TF, bool INFO = false, bool SKIP = false, bool WORK = false, bool AUDIT = false>
+VR_HD void expected_pixel(const SceneParams& P, int32_t px, int32_t py, int32_t n, float out[8], ExpectedRayInfo* info = nullptr,
+                          const ClearTable* clear = nullptr, ExpectedWork* work = nullptr) {
     ExpectedSums S;
     S.K = 0.0f; S.D = 0.0f; S.A = v3{ 0, 0, 0 }; S.N = v3{ 0, 0, 0 };
+    const bool skip = SKIP && clear && clear->d && !(expected_sigma_of_zero<TF>(P) > 0.0f);
     for (int32_t j = 0; j < n; ++j)
-        for (int32_t i = 0; i < n; ++i) expected_subray<TF, INFO>(P, px, py, i, j, n, S, INFO ? info + (j * n + i) : nullptr);
+        for (int32_t i = 0; i < n; ++i) expected_subray<TF, INFO, SKIP, WORK, AUDIT>(P, px, py, i, j, n, S, INFO ? info + (j * n + i) : nullptr, clear, skip, work);
     for (int32_t c = 0; c < 8; ++c) out[c] = 0.0f;
     if (!(S.K > 0.0f)) return;
     out[0] = S.A.x / S.K; out[1] = S.A.y / S.K; out[2] = S.A.z / S.K; out[3] = S.K / (float)(n * n);

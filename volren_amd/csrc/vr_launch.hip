@@ -101,22 +101,50 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
 // deterministic marches of at most kExpectedMaxSteps steps each -- a bounded loop, so no status word.  An 8x8 patch of neighbouring rays walks the same bricks
 // nearly in lockstep: a step's eight corner taps mostly hit lines a neighbouring lane has just loaded, and trip counts differ only at silhouettes.  The LUT is read
 // from global memory: its two rows per step are shared by neighbouring lanes too, and the kernel keeps its registers and LDS for occupancy.
-template <bool TF>
+// SKIP: the instance that reads the clear-distance table `clear` (vr_expected.h: steps in clear cells are dropped with their loads, same bits); the table is an
+// argument of this kernel alone.  STATS: the instrumented twin: every lane counts (ExpectedWork), the wavefront sums, and its lanes 0..3 add one total each to
+// stats[0..3] in one atomic instruction.  No lane leaves before that sum.
+template <bool TF, bool SKIP, bool STATS>
 __global__ void __launch_bounds__(256)
-features_expected_kernel(const SceneParams P, const int32_t* __restrict__ tiles, int32_t rays, float* __restrict__ out) {
+features_expected_kernel(const SceneParams P, const int32_t* __restrict__ tiles, int32_t rays, float* __restrict__ out, const ClearTable clear,
+                         unsigned long long* __restrict__ stats) {
     const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
     const TilePixel q = wave_tiled_pixel(tiles ? tiles[blockIdx.x] : (int32_t)blockIdx.x, threadIdx.x, W);
-    if (q.px >= W || q.py >= H) return;
-    float f[8];
-    expected_pixel<TF>(P, q.px, q.py, rays, f);
-    float4* o = reinterpret_cast<float4*>(out) + 2u * ((size_t)q.py * W + q.px);
-    o[0] = pack4(f);
-    o[1] = pack4(f + 4);
+    const bool live = q.px < W && q.py < H;
+    if (!STATS && !live) return;
+    ExpectedWork work = { 0u, 0u, 0u, 0u, 0u };
+    if (live) {
+        float f[8];
+        expected_pixel<TF, false, SKIP, STATS>(P, q.px, q.py, rays, f, nullptr, SKIP ? &clear : nullptr, STATS ? &work : nullptr);
+        float4* o = reinterpret_cast<float4*>(out) + 2u * ((size_t)q.py * W + q.px);
+        o[0] = pack4(f);
+        o[1] = pack4(f + 4);
+    }
+    if (STATS) {
+        uint32_t v[4] = { work.rays, work.steps, work.fetched, work.reads };      // per lane at most 16 x 4096 steps: the sums of 64 lanes fit
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            for (int o = 32; o > 0; o >>= 1) v[c] += (uint32_t)__shfl_xor((int)v[c], o);
+        const uint32_t lane = threadIdx.x & 63u;
+        if (lane < 4u) atomicAdd(stats + lane, (unsigned long long)(lane == 0u ? v[0] : (lane == 1u ? v[1] : (lane == 2u ? v[2] : v[3]))));
+    }
 }
-void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream) {
+void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream,
+                              const ClearTable* clear, unsigned long long* stats) {
     if (n_tiles <= 0 || rays < 1 || rays > kExpectedMaxRays) return;
-    if (P.u.use_tf) hipLaunchKernelGGL(features_expected_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, rays, out);
-    else hipLaunchKernelGGL(features_expected_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0, stream, P, tiles, rays, out);
+    const bool skip = clear && clear->d;
+    const ClearTable C = skip ? *clear : ClearTable{ nullptr, { 0, 0, 0 } };
+    const bool tf = P.u.use_tf != 0;
+    const dim3 grid((unsigned)n_tiles), block(256);
+#define VR_EXPECTED_LAUNCH(TF, SKIP, STATS) hipLaunchKernelGGL((features_expected_kernel<TF, SKIP, STATS>), grid, block, 0, stream, P, tiles, rays, out, C, stats)
+    if (stats) {
+        if (skip) { if (tf) VR_EXPECTED_LAUNCH(true, true, true); else VR_EXPECTED_LAUNCH(false, true, true); }
+        else { if (tf) VR_EXPECTED_LAUNCH(true, false, true); else VR_EXPECTED_LAUNCH(false, false, true); }
+    } else {
+        if (skip) { if (tf) VR_EXPECTED_LAUNCH(true, true, false); else VR_EXPECTED_LAUNCH(false, true, false); }
+        else { if (tf) VR_EXPECTED_LAUNCH(true, false, false); else VR_EXPECTED_LAUNCH(false, false, false); }
+    }
+#undef VR_EXPECTED_LAUNCH
 }
 
 // Units of 8 samples x 64 pixels, except on the dense-grid kernel, whose long paths (128 bounces, every camera ray scatters) fill

@@ -162,6 +162,13 @@ VR_SCENE_HD uint64_t grid_largest_table_bytes(const GridView& g, bool paired, bo
     return a > m ? a : m;
 }
 
+// The clear-distance table of a density grid (vr_clear.h): one byte per cell of 8^3 voxels -- the bricks; ceil(dim / 8) cells per axis of a dense grid --, x
+// fastest.  An argument of its own of the one kernel that reads it (vr_launch.hip features_expected_kernel), not part of the views above.  d == nullptr: no table.
+struct ClearTable { const uint8_t* d; int32_t n[3]; };
+VR_SCENE_HD void clear_cells(const GridView& g, int32_t n[3]) {
+    for (int i = 0; i < 3; ++i) n[i] = g.dense ? (g.dim[i] + 7) >> 3 : g.nb[i];
+}
+
 struct Uniforms {                // names follow the GLSL uniforms
     int32_t bounces, seed, show_environment;
     float cam_pos[3], cam_fov, cam_transform[9];

@@ -1,8 +1,9 @@
 // vr_setup.hip -- scene and environment setup kernels (gfx950), run at commit() or when a setting changes, never per frame:
 // the environment importance pyramid + warp table (env_setup.glsl, environment.cpp), the dense->brick encoder (voldata to_brick_grid at
-// commit()) with its range mips, the paired and the decoded atlas, and the majorant tables.
+// commit()) with its range mips, the paired and the decoded atlas, the majorant tables, and the clear-distance table of the expected-value pass.
 #include <hip/hip_runtime.h>
 
+#include "vr_clear.h"
 #include "vr_device.h"
 #include "vr_trace.h"
 
@@ -257,6 +258,39 @@ void launch_majorants(const SceneParams& P, const uint32_t* range_words_all_mips
     L.n_mips = n_mips;
     const uint32_t n = (uint32_t)majorant_padded_cells((uint32_t)(mshift[0] + mshift[1] + mshift[2]));
     hipLaunchKernelGGL(majorant_kernel, dim3((n + 256u) / 256u), dim3(256), 0, stream, P, range_words_all_mips, L, n, out_padded, out16_padded);      // n + 1 cells
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Clear-distance table of a density grid (vr_clear.h), built at the first expected-value pass that reads the grid.
+//   1. clear_mark_kernel : one wavefront per cell, the 1000 voxels of its grown box spread over the lanes; 255 when all of them are +0, else 0
+//   2. clear_axis_kernel : one thread per cell, once per axis (x, y, z), each from one buffer into the other
+__global__ void __launch_bounds__(256)
+clear_mark_kernel(const GridView g, int32_t n0, int32_t n1, int32_t n2, uint8_t* __restrict__ out) {
+    const uint32_t cell = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (cell >= (uint32_t)n0 * (uint32_t)n1 * (uint32_t)n2) return;                    // the whole wavefront
+    const int32_t cx = (int32_t)(cell % (uint32_t)n0), cy = (int32_t)((cell / (uint32_t)n0) % (uint32_t)n1), cz = (int32_t)(cell / ((uint32_t)n0 * (uint32_t)n1));
+    const uint32_t bits = clear_box_bits(g, cx, cy, cz, (int32_t)lane, 64);
+    const bool any = __ballot(bits != 0u) != 0ull;
+    if (lane == 0u) out[cell] = any ? (uint8_t)0 : (uint8_t)kClearMax;
+}
+__global__ void __launch_bounds__(256)
+clear_axis_kernel(const uint8_t* __restrict__ in, int32_t n0, int32_t n1, int32_t n2, int32_t axis, uint8_t* __restrict__ out) {
+    const uint32_t cell = blockIdx.x * 256u + threadIdx.x;
+    if (cell >= (uint32_t)n0 * (uint32_t)n1 * (uint32_t)n2) return;
+    const int32_t n[3] = { n0, n1, n2 };
+    const int32_t cx = (int32_t)(cell % (uint32_t)n0), cy = (int32_t)((cell / (uint32_t)n0) % (uint32_t)n1), cz = (int32_t)(cell / ((uint32_t)n0 * (uint32_t)n1));
+    out[cell] = (uint8_t)clear_axis_pass(in, n, axis, cx, cy, cz);
+}
+void launch_clear_table(const GridView& g, uint8_t* table, uint8_t* scratch, hipStream_t stream) {
+    int32_t n[3];
+    clear_cells(g, n);
+    const uint32_t cells = (uint32_t)n[0] * (uint32_t)n[1] * (uint32_t)n[2];
+    if (cells == 0u) return;
+    hipLaunchKernelGGL(clear_mark_kernel, dim3((cells + 3u) / 4u), dim3(256), 0, stream, g, n[0], n[1], n[2], scratch);
+    const dim3 grid((cells + 255u) / 256u);
+    hipLaunchKernelGGL(clear_axis_kernel, grid, dim3(256), 0, stream, scratch, n[0], n[1], n[2], 0, table);
+    hipLaunchKernelGGL(clear_axis_kernel, grid, dim3(256), 0, stream, table, n[0], n[1], n[2], 1, scratch);
+    hipLaunchKernelGGL(clear_axis_kernel, grid, dim3(256), 0, stream, scratch, n[0], n[1], n[2], 2, table);
 }
 
 // Path-seed table: one thread per entry of the sample numbers [s_begin, s_begin + n) (vr_device.h launch_seed_fill).  Consecutive threads write consecutive entries.

@@ -8,7 +8,8 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "denoise_moments", "wide_addressing", "seed_table_mb", "seed_table_max_samples")
+               "variance", "denoise_iterations", "denoise_moments", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
+               "expected_skip", "expected_stats")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
@@ -254,6 +255,26 @@ class Renderer:
         if sync:
             self.synchronize()
 
+    def expected_stats(self, enable=None):
+        """Work counters of the expected-value pass (include/volren_amd.h vr_expected_stats).  Like `variance`, the name is a field and a method:
+        `r.expected_stats = 1`, or expected_stats(True / False), switches the counting of the following passes on or off (vr_set_int
+        "expected_stats"; get_int reads it back); expected_stats() waits and returns the last pass's totals
+        {"rays", "steps", "fetched", "reads"}: sub-rays marched, steps reached, steps that fetched their corners, reads of the clear-distance table."""
+        if enable is not None:
+            _lib.check(self._L.vr_set_int(self._h, b"expected_stats", 1 if enable else 0))
+            return None
+        out = (C.c_uint64 * 4)()
+        _lib.check(self._L.vr_expected_stats(self._h, out))
+        return dict(zip(("rays", "steps", "fetched", "reads"), (int(v) for v in out)))
+
+    def expected_clear_table(self):
+        """Test hook (vr_expected_clear_table): the clear-distance table of the current density grid, uint8 [cz][cy][cx], built if need be."""
+        n = (C.c_int * 3)()
+        _lib.check(self._L.vr_expected_clear_table(self._h, None, n))
+        out = np.empty((n[2], n[1], n[0]), np.uint8)
+        _lib.check(self._L.vr_expected_clear_table(self._h, out.ctypes.data, n))
+        return out
+
     def features(self):
         """[H][W][8] float32, row 0 = bottom: albedo.rgb, coverage, normal.xyz, depth."""
         out = np.empty((self.height, self.width, 8), np.float32)
@@ -489,6 +510,17 @@ class ShardedRenderer:
         _lib.check(self._L.vr_sharded_render_features_expected(self._h, int(rays)))
         if sync:
             self.synchronize()
+
+    @property
+    def expected_skip(self):
+        """Whether the parts' expected-value passes drop the steps of empty space (Renderer.expected_skip): part 0's field; setting it sets every part's.
+        Every part builds the clear-distance table of its own copy of the grid."""
+        return self.parts[0].expected_skip
+
+    @expected_skip.setter
+    def expected_skip(self, value):
+        for p in self.parts:
+            p.expected_skip = value
 
     def gather_guides(self):
         """Every part's moments and features of its tiles into `parts[0]` (vr_sharded_gather_guides): one exchange, asynchronous."""

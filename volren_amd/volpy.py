@@ -424,7 +424,7 @@ class Renderer:
     def __getattr__(self, name):
         if name == "variance":
             return self._r.get_int("variance")
-        if name in ("denoise_reject", "denoise_moments"):
+        if name in ("denoise_reject", "denoise_moments", "expected_skip"):
             return getattr(self._r, name)
         if name in _SCALARS:
             return getattr(self._r, name)
@@ -433,7 +433,7 @@ class Renderer:
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments"):
+        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments", "expected_skip"):
             setattr(self._r, name, value)
         elif name in _VEC3S:
             setattr(self._r, name, np.asarray(vec3(value) if np.ndim(value) == 0 else value, np.float32).reshape(3))
@@ -539,7 +539,8 @@ class Renderer:
         self._r.render_features(int(spp))
 
     def render_features_expected(self, rays=2):
-        """The same features as expected values: rays x rays deterministic ray marches per pixel (1..4), noise-free and independent of `seed`."""
+        """The same features as expected values: rays x rays deterministic ray marches per pixel (1..4), noise-free and independent of `seed`.
+        `expected_skip` (default 1) lets the march drop the steps of empty space; 0 runs every step, to the same bits."""
         self._r.render_features_expected(int(rays))
 
     def feature_data(self):
