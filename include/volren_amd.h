@@ -264,6 +264,38 @@ int vr_denoise_history_reset(vr_renderer* r);
 int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* length_out);
 int vr_denoise_reject_stat(vr_renderer* r, float* out);
 int vr_denoise_history_moments(vr_renderer* r, float* out);
+/* --- the frame's hit/miss noise replaced by the expected coverage: a control variate in image space (no reference counterpart).
+ *     A sample's alpha is 1 when its path scattered at least once and 0 when it flew through, so the framebuffer's alpha is kappa^, the share of a
+ *     pixel's samples that hit.  vr_render_features_expected gives the same number without noise: kappa, the coverage channel of the feature buffer.
+ *     In a partially covered pixel a sample is either the environment behind the volume (radiance B) or scattered light (conditional mean C); which
+ *     of the two is a coin toss whose variance kappa (1 - kappa) (B - C)^2 dominates the pixel wherever the environment is much brighter or darker
+ *     than the volume.  vr_resolve removes it:
+ *         y = x + beta (kappa^ - kappa),   beta = B - C~
+ *     x the frame's mean; B the mean environment radiance over the sub-rays of the expected pass (what the path tracer adds for an escaping camera
+ *     ray, strength and transform included; 0 while "show_environment" is 0); C~ = sum (x - (1 - kappa^) B) / sum kappa^ over the pixel's 7x7
+ *     neighbourhood, 0 where nothing in it hit; y.rgb not below 0, y.a = kappa.  A pixel with kappa^ = kappa keeps its rgb bit for bit.  The arithmetic
+ *     is specified operation by operation in volren_amd/csrc/vr_resolve.h and reproducible bit for bit.
+ *     Expectation: E[y] = E[x] + beta (E[kappa^] - kappa).  Under a transfer function the path tracer's tracker collides on the very field the expected
+ *     pass marches, and y is unbiased up to the coupling of C~ with kappa^.  Without one the tracker uses the smoother stochastic-tricubic field: the
+ *     two coverages differ by about 0.002 on average, and y carries beta times that as bias (README.md states the measured bias and the sample count
+ *     up to which the call pays).  With an emission grid the estimator stays valid but beta is no longer the best coefficient.
+ *     vr_resolve: asynchronous on the renderer's stream; a flush point like vr_denoise.  Works at any sample count, on ragged frames of
+ *     vr_render_adaptive too (only means are used), and needs no "variance".  VR_ERR, before anything is launched, when no sample is in the frame,
+ *     while a tile subset is set, while "integrator" is 2 (its alpha is an opacity, not a hit indicator), when the feature buffer was not last filled
+ *     by vr_render_features_expected since the last resize, or when that pass ran with rays < 2 (one ray gives the coverage of the pixel's centre,
+ *     not of its area).  The framebuffer, the features, the moments and what vr_draw / vr_display / vr_save_png show are left as they were; the three
+ *     W*H*4 buffers of the call are allocated by the first call and dropped by vr_resize.
+ *     vr_resolved waits and writes W*H*4 floats, linear (not tonemapped), row 0 at the bottom; vr_resolve_background (a test hook) the same of B, alpha 0.
+ *     Both are VR_ERR before the first vr_resolve since the last resize.
+ *     vr_set_int / vr_get_int "denoise_resolve" (0 or 1; default 0, and then every launch, allocation and result is what it is without this
+ *     paragraph; anything else is VR_ERR, the old value kept; a call that changes the value drops the history).  With 1, vr_denoise and
+ *     vr_denoise_temporal -- with "denoise_reject" and with "denoise_moments" too -- run vr_resolve first and start from y instead of the
+ *     framebuffer's colour, with the frame's variance unchanged (a variance derived for y filtered worse); whatever vr_resolve refuses they refuse
+ *     then, besides their own refusals.  vr_sharded_denoise / vr_sharded_denoise_temporal honour part 0's setting: part 0 holds the gathered frame and
+ *     guide, the resolve runs there, and the result is bit for bit one device's. */
+int vr_resolve(vr_renderer* r);
+int vr_resolved(vr_renderer* r, float* rgba_out);
+int vr_resolve_background(vr_renderer* r, float* rgba_out);
 /* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
  *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
  *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the

@@ -59,7 +59,8 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     resolution = { (int)w, (int)h };
     color = make_device_buffer((size_t)w * h * 4 * sizeof(float));
     display.reset();
-    features_.reset();
+    features_.reset(); features_pass_ = 0; features_rays_ = 0;
+    rs_bg_.reset(); rs_part_.reset(); resolved_.reset();
     moments_.reset(); moments_n_ = -1;
     dn_guide_.reset(); dn_var_[0].reset(); dn_var_[1].reset(); dn_color_[0].reset(); dn_color_[1].reset(); denoised_.reset();
     drop_history();
@@ -927,6 +928,7 @@ void RendererHIP::render_features(int spp) {
     if (spp <= 0) throw std::runtime_error("render_features: spp must be positive");
     SceneParams P;
     const int n_tiles = begin_feature_pass(P);
+    features_pass_ = 1; features_rays_ = 0;
     launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, features_->as<float>(), status_->as<uint32_t>(), stream);
     VR_HIP(hipGetLastError());
 }
@@ -945,6 +947,7 @@ void RendererHIP::render_features_expected(int rays) {
         VR_HIP(hipMemsetAsync(expected_stats_->get(), 0, expected_stats_->size_bytes(), stream));
         counters = expected_stats_->as<unsigned long long>();
     }
+    features_pass_ = 2; features_rays_ = rays;
     launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, features_->as<float>(), stream, &clear, counters);
     VR_HIP(hipGetLastError());
     expected_stats_valid_ = counters != nullptr;
@@ -1058,6 +1061,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     check_moments(who);
     if (temporal && denoise_moments != 0 && denoise_reject > 0.0f)
         throw std::runtime_error(me + "denoise_moments = 1 and denoise_reject > 0 do not go together: the rejection statistic needs the frames' sample variance, and the moment variance of 1-spp frames is too heavy-tailed for it (DESIGN.md 5)");
+    if (denoise_resolve != 0) check_resolve(me + "denoise_resolve = 1: ", whole_frame_gathered);
     const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
     if (ragged()) {
         for (int32_t c : tile_n_)
@@ -1085,9 +1089,11 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (N >= 2) { ensure_buffer(dn_var_[1], px * sizeof(float)); ensure_buffer(dn_color_[0], px * 4 * sizeof(float)); }
     if (N >= 3) ensure_buffer(dn_color_[1], px * 4 * sizeof(float));
     const float vscale = variance_scale(sample);      // download_variance's factor
+    if (denoise_resolve != 0) run_resolve();      // vr_resolve.h: the filter starts from y, with the frame's own variance
+    const DeviceBuffer* frame = denoise_resolve != 0 ? resolved_.get() : color.get();
     launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, counts, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
     VR_HIP(hipGetLastError());
-    const DeviceBuffer* first = color.get();          // what iteration 0 reads
+    const DeviceBuffer* first = frame;                // what iteration 0 reads
     if (temporal) {
         TemporalCamera cur;
         memset(&cur, 0, sizeof cur);
@@ -1101,14 +1107,14 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         const float* hr = have ? hist_record_[hist_cur_]->as<float>() : nullptr;
         const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
         if (moments)
-            launch_denoise_temporal_moments(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, have ? hist_moments_[hist_cur_]->as<float>() : nullptr,
+            launch_denoise_temporal_moments(frame->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, have ? hist_moments_[hist_cur_]->as<float>() : nullptr,
                                             same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha, sg, hist_color_[to]->as<float>(), hist_record_[to]->as<float>(),
                                             hist_moments_[to]->as<float>(), stream);
         else if (reject)
-            launch_denoise_temporal_reject(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H,
+            launch_denoise_temporal_reject(frame->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H,
                                            denoise_alpha, denoise_reject, dn_reject_->as<float>(), hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
         else
-            launch_denoise_temporal(color->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha,
+            launch_denoise_temporal(frame->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha,
                                     hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
         VR_HIP(hipGetLastError());
         reject_stat_ = reject;
@@ -1142,6 +1148,53 @@ void RendererHIP::set_denoise_moments(int v) {
     flush_pending();
     drop_history();
     denoise_moments = v;
+}
+
+// The control variate on the expected coverage (vr_resolve.h): prepare (B, P) and resolve, two launches on the whole frame.
+void RendererHIP::check_resolve(const std::string& me, bool whole_frame_gathered) {
+    if (sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
+    if (!tiles_host_.empty() && !whole_frame_gathered) throw std::runtime_error(me + "a tile subset is set (set_tiles); the coefficient pools every pixel's neighbours and is formed on whole frames only");
+    if (integrator == 2) throw std::runtime_error(me + "integrator = 2 (direct volume rendering) writes an opacity into alpha, not the share of samples that hit");
+    if (!features_ || features_pass_ != 2)
+        throw std::runtime_error(me + "the feature buffer was not last filled by render_features_expected since the last resize (the expected coverage is what replaces the frame's)");
+    if (features_rays_ < 2)
+        throw std::runtime_error(me + "the expected-value pass ran with rays = " + std::to_string(features_rays_) + "; rays >= 2 is needed (one ray gives the coverage of the pixel's centre, not of its area)");
+    if ((size_t)resolution.x * (size_t)resolution.y * 2u > (size_t)INT32_MAX) throw std::runtime_error(me + "frame too large (32-bit pixel indices)");
+}
+
+void RendererHIP::run_resolve() {
+    LaunchInputs in;
+    capture(in);                                                 // the scene as a launch reads it: the environment's arrays, strength and transform, the camera
+    const size_t bytes = (size_t)resolution.x * resolution.y * 4 * sizeof(float);
+    ensure_buffer(rs_bg_, bytes); ensure_buffer(rs_part_, bytes); ensure_buffer(resolved_, bytes);
+    launch_resolve(in.P, color->as<float>(), features_->as<float>(), features_rays_, rs_bg_->as<float>(), rs_part_->as<float>(), resolved_->as<float>(), stream);
+    VR_HIP(hipGetLastError());
+}
+
+void RendererHIP::resolve() {
+    flush_pending();
+    check_resolve("resolve: ", false);
+    run_resolve();
+}
+
+void RendererHIP::download_resolved(float* rgba) {
+    if (!resolved_) throw std::runtime_error("resolved: no resolve since the last resize (call resolve first)");
+    flush_pending();
+    resolved_->download(rgba, resolved_->size_bytes(), stream);
+}
+
+void RendererHIP::download_resolve_background(float* rgba) {
+    if (!rs_bg_ || !resolved_) throw std::runtime_error("resolve_background: no resolve since the last resize (call resolve first)");
+    flush_pending();
+    rs_bg_->download(rgba, rs_bg_->size_bytes(), stream);
+}
+
+void RendererHIP::set_denoise_resolve(int v) {
+    if (v != 0 && v != 1) throw std::runtime_error("denoise_resolve: 0 (the filter starts from the framebuffer) or 1 (from the frame resolved against the expected coverage)");
+    if (v == denoise_resolve) return;
+    flush_pending();
+    drop_history();
+    denoise_resolve = v;
 }
 
 void RendererHIP::download_history_moments(float* out) {

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "devmem.h"
@@ -234,12 +235,28 @@ struct RendererHIP {
     void denoise();
     void denoise_temporal();
     void drop_history();
+    // The control variate on the expected coverage (vr_resolve.h).  resolve(): the frame with its hit/miss noise replaced by the feature buffer's expected
+    // coverage, y = x + beta (alpha - kappa), into its own W*H*4 buffer (asynchronous; flushes recorded samples first).  Throws, before anything is launched,
+    // when sample < 1, a tile subset is set, integrator = 2 (its alpha is an opacity, not a hit indicator), or the feature buffer was not last filled -- since
+    // the last resize -- by render_features_expected with rays >= 2.  Ragged frames are fine: only means are used.  The framebuffer, features, moments and
+    // display are not touched.  download_resolved: that buffer, W*H*4 floats, alpha = kappa.  download_resolve_background: B, the environment behind every pixel
+    // as the last resolve() formed it (W*H*4, alpha 0; test hook).  Both throw before the first resolve since the last resize.
+    // denoise_resolve = 1: denoise() and denoise_temporal() -- with rejection and with moments too -- run resolve() first and start from its result instead of
+    // the framebuffer's colour, the frame's variance unchanged; whatever resolve() refuses they refuse then (0 is today's calls exactly).
+    // set_denoise_resolve: 0 or 1, throws otherwise; a change drops the history.
+    void resolve();
+    void check_resolve(const std::string& me, bool whole_frame_gathered);      // resolve()'s refusals, from host state alone: throws, launches nothing
+    void download_resolved(float* rgba);
+    void download_resolve_background(float* rgba);
+    void set_denoise_resolve(int v);
+    int denoise_resolve = 0;
     void download_history(float* rgba, float* var, float* length);
     void download_reject_stat(float* out);
     void set_denoise_moments(int v);
     void download_history_moments(float* out);
     void download_denoised(float* rgba);
     const DeviceBuffer* denoised() const { return denoised_.get(); }
+    const DeviceBuffer* resolved() const { return resolved_.get(); }
     // copy + tonemap of a W*H*4 buffer into `display` (draw() = draw_from(*color) after the flush)
     void draw_from(const DeviceBuffer& src);
     void download_display(float* rgba) const;
@@ -316,6 +333,9 @@ private:
     const uint32_t* seed_table_for(const SceneParams& P, int s0, int n, hipStream_t stream, int* samples);
     DeviceBufferPtr stats_;                            // 32 counters of the instrumented kernels (sched_stats)
     DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
+    int features_pass_ = 0, features_rays_ = 0;        // which pass filled it last since the resize: 0 none, 1 render_features, 2 render_features_expected with that many rays
+    DeviceBufferPtr rs_bg_, rs_part_, resolved_;       // resolve(): B, P and the resolved frame, W*H*4 each (allocated on first use, dropped by resize)
+    void run_resolve();                                       // its launches, after check_resolve
     DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
     bool expected_stats_valid_ = false;                // ... which that pass filled
     ClearTable clear_table_of(BrickGridHIP& g, const GridView& view);      // the grid's table, built on `stream` if it has none

@@ -367,6 +367,16 @@ void ShardedRenderer::exchange_guides() {
 
 void ShardedRenderer::run_denoise(const char* who, bool temporal) {
     check_guides(who);
+    if (parts_[0]->denoise_resolve != 0) {      // part 0's setting: its resolve reads the gathered guide, which must be one expected-value pass on every part
+        VR_HIP(hipSetDevice(devices_[0]));
+        parts_[0]->check_resolve(std::string("ShardedRenderer::") + who + ": denoise_resolve = 1: ", transport_ != "none");      // before the exchange launches anything
+        for (size_t i = 0; i < parts_.size(); ++i) {
+            if (transport_ != "none" && buf_[i].n_own == 0) continue;
+            if (parts_[i]->features_pass_ != parts_[0]->features_pass_ || parts_[i]->features_rays_ != parts_[0]->features_rays_)
+                throw std::runtime_error(std::string("ShardedRenderer::") + who + ": denoise_resolve = 1: part " + std::to_string(i) +
+                                         "'s feature buffer was not filled by the same pass as part 0's (call render_features_expected on the sharded renderer)");
+        }
+    }
     exchange_guides();
     VR_HIP(hipSetDevice(devices_[0]));
     parts_[0]->run_denoise(who, temporal, transport_ != "none");

@@ -97,6 +97,10 @@ void launch_denoise_temporal_moments(const float* color, float* v, const float* 
 void launch_denoise_temporal_reject(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
                                     const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float tau, float* scratch,
                                     float* out_color, float* out_record, hipStream_t stream);
+// The control variate of vr_resolve.h on the whole frame of P.u.resolution: fb (W*H*4, alpha = the share of samples that hit) and the coverage word of features
+// (W*H*8, an expected-value pass of `rays` rays per axis) -> B (W*H*4: the environment behind each pixel, 0 with it hidden), Pq (W*H*4: the scattered part and its
+// weight) and out (W*H*4: the resolved frame, alpha = the expected coverage).  Two kernels; no two arguments may overlap.
+void launch_resolve(const SceneParams& P, const float* fb, const float* features, int32_t rays, float* B, float* Pq, float* out, hipStream_t stream);
 // Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,

@@ -1,6 +1,6 @@
 // vr_filters.hip -- the image-space kernels (gfx950): everything that reads or writes whole frames or tiles of them after the path tracer.
 // The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h, vr_moments.h), the error estimate of adaptive
-// sampling (vr_adaptive.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
+// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
 // the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include "vr_denoise.h"
 #include "vr_device.h"
 #include "vr_moments.h"
+#include "vr_resolve.h"
 #include "vr_temporal.h"
 
 namespace vr {
@@ -245,6 +246,63 @@ void launch_denoise_temporal_reject(const float* color, float* v, const float* g
                        have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, sh, sr);
     hipLaunchKernelGGL(denoise_temporal_resolve_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
                        reinterpret_cast<const float4*>(guide), sh, sr, W, H, alpha, tau, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
+}
+
+// The control variate of vr_resolve.h, two kernels with the frames B and P (W*H float4 each) between them, because a pixel's coefficient pools the P of its
+// 7 x 7 neighbours.
+// prepare: the pixel's framebuffer texel in (one dwordx4), rays x rays environment lookups (none with the environment hidden), B and P out (two dwordx4).
+// resolve: stages P of the tile's 22 x 22 footprint (16 x 16 plus a halo of 3, one dwordx4 load per texel; zeros off the frame, which the lane code never
+// asks for) in 7744 B of LDS, one barrier -- threads outside the frame stage and wait with the others -- then reads the pixel's texels of the framebuffer and
+// of B and the coverage word of its features, sums its 49 taps from LDS and writes one dwordx4.  The same kernel with the taps read from global memory, as the
+// a-trous kernel reads its own, measured 53.5 us against 24.1 us at 1024 x 1024 (profiles/r13_resolve.txt) and was dropped.  No atomics, no scratch.
+constexpr int32_t kResolveFoot = 16 + 2 * kResolveWindow;      // edge of a tile's footprint in pixels
+struct ResolveWindowDev {
+    const float4* win;     // the staged footprint
+    int32_t at;            // the pixel's own texel in it
+    __device__ __forceinline__ void tap(int32_t dx, int32_t dy, float o[4]) const { unpack4(win[at + dy * kResolveFoot + dx], o); }
+};
+__global__ void __launch_bounds__(256)
+resolve_prepare_kernel(const SceneParams P, const float4* __restrict__ fb, int32_t rays, float4* __restrict__ B, float4* __restrict__ Pq) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float x[4], b[4], p[4];
+    unpack4(fb[i], x);
+    resolve_prepare_pixel(x, resolve_background(P, q.px, q.py, rays), b, p);
+    B[i] = pack4(b);
+    Pq[i] = pack4(p);
+}
+__global__ void __launch_bounds__(256)
+resolve_kernel(const float4* __restrict__ fb, const float4* __restrict__ features, const float4* __restrict__ B, const float4* __restrict__ Pq, int32_t W, int32_t H,
+               float4* __restrict__ out) {
+    __shared__ float4 win[kResolveFoot * kResolveFoot];
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    const int32_t nx = tiles_x(W);
+    const int32_t x0 = ((int32_t)blockIdx.x % nx) * 16 - kResolveWindow, y0 = ((int32_t)blockIdx.x / nx) * 16 - kResolveWindow;
+    for (int32_t f = (int32_t)threadIdx.x; f < kResolveFoot * kResolveFoot; f += 256) {
+        const int32_t x = x0 + f % kResolveFoot, y = y0 + f / kResolveFoot;
+        float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (x >= 0 && x < W && y >= 0 && y < H) t = Pq[y * W + x];
+        win[f] = t;
+    }
+    __syncthreads();
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float x[4], b[4], y[4];
+    unpack4(fb[i], x);
+    unpack4(B[i], b);
+    resolve_pixel(ResolveWindowDev{ win, (q.py - y0) * kResolveFoot + (q.px - x0) }, W, H, q.px, q.py, x, b, features[2 * i].w, y);
+    out[i] = pack4(y);
+}
+void launch_resolve(const SceneParams& P, const float* fb, const float* features, int32_t rays, float* B, float* Pq, float* out, hipStream_t stream) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    if (W <= 0 || H <= 0 || rays < 1) return;
+    const dim3 grid((unsigned)tile_count(W, H)), block(256);
+    hipLaunchKernelGGL(resolve_prepare_kernel, grid, block, 0, stream, P, reinterpret_cast<const float4*>(fb), rays, reinterpret_cast<float4*>(B),
+                       reinterpret_cast<float4*>(Pq));
+    hipLaunchKernelGGL(resolve_kernel, grid, block, 0, stream, reinterpret_cast<const float4*>(fb), reinterpret_cast<const float4*>(features),
+                       reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(Pq), W, H, reinterpret_cast<float4*>(out));
 }
 
 // Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile; each lane forms e_p of its pixel (-inf outside

@@ -8,7 +8,7 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "denoise_moments", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
+               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
                "expected_skip", "expected_stats")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
@@ -335,6 +335,28 @@ class Renderer:
         _lib.check(self._L.vr_denoised(self._h, out.ctypes.data))
         return out
 
+    # ---- control variate on the expected coverage ----
+    def resolve(self, sync=True):
+        """The frame with its hit/miss noise replaced by the expected coverage, y = x + (B - C~)(alpha - kappa) (include/volren_amd.h vr_resolve): needs
+        a render_features_expected(rays >= 2) since the last resize, no tile subset, `integrator` != 2; works at any sample count.  `denoise_resolve = 1`
+        makes denoise() and denoise_temporal() start from it."""
+        _lib.check(self._L.vr_resolve(self._h))
+        if sync:
+            self.synchronize()
+
+    def resolved(self):
+        """[H][W][4] float32, row 0 = bottom: the last resolve()'s result, linear (not tonemapped), alpha = the expected coverage."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _lib.check(self._L.vr_resolved(self._h, out.ctypes.data))
+        return out
+
+    def resolve_background(self):
+        """Test hook (vr_resolve_background): [H][W][4] float32, row 0 = bottom: the environment radiance B behind every pixel as the last resolve()
+        formed it (0 while `show_environment` is 0), alpha 0."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _lib.check(self._L.vr_resolve_background(self._h, out.ctypes.data))
+        return out
+
     # ---- adaptive sampling ----
     def render_adaptive(self, min_spp, max_spp, threshold, sync=True):
         """Per 16x16 tile: min_spp samples, then doubling until the tile's error e_t is below `threshold` or it has max_spp samples
@@ -573,6 +595,17 @@ class ShardedRenderer:
 
     def denoise_history_moments(self):
         return self.parts[0].denoise_history_moments()
+
+    @property
+    def denoise_resolve(self):
+        """Whether denoise() / denoise_temporal() start from the frame resolved against the expected coverage (Renderer.resolve): part 0's field, which
+        holds the gathered frame and guide and runs the resolve; setting it sets every part's."""
+        return self.parts[0].denoise_resolve
+
+    @denoise_resolve.setter
+    def denoise_resolve(self, value):
+        for p in self.parts:
+            p.denoise_resolve = value
 
 
 def math_probe(fn, a, b=None):

@@ -424,7 +424,7 @@ class Renderer:
     def __getattr__(self, name):
         if name == "variance":
             return self._r.get_int("variance")
-        if name in ("denoise_reject", "denoise_moments", "expected_skip"):
+        if name in ("denoise_reject", "denoise_moments", "denoise_resolve", "expected_skip"):
             return getattr(self._r, name)
         if name in _SCALARS:
             return getattr(self._r, name)
@@ -433,7 +433,7 @@ class Renderer:
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments", "expected_skip"):
+        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments", "denoise_resolve", "expected_skip"):
             setattr(self._r, name, value)
         elif name in _VEC3S:
             setattr(self._r, name, np.asarray(vec3(value) if np.ndim(value) == 0 else value, np.float32).reshape(3))
@@ -581,6 +581,17 @@ class Renderer:
     def denoised_data(self):
         """(w, h, 3) float: the colour of the last denoise() or denoise_temporal(), in fbo_data()'s shape."""
         return self._r.denoised()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
+
+    # -- control variate on the expected coverage (no reference counterpart): render, render_features_expected(rays >= 2), then resolve()
+    def resolve(self):
+        """The current frame with its hit/miss noise replaced by the expected coverage of the last render_features_expected (rays >= 2), at any sample
+        count (volren_amd.Renderer.resolve).  `denoise_resolve = 1` (default 0; a change drops the history) makes denoise() and denoise_temporal()
+        run it first and start from its result."""
+        self._r.resolve()
+
+    def resolved_data(self):
+        """(w, h, 3) float: the colour of the last resolve(), in fbo_data()'s shape."""
+        return self._r.resolved()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
 
     # -- adaptive sampling (no reference counterpart): like render(), from sample 0
     def render_adaptive(self, min_spp, max_spp, threshold):
