@@ -52,5 +52,13 @@ def pool_slots(chunk, n_tiles, tile_slot, sub, spu, sample, lane):
     return o64.reshape(args[0].shape), o32.reshape(args[0].shape)
 
 
+def window(r, tile, w):
+    """TileWindow<r> of `tile`: (kFoot, kTexels, x0, y0) and at[256], the window index of every wave-tiled thread's pixel"""
+    geom = np.zeros(4, np.int32)
+    at = np.zeros(256, np.int32)
+    assert lib().hk_tiles_window(int(r), int(tile), int(w), _p(geom), _p(at)) == 0, r
+    return tuple(int(v) for v in geom), at
+
+
 def variance_scale(n):
     return np.float32(lib().hk_tiles_variance_scale(int(n)))

@@ -7,31 +7,13 @@
 // A camera is 13 floats: cam_pos (3), cam_transform (9, column-major), cam_z.  checked != 0: every read of the history, of the window and of the
 // guide goes through a range check, and the functions return the number of reads outside the frame (0 is the only right answer).
 #include <cstdint>
-#include <cstring>
 
 #include "../../volren_amd/csrc/vr_moments.h"
+#include "host_frame.h"
 
 using namespace vr;
 
 namespace {
-// an index outside [0, n) is counted and not dereferenced (bad = nullptr: not checked)
-struct Range {
-    int64_t n;
-    int64_t* bad;
-    bool ok(int64_t i) const { if (!bad || (i >= 0 && i < n)) return true; ++*bad; return false; }
-};
-struct HostHist {
-    const float* c;      // W*H*4
-    const float* s;      // W*H*4: (V, N, K, D)
-    Range range;
-    void color(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? c[4 * (size_t)i + k] : 0.0f; }
-    void record(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? s[4 * (size_t)i + k] : 0.0f; }
-};
-struct HostMoments {
-    const float* m;      // W*H*4: (m1, m2, E, S)
-    Range range;
-    void moments(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? m[4 * (size_t)i + k] : 0.0f; }
-};
 // the window of pixel (px, py) over the whole frame's moment records (the kernel's LDS footprint holds the same pairs)
 struct HostWindow {
     const float* m;
@@ -46,18 +28,6 @@ struct HostWindow {
         o[0] = m[4 * i]; o[1] = m[4 * i + 1];
     }
 };
-struct HostGuide {
-    const float* g;      // W*H*8
-    Range range;
-    void guide(int32_t i, float o[8]) const { for (int k = 0; k < 8; ++k) o[k] = range.ok(i) ? g[8 * (size_t)i + k] : 0.0f; }
-};
-TemporalCamera camera_of(const float* p) {
-    TemporalCamera c;
-    std::memcpy(c.pos, p, 3 * sizeof(float));
-    std::memcpy(c.m, p + 3, 9 * sizeof(float));
-    c.cam_z = p[12];
-    return c;
-}
 }  // namespace
 
 extern "C" {

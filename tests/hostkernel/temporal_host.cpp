@@ -6,27 +6,15 @@
 // (tests/hk_temporal.py); tests/test_gpu_temporal.py and tests/test_gpu_reject.py check the HIP kernels against it bit for bit.
 // A camera is 13 floats: cam_pos (3), cam_transform (9, column-major), cam_z.
 #include <cstdint>
-#include <cstring>
 #include <vector>
 
 #include "../../volren_amd/csrc/vr_temporal.h"
+#include "host_frame.h"
 
 using namespace vr;
 
 namespace {
-// every read of the history and of the window goes through here: an index outside [0, n) is counted and not dereferenced (bad = nullptr: not checked)
-struct Range {
-    int64_t n;
-    int64_t* bad;
-    bool ok(int64_t i) const { if (!bad || (i >= 0 && i < n)) return true; ++*bad; return false; }
-};
-struct HostHist {
-    const float* c;      // W*H*4
-    const float* s;      // W*H*4: (V, N, K, D)
-    Range range;
-    void color(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? c[4 * (size_t)i + k] : 0.0f; }
-    void record(int32_t i, float o[4]) const { for (int k = 0; k < 4; ++k) o[k] = range.ok(i) ? s[4 * (size_t)i + k] : 0.0f; }
-};
+// every read of the history (host_frame.h HostHist) and of the window goes through a Range
 // the window of pixel (px, py) over the whole frame's z2 / has planes (the kernel's LDS footprint holds the same words)
 struct HostWindow {
     const float* z2;
@@ -41,13 +29,6 @@ struct HostWindow {
         return temporal_window_word(has[i] != 0, z2[i]);
     }
 };
-TemporalCamera camera_of(const float* p) {
-    TemporalCamera c;
-    std::memcpy(c.pos, p, 3 * sizeof(float));
-    std::memcpy(c.m, p + 3, 9 * sizeof(float));
-    c.cam_z = p[12];
-    return c;
-}
 // steps 1-4 of a whole frame; out_stat = nullptr: without 2a and 3a, in one pass.  -> the number of reads outside the frame (counted only if checked)
 int64_t step_frame(bool checked, int W, int H, int have, int same_cam, const float* cur, const float* prev, const float* color, const float* v, const float* k,
                    const float* d, const float* hist_color, const float* hist_record, float alpha, float tau, float* out_color, float* out_record, float* out_stat) {

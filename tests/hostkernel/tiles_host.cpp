@@ -1,7 +1,7 @@
 // tests/hostkernel/tiles_host.cpp -- TEST HARNESS ONLY, never part of the product.
 //
 // The tile layout of the product (volren_amd/csrc/vr_tiles.h) compiled for the host: tests/test_tiles_host.py checks both thread layouts, the
-// sample pool's slots and the variance factor against statements of its own (tests/hk_tiles.py).
+// staged window of a tile (TileWindow), the sample pool's slots and the variance factor against statements of its own (tests/hk_tiles.py).
 #include <cstddef>
 #include <cstdint>
 
@@ -33,5 +33,21 @@ void hk_tiles_pool_slots(int n, const uint32_t* chunk, int n_tiles, const uint32
 }
 
 float hk_tiles_variance_scale(int n) { return variance_scale(n); }
+
+// TileWindow<R> of `tile`, R = 2 or 3 (the halos the staged kernels use): geom = (kFoot, kTexels, x0, y0), at[t] = at(px, py) of the wave-tiled thread t's
+// pixel.  -> 0, or -1 for another R
+int hk_tiles_window(int R, int tile, int W, int32_t* geom, int32_t* at) {
+    const auto fill = [&](auto window) {
+        geom[0] = window.kFoot; geom[1] = window.kTexels; geom[2] = window.x0; geom[3] = window.y0;
+        for (uint32_t t = 0; t < 256u; ++t) {
+            const TilePixel q = wave_tiled_pixel(tile, t, W);
+            at[t] = window.at(q.px, q.py);
+        }
+        return 0;
+    };
+    if (R == 2) return fill(TileWindow<2>::of(tile, W));
+    if (R == 3) return fill(TileWindow<3>::of(tile, W));
+    return -1;
+}
 
 }

@@ -51,8 +51,9 @@ def test_fixed_then_turning_camera_matches_the_host_lane_code(name, spp, iterati
     assert (n < 4).any() and (n >= 4).any(), np.bincount(n.astype(int).reshape(-1))
 
 
-# one pixel, less than a wave, one pixel in each second tile, exactly one tile
-@pytest.mark.parametrize("w,h", ((1, 1), (2, 3), (17, 17), (16, 16)))
+# one pixel, less than a wave, one pixel in each second tile, exactly one tile; thin both ways, one pixel past a tile, one short of two tiles: the
+# staged window's halo of 3 leaves the frame on each side in turn and crosses a tile edge with a partial tile next to it
+@pytest.mark.parametrize("w,h", ((1, 1), (2, 3), (17, 17), (16, 16), (1, 37), (37, 1), (17, 16), (33, 31)))
 def test_degenerate_frames(w, h):
     r = _moments_scene("c2", w, h)
     replay = hm.Replay()

@@ -62,6 +62,19 @@ def test_the_kernels_match_the_host_build_bit_for_bit(name):
     r.close()
 
 
+# thin both ways, one pixel past a tile, one short of two tiles: the staged window's halo of 3 leaves the frame on each side in turn and crosses
+# a tile edge with a partial tile next to it
+@pytest.mark.parametrize("w,h", ((1, 37), (37, 1), (17, 16), (33, 31)))
+def test_thin_and_one_past_a_tile_frames_match_the_host_build_bit_for_bit(w, h):
+    r, o = _pair("c2", w, h)
+    _frame(r, spp=2)
+    fb, guide = r.framebuffer(), r.features()
+    want, want_b = hr.resolved(o, RAYS, fb, guide)
+    r.resolve()
+    assert _same(r.resolve_background(), want_b) and _same(r.resolved(), want)
+    r.close()
+
+
 @pytest.mark.parametrize("name", SCENES)
 def test_the_filter_starts_from_the_resolved_frame(name):
     """vr_denoise, then three frames of vr_denoise_temporal, with "denoise_resolve" 1: the host filter (hk_denoise, hk_temporal) run on the host's

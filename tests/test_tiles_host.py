@@ -87,6 +87,36 @@ def test_pool_slots_are_distinct_and_dense(w, h, spu):
     assert len(seen) == 256 * len(subset)
 
 
+# thin both ways, one past a tile on either axis, one short of two tiles, several ragged tiles: the halo leaves the frame on every side in turn
+WINDOW_FRAMES = ((1, 1), (1, 37), (37, 1), (17, 16), (33, 31), (40, 24))
+
+
+@pytest.mark.parametrize("r", (2, 3))
+@pytest.mark.parametrize("w,h", WINDOW_FRAMES)
+def test_staged_window_holds_every_neighbour_where_the_kernels_look(w, h, r):
+    """TileWindow<R>: texel f of the footprint is the frame coordinate (x0 + f % kFoot, y0 + f / kFoot) -- how stage_window fills it -- and a thread finds
+    its neighbour (dx, dy) at at(px, py) + dy * kFoot + dx -- how the *WindowDev accessors read it."""
+    tx, ty = _grid(w, h)
+    d = np.arange(-r, r + 1)
+    dx, dy = np.meshgrid(d, d, indexing="xy")
+    for tile in range(tx * ty):
+        (foot, texels, x0, y0), at = ht.window(r, tile, w)
+        assert (foot, texels) == (16 + 2 * r, (16 + 2 * r) ** 2)
+        f = np.arange(texels)
+        fx, fy = x0 + f % foot, y0 + f // foot
+        # one-to-one onto the tile's square grown by r on every side
+        tx0, ty0 = (tile % tx) * 16, (tile // tx) * 16
+        want = {(x, y) for x in range(tx0 - r, tx0 + 16 + r) for y in range(ty0 - r, ty0 + 16 + r)}
+        assert len(want) == texels and set(zip(fx.tolist(), fy.tolist())) == want
+        q = ht.pixels(tile, w)
+        inside = (q[:, 3] < w) & (q[:, 4] < h)
+        assert inside.any()
+        px, py, a = q[inside, 3], q[inside, 4], at[inside]
+        idx = a[:, None, None] + dy[None] * foot + dx[None]
+        assert idx.min() >= 0 and idx.max() < texels
+        assert np.array_equal(fx[idx], px[:, None, None] + dx[None]) and np.array_equal(fy[idx], py[:, None, None] + dy[None])
+
+
 def test_variance_scale_is_the_literal_expression():
     for n in (0, 1, 2, 3, 16777217):
         want = np.float32(n) / np.float32(n - 1) if n >= 2 else np.float32(0.0)

@@ -48,6 +48,7 @@ static int guard(const std::function<void()>& fn) {
 }
 static int fail(int code, const char* msg) { g_last_error = msg; return code; }
 #define NEED(r) do { if (!(r)) return fail(VR_ERR_ARG, "null renderer"); } while (0)
+#define NEED_DEVICE() do { if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)"); } while (0)
 
 static void use_device(vr_renderer* r) { VR_HIP(hipSetDevice(r->device)); }
 
@@ -65,7 +66,7 @@ int vr_device_count(void) {
 int vr_create(vr_renderer** out, int device, int width, int height) {
     if (!out) return fail(VR_ERR_ARG, "null out pointer");
     *out = nullptr;
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     vr_renderer* r = nullptr;
     const int rc = guard([&] {
         if (width <= 0 || height <= 0) throw std::runtime_error("vr_create: resolution must be positive");
@@ -477,94 +478,94 @@ int vr_framebuffer(vr_renderer* r, float* out) {
 // denoiser data: the device is checked before the renderer is touched
 int vr_render_features(vr_renderer* r, int spp) {
     NEED(r);
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.render_features(spp); });
 }
 int vr_render_features_expected(vr_renderer* r, int rays) {
     NEED(r);
     if (rays < 1 || rays > vr::kExpectedMaxRays) return fail(VR_ERR_ARG, "vr_render_features_expected: rays must be 1..4");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.render_features_expected(rays); });
 }
 int vr_expected_stats(vr_renderer* r, uint64_t out[4]) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.expected_stats_read(out); });
 }
 int vr_expected_clear_table(vr_renderer* r, uint8_t* out, int cells[3]) {
     NEED(r);
     if (!cells) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.expected_clear_table(out, cells); });
 }
 int vr_features(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_features(out); });
 }
 int vr_variance(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_variance(out); });
 }
 int vr_denoise(vr_renderer* r) {
     NEED(r);
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.denoise(); });
 }
 int vr_denoise_temporal(vr_renderer* r) {
     NEED(r);
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.denoise_temporal(); });
 }
 int vr_denoise_history_reset(vr_renderer* r) {
     NEED(r);
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.flush_pending(); r->impl.drop_history(); });
 }
 int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* length_out) {
     NEED(r);
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_history(rgba_out, var_out, length_out); });
 }
 int vr_denoise_reject_stat(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_reject_stat(out); });
 }
 int vr_denoise_history_moments(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_history_moments(out); });
 }
 // (the refusals read host state only: they come before the device is asked for)
 int vr_resolve(vr_renderer* r) {
     NEED(r);
     if (const int rc = guard([&] { r->impl.check_resolve("resolve: ", false); })) return rc;
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.resolve(); });
 }
 int vr_resolved(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_resolved(out); });
 }
 int vr_resolve_background(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_resolve_background(out); });
 }
 int vr_denoised(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_denoised(out); });
 }
 // adaptive sampling: the arguments, then the device, are checked before the renderer is touched
@@ -572,7 +573,7 @@ int vr_render_adaptive(vr_renderer* r, int min_spp, int max_spp, float threshold
     NEED(r);
     if (min_spp < 2 || min_spp > max_spp || !(threshold >= 0.0f) || !std::isfinite(threshold))
         return fail(VR_ERR_ARG, "vr_render_adaptive: needs 2 <= min_spp <= max_spp and a finite threshold >= 0");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.render_adaptive(min_spp, max_spp, threshold); });
 }
 static int tile_count_arg(vr_renderer* r, int n_tiles) {
@@ -582,7 +583,7 @@ static int tile_count_arg(vr_renderer* r, int n_tiles) {
 int vr_tile_samples(vr_renderer* r, int32_t* out, int n_tiles) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     if (tile_count_arg(r, n_tiles) != VR_OK) return VR_ERR_ARG;
     return guard([&] {
         use_device(r);
@@ -594,7 +595,7 @@ int vr_tile_samples(vr_renderer* r, int32_t* out, int n_tiles) {
 int vr_tile_error(vr_renderer* r, float* out, int n_tiles) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     if (tile_count_arg(r, n_tiles) != VR_OK) return VR_ERR_ARG;
     return guard([&] {
         use_device(r);
@@ -678,7 +679,7 @@ int vr_sharded_create(vr_sharded** out, const int* devices, int n_parts, int wid
     if (!out) return fail(VR_ERR_ARG, "null out pointer");
     *out = nullptr;
     if (!devices || n_parts <= 0 || n_parts > 64) return fail(VR_ERR_ARG, "vr_sharded_create: 1..64 parts, one device ordinal each");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     vr_sharded* s = new vr_sharded();
     const int rc = guard([&] {
         std::vector<vr::RendererHIP*> impls;
@@ -838,7 +839,7 @@ int vr_math_sweep(int fn, uint32_t first, long long count, float b, float* out) 
 int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, long long n) {
     NEED(r);
     if (!in || !out || n < 0) return fail(VR_ERR_ARG, "bad arguments");
-    if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)");
+    NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.probe(what, form, static_cast<const uint32_t*>(in), out, (size_t)n); });
 }
 

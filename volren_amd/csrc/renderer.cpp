@@ -59,13 +59,8 @@ void RendererHIP::resize(uint32_t w, uint32_t h) {
     resolution = { (int)w, (int)h };
     color = make_device_buffer((size_t)w * h * 4 * sizeof(float));
     display.reset();
-    features_.reset(); features_pass_ = 0; features_rays_ = 0;
-    rs_bg_.reset(); rs_part_.reset(); resolved_.reset();
-    moments_.reset(); moments_n_ = -1;
-    dn_guide_.reset(); dn_var_[0].reset(); dn_var_[1].reset(); dn_color_[0].reset(); dn_color_[1].reset(); denoised_.reset();
-    drop_history();
-    dn_reject_.reset(); reject_stat_ = false;
-    drop_tile_samples(); tile_n_dev_.reset(); adaptive_lists_.reset(); adaptive_err_.reset();
+    sized_ = Sized{};                                            // features, moments, the filters' buffers and the history, with what says they are valid
+    drop_tile_samples();
     drop_seed_table();                                           // keyed by the frame size
     VR_HIP(hipMemset(color->get(), 0, color->size_bytes()));
     if (!tiles_host_.empty()) set_tiles(tiles_host_);
@@ -674,14 +669,14 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     float* moments = nullptr;
     if (in.variance) {
         const size_t bytes = color->size_bytes();
-        if (ensure_buffer(moments_, bytes)) {
-            VR_HIP(hipMemsetAsync(moments_->get(), 0, bytes, stream));
-            if (first > 0) moments_n_ = -1;
+        if (ensure_buffer(sized_.moments, bytes)) {
+            VR_HIP(hipMemsetAsync(sized_.moments->get(), 0, bytes, stream));
+            if (first > 0) sized_.moments_n = -1;
         }
-        moments = moments_->as<float>();
-        moments_n_ = first == 0 ? n : (moments_n_ == first ? first + n : -1);
+        moments = sized_.moments->as<float>();
+        sized_.moments_n = first == 0 ? n : (sized_.moments_n == first ? first + n : -1);
     } else {
-        moments_n_ = -1;
+        sized_.moments_n = -1;
     }
     if (!keep_timing_) {
         VR_HIP(hipEventRecord(ev0_, stream));
@@ -918,8 +913,8 @@ int RendererHIP::begin_feature_pass(SceneParams& P) {
     }
     const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y);
     const size_t bytes = (size_t)resolution.x * resolution.y * 8 * sizeof(float);
-    if (ensure_buffer(features_, bytes)) {
-        VR_HIP(hipMemsetAsync(features_->get(), 0, bytes, stream));
+    if (ensure_buffer(sized_.features, bytes)) {
+        VR_HIP(hipMemsetAsync(sized_.features->get(), 0, bytes, stream));
     }
     return n_tiles;
 }
@@ -928,8 +923,8 @@ void RendererHIP::render_features(int spp) {
     if (spp <= 0) throw std::runtime_error("render_features: spp must be positive");
     SceneParams P;
     const int n_tiles = begin_feature_pass(P);
-    features_pass_ = 1; features_rays_ = 0;
-    launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, features_->as<float>(), status_->as<uint32_t>(), stream);
+    sized_.pass = 1; sized_.rays = 0;
+    launch_features(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, spp, sized_.features->as<float>(), status_->as<uint32_t>(), stream);
     VR_HIP(hipGetLastError());
 }
 
@@ -947,8 +942,8 @@ void RendererHIP::render_features_expected(int rays) {
         VR_HIP(hipMemsetAsync(expected_stats_->get(), 0, expected_stats_->size_bytes(), stream));
         counters = expected_stats_->as<unsigned long long>();
     }
-    features_pass_ = 2; features_rays_ = rays;
-    launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, features_->as<float>(), stream, &clear, counters);
+    sized_.pass = 2; sized_.rays = rays;
+    launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, sized_.features->as<float>(), stream, &clear, counters);
     VR_HIP(hipGetLastError());
     expected_stats_valid_ = counters != nullptr;
 }
@@ -1015,15 +1010,18 @@ void RendererHIP::probe(int what, int form, const uint32_t* in, float* out, size
     VR_HIP(hipStreamSynchronize(stream));
 }
 
-void RendererHIP::download_features(float* out) {
-    if (!features_) throw std::runtime_error("features: no feature pass since the last resize (call render_features first)");
+// the common body of the download_* of whole buffers: the refusal comes before the flush
+void RendererHIP::download_whole(const DeviceBufferPtr& b, float* out, const char* absent) {
+    if (!b) throw std::runtime_error(absent);
     flush_pending();
-    features_->download(out, features_->size_bytes(), stream);
+    b->download(out, b->size_bytes(), stream);
 }
 
+void RendererHIP::download_features(float* out) { download_whole(sized_.features, out, "features: no feature pass since the last resize (call render_features first)"); }
+
 void RendererHIP::check_moments(const char* who) {
-    if (ragged() && moments_) return;                 // render_adaptive keeps the moments of every launch: they cover each tile's own count
-    if (sample < 1 || !moments_ || moments_n_ != sample)
+    if (ragged() && sized_.moments) return;                 // render_adaptive keeps the moments of every launch: they cover each tile's own count
+    if (sample < 1 || !sized_.moments || sized_.moments_n != sample)
         throw std::runtime_error(std::string(who) + ": the moments do not cover samples 1.." + std::to_string(sample) +
                                  " (variance was off for some of them, e.g. switched on mid-frame): reset() and render with variance = 1");
 }
@@ -1031,7 +1029,7 @@ void RendererHIP::check_moments(const char* who) {
 void RendererHIP::download_variance(float* rgba) {
     flush_pending();
     check_moments("variance");
-    moments_->download(rgba, moments_->size_bytes(), stream);
+    sized_.moments->download(rgba, sized_.moments->size_bytes(), stream);
     const bool per_tile = ragged();                   // each tile's own count and factor
     const int W = resolution.x, H = resolution.y;
     for (int y = 0; y < H; ++y)
@@ -1045,7 +1043,7 @@ void RendererHIP::download_variance(float* rgba) {
 
 // The a-trous denoiser (vr_denoise.h) on whole frames: prepare (variance of the mean, guide) once, then `denoise_iterations` passes at steps
 // 1, 2, 4, ...  Iteration 0 reads the framebuffer itself; colour and variance ping-pong between buffers of their own, and the last iteration
-// writes `denoised_` (N = 0: a copy of the framebuffer).
+// writes `denoised` (N = 0: a copy of the framebuffer).
 // temporal (denoise_temporal, vr_temporal.h): between prepare and the iterations the frame is blended with the history, and the iterations start
 // from the new history's colour and variance instead.  Every buffer the call needs is allocated before its first launch, so a failed allocation
 // leaves the last result and the history as they were.
@@ -1056,7 +1054,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     flush_pending();
     const std::string me = std::string(who) + ": ";
     if (!tiles_host_.empty() && !whole_frame_gathered) throw std::runtime_error(me + "a tile subset is set (set_tiles); the filter needs every pixel's neighbours and runs on whole frames only");
-    if (!features_) throw std::runtime_error(me + "no feature pass since the last resize (call render_features first)");
+    if (!sized_.features) throw std::runtime_error(me + "no feature pass since the last resize (call render_features first)");
     if (sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
     check_moments(who);
     if (temporal && denoise_moments != 0 && denoise_reject > 0.0f)
@@ -1067,32 +1065,34 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         for (int32_t c : tile_n_)
             if (c < 1) throw std::runtime_error(me + "a tile of the frame holds no samples (sample < 1 there: render_adaptive over a tile subset from sample 0)");
         const size_t bytes = tile_n_.size() * sizeof(int32_t);
-        ensure_buffer(tile_n_dev_, bytes);
-        tile_n_dev_->upload(tile_n_.data(), bytes, stream);
-        counts = tile_n_dev_->as<int32_t>();
+        ensure_buffer(sized_.tile_n_dev, bytes);
+        sized_.tile_n_dev->upload(tile_n_.data(), bytes, stream);
+        counts = sized_.tile_n_dev->as<int32_t>();
     }
     const int32_t W = resolution.x, H = resolution.y, N = denoise_iterations;
     if ((size_t)W * (size_t)H * 2u > (size_t)INT32_MAX) throw std::runtime_error(me + "frame too large (32-bit pixel indices)");
     if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error(me + "denoise_iterations out of range");
     const size_t px = (size_t)W * H;
+    Sized::History& hist = sized_.hist;
     // a history without moment records cannot continue one with them, nor the other way round (denoise_moments set as a field, past set_denoise_moments)
-    if (temporal && hist_cur_ >= 0 && (hist_moments_[hist_cur_] != nullptr) != (denoise_moments != 0)) drop_history();
-    const int to = hist_cur_ < 0 ? 0 : 1 - hist_cur_;      // the half of the history pair this call writes
+    if (temporal && hist.cur >= 0 && (hist.moments[hist.cur] != nullptr) != (denoise_moments != 0)) drop_history();
+    const int to = hist.cur < 0 ? 0 : 1 - hist.cur;      // the half of the history pair this call writes
     const bool reject = temporal && denoise_reject > 0.0f;      // vr_temporal.h steps 2a, 3a: the fetch / resolve pair instead of the one kernel
     const bool moments = temporal && denoise_moments != 0;      // vr_moments.h: the temporal kernel with the moment records, then the variance kernel
-    if (moments) ensure_buffer(hist_moments_[to], px * 4 * sizeof(float));
-    if (temporal) { ensure_buffer(hist_color_[to], px * 4 * sizeof(float)); ensure_buffer(hist_record_[to], px * 4 * sizeof(float)); }
-    if (reject) ensure_buffer(dn_reject_, px * 8 * sizeof(float));
-    ensure_buffer(dn_guide_, px * 8 * sizeof(float));
-    ensure_buffer(dn_var_[0], px * sizeof(float));
-    ensure_buffer(denoised_, px * 4 * sizeof(float));
-    if (N >= 2) { ensure_buffer(dn_var_[1], px * sizeof(float)); ensure_buffer(dn_color_[0], px * 4 * sizeof(float)); }
-    if (N >= 3) ensure_buffer(dn_color_[1], px * 4 * sizeof(float));
+    if (moments) ensure_buffer(hist.moments[to], px * 4 * sizeof(float));
+    if (temporal) { ensure_buffer(hist.color[to], px * 4 * sizeof(float)); ensure_buffer(hist.record[to], px * 4 * sizeof(float)); }
+    if (reject) ensure_buffer(sized_.dn_reject, px * 8 * sizeof(float));
+    ensure_buffer(sized_.dn_guide, px * 8 * sizeof(float));
+    ensure_buffer(sized_.dn_var[0], px * sizeof(float));
+    ensure_buffer(sized_.denoised, px * 4 * sizeof(float));
+    if (N >= 2) { ensure_buffer(sized_.dn_var[1], px * sizeof(float)); ensure_buffer(sized_.dn_color[0], px * 4 * sizeof(float)); }
+    if (N >= 3) ensure_buffer(sized_.dn_color[1], px * 4 * sizeof(float));
     const float vscale = variance_scale(sample);      // download_variance's factor
     if (denoise_resolve != 0) run_resolve();      // vr_resolve.h: the filter starts from y, with the frame's own variance
-    const DeviceBuffer* frame = denoise_resolve != 0 ? resolved_.get() : color.get();
-    launch_denoise_prepare(moments_->as<float>(), features_->as<float>(), W, H, sample, vscale, counts, dn_var_[0]->as<float>(), dn_guide_->as<float>(), stream);
+    const DeviceBuffer* frame = denoise_resolve != 0 ? sized_.resolved.get() : color.get();
+    launch_denoise_prepare(sized_.moments->as<float>(), sized_.features->as<float>(), W, H, sample, vscale, counts, sized_.dn_var[0]->as<float>(), sized_.dn_guide->as<float>(), stream);
     VR_HIP(hipGetLastError());
+    const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
     const DeviceBuffer* first = frame;                // what iteration 0 reads
     if (temporal) {
         TemporalCamera cur;
@@ -1101,46 +1101,38 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         const mat3 ct = camera.view_inverse();
         memcpy(cur.m, ct.m, sizeof ct.m);
         cur.cam_z = camera_z(camera.fov_degree);
-        const bool have = hist_cur_ >= 0;
-        const bool same = have && memcmp(&cur, &hist_cam_, sizeof cur) == 0;
-        const float* hc = have ? hist_color_[hist_cur_]->as<float>() : nullptr;
-        const float* hr = have ? hist_record_[hist_cur_]->as<float>() : nullptr;
-        const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
-        if (moments)
-            launch_denoise_temporal_moments(frame->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, have ? hist_moments_[hist_cur_]->as<float>() : nullptr,
-                                            same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha, sg, hist_color_[to]->as<float>(), hist_record_[to]->as<float>(),
-                                            hist_moments_[to]->as<float>(), stream);
-        else if (reject)
-            launch_denoise_temporal_reject(frame->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H,
-                                           denoise_alpha, denoise_reject, dn_reject_->as<float>(), hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
-        else
-            launch_denoise_temporal(frame->as<float>(), dn_var_[0]->as<float>(), dn_guide_->as<float>(), hc, hr, same, cur, have ? hist_cam_ : cur, W, H, denoise_alpha,
-                                    hist_color_[to]->as<float>(), hist_record_[to]->as<float>(), stream);
+        const bool have = hist.cur >= 0;
+        TemporalPass t;
+        t.color = frame->as<float>(); t.v = sized_.dn_var[0]->as<float>(); t.guide = sized_.dn_guide->as<float>();
+        if (have) { t.hist_color = hist.color[hist.cur]->as<float>(); t.hist_record = hist.record[hist.cur]->as<float>(); }
+        if (have && moments) t.hist_moments = hist.moments[hist.cur]->as<float>();
+        t.same_cam = have && memcmp(&cur, &hist.cam, sizeof cur) == 0;
+        t.cur = cur; t.prev = have ? hist.cam : cur;
+        t.W = W; t.H = H; t.alpha = denoise_alpha;
+        if (reject) { t.tau = denoise_reject; t.scratch = sized_.dn_reject->as<float>(); }
+        t.sigma = sg;
+        t.out_color = hist.color[to]->as<float>(); t.out_record = hist.record[to]->as<float>();
+        if (moments) t.out_moments = hist.moments[to]->as<float>();
+        launch_denoise_temporal(t, stream);
         VR_HIP(hipGetLastError());
-        reject_stat_ = reject;
-        hist_cur_ = to;
-        hist_cam_ = cur;
-        first = hist_color_[to].get();
+        sized_.reject_stat = reject;
+        hist.cur = to; hist.cam = cur;
+        first = hist.color[to].get();
     }
     if (N == 0) {
-        VR_HIP(hipMemcpyAsync(denoised_->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
+        VR_HIP(hipMemcpyAsync(sized_.denoised->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
         return;
     }
-    const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
     for (int32_t k = 0; k < N; ++k) {
-        const float* cin = k == 0 ? first->as<float>() : dn_color_[(k - 1) & 1]->as<float>();
-        float* cout = k == N - 1 ? denoised_->as<float>() : dn_color_[k & 1]->as<float>();
-        float* vout = k == N - 1 ? nullptr : dn_var_[(k + 1) & 1]->as<float>();
-        launch_denoise_atrous(cin, dn_var_[k & 1]->as<float>(), dn_guide_->as<float>(), W, H, 1 << k, sg, cout, vout, stream);
+        const float* cin = k == 0 ? first->as<float>() : sized_.dn_color[(k - 1) & 1]->as<float>();
+        float* cout = k == N - 1 ? sized_.denoised->as<float>() : sized_.dn_color[k & 1]->as<float>();
+        float* vout = k == N - 1 ? nullptr : sized_.dn_var[(k + 1) & 1]->as<float>();
+        launch_denoise_atrous(cin, sized_.dn_var[k & 1]->as<float>(), sized_.dn_guide->as<float>(), W, H, 1 << k, sg, cout, vout, stream);
         VR_HIP(hipGetLastError());
     }
 }
 
-void RendererHIP::drop_history() {
-    hist_color_[0].reset(); hist_color_[1].reset(); hist_record_[0].reset(); hist_record_[1].reset();
-    hist_moments_[0].reset(); hist_moments_[1].reset();
-    hist_cur_ = -1;
-}
+void RendererHIP::drop_history() { sized_.hist = Sized::History{}; }
 
 void RendererHIP::set_denoise_moments(int v) {
     if (v != 0 && v != 1) throw std::runtime_error("denoise_moments: 0 (the frames' sample variance) or 1 (luminance moments kept in the history)");
@@ -1155,10 +1147,10 @@ void RendererHIP::check_resolve(const std::string& me, bool whole_frame_gathered
     if (sample < 1) throw std::runtime_error(me + "the framebuffer holds no samples (sample < 1)");
     if (!tiles_host_.empty() && !whole_frame_gathered) throw std::runtime_error(me + "a tile subset is set (set_tiles); the coefficient pools every pixel's neighbours and is formed on whole frames only");
     if (integrator == 2) throw std::runtime_error(me + "integrator = 2 (direct volume rendering) writes an opacity into alpha, not the share of samples that hit");
-    if (!features_ || features_pass_ != 2)
+    if (!sized_.features || sized_.pass != 2)
         throw std::runtime_error(me + "the feature buffer was not last filled by render_features_expected since the last resize (the expected coverage is what replaces the frame's)");
-    if (features_rays_ < 2)
-        throw std::runtime_error(me + "the expected-value pass ran with rays = " + std::to_string(features_rays_) + "; rays >= 2 is needed (one ray gives the coverage of the pixel's centre, not of its area)");
+    if (sized_.rays < 2)
+        throw std::runtime_error(me + "the expected-value pass ran with rays = " + std::to_string(sized_.rays) + "; rays >= 2 is needed (one ray gives the coverage of the pixel's centre, not of its area)");
     if ((size_t)resolution.x * (size_t)resolution.y * 2u > (size_t)INT32_MAX) throw std::runtime_error(me + "frame too large (32-bit pixel indices)");
 }
 
@@ -1166,8 +1158,8 @@ void RendererHIP::run_resolve() {
     LaunchInputs in;
     capture(in);                                                 // the scene as a launch reads it: the environment's arrays, strength and transform, the camera
     const size_t bytes = (size_t)resolution.x * resolution.y * 4 * sizeof(float);
-    ensure_buffer(rs_bg_, bytes); ensure_buffer(rs_part_, bytes); ensure_buffer(resolved_, bytes);
-    launch_resolve(in.P, color->as<float>(), features_->as<float>(), features_rays_, rs_bg_->as<float>(), rs_part_->as<float>(), resolved_->as<float>(), stream);
+    ensure_buffer(sized_.rs_bg, bytes); ensure_buffer(sized_.rs_part, bytes); ensure_buffer(sized_.resolved, bytes);
+    launch_resolve(in.P, color->as<float>(), sized_.features->as<float>(), sized_.rays, sized_.rs_bg->as<float>(), sized_.rs_part->as<float>(), sized_.resolved->as<float>(), stream);
     VR_HIP(hipGetLastError());
 }
 
@@ -1177,16 +1169,10 @@ void RendererHIP::resolve() {
     run_resolve();
 }
 
-void RendererHIP::download_resolved(float* rgba) {
-    if (!resolved_) throw std::runtime_error("resolved: no resolve since the last resize (call resolve first)");
-    flush_pending();
-    resolved_->download(rgba, resolved_->size_bytes(), stream);
-}
+void RendererHIP::download_resolved(float* rgba) { download_whole(sized_.resolved, rgba, "resolved: no resolve since the last resize (call resolve first)"); }
 
 void RendererHIP::download_resolve_background(float* rgba) {
-    if (!rs_bg_ || !resolved_) throw std::runtime_error("resolve_background: no resolve since the last resize (call resolve first)");
-    flush_pending();
-    rs_bg_->download(rgba, rs_bg_->size_bytes(), stream);
+    download_whole(sized_.resolved ? sized_.rs_bg : nullptr, rgba, "resolve_background: no resolve since the last resize (call resolve first)");
 }
 
 void RendererHIP::set_denoise_resolve(int v) {
@@ -1198,20 +1184,20 @@ void RendererHIP::set_denoise_resolve(int v) {
 }
 
 void RendererHIP::download_history_moments(float* out) {
-    if (hist_cur_ < 0 || !hist_moments_[hist_cur_])
-        throw std::runtime_error("denoise_history_moments: no history with moment records (no denoise_temporal with denoise_moments = 1 since the last resize, history reset or change of the setting)");
-    flush_pending();
-    hist_moments_[hist_cur_]->download(out, hist_moments_[hist_cur_]->size_bytes(), stream);
+    const Sized::History& hist = sized_.hist;
+    download_whole(hist.cur < 0 ? nullptr : hist.moments[hist.cur], out,
+                   "denoise_history_moments: no history with moment records (no denoise_temporal with denoise_moments = 1 since the last resize, history reset or change of the setting)");
 }
 
 void RendererHIP::download_history(float* rgba, float* var, float* length) {
-    if (hist_cur_ < 0) throw std::runtime_error("denoise_history: no history (no denoise_temporal since the last resize or history reset)");
+    const Sized::History& hist = sized_.hist;
+    if (hist.cur < 0) throw std::runtime_error("denoise_history: no history (no denoise_temporal since the last resize or history reset)");
     flush_pending();
-    if (rgba) hist_color_[hist_cur_]->download(rgba, hist_color_[hist_cur_]->size_bytes(), stream);
+    if (rgba) hist.color[hist.cur]->download(rgba, hist.color[hist.cur]->size_bytes(), stream);
     if (!var && !length) return;
     const size_t px = (size_t)resolution.x * resolution.y;
     std::vector<float> rec(px * 4);
-    hist_record_[hist_cur_]->download(rec.data(), rec.size() * sizeof(float), stream);
+    hist.record[hist.cur]->download(rec.data(), rec.size() * sizeof(float), stream);
     for (size_t i = 0; i < px; ++i) {
         if (var) var[i] = rec[4 * i];
         if (length) length[i] = rec[4 * i + 1];
@@ -1219,20 +1205,16 @@ void RendererHIP::download_history(float* rgba, float* var, float* length) {
 }
 
 void RendererHIP::download_reject_stat(float* out) {
-    if (!reject_stat_) throw std::runtime_error("denoise_reject_stat: the last denoise_temporal since the resize did not run with denoise_reject > 0");
+    if (!sized_.reject_stat) throw std::runtime_error("denoise_reject_stat: the last denoise_temporal since the resize did not run with denoise_reject > 0");
     flush_pending();
     const size_t px = (size_t)resolution.x * resolution.y;
     std::vector<float> rec(px * 4);      // the scratch's second half, (T, N_h, z2, has) per pixel
-    VR_HIP(hipMemcpyAsync(rec.data(), dn_reject_->as<float>() + px * 4, rec.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipMemcpyAsync(rec.data(), sized_.dn_reject->as<float>() + px * 4, rec.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
     for (size_t i = 0; i < px; ++i) out[i] = rec[4 * i];
 }
 
-void RendererHIP::download_denoised(float* rgba) {
-    if (!denoised_) throw std::runtime_error("denoised: no denoise since the last resize (call denoise first)");
-    flush_pending();
-    denoised_->download(rgba, denoised_->size_bytes(), stream);
-}
+void RendererHIP::download_denoised(float* rgba) { download_whole(sized_.denoised, rgba, "denoised: no denoise since the last resize (call denoise first)"); }
 
 // ---- adaptive sampling (vr_adaptive.h) -----------------------------------------------------------------------------------------------------------
 bool RendererHIP::ragged() {
@@ -1256,14 +1238,14 @@ std::vector<float> RendererHIP::tile_error() {
     const int n_all = (int)counts.size();
     std::vector<int32_t> lists((size_t)n_all * 2);
     for (int t = 0; t < n_all; ++t) { lists[(size_t)t] = t; lists[(size_t)(n_all + t)] = counts[(size_t)t]; }
-    ensure_buffer_at_least(adaptive_lists_, lists.size() * sizeof(int32_t));
-    ensure_buffer_at_least(adaptive_err_, (size_t)n_all * sizeof(float));
-    adaptive_lists_->upload(lists.data(), lists.size() * sizeof(int32_t), stream);
-    launch_adaptive_error(color->as<float>(), moments_->as<float>(), adaptive_lists_->as<int32_t>(), adaptive_lists_->as<int32_t>() + n_all, n_all, resolution.x,
-                          resolution.y, adaptive_err_->as<float>(), stream);
+    ensure_buffer_at_least(sized_.adaptive_lists, lists.size() * sizeof(int32_t));
+    ensure_buffer_at_least(sized_.adaptive_err, (size_t)n_all * sizeof(float));
+    sized_.adaptive_lists->upload(lists.data(), lists.size() * sizeof(int32_t), stream);
+    launch_adaptive_error(color->as<float>(), sized_.moments->as<float>(), sized_.adaptive_lists->as<int32_t>(), sized_.adaptive_lists->as<int32_t>() + n_all, n_all, resolution.x,
+                          resolution.y, sized_.adaptive_err->as<float>(), stream);
     VR_HIP(hipGetLastError());
     std::vector<float> e((size_t)n_all);
-    adaptive_err_->download(e.data(), e.size() * sizeof(float), stream);
+    sized_.adaptive_err->download(e.data(), e.size() * sizeof(float), stream);
     return e;
 }
 
@@ -1276,7 +1258,7 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
     flush_pending();
     if (!color) throw std::runtime_error("render_adaptive: no framebuffer (call resize first)");
     const bool was_ragged = ragged();
-    if (sample > 0 && !was_ragged && !(moments_ && moments_n_ == sample))
+    if (sample > 0 && !was_ragged && !(sized_.moments && sized_.moments_n == sample))
         throw std::runtime_error("render_adaptive: the moments do not cover samples 1.." + std::to_string(sample) +
                                  " (variance was off for some of them): reset() and render with variance = 1");
     LaunchInputs in;
@@ -1286,8 +1268,8 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
     if (!was_ragged) tile_n_.assign((size_t)n_all, std::max(sample, 0));
     std::vector<int32_t> set(tiles_host_);
     if (set.empty()) { set.resize((size_t)n_all); for (int t = 0; t < n_all; ++t) set[(size_t)t] = t; }
-    ensure_buffer_at_least(adaptive_lists_, (size_t)n_all * 2 * sizeof(int32_t));
-    ensure_buffer_at_least(adaptive_err_, (size_t)n_all * sizeof(float));
+    ensure_buffer_at_least(sized_.adaptive_lists, (size_t)n_all * 2 * sizeof(int32_t));
+    ensure_buffer_at_least(sized_.adaptive_err, (size_t)n_all * sizeof(float));
     const bool ordered = in.order_tiles >= 1;
     VR_HIP(hipEventRecord(ev0_, in.stream));
     last_launches = 0;
@@ -1303,11 +1285,11 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
             packed.insert(packed.end(), o.begin(), o.end());
         }
         if (packed.empty()) return;
-        adaptive_lists_->upload(packed.data(), packed.size() * sizeof(int32_t), in.stream);
+        sized_.adaptive_lists->upload(packed.data(), packed.size() * sizeof(int32_t), in.stream);
         size_t off = 0;
         for (const auto& g : groups) {
             const int32_t n = g.first, next = to(n);
-            submit(in, n, next - n, adaptive_lists_->as<int32_t>() + off, (int)g.second.size());
+            submit(in, n, next - n, sized_.adaptive_lists->as<int32_t>() + off, (int)g.second.size());
             for (int32_t t : g.second) tile_n_[(size_t)t] = next;
             off += g.second.size();
         }
@@ -1318,8 +1300,8 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
         timing_pending_ = true;
         const auto mm = std::minmax_element(tile_n_.begin(), tile_n_.end());
         sample = *mm.second;
-        if (*mm.first == *mm.second) { drop_tile_samples(); moments_n_ = sample; }      // every tile at one count: an ordinary uniform frame
-        else { tile_n_sample_ = sample; moments_n_ = -1; }
+        if (*mm.first == *mm.second) { drop_tile_samples(); sized_.moments_n = sample; }      // every tile at one count: an ordinary uniform frame
+        else { tile_n_sample_ = sample; sized_.moments_n = -1; }
     };
     try {
         std::vector<int32_t> low;                     // step 1: the set to min_spp
@@ -1332,12 +1314,12 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
             const size_t m = live.size();
             std::vector<int32_t> lists(live);
             for (int32_t t : live) lists.push_back(tile_n_[(size_t)t]);
-            adaptive_lists_->upload(lists.data(), lists.size() * sizeof(int32_t), in.stream);
-            launch_adaptive_error(color->as<float>(), moments_->as<float>(), adaptive_lists_->as<int32_t>(), adaptive_lists_->as<int32_t>() + m, (int32_t)m, W, H,
-                                  adaptive_err_->as<float>(), in.stream);
+            sized_.adaptive_lists->upload(lists.data(), lists.size() * sizeof(int32_t), in.stream);
+            launch_adaptive_error(color->as<float>(), sized_.moments->as<float>(), sized_.adaptive_lists->as<int32_t>(), sized_.adaptive_lists->as<int32_t>() + m, (int32_t)m, W, H,
+                                  sized_.adaptive_err->as<float>(), in.stream);
             VR_HIP(hipGetLastError());
             std::vector<float> e(m);
-            adaptive_err_->download(e.data(), m * sizeof(float), in.stream);
+            sized_.adaptive_err->download(e.data(), m * sizeof(float), in.stream);
             check_watchdog();
             go.clear();
             for (size_t k = 0; k < m; ++k) if (!adaptive_converged(e[k], threshold)) go.push_back(live[k]);

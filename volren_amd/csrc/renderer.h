@@ -255,8 +255,8 @@ struct RendererHIP {
     void set_denoise_moments(int v);
     void download_history_moments(float* out);
     void download_denoised(float* rgba);
-    const DeviceBuffer* denoised() const { return denoised_.get(); }
-    const DeviceBuffer* resolved() const { return resolved_.get(); }
+    const DeviceBuffer* denoised() const { return sized_.denoised.get(); }
+    const DeviceBuffer* resolved() const { return sized_.resolved.get(); }
     // copy + tonemap of a W*H*4 buffer into `display` (draw() = draw_from(*color) after the flush)
     void draw_from(const DeviceBuffer& src);
     void download_display(float* rgba) const;
@@ -313,10 +313,9 @@ private:
     uint64_t order_key_ = 0;
     std::vector<int32_t> costliest_first(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const;
     const int32_t* tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles);
-    // adaptive sampling: samples behind each raster tile, meaningful while `sample` == tile_n_sample_ (ragged()); device copy for the denoiser
+    // adaptive sampling: samples behind each raster tile, meaningful while `sample` == tile_n_sample_ (ragged()); the denoiser's device copy: sized_.tile_n_dev
     std::vector<int32_t> tile_n_;
     int tile_n_sample_ = -1;
-    DeviceBufferPtr tile_n_dev_, adaptive_lists_, adaptive_err_;
     bool keep_timing_ = false;                         // submit() adds to the timing window of the call in progress instead of opening its own
     DeviceBufferPtr status_;
     DeviceBufferPtr pool_;
@@ -332,27 +331,35 @@ private:
     // the table for a launch of the 0-based sample numbers [s0, s0 + n) on `stream`, filled as far as it reaches: *samples = the numbers it covers (0: no table)
     const uint32_t* seed_table_for(const SceneParams& P, int s0, int n, hipStream_t stream, int* samples);
     DeviceBufferPtr stats_;                            // 32 counters of the instrumented kernels (sched_stats)
-    DeviceBufferPtr features_;                         // W*H*8 floats of the last render_features (dropped by resize)
-    int features_pass_ = 0, features_rays_ = 0;        // which pass filled it last since the resize: 0 none, 1 render_features, 2 render_features_expected with that many rays
-    DeviceBufferPtr rs_bg_, rs_part_, resolved_;       // resolve(): B, P and the resolved frame, W*H*4 each (allocated on first use, dropped by resize)
-    void run_resolve();                                       // its launches, after check_resolve
+    // Everything whose contents or validity belong to one frame size W x H: the buffers (each allocated on first use) with the flags that say what they hold.
+    // resize() assigns a fresh one, drop_history() a fresh History: a new member needs no line in either.
+    struct Sized {
+        DeviceBufferPtr features;                      // W*H*8 floats of the last render_features
+        int pass = 0, rays = 0;                        // which pass filled it last: 0 none, 1 render_features, 2 render_features_expected with that many rays
+        DeviceBufferPtr moments;                       // W*H*4 second moments, allocated by the first launch with `variance` on
+        int moments_n = -1;                            // the moments cover samples 1..moments_n (-1: they do not start at sample 1)
+        DeviceBufferPtr rs_bg, rs_part, resolved;      // resolve(): B, P and the resolved frame, W*H*4 each
+        DeviceBufferPtr dn_guide, dn_var[2], dn_color[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4
+        DeviceBufferPtr denoised;                      // W*H*4: the last denoise()'s or denoise_temporal()'s result
+        DeviceBufferPtr dn_reject;                     // denoise_temporal() with denoise_reject > 0: the scratch between its two kernels, W*H*8
+        bool reject_stat = false;                      // dn_reject holds the statistic of the last denoise_temporal()
+        DeviceBufferPtr tile_n_dev, adaptive_lists, adaptive_err;      // adaptive sampling: tile_n_ on the device, the rounds' tile lists and error values
+        struct History {                               // denoise_temporal(): a ping-pong pair of
+            DeviceBufferPtr color[2], record[2];       // W*H*4 colours and W*H*4 (V, N, K, D) records, and
+            DeviceBufferPtr moments[2];                // with denoise_moments = 1 the W*H*4 moment records (m1, m2, E, S); the current half exists iff the history has them
+            int cur = -1;                              // the half that holds the history (-1: none)
+            TemporalCamera cam{};                      // the camera of the frame that wrote it
+        } hist;
+    } sized_;
+    void download_whole(const DeviceBufferPtr& b, float* out, const char* absent);      // throws `absent` when b is null; else flushes and copies all of b
+    void run_resolve();                                       // resolve()'s launches, after check_resolve
     DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
     bool expected_stats_valid_ = false;                // ... which that pass filled
     ClearTable clear_table_of(BrickGridHIP& g, const GridView& view);      // the grid's table, built on `stream` if it has none
-    DeviceBufferPtr moments_;                          // W*H*4 second moments, allocated by the first launch with `variance` on
-    int moments_n_ = -1;                               // the moments cover samples 1..moments_n_ (-1: they do not start at sample 1)
     void check_moments(const char* who);               // throws unless the moments cover samples 1..sample (of every tile, on a ragged frame)
-    DeviceBufferPtr dn_guide_, dn_var_[2], dn_color_[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4 (dropped by resize)
-    DeviceBufferPtr denoised_;                         // W*H*4: the last denoise()'s or denoise_temporal()'s result (dropped by resize)
     void run_denoise(const char* who, bool temporal, bool whole_frame_gathered = false);  // the body of both; whole_frame_gathered: part 0 of a ShardedRenderer,
                                                        // whose moments and features hold every part's tiles (gather_guides) -- the tile subset is no obstacle then
-    friend struct ShardedRenderer;                     // sharded.h: packs moments_ / features_ of every part, unpacks into part 0's, runs part 0's filter
-    DeviceBufferPtr hist_color_[2], hist_record_[2];   // denoise_temporal(): the history, a ping-pong pair of W*H*4 colours and W*H*4 (V, N, K, D) records
-    DeviceBufferPtr hist_moments_[2];                  // with denoise_moments = 1: the pair's W*H*4 moment records (m1, m2, E, S); the current half exists iff the history has them
-    int hist_cur_ = -1;                                // the half that holds the history (-1: none)
-    TemporalCamera hist_cam_{};                        // the camera of the frame that wrote it
-    DeviceBufferPtr dn_reject_;                        // denoise_temporal() with denoise_reject > 0: the scratch between its two kernels, W*H*8 (dropped by resize)
-    bool reject_stat_ = false;                         // dn_reject_ holds the statistic of the last denoise_temporal()
+    friend struct ShardedRenderer;                     // sharded.h: packs sized_.moments / features of every part, unpacks into part 0's, runs part 0's filter
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     std::vector<hipEvent_t> pt_events_;                // (begin, end) around the path-tracing kernel of every sub-launch
     size_t pt_events_used_ = 0;

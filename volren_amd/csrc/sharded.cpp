@@ -326,7 +326,7 @@ void ShardedRenderer::check_guides(const char* who) {
         p.flush_pending();                                                    // recorded trace() calls: their launch brings the moments up to `sample`
         if (p.ragged()) throw std::runtime_error(part + "its frame is ragged (render_adaptive): adaptive sampling is not available on several devices");
         try { p.check_moments(who); } catch (const std::exception& e) { throw std::runtime_error(part + e.what()); }
-        if (!p.features_) throw std::runtime_error(part + "no feature pass since the last resize (call render_features first)");
+        if (!p.sized_.features) throw std::runtime_error(part + "no feature pass since the last resize (call render_features first)");
     }
 }
 
@@ -351,7 +351,7 @@ void ShardedRenderer::exchange_guides() {
         if (buf_[i].n_own == 0) continue;
         VR_HIP(hipSetDevice(devices_[i]));
         RendererHIP& p = *parts_[i];
-        launch_pack_guides(p.moments_->as<float>(), p.features_->as<float>(), width_, height_, buf_[i].pack_ids->as<int32_t>(), n_max_,
+        launch_pack_guides(p.sized_.moments->as<float>(), p.sized_.features->as<float>(), width_, height_, buf_[i].pack_ids->as<int32_t>(), n_max_,
                            buf_[i].guides_packed->as<float>(), buf_[i].stream);
         VR_HIP(hipGetLastError());
     }
@@ -360,8 +360,8 @@ void ShardedRenderer::exchange_guides() {
     // accumulate and feature pass, which write its own tiles only; the other parts' passes touch their own buffers and need no ordering against this.
     VR_HIP(hipSetDevice(devices_[0]));
     RendererHIP& first = *parts_[0];
-    launch_unpack_guides(buf_[0].guides_gathered->as<float>(), unpack_ids_->as<int32_t>(), (int32_t)(n * (size_t)n_max_), first.moments_->as<float>(),
-                         first.features_->as<float>(), width_, height_, buf_[0].stream);
+    launch_unpack_guides(buf_[0].guides_gathered->as<float>(), unpack_ids_->as<int32_t>(), (int32_t)(n * (size_t)n_max_), first.sized_.moments->as<float>(),
+                         first.sized_.features->as<float>(), width_, height_, buf_[0].stream);
     VR_HIP(hipGetLastError());
 }
 
@@ -372,7 +372,7 @@ void ShardedRenderer::run_denoise(const char* who, bool temporal) {
         parts_[0]->check_resolve(std::string("ShardedRenderer::") + who + ": denoise_resolve = 1: ", transport_ != "none");      // before the exchange launches anything
         for (size_t i = 0; i < parts_.size(); ++i) {
             if (transport_ != "none" && buf_[i].n_own == 0) continue;
-            if (parts_[i]->features_pass_ != parts_[0]->features_pass_ || parts_[i]->features_rays_ != parts_[0]->features_rays_)
+            if (parts_[i]->sized_.pass != parts_[0]->sized_.pass || parts_[i]->sized_.rays != parts_[0]->sized_.rays)
                 throw std::runtime_error(std::string("ShardedRenderer::") + who + ": denoise_resolve = 1: part " + std::to_string(i) +
                                          "'s feature buffer was not filled by the same pass as part 0's (call render_features_expected on the sharded renderer)");
         }

@@ -79,24 +79,29 @@ void launch_denoise_prepare(const float* moments, const float* features, int32_t
                             hipStream_t stream);
 void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
                            float* cout, float* vout, hipStream_t stream);
-// Temporal accumulation (vr_temporal.h), between prepare and the iterations: blends (color W*H*4, v W*H, guide) with the history (hist_color W*H*4,
-// hist_record W*H*4 = (V, N, K, D); both nullptr: no history yet) seen from camera `prev`, writes the new history into out_color / out_record
-// (not the buffers read) and the integrated variance over v.  same_cam: `cur` equals `prev` byte for byte (no reprojection).
-void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
-                             const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
-                             hipStream_t stream);
-// The same with the luminance moments of vr_moments.h ("denoise_moments" = 1), as two kernels: pass 1 also gathers and blends the moment records
-// (hist_moments / out_moments, W*H*4 = (m1, m2, E, S); nullptr with the other two: no history yet), pass 2 forms S and V = S * E with the guide
-// weights of sigma `sg` and writes V into out_record and over v.  The frame's own v is not read.
-void launch_denoise_temporal_moments(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, const float* hist_moments,
-                                     bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, const DenoiseSigma& sg,
-                                     float* out_color, float* out_record, float* out_moments, hipStream_t stream);
-// The same with the rejection test of threshold tau > 0 (vr_temporal.h steps 2a, 3a): two kernels with `scratch` between them, W*H*8 floats that no
-// other argument overlaps: W*H*4 of h, then W*H*4 of (v_h, N_h, z2, has).  Afterwards the first word of each of the latter holds the pixel's
-// statistic T, -1 where the pixel had no history.
-void launch_denoise_temporal_reject(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
-                                    const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float tau, float* scratch,
-                                    float* out_color, float* out_record, hipStream_t stream);
+// Temporal accumulation (vr_temporal.h), between prepare and the iterations, described by one struct.  The plain pass blends (color W*H*4, v W*H, guide
+// W*H*8) with the history (hist_color W*H*4, hist_record W*H*4 = (V, N, K, D)) seen from camera `prev`, writes the new history into out_color / out_record
+// (not the buffers read) and the integrated variance over v.  What else the struct carries picks the kernels:
+//   out_moments set ("denoise_moments" = 1, vr_moments.h), two kernels: pass 1 also gathers and blends the moment records (hist_moments / out_moments, W*H*4 =
+//     (m1, m2, E, S)), pass 2 forms S and V = S * E with the guide weights of `sigma` and writes V into out_record and over v.  The frame's own v is not read.
+//   tau > 0 (the rejection test of vr_temporal.h steps 2a, 3a), two kernels with `scratch` between them, W*H*8 floats that nothing else here overlaps: W*H*4
+//     of h, then W*H*4 of (v_h, N_h, z2, has).  Afterwards the first word of each of the latter holds the pixel's statistic T, -1 where it had no history.
+// The launcher throws for a struct that asks for both, that asks for rejection without a scratch, or whose history pointers are not all set or all null.
+struct TemporalPass {
+    const float* color = nullptr;
+    float* v = nullptr;
+    const float* guide = nullptr;
+    const float *hist_color = nullptr, *hist_record = nullptr, *hist_moments = nullptr;      // the previous history: all nullptr = none yet (hist_moments: with out_moments only)
+    bool same_cam = false;                    // `cur` equals `prev` byte for byte (no reprojection)
+    TemporalCamera cur{}, prev{};
+    int32_t W = 0, H = 0;
+    float alpha = 1.0f;
+    float tau = 0.0f;                         // 0 = no rejection
+    float* scratch = nullptr;                 // rejection only
+    DenoiseSigma sigma{};                     // moments only
+    float *out_color = nullptr, *out_record = nullptr, *out_moments = nullptr;
+};
+void launch_denoise_temporal(const TemporalPass& t, hipStream_t stream);
 // The control variate of vr_resolve.h on the whole frame of P.u.resolution: fb (W*H*4, alpha = the share of samples that hit) and the coverage word of features
 // (W*H*8, an expected-value pass of `rays` rays per axis) -> B (W*H*4: the environment behind each pixel, 0 with it hidden), Pq (W*H*4: the scattered part and its
 // weight) and out (W*H*4: the resolved frame, alpha = the expected coverage).  Two kernels; no two arguments may overlap.

@@ -4,6 +4,8 @@
 // the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
+
 #include "vr_adaptive.h"
 #include "vr_denoise.h"
 #include "vr_device.h"
@@ -15,13 +17,15 @@ namespace vr {
 
 // Denoiser (vr_denoise.h).  No LDS: from step 4 on the 5x5 footprint leaves the tile, and the working set fits the Infinity Cache.  Per tap: the
 // colour (one dwordx4), the variance (one dword) and the guide (two dwordx4).
-struct DenoiseSrcDev {
+struct GuideDev {          // the guide by pixel index, also for pass 2 of vr_moments.h
+    const float4* __restrict__ g;
+    __device__ __forceinline__ void guide(int32_t i, float o[8]) const { const float4 a = g[2 * i], b = g[2 * i + 1]; unpack4(a, o); unpack4(b, o + 4); }
+};
+struct DenoiseSrcDev : GuideDev {
     const float4* __restrict__ c;
     const float* __restrict__ v;
-    const float4* __restrict__ g;
     __device__ __forceinline__ void color(int32_t i, float o[4]) const { unpack4(c[i], o); }
     __device__ __forceinline__ float var(int32_t i) const { return v[i]; }
-    __device__ __forceinline__ void guide(int32_t i, float o[8]) const { const float4 a = g[2 * i], b = g[2 * i + 1]; unpack4(a, o); unpack4(b, o + 4); }
 };
 // prepare: moments S (W*H*4, Welford's M2 / n) -> the unbiased variance var = S * vscale exactly as vr_variance forms it (0 for n = 1), then
 // the variance of the mean's luminance v (W*H) and the guide (W*H*8) from the features.  counts (a frame of adaptive sampling: one count per
@@ -50,7 +54,7 @@ denoise_atrous_kernel(const float4* __restrict__ cin, const float* __restrict__ 
                       int32_t step, const DenoiseSigma sg, float4* __restrict__ cout, float* __restrict__ vout) {
     const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
     if (q.px >= W || q.py >= H) return;
-    const DenoiseSrcDev src{ cin, vin, guide };
+    const DenoiseSrcDev src{ { guide }, cin, vin };
     float o[4], ov;
     denoise_atrous_pixel(src, W, H, q.px, q.py, step, sg, o, ov);
     const int32_t i = q.py * W + q.px;
@@ -109,16 +113,6 @@ denoise_temporal_kernel(const float4* __restrict__ color, float* __restrict__ v,
     os[i] = pack4(S);
     if constexpr (!MOMENTS) v[i] = S[0];
 }
-void launch_denoise_temporal(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
-                             const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float* out_color, float* out_record,
-                             hipStream_t stream) {
-    if (W <= 0 || H <= 0) return;
-    const bool have = hist_color && hist_record;
-    hipLaunchKernelGGL(denoise_temporal_kernel<false>, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
-                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
-                       (const float4*)nullptr, have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color),
-                       reinterpret_cast<float4*>(out_record), (float4*)nullptr);
-}
 
 // Pass 2 of vr_moments.h: the variance of the filter's input from the moments pass 1 blended.  Stages (m1, m2) of the tile's 22 x 22 footprint (16 x 16
 // plus a halo of 3; one dwordx2 load per pixel, m2 = -1 "off the frame") in 3872 B of LDS, one barrier -- threads outside the frame stage and wait with
@@ -127,49 +121,26 @@ void launch_denoise_temporal(const float* color, float* v, const float* guide, c
 // guide per tile would charge every tile of every frame 15 KiB of loads for taps that almost none of its pixels make; on the first frame, where all do,
 // the 49 x 32 B of a pixel are its neighbours' too and hit the L2.  Writes S into the pixel's moment record, V = S * E into its history record and over
 // its v: words of its own pixel that no other thread reads (the staging of the neighbouring tiles reads m1, m2 only, at no fixed time).  No atomics.
-constexpr int32_t kMomentsFoot = 16 + 2 * kMomentsWindow;      // edge of a tile's footprint in pixels
+using MomentsWindow = TileWindow<kMomentsWindow>;
 struct MomentsWindowDev {
     const float2* win;     // the staged footprint
     int32_t at;            // the pixel's own pair in it
-    __device__ __forceinline__ void moments(int32_t dx, int32_t dy, float m[2]) const { const float2 p = win[at + dy * kMomentsFoot + dx]; m[0] = p.x; m[1] = p.y; }
-};
-struct MomentsGuideDev {
-    const float4* __restrict__ g;
-    __device__ __forceinline__ void guide(int32_t i, float o[8]) const { const float4 a = g[2 * i], b = g[2 * i + 1]; unpack4(a, o); unpack4(b, o + 4); }
+    __device__ __forceinline__ void moments(int32_t dx, int32_t dy, float m[2]) const { const float2 p = win[at + dy * MomentsWindow::kFoot + dx]; m[0] = p.x; m[1] = p.y; }
 };
 __global__ void __launch_bounds__(256)
 denoise_moments_variance_kernel(const float4* __restrict__ guide, int32_t W, int32_t H, const DenoiseSigma sg, float4* os, float4* om, float* __restrict__ v) {
-    __shared__ float2 win[kMomentsFoot * kMomentsFoot];
+    __shared__ float2 win[MomentsWindow::kTexels];
     const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
-    const int32_t nx = tiles_x(W);
-    const int32_t x0 = ((int32_t)blockIdx.x % nx) * 16 - kMomentsWindow, y0 = ((int32_t)blockIdx.x / nx) * 16 - kMomentsWindow;
-    for (int32_t f = (int32_t)threadIdx.x; f < kMomentsFoot * kMomentsFoot; f += 256) {
-        const int32_t x = x0 + f % kMomentsFoot, y = y0 + f / kMomentsFoot;
-        float2 pair = make_float2(0.0f, kMomentsOffFrame);
-        if (x >= 0 && x < W && y >= 0 && y < H) pair = *reinterpret_cast<const float2*>(&om[y * W + x].x);
-        win[f] = pair;
-    }
-    __syncthreads();
+    const MomentsWindow window = MomentsWindow::of((int32_t)blockIdx.x, W);
+    stage_window(win, window, W, H, make_float2(0.0f, kMomentsOffFrame), [&](int32_t i) { return *reinterpret_cast<const float2*>(&om[i].x); });
     if (q.px >= W || q.py >= H) return;
     const int32_t i = q.py * W + q.px;
     const float N = os[i].y, E = om[i].z;
-    const float S = moments_variance(MomentsWindowDev{ win, (q.py - y0) * kMomentsFoot + (q.px - x0) }, MomentsGuideDev{ guide }, W, q.px, q.py, N, sg);
+    const float S = moments_variance(MomentsWindowDev{ win, window.at(q.px, q.py) }, GuideDev{ guide }, W, q.px, q.py, N, sg);
     const float V = S * E;
     om[i].w = S;
     os[i].x = V;
     v[i] = V;
-}
-void launch_denoise_temporal_moments(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, const float* hist_moments,
-                                     bool same_cam, const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, const DenoiseSigma& sg,
-                                     float* out_color, float* out_record, float* out_moments, hipStream_t stream) {
-    if (W <= 0 || H <= 0) return;
-    const bool have = hist_color && hist_record && hist_moments;
-    hipLaunchKernelGGL(denoise_temporal_kernel<true>, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
-                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
-                       reinterpret_cast<const float4*>(hist_moments), have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, alpha, reinterpret_cast<float4*>(out_color),
-                       reinterpret_cast<float4*>(out_record), reinterpret_cast<float4*>(out_moments));
-    hipLaunchKernelGGL(denoise_moments_variance_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(guide), W, H, sg,
-                       reinterpret_cast<float4*>(out_record), reinterpret_cast<float4*>(out_moments), v);
 }
 
 // The same with the rejection test (vr_temporal.h steps 2a, 3a; tau > 0 only), as two kernels, because a pixel's decision needs the z2 of its 5 x 5
@@ -179,11 +150,11 @@ void launch_denoise_temporal_moments(const float* color, float* v, const float* 
 // in 1600 B of LDS, one barrier -- threads outside the frame stage and wait with the others -- then sums its 25 words from LDS, blends, and writes
 // the new history and v where denoise_temporal_kernel writes them.  The statistic T (-1 without a history) goes over the pixel's v_h word, which only
 // this thread reads: the z2 and has words are read by the neighbouring tiles' staging, at no fixed time, so they stay as they are.  No atomics.
-constexpr int32_t kRejectFoot = 16 + 2 * kTemporalWindow;      // edge of a tile's footprint in pixels
+using RejectWindow = TileWindow<kTemporalWindow>;
 struct TemporalWindowDev {
     const float* win;      // the staged footprint
     int32_t at;            // the pixel's own word in it
-    __device__ __forceinline__ float word(int32_t dx, int32_t dy) const { return win[at + dy * kRejectFoot + dx]; }
+    __device__ __forceinline__ float word(int32_t dx, int32_t dy) const { return win[at + dy * RejectWindow::kFoot + dx]; }
 };
 __global__ void __launch_bounds__(256)
 denoise_temporal_fetch_kernel(const float4* __restrict__ color, const float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ hc,
@@ -204,20 +175,13 @@ denoise_temporal_fetch_kernel(const float4* __restrict__ color, const float* __r
 __global__ void __launch_bounds__(256)
 denoise_temporal_resolve_kernel(const float4* __restrict__ color, float* __restrict__ v, const float4* __restrict__ guide, const float4* __restrict__ sh,
                                 float4* sr, int32_t W, int32_t H, float alpha, float tau, float4* __restrict__ oc, float4* __restrict__ os) {
-    __shared__ float win[kRejectFoot * kRejectFoot];
+    __shared__ float win[RejectWindow::kTexels];
     const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
-    const int32_t nx = tiles_x(W);
-    const int32_t x0 = ((int32_t)blockIdx.x % nx) * 16 - kTemporalWindow, y0 = ((int32_t)blockIdx.x / nx) * 16 - kTemporalWindow;
-    for (int32_t f = (int32_t)threadIdx.x; f < kRejectFoot * kRejectFoot; f += 256) {
-        const int32_t x = x0 + f % kRejectFoot, y = y0 + f / kRejectFoot;
-        float word = kTemporalNoHistory;
-        if (x >= 0 && x < W && y >= 0 && y < H) {
-            const float2 zh = *reinterpret_cast<const float2*>(&sr[y * W + x].z);
-            word = temporal_window_word(zh.y != 0.0f, zh.x);
-        }
-        win[f] = word;
-    }
-    __syncthreads();
+    const RejectWindow window = RejectWindow::of((int32_t)blockIdx.x, W);
+    stage_window(win, window, W, H, kTemporalNoHistory, [&](int32_t i) {
+        const float2 zh = *reinterpret_cast<const float2*>(&sr[i].z);
+        return temporal_window_word(zh.y != 0.0f, zh.x);
+    });
     if (q.px >= W || q.py >= H) return;
     const int32_t i = q.py * W + q.px;
     float c[4], h[4];
@@ -226,7 +190,7 @@ denoise_temporal_resolve_kernel(const float4* __restrict__ color, float* __restr
     const float4 r = sr[i];
     const bool has = r.w != 0.0f;
     float T = kTemporalNoHistory;
-    if (has) T = temporal_pool(TemporalWindowDev{ win, (q.py - y0) * kRejectFoot + (q.px - x0) });
+    if (has) T = temporal_pool(TemporalWindowDev{ win, window.at(q.px, q.py) });
     float C[4], S[4];
     temporal_blend(has && !temporal_rejects(T, tau), h, r.x, r.y, c, v[i], guide[2 * i].w, guide[2 * i + 1].w, alpha, C, S);
     oc[i] = pack4(C);
@@ -234,18 +198,30 @@ denoise_temporal_resolve_kernel(const float4* __restrict__ color, float* __restr
     v[i] = S[0];
     sr[i].x = T;
 }
-void launch_denoise_temporal_reject(const float* color, float* v, const float* guide, const float* hist_color, const float* hist_record, bool same_cam,
-                                    const TemporalCamera& cur, const TemporalCamera& prev, int32_t W, int32_t H, float alpha, float tau, float* scratch,
-                                    float* out_color, float* out_record, hipStream_t stream) {
-    if (W <= 0 || H <= 0) return;
-    const bool have = hist_color && hist_record;
-    float4* sh = reinterpret_cast<float4*>(scratch);
-    float4* sr = sh + (size_t)W * H;
-    hipLaunchKernelGGL(denoise_temporal_fetch_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
-                       reinterpret_cast<const float4*>(guide), reinterpret_cast<const float4*>(hist_color), reinterpret_cast<const float4*>(hist_record),
-                       have ? 1 : 0, same_cam ? 1 : 0, cur, prev, W, H, sh, sr);
-    hipLaunchKernelGGL(denoise_temporal_resolve_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(color), v,
-                       reinterpret_cast<const float4*>(guide), sh, sr, W, H, alpha, tau, reinterpret_cast<float4*>(out_color), reinterpret_cast<float4*>(out_record));
+// The one launcher of the three forms (vr_device.h TemporalPass): what the struct carries picks the kernels.
+void launch_denoise_temporal(const TemporalPass& t, hipStream_t stream) {
+    const bool moments = t.out_moments != nullptr, reject = t.tau > 0.0f, have = t.hist_color != nullptr;
+    if (moments && reject) throw std::invalid_argument("launch_denoise_temporal: moment records and rejection do not go together");
+    if (reject && !t.scratch) throw std::invalid_argument("launch_denoise_temporal: rejection without a scratch buffer");
+    if ((t.hist_record != nullptr) != have || (t.hist_moments != nullptr) != (have && moments))
+        throw std::invalid_argument("launch_denoise_temporal: the history's pointers are not all set or all null");
+    if (t.W <= 0 || t.H <= 0) return;
+    const dim3 grid((unsigned)tile_count(t.W, t.H)), block(256);
+    const float4 *color = reinterpret_cast<const float4*>(t.color), *guide = reinterpret_cast<const float4*>(t.guide);
+    const float4 *hc = reinterpret_cast<const float4*>(t.hist_color), *hs = reinterpret_cast<const float4*>(t.hist_record), *hm = reinterpret_cast<const float4*>(t.hist_moments);
+    float4 *oc = reinterpret_cast<float4*>(t.out_color), *os = reinterpret_cast<float4*>(t.out_record), *om = reinterpret_cast<float4*>(t.out_moments);
+    const int32_t have_i = have ? 1 : 0, same_i = t.same_cam ? 1 : 0;
+    if (moments) {
+        hipLaunchKernelGGL(denoise_temporal_kernel<true>, grid, block, 0, stream, color, t.v, guide, hc, hs, hm, have_i, same_i, t.cur, t.prev, t.W, t.H, t.alpha, oc, os, om);
+        hipLaunchKernelGGL(denoise_moments_variance_kernel, grid, block, 0, stream, guide, t.W, t.H, t.sigma, os, om, t.v);
+    } else if (reject) {
+        float4* sh = reinterpret_cast<float4*>(t.scratch);
+        float4* sr = sh + (size_t)t.W * t.H;
+        hipLaunchKernelGGL(denoise_temporal_fetch_kernel, grid, block, 0, stream, color, t.v, guide, hc, hs, have_i, same_i, t.cur, t.prev, t.W, t.H, sh, sr);
+        hipLaunchKernelGGL(denoise_temporal_resolve_kernel, grid, block, 0, stream, color, t.v, guide, sh, sr, t.W, t.H, t.alpha, t.tau, oc, os);
+    } else {
+        hipLaunchKernelGGL(denoise_temporal_kernel<false>, grid, block, 0, stream, color, t.v, guide, hc, hs, hm, have_i, same_i, t.cur, t.prev, t.W, t.H, t.alpha, oc, os, om);
+    }
 }
 
 // The control variate of vr_resolve.h, two kernels with the frames B and P (W*H float4 each) between them, because a pixel's coefficient pools the P of its
@@ -255,11 +231,11 @@ void launch_denoise_temporal_reject(const float* color, float* v, const float* g
 // asks for) in 7744 B of LDS, one barrier -- threads outside the frame stage and wait with the others -- then reads the pixel's texels of the framebuffer and
 // of B and the coverage word of its features, sums its 49 taps from LDS and writes one dwordx4.  The same kernel with the taps read from global memory, as the
 // a-trous kernel reads its own, measured 53.5 us against 24.1 us at 1024 x 1024 (profiles/r13_resolve.txt) and was dropped.  No atomics, no scratch.
-constexpr int32_t kResolveFoot = 16 + 2 * kResolveWindow;      // edge of a tile's footprint in pixels
+using ResolveWindow = TileWindow<kResolveWindow>;
 struct ResolveWindowDev {
     const float4* win;     // the staged footprint
     int32_t at;            // the pixel's own texel in it
-    __device__ __forceinline__ void tap(int32_t dx, int32_t dy, float o[4]) const { unpack4(win[at + dy * kResolveFoot + dx], o); }
+    __device__ __forceinline__ void tap(int32_t dx, int32_t dy, float o[4]) const { unpack4(win[at + dy * ResolveWindow::kFoot + dx], o); }
 };
 __global__ void __launch_bounds__(256)
 resolve_prepare_kernel(const SceneParams P, const float4* __restrict__ fb, int32_t rays, float4* __restrict__ B, float4* __restrict__ Pq) {
@@ -276,23 +252,16 @@ resolve_prepare_kernel(const SceneParams P, const float4* __restrict__ fb, int32
 __global__ void __launch_bounds__(256)
 resolve_kernel(const float4* __restrict__ fb, const float4* __restrict__ features, const float4* __restrict__ B, const float4* __restrict__ Pq, int32_t W, int32_t H,
                float4* __restrict__ out) {
-    __shared__ float4 win[kResolveFoot * kResolveFoot];
+    __shared__ float4 win[ResolveWindow::kTexels];
     const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
-    const int32_t nx = tiles_x(W);
-    const int32_t x0 = ((int32_t)blockIdx.x % nx) * 16 - kResolveWindow, y0 = ((int32_t)blockIdx.x / nx) * 16 - kResolveWindow;
-    for (int32_t f = (int32_t)threadIdx.x; f < kResolveFoot * kResolveFoot; f += 256) {
-        const int32_t x = x0 + f % kResolveFoot, y = y0 + f / kResolveFoot;
-        float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (x >= 0 && x < W && y >= 0 && y < H) t = Pq[y * W + x];
-        win[f] = t;
-    }
-    __syncthreads();
+    const ResolveWindow window = ResolveWindow::of((int32_t)blockIdx.x, W);
+    stage_window(win, window, W, H, make_float4(0.0f, 0.0f, 0.0f, 0.0f), [&](int32_t i) { return Pq[i]; });
     if (q.px >= W || q.py >= H) return;
     const int32_t i = q.py * W + q.px;
     float x[4], b[4], y[4];
     unpack4(fb[i], x);
     unpack4(B[i], b);
-    resolve_pixel(ResolveWindowDev{ win, (q.py - y0) * kResolveFoot + (q.px - x0) }, W, H, q.px, q.py, x, b, features[2 * i].w, y);
+    resolve_pixel(ResolveWindowDev{ win, window.at(q.px, q.py) }, W, H, q.px, q.py, x, b, features[2 * i].w, y);
     out[i] = pack4(y);
 }
 void launch_resolve(const SceneParams& P, const float* fb, const float* features, int32_t rays, float* B, float* Pq, float* out, hipStream_t stream) {

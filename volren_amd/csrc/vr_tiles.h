@@ -3,6 +3,7 @@
 //   wave-tiled : as four 8x8 sub-tiles, one per wavefront (sub-tile s at (8 (s & 1), 8 (s >> 1)), lane l at (l & 7, l >> 3) in it) -- every per-pixel
 //                kernel, and the path tracer's work units (vr_pathtrace.h make_unit: a unit is one sub-tile x spu samples); or
 //   raster     : thread t at (t & 15, t >> 4) -- the packed tiles of the sharded framebuffer and of its denoiser guides only, whose texel order is wire format.
+// Also here: the window of a tile's pixels plus a halo that a kernel stages in LDS (TileWindow, stage_window), and the wire and table indices below.
 // tests/hostkernel/tiles_host.cpp and guides_host.cpp build this header for the host.
 #pragma once
 
@@ -33,6 +34,17 @@ VR_HD TilePixel raster_in_tile_pixel(int32_t tile, uint32_t t, int32_t W) {
     const int32_t nx = tiles_x(W);
     return TilePixel{ tile, 0, 0, (tile % nx) * 16 + (int32_t)(t & 15u), (tile / nx) * 16 + (int32_t)(t >> 4) };
 }
+// The window a workgroup stages for its tile: the tile's 16 x 16 pixels plus a halo of R on every side, kFoot x kFoot texels in raster order, texel f at
+// frame coordinates (x0 + f % kFoot, y0 + f / kFoot) -- outside the frame along its borders.  at(px, py): the texel of a pixel of the tile; its neighbour
+// (dx, dy), |dx|, |dy| <= R, lies dy * kFoot + dx further on.  tests/hostkernel/tiles_host.cpp checks that arithmetic on the host.
+template <int32_t R>
+struct TileWindow {
+    static constexpr int32_t kFoot = 16 + 2 * R, kTexels = kFoot * kFoot;
+    int32_t x0, y0;
+    VR_HD static TileWindow of(int32_t tile, int32_t W) { const int32_t nx = tiles_x(W); return TileWindow{ (tile % nx) * 16 - R, (tile / nx) * 16 - R }; }
+    VR_HD int32_t at(int32_t px, int32_t py) const { return (py - y0) * kFoot + (px - x0); }
+};
+
 // The packed denoiser guides of the sharded renderer (pack_guides_kernel / unpack_guides_kernel): kGuidePlanes float4 planes per pixel -- 0 the moments
 // texel, 1 and 2 the two float4 of the pixel's eight features -- plane-major inside a tile slot, thread t in raster_in_tile_pixel order.  The float4
 // index below is WIRE FORMAT: the parts of a sharded renderer exchange these buffers, n_max * kGuidePlanes * 256 float4 per part.
@@ -69,6 +81,19 @@ VR_HD float variance_scale(int32_t n) { return n >= 2 ? (float)n / (float)(n - 1
 // a texel as the lane code takes it, float[4], and back: one dwordx4 either way
 __device__ __forceinline__ void unpack4(const float4 t, float o[4]) { o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w; }
 __device__ __forceinline__ float4 pack4(const float o[4]) { return make_float4(o[0], o[1], o[2], o[3]); }
+// Fills win[0 .. kTexels) -- LDS of the workgroup of 256 threads that serves the window's tile -- with load(y * W + x) for a texel inside the W x H frame and
+// off_value for any other, then waits for all of them.  EVERY thread of the workgroup calls it, before the `px >= W || py >= H` return of the threads whose
+// pixel lies outside a ragged frame: they stage texels like the others, and the barrier counts them.
+template <int32_t R, class T, class Load>
+__device__ __forceinline__ void stage_window(T* win, const TileWindow<R> window, int32_t W, int32_t H, const T off_value, Load load) {
+    for (int32_t f = (int32_t)threadIdx.x; f < TileWindow<R>::kTexels; f += 256) {
+        const int32_t x = window.x0 + f % TileWindow<R>::kFoot, y = window.y0 + f / TileWindow<R>::kFoot;
+        T t = off_value;
+        if (x >= 0 && x < W && y >= 0 && y < H) t = load(y * W + x);
+        win[f] = t;
+    }
+    __syncthreads();
+}
 #endif
 
 }  // namespace vr
