@@ -296,6 +296,26 @@ int vr_denoise_history_moments(vr_renderer* r, float* out);
 int vr_resolve(vr_renderer* r);
 int vr_resolved(vr_renderer* r, float* rgba_out);
 int vr_resolve_background(vr_renderer* r, float* rgba_out);
+/* --- the filter on the scattered layer alone, normalised by the expected coverage (no reference counterpart).
+ *     A partially covered pixel shows (1 - kappa) B + kappa C.  kappa is exact (vr_render_features_expected), B analytic (vr_resolve); only C is noisy.
+ *     vr_set_int / vr_get_int "denoise_layers" (0 or 1; default 0, and then every launch, allocation and result is what it is without this
+ *     paragraph; anything else is VR_ERR, the old value kept; a call that changes the value drops the history).  With 1, vr_denoise and
+ *     vr_denoise_temporal -- with "denoise_reject" and with "denoise_moments" too -- run vr_resolve's kernels (whatever "denoise_resolve" says), then
+ *         split:   G = (1 - kappa) B;   S.rgb = y.rgb - G (signed);   S.a = kappa
+ *         filter:  their own kernels, unchanged, on S in place of the frame, with the frame's variance: F (F.a is kappa under the colour's weights)
+ *         merge:   L.rgb = F.a > 2^-20 ? F.rgb * (kappa / F.a) : F.rgb;   L.a = kappa;   out.rgb = max(0, G + L.rgb);   out.a = kappa
+ *     so the sky seen through thin smoke is not blurred and the silhouette ramp is kappa's own; a pixel with kappa = 0 within the filter's reach of
+ *     the volume (F.a > 2^-20) comes out as B bit for bit.
+ *     The arithmetic is specified operation by operation in volren_amd/csrc/vr_layers.h and reproducible bit for bit.  vr_denoised returns out;
+ *     under vr_denoise_temporal the history (vr_denoise_history) holds the layer S blended over the frames, not the composite, so a turning camera
+ *     does not drag old sky along behind the volume.  Whatever vr_resolve refuses these calls refuse then, before anything is launched, besides their
+ *     own refusals: it needs vr_render_features_expected with rays >= 2 as the last feature pass.  Without a transfer function kappa lies about
+ *     0.0004 below the path tracer's coverage, and that bias stays, as with vr_resolve.  README.md has the measured errors, among them the case that
+ *     loses.  vr_sharded_denoise / vr_sharded_denoise_temporal honour part 0's setting, bit for bit one device's result.
+ *     vr_denoised_layer waits and writes L of the last such call, W*H*4 floats, linear, row 0 at the bottom: the scattered light premultiplied by the
+ *     exact coverage, alpha = kappa; composite it over any background B' as (1 - a) B' + rgb.  VR_ERR before the first vr_denoise or
+ *     vr_denoise_temporal with the setting on since the last resize. */
+int vr_denoised_layer(vr_renderer* r, float* rgba_out);
 /* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
  *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
  *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the

@@ -22,7 +22,7 @@ SYMBOLS = [
     "vr_sharded_create", "vr_sharded_destroy", "vr_sharded_parts", "vr_sharded_part", "vr_sharded_transport", "vr_sharded_collective", "vr_sharded_reset", "vr_sharded_render", "vr_sharded_synchronize", "vr_tile_owners", "vr_wave_timeline",
     "vr_render_features", "vr_render_features_expected", "vr_expected_stats", "vr_expected_clear_table", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
     "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history", "vr_denoise_reject_stat", "vr_denoise_history_moments",
-    "vr_resolve", "vr_resolved", "vr_resolve_background",
+    "vr_resolve", "vr_resolved", "vr_resolve_background", "vr_denoised_layer",
     "vr_render_adaptive", "vr_tile_samples", "vr_tile_error",
     "vr_seed_table_default_mb", "vr_seed_table_samples_for",
     "vr_sharded_render_features", "vr_sharded_render_features_expected", "vr_sharded_gather_guides", "vr_sharded_denoise", "vr_sharded_denoise_temporal",
@@ -92,6 +92,7 @@ def load():
     L.vr_resolve.argtypes = [vp]
     L.vr_resolved.argtypes = [vp, vp]
     L.vr_resolve_background.argtypes = [vp, vp]
+    L.vr_denoised_layer.argtypes = [vp, vp]
     L.vr_render_adaptive.argtypes = [vp, ci, ci, cf]
     L.vr_tile_samples.argtypes = [vp, vp, ci]
     L.vr_tile_error.argtypes = [vp, vp, ci]

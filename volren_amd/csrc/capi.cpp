@@ -296,6 +296,7 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
         }
         else if (n == "denoise_moments") R.set_denoise_moments(v);
         else if (n == "denoise_resolve") R.set_denoise_resolve(v);
+        else if (n == "denoise_layers") R.set_denoise_layers(v);
         else if (n == "coalesce_trace") { R.flush_pending(); R.coalesce_trace = v != 0; }
         else if (n == "majorant_layout") { if (v < -1 || v > 1) throw std::runtime_error("majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)"); R.majorant_layout = v; }
         else if (n == "tf_float_atlas") R.tf_float_atlas = v != 0;
@@ -336,6 +337,7 @@ int vr_get_int(vr_renderer* r, const char* name, int* v) {
         else if (n == "denoise_iterations") *v = R.denoise_iterations;
         else if (n == "denoise_moments") *v = R.denoise_moments;
         else if (n == "denoise_resolve") *v = R.denoise_resolve;
+        else if (n == "denoise_layers") *v = R.denoise_layers;
         else if (n == "coalesce_trace") *v = R.coalesce_trace ? 1 : 0;
         else if (n == "majorant_layout") *v = R.majorant_layout;
         else if (n == "majorant_blocked") {          // what the current frame's next launch will use
@@ -561,6 +563,12 @@ int vr_resolve_background(vr_renderer* r, float* out) {
     if (!out) return fail(VR_ERR_ARG, "null argument");
     NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_resolve_background(out); });
+}
+int vr_denoised_layer(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); r->impl.download_denoised_layer(out); });
 }
 int vr_denoised(vr_renderer* r, float* out) {
     NEED(r);

@@ -16,6 +16,8 @@
 // the sampled feature pass (refused without a denoise flag).
 // --resolve with --expected-features N, N >= 2: the frame's hit/miss noise is replaced by the expected coverage of that pass (vr_resolve.h).  Alone it writes the
 // tonemapped resolved frame; with --denoise / --denoise-temporal the filter starts from the resolved frame ("denoise_resolve" = 1).  One device only.
+// --denoise-layers with --denoise / --denoise-temporal and --expected-features N, N >= 2: the filter runs on the scattered layer alone and the analytic
+// background is put back afterwards ("denoise_layers" = 1, vr_layers.h); refused without them.
 // --expected-skip 0|1 with --expected-features: whether that pass skips empty space by the clear-distance table (default 1; the frame is the same either
 // way; refused without --expected-features).
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
@@ -96,7 +98,7 @@ static void parse_cmd(int argc, char** argv) {
     Args a{ argc, argv, 0 };
     for (a.i = 1; a.i < argc; ++a.i) {
         const std::string arg = argv[a.i];
-        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments" || arg == "--resolve") {      // --denoise*, --adaptive: main()
+        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments" || arg == "--denoise-layers" || arg == "--resolve") {      // --denoise*, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
@@ -178,6 +180,7 @@ int main(int argc, char** argv) {
     int expected_rays = 0;      // --expected-features N: the denoise flags take their guide from render_features_expected(N) instead of render_features(min(spp, 16))
     int expected_skip = -1;     // --expected-skip 0|1 (with --expected-features): whether that pass drops the steps of empty space (same frame either way); -1: the renderer's default
     bool resolve = false;       // --resolve (with --expected-features N >= 2): the control variate on the expected coverage, alone or in front of the filter
+    bool layers = false;        // --denoise-layers (with a denoise flag and --expected-features N >= 2): the filter runs on the scattered layer alone ("denoise_layers" = 1, vr_layers.h)
     bool reject_given = false, moments = false;      // moments: --denoise-moments, the filter's variance from the history's luminance moments (low-spp sequences)
     std::vector<int> devices;
     try {
@@ -191,6 +194,7 @@ int main(int argc, char** argv) {
             else if (arg == "--denoise") denoise = true;
             else if (arg == "--denoise-temporal") denoise = temporal = true;
             else if (arg == "--denoise-moments") moments = true;
+            else if (arg == "--denoise-layers") layers = true;
             else if (arg == "--resolve") resolve = true;
             else if (arg == "--denoise-reject") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --denoise-reject");
@@ -217,6 +221,8 @@ int main(int argc, char** argv) {
         if (reject_given && !temporal) throw std::runtime_error("--denoise-reject needs --denoise-temporal: it rejects the history that only that call keeps");
         if (resolve && expected_rays == 0) throw std::runtime_error("--resolve needs --expected-features N with N >= 2: the expected coverage of that pass is what replaces the frame's");
         if (resolve && expected_rays < 2) throw std::runtime_error("--resolve needs --expected-features N with N >= 2: one ray gives the coverage of the pixel's centre, not of its area");
+        if (layers && !denoise) throw std::runtime_error("--denoise-layers needs --denoise or --denoise-temporal: it is a setting of their filter");
+        if (layers && expected_rays < 2) throw std::runtime_error("--denoise-layers needs --expected-features N with N >= 2: the expected coverage of that pass splits the frame into background and scattered layer");
         if (expected_rays > 0 && !denoise && !resolve) throw std::runtime_error("--expected-features needs --denoise, --denoise-temporal or --resolve: it chooses the guide of their filter");
         if (expected_skip >= 0 && expected_rays == 0) throw std::runtime_error("--expected-skip needs --expected-features: it is a setting of that pass");
         if (moments && !temporal) throw std::runtime_error("--denoise-moments needs --denoise-temporal: the moments live in the history that only that call keeps");
@@ -254,6 +260,7 @@ int main(int argc, char** argv) {
             renderer->denoise_reject = reject;
             renderer->denoise_moments = moments ? 1 : 0;
             renderer->denoise_resolve = resolve && denoise ? 1 : 0;
+            renderer->denoise_layers = layers ? 1 : 0;
             if (expected_skip >= 0) renderer->expected_skip = expected_skip;
             parts.push_back(renderer);
         }

@@ -1045,7 +1045,9 @@ void RendererHIP::download_variance(float* rgba) {
 // 1, 2, 4, ...  Iteration 0 reads the framebuffer itself; colour and variance ping-pong between buffers of their own, and the last iteration
 // writes `denoised` (N = 0: a copy of the framebuffer).
 // temporal (denoise_temporal, vr_temporal.h): between prepare and the iterations the frame is blended with the history, and the iterations start
-// from the new history's colour and variance instead.  Every buffer the call needs is allocated before its first launch, so a failed allocation
+// from the new history's colour and variance instead.  layers (denoise_layers, vr_layers.h): the frame all of this reads is the resolved frame's
+// scattered layer S (resolve, then a split), the last iteration writes a buffer F of its own, and a merge writes `denoised` and the layer from F.
+// Every buffer the call needs is allocated before its first launch, so a failed allocation
 // leaves the last result and the history as they were.
 void RendererHIP::denoise() { run_denoise("denoise", false); }
 void RendererHIP::denoise_temporal() { run_denoise("denoise_temporal", true); }
@@ -1060,6 +1062,8 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (temporal && denoise_moments != 0 && denoise_reject > 0.0f)
         throw std::runtime_error(me + "denoise_moments = 1 and denoise_reject > 0 do not go together: the rejection statistic needs the frames' sample variance, and the moment variance of 1-spp frames is too heavy-tailed for it (DESIGN.md 5)");
     if (denoise_resolve != 0) check_resolve(me + "denoise_resolve = 1: ", whole_frame_gathered);
+    const bool layers = denoise_layers != 0;          // vr_layers.h: the filter runs on the scattered layer, between a split and a merge
+    if (layers) check_resolve(me + "denoise_layers = 1: ", whole_frame_gathered);
     const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
     if (ragged()) {
         for (int32_t c : tile_n_)
@@ -1074,8 +1078,9 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (N < 0 || N > kDenoiseMaxIterations) throw std::runtime_error(me + "denoise_iterations out of range");
     const size_t px = (size_t)W * H;
     Sized::History& hist = sized_.hist;
-    // a history without moment records cannot continue one with them, nor the other way round (denoise_moments set as a field, past set_denoise_moments)
-    if (temporal && hist.cur >= 0 && (hist.moments[hist.cur] != nullptr) != (denoise_moments != 0)) drop_history();
+    // a history without moment records cannot continue one with them, nor the other way round (denoise_moments set as a field, past set_denoise_moments);
+    // nor one of composites one of layers (denoise_layers set as a field, past set_denoise_layers)
+    if (temporal && hist.cur >= 0 && ((hist.moments[hist.cur] != nullptr) != (denoise_moments != 0) || hist.layers != layers)) drop_history();
     const int to = hist.cur < 0 ? 0 : 1 - hist.cur;      // the half of the history pair this call writes
     const bool reject = temporal && denoise_reject > 0.0f;      // vr_temporal.h steps 2a, 3a: the fetch / resolve pair instead of the one kernel
     const bool moments = temporal && denoise_moments != 0;      // vr_moments.h: the temporal kernel with the moment records, then the variance kernel
@@ -1087,9 +1092,16 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     ensure_buffer(sized_.denoised, px * 4 * sizeof(float));
     if (N >= 2) { ensure_buffer(sized_.dn_var[1], px * sizeof(float)); ensure_buffer(sized_.dn_color[0], px * 4 * sizeof(float)); }
     if (N >= 3) ensure_buffer(sized_.dn_color[1], px * 4 * sizeof(float));
+    if (layers) { ensure_buffer(sized_.ly_split, px * 4 * sizeof(float)); ensure_buffer(sized_.ly_filtered, px * 4 * sizeof(float)); ensure_buffer(sized_.layer, px * 4 * sizeof(float)); }
     const float vscale = variance_scale(sample);      // download_variance's factor
-    if (denoise_resolve != 0) run_resolve();      // vr_resolve.h: the filter starts from y, with the frame's own variance
+    if (denoise_resolve != 0 || layers) run_resolve();      // vr_resolve.h: the filter starts from y, with the frame's own variance
     const DeviceBuffer* frame = denoise_resolve != 0 ? sized_.resolved.get() : color.get();
+    if (layers) {                                     // ... or from y's scattered layer S; the last iteration then writes F, and the merge writes `denoised` and the layer
+        launch_layers_split(sized_.resolved->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.ly_split->as<float>(), stream);
+        VR_HIP(hipGetLastError());
+        frame = sized_.ly_split.get();
+    }
+    DeviceBuffer* const result = layers ? sized_.ly_filtered.get() : sized_.denoised.get();
     launch_denoise_prepare(sized_.moments->as<float>(), sized_.features->as<float>(), W, H, sample, vscale, counts, sized_.dn_var[0]->as<float>(), sized_.dn_guide->as<float>(), stream);
     VR_HIP(hipGetLastError());
     const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
@@ -1116,19 +1128,21 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         launch_denoise_temporal(t, stream);
         VR_HIP(hipGetLastError());
         sized_.reject_stat = reject;
-        hist.cur = to; hist.cam = cur;
+        hist.cur = to; hist.cam = cur; hist.layers = layers;
         first = hist.color[to].get();
     }
-    if (N == 0) {
-        VR_HIP(hipMemcpyAsync(sized_.denoised->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
-        return;
-    }
+    if (N == 0) VR_HIP(hipMemcpyAsync(result->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
     for (int32_t k = 0; k < N; ++k) {
         const float* cin = k == 0 ? first->as<float>() : sized_.dn_color[(k - 1) & 1]->as<float>();
-        float* cout = k == N - 1 ? sized_.denoised->as<float>() : sized_.dn_color[k & 1]->as<float>();
+        float* cout = k == N - 1 ? result->as<float>() : sized_.dn_color[k & 1]->as<float>();
         float* vout = k == N - 1 ? nullptr : sized_.dn_var[(k + 1) & 1]->as<float>();
         launch_denoise_atrous(cin, sized_.dn_var[k & 1]->as<float>(), sized_.dn_guide->as<float>(), W, H, 1 << k, sg, cout, vout, stream);
         VR_HIP(hipGetLastError());
+    }
+    if (layers) {
+        launch_layers_merge(result->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.denoised->as<float>(), sized_.layer->as<float>(), stream);
+        VR_HIP(hipGetLastError());
+        sized_.layer_valid = true;
     }
 }
 
@@ -1181,6 +1195,18 @@ void RendererHIP::set_denoise_resolve(int v) {
     flush_pending();
     drop_history();
     denoise_resolve = v;
+}
+
+void RendererHIP::set_denoise_layers(int v) {
+    if (v != 0 && v != 1) throw std::runtime_error("denoise_layers: 0 (the filter runs on the frame) or 1 (on the scattered layer, the background of the expected coverage put back afterwards)");
+    if (v == denoise_layers) return;
+    flush_pending();
+    drop_history();
+    denoise_layers = v;
+}
+
+void RendererHIP::download_denoised_layer(float* rgba) {
+    download_whole(sized_.layer_valid ? sized_.layer : nullptr, rgba, "denoised_layer: no denoise with denoise_layers = 1 since the last resize");
 }
 
 void RendererHIP::download_history_moments(float* out) {

@@ -250,6 +250,15 @@ struct RendererHIP {
     void download_resolve_background(float* rgba);
     void set_denoise_resolve(int v);
     int denoise_resolve = 0;
+    // The layered filter (vr_layers.h).  denoise_layers = 1: denoise() and denoise_temporal() -- with rejection and with moments too -- run resolve()'s two kernels
+    // (whatever denoise_resolve says), split the resolved frame into the background's share and the scattered layer, filter the layer with the frame's own variance,
+    // and merge: the layer renormalised by the exact coverage, the analytic background added back.  The history then holds the layer, not the composite.  Whatever
+    // resolve() refuses they refuse then, before anything is launched (0 is today's calls exactly: the same launches, allocations and results).
+    // set_denoise_layers: 0 or 1, throws otherwise; a change drops the history.  download_denoised_layer: the layer of the last such call, W*H*4 floats: scattered
+    // light premultiplied by the exact coverage, alpha = the coverage; throws before the first such call since the last resize.
+    void set_denoise_layers(int v);
+    int denoise_layers = 0;
+    void download_denoised_layer(float* rgba);
     void download_history(float* rgba, float* var, float* length);
     void download_reject_stat(float* out);
     void set_denoise_moments(int v);
@@ -339,6 +348,8 @@ private:
         DeviceBufferPtr moments;                       // W*H*4 second moments, allocated by the first launch with `variance` on
         int moments_n = -1;                            // the moments cover samples 1..moments_n (-1: they do not start at sample 1)
         DeviceBufferPtr rs_bg, rs_part, resolved;      // resolve(): B, P and the resolved frame, W*H*4 each
+        DeviceBufferPtr ly_split, ly_filtered, layer;  // denoise() with denoise_layers = 1: S, F and the layer L, W*H*4 each (vr_layers.h)
+        bool layer_valid = false;                      // `layer` holds the layer of a finished call's merge
         DeviceBufferPtr dn_guide, dn_var[2], dn_color[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4
         DeviceBufferPtr denoised;                      // W*H*4: the last denoise()'s or denoise_temporal()'s result
         DeviceBufferPtr dn_reject;                     // denoise_temporal() with denoise_reject > 0: the scratch between its two kernels, W*H*8
@@ -348,6 +359,7 @@ private:
             DeviceBufferPtr color[2], record[2];       // W*H*4 colours and W*H*4 (V, N, K, D) records, and
             DeviceBufferPtr moments[2];                // with denoise_moments = 1 the W*H*4 moment records (m1, m2, E, S); the current half exists iff the history has them
             int cur = -1;                              // the half that holds the history (-1: none)
+            bool layers = false;                       // it holds the scattered layer (denoise_layers = 1), not the composite
             TemporalCamera cam{};                      // the camera of the frame that wrote it
         } hist;
     } sized_;

@@ -367,13 +367,15 @@ void ShardedRenderer::exchange_guides() {
 
 void ShardedRenderer::run_denoise(const char* who, bool temporal) {
     check_guides(who);
-    if (parts_[0]->denoise_resolve != 0) {      // part 0's setting: its resolve reads the gathered guide, which must be one expected-value pass on every part
+    // part 0's settings: its resolve (in front of the filter, or of the layered filter's split) reads the gathered guide, which must be one expected-value pass on every part
+    if (parts_[0]->denoise_resolve != 0 || parts_[0]->denoise_layers != 0) {
+        const std::string setting = parts_[0]->denoise_resolve != 0 ? ": denoise_resolve = 1: " : ": denoise_layers = 1: ";
         VR_HIP(hipSetDevice(devices_[0]));
-        parts_[0]->check_resolve(std::string("ShardedRenderer::") + who + ": denoise_resolve = 1: ", transport_ != "none");      // before the exchange launches anything
+        parts_[0]->check_resolve(std::string("ShardedRenderer::") + who + setting, transport_ != "none");      // before the exchange launches anything
         for (size_t i = 0; i < parts_.size(); ++i) {
             if (transport_ != "none" && buf_[i].n_own == 0) continue;
             if (parts_[i]->sized_.pass != parts_[0]->sized_.pass || parts_[i]->sized_.rays != parts_[0]->sized_.rays)
-                throw std::runtime_error(std::string("ShardedRenderer::") + who + ": denoise_resolve = 1: part " + std::to_string(i) +
+                throw std::runtime_error(std::string("ShardedRenderer::") + who + setting + "part " + std::to_string(i) +
                                          "'s feature buffer was not filled by the same pass as part 0's (call render_features_expected on the sharded renderer)");
         }
     }

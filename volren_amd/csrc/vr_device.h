@@ -106,6 +106,11 @@ void launch_denoise_temporal(const TemporalPass& t, hipStream_t stream);
 // (W*H*8, an expected-value pass of `rays` rays per axis) -> B (W*H*4: the environment behind each pixel, 0 with it hidden), Pq (W*H*4: the scattered part and its
 // weight) and out (W*H*4: the resolved frame, alpha = the expected coverage).  Two kernels; no two arguments may overlap.
 void launch_resolve(const SceneParams& P, const float* fb, const float* features, int32_t rays, float* B, float* Pq, float* out, hipStream_t stream);
+// The layered filter of vr_layers.h on whole W x H frames.  split: y (W*H*4, the resolved frame), B (W*H*4, launch_resolve's) and the coverage word of features
+// (W*H*8) -> S (W*H*4: the scattered layer, alpha = the coverage), which the denoiser's kernels read in the frame's place.  merge: F (W*H*4, their output), B and
+// features -> out (W*H*4: the frame with the background back) and L (W*H*4: the layer).  One kernel each; outputs must not overlap inputs.
+void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream);
+void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream);
 // Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,

@@ -1,6 +1,6 @@
 // vr_filters.hip -- the image-space kernels (gfx950): everything that reads or writes whole frames or tiles of them after the path tracer.
 // The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h, vr_moments.h), the error estimate of adaptive
-// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
+// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), the layered filter's split and merge (vr_layers.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
 // the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include "vr_adaptive.h"
 #include "vr_denoise.h"
 #include "vr_device.h"
+#include "vr_layers.h"
 #include "vr_moments.h"
 #include "vr_resolve.h"
 #include "vr_temporal.h"
@@ -272,6 +273,45 @@ void launch_resolve(const SceneParams& P, const float* fb, const float* features
                        reinterpret_cast<float4*>(Pq));
     hipLaunchKernelGGL(resolve_kernel, grid, block, 0, stream, reinterpret_cast<const float4*>(fb), reinterpret_cast<const float4*>(features),
                        reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(Pq), W, H, reinterpret_cast<float4*>(out));
+}
+
+// The layered filter of vr_layers.h: split in front of the denoiser's kernels, merge behind them.  One thread per pixel, dwordx4 loads and stores, no LDS, no
+// atomics.  split reads the pixel's texels of the resolved frame and of B and the first float4 of its features (the coverage word) and writes S: 64 B a pixel.
+// merge reads the filter's output, B and the same float4 and writes the frame and the layer: 80 B a pixel.
+__global__ void __launch_bounds__(256)
+layers_split_kernel(const float4* __restrict__ y, const float4* __restrict__ B, const float4* __restrict__ features, int32_t W, int32_t H, float4* __restrict__ S) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float yy[4], b[4], s[4];
+    unpack4(y[i], yy);
+    unpack4(B[i], b);
+    layers_split_pixel(yy, b, features[2 * i].w, s);
+    S[i] = pack4(s);
+}
+__global__ void __launch_bounds__(256)
+layers_merge_kernel(const float4* __restrict__ F, const float4* __restrict__ B, const float4* __restrict__ features, int32_t W, int32_t H, float4* __restrict__ out,
+                    float4* __restrict__ L) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float f[4], b[4], l[4], o[4];
+    unpack4(F[i], f);
+    unpack4(B[i], b);
+    layers_merge_pixel(f, b, features[2 * i].w, l, o);
+    out[i] = pack4(o);
+    L[i] = pack4(l);
+}
+void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(layers_split_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(y),
+                       reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(features), W, H, reinterpret_cast<float4*>(S));
+}
+void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(layers_merge_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(F),
+                       reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(features), W, H, reinterpret_cast<float4*>(out),
+                       reinterpret_cast<float4*>(L));
 }
 
 // Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile; each lane forms e_p of its pixel (-inf outside

@@ -8,7 +8,7 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
+               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
                "expected_skip", "expected_stats")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
@@ -357,6 +357,14 @@ class Renderer:
         _lib.check(self._L.vr_resolve_background(self._h, out.ctypes.data))
         return out
 
+    def denoised_layer(self):
+        """[H][W][4] float32, row 0 = bottom: the layer of the last denoise() / denoise_temporal() with `denoise_layers = 1` (include/volren_amd.h
+        vr_denoised_layer): the filtered scattered light premultiplied by the exact coverage, alpha = the coverage; over a background B' it composites
+        as (1 - a) B' + rgb.  Refused before the first such call since the last resize."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        _lib.check(self._L.vr_denoised_layer(self._h, out.ctypes.data))
+        return out
+
     # ---- adaptive sampling ----
     def render_adaptive(self, min_spp, max_spp, threshold, sync=True):
         """Per 16x16 tile: min_spp samples, then doubling until the tile's error e_t is below `threshold` or it has max_spp samples
@@ -606,6 +614,20 @@ class ShardedRenderer:
     def denoise_resolve(self, value):
         for p in self.parts:
             p.denoise_resolve = value
+
+    @property
+    def denoise_layers(self):
+        """Whether denoise() / denoise_temporal() filter the scattered layer alone and put the analytic background back (Renderer.denoise_layers): part 0's
+        field, which holds the gathered frame and guide and runs it; setting it sets every part's."""
+        return self.parts[0].denoise_layers
+
+    @denoise_layers.setter
+    def denoise_layers(self, value):
+        for p in self.parts:
+            p.denoise_layers = value
+
+    def denoised_layer(self):
+        return self.parts[0].denoised_layer()
 
 
 def math_probe(fn, a, b=None):

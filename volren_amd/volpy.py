@@ -424,7 +424,7 @@ class Renderer:
     def __getattr__(self, name):
         if name == "variance":
             return self._r.get_int("variance")
-        if name in ("denoise_reject", "denoise_moments", "denoise_resolve", "expected_skip"):
+        if name in ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "expected_skip"):
             return getattr(self._r, name)
         if name in _SCALARS:
             return getattr(self._r, name)
@@ -433,7 +433,7 @@ class Renderer:
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments", "denoise_resolve", "expected_skip"):
+        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "expected_skip"):
             setattr(self._r, name, value)
         elif name in _VEC3S:
             setattr(self._r, name, np.asarray(vec3(value) if np.ndim(value) == 0 else value, np.float32).reshape(3))
@@ -592,6 +592,13 @@ class Renderer:
     def resolved_data(self):
         """(w, h, 3) float: the colour of the last resolve(), in fbo_data()'s shape."""
         return self._r.resolved()[..., :3].copy().reshape(self._r.width, self._r.height, 3)
+
+    def denoised_layer_data(self):
+        """(w, h, 4) float: the layer of the last denoise() or denoise_temporal() run with `denoise_layers = 1` (default 0; a change drops the history;
+        needs render_features_expected with rays >= 2), in fbo_data()'s shape: the filtered scattered light premultiplied by the exact coverage, alpha =
+        the coverage (volren_amd.Renderer.denoised_layer).  With the setting on the filter runs on that layer alone and the analytic background is put
+        back afterwards: denoised_data() is the composite."""
+        return self._r.denoised_layer().reshape(self._r.width, self._r.height, 4)
 
     # -- adaptive sampling (no reference counterpart): like render(), from sample 0
     def render_adaptive(self, min_spp, max_spp, threshold):
