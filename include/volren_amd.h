@@ -316,6 +316,33 @@ int vr_resolve_background(vr_renderer* r, float* rgba_out);
  *     exact coverage, alpha = kappa; composite it over any background B' as (1 - a) B' + rgb.  VR_ERR before the first vr_denoise or
  *     vr_denoise_temporal with the setting on since the last resize. */
 int vr_denoised_layer(vr_renderer* r, float* rgba_out);
+/* --- the denoised scattered layer upsampled under a full-resolution guide (no reference counterpart).
+ *     kappa and B of (1 - kappa) B + kappa C are functions of the camera ray alone and cost no path-tracing sample at any resolution; C is smooth after the
+ *     filter.  So a frame can be path-traced and filtered `factor` times smaller per axis -- the same samples buy factor^2 times the spp there -- and the
+ *     full-size picture rebuilt from its layer.  vr_upsample(r, factor, rays), after vr_denoise or vr_denoise_temporal with "denoise_layers" = 1 on the
+ *     renderer's w x h frame ("lo"), writes the W = factor w by H = factor h frame ("hi") into buffers of its own:
+ *         guide:   an expected-value pass of rays x rays sub-rays at W x H (bit for bit vr_render_features_expected's of a renderer resized to W x H; it honours
+ *                  "expected_skip" and "expected_stats" alike), and B_p, vr_resolve's background, at W x H
+ *         taps:    the 4 x 4 lo pixels around the hi pixel's centre, spatial weight s the uniform cubic B-spline's, edge factor e = w_n w_d w_a of vr_denoise
+ *                  between the hi and the lo guide with "denoise_sigma" (1 unless both coverages are positive); no colour and no coverage weight
+ *         C = sum (s e) L_q.rgb / sum (s e) kappa_q where that sum exceeds 2^-20, else the same with s alone, else 0
+ *         L_p.rgb = kappa_p C;   L_p.a = kappa_p;   out.rgb = max(0, (1 - kappa_p) B_p + L_p.rgb);   out.a = kappa_p
+ *     so the silhouette ramp and the sky are the hi frame's own, and a hi pixel with kappa_p = 0 is B_p bit for bit.  The arithmetic is specified operation
+ *     by operation in volren_amd/csrc/vr_upsample.h and reproducible bit for bit.  Asynchronous on the renderer's stream, and a flush point like vr_denoise.
+ *     VR_ERR_ARG for a factor outside 2..4 or rays outside 1..4.  VR_ERR, before anything is launched, when vr_denoised_layer would be refused (no denoise call
+ *     with "denoise_layers" = 1 since the last resize) or a tile subset is set.  The first call allocates the hi buffers; vr_resize drops them, and so does a
+ *     call with another factor.  The hi guide is marched when the call is made: the camera and the scene are the caller's to keep as they were at the denoise
+ *     call.  The framebuffer, vr_features, vr_denoised, vr_denoised_layer and the history are left as they were.  There is no history at the hi size.
+ *     Sharded renderers: after vr_sharded_denoise part 0 holds the gathered frame, guide and layer, and vr_upsample on vr_sharded_part(s, 0) is the call -- one
+ *     device's work.  README.md has the measured errors and costs, among them the cells that lose.
+ *     vr_upsampled and vr_upsampled_layer wait and write W*H*4 floats, linear, row 0 at the bottom: out, and L (premultiplied by the exact coverage, alpha =
+ *     kappa_p; composite it as (1 - a) B' + rgb).  vr_upsampled_features writes the hi feature buffer, W*H*8 floats in vr_features' layout.  vr_upsampled_size
+ *     writes (W, H).  All four are VR_ERR before the first vr_upsample since the last resize. */
+int vr_upsample(vr_renderer* r, int factor, int rays);
+int vr_upsampled(vr_renderer* r, float* rgba_out);
+int vr_upsampled_layer(vr_renderer* r, float* rgba_out);
+int vr_upsampled_features(vr_renderer* r, float* out);
+int vr_upsampled_size(vr_renderer* r, int wh[2]);
 /* --- adaptive sampling (no reference counterpart): "render until the error is below t, at most N spp", decided per 16x16 tile.
  *     The error of tile t is e_t, the worst relative standard error of a pixel mean's luminance in the tile: per pixel of n samples,
  *     e_p = sqrt(the variance of the mean's luminance, as vr_denoise forms it) / (luma(mean) + 2^-10), +inf for n < 2; e_t = the max over the

@@ -23,6 +23,7 @@ SYMBOLS = [
     "vr_render_features", "vr_render_features_expected", "vr_expected_stats", "vr_expected_clear_table", "vr_features", "vr_variance", "vr_denoise", "vr_denoised",
     "vr_denoise_temporal", "vr_denoise_history_reset", "vr_denoise_history", "vr_denoise_reject_stat", "vr_denoise_history_moments",
     "vr_resolve", "vr_resolved", "vr_resolve_background", "vr_denoised_layer",
+    "vr_upsample", "vr_upsampled", "vr_upsampled_layer", "vr_upsampled_features", "vr_upsampled_size",
     "vr_render_adaptive", "vr_tile_samples", "vr_tile_error",
     "vr_seed_table_default_mb", "vr_seed_table_samples_for",
     "vr_sharded_render_features", "vr_sharded_render_features_expected", "vr_sharded_gather_guides", "vr_sharded_denoise", "vr_sharded_denoise_temporal",
@@ -93,6 +94,11 @@ def load():
     L.vr_resolved.argtypes = [vp, vp]
     L.vr_resolve_background.argtypes = [vp, vp]
     L.vr_denoised_layer.argtypes = [vp, vp]
+    L.vr_upsample.argtypes = [vp, ci, ci]
+    L.vr_upsampled.argtypes = [vp, vp]
+    L.vr_upsampled_layer.argtypes = [vp, vp]
+    L.vr_upsampled_features.argtypes = [vp, vp]
+    L.vr_upsampled_size.argtypes = [vp, vp]
     L.vr_render_adaptive.argtypes = [vp, ci, ci, cf]
     L.vr_tile_samples.argtypes = [vp, vp, ci]
     L.vr_tile_error.argtypes = [vp, vp, ci]

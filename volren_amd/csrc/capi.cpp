@@ -570,6 +570,37 @@ int vr_denoised_layer(vr_renderer* r, float* out) {
     NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_denoised_layer(out); });
 }
+int vr_upsample(vr_renderer* r, int factor, int rays) {
+    NEED(r);
+    if (factor < 2 || factor > 4) return fail(VR_ERR_ARG, "vr_upsample: factor must be 2..4");
+    if (rays < 1 || rays > vr::kExpectedMaxRays) return fail(VR_ERR_ARG, "vr_upsample: rays must be 1..4");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); r->impl.upsample(factor, rays); });
+}
+int vr_upsampled(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); r->impl.download_upsampled(out); });
+}
+int vr_upsampled_layer(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); r->impl.download_upsampled_layer(out); });
+}
+int vr_upsampled_features(vr_renderer* r, float* out) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); r->impl.download_upsampled_features(out); });
+}
+int vr_upsampled_size(vr_renderer* r, int wh[2]) {
+    NEED(r);
+    if (!wh) return fail(VR_ERR_ARG, "null argument");
+    NEED_DEVICE();
+    return guard([&] { r->impl.upsampled_size(wh); });
+}
 int vr_denoised(vr_renderer* r, float* out) {
     NEED(r);
     if (!out) return fail(VR_ERR_ARG, "null argument");

@@ -18,6 +18,9 @@
 // tonemapped resolved frame; with --denoise / --denoise-temporal the filter starts from the resolved frame ("denoise_resolve" = 1).  One device only.
 // --denoise-layers with --denoise / --denoise-temporal and --expected-features N, N >= 2: the filter runs on the scattered layer alone and the analytic
 // background is put back afterwards ("denoise_layers" = 1, vr_layers.h); refused without them.
+// --upsample F (2..4) with --denoise-layers (and so with a denoise flag and --expected-features N): the frame is rendered and filtered at -w x -h, its layer is
+// rebuilt at F times that size per axis under an expected-value guide of N rays at the large size (vr_upsample.h), and the tonemapped F w x F h frame is
+// written; refused alone.
 // --expected-skip 0|1 with --expected-features: whether that pass skips empty space by the clear-distance table (default 1; the frame is the same either
 // way; refused without --expected-features).
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
@@ -101,6 +104,8 @@ static void parse_cmd(int argc, char** argv) {
         if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments" || arg == "--denoise-layers" || arg == "--resolve") {      // --denoise*, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
+        } else if (arg == "--upsample") {
+            a.next();                                           // main()
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
         } else if (arg == "--output") out_filename = a.next();
         else if (arg == "--samples" || arg == "--spp" || arg == "--sppx") renderer->sppx = a.nexti();
@@ -181,6 +186,7 @@ int main(int argc, char** argv) {
     int expected_skip = -1;     // --expected-skip 0|1 (with --expected-features): whether that pass drops the steps of empty space (same frame either way); -1: the renderer's default
     bool resolve = false;       // --resolve (with --expected-features N >= 2): the control variate on the expected coverage, alone or in front of the filter
     bool layers = false;        // --denoise-layers (with a denoise flag and --expected-features N >= 2): the filter runs on the scattered layer alone ("denoise_layers" = 1, vr_layers.h)
+    int upsample = 0;           // --upsample F (with --denoise-layers): the frame written is F times -w x -h, rebuilt from the filtered layer (vr_upsample.h); 0: off
     bool reject_given = false, moments = false;      // moments: --denoise-moments, the filter's variance from the history's luminance moments (low-spp sequences)
     std::vector<int> devices;
     try {
@@ -206,6 +212,10 @@ int main(int argc, char** argv) {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-features");
                 expected_rays = std::stoi(argv[++i]);
                 if (expected_rays < 1 || expected_rays > kExpectedMaxRays) throw std::runtime_error("--expected-features: the rays per pixel axis must be 1..4");
+            } else if (arg == "--upsample") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --upsample");
+                upsample = std::stoi(argv[++i]);
+                if (upsample < 2 || upsample > 4) throw std::runtime_error("--upsample: the factor per axis must be 2..4");
             } else if (arg == "--expected-skip") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-skip");
                 const std::string v = argv[++i];
@@ -223,6 +233,7 @@ int main(int argc, char** argv) {
         if (resolve && expected_rays < 2) throw std::runtime_error("--resolve needs --expected-features N with N >= 2: one ray gives the coverage of the pixel's centre, not of its area");
         if (layers && !denoise) throw std::runtime_error("--denoise-layers needs --denoise or --denoise-temporal: it is a setting of their filter");
         if (layers && expected_rays < 2) throw std::runtime_error("--denoise-layers needs --expected-features N with N >= 2: the expected coverage of that pass splits the frame into background and scattered layer");
+        if (upsample > 0 && !layers) throw std::runtime_error("--upsample needs --denoise-layers: the filtered scattered layer is what it upsamples");
         if (expected_rays > 0 && !denoise && !resolve) throw std::runtime_error("--expected-features needs --denoise, --denoise-temporal or --resolve: it chooses the guide of their filter");
         if (expected_skip >= 0 && expected_rays == 0) throw std::runtime_error("--expected-skip needs --expected-features: it is a setting of that pass");
         if (moments && !temporal) throw std::runtime_error("--denoise-moments needs --denoise-temporal: the moments live in the history that only that call keeps");
@@ -314,7 +325,11 @@ int main(int argc, char** argv) {
                 else renderer->denoise();
                 renderer->synchronize();
                 if (renderer->watchdog_status()) throw std::runtime_error("feature pass: a camera segment exceeded its step budget");
-                renderer->draw_from(*renderer->denoised());
+                if (upsample > 0) {
+                    renderer->upsample(upsample, expected_rays);
+                    renderer->synchronize();
+                }
+                renderer->draw_from(upsample > 0 ? *renderer->upsampled() : *renderer->denoised());
             } else if (resolve) {
                 renderer->render_features_expected(expected_rays);
                 renderer->resolve();
@@ -323,14 +338,15 @@ int main(int argc, char** argv) {
             } else {
                 renderer->draw();
             }
-            std::vector<float> fb((size_t)width * height * 4);
+            const int out_w = upsample > 0 ? upsample * width : width, out_h = upsample > 0 ? upsample * height : height;
+            std::vector<float> fb((size_t)out_w * out_h * 4);
             renderer->download_display(fb.data());
             std::vector<uint8_t> rgba;
-            framebuffer_to_rgba8(fb.data(), width, height, rgba);
+            framebuffer_to_rgba8(fb.data(), out_w, out_h, rgba);
             char num[16];
             snprintf(num, sizeof num, "%06zu", i);
             const std::string out_fn = fs::path(out_filename).stem().string() + "_" + num + ".png";   // directory of --output is dropped (reference quirk)
-            save_png_rgba8(out_fn, rgba.data(), width, height);
+            save_png_rgba8(out_fn, rgba.data(), out_w, out_h);
             std::cout << out_fn << " written." << std::endl;
         }
         shards.reset();                                 // before the parts it points at

@@ -14,6 +14,7 @@
 #include "vr_device.h"
 #include "vr_math.h"
 #include "vr_probe.h"
+#include "vr_upsample.h"
 
 namespace vr {
 
@@ -835,7 +836,7 @@ void RendererHIP::draw_from(const DeviceBuffer& src) {
     ensure_buffer(display, src.size_bytes());
     VR_HIP(hipMemcpyAsync(display->get(), src.get(), src.size_bytes(), hipMemcpyDeviceToDevice, stream));
     if (tonemapping) {
-        launch_tonemap(display->as<float>(), resolution.x, resolution.y, tonemap_exposure, tonemap_gamma, stream);
+        launch_tonemap(display->as<float>(), (int32_t)(src.size_bytes() / (4 * sizeof(float))), 1, tonemap_exposure, tonemap_gamma, stream);      // src's own texels: upsample()'s frame is larger than the renderer's
         VR_HIP(hipGetLastError());
     }
 }
@@ -898,9 +899,10 @@ void RendererHIP::download_display(float* rgba) const {
 // The feature pass reads the scene as a render() would: capture() (which also decodes the float atlas under a transfer function) and the majorant
 // table of the current density scale and LUT.  It runs the lane code of the run-time kernel variant, which reads every grid from its own atlas:
 // the views of a frame whose grids share a paired atlas are made again without it (the majorant layout stays the one the table is built in).
+// feature_scene: P = that scene, and nothing else -- upsample() marches a pass at another resolution into a buffer of its own with it.
 // begin_feature_pass: what both feature passes do before their launch -- P = that scene; the feature buffer exists (zero-filled when it is new); returns the
 // number of tiles of the tile set.
-int RendererHIP::begin_feature_pass(SceneParams& P) {
+void RendererHIP::feature_scene(SceneParams& P) {
     flush_pending();
     LaunchInputs in;
     capture(in);
@@ -911,6 +913,10 @@ int RendererHIP::begin_feature_pass(SceneParams& P) {
         P.emission = make_view(emission_grids.at(in.frame), false);
         P.paired = 0;
     }
+}
+
+int RendererHIP::begin_feature_pass(SceneParams& P) {
+    feature_scene(P);
     const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y);
     const size_t bytes = (size_t)resolution.x * resolution.y * 8 * sizeof(float);
     if (ensure_buffer(sized_.features, bytes)) {
@@ -933,6 +939,11 @@ void RendererHIP::render_features_expected(int rays) {
     if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("render_features_expected: rays must be 1.." + std::to_string(kExpectedMaxRays));
     SceneParams P;
     const int n_tiles = begin_feature_pass(P);
+    sized_.pass = 2; sized_.rays = rays;
+    launch_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, sized_.features->as<float>());
+}
+
+void RendererHIP::launch_expected(const SceneParams& P, const int32_t* tiles, int n_tiles, int rays, float* out) {
     ClearTable clear = { nullptr, { 0, 0, 0 } };
     if (expected_skip) clear = clear_table_of(density_grids.at(volume->grid_frame_counter), P.density);
     expected_stats_valid_ = false;
@@ -942,8 +953,7 @@ void RendererHIP::render_features_expected(int rays) {
         VR_HIP(hipMemsetAsync(expected_stats_->get(), 0, expected_stats_->size_bytes(), stream));
         counters = expected_stats_->as<unsigned long long>();
     }
-    sized_.pass = 2; sized_.rays = rays;
-    launch_features_expected(P, tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr, n_tiles, rays, sized_.features->as<float>(), stream, &clear, counters);
+    launch_features_expected(P, tiles, n_tiles, rays, out, stream, &clear, counters);
     VR_HIP(hipGetLastError());
     expected_stats_valid_ = counters != nullptr;
 }
@@ -1143,6 +1153,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         launch_layers_merge(result->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.denoised->as<float>(), sized_.layer->as<float>(), stream);
         VR_HIP(hipGetLastError());
         sized_.layer_valid = true;
+        sized_.layer_gathered = whole_frame_gathered;
     }
 }
 
@@ -1207,6 +1218,40 @@ void RendererHIP::set_denoise_layers(int v) {
 
 void RendererHIP::download_denoised_layer(float* rgba) {
     download_whole(sized_.layer_valid ? sized_.layer : nullptr, rgba, "denoised_layer: no denoise with denoise_layers = 1 since the last resize");
+}
+
+// The layer upsampled under a full-resolution guide (vr_upsample.h): the expected-value pass at the hi size into the call's own buffer, then one kernel.
+void RendererHIP::upsample(int factor, int rays) {
+    if (factor < kUpsampleMinFactor || factor > kUpsampleMaxFactor) throw std::runtime_error("upsample: factor must be 2..4");
+    if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("upsample: rays must be 1.." + std::to_string(kExpectedMaxRays));
+    flush_pending();
+    if (!sized_.layer_valid) throw std::runtime_error("upsample: no denoise with denoise_layers = 1 since the last resize (its layer is what the call upsamples)");
+    if (!tiles_host_.empty() && !sized_.layer_gathered) throw std::runtime_error("upsample: a tile subset is set (set_tiles); the call rebuilds whole frames only");
+    const int32_t w = resolution.x, h = resolution.y, W = factor * w, H = factor * h;
+    const size_t px = (size_t)W * (size_t)H;
+    if (px * 2u > (size_t)INT32_MAX) throw std::runtime_error("upsample: the upsampled frame is too large (32-bit pixel indices)");
+    SceneParams P;
+    feature_scene(P);
+    P.u.resolution[0] = W; P.u.resolution[1] = H;         // all else as it is: the kernels take the frame's size from here alone
+    if (sized_.up_factor != factor) { sized_.up_factor = 0; sized_.up_features.reset(); sized_.up_out.reset(); sized_.up_layer.reset(); }
+    ensure_buffer(sized_.up_features, px * 8 * sizeof(float));
+    ensure_buffer(sized_.up_out, px * 4 * sizeof(float));
+    ensure_buffer(sized_.up_layer, px * 4 * sizeof(float));
+    launch_expected(P, nullptr, tile_count(W, H), rays, sized_.up_features->as<float>());
+    const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
+    launch_upsample(P, sized_.layer->as<float>(), sized_.dn_guide->as<float>(), w, h, factor, sized_.up_features->as<float>(), rays, sg, sized_.up_out->as<float>(),
+                    sized_.up_layer->as<float>(), stream);
+    VR_HIP(hipGetLastError());
+    sized_.up_factor = factor;
+}
+
+static const char* const kNoUpsample = "upsampled: no upsample since the last resize (call upsample first)";
+void RendererHIP::download_upsampled(float* rgba) { download_whole(sized_.up_factor ? sized_.up_out : nullptr, rgba, kNoUpsample); }
+void RendererHIP::download_upsampled_layer(float* rgba) { download_whole(sized_.up_factor ? sized_.up_layer : nullptr, rgba, kNoUpsample); }
+void RendererHIP::download_upsampled_features(float* out) { download_whole(sized_.up_factor ? sized_.up_features : nullptr, out, kNoUpsample); }
+void RendererHIP::upsampled_size(int wh[2]) const {
+    if (!sized_.up_factor) throw std::runtime_error(kNoUpsample);
+    wh[0] = sized_.up_factor * resolution.x; wh[1] = sized_.up_factor * resolution.y;
 }
 
 void RendererHIP::download_history_moments(float* out) {

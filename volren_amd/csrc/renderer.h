@@ -259,6 +259,21 @@ struct RendererHIP {
     void set_denoise_layers(int v);
     int denoise_layers = 0;
     void download_denoised_layer(float* rgba);
+    // The layer upsampled under a full-resolution guide (vr_upsample.h).  upsample(factor, rays): the frame at factor x the renderer's size per axis, rebuilt from
+    // the layer of the last denoise() / denoise_temporal() with denoise_layers = 1 and an expected-value pass of `rays` rays per axis at that size, which the call
+    // marches into a buffer of its own with the scene and camera as they are now -- the caller keeps them as they were at the denoise call.  expected_skip and
+    // expected_stats act on that pass as on render_features_expected.  Asynchronous; flushes recorded samples first.  factor in 2..4, rays in 1..4.  Throws, before
+    // anything is launched, when download_denoised_layer would, or when a tile subset is set (unless the layer is a gathered whole frame's: part 0 of a
+    // ShardedRenderer).  The first call allocates the hi buffers; resize drops them, and so does a call with another factor.  The framebuffer, the lo feature
+    // buffer with what says which pass filled it, the filter's results and the history are not touched.
+    // download_upsampled / download_upsampled_layer: the hi frame and the hi layer, W*H*4 floats each; download_upsampled_features: the hi feature buffer, W*H*8,
+    // bit for bit render_features_expected's of a renderer resized to W x H.  upsampled_size: (W, H).  All four throw before the first upsample since the last resize.
+    void upsample(int factor, int rays);
+    void download_upsampled(float* rgba);
+    void download_upsampled_layer(float* rgba);
+    void download_upsampled_features(float* out);
+    void upsampled_size(int wh[2]) const;
+    const DeviceBuffer* upsampled() const { return sized_.up_factor ? sized_.up_out.get() : nullptr; }
     void download_history(float* rgba, float* var, float* length);
     void download_reject_stat(float* out);
     void set_denoise_moments(int v);
@@ -278,6 +293,9 @@ struct RendererHIP {
     // with the values they were recorded with.
     void flush_pending();
     int begin_feature_pass(SceneParams& P);      // the common head of render_features / render_features_expected (renderer.cpp)
+    void feature_scene(SceneParams& P);          // its first half, which upsample() shares: the scene as a feature pass reads it; touches no feature buffer
+    // the expected-value pass both callers launch: the clear-distance table and the counters as expected_skip / expected_stats say, then the kernel over `tiles`
+    void launch_expected(const SceneParams& P, const int32_t* tiles, int n_tiles, int rays, float* out);
     int pending_samples() const { return pending_n_; }         // samples recorded by trace() and not launched yet
     bool coalesce_trace = true;                                // false: every trace() is its own launch (round 4's behaviour; A/B and tests)
     double last_kernel_ms();                                    // HIP-event time of the last launch (a render(), or the trace() calls coalesced into one): all sub-launches, path tracing + accumulation (waits for it)
@@ -350,6 +368,9 @@ private:
         DeviceBufferPtr rs_bg, rs_part, resolved;      // resolve(): B, P and the resolved frame, W*H*4 each
         DeviceBufferPtr ly_split, ly_filtered, layer;  // denoise() with denoise_layers = 1: S, F and the layer L, W*H*4 each (vr_layers.h)
         bool layer_valid = false;                      // `layer` holds the layer of a finished call's merge
+        bool layer_gathered = false;                   // ... of a gathered whole frame (part 0 of a ShardedRenderer): the renderer's tile subset is no obstacle to upsample()
+        DeviceBufferPtr up_features, up_out, up_layer; // upsample(): the hi feature buffer (W*H*8), the hi frame and the hi layer (W*H*4 each), W x H = up_factor x the frame
+        int up_factor = 0;                             // the factor they were allocated and last filled for (0: none)
         DeviceBufferPtr dn_guide, dn_var[2], dn_color[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4
         DeviceBufferPtr denoised;                      // W*H*4: the last denoise()'s or denoise_temporal()'s result
         DeviceBufferPtr dn_reject;                     // denoise_temporal() with denoise_reject > 0: the scratch between its two kernels, W*H*8

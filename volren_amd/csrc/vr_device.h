@@ -111,6 +111,11 @@ void launch_resolve(const SceneParams& P, const float* fb, const float* features
 // features -> out (W*H*4: the frame with the background back) and L (W*H*4: the layer).  One kernel each; outputs must not overlap inputs.
 void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream);
 void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream);
+// The upsampling of vr_upsample.h.  P: the scene with the HI resolution W x H = f w x f h (f in 2..4, or it throws); lo_layer (w*h*4: launch_layers_merge's L),
+// lo_guide (w*h*8: launch_denoise_prepare's guide), hi_features (W*H*8: an expected-value pass at the hi resolution, `rays` rays per axis) -> out (W*H*4: the hi
+// frame) and L (W*H*4: the hi layer).  One kernel; outputs must not overlap inputs.
+void launch_upsample(const SceneParams& P, const float* lo_layer, const float* lo_guide, int32_t w, int32_t h, int32_t f, const float* hi_features, int32_t rays,
+                     const DenoiseSigma& sg, float* out, float* L, hipStream_t stream);
 // Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,

@@ -1,6 +1,6 @@
 // vr_filters.hip -- the image-space kernels (gfx950): everything that reads or writes whole frames or tiles of them after the path tracer.
 // The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h, vr_moments.h), the error estimate of adaptive
-// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), the layered filter's split and merge (vr_layers.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
+// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), the layered filter's split and merge (vr_layers.h), the layer's upsampling under a full-resolution guide (vr_upsample.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
 // the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "vr_moments.h"
 #include "vr_resolve.h"
 #include "vr_temporal.h"
+#include "vr_upsample.h"
 
 namespace vr {
 
@@ -312,6 +313,75 @@ void launch_layers_merge(const float* F, const float* B, const float* features, 
     hipLaunchKernelGGL(layers_merge_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(F),
                        reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(features), W, H, reinterpret_cast<float4*>(out),
                        reinterpret_cast<float4*>(L));
+}
+
+// The upsampling of vr_upsample.h: one workgroup per 16 x 16 tile of the HI frame, F = hi / lo per axis at compile time (the window's size and the divisions
+// by 2F).  Stages the lo texels the tile's taps can touch (vr_tiles.h ScaledTileWindow: 12 x 12 at most, for F = 2) as records of three float4 -- the layer and
+// the two float4 of the lo guide, 48 B a texel, 6912 B of LDS at most -- once, one barrier; threads outside a ragged hi frame stage and wait with the others,
+// and texels off the lo frame hold a record no tap reads (the lane code skips such taps by their coordinates).  Then a pixel reads the two float4 of its hi
+// features, forms its guide and B_p (rays x rays environment lookups, none with the environment hidden), runs its 16 taps from LDS and writes out and L, one
+// dwordx4 each.  VR_UPSAMPLE_GLOBAL_TAPS = 1 builds the form whose taps read the three float4 from global memory instead (no LDS, no barrier): measured, not
+// shipped.  No atomics, no scratch.
+#ifndef VR_UPSAMPLE_GLOBAL_TAPS
+#define VR_UPSAMPLE_GLOBAL_TAPS 0
+#endif
+struct UpsampleTexel { float4 L, ga, gb; };
+template <int32_t F>
+struct UpsampleWindowDev {
+    const UpsampleTexel* win;          // the staged window
+    ScaledTileWindow<F> window;
+    __device__ __forceinline__ void tap(int32_t lx, int32_t ly, float L[4], float g[8]) const {
+        const UpsampleTexel& t = win[window.at(lx, ly)];
+        unpack4(t.L, L); unpack4(t.ga, g); unpack4(t.gb, g + 4);
+    }
+};
+struct UpsampleGlobalDev {
+    const float4* __restrict__ L;
+    const float4* __restrict__ g;
+    int32_t w;
+    __device__ __forceinline__ void tap(int32_t lx, int32_t ly, float Lq[4], float gq[8]) const {
+        const int32_t i = ly * w + lx;
+        unpack4(L[i], Lq); unpack4(g[2 * i], gq); unpack4(g[2 * i + 1], gq + 4);
+    }
+};
+template <int32_t F>
+__global__ void __launch_bounds__(256)
+upsample_kernel(const SceneParams P, const float4* __restrict__ lo_layer, const float4* __restrict__ lo_guide, int32_t w, int32_t h,
+                const float4* __restrict__ hi_features, int32_t rays, const DenoiseSigma sg, float4* __restrict__ out, float4* __restrict__ L) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+#if !VR_UPSAMPLE_GLOBAL_TAPS
+    using Window = ScaledTileWindow<F>;
+    __shared__ UpsampleTexel win[Window::kTexels];
+    const Window window = Window::of((int32_t)blockIdx.x, W);
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    stage_window(win, window, w, h, UpsampleTexel{ zero, zero, zero }, [&](int32_t i) { return UpsampleTexel{ lo_layer[i], lo_guide[2 * i], lo_guide[2 * i + 1] }; });
+#endif
+    if (q.px >= W || q.py >= H) return;
+    const int32_t i = q.py * W + q.px;
+    float f[8], gp[8], B[4], l[4], o[4];
+    unpack4(hi_features[2 * i], f); unpack4(hi_features[2 * i + 1], f + 4);
+    denoise_guide(f, gp);
+    const v3 b = resolve_background(P, q.px, q.py, rays);
+    B[0] = b.x; B[1] = b.y; B[2] = b.z; B[3] = 0.0f;
+#if VR_UPSAMPLE_GLOBAL_TAPS
+    upsample_pixel(UpsampleGlobalDev{ lo_layer, lo_guide, w }, w, h, F, q.px, q.py, gp, B, sg, l, o);
+#else
+    upsample_pixel(UpsampleWindowDev<F>{ win, window }, w, h, F, q.px, q.py, gp, B, sg, l, o);
+#endif
+    out[i] = pack4(o);
+    L[i] = pack4(l);
+}
+void launch_upsample(const SceneParams& P, const float* lo_layer, const float* lo_guide, int32_t w, int32_t h, int32_t f, const float* hi_features, int32_t rays,
+                     const DenoiseSigma& sg, float* out, float* L, hipStream_t stream) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    if (f < kUpsampleMinFactor || f > kUpsampleMaxFactor || W != f * w || H != f * h) throw std::invalid_argument("launch_upsample: the hi frame is not f times the lo frame, f in 2..4");
+    if (w <= 0 || h <= 0 || rays < 1) return;
+    const dim3 grid((unsigned)tile_count(W, H)), block(256);
+#define VR_UPSAMPLE_LAUNCH(F) hipLaunchKernelGGL(upsample_kernel<F>, grid, block, 0, stream, P, reinterpret_cast<const float4*>(lo_layer), reinterpret_cast<const float4*>(lo_guide), \
+                                                 w, h, reinterpret_cast<const float4*>(hi_features), rays, sg, reinterpret_cast<float4*>(out), reinterpret_cast<float4*>(L))
+    if (f == 2) VR_UPSAMPLE_LAUNCH(2); else if (f == 3) VR_UPSAMPLE_LAUNCH(3); else VR_UPSAMPLE_LAUNCH(4);
+#undef VR_UPSAMPLE_LAUNCH
 }
 
 // Adaptive sampling (vr_adaptive.h): e_t of every listed tile.  One workgroup per listed tile; each lane forms e_p of its pixel (-inf outside

@@ -3,7 +3,8 @@
 //   wave-tiled : as four 8x8 sub-tiles, one per wavefront (sub-tile s at (8 (s & 1), 8 (s >> 1)), lane l at (l & 7, l >> 3) in it) -- every per-pixel
 //                kernel, and the path tracer's work units (vr_pathtrace.h make_unit: a unit is one sub-tile x spu samples); or
 //   raster     : thread t at (t & 15, t >> 4) -- the packed tiles of the sharded framebuffer and of its denoiser guides only, whose texel order is wire format.
-// Also here: the window of a tile's pixels plus a halo that a kernel stages in LDS (TileWindow, stage_window), and the wire and table indices below.
+// Also here: the window of a tile's pixels plus a halo that a kernel stages in LDS (TileWindow, stage_window), the same for a tile of a frame F times the staged
+// one's size (ScaledTileWindow), and the wire and table indices below.
 // tests/hostkernel/tiles_host.cpp and guides_host.cpp build this header for the host.
 #pragma once
 
@@ -45,6 +46,19 @@ struct TileWindow {
     VR_HD int32_t at(int32_t px, int32_t py) const { return (py - y0) * kFoot + (px - x0); }
 };
 
+// The window of a hi tile in a frame F times smaller per axis (vr_upsample.h): the lo texels that the 4 x 4 taps of the tile's 16 x 16 hi pixels can touch.  Hi
+// pixel x has its taps at x0 - 1 .. x0 + 2 with x0 = floor((2x + 1 - F) / 2F) (upsample_split), so the window starts one below the x0 of the tile's first
+// pixel and ends two above that of its last: kFoot = ceil(30 / 2F) + 4 texels per axis at most, whatever the tile (12, 9, 8 for F = 2, 3, 4).  Texel order and
+// at() as in TileWindow, in lo coordinates; of() takes the HI frame's width.  tests/hostkernel/upsample_host.cpp checks the arithmetic on the host.
+template <int32_t F>
+struct ScaledTileWindow {
+    static constexpr int32_t kFoot = (29 + 2 * F) / (2 * F) + 4, kTexels = kFoot * kFoot;
+    int32_t x0, y0;
+    VR_HD static int32_t first(int32_t hi) { return (2 * hi + 1 + F) / (2 * F) - 2; }      // x0 - 1 of hi coordinate `hi`, the floor taken of a positive numerator
+    VR_HD static ScaledTileWindow of(int32_t tile, int32_t W) { const int32_t nx = tiles_x(W); return ScaledTileWindow{ first((tile % nx) * 16), first((tile / nx) * 16) }; }
+    VR_HD int32_t at(int32_t lx, int32_t ly) const { return (ly - y0) * kFoot + (lx - x0); }
+};
+
 // The packed denoiser guides of the sharded renderer (pack_guides_kernel / unpack_guides_kernel): kGuidePlanes float4 planes per pixel -- 0 the moments
 // texel, 1 and 2 the two float4 of the pixel's eight features -- plane-major inside a tile slot, thread t in raster_in_tile_pixel order.  The float4
 // index below is WIRE FORMAT: the parts of a sharded renderer exchange these buffers, n_max * kGuidePlanes * 256 float4 per part.
@@ -84,10 +98,11 @@ __device__ __forceinline__ float4 pack4(const float o[4]) { return make_float4(o
 // Fills win[0 .. kTexels) -- LDS of the workgroup of 256 threads that serves the window's tile -- with load(y * W + x) for a texel inside the W x H frame and
 // off_value for any other, then waits for all of them.  EVERY thread of the workgroup calls it, before the `px >= W || py >= H` return of the threads whose
 // pixel lies outside a ragged frame: they stage texels like the others, and the barrier counts them.
-template <int32_t R, class T, class Load>
-__device__ __forceinline__ void stage_window(T* win, const TileWindow<R> window, int32_t W, int32_t H, const T off_value, Load load) {
-    for (int32_t f = (int32_t)threadIdx.x; f < TileWindow<R>::kTexels; f += 256) {
-        const int32_t x = window.x0 + f % TileWindow<R>::kFoot, y = window.y0 + f / TileWindow<R>::kFoot;
+// Window: TileWindow<R>, or ScaledTileWindow<F> with W x H the lo frame.
+template <class Window, class T, class Load>
+__device__ __forceinline__ void stage_window(T* win, const Window window, int32_t W, int32_t H, const T off_value, Load load) {
+    for (int32_t f = (int32_t)threadIdx.x; f < Window::kTexels; f += 256) {
+        const int32_t x = window.x0 + f % Window::kFoot, y = window.y0 + f / Window::kFoot;
         T t = off_value;
         if (x >= 0 && x < W && y >= 0 && y < H) t = load(y * W + x);
         win[f] = t;

@@ -365,6 +365,37 @@ class Renderer:
         _lib.check(self._L.vr_denoised_layer(self._h, out.ctypes.data))
         return out
 
+    def upsample(self, factor=2, rays=2):
+        """Rebuild the frame at `factor` (2..4) times this renderer's size per axis from the layer of the last denoise() / denoise_temporal() with
+        `denoise_layers = 1`, under an expected-value guide of `rays` (1..4) rays per axis marched at the large size (include/volren_amd.h vr_upsample,
+        csrc/vr_upsample.h).  Asynchronous.  Keep the camera and the scene as they were at the denoise call.  Refused without such a layer since the last
+        resize, or with a tile subset set.  Results: upsampled(), upsampled_layer(), upsampled_features()."""
+        _lib.check(self._L.vr_upsample(self._h, int(factor), int(rays)))
+
+    def upsampled_size(self):
+        """(W, H) of the last upsample(); refused before the first one since the last resize."""
+        wh = (C.c_int * 2)()
+        _lib.check(self._L.vr_upsampled_size(self._h, wh))
+        return int(wh[0]), int(wh[1])
+
+    def _upsampled(self, fn, channels):
+        w, h = self.upsampled_size()
+        out = np.empty((h, w, channels), np.float32)
+        _lib.check(fn(self._h, out.ctypes.data))
+        return out
+
+    def upsampled(self):
+        """[H][W][4] float32 at the upsampled size, row 0 = bottom: the frame of the last upsample(), alpha = the exact coverage."""
+        return self._upsampled(self._L.vr_upsampled, 4)
+
+    def upsampled_layer(self):
+        """[H][W][4] float32 at the upsampled size: the scattered light premultiplied by the exact coverage, alpha = the coverage (as denoised_layer())."""
+        return self._upsampled(self._L.vr_upsampled_layer, 4)
+
+    def upsampled_features(self):
+        """[H][W][8] float32 at the upsampled size: the expected-value feature buffer the last upsample() marched, in features()'s layout."""
+        return self._upsampled(self._L.vr_upsampled_features, 8)
+
     # ---- adaptive sampling ----
     def render_adaptive(self, min_spp, max_spp, threshold, sync=True):
         """Per 16x16 tile: min_spp samples, then doubling until the tile's error e_t is below `threshold` or it has max_spp samples

@@ -600,6 +600,16 @@ class Renderer:
         back afterwards: denoised_data() is the composite."""
         return self._r.denoised_layer().reshape(self._r.width, self._r.height, 4)
 
+    def upsample(self, factor=2, rays=2):
+        """Rebuild the frame at `factor` times the renderer's size per axis from the layer of the last denoise() / denoise_temporal() run with
+        `denoise_layers = 1`, under an expected-value guide of `rays` rays per axis at the large size (volren_amd.Renderer.upsample)."""
+        self._r.upsample(factor, rays)
+
+    def upsampled_data(self):
+        """(W, H, 3) float: the colour of the last upsample(), in fbo_data()'s shape at the upsampled size W x H = factor x the renderer's."""
+        w, h = self._r.upsampled_size()
+        return self._r.upsampled()[..., :3].copy().reshape(w, h, 3)
+
     # -- adaptive sampling (no reference counterpart): like render(), from sample 0
     def render_adaptive(self, min_spp, max_spp, threshold):
         """Renders the frame afresh (as render() does), per 16x16 tile from min_spp up to max_spp samples, doubling until the tile's error is
