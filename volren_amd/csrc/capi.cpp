@@ -2,6 +2,7 @@
 #include "../../include/volren_amd.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <filesystem>
@@ -48,9 +49,139 @@ static int guard(const std::function<void()>& fn) {
 }
 static int fail(int code, const char* msg) { g_last_error = msg; return code; }
 #define NEED(r) do { if (!(r)) return fail(VR_ERR_ARG, "null renderer"); } while (0)
+#define NEED_SHARDED(s) do { if (!(s)) return fail(VR_ERR_ARG, "null sharded renderer"); } while (0)
 #define NEED_DEVICE() do { if (vr_device_count() <= 0) return fail(VR_ERR_NO_DEVICE, "no HIP device available (libvolren_amd has no CPU path)"); } while (0)
 
 static void use_device(vr_renderer* r) { VR_HIP(hipSetDevice(r->device)); }
+
+// A whole-frame read-back of the denoiser's data: the renderer, the output, then the device are checked before the renderer is touched.
+static int read_back(vr_renderer* r, float* out, void (vr::RendererHIP::*download)(float*)) {
+    NEED(r);
+    if (!out) return fail(VR_ERR_ARG, "null argument");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); (r->impl.*download)(out); });
+}
+
+namespace {
+using Rn = vr::RendererHIP;
+// The int parameters, one row each: the name, how it is read, how it is written (none: read-only), the accepted range (none where lo > hi) and what
+// a value outside it is answered with.  vr_set_int and vr_get_int are lookups here.  A writer may refuse by itself: the ones that need more than a range.
+struct IntParam {
+    const char* name;
+    int (*get)(Rn&);
+    void (*set)(Rn&, int);
+    int lo, hi;
+    const char* refusal;
+};
+vr::SceneParams next_launch(Rn& R) { vr::SceneParams P; R.fill_params(P); return P; }      // the scene as the current frame's next launch will read it
+int variant_reason(Rn& R) { int why = 0; vr::pathtrace_variant_of(next_launch(R), &why); return why; }
+int kernel_wide(Rn& R) { const vr::SceneParams P = next_launch(R); return (vr::pathtrace_wide_of(R.tuning, P) || vr::pathtrace_variant_of(P, nullptr) >= 2) ? 1 : 0; }
+void set_grid_frame(Rn& R, int v) {
+    if (!R.volume || v < 0 || (size_t)v >= R.volume->n_grid_frames()) throw std::runtime_error("grid_frame_counter out of range");
+    R.volume->grid_frame_counter = (size_t)v;
+}
+#define VR_GET(expr) [](Rn& R) -> int { return expr; }
+#define VR_SET(stmt) [](Rn& R, int v) { stmt; }
+#define VR_INT(field) VR_GET(R.field), VR_SET(R.field = v)
+#define VR_FLAG(field) VR_GET(R.field ? 1 : 0), VR_SET(R.field = v != 0)      // any value but 0 switches it on
+#define VR_ANY 1, 0, nullptr
+#define VR_READ_ONLY(expr) VR_GET(expr), nullptr, VR_ANY
+const IntParam kIntParams[] = {
+    { "sample", VR_GET(R.sample), VR_SET(R.sample = v; R.drop_tile_samples()), VR_ANY },      // a count set by hand is a uniform frame's (include/volren_amd.h: ragged frames)
+    { "sppx", VR_INT(sppx), VR_ANY },
+    { "seed", VR_INT(seed), VR_ANY },
+    { "bounces", VR_INT(bounces), VR_ANY },
+    { "show_environment", VR_FLAG(show_environment), VR_ANY },
+    { "tonemapping", VR_FLAG(tonemapping), VR_ANY },
+    { "integrator", VR_INT(integrator), VR_ANY },
+    { "fast_math", VR_FLAG(fast_math), VR_ANY },
+    { "variance", VR_INT(variance), 0, 1, "variance: 0 (off) or 1 (keep the per-pixel second moments)" },
+    { "denoise_iterations", VR_INT(denoise_iterations), 0, vr::kDenoiseMaxIterations, "denoise_iterations must be in [0, 10]" },
+    { "denoise_moments", VR_GET(R.denoise_moments), VR_SET(R.set_denoise_moments(v)), VR_ANY },
+    { "denoise_resolve", VR_GET(R.denoise_resolve), VR_SET(R.set_denoise_resolve(v)), VR_ANY },
+    { "denoise_layers", VR_GET(R.denoise_layers), VR_SET(R.set_denoise_layers(v)), VR_ANY },
+    { "coalesce_trace", VR_GET(R.coalesce_trace ? 1 : 0), VR_SET(R.flush_pending(); R.coalesce_trace = v != 0), VR_ANY },
+    { "majorant_layout", VR_INT(majorant_layout), -1, 1, "majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)" },
+    { "majorant_blocked", VR_READ_ONLY(next_launch(R).density.maj_blocked) },
+    // which compiled kernel the next launch uses, and what sent it to the run-time one (vr_device.h PathtraceVariantReason)
+    { "kernel_variant", VR_READ_ONLY(vr::pathtrace_variant_of(next_launch(R), nullptr)) },
+    { "kernel_variant_reason", VR_READ_ONLY(variant_reason(R)) },
+    { "tf_float_atlas", VR_FLAG(tf_float_atlas), VR_ANY },
+    { "wide_addressing", VR_INT(tuning.wide_addressing), 0, 1, "wide_addressing: 0 (by the tables' sizes), 1 (always the kernels with 64-bit gather addresses)" },
+    // the next launch's kernel forms 64-bit gather addresses: forced, a table of 4 GiB or more, or a variant that always does (2, 3, 4)
+    { "kernel_wide", VR_READ_ONLY(kernel_wide(R)) },
+    { "env_div_safe", VR_READ_ONLY(R.environment && R.environment->cdf_div_safe ? 1 : 0) },      // the environment's warp table passed env_cdf_kernel's check (vr_math.h div_core)
+    { "env_compact", VR_READ_ONLY(R.environment && R.environment->envmap_rgbe ? 1 : 0) },      // the path tracer fetches the map's texels as RGBE dwords (vr_scene.h SceneParams::env_rgbe)
+    { "pending_samples", VR_READ_ONLY(R.pending_samples()) },
+    { "gpu_encoder", VR_FLAG(gpu_encoder), VR_ANY },
+    { "sample_pool_mb", VR_GET((int)(R.sample_pool_bytes >> 20)), VR_SET(R.sample_pool_bytes = (size_t)v << 20), 16, 65536,
+      "sample_pool_mb must be in [16, 65536] (item indices of a sub-launch are 32-bit: < 2^32 RGBA32F items)" },
+    { "seed_table_mb", VR_GET(R.seed_table_budget_mb()), VR_SET(R.seed_table_mb = v), -1, Rn::kSeedTableMaxMb,      // reads back the budget -1 resolves to
+      "seed_table_mb must be in [0, 8192] (0 = no table), or -1 for the default min(4096, sample_pool_mb / 4)" },
+    { "seed_table_max_samples", VR_INT(seed_table_max_samples), 0, INT_MAX, "seed_table_max_samples must be >= 0 (0 = as many as seed_table_mb holds)" },
+    { "seed_table_samples", VR_READ_ONLY(R.seed_table_samples()) },
+    { "seed_table_fills", VR_READ_ONLY(R.seed_table_fills()) },
+    { "launch_target_ms", VR_INT(launch_target_ms), 0, INT_MAX, "launch_target_ms must be >= 0 (0 = no sizing by time)" },
+    { "expected_skip", VR_INT(expected_skip), 0, 1, "expected_skip: 0 (march every step) or 1 (drop the steps of empty space by the clear-distance table)" },
+    { "expected_stats", VR_INT(expected_stats), 0, 1, "expected_stats: 0 (off) or 1 (the expected-value passes count their work)" },
+    { "order_tiles", VR_INT(order_tiles), 0, 2, "order_tiles: 0 (never), 1 (tile subsets), 2 (always)" },
+    { "grid_frame_counter", VR_GET(R.volume ? (int)R.volume->grid_frame_counter : 0), set_grid_frame, VR_ANY },
+    { "n_grid_frames", VR_READ_ONLY(R.volume ? (int)R.volume->n_grid_frames() : 0) },
+    { "last_launches", VR_READ_ONLY(R.last_launches) },
+    { "adaptive_rounds", VR_READ_ONLY(R.adaptive_rounds) },
+    { "width", VR_READ_ONLY(R.resolution.x) },
+    { "height", VR_READ_ONLY(R.resolution.y) },
+};
+#undef VR_GET
+#undef VR_SET
+#undef VR_INT
+#undef VR_FLAG
+#undef VR_ANY
+#undef VR_READ_ONLY
+// the row of `name`; `writable`: a read-only name is as unknown to vr_set_int as any other
+const IntParam& int_param(const char* name, bool writable) {
+    for (const IntParam& p : kIntParams)
+        if (!strcmp(p.name, name) && (p.set || !writable)) return p;
+    throw std::runtime_error(std::string("unknown int parameter: ") + name);
+}
+
+// The float parameters, one row each: where the values live, how many they are and, where they have a range, the check vr_set_float runs on the
+// caller's values.  The check comes before the count is compared, so it sees the caller's count: denoise_sigma answers a wrong one in its own words.
+struct FloatField { float* ptr; int count; void (*check)(const float* values, int count) = nullptr; };
+FloatField float_field(vr::RendererHIP& R, const std::string& n) {
+    if (n == "tonemap_exposure") return { &R.tonemap_exposure, 1 };
+    if (n == "tonemap_gamma") return { &R.tonemap_gamma, 1 };
+    if (n == "albedo") return { &R.albedo.x, 3 };
+    if (n == "phase") return { &R.phase, 1 };
+    if (n == "density_scale") return { &R.density_scale, 1 };
+    if (n == "emission_scale") return { &R.emission_scale, 1 };
+    if (n == "vol_clip_min") return { &R.vol_clip_min.x, 3 };
+    if (n == "vol_clip_max") return { &R.vol_clip_max.x, 3 };
+    if (n == "cam_pos") return { &R.camera.pos.x, 3 };
+    if (n == "cam_dir") return { &R.camera.dir.x, 3 };
+    if (n == "cam_up") return { &R.camera.up.x, 3 };
+    if (n == "cam_fov") return { &R.camera.fov_degree, 1 };
+    if (n == "env_strength") { if (!R.environment) throw std::runtime_error("no environment"); return { &R.environment->strength, 1 }; }
+    if (n == "env_transform") { if (!R.environment) throw std::runtime_error("no environment"); return { R.environment->transform.m, 9 }; }
+    if (n == "tf_window_left") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_left, 1 }; }
+    if (n == "tf_window_width") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_width, 1 }; }
+    if (n == "volume_transform") { if (!R.volume) throw std::runtime_error("no volume"); return { R.volume->transform.m, 16 }; }
+    if (n == "denoise_sigma") return { R.denoise_sigma, 5, [](const float* values, int count) {      // colour, normal, depth, coverage, albedo: each in [2^-60, 2^60] (vr_denoise.h)
+        if (count != 5) throw std::runtime_error("denoise_sigma takes 5 values (colour, normal, depth, coverage, albedo)");
+        for (int i = 0; i < 5; ++i)
+            if (!(values[i] >= vr::kDenoiseSigmaMin && values[i] <= vr::kDenoiseSigmaMax))
+                throw std::runtime_error("denoise_sigma: every value must be in [2^-60, 2^60]");
+    } };
+    if (n == "denoise_alpha") return { &R.denoise_alpha, 1, [](const float* values, int count) {      // vr_temporal.h
+        if (count == 1 && !(values[0] >= vr::kTemporalAlphaMin && values[0] <= vr::kTemporalAlphaMax)) throw std::runtime_error("denoise_alpha must be in [2^-20, 1]");
+    } };
+    if (n == "denoise_reject") return { &R.denoise_reject, 1, [](const float* values, int count) {
+        if (count == 1 && !(values[0] == 0.0f || (values[0] >= vr::kTemporalRejectMin && values[0] <= vr::kTemporalRejectMax)))
+            throw std::runtime_error("denoise_reject must be 0 (off) or in [2^-10, 2^20]");
+    } };
+    throw std::runtime_error("unknown float parameter: " + n);
+}
+}  // namespace
 
 extern "C" {
 
@@ -279,130 +410,17 @@ int vr_set_int(vr_renderer* r, const char* name, int v) {
     NEED(r);
     if (!name) return fail(VR_ERR_ARG, "null name");
     return guard([&] {
-        auto& R = r->impl;
-        const std::string n = name;
-        if (n == "sample") { R.sample = v; R.drop_tile_samples(); }      // a count set by hand is a uniform frame's (include/volren_amd.h: ragged frames)
-        else if (n == "sppx") R.sppx = v;
-        else if (n == "seed") R.seed = v;
-        else if (n == "bounces") R.bounces = v;
-        else if (n == "show_environment") R.show_environment = v != 0;
-        else if (n == "tonemapping") R.tonemapping = v != 0;
-        else if (n == "integrator") R.integrator = v;
-        else if (n == "fast_math") R.fast_math = v != 0;
-        else if (n == "variance") { if (v < 0 || v > 1) throw std::runtime_error("variance: 0 (off) or 1 (keep the per-pixel second moments)"); R.variance = v; }
-        else if (n == "denoise_iterations") {
-            if (v < 0 || v > vr::kDenoiseMaxIterations) throw std::runtime_error("denoise_iterations must be in [0, 10]");
-            R.denoise_iterations = v;
-        }
-        else if (n == "denoise_moments") R.set_denoise_moments(v);
-        else if (n == "denoise_resolve") R.set_denoise_resolve(v);
-        else if (n == "denoise_layers") R.set_denoise_layers(v);
-        else if (n == "coalesce_trace") { R.flush_pending(); R.coalesce_trace = v != 0; }
-        else if (n == "majorant_layout") { if (v < -1 || v > 1) throw std::runtime_error("majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)"); R.majorant_layout = v; }
-        else if (n == "tf_float_atlas") R.tf_float_atlas = v != 0;
-        else if (n == "wide_addressing") { if (v < 0 || v > 1) throw std::runtime_error("wide_addressing: 0 (by the tables' sizes), 1 (always the kernels with 64-bit gather addresses)"); R.tuning.wide_addressing = v; }
-        else if (n == "gpu_encoder") R.gpu_encoder = v != 0;
-        else if (n == "sample_pool_mb") { if (v < 16 || v > 65536) throw std::runtime_error("sample_pool_mb must be in [16, 65536] (item indices of a sub-launch are 32-bit: < 2^32 RGBA32F items)"); R.sample_pool_bytes = (size_t)v << 20; }
-        else if (n == "seed_table_mb") {
-            if (v < -1 || v > vr::RendererHIP::kSeedTableMaxMb) throw std::runtime_error("seed_table_mb must be in [0, 8192] (0 = no table), or -1 for the default min(4096, sample_pool_mb / 4)");
-            R.seed_table_mb = v;
-        }
-        else if (n == "seed_table_max_samples") { if (v < 0) throw std::runtime_error("seed_table_max_samples must be >= 0 (0 = as many as seed_table_mb holds)"); R.seed_table_max_samples = v; }
-        else if (n == "launch_target_ms") { if (v < 0) throw std::runtime_error("launch_target_ms must be >= 0 (0 = no sizing by time)"); R.launch_target_ms = v; }
-        else if (n == "expected_skip") { if (v < 0 || v > 1) throw std::runtime_error("expected_skip: 0 (march every step) or 1 (drop the steps of empty space by the clear-distance table)"); R.expected_skip = v; }
-        else if (n == "expected_stats") { if (v < 0 || v > 1) throw std::runtime_error("expected_stats: 0 (off) or 1 (the expected-value passes count their work)"); R.expected_stats = v; }
-        else if (n == "order_tiles") { if (v < 0 || v > 2) throw std::runtime_error("order_tiles: 0 (never), 1 (tile subsets), 2 (always)"); R.order_tiles = v; }
-        else if (n == "grid_frame_counter") {
-            if (!R.volume || v < 0 || (size_t)v >= R.volume->n_grid_frames()) throw std::runtime_error("grid_frame_counter out of range");
-            R.volume->grid_frame_counter = (size_t)v;
-        } else throw std::runtime_error("unknown int parameter: " + n);
+        const IntParam& p = int_param(name, true);
+        if (p.lo <= p.hi && (v < p.lo || v > p.hi)) throw std::runtime_error(p.refusal);
+        p.set(r->impl, v);
     });
 }
 
 int vr_get_int(vr_renderer* r, const char* name, int* v) {
     NEED(r);
     if (!name || !v) return fail(VR_ERR_ARG, "null argument");
-    return guard([&] {
-        auto& R = r->impl;
-        const std::string n = name;
-        if (n == "sample") *v = R.sample;
-        else if (n == "sppx") *v = R.sppx;
-        else if (n == "seed") *v = R.seed;
-        else if (n == "bounces") *v = R.bounces;
-        else if (n == "show_environment") *v = R.show_environment ? 1 : 0;
-        else if (n == "tonemapping") *v = R.tonemapping ? 1 : 0;
-        else if (n == "integrator") *v = R.integrator;
-        else if (n == "fast_math") *v = R.fast_math ? 1 : 0;
-        else if (n == "variance") *v = R.variance;
-        else if (n == "denoise_iterations") *v = R.denoise_iterations;
-        else if (n == "denoise_moments") *v = R.denoise_moments;
-        else if (n == "denoise_resolve") *v = R.denoise_resolve;
-        else if (n == "denoise_layers") *v = R.denoise_layers;
-        else if (n == "coalesce_trace") *v = R.coalesce_trace ? 1 : 0;
-        else if (n == "majorant_layout") *v = R.majorant_layout;
-        else if (n == "majorant_blocked") {          // what the current frame's next launch will use
-            vr::SceneParams P; R.fill_params(P); *v = P.density.maj_blocked;
-        }
-        else if (n == "kernel_variant" || n == "kernel_variant_reason") {      // which compiled kernel the next launch uses, and what sent it to the run-time one (vr_device.h PathtraceVariantReason)
-            vr::SceneParams P; R.fill_params(P);
-            int why = 0; const int variant = vr::pathtrace_variant_of(P, &why);
-            *v = n == "kernel_variant" ? variant : why;
-        }
-        else if (n == "wide_addressing") *v = R.tuning.wide_addressing;
-        else if (n == "kernel_wide") {               // the next launch's kernel forms 64-bit gather addresses: forced, a table of 4 GiB or more, or a variant that always does (2, 3, 4)
-            vr::SceneParams P; R.fill_params(P);
-            *v = (vr::pathtrace_wide_of(R.tuning, P) || vr::pathtrace_variant_of(P, nullptr) >= 2) ? 1 : 0;
-        }
-        else if (n == "env_div_safe") *v = R.environment && R.environment->cdf_div_safe ? 1 : 0;      // the environment's warp table passed env_cdf_kernel's check (vr_math.h div_core)
-        else if (n == "env_compact") *v = R.environment && R.environment->envmap_rgbe ? 1 : 0;      // the path tracer fetches the map's texels as RGBE dwords (vr_scene.h SceneParams::env_rgbe)
-        else if (n == "pending_samples") *v = R.pending_samples();
-        else if (n == "tf_float_atlas") *v = R.tf_float_atlas ? 1 : 0;
-        else if (n == "gpu_encoder") *v = R.gpu_encoder ? 1 : 0;
-        else if (n == "sample_pool_mb") *v = (int)(R.sample_pool_bytes >> 20);
-        else if (n == "seed_table_mb") *v = R.seed_table_budget_mb();
-        else if (n == "seed_table_max_samples") *v = R.seed_table_max_samples;
-        else if (n == "seed_table_samples") *v = R.seed_table_samples();
-        else if (n == "seed_table_fills") *v = R.seed_table_fills();
-        else if (n == "launch_target_ms") *v = R.launch_target_ms;
-        else if (n == "expected_skip") *v = R.expected_skip;
-        else if (n == "expected_stats") *v = R.expected_stats;
-        else if (n == "order_tiles") *v = R.order_tiles;
-        else if (n == "grid_frame_counter") *v = R.volume ? (int)R.volume->grid_frame_counter : 0;
-        else if (n == "n_grid_frames") *v = R.volume ? (int)R.volume->n_grid_frames() : 0;
-        else if (n == "last_launches") *v = R.last_launches;
-        else if (n == "adaptive_rounds") *v = R.adaptive_rounds;
-        else if (n == "width") *v = R.resolution.x;
-        else if (n == "height") *v = R.resolution.y;
-        else throw std::runtime_error("unknown int parameter: " + n);
-    });
+    return guard([&] { *v = int_param(name, false).get(r->impl); });
 }
-
-namespace {
-struct FloatField { float* ptr; int count; };
-FloatField float_field(vr::RendererHIP& R, const std::string& n) {
-    if (n == "tonemap_exposure") return { &R.tonemap_exposure, 1 };
-    if (n == "tonemap_gamma") return { &R.tonemap_gamma, 1 };
-    if (n == "albedo") return { &R.albedo.x, 3 };
-    if (n == "phase") return { &R.phase, 1 };
-    if (n == "density_scale") return { &R.density_scale, 1 };
-    if (n == "emission_scale") return { &R.emission_scale, 1 };
-    if (n == "vol_clip_min") return { &R.vol_clip_min.x, 3 };
-    if (n == "vol_clip_max") return { &R.vol_clip_max.x, 3 };
-    if (n == "cam_pos") return { &R.camera.pos.x, 3 };
-    if (n == "cam_dir") return { &R.camera.dir.x, 3 };
-    if (n == "cam_up") return { &R.camera.up.x, 3 };
-    if (n == "cam_fov") return { &R.camera.fov_degree, 1 };
-    if (n == "env_strength") { if (!R.environment) throw std::runtime_error("no environment"); return { &R.environment->strength, 1 }; }
-    if (n == "env_transform") { if (!R.environment) throw std::runtime_error("no environment"); return { R.environment->transform.m, 9 }; }
-    if (n == "tf_window_left") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_left, 1 }; }
-    if (n == "tf_window_width") { if (!R.transferfunc) throw std::runtime_error("no transfer function"); return { &R.transferfunc->window_width, 1 }; }
-    if (n == "volume_transform") { if (!R.volume) throw std::runtime_error("no volume"); return { R.volume->transform.m, 16 }; }
-    if (n == "denoise_sigma") return { R.denoise_sigma, 5 };
-    if (n == "denoise_alpha") return { &R.denoise_alpha, 1 };
-    if (n == "denoise_reject") return { &R.denoise_reject, 1 };
-    throw std::runtime_error("unknown float parameter: " + n);
-}
-}  // namespace
 
 int vr_set_float(vr_renderer* r, const char* name, const float* values, int count) {
     NEED(r);
@@ -417,17 +435,8 @@ int vr_set_float(vr_renderer* r, const char* name, const float* values, int coun
             return;
         }
         if (n == "albedo" && count == 1) { R.albedo = vr::vec3(values[0]); return; }      // main.cpp:371-372
-        if (n == "denoise_sigma") {                 // colour, normal, depth, coverage, albedo: each in [2^-60, 2^60] (vr_denoise.h)
-            if (count != 5) throw std::runtime_error("denoise_sigma takes 5 values (colour, normal, depth, coverage, albedo)");
-            for (int i = 0; i < 5; ++i)
-                if (!(values[i] >= vr::kDenoiseSigmaMin && values[i] <= vr::kDenoiseSigmaMax))
-                    throw std::runtime_error("denoise_sigma: every value must be in [2^-60, 2^60]");
-        }
-        if (n == "denoise_alpha" && count == 1 && !(values[0] >= vr::kTemporalAlphaMin && values[0] <= vr::kTemporalAlphaMax))      // vr_temporal.h
-            throw std::runtime_error("denoise_alpha must be in [2^-20, 1]");
-        if (n == "denoise_reject" && count == 1 && !(values[0] == 0.0f || (values[0] >= vr::kTemporalRejectMin && values[0] <= vr::kTemporalRejectMax)))
-            throw std::runtime_error("denoise_reject must be 0 (off) or in [2^-10, 2^20]");
         const FloatField f = float_field(R, n);
+        if (f.check) f.check(values, count);
         if (count != f.count) throw std::runtime_error("wrong value count for " + n);
         memcpy(f.ptr, values, sizeof(float) * (size_t)count);
     });
@@ -501,18 +510,8 @@ int vr_expected_clear_table(vr_renderer* r, uint8_t* out, int cells[3]) {
     NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.expected_clear_table(out, cells); });
 }
-int vr_features(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_features(out); });
-}
-int vr_variance(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_variance(out); });
-}
+int vr_features(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_features); }
+int vr_variance(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_variance); }
 int vr_denoise(vr_renderer* r) {
     NEED(r);
     NEED_DEVICE();
@@ -533,18 +532,8 @@ int vr_denoise_history(vr_renderer* r, float* rgba_out, float* var_out, float* l
     NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.download_history(rgba_out, var_out, length_out); });
 }
-int vr_denoise_reject_stat(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_reject_stat(out); });
-}
-int vr_denoise_history_moments(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_history_moments(out); });
-}
+int vr_denoise_reject_stat(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_reject_stat); }
+int vr_denoise_history_moments(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_history_moments); }
 // (the refusals read host state only: they come before the device is asked for)
 int vr_resolve(vr_renderer* r) {
     NEED(r);
@@ -552,24 +541,9 @@ int vr_resolve(vr_renderer* r) {
     NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.resolve(); });
 }
-int vr_resolved(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_resolved(out); });
-}
-int vr_resolve_background(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_resolve_background(out); });
-}
-int vr_denoised_layer(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_denoised_layer(out); });
-}
+int vr_resolved(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_resolved); }
+int vr_resolve_background(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_resolve_background); }
+int vr_denoised_layer(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_denoised_layer); }
 int vr_upsample(vr_renderer* r, int factor, int rays) {
     NEED(r);
     if (factor < 2 || factor > 4) return fail(VR_ERR_ARG, "vr_upsample: factor must be 2..4");
@@ -577,36 +551,16 @@ int vr_upsample(vr_renderer* r, int factor, int rays) {
     NEED_DEVICE();
     return guard([&] { use_device(r); r->impl.upsample(factor, rays); });
 }
-int vr_upsampled(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_upsampled(out); });
-}
-int vr_upsampled_layer(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_upsampled_layer(out); });
-}
-int vr_upsampled_features(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_upsampled_features(out); });
-}
+int vr_upsampled(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_upsampled); }
+int vr_upsampled_layer(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_upsampled_layer); }
+int vr_upsampled_features(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_upsampled_features); }
 int vr_upsampled_size(vr_renderer* r, int wh[2]) {
     NEED(r);
     if (!wh) return fail(VR_ERR_ARG, "null argument");
     NEED_DEVICE();
     return guard([&] { r->impl.upsampled_size(wh); });
 }
-int vr_denoised(vr_renderer* r, float* out) {
-    NEED(r);
-    if (!out) return fail(VR_ERR_ARG, "null argument");
-    NEED_DEVICE();
-    return guard([&] { use_device(r); r->impl.download_denoised(out); });
-}
+int vr_denoised(vr_renderer* r, float* out) { return read_back(r, out, &vr::RendererHIP::download_denoised); }
 // adaptive sampling: the arguments, then the device, are checked before the renderer is touched
 int vr_render_adaptive(vr_renderer* r, int min_spp, int max_spp, float threshold) {
     NEED(r);
@@ -748,36 +702,36 @@ vr_renderer* vr_sharded_part(vr_sharded* s, int i) { return (s && i >= 0 && i < 
 const char* vr_sharded_transport(vr_sharded* s) { return s ? s->transport.c_str() : ""; }
 const char* vr_sharded_collective(vr_sharded* s) { return s ? s->collective.c_str() : ""; }
 int vr_sharded_reset(vr_sharded* s) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->reset(); });
 }
 int vr_sharded_render(vr_sharded* s, int spp) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->render(spp); });
 }
 int vr_sharded_render_features(vr_sharded* s, int spp) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->render_features(spp); });
 }
 int vr_sharded_render_features_expected(vr_sharded* s, int rays) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     if (rays < 1 || rays > vr::kExpectedMaxRays) return fail(VR_ERR_ARG, "vr_sharded_render_features_expected: rays must be 1..4");
     return guard([&] { s->impl->render_features_expected(rays); });
 }
 int vr_sharded_gather_guides(vr_sharded* s) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->gather_guides(); });
 }
 int vr_sharded_denoise(vr_sharded* s) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->denoise(); });
 }
 int vr_sharded_denoise_temporal(vr_sharded* s) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->denoise_temporal(); });
 }
 int vr_sharded_synchronize(vr_sharded* s) {
-    if (!s) return fail(VR_ERR_ARG, "null sharded renderer");
+    NEED_SHARDED(s);
     return guard([&] { s->impl->synchronize(); });
 }
 

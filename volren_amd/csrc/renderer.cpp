@@ -1114,7 +1114,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     DeviceBuffer* const result = layers ? sized_.ly_filtered.get() : sized_.denoised.get();
     launch_denoise_prepare(sized_.moments->as<float>(), sized_.features->as<float>(), W, H, sample, vscale, counts, sized_.dn_var[0]->as<float>(), sized_.dn_guide->as<float>(), stream);
     VR_HIP(hipGetLastError());
-    const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
+    const DenoiseSigma sg = sigma();
     const DeviceBuffer* first = frame;                // what iteration 0 reads
     if (temporal) {
         TemporalCamera cur;
@@ -1159,12 +1159,22 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
 
 void RendererHIP::drop_history() { sized_.hist = Sized::History{}; }
 
-void RendererHIP::set_denoise_moments(int v) {
-    if (v != 0 && v != 1) throw std::runtime_error("denoise_moments: 0 (the frames' sample variance) or 1 (luminance moments kept in the history)");
-    if (v == denoise_moments) return;
+// The switches that decide what the history holds: 0 or 1, and a change drops the history.
+void RendererHIP::set_history_switch(int& field, int v, const char* refusal) {
+    if (v != 0 && v != 1) throw std::runtime_error(refusal);
+    if (v == field) return;
     flush_pending();
     drop_history();
-    denoise_moments = v;
+    field = v;
+}
+void RendererHIP::set_denoise_moments(int v) {
+    set_history_switch(denoise_moments, v, "denoise_moments: 0 (the frames' sample variance) or 1 (luminance moments kept in the history)");
+}
+void RendererHIP::set_denoise_resolve(int v) {
+    set_history_switch(denoise_resolve, v, "denoise_resolve: 0 (the filter starts from the framebuffer) or 1 (from the frame resolved against the expected coverage)");
+}
+void RendererHIP::set_denoise_layers(int v) {
+    set_history_switch(denoise_layers, v, "denoise_layers: 0 (the filter runs on the frame) or 1 (on the scattered layer, the background of the expected coverage put back afterwards)");
 }
 
 // The control variate on the expected coverage (vr_resolve.h): prepare (B, P) and resolve, two launches on the whole frame.
@@ -1200,22 +1210,6 @@ void RendererHIP::download_resolve_background(float* rgba) {
     download_whole(sized_.resolved ? sized_.rs_bg : nullptr, rgba, "resolve_background: no resolve since the last resize (call resolve first)");
 }
 
-void RendererHIP::set_denoise_resolve(int v) {
-    if (v != 0 && v != 1) throw std::runtime_error("denoise_resolve: 0 (the filter starts from the framebuffer) or 1 (from the frame resolved against the expected coverage)");
-    if (v == denoise_resolve) return;
-    flush_pending();
-    drop_history();
-    denoise_resolve = v;
-}
-
-void RendererHIP::set_denoise_layers(int v) {
-    if (v != 0 && v != 1) throw std::runtime_error("denoise_layers: 0 (the filter runs on the frame) or 1 (on the scattered layer, the background of the expected coverage put back afterwards)");
-    if (v == denoise_layers) return;
-    flush_pending();
-    drop_history();
-    denoise_layers = v;
-}
-
 void RendererHIP::download_denoised_layer(float* rgba) {
     download_whole(sized_.layer_valid ? sized_.layer : nullptr, rgba, "denoised_layer: no denoise with denoise_layers = 1 since the last resize");
 }
@@ -1238,7 +1232,7 @@ void RendererHIP::upsample(int factor, int rays) {
     ensure_buffer(sized_.up_out, px * 4 * sizeof(float));
     ensure_buffer(sized_.up_layer, px * 4 * sizeof(float));
     launch_expected(P, nullptr, tile_count(W, H), rays, sized_.up_features->as<float>());
-    const DenoiseSigma sg{ denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] };
+    const DenoiseSigma sg = sigma();
     launch_upsample(P, sized_.layer->as<float>(), sized_.dn_guide->as<float>(), w, h, factor, sized_.up_features->as<float>(), rays, sg, sized_.up_out->as<float>(),
                     sized_.up_layer->as<float>(), stream);
     VR_HIP(hipGetLastError());

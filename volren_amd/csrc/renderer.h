@@ -386,6 +386,8 @@ private:
     } sized_;
     void download_whole(const DeviceBufferPtr& b, float* out, const char* absent);      // throws `absent` when b is null; else flushes and copies all of b
     void run_resolve();                                       // resolve()'s launches, after check_resolve
+    void set_history_switch(int& field, int v, const char* refusal);      // the body of set_denoise_moments / _resolve / _layers, each with its own refusal
+    DenoiseSigma sigma() const { return { denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] }; }      // denoise_sigma as the kernels take it
     DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
     bool expected_stats_valid_ = false;                // ... which that pass filled
     ClearTable clear_table_of(BrickGridHIP& g, const GridView& view);      // the grid's table, built on `stream` if it has none

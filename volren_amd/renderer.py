@@ -10,6 +10,8 @@ _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemap
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
                "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
                "expected_skip", "expected_stats")
+_READ_ONLY_INT_FIELDS = ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
+                         "kernel_wide", "adaptive_rounds", "seed_table_samples", "seed_table_fills")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
@@ -60,11 +62,9 @@ class Renderer:
         return v.value
 
     def __getattr__(self, name):
-        if name in _INT_FIELDS or name in ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason", "kernel_wide",
-                                              "adaptive_rounds", "seed_table_samples", "seed_table_fills"):
-            v = C.c_int()
-            _lib.check(self._L.vr_get_int(self._h, name.encode(), C.byref(v)))
-            return bool(v.value) if name in ("show_environment", "tonemapping") else v.value
+        if name in _INT_FIELDS or name in _READ_ONLY_INT_FIELDS:
+            v = self.get_int(name)
+            return bool(v) if name in ("show_environment", "tonemapping") else v
         if name in _FLOAT_FIELDS:
             n = _FLOAT_FIELDS[name]
             buf = (C.c_float * n)()
@@ -219,11 +219,16 @@ class Renderer:
         _lib.check(self._L.vr_last_pathtrace_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def _read_back(self, fn, *trailing, size=None):
+        """[H][W] + trailing float32 filled by fn(handle, pointer); size: (W, H) where it is not the renderer's."""
+        w, h = size or (self.width, self.height)
+        out = np.empty((h, w) + trailing, np.float32)
+        _lib.check(fn(self._h, out.ctypes.data))
+        return out
+
     def framebuffer(self):
         """RGBA32F [H][W][4], row 0 = bottom (GL order)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_framebuffer(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_framebuffer, 4)
 
     def fbo_data(self):
         """float RGB of the framebuffer (bindings.cpp:141-148)."""
@@ -277,15 +282,11 @@ class Renderer:
 
     def features(self):
         """[H][W][8] float32, row 0 = bottom: albedo.rgb, coverage, normal.xyz, depth."""
-        out = np.empty((self.height, self.width, 8), np.float32)
-        _lib.check(self._L.vr_features(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_features, 8)
 
     def variance(self):
         """[H][W][4] float32, row 0 = bottom: unbiased per-channel variance of samples 1..sample (needs `variance = 1` for all of them)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_variance(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_variance, 4)
 
     # ---- denoiser ----
     def denoise(self, sync=True):
@@ -313,17 +314,13 @@ class Renderer:
     def denoise_reject_stat(self):
         """[H][W] float32, row 0 = bottom: the rejection statistic T of the last denoise_temporal() (a pixel was rejected iff not T <= `denoise_reject`),
         -1 where the pixel had no history.  Needs `denoise_reject` > 0 at that call."""
-        out = np.empty((self.height, self.width), np.float32)
-        _lib.check(self._L.vr_denoise_reject_stat(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_denoise_reject_stat)
 
     def denoise_history_moments(self):
         """[H][W][4] float32, row 0 = bottom: the history's moment records (m1, m2, E, S) -- integrated first and second moments of the frames' luminance,
         the sum of squared blend weights, the variance of one frame's luminance.  Needs a history written with `denoise_moments = 1` (a change of that
         field drops the history)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_denoise_history_moments(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_denoise_history_moments, 4)
 
     def denoise_history_reset(self):
         """Drops the history: the next denoise_temporal() starts afresh."""
@@ -331,9 +328,7 @@ class Renderer:
 
     def denoised(self):
         """[H][W][4] float32, row 0 = bottom: the last denoise()'s or denoise_temporal()'s result, linear (not tonemapped)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_denoised(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_denoised, 4)
 
     # ---- control variate on the expected coverage ----
     def resolve(self, sync=True):
@@ -346,24 +341,18 @@ class Renderer:
 
     def resolved(self):
         """[H][W][4] float32, row 0 = bottom: the last resolve()'s result, linear (not tonemapped), alpha = the expected coverage."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_resolved(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_resolved, 4)
 
     def resolve_background(self):
         """Test hook (vr_resolve_background): [H][W][4] float32, row 0 = bottom: the environment radiance B behind every pixel as the last resolve()
         formed it (0 while `show_environment` is 0), alpha 0."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_resolve_background(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_resolve_background, 4)
 
     def denoised_layer(self):
         """[H][W][4] float32, row 0 = bottom: the layer of the last denoise() / denoise_temporal() with `denoise_layers = 1` (include/volren_amd.h
         vr_denoised_layer): the filtered scattered light premultiplied by the exact coverage, alpha = the coverage; over a background B' it composites
         as (1 - a) B' + rgb.  Refused before the first such call since the last resize."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_denoised_layer(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_denoised_layer, 4)
 
     def upsample(self, factor=2, rays=2):
         """Rebuild the frame at `factor` (2..4) times this renderer's size per axis from the layer of the last denoise() / denoise_temporal() with
@@ -379,10 +368,7 @@ class Renderer:
         return int(wh[0]), int(wh[1])
 
     def _upsampled(self, fn, channels):
-        w, h = self.upsampled_size()
-        out = np.empty((h, w, channels), np.float32)
-        _lib.check(fn(self._h, out.ctypes.data))
-        return out
+        return self._read_back(fn, channels, size=self.upsampled_size())
 
     def upsampled(self):
         """[H][W][4] float32 at the upsampled size, row 0 = bottom: the frame of the last upsample(), alpha = the exact coverage."""
@@ -428,9 +414,7 @@ class Renderer:
         _lib.check(self._L.vr_draw(self._h))
 
     def display(self):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        _lib.check(self._L.vr_display(self._h, out.ctypes.data))
-        return out
+        return self._read_back(self._L.vr_display, 4)
 
     def save(self, path):
         _lib.check(self._L.vr_save_png(self._h, str(path).encode()))
@@ -496,6 +480,17 @@ class Renderer:
         out = np.empty(n, np.float32)
         _lib.check(self._L.vr_get_impmap(self._h, out.ctypes.data, n))
         return out
+
+
+def _part0(name, settable, doc):
+    """A ShardedRenderer attribute that reads part 0's field `name`; settable: writing it writes every part's."""
+    def fget(self):
+        return getattr(self.parts[0], name)
+
+    def fset(self, value):
+        for p in self.parts:
+            setattr(p, name, value)
+    return property(fget, fset if settable else None, doc=doc)
 
 
 class ShardedRenderer:
@@ -572,16 +567,9 @@ class ShardedRenderer:
         if sync:
             self.synchronize()
 
-    @property
-    def expected_skip(self):
+    expected_skip = _part0("expected_skip", True,
         """Whether the parts' expected-value passes drop the steps of empty space (Renderer.expected_skip): part 0's field; setting it sets every part's.
-        Every part builds the clear-distance table of its own copy of the grid."""
-        return self.parts[0].expected_skip
-
-    @expected_skip.setter
-    def expected_skip(self, value):
-        for p in self.parts:
-            p.expected_skip = value
+        Every part builds the clear-distance table of its own copy of the grid.""")
 
     def gather_guides(self):
         """Every part's moments and features of its tiles into `parts[0]` (vr_sharded_gather_guides): one exchange, asynchronous."""
@@ -619,43 +607,25 @@ class ShardedRenderer:
     def denoise_history_reset(self):
         self.parts[0].denoise_history_reset()
 
-    @property
-    def denoise_reject(self):
-        """The rejection threshold the filter runs with: part 0's (set it on `parts[0]`, or on every part with `each`)."""
-        return self.parts[0].denoise_reject
+    denoise_reject = _part0("denoise_reject", False,
+        """The rejection threshold the filter runs with: part 0's (set it on `parts[0]`, or on every part with `each`).""")
 
     def denoise_reject_stat(self):
         return self.parts[0].denoise_reject_stat()
 
-    @property
-    def denoise_moments(self):
-        """Whether the filter takes its variance from the history's luminance moments: part 0's field (set it on `parts[0]`, or on every part with `each`)."""
-        return self.parts[0].denoise_moments
+    denoise_moments = _part0("denoise_moments", False,
+        """Whether the filter takes its variance from the history's luminance moments: part 0's field (set it on `parts[0]`, or on every part with `each`).""")
 
     def denoise_history_moments(self):
         return self.parts[0].denoise_history_moments()
 
-    @property
-    def denoise_resolve(self):
+    denoise_resolve = _part0("denoise_resolve", True,
         """Whether denoise() / denoise_temporal() start from the frame resolved against the expected coverage (Renderer.resolve): part 0's field, which
-        holds the gathered frame and guide and runs the resolve; setting it sets every part's."""
-        return self.parts[0].denoise_resolve
+        holds the gathered frame and guide and runs the resolve; setting it sets every part's.""")
 
-    @denoise_resolve.setter
-    def denoise_resolve(self, value):
-        for p in self.parts:
-            p.denoise_resolve = value
-
-    @property
-    def denoise_layers(self):
+    denoise_layers = _part0("denoise_layers", True,
         """Whether denoise() / denoise_temporal() filter the scattered layer alone and put the analytic background back (Renderer.denoise_layers): part 0's
-        field, which holds the gathered frame and guide and runs it; setting it sets every part's."""
-        return self.parts[0].denoise_layers
-
-    @denoise_layers.setter
-    def denoise_layers(self, value):
-        for p in self.parts:
-            p.denoise_layers = value
+        field, which holds the gathered frame and guide and runs it; setting it sets every part's.""")
 
     def denoised_layer(self):
         return self.parts[0].denoised_layer()

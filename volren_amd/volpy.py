@@ -403,6 +403,7 @@ def set_context(width=None, height=None, device=None):
 _SCALARS = ("sample", "sppx", "bounces", "seed", "tonemap_exposure", "tonemap_gamma", "tonemapping", "show_environment",
             "phase", "density_scale", "emission_scale", "cam_fov")
 _VEC3S = ("albedo", "vol_clip_min", "vol_clip_max", "cam_pos", "cam_dir", "cam_up")
+_PASS_THROUGH = ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "expected_skip")      # this build's own fields: the inner renderer's, as they are
 
 
 class Renderer:
@@ -424,16 +425,14 @@ class Renderer:
     def __getattr__(self, name):
         if name == "variance":
             return self._r.get_int("variance")
-        if name in ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "expected_skip"):
-            return getattr(self._r, name)
-        if name in _SCALARS:
+        if name in _SCALARS or name in _PASS_THROUGH:
             return getattr(self._r, name)
         if name in _VEC3S:
             return vec3(getattr(self._r, name))
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in _SCALARS or name in ("variance", "denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "expected_skip"):
+        if name in _SCALARS or name in _PASS_THROUGH or name == "variance":
             setattr(self._r, name, value)
         elif name in _VEC3S:
             setattr(self._r, name, np.asarray(vec3(value) if np.ndim(value) == 0 else value, np.float32).reshape(3))
