@@ -56,7 +56,7 @@ def lib(fast_tap=False):
 
 
 # The forms of the lane code the harness compiles: exactly the 14 configurations the device ships (host_kernel.cpp FormCfg, vr_pathtrace.hip Cfg), in the
-# harness's order: (kernel variant, 64-bit gather addresses, transfer function)
+# order of the product's instances (vr_variant.h PathtraceKernel::instance; form = 2 * instance + tf): (kernel variant, 64-bit gather addresses, transfer function)
 FORMS = tuple((variant, wide, tf) for variant, wide in ((0, False), (0, True), (1, False), (1, True), (2, True), (4, True), (3, True)) for tf in (False, True))
 COUNTERS = ("steps", "clean_march", "clean_collide", "general_march", "general_collide")
 HS_MAJ_BLOCKED = 1            # host_scene.h
@@ -79,7 +79,7 @@ def forms_that_ran(fast_tap=False):
 
 def render(orc_renderer, spp, rect=None, fb=None, first_sample=1, fast_tap=False, wide=False, blocked=False):
     """Run the host-compiled product kernel on the scene held by an oracle.binding.OracleRenderer, in the form the product's launch would pick for it
-    (vr_launch.hip pathtrace_variant_of / pathtrace_wide_of).  wide: the 64-bit form of variants 0 and 1 (the product's wide_addressing = 1);
+    (vr_variant.h pathtrace_kernel_of, which the harness calls).  wide: the 64-bit form of variants 0 and 1 (the product's wide_addressing = 1);
     blocked: majorant levels 0-1 in 4x4x4-cell blocks where the product has a kernel for them (majorant_layout = 1: variant 4 instead of 2)."""
     L = lib(fast_tap)
     p = orc_renderer.params()

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../volren_amd/csrc/vr_variant.h"
 #include "host_scene.h"
 
 using namespace vr;
@@ -38,7 +39,7 @@ static void trace_access(const Hot& h, const SceneParams& P) {
 }
 
 // ---- the compiled forms of the lane code: exactly the 14 configurations the device ships (volren_amd/csrc/vr_pathtrace.hip Cfg) -----------------------------------
-// form = 2 * slot + (transfer function ? 1 : 0); slots: 0 variant 0 with 32-bit gather offsets, 1 variant 0 with 64-bit addresses ("wide"), 2 and 3 the same for variant 1,
+// form = 2 * slot + (transfer function ? 1 : 0); slots = the product's instances (vr_variant.h PathtraceKernel::instance): 0 variant 0 with 32-bit gather offsets, 1 variant 0 with 64-bit addresses ("wide"), 2 and 3 the same for variant 1,
 // 4 variant 2, 5 variant 4, 6 variant 3 (the last three always form 64-bit addresses).  What stays out is what only the device's scheduler has: the emission
 // state cached in the hot registers (collide_finish's CACHED) and the LDS stores.
 enum { HK_SLOTS = 7, HK_FORMS = 2 * HK_SLOTS, HK_COUNTERS = 5 };
@@ -60,32 +61,14 @@ struct ColdHost {
     void st(int32_t f, float x) { v[f] = x; }
 };
 
-// Which form serves a scene: vr_launch.hip pathtrace_variant_of / pathtrace_wide_of, restated (that file is device code).  `paired`: the scene's two brick grids
-// share a paired atlas (build_lane_scene below, as RendererHIP::fill_params decides it).
-static int form_of(const SceneParams& P, bool paired, bool force_wide) {
-    const Uniforms& u = P.u;
-    const bool scale_ok = u.vol_density_scale >= 1.0f / 65536.0f && u.vol_density_scale <= 16777216.0f;
-    int slot;
-    if (u.integrator != 0 || !P.env_div_safe || !scale_ok) slot = 6;
-    else if (u.has_emission) slot = (P.density.dense || P.emission.dense || (VR_PAIRED_ATLAS && !paired)) ? 6 : (P.density.maj_blocked ? 5 : 4);
-    else {
-        uint64_t m = grid_largest_table_bytes(P.density, false, u.use_tf != 0);
-        const bool wide = force_wide || m >= (1ull << 32);
-        slot = (P.density.dense ? 2 : 0) + (wide ? 1 : 0);
-    }
-    return 2 * slot + (u.use_tf ? 1 : 0);
-}
-
-// The scene with the views the serving kernel gets (RendererHIP::fill_params): two brick grids of one brick layout under the DDA trackers, with a warp table that
-// passed the division check and a density scale the fixed kernels take, are read from ONE paired atlas -- and only that kernel reads a majorant table whose
-// levels 0-1 are in 4x4x4-cell blocks; for every other scene the table is built linear, whatever the caller asked for.
-static bool build_lane_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
+// The scene with the views the serving kernel gets (RendererHIP::fill_params): two brick grids that can share a paired atlas, in a scene nothing sends to the
+// run-time variant (vr_variant.h), are read from ONE paired atlas -- and only that kernel reads a majorant table whose levels 0-1 are in 4x4x4-cell blocks; for
+// every other scene the table is built linear, whatever the caller asked for.
+static void build_lane_scene(HostScene& S, const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
                              const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim, int flags) {
     build_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
     SceneParams& P = S.P;
-    const bool scale_ok = P.u.vol_density_scale >= 1.0f / 65536.0f && P.u.vol_density_scale <= 16777216.0f;
-    const bool paired = VR_PAIRED_ATLAS && P.u.has_emission && emission && !P.density.dense && !P.emission.dense && P.u.integrator == 0 && P.env_div_safe && scale_ok &&
-                        P.density.nb[0] == P.emission.nb[0] && P.density.nb[1] == P.emission.nb[1] && P.density.nb[2] == P.emission.nb[2];
+    const bool paired = scene_pairs_atlases(P);      // (has_emission without an emission descriptor: the emission view stays as HostScene value-initialised it, all zeros, which pairs with no grid)
     if (!paired && P.density.maj_blocked) build_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags | HS_MAJ_LINEAR);
     if (paired) {
         build_paired_atlas(S.dg, S.eg, S.paired);
@@ -93,7 +76,6 @@ static bool build_lane_scene(HostScene& S, const Uniforms* up, const hk_grid_des
         P.emission.atlas = S.paired.data();
         P.paired = 1;
     }
-    return paired;
 }
 
 // wave-sized work units exactly like the HIP kernel: 8x8 tile x chunk of samples -> sample buffer -> running mean
@@ -159,26 +141,27 @@ long long hk_render(const Uniforms* up, const hk_grid_desc* density, const hk_gr
                     const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim,
                     float* fb, int x0, int y0, int x1, int y1, int first_sample, int n_samples, int force_wide, int flags) {
     HostScene S;
-    const bool paired = build_lane_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
+    build_lane_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
     const SceneParams& P = S.P;
     const Uniforms& u = P.u;
+    const PathtraceKernel kernel = pathtrace_kernel_of(P, force_wide != 0, false);      // the product's own rule (vr_variant.h)
     long long steps = 0;
     const int W = u.resolution[0];
-    if (u.integrator == 2 && u.use_tf) {       // direct volume rendering: one call per (pixel, sample)
+    if (kernel.item_integrator == 2) {         // direct volume rendering: one call per (pixel, sample)
         for (int y = y0; y < y1; ++y) for (int x = x0; x < x1; ++x) {
             float* px = fb + 4 * ((size_t)y * W + x);
             for (int k = 0; k < n_samples; ++k) { float L[4]; dvr_sample(P, x, y, first_sample + k, L); accumulate_sample(px, L, first_sample + k); ++steps; }
         }
         return steps;
     }
-    if (u.integrator == 3) {                   // trace_path with the ray-marching trackers: one call per (pixel, sample)
+    if (kernel.item_integrator == 3) {         // trace_path with the ray-marching trackers: one call per (pixel, sample)
         for (int y = y0; y < y1; ++y) for (int x = x0; x < x1; ++x) {
             float* px = fb + 4 * ((size_t)y * W + x);
             for (int k = 0; k < n_samples; ++k) { float L[4]; raymarch_path_sample(P, x, y, first_sample + k, L); accumulate_sample(px, L, first_sample + k); ++steps; }
         }
         return steps;
     }
-    const int form = form_of(P, paired, force_wide != 0);
+    const int form = 2 * kernel.instance + (u.use_tf ? 1 : 0);
     switch (form) {
 #define HK_FORM(SLOT) \
     case 2 * SLOT: return render_units<FormCfg<SLOT, false>::type>(P, form, fb, x0, y0, x1, y1, first_sample, n_samples); \

@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "../../volren_amd/csrc/vr_probe.h"
+#include "../../volren_amd/csrc/vr_variant.h"
 #include "host_scene.h"
 
 using namespace vr;
@@ -27,17 +28,14 @@ extern "C" {
 
 int hp_uniforms_size() { return (int)sizeof(Uniforms); }
 
-// flags: host_scene.h HS_*; 8 = pair the atlases when the product would (both grids in brick form with the same brick layout, integrator 0, a warp table that
-// passed the division check, a density scale in [2^-16, 2^24])
+// flags: host_scene.h HS_*; 8 = pair the atlases when the product would (vr_variant.h: two grids that can share one, in a scene nothing sends to the run-time variant)
 void* hp_scene_create(const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
                       const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim, int flags) {
     ProbeScene* ps = new ProbeScene;
     build_scene(ps->S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
     SceneParams& P = ps->S.P;
     ps->paired = P;
-    const bool scale_ok = P.u.vol_density_scale >= 1.0f / 65536.0f && P.u.vol_density_scale <= 16777216.0f;
-    if ((flags & 8) && P.u.has_emission && emission && !P.density.dense && !P.emission.dense && P.u.integrator == 0 && P.env_div_safe && scale_ok &&
-        P.density.nb[0] == P.emission.nb[0] && P.density.nb[1] == P.emission.nb[1] && P.density.nb[2] == P.emission.nb[2]) {
+    if ((flags & 8) && scene_pairs_atlases(P)) {      // (no emission descriptor: a zero emission view, as in host_kernel.cpp build_lane_scene)
         build_paired_atlas(ps->S.dg, ps->S.eg, ps->S.paired);
         ps->paired.density.atlas = ps->S.paired.data();
         ps->paired.emission.atlas = ps->S.paired.data();

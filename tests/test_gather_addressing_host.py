@@ -1,5 +1,5 @@
 """CPU: the two addressing forms of the path-tracing kernels' gathers (vr_trace.h table_load / line_load) read the same elements, and the rule that chooses
-between them per launch (vr_scene.h grid_largest_table_bytes, vr_launch.hip pathtrace_wide_of: 64-bit addresses from 4 GiB on) says what the layouts of
+between them per launch (vr_scene.h grid_largest_table_bytes, vr_variant.h pathtrace_kernel_of: 64-bit addresses from 4 GiB on) says what the layouts of
 DESIGN.md 4 say, at the extents where the answer changes -- which no GPU test can afford to build."""
 import hk_hotpair as hp
 

@@ -1,7 +1,7 @@
 """GPU: the two addressing forms of the hot pair's gathers, and the shortcut for blocked shadow rays, against the oracle.
 
 Kernel variants 0 and 1 form the byte offsets of their gathers into the grids' tables in 32 bits and exist a second time with 64-bit addresses for tables
-of 4 GiB or more (vr_trace.h table_load, vr_launch.hip pathtrace_wide_of); vr_set_int "wide_addressing" forces the second set, so both run here on small
+of 4 GiB or more (vr_trace.h table_load, vr_variant.h pathtrace_kernel_of); vr_set_int "wide_addressing" forces the second set, so both run here on small
 grids: every frame below is rendered once per form and must be the oracle's, bit for bit.  The last scene -- 1000 bounces at albedo 1 -- ends most of its
 shadow rays blocked, which is where collide_finish takes its shortcut (tests/test_collide_shadow_host.py holds the code behind it to the reference)."""
 import numpy as np

@@ -442,7 +442,7 @@ _crop_bricks = scenes.crop_bricks
 
 def test_dense_fp16_density_with_emission_grid():
     """The one combination no specialised kernel serves -- a dense fp16 density grid together with a (brick) temperature grid, with and without a
-    transfer function -- runs on the everything-at-run-time variant (vr_launch.hip pathtrace_variant -> 3): bit for bit the oracle's image."""
+    transfer function -- runs on the everything-at-run-time variant (vr_variant.h pathtrace_kernel_of -> 3): bit for bit the oracle's image."""
     from oracle import binding as ob
     import encoder_ref
     import volren_amd

@@ -74,8 +74,7 @@ struct IntParam {
     const char* refusal;
 };
 vr::SceneParams next_launch(Rn& R) { vr::SceneParams P; R.fill_params(P); return P; }      // the scene as the current frame's next launch will read it
-int variant_reason(Rn& R) { int why = 0; vr::pathtrace_variant_of(next_launch(R), &why); return why; }
-int kernel_wide(Rn& R) { const vr::SceneParams P = next_launch(R); return (vr::pathtrace_wide_of(R.tuning, P) || vr::pathtrace_variant_of(P, nullptr) >= 2) ? 1 : 0; }
+vr::PathtraceKernel next_kernel(Rn& R) { return vr::pathtrace_kernel_of(next_launch(R), R.tuning.wide_addressing != 0, R.tuning.stats != nullptr); }      // ... and the kernel that serves it (vr_variant.h)
 void set_grid_frame(Rn& R, int v) {
     if (!R.volume || v < 0 || (size_t)v >= R.volume->n_grid_frames()) throw std::runtime_error("grid_frame_counter out of range");
     R.volume->grid_frame_counter = (size_t)v;
@@ -103,13 +102,13 @@ const IntParam kIntParams[] = {
     { "coalesce_trace", VR_GET(R.coalesce_trace ? 1 : 0), VR_SET(R.flush_pending(); R.coalesce_trace = v != 0), VR_ANY },
     { "majorant_layout", VR_INT(majorant_layout), -1, 1, "majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)" },
     { "majorant_blocked", VR_READ_ONLY(next_launch(R).density.maj_blocked) },
-    // which compiled kernel the next launch uses, and what sent it to the run-time one (vr_device.h PathtraceVariantReason)
-    { "kernel_variant", VR_READ_ONLY(vr::pathtrace_variant_of(next_launch(R), nullptr)) },
-    { "kernel_variant_reason", VR_READ_ONLY(variant_reason(R)) },
+    // which compiled kernel the next launch uses, and what sent it to the run-time one (vr_variant.h PathtraceVariantReason)
+    { "kernel_variant", VR_READ_ONLY(next_kernel(R).variant) },
+    { "kernel_variant_reason", VR_READ_ONLY(next_kernel(R).reason) },
     { "tf_float_atlas", VR_FLAG(tf_float_atlas), VR_ANY },
     { "wide_addressing", VR_INT(tuning.wide_addressing), 0, 1, "wide_addressing: 0 (by the tables' sizes), 1 (always the kernels with 64-bit gather addresses)" },
     // the next launch's kernel forms 64-bit gather addresses: forced, a table of 4 GiB or more, or a variant that always does (2, 3, 4)
-    { "kernel_wide", VR_READ_ONLY(kernel_wide(R)) },
+    { "kernel_wide", VR_READ_ONLY(next_kernel(R).wide ? 1 : 0) },
     { "env_div_safe", VR_READ_ONLY(R.environment && R.environment->cdf_div_safe ? 1 : 0) },      // the environment's warp table passed env_cdf_kernel's check (vr_math.h div_core)
     { "env_compact", VR_READ_ONLY(R.environment && R.environment->envmap_rgbe ? 1 : 0) },      // the path tracer fetches the map's texels as RGBE dwords (vr_scene.h SceneParams::env_rgbe)
     { "pending_samples", VR_READ_ONLY(R.pending_samples()) },

@@ -104,7 +104,7 @@ void RendererHIP::commit() {
     for (size_t f : with_emission) {
         BrickGridHIP& gd = density_grids[f];
         BrickGridHIP& ge = emission_grids[f];
-        if (!(VR_PAIRED_ATLAS && VR_BRICK_HEADERS && gd.atlas && ge.atlas && !gd.dense && !ge.dense && gd.nb[0] == ge.nb[0] && gd.nb[1] == ge.nb[1] && gd.nb[2] == ge.nb[2])) continue;
+        if (!(VR_BRICK_HEADERS && gd.atlas && ge.atlas && grids_can_pair(gd, ge))) continue;
         try {
             const size_t n_rec = brick_records(gd);
             check_grid_bytes(n_rec * kPairBlockBytes, "the paired density + emission atlas", gd.nb);
@@ -221,9 +221,11 @@ BrickGridHIP RendererHIP::dense_to_bricks_on_device(const std::shared_ptr<DenseG
     return out;
 }
 
-static uint64_t fnv1a(const std::vector<uint8_t>& v) {
-    uint64_t h = 1469598103934665603ull;
-    for (uint8_t b : v) { h ^= b; h *= 1099511628211ull; }
+// FNV-1a over `n` bytes, continuing from `h` (default: the start value): the checksums below, and the keys of tile_order and submit
+constexpr uint64_t kFnv1aStart = 1469598103934665603ull;
+static uint64_t fnv1a(const void* p, size_t n, uint64_t h = kFnv1aStart) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
     return h;
 }
 void RendererHIP::grid_checksums(const BrickGridHIP& g, uint64_t out[3]) const {
@@ -233,7 +235,7 @@ void RendererHIP::grid_checksums(const BrickGridHIP& g, uint64_t out[3]) const {
         if (!bufs[i]) continue;
         std::vector<uint8_t> h(bufs[i]->size_bytes());
         bufs[i]->download(h.data(), h.size(), stream);
-        out[i] = fnv1a(h);
+        out[i] = fnv1a(h.data(), h.size());
     }
 }
 
@@ -346,7 +348,7 @@ static GridView make_view(const BrickGridHIP& g, bool paired = false, bool maj_b
     for (int i = 0; i < 3; ++i) v.nb[i] = g.nb[i];
     for (int i = 0; i < 3; ++i) { v.mshift[i] = g.mshift[i]; v.mlim[i] = (float)(8u << g.mshift[i]); }
     v.n_mips = g.n_mips;
-    v.maj_blocked = maj_blocked ? 1 : 0;         // the layout the majorant table is (re)built in and the kernel variant reads (vr_launch.hip pathtrace_variant)
+    v.maj_blocked = maj_blocked ? 1 : 0;         // the layout the majorant table is (re)built in and the kernel variant reads (vr_variant.h)
     v.maj_outside = (int32_t)majorant_padded_cells((uint32_t)(g.mshift[0] + g.mshift[1] + g.mshift[2]));
     return v;
 }
@@ -361,6 +363,8 @@ void RendererHIP::fill_params(SceneParams& P) {
     u.bounces = bounces;
     u.seed = seed;
     u.show_environment = show_environment ? 1 : 0;
+    u.integrator = integrator;
+    P.env_div_safe = environment->cdf_div_safe ? 1 : 0;      // (here already: with the density scale, what decides below which views of the grids the kernel is handed)
     // camera
     copy3(u.cam_pos, camera.pos);
     u.cam_fov = camera.fov_degree;
@@ -397,9 +401,8 @@ void RendererHIP::fill_params(SceneParams& P) {
         const mat4 efd = eti * dt;
         memcpy(P.emission_from_density, efd.m, sizeof efd.m);
         // the kernel compiled for two brick grids (DDA trackers) reads them from their paired atlas; every other kernel reads each grid's own
-        // (an environment that fails the warp table's check is rendered by the run-time variant, from the grids' own atlases: vr_launch.hip pathtrace_variant)
-        const bool scale_ok = u.vol_density_scale >= 1.0f / 65536.0f && u.vol_density_scale <= 16777216.0f;      // (the same goes for a density scale the fixed kernels' march does not divide by)
-        P.paired = (integrator == 0 && environment->cdf_div_safe && scale_ok && density.atlas_paired && density.atlas_paired == emission.atlas_paired) ? 1 : 0;
+        // (a scene that goes to the run-time variant whatever its grids -- integrator, warp table, density scale: vr_variant.h -- is rendered from the grids' own atlases)
+        P.paired = (density.atlas_paired && density.atlas_paired == emission.atlas_paired && pathtrace_scene_reasons(P) == 0) ? 1 : 0;
         // ... and is the one kernel compiled for both layouts of the majorant table's fine levels: blocked for the grids commit() marked (or as majorant_layout says)
         if (P.paired) P.density = make_view(density, true, majorant_layout < 0 ? density.maj_blocked : majorant_layout == 1);
         P.emission = make_view(emission, P.paired != 0);
@@ -427,19 +430,14 @@ void RendererHIP::fill_params(SceneParams& P) {
     P.impmap = environment->impmap->as<float>();
     P.imp_dim = (int)environment->dimension();
     P.env_cdf = environment->cdf->as<float>();
-    P.env_div_safe = environment->cdf_div_safe ? 1 : 0;
     u.resolution[0] = resolution.x; u.resolution[1] = resolution.y;
-    u.integrator = integrator;
 }
 
 void RendererHIP::update_majorants(const LaunchInputs& in, BrickGridHIP& g) {
-    const MajKey& k = in.maj;
-    if (k.density_scale == maj_key_.density_scale && k.tf_version == maj_key_.tf_version &&
-        k.wl == maj_key_.wl && k.ww == maj_key_.ww && k.frame == maj_key_.frame && k.blocked == maj_key_.blocked)
-        return;
+    if (in.maj == maj_key_) return;
     launch_majorants(in.P, g.range_words->as<uint32_t>(), g.nb, g.mip_off, g.n_mips, g.mshift, g.majorant->as<float>(), g.majorant16->as<uint16_t>(), in.stream);
     VR_HIP(hipGetLastError());
-    maj_key_ = k;
+    maj_key_ = in.maj;
 }
 
 void RendererHIP::set_tiles(const std::vector<int32_t>& tile_ids) {
@@ -499,8 +497,8 @@ std::vector<int32_t> RendererHIP::costliest_first(const SceneParams& P, const st
 
 const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) {
     const Uniforms& u = P.u;
-    uint64_t key = 1469598103934665603ull;
-    auto mix = [&key](const void* p, size_t nbytes) { const uint8_t* b = static_cast<const uint8_t*>(p); for (size_t i = 0; i < nbytes; ++i) { key ^= b[i]; key *= 1099511628211ull; } };
+    uint64_t key = kFnv1aStart;
+    auto mix = [&key](const void* p, size_t nbytes) { key = fnv1a(p, nbytes, key); };
     mix(u.cam_pos, sizeof u.cam_pos); mix(u.cam_transform, sizeof u.cam_transform); mix(&P.cam_z, sizeof P.cam_z);
     mix(u.vol_bb_min, sizeof u.vol_bb_min); mix(u.vol_bb_max, sizeof u.vol_bb_max); mix(u.resolution, sizeof u.resolution); mix(&n_tiles, sizeof n_tiles);
     if (!ids.empty()) mix(ids.data(), ids.size() * sizeof(int32_t));
@@ -514,10 +512,8 @@ const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<i
 }
 
 bool RendererHIP::LaunchInputs::same_launch_as(const LaunchInputs& o) const {
-    return memcmp(&P, &o.P, sizeof P) == 0 && frame == o.frame && maj.density_scale == o.maj.density_scale && maj.tf_version == o.maj.tf_version &&
-           maj.wl == o.maj.wl && maj.ww == o.maj.ww && maj.blocked == o.maj.blocked && memcmp(tuning.thr, o.tuning.thr, sizeof tuning.thr) == 0 && tuning.stats == o.tuning.stats &&
-           tuning.samples_per_unit == o.tuning.samples_per_unit && tuning.blocks_per_cu == o.tuning.blocks_per_cu && tuning.wide_addressing == o.tuning.wide_addressing && order_tiles == o.order_tiles &&
-           launch_target_ms == o.launch_target_ms && fast_math == o.fast_math && variance == o.variance && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
+    return memcmp(&P, &o.P, sizeof P) == 0 && frame == o.frame && maj == o.maj && tuning == o.tuning && order_tiles == o.order_tiles && launch_target_ms == o.launch_target_ms &&
+           fast_math == o.fast_math && variance == o.variance && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
 }
 
 // What a launch reads from the renderer's public, freely mutable state -- taken when trace() / render() is CALLED (the reference issues its dispatch at that
@@ -594,17 +590,27 @@ int RendererHIP::samples_per_launch(const LaunchInputs& in, int n_tiles) const {
 
 void RendererHIP::submit_tile_set(const LaunchInputs& in, int first, int n) {
     if (n <= 0) return;
-    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(in.P.u.resolution[0], in.P.u.resolution[1]);
+    const int n_tiles = tile_set_size();
     const bool ordered = in.order_tiles >= 2 || (in.order_tiles == 1 && tiles_dev_);
     const int32_t* tiles = ordered ? tile_order(in.P, tiles_host_, n_tiles) : (tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr);
-    submit(in, first, n, tiles, n_tiles);
+    const int per_launch = prepare_submit(in, first, n, n_tiles);      // (a throw here leaves the last call's window as it is)
+    open_timing_window(in.stream);
+    submit(in, first, n, tiles, n_tiles, per_launch);
+    close_timing_window(in.stream);                              // (not after a throw: a call that failed leaves no time to read)
 }
 
-void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles) {
-    if (n <= 0) return;
-    const SceneParams& P = in.P;
+int RendererHIP::tile_set_size() const { return tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y); }
+
+// The timing window of one call (last_launches, last_kernel_ms, last_pathtrace_ms) spans its launches: render() and trace() open it between prepare_submit and
+// submit, so that it holds the sub-launches alone; render_adaptive opens it before its first group and closes it after its last.
+void RendererHIP::open_timing_window(hipStream_t s) { VR_HIP(hipEventRecord(ev0_, s)); last_launches = 0; pt_events_used_ = 0; }
+void RendererHIP::close_timing_window(hipStream_t s) { VR_HIP(hipEventRecord(ev1_, s)); timing_pending_ = true; }
+
+// What a submit needs in place before its launches: the majorant table, the sample pool, the workspace and the moments; and the rate of the last sub-launch
+// enqueued, read while the window that goes still holds its events.  Returns the samples of one sub-launch as the pool allows.
+int RendererHIP::prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles) {
+    if (n <= 0) return 0;
     hipStream_t stream = in.stream;                              // (shadows the member: the launch goes where it was recorded for)
-    const bool has_tf = P.u.use_tf != 0;
     update_majorants(in, density_grids.at(in.frame));
     // per-sample radiances live in a device pool; split the request so that one sub-launch fits the pool
     int per_launch = std::min(samples_per_launch(in, n_tiles), n);
@@ -631,16 +637,29 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
         VR_HIP(hipMemsetAsync(workspace_->get(), 0xFF, workspace_->size_bytes(), stream));
         VR_HIP(hipMemsetAsync(pool_->get(), 0xFF, pool_->size_bytes(), stream));
     }
-    const int integ = P.u.integrator;
-    const bool pt_kernel = !(integ == 3 || (integ == 2 && has_tf));      // launch_pathtrace records the events around the path-tracing kernel only
+    if (in.launch_target_ms > 0 && in.kernel().item_integrator == 0) harvest_rate(false);      // what submit plans with
+    // second moments: valid while every launch since sample 1 has kept them (a launch from sample 1 starts them afresh)
+    if (in.variance && ensure_buffer(sized_.moments, color->size_bytes())) {
+        VR_HIP(hipMemsetAsync(sized_.moments->get(), 0, color->size_bytes(), stream));
+        if (first > 0) sized_.moments_n = -1;
+    }
+    sized_.moments_n = !in.variance ? -1 : (first == 0 ? n : (sized_.moments_n == first ? first + n : -1));
+    return per_launch;
+}
+
+void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch) {
+    const SceneParams& P = in.P;
+    hipStream_t stream = in.stream;
+    const PathtraceKernel kernel = in.kernel();
+    const bool pt_kernel = kernel.item_integrator == 0;          // launch_pathtrace records the events around the path-tracing kernel only
     // Launch sizing by time (round 4): no sub-launch is PLANNED to take longer than launch_target_ms.  The plan uses the rate of this renderer's last
     // finished sub-launch; when there is none for the current settings and the request is large, a short probe launch measures it first (one
     // synchronisation, once per change of settings).  A plan can still be off -- the rate is a property of the scene AND the view -- which costs nothing
     // but the bound: the kernel's watchdog watches progress, not duration (vr_pathtrace.h).
     const double px_samples = (double)n_tiles * 256.0;                          // samples per spp of this launch
     const uint64_t key = [&] {
-        uint64_t h = 1469598103934665603ull;
-        auto mix = [&h](const void* p, size_t nbytes) { const uint8_t* b = static_cast<const uint8_t*>(p); for (size_t i = 0; i < nbytes; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
+        uint64_t h = kFnv1aStart;
+        auto mix = [&h](const void* p, size_t nbytes) { h = fnv1a(p, nbytes, h); };
         const Uniforms& u = P.u;
         mix(&u.bounces, sizeof u.bounces); mix(u.vol_albedo, sizeof u.vol_albedo); mix(&u.vol_phase_g, sizeof u.vol_phase_g); mix(&u.vol_density_scale, sizeof u.vol_density_scale);
         mix(&u.use_tf, sizeof u.use_tf); mix(&u.tf_window_left, sizeof u.tf_window_left); mix(&u.tf_window_width, sizeof u.tf_window_width); mix(&u.integrator, sizeof u.integrator);
@@ -658,7 +677,6 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     };
     int probe = 0;
     if (pt_kernel && in.launch_target_ms > 0) {
-        harvest_rate(false);
         const bool known = rate_samples_per_ms_ > 0.0 && rate_key_ == key;
         if (!known && px_samples * (double)std::min(per_launch, n) > (double)(1u << 26)) {
             rate_samples_per_ms_ = 0.0;                                          // measured under other settings: not a basis for a plan
@@ -666,24 +684,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
             probe = std::min(probe, n);
         } else per_launch = cap_by_rate(per_launch);
     }
-    // second moments: valid while every launch since sample 1 has kept them (a launch from sample 1 starts them afresh)
-    float* moments = nullptr;
-    if (in.variance) {
-        const size_t bytes = color->size_bytes();
-        if (ensure_buffer(sized_.moments, bytes)) {
-            VR_HIP(hipMemsetAsync(sized_.moments->get(), 0, bytes, stream));
-            if (first > 0) sized_.moments_n = -1;
-        }
-        moments = sized_.moments->as<float>();
-        sized_.moments_n = first == 0 ? n : (sized_.moments_n == first ? first + n : -1);
-    } else {
-        sized_.moments_n = -1;
-    }
-    if (!keep_timing_) {
-        VR_HIP(hipEventRecord(ev0_, stream));
-        last_launches = 0;
-        pt_events_used_ = 0;
-    }
+    float* moments = in.variance ? sized_.moments->as<float>() : nullptr;
     for (int done = 0; done < n;) {
         ++last_launches;
         const int m = probe > 0 ? probe : std::min(per_launch, n - done);
@@ -694,7 +695,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
             pt_events_used_ += 2;
         }
         int seed_samples = 0;
-        const uint32_t* seed_table = pathtrace_reads_seed_table(in.tuning, P) ? seed_table_for(P, first + done, m, stream, &seed_samples) : nullptr;
+        const uint32_t* seed_table = kernel.reads_seed_table ? seed_table_for(P, first + done, m, stream, &seed_samples) : nullptr;
         launch_pathtrace(in.tuning, P, color->as<float>(), pool_->as<float>(), workspace_->as<float>(), status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m, status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments,
                          seed_table, seed_samples);
         VR_HIP(hipGetLastError());
@@ -706,8 +707,6 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
             per_launch = cap_by_rate(per_launch);
         }
     }
-    VR_HIP(hipEventRecord(ev1_, stream));
-    timing_pending_ = true;
 }
 
 // ---- seed table (renderer.h) ------------------------------------------------------------------------------------------------------------------
@@ -798,8 +797,7 @@ void RendererHIP::trace() {
     if (pending_n_ == 0) {
         pending_ = std::move(now);
         pending_first_ = sample;
-        const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y);
-        pending_cap_ = samples_per_launch(pending_, n_tiles);      // a full sub-launch goes out at once: the GPU works while the caller keeps calling
+        pending_cap_ = samples_per_launch(pending_, tile_set_size());     // a full sub-launch goes out at once: the GPU works while the caller keeps calling
     }
     ++pending_n_;
     ++sample;
@@ -897,8 +895,8 @@ void RendererHIP::download_display(float* rgba) const {
 }
 
 // The feature pass reads the scene as a render() would: capture() (which also decodes the float atlas under a transfer function) and the majorant
-// table of the current density scale and LUT.  It runs the lane code of the run-time kernel variant, which reads every grid from its own atlas:
-// the views of a frame whose grids share a paired atlas are made again without it (the majorant layout stays the one the table is built in).
+// table of the current density scale and LUT.  It runs the lane code of the run-time kernel variant, which reads every grid from its own atlas
+// (unpair_views).
 // feature_scene: P = that scene, and nothing else -- upsample() marches a pass at another resolution into a buffer of its own with it.
 // begin_feature_pass: what both feature passes do before their launch -- P = that scene; the feature buffer exists (zero-filled when it is new); returns the
 // number of tiles of the tile set.
@@ -908,21 +906,24 @@ void RendererHIP::feature_scene(SceneParams& P) {
     capture(in);
     update_majorants(in, density_grids.at(in.frame));
     P = in.P;
-    if (P.paired) {
-        P.density = make_view(density_grids.at(in.frame), false, P.density.maj_blocked != 0);
-        P.emission = make_view(emission_grids.at(in.frame), false);
-        P.paired = 0;
-    }
+    unpair_views(P, in.frame);
+}
+
+// the scene with each grid's own atlas: the views of a frame whose grids share a paired atlas, made again without it (the majorant layout stays the one the table is built in)
+void RendererHIP::unpair_views(SceneParams& P, size_t frame) const {
+    if (!P.paired) return;
+    P.density = make_view(density_grids.at(frame), false, P.density.maj_blocked != 0);
+    P.emission = make_view(emission_grids.at(frame), false);
+    P.paired = 0;
 }
 
 int RendererHIP::begin_feature_pass(SceneParams& P) {
     feature_scene(P);
-    const int n_tiles = tiles_dev_ ? (int)tiles_host_.size() : tile_count(resolution.x, resolution.y);
     const size_t bytes = (size_t)resolution.x * resolution.y * 8 * sizeof(float);
     if (ensure_buffer(sized_.features, bytes)) {
         VR_HIP(hipMemsetAsync(sized_.features->get(), 0, bytes, stream));
     }
-    return n_tiles;
+    return tile_set_size();
 }
 
 void RendererHIP::render_features(int spp) {
@@ -1005,11 +1006,7 @@ void RendererHIP::probe(int what, int form, const uint32_t* in, float* out, size
     SceneParams P = li.P;
     if (const char* why = probe_form_error(P, what, form)) throw std::runtime_error(std::string("probe: this scene cannot serve that form: ") + why);
     if (const char* why = probe_items_error(P, what, form, in, n)) throw std::runtime_error(std::string("probe: bad item: ") + why);
-    if (P.paired && probe_decode_form(what, form).pair == 0) {
-        P.density = make_view(density_grids.at(li.frame), false, P.density.maj_blocked != 0);
-        P.emission = make_view(emission_grids.at(li.frame), false);
-        P.paired = 0;
-    }
+    if (probe_decode_form(what, form).pair == 0) unpair_views(P, li.frame);
     if (n == 0) return;
     const size_t in_bytes = n * kProbeInWords * sizeof(uint32_t), out_bytes = n * (size_t)probe_out_words(what) * sizeof(float);
     DeviceBuffer din(in_bytes), dout(out_bytes);
@@ -1336,11 +1333,8 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
     ensure_buffer_at_least(sized_.adaptive_lists, (size_t)n_all * 2 * sizeof(int32_t));
     ensure_buffer_at_least(sized_.adaptive_err, (size_t)n_all * sizeof(float));
     const bool ordered = in.order_tiles >= 1;
-    VR_HIP(hipEventRecord(ev0_, in.stream));
-    last_launches = 0;
-    pt_events_used_ = 0;
+    open_timing_window(in.stream);                    // one window over all the call's submits
     adaptive_rounds = 0;
-    keep_timing_ = true;
     // every group of `ids` from its count n to to(n), as one submit each
     auto launch_groups = [&](const std::vector<int32_t>& ids, const auto& to) {
         const auto groups = adaptive_groups(ids, tile_n_);
@@ -1354,15 +1348,14 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
         size_t off = 0;
         for (const auto& g : groups) {
             const int32_t n = g.first, next = to(n);
-            submit(in, n, next - n, sized_.adaptive_lists->as<int32_t>() + off, (int)g.second.size());
+            const int n_tiles = (int)g.second.size();
+            submit(in, n, next - n, sized_.adaptive_lists->as<int32_t>() + off, n_tiles, prepare_submit(in, n, next - n, n_tiles));
             for (int32_t t : g.second) tile_n_[(size_t)t] = next;
             off += g.second.size();
         }
     };
     auto finish = [&] {
-        keep_timing_ = false;
-        VR_HIP(hipEventRecord(ev1_, in.stream));
-        timing_pending_ = true;
+        close_timing_window(in.stream);               // (on a throw too)
         const auto mm = std::minmax_element(tile_n_.begin(), tile_n_.end());
         sample = *mm.second;
         if (*mm.first == *mm.second) { drop_tile_samples(); sized_.moments_n = sample; }      // every tile at one count: an ordinary uniform frame

@@ -308,7 +308,11 @@ struct RendererHIP {
 
 private:
     // majorant cache key
-    struct MajKey { float density_scale = -1.f; uint64_t tf_version = ~0ull; float wl = 0, ww = 0; size_t frame = ~(size_t)0; int blocked = -1; };   // tf_version: TransferFunction::version (unique per upload), 0 = no LUT
+    struct MajKey {                                                // tf_version: TransferFunction::version (unique per upload), 0 = no LUT
+        float density_scale = -1.f; uint64_t tf_version = ~0ull; float wl = 0, ww = 0; size_t frame = ~(size_t)0; int blocked = -1;
+        // (field by field: the padding is not zeroed)
+        bool operator==(const MajKey& o) const { return density_scale == o.density_scale && tf_version == o.tf_version && wl == o.wl && ww == o.ww && frame == o.frame && blocked == o.blocked; }
+    };
     // Everything a launch reads from the renderer's mutable state, as one trace()/render() call found it.  `P` is zero-filled before it is written
     // (fill_params), so two snapshots are compared byte by byte; the handles keep alive what P points into (a caller may replace the environment or
     // re-upload the LUT between two trace() calls: the recorded samples still see the old arrays, as the reference's already issued dispatches do).
@@ -324,11 +328,18 @@ private:
         std::shared_ptr<TransferFunction> tf;
         DeviceBufferPtr keep[5];               // envmap, impmap, env_cdf, lut, compact envmap
         bool same_launch_as(const LaunchInputs& o) const;
+        PathtraceKernel kernel() const { return pathtrace_kernel_of(P, tuning.wide_addressing != 0, tuning.stats != nullptr); }      // the kernel that serves the launch (vr_variant.h)
     };
     void capture(LaunchInputs& in);            // validates, builds the decoded float atlas when a LUT needs it, fills `in` from the current fields
-    // samples first+1 .. first+n of the `n_tiles` tiles of the device list `tiles` in that order (nullptr: the whole frame in raster order)
-    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles);
-    void submit_tile_set(const LaunchInputs& in, int first, int n);      // submit over the renderer's tile set (set_tiles), ordered as order_tiles says
+    // samples first+1 .. first+n of the `n_tiles` tiles of the device list `tiles` in that order (nullptr: the whole frame in raster order), inside the
+    // timing window its caller opened, per_launch samples at a time: what prepare_submit returned for the same arguments, after it brought the majorant table, the
+    // pool, the workspace and the moments up to date -- outside the window of render() / trace(), which spans the sub-launches alone
+    int prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles);
+    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch);
+    void submit_tile_set(const LaunchInputs& in, int first, int n);      // prepare, then one window around a submit over the renderer's tile set (set_tiles), ordered as order_tiles says
+    void open_timing_window(hipStream_t s), close_timing_window(hipStream_t s);      // of one call: last_launches, last_kernel_ms, last_pathtrace_ms
+    int tile_set_size() const;                 // tiles of the renderer's tile set: the listed ones, or all of the frame
+    void unpair_views(SceneParams& P, size_t frame) const;
     int samples_per_launch(const LaunchInputs& in, int n_tiles) const;
     LaunchInputs pending_;
     int pending_n_ = 0, pending_first_ = 0, pending_cap_ = 0;
@@ -343,7 +354,6 @@ private:
     // adaptive sampling: samples behind each raster tile, meaningful while `sample` == tile_n_sample_ (ragged()); the denoiser's device copy: sized_.tile_n_dev
     std::vector<int32_t> tile_n_;
     int tile_n_sample_ = -1;
-    bool keep_timing_ = false;                         // submit() adds to the timing window of the call in progress instead of opening its own
     DeviceBufferPtr status_;
     DeviceBufferPtr pool_;
     DeviceBufferPtr workspace_;

@@ -9,6 +9,7 @@
 #include "vr_scene.h"
 #include "vr_temporal.h"
 #include "vr_tiles.h"
+#include "vr_variant.h"
 
 namespace vr {
 
@@ -27,7 +28,11 @@ struct PathtraceTuning {
     unsigned long long* stats = nullptr;      // device buffer of 32 counters: the launch uses the instrumented (STATS) kernels; or null
     int32_t samples_per_unit = 0;             // samples of a work unit; 0 = per kernel variant
     int32_t blocks_per_cu = 0;                // resident workgroups per CU; 0 = from the occupancy query (cached per device)
-    int32_t wide_addressing = 0;              // diagnostic (vr_set_int "wide_addressing"): 1 = the kernels with 64-bit gather addresses whatever the tables' sizes (pathtrace_wide_of)
+    int32_t wide_addressing = 0;              // diagnostic (vr_set_int "wide_addressing"): 1 = the kernels with 64-bit gather addresses whatever the tables' sizes (vr_variant.h)
+    bool operator==(const PathtraceTuning& o) const {
+        for (int i = 0; i < 8; ++i) if (thr[i] != o.thr[i]) return false;
+        return stats == o.stats && samples_per_unit == o.samples_per_unit && blocks_per_cu == o.blocks_per_cu && wide_addressing == o.wide_addressing;
+    }
 };
 PathtraceTuning default_tuning();             // the defaults, with the diagnostic overrides VR_SPU / VR_BLOCKS_PER_CU of the environment (read once)
 size_t pathtrace_pool_floats(const PathtraceTuning& T, int32_t n_tiles, int32_t n_samples);
@@ -52,21 +57,7 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
 constexpr int32_t kExpectedMaxRays = 4;
 void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream,
                               const ClearTable* clear = nullptr, unsigned long long* stats = nullptr);
-// which compiled kernel variant (vr_pathtrace.hip: 0 bricks, 1 dense fp16, 2 / 4 bricks + emission grid, 3 everything at run time) serves a scene, and -- *why, a mask --
-// what sent it to the run-time variant (0: nothing, the scene has a kernel of its own kind)
-enum PathtraceVariantReason : int {
-    VR_VARIANT_INTEGRATOR = 1,        // a global-majorant / ray-marching integrator was asked for
-    VR_VARIANT_ENV_DIVISION = 2,      // the environment's warp table failed env_cdf_kernel's check (thresholds below 2^-76: vr_math.h div_core does not apply)
-    VR_VARIANT_DENSITY_SCALE = 4,     // density scale outside [2^-16, 2^24] (the clean march divides by majorants without rescaling)
-    VR_VARIANT_GRID_FORMS = 8         // emission grid with a dense grid on either side, or brick grids of different layouts (no paired atlas)
-};
-int pathtrace_variant_of(const SceneParams& P, int* why);
-// true when the kernel instance that serves the scene reads a seed table (vr_pathtrace.h seed_request_point: the brick kernels without an emission grid, not
-// their instrumented forms): for every other launch the renderer neither fills nor passes one
-bool pathtrace_reads_seed_table(const PathtraceTuning& T, const SceneParams& P);
-// Kernel variants 0 and 1 form the byte offsets of their gathers into the grids' tables in 32 bits (vr_trace.h table_load) and exist a second time with 64-bit
-// addresses: true when a table such a kernel would index on this scene holds 4 GiB or more -- or when the tuning forces it.  (Variants 2, 3 and 4 are always wide.)
-bool pathtrace_wide_of(const PathtraceTuning& T, const SceneParams& P);
+// which compiled kernel instance serves a scene, why, and whether it reads a seed table: vr_variant.h pathtrace_kernel_of
 // fast_math: the opt-in tolerance-mode kernels (hardware transcendentals, reciprocal division; vr_math.h VR_FAST_MATH); the default
 // kernels are bit-identical to the CPU oracle
 // ---- vr_filters.hip --------------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 //
 // pathtrace_kernel (the hot path): the per-path code -- the reference's trace_path and everything it calls, restated as a state
 // machine -- is in vr_trace.h, its scheduler (persistent wavefronts that pull work units of 8x8 pixels x 8 samples) in vr_pathtrace.h and
-// its compiled variants in vr_pathtrace.hip; this file chooses the variant, sizes the launch and launches it.
+// its compiled variants in vr_pathtrace.hip; vr_variant.h chooses the instance, this file sizes the launch and launches it.
 // Radiance per (pixel, sample) goes to a sample pool; accumulate_kernel folds it into the RGBA32F running mean in sample
 // order, which makes the result bit-identical to the reference's one-dispatch-per-sample loop (renderer.cpp:138-140,
 // pathtracer_brick.glsl:36).  MFMA is not used: there is no dense contraction on this path.
@@ -147,12 +147,8 @@ void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_
 #undef VR_EXPECTED_LAUNCH
 }
 
-// Units of 8 samples x 64 pixels, except on the dense-grid kernel, whose long paths (128 bounces, every camera ray scatters) fill
-// the pools better from units of 4: c4 +1.3 %, c2 +-0, c3 -1 % (profiles/r2x_occupancy_recheck.txt) -- and, round 4, on the emission kernel:
-// c5cloud +1 %, c5full +0.5 % (profiles/r4d_*)
-constexpr int32_t kMaxSamplesPerUnit = 8;
-static int32_t samples_per_unit(const PathtraceTuning& T, int variant) { return T.samples_per_unit > 0 ? T.samples_per_unit : ((variant == 1 || variant == 2 || variant == 4) ? 4 : kMaxSamplesPerUnit); }
-constexpr int kPtVariants = 5;
+// samples of a work unit: the tuning's, or the variant's own (vr_variant.h)
+static int32_t samples_per_unit(const PathtraceTuning& T, int32_t variant_default) { return T.samples_per_unit > 0 ? T.samples_per_unit : variant_default; }
 
 PathtraceTuning default_tuning() {
     static std::once_flag once;
@@ -171,7 +167,7 @@ size_t pathtrace_pool_floats(const PathtraceTuning& T, int32_t n_tiles, int32_t 
     // the samples are rounded up to whole units: sized for whichever unit size a variant may use (samples_per_unit)
     size_t padded = 0;
     for (int variant = 0; variant < kPtVariants; ++variant) {
-        const int32_t spu = std::min(n_samples, samples_per_unit(T, variant));
+        const int32_t spu = std::min(n_samples, samples_per_unit(T, pathtrace_unit_samples(variant)));
         padded = std::max(padded, (size_t)((n_samples + spu - 1) / spu) * (size_t)spu);
     }
     return padded * (size_t)n_tiles * 4u * 64u * 4u;
@@ -188,56 +184,17 @@ VR_PT_DECL(0w) VR_PT_DECL(1w) VR_PT_DECL(0w_fast) VR_PT_DECL(1w_fast)      // 64
 }
 typedef int (*PtOccupancy)(int, int);
 typedef void (*PtLaunch)(int, int, unsigned, hipStream_t, const void*, float*, float*, const void*, const void*, uint32_t*, unsigned long long*, const void*);
-// [arithmetic mode][wide][variant]; variants 2, 3 and 4 have one build each, which is wide
-static const PtOccupancy kPtOccupancy[2][2][kPtVariants] = { { { vr_pt_occupancy_0, vr_pt_occupancy_1, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 },
-                                                               { vr_pt_occupancy_0w, vr_pt_occupancy_1w, vr_pt_occupancy_2, vr_pt_occupancy_3, vr_pt_occupancy_4 } },
-                                                             { { vr_pt_occupancy_0_fast, vr_pt_occupancy_1_fast, vr_pt_occupancy_2_fast, vr_pt_occupancy_3_fast, vr_pt_occupancy_4_fast },
-                                                               { vr_pt_occupancy_0w_fast, vr_pt_occupancy_1w_fast, vr_pt_occupancy_2_fast, vr_pt_occupancy_3_fast, vr_pt_occupancy_4_fast } } };
-static const PtLaunch kPtLaunch[2][2][kPtVariants] = { { { vr_pt_launch_0, vr_pt_launch_1, vr_pt_launch_2, vr_pt_launch_3, vr_pt_launch_4 },
-                                                         { vr_pt_launch_0w, vr_pt_launch_1w, vr_pt_launch_2, vr_pt_launch_3, vr_pt_launch_4 } },
-                                                       { { vr_pt_launch_0_fast, vr_pt_launch_1_fast, vr_pt_launch_2_fast, vr_pt_launch_3_fast, vr_pt_launch_4_fast },
-                                                         { vr_pt_launch_0w_fast, vr_pt_launch_1w_fast, vr_pt_launch_2_fast, vr_pt_launch_3_fast, vr_pt_launch_4_fast } } };
+// [arithmetic mode][instance], in the order of vr_variant.h PathtraceKernel::instance
+static const struct { PtOccupancy occupancy; PtLaunch launch; } kPtInstance[2][kPtInstances] = {
+    { { vr_pt_occupancy_0, vr_pt_launch_0 }, { vr_pt_occupancy_0w, vr_pt_launch_0w }, { vr_pt_occupancy_1, vr_pt_launch_1 }, { vr_pt_occupancy_1w, vr_pt_launch_1w },
+      { vr_pt_occupancy_2, vr_pt_launch_2 }, { vr_pt_occupancy_4, vr_pt_launch_4 }, { vr_pt_occupancy_3, vr_pt_launch_3 } },
+    { { vr_pt_occupancy_0_fast, vr_pt_launch_0_fast }, { vr_pt_occupancy_0w_fast, vr_pt_launch_0w_fast }, { vr_pt_occupancy_1_fast, vr_pt_launch_1_fast }, { vr_pt_occupancy_1w_fast, vr_pt_launch_1w_fast },
+      { vr_pt_occupancy_2_fast, vr_pt_launch_2_fast }, { vr_pt_occupancy_4_fast, vr_pt_launch_4_fast }, { vr_pt_occupancy_3_fast, vr_pt_launch_3_fast } } };
 
-// which compiled variant serves a scene (see vr_pathtrace.hip), and why -- `why` is a mask of PathtraceVariantReason (vr_device.h): the run-time variant (3) is an
-// order of magnitude slower than the kernels of one scene kind on some scenes (one copy of the hot pair, general forms only, everything decided per wavefront), so a
-// scene that lands there for a reason its caller did not ask for is told so (launch_pathtrace, vr_get_int "kernel_variant_reason")
-int pathtrace_variant_of(const SceneParams& P, int* why) {
-    // (an environment whose warp table failed the check of env_cdf_kernel -- thresholds below 2^-76: the kernels of one scene kind divide by vr_math.h div_core there --
-    // goes to the run-time variant, which divides in full; RendererHIP::fill_params pairs no atlases for it)
-    // -- and so does a density scale outside [2^-16, 2^24]: the CLEAN form of the march divides by majorants = density_scale x an fp16 number (vr_trace.h march_finish)
-    const bool scale_ok = P.u.vol_density_scale >= 1.0f / 65536.0f && P.u.vol_density_scale <= 16777216.0f;
-    int reason = 0;
-    if (P.u.integrator != 0) reason |= VR_VARIANT_INTEGRATOR;
-    if (!P.env_div_safe) reason |= VR_VARIANT_ENV_DIVISION;
-    if (!scale_ok) reason |= VR_VARIANT_DENSITY_SCALE;
-    int variant;
-    if (reason) variant = 3;
-    // variant 2: both grids in brick form -- and, when the kernels are built for the paired atlas, sharing one (same brick layout: RendererHIP::commit)
-    // (4 = 2 compiled for majorant levels 0-1 in 4x4x4-cell blocks; every other kernel of a fixed layout reads linear tables: RendererHIP::fill_params only
-    // sets maj_blocked on the views of frames this variant -- or the run-time variant -- serves)
-    else if (P.u.has_emission) {
-        const bool mixed = P.density.dense || P.emission.dense || (VR_PAIRED_ATLAS && !P.paired);
-        if (mixed) reason |= VR_VARIANT_GRID_FORMS;
-        variant = mixed ? 3 : (P.density.maj_blocked ? 4 : 2);
-    } else variant = P.density.dense ? 1 : 0;
-    if (why) *why = reason;
-    return variant;
-}
-// a kernel's 32-bit byte offsets reach every byte of a table smaller than 2^32 bytes (vr_scene.h grid_largest_table_bytes)
-bool pathtrace_wide_of(const PathtraceTuning& T, const SceneParams& P) {
-    if (T.wide_addressing) return true;
-    uint64_t m = grid_largest_table_bytes(P.density, P.paired != 0, P.u.use_tf != 0);
-    if (P.u.has_emission) m = std::max(m, grid_largest_table_bytes(P.emission, P.paired != 0, false));
-    return m >= (1ull << 32);
-}
-bool pathtrace_reads_seed_table(const PathtraceTuning& T, const SceneParams& P) {
-    const bool item_kernel_serves = P.u.integrator == 3 || (P.u.integrator == 2 && P.u.use_tf);
-    return !item_kernel_serves && T.stats == nullptr && pathtrace_variant_of(P, nullptr) == 0;
-}
-static int pathtrace_variant(const SceneParams& P) {
-    int why = 0;
-    const int variant = pathtrace_variant_of(P, &why);
-    // the two reasons a caller cannot see coming: said once per process, on stderr
+// The run-time variant (3) is an order of magnitude slower than the kernels of one scene kind on some scenes (one copy of the hot pair, general forms only, everything
+// decided per wavefront), so a scene that lands there for a reason its caller did not ask for is told so (here, and vr_get_int "kernel_variant_reason").
+// The two reasons a caller cannot see coming: said once per process, on stderr
+static void note_unexpected_reasons(int why) {
     if (why & (VR_VARIANT_ENV_DIVISION | VR_VARIANT_DENSITY_SCALE)) {
         static std::once_flag once;
         std::call_once(once, [&] {
@@ -246,23 +203,22 @@ static int pathtrace_variant(const SceneParams& P) {
                     (why & VR_VARIANT_DENSITY_SCALE) ? " the density scale lies outside [2^-16, 2^24];" : "");
         });
     }
-    return variant;
 }
 
 // resident workgroups of a kernel instance on the CURRENT device: occupancy query x CU count, cached per (device, instance)
-static int resident_blocks(const PathtraceTuning& T, int mode, int wide, int variant, bool tf, bool stats) {
+static int resident_blocks(const PathtraceTuning& T, int mode, int instance, bool tf, bool stats) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 1024;
     static std::mutex mu;
     static std::map<uint32_t, std::pair<int, int>> cache;            // key -> (CUs, workgroups per CU)
-    const uint32_t key = ((uint32_t)dev << 8) | ((uint32_t)wide << 6) | ((uint32_t)mode << 5) | ((uint32_t)variant << 2) | (tf ? 2u : 0u) | (stats ? 1u : 0u);
+    const uint32_t key = ((uint32_t)dev << 8) | ((uint32_t)mode << 5) | ((uint32_t)instance << 2) | (tf ? 2u : 0u) | (stats ? 1u : 0u);
     std::pair<int, int> v;
     {
         std::lock_guard<std::mutex> lock(mu);
         auto it = cache.find(key);
         if (it == cache.end()) {
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            it = cache.emplace(key, std::make_pair(cus, kPtOccupancy[mode][wide][variant](tf, stats))).first;
+            it = cache.emplace(key, std::make_pair(cus, kPtInstance[mode][instance].occupancy(tf, stats))).first;
         }
         v = it->second;
     }
@@ -280,8 +236,10 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     for (int i = 0; i < ST_COUNT; ++i) S.thr[i] = T.thr[i];
     LaunchDesc D;
     D.tiles = tiles; D.n_tiles = n_tiles; D.first_sample = first_sample; D.n_samples = n_samples;
-    const int variant = pathtrace_variant(P);
-    D.spu = std::min(n_samples, samples_per_unit(T, variant));
+    const bool tf = P.u.use_tf != 0, stats = T.stats != nullptr;
+    const PathtraceKernel K = pathtrace_kernel_of(P, T.wide_addressing != 0, stats);
+    note_unexpected_reasons(K.reason);
+    D.spu = std::min(n_samples, samples_per_unit(T, K.samples_per_unit));
     const int32_t chunks = (n_samples + D.spu - 1) / D.spu;
     // item indices are 32-bit (WorkUnit::base, the sample pool's slots): RendererHIP::samples_per_launch sizes sub-launches below that; anything else is a caller's bug
     if ((uint64_t)chunks * (uint64_t)n_tiles * 4u * (uint64_t)(D.spu * 64) > 0xFFFFFFFFull)
@@ -300,19 +258,18 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     // collision code (8 corner taps + LUT) is the dearest (+4.4 %); profiles/r2ab_collide_threshold.txt
     // (round 4: 32 also with an emission grid, whose collision code carries two stochastic taps: c5cloud +0.8 %, c5full +1 %, profiles/r4a_*)
     if (S.thr[ST_COLLIDE] <= 0) S.thr[ST_COLLIDE] = (P.u.use_tf || P.u.has_emission) ? 32 : 24;
-    const bool tf = P.u.use_tf != 0, stats = T.stats != nullptr;
-    const int mode = fast_math ? 1 : 0, wide = pathtrace_wide_of(T, P) ? 1 : 0;
-    const int blocks = resident_blocks(T, mode, wide, variant, tf, stats);
+    const int mode = fast_math ? 1 : 0;
+    const int blocks = resident_blocks(T, mode, K.instance, tf, stats);
     const uint32_t groups_needed = (D.n_units + (uint32_t)kWgWaves - 1u) / (uint32_t)kWgWaves;      // a wavefront per unit at least
     const dim3 grid((unsigned)std::min<uint32_t>((uint32_t)blocks, groups_needed > 0 ? groups_needed : 1u)), block(256);
-    if (P.u.integrator == 3 || (P.u.integrator == 2 && P.u.use_tf)) {
+    if (K.item_integrator) {
         const uint64_t items = (uint64_t)D.n_units * (uint64_t)(D.spu * 64);
-        const auto integrate = P.u.integrator == 2 ? item_kernel<2> : item_kernel<3>;
+        const auto integrate = K.item_integrator == 2 ? item_kernel<2> : item_kernel<3>;
         hipLaunchKernelGGL(integrate, dim3((unsigned)((items + 255) / 256)), block, 0, stream, P, sample_pool, D);
     } else {
         (void)hipMemsetAsync(unit_counter, 0, kQueueSegments * sizeof(uint32_t), stream);
         if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
-        kPtLaunch[mode][wide][variant](tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats, &seeds);
+        kPtInstance[mode][K.instance].launch(tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats, &seeds);
         if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
     }
     const auto accumulate = moments ? accumulate_kernel<true> : accumulate_kernel<false>;
