@@ -71,7 +71,7 @@ volren_amd/volren: $(CSRC)/main.cpp volren_amd/libvolren_amd.so $(HDRS)
 # A caller written against the reference's src/renderer.h builds with: hipcc -I<p>/include caller.cpp -L<p>/lib -lvolren_amd
 PREFIX ?= /usr/local
 # what volren_amd.hpp pulls in (host-side class headers; the kernel headers vr_trace.h / vr_pathtrace.h / vr_math.h stay private)
-INSTALL_HDRS := renderer.h environment.h transferfunc.h grids.h sharded.h devmem.h hostmath.h vr_math.h vr_device.h vr_denoise.h vr_temporal.h vr_tiles.h vr_scene.h vr_variant.h
+INSTALL_HDRS := renderer.h environment.h transferfunc.h grids.h sharded.h devmem.h hostmath.h vr_math.h vr_device.h vr_denoise.h vr_layers.h vr_upsample.h vr_regress.h vr_temporal.h vr_tiles.h vr_scene.h vr_variant.h
 install: all
 	install -d $(DESTDIR)$(PREFIX)/include/volren_amd $(DESTDIR)$(PREFIX)/lib $(DESTDIR)$(PREFIX)/bin
 	install -m 644 include/volren_amd.h include/volren_amd.hpp $(DESTDIR)$(PREFIX)/include/

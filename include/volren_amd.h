@@ -314,7 +314,21 @@ int vr_resolve_background(vr_renderer* r, float* rgba_out);
  *     loses.  vr_sharded_denoise / vr_sharded_denoise_temporal honour part 0's setting, bit for bit one device's result.
  *     vr_denoised_layer waits and writes L of the last such call, W*H*4 floats, linear, row 0 at the bottom: the scattered light premultiplied by the
  *     exact coverage, alpha = kappa; composite it over any background B' as (1 - a) B' + rgb.  VR_ERR before the first vr_denoise or
- *     vr_denoise_temporal with the setting on since the last resize. */
+ *     vr_denoise_temporal with the setting on since the last resize.
+ *     The filter of the layer: vr_set_int / vr_get_int "denoise_filter" (0 or 1; default 0, and then every launch, allocation and result is what it is
+ *     without this paragraph; anything else is VR_ERR, the old value kept; a call that changes the value drops the history).  With 1 -- and
+ *     "denoise_layers" = 1: without it vr_denoise and vr_denoise_temporal are VR_ERR before anything is launched, as they are for whatever "denoise_layers"
+ *     itself refuses -- one pass of weighted local regression over an 11 x 11 window takes the place of the a-trous iterations; the resolve, the split,
+ *     the temporal blend with rejection or moments and the merge stay as they are, and "denoise_iterations" = 0 still leaves S unfiltered.  Per pixel p
+ *     with kappa_p > 0, over the taps q with S_q.a > 2^-20 and kappa_q > 0 (dy outer, dx inner):
+ *         w = s(dx) s(dy) e_q S_q.a,  s the Gaussian of sigma 2.5, e_q = w_n w_d w_a of vr_denoise with "denoise_sigma" (1 at the centre, and 1 unless both
+ *             coverages are positive); no colour weight, no coverage weight, and the variance is neither read nor written
+ *         x = (1, (d_q - d_p) / max(d_p, 2^-20), n_q - n_p, a_q - a_p): the fit C ~ beta . x of the targets S_q.rgb / S_q.a by weighted least squares, with
+ *             lambda sum(w) added to the seven slopes' diagonal, lambda = vr_set_float "denoise_ridge" (0, or in [2^-20, 2^20]; VR_ERR otherwise)
+ *         F.rgb = kappa_p beta_0, F.a = kappa_p; lambda = 0 is zero order, beta_0 = sum(w c) / sum(w), and the default (README.md has the sweep that chose it)
+ *     and F = 0 where kappa_p = 0 or sum(w) <= 2^-20, so every pixel without coverage comes out as B bit for bit.  The arithmetic is specified operation
+ *     by operation in volren_amd/csrc/vr_regress.h and reproducible bit for bit; vr_upsample, the history and vr_sharded_denoise (part 0's settings) take
+ *     it as they take the a-trous's result. */
 int vr_denoised_layer(vr_renderer* r, float* rgba_out);
 /* --- the denoised scattered layer upsampled under a full-resolution guide (no reference counterpart).
  *     kappa and B of (1 - kappa) B + kappa C are functions of the camera ray alone and cost no path-tracing sample at any resolution; C is smooth after the

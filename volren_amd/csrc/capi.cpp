@@ -99,6 +99,7 @@ const IntParam kIntParams[] = {
     { "denoise_moments", VR_GET(R.denoise_moments), VR_SET(R.set_denoise_moments(v)), VR_ANY },
     { "denoise_resolve", VR_GET(R.denoise_resolve), VR_SET(R.set_denoise_resolve(v)), VR_ANY },
     { "denoise_layers", VR_GET(R.denoise_layers), VR_SET(R.set_denoise_layers(v)), VR_ANY },
+    { "denoise_filter", VR_GET(R.denoise_filter), VR_SET(R.set_denoise_filter(v)), VR_ANY },
     { "coalesce_trace", VR_GET(R.coalesce_trace ? 1 : 0), VR_SET(R.flush_pending(); R.coalesce_trace = v != 0), VR_ANY },
     { "majorant_layout", VR_INT(majorant_layout), -1, 1, "majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)" },
     { "majorant_blocked", VR_READ_ONLY(next_launch(R).density.maj_blocked) },
@@ -177,6 +178,9 @@ FloatField float_field(vr::RendererHIP& R, const std::string& n) {
     if (n == "denoise_reject") return { &R.denoise_reject, 1, [](const float* values, int count) {
         if (count == 1 && !(values[0] == 0.0f || (values[0] >= vr::kTemporalRejectMin && values[0] <= vr::kTemporalRejectMax)))
             throw std::runtime_error("denoise_reject must be 0 (off) or in [2^-10, 2^20]");
+    } };
+    if (n == "denoise_ridge") return { &R.denoise_ridge, 1, [](const float* values, int count) {      // vr_regress.h
+        if (count == 1 && !vr::regress_ridge_ok(values[0])) throw std::runtime_error("denoise_ridge must be 0 (zero order) or in [2^-20, 2^20]");
     } };
     throw std::runtime_error("unknown float parameter: " + n);
 }

@@ -18,6 +18,8 @@
 // tonemapped resolved frame; with --denoise / --denoise-temporal the filter starts from the resolved frame ("denoise_resolve" = 1).  One device only.
 // --denoise-layers with --denoise / --denoise-temporal and --expected-features N, N >= 2: the filter runs on the scattered layer alone and the analytic
 // background is put back afterwards ("denoise_layers" = 1, vr_layers.h); refused without them.
+// --denoise-filter 0|1 and --denoise-ridge X with --denoise-layers: 1 runs one pass of local regression on the scattered layer in the place of the a-trous
+// iterations ("denoise_filter" = 1, vr_regress.h), X is the ridge on its slopes ("denoise_ridge": 0 = zero order, or in [2^-20, 2^20]); refused without it.
 // --upsample F (2..4) with --denoise-layers (and so with a denoise flag and --expected-features N): the frame is rendered and filtered at -w x -h, its layer is
 // rebuilt at F times that size per axis under an expected-value guide of N rays at the large size (vr_upsample.h), and the tonemapped F w x F h frame is
 // written; refused alone.
@@ -104,7 +106,7 @@ static void parse_cmd(int argc, char** argv) {
         if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments" || arg == "--denoise-layers" || arg == "--resolve") {      // --denoise*, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
-        } else if (arg == "--upsample") {
+        } else if (arg == "--upsample" || arg == "--denoise-filter" || arg == "--denoise-ridge") {
             a.next();                                           // main()
         } else if (arg == "--no-resize" || arg == "--hidden" || arg == "--no-decoration" || arg == "--floating" || arg == "--maximised" || arg == "---debug") {
         } else if (arg == "--output") out_filename = a.next();
@@ -186,6 +188,8 @@ int main(int argc, char** argv) {
     int expected_skip = -1;     // --expected-skip 0|1 (with --expected-features): whether that pass drops the steps of empty space (same frame either way); -1: the renderer's default
     bool resolve = false;       // --resolve (with --expected-features N >= 2): the control variate on the expected coverage, alone or in front of the filter
     bool layers = false;        // --denoise-layers (with a denoise flag and --expected-features N >= 2): the filter runs on the scattered layer alone ("denoise_layers" = 1, vr_layers.h)
+    int filter = -1;            // --denoise-filter 0|1 (with --denoise-layers): one pass of local regression in the iterations' place (vr_regress.h); -1: not given
+    float ridge = -1.f;         // --denoise-ridge X (with --denoise-layers): the ridge of that regression; -1: not given, the renderer's default
     int upsample = 0;           // --upsample F (with --denoise-layers): the frame written is F times -w x -h, rebuilt from the filtered layer (vr_upsample.h); 0: off
     bool reject_given = false, moments = false;      // moments: --denoise-moments, the filter's variance from the history's luminance moments (low-spp sequences)
     std::vector<int> devices;
@@ -212,6 +216,15 @@ int main(int argc, char** argv) {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-features");
                 expected_rays = std::stoi(argv[++i]);
                 if (expected_rays < 1 || expected_rays > kExpectedMaxRays) throw std::runtime_error("--expected-features: the rays per pixel axis must be 1..4");
+            } else if (arg == "--denoise-filter") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --denoise-filter");
+                const std::string v = argv[++i];
+                if (v != "0" && v != "1") throw std::runtime_error("--denoise-filter: 0 (the a-trous iterations) or 1 (one pass of local regression)");
+                filter = v == "1" ? 1 : 0;
+            } else if (arg == "--denoise-ridge") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --denoise-ridge");
+                ridge = std::stof(argv[++i]);
+                if (!regress_ridge_ok(ridge)) throw std::runtime_error("--denoise-ridge: the ridge must be 0 (zero order) or in [2^-20, 2^20]");
             } else if (arg == "--upsample") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --upsample");
                 upsample = std::stoi(argv[++i]);
@@ -233,6 +246,8 @@ int main(int argc, char** argv) {
         if (resolve && expected_rays < 2) throw std::runtime_error("--resolve needs --expected-features N with N >= 2: one ray gives the coverage of the pixel's centre, not of its area");
         if (layers && !denoise) throw std::runtime_error("--denoise-layers needs --denoise or --denoise-temporal: it is a setting of their filter");
         if (layers && expected_rays < 2) throw std::runtime_error("--denoise-layers needs --expected-features N with N >= 2: the expected coverage of that pass splits the frame into background and scattered layer");
+        if (filter >= 0 && !layers) throw std::runtime_error("--denoise-filter needs --denoise-layers: the regression is defined on the scattered layer");
+        if (ridge >= 0.f && !layers) throw std::runtime_error("--denoise-ridge needs --denoise-layers: it is a setting of the regression on the scattered layer");
         if (upsample > 0 && !layers) throw std::runtime_error("--upsample needs --denoise-layers: the filtered scattered layer is what it upsamples");
         if (expected_rays > 0 && !denoise && !resolve) throw std::runtime_error("--expected-features needs --denoise, --denoise-temporal or --resolve: it chooses the guide of their filter");
         if (expected_skip >= 0 && expected_rays == 0) throw std::runtime_error("--expected-skip needs --expected-features: it is a setting of that pass");
@@ -272,6 +287,8 @@ int main(int argc, char** argv) {
             renderer->denoise_moments = moments ? 1 : 0;
             renderer->denoise_resolve = resolve && denoise ? 1 : 0;
             renderer->denoise_layers = layers ? 1 : 0;
+            if (filter >= 0) renderer->set_denoise_filter(filter);
+            if (ridge >= 0.f) renderer->set_denoise_ridge(ridge);
             if (expected_skip >= 0) renderer->expected_skip = expected_skip;
             parts.push_back(renderer);
         }

@@ -1054,6 +1054,7 @@ void RendererHIP::download_variance(float* rgba) {
 // temporal (denoise_temporal, vr_temporal.h): between prepare and the iterations the frame is blended with the history, and the iterations start
 // from the new history's colour and variance instead.  layers (denoise_layers, vr_layers.h): the frame all of this reads is the resolved frame's
 // scattered layer S (resolve, then a split), the last iteration writes a buffer F of its own, and a merge writes `denoised` and the layer from F.
+// regress (denoise_filter, vr_regress.h; with layers only): one kernel from what iteration 0 would read to F takes the iterations' place.
 // Every buffer the call needs is allocated before its first launch, so a failed allocation
 // leaves the last result and the history as they were.
 void RendererHIP::denoise() { run_denoise("denoise", false); }
@@ -1071,6 +1072,9 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (denoise_resolve != 0) check_resolve(me + "denoise_resolve = 1: ", whole_frame_gathered);
     const bool layers = denoise_layers != 0;          // vr_layers.h: the filter runs on the scattered layer, between a split and a merge
     if (layers) check_resolve(me + "denoise_layers = 1: ", whole_frame_gathered);
+    const bool regress = denoise_filter != 0;         // vr_regress.h: one pass of local regression in the place of the iterations
+    if (regress && !layers) throw std::runtime_error(me + "denoise_filter = 1 needs denoise_layers = 1: the regression is defined on the scattered layer S with S.a = the expected coverage");
+    if (regress && !regress_ridge_ok(denoise_ridge)) throw std::runtime_error(me + "denoise_ridge must be 0 (zero order) or in [2^-20, 2^20]");
     const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
     if (ragged()) {
         for (int32_t c : tile_n_)
@@ -1097,8 +1101,9 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     ensure_buffer(sized_.dn_guide, px * 8 * sizeof(float));
     ensure_buffer(sized_.dn_var[0], px * sizeof(float));
     ensure_buffer(sized_.denoised, px * 4 * sizeof(float));
-    if (N >= 2) { ensure_buffer(sized_.dn_var[1], px * sizeof(float)); ensure_buffer(sized_.dn_color[0], px * 4 * sizeof(float)); }
-    if (N >= 3) ensure_buffer(sized_.dn_color[1], px * 4 * sizeof(float));
+    const int32_t passes = regress ? 0 : N;           // the a-trous iterations this call launches
+    if (passes >= 2) { ensure_buffer(sized_.dn_var[1], px * sizeof(float)); ensure_buffer(sized_.dn_color[0], px * 4 * sizeof(float)); }
+    if (passes >= 3) ensure_buffer(sized_.dn_color[1], px * 4 * sizeof(float));
     if (layers) { ensure_buffer(sized_.ly_split, px * 4 * sizeof(float)); ensure_buffer(sized_.ly_filtered, px * 4 * sizeof(float)); ensure_buffer(sized_.layer, px * 4 * sizeof(float)); }
     const float vscale = variance_scale(sample);      // download_variance's factor
     if (denoise_resolve != 0 || layers) run_resolve();      // vr_resolve.h: the filter starts from y, with the frame's own variance
@@ -1139,7 +1144,11 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         first = hist.color[to].get();
     }
     if (N == 0) VR_HIP(hipMemcpyAsync(result->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
-    for (int32_t k = 0; k < N; ++k) {
+    if (regress && N > 0) {                           // the iterations' input in, the merge's input out: no ping-pong, no variance
+        launch_denoise_regress(first->as<float>(), sized_.dn_guide->as<float>(), W, H, sg, denoise_ridge, result->as<float>(), stream);
+        VR_HIP(hipGetLastError());
+    }
+    for (int32_t k = 0; k < passes; ++k) {
         const float* cin = k == 0 ? first->as<float>() : sized_.dn_color[(k - 1) & 1]->as<float>();
         float* cout = k == N - 1 ? result->as<float>() : sized_.dn_color[k & 1]->as<float>();
         float* vout = k == N - 1 ? nullptr : sized_.dn_var[(k + 1) & 1]->as<float>();
@@ -1169,6 +1178,13 @@ void RendererHIP::set_denoise_moments(int v) {
 }
 void RendererHIP::set_denoise_resolve(int v) {
     set_history_switch(denoise_resolve, v, "denoise_resolve: 0 (the filter starts from the framebuffer) or 1 (from the frame resolved against the expected coverage)");
+}
+void RendererHIP::set_denoise_filter(int v) {
+    set_history_switch(denoise_filter, v, "denoise_filter: 0 (the a-trous iterations) or 1 (one pass of local regression on the scattered layer; needs denoise_layers = 1)");
+}
+void RendererHIP::set_denoise_ridge(float v) {
+    if (!regress_ridge_ok(v)) throw std::runtime_error("denoise_ridge must be 0 (zero order) or in [2^-20, 2^20]");
+    denoise_ridge = v;
 }
 void RendererHIP::set_denoise_layers(int v) {
     set_history_switch(denoise_layers, v, "denoise_layers: 0 (the filter runs on the frame) or 1 (on the scattered layer, the background of the expected coverage put back afterwards)");

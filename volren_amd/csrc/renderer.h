@@ -24,6 +24,7 @@
 #include "grids.h"
 #include "transferfunc.h"
 #include "vr_device.h"
+#include "vr_regress.h"
 #include "vr_scene.h"
 
 namespace vr {
@@ -259,6 +260,16 @@ struct RendererHIP {
     void set_denoise_layers(int v);
     int denoise_layers = 0;
     void download_denoised_layer(float* rgba);
+    // The one-pass regression (vr_regress.h).  denoise_filter = 1: with denoise_layers = 1, one 11 x 11 pass of weighted local regression on the scattered layer
+    // takes the place of the a-trous iterations of denoise() and denoise_temporal(); resolve, split, the temporal pass with rejection or moments and the merge stay
+    // as they are, denoise_iterations = 0 still leaves the layer unfiltered, and the variance is neither read nor written by the pass.  Without denoise_layers = 1
+    // the calls throw before anything is launched, and whatever denoise_layers refuses they refuse (0 is today's calls exactly).  set_denoise_filter: 0 or 1,
+    // throws otherwise; a change drops the history.  denoise_ridge: the ridge lambda on the fit's seven slopes, 0 (zero order: the normalised weighted mean) or
+    // in [2^-20, 2^20]; set_denoise_ridge throws for anything else.
+    void set_denoise_filter(int v);
+    int denoise_filter = 0;
+    void set_denoise_ridge(float v);
+    float denoise_ridge = kRegressDefaultRidge;
     // The layer upsampled under a full-resolution guide (vr_upsample.h).  upsample(factor, rays): the frame at factor x the renderer's size per axis, rebuilt from
     // the layer of the last denoise() / denoise_temporal() with denoise_layers = 1 and an expected-value pass of `rays` rays per axis at that size, which the call
     // marches into a buffer of its own with the scene and camera as they are now -- the caller keeps them as they were at the denoise call.  expected_skip and
@@ -396,7 +407,7 @@ private:
     } sized_;
     void download_whole(const DeviceBufferPtr& b, float* out, const char* absent);      // throws `absent` when b is null; else flushes and copies all of b
     void run_resolve();                                       // resolve()'s launches, after check_resolve
-    void set_history_switch(int& field, int v, const char* refusal);      // the body of set_denoise_moments / _resolve / _layers, each with its own refusal
+    void set_history_switch(int& field, int v, const char* refusal);      // the body of set_denoise_moments / _resolve / _layers / _filter, each with its own refusal
     DenoiseSigma sigma() const { return { denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] }; }      // denoise_sigma as the kernels take it
     DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
     bool expected_stats_valid_ = false;                // ... which that pass filled

@@ -102,6 +102,9 @@ void launch_resolve(const SceneParams& P, const float* fb, const float* features
 // features -> out (W*H*4: the frame with the background back) and L (W*H*4: the layer).  One kernel each; outputs must not overlap inputs.
 void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream);
 void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream);
+// The one-pass regression of vr_regress.h on a whole W x H frame, in the place of the a-trous iterations: S (W*H*4: what iteration 0 would read, alpha = the
+// coverage) and guide (W*H*8: launch_denoise_prepare's) -> F (W*H*4, what launch_layers_merge reads).  One kernel; F must not overlap the inputs.
+void launch_denoise_regress(const float* S, const float* guide, int32_t W, int32_t H, const DenoiseSigma& sg, float ridge, float* F, hipStream_t stream);
 // The upsampling of vr_upsample.h.  P: the scene with the HI resolution W x H = f w x f h (f in 2..4, or it throws); lo_layer (w*h*4: launch_layers_merge's L),
 // lo_guide (w*h*8: launch_denoise_prepare's guide), hi_features (W*H*8: an expected-value pass at the hi resolution, `rays` rays per axis) -> out (W*H*4: the hi
 // frame) and L (W*H*4: the hi layer).  One kernel; outputs must not overlap inputs.

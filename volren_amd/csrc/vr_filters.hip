@@ -1,6 +1,6 @@
 // vr_filters.hip -- the image-space kernels (gfx950): everything that reads or writes whole frames or tiles of them after the path tracer.
 // The a-trous denoiser (vr_denoise.h: prepare, iterations) with its temporal accumulation (vr_temporal.h, vr_moments.h), the error estimate of adaptive
-// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), the layered filter's split and merge (vr_layers.h), the layer's upsampling under a full-resolution guide (vr_upsample.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
+// sampling (vr_adaptive.h), the control variate on the expected coverage (vr_resolve.h), the layered filter's split and merge (vr_layers.h), its one-pass regression (vr_regress.h), the layer's upsampling under a full-resolution guide (vr_upsample.h), tonemap.glsl, and tile pack / unpack for the multi-GPU gather.  One thread per pixel; the per-pixel kernels use
 // the wave-tiled layout of vr_tiles.h (16x16 tiles of four 8x8 wavefronts, like the accumulate kernel) for the 2-D locality of their footprints.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include "vr_device.h"
 #include "vr_layers.h"
 #include "vr_moments.h"
+#include "vr_regress.h"
 #include "vr_resolve.h"
 #include "vr_temporal.h"
 #include "vr_upsample.h"
@@ -313,6 +314,60 @@ void launch_layers_merge(const float* F, const float* B, const float* features, 
     hipLaunchKernelGGL(layers_merge_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(F),
                        reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(features), W, H, reinterpret_cast<float4*>(out),
                        reinterpret_cast<float4*>(L));
+}
+
+// The one-pass regression of vr_regress.h ("denoise_filter" = 1), in the place of the a-trous iterations: one workgroup per 16 x 16 tile.  Stages the tile's
+// 26 x 26 footprint (16 x 16 plus a halo of 5) as records of three float4 -- S and the two float4 of the guide, 48 B a texel, 32448 B of static LDS: four
+// workgroups, 16 waves, a CU -- once, one barrier; threads outside a ragged frame stage and wait with the others, and texels off the frame hold a record no tap
+// reads (the lane code skips such taps by their coordinates).  Then a pixel runs its 121 taps from LDS, three ds_read_b128 a tap, with the 60 sums and the solve
+// in registers, and writes one dwordx4.  The 48-byte records put the three reads of a 16-lane group two and three deep on some banks (MI355X: 64 banks, the
+// row pitch 26 texels); a tap is some 300 VALU instructions -- the edge factors' pow_ and two exp_, the 60 multiply-add pairs -- against 12 LDS cycles without
+// conflicts, so the layout is left as stage_window writes it.  VR_REGRESS_GLOBAL_TAPS = 1 builds the form whose taps read the three float4 from global memory
+// instead (no LDS, no barrier), for comparison.  No atomics, no scratch.
+#ifndef VR_REGRESS_GLOBAL_TAPS
+#define VR_REGRESS_GLOBAL_TAPS 0
+#endif
+using RegressWindow = TileWindow<kRegressRadius>;
+struct RegressTexel { float4 S, ga, gb; };
+struct RegressWindowDev {
+    const RegressTexel* win;     // the staged footprint
+    int32_t at;                  // the pixel's own texel in it
+    __device__ __forceinline__ void tap(int32_t dx, int32_t dy, float S[4], float g[8]) const {
+        const RegressTexel& t = win[at + dy * RegressWindow::kFoot + dx];
+        unpack4(t.S, S); unpack4(t.ga, g); unpack4(t.gb, g + 4);
+    }
+};
+struct RegressGlobalDev {
+    const float4* __restrict__ S;
+    const float4* __restrict__ g;
+    int32_t at, W;               // the pixel's own index, the frame's width
+    __device__ __forceinline__ void tap(int32_t dx, int32_t dy, float Sq[4], float gq[8]) const {
+        const int32_t i = at + dy * W + dx;
+        unpack4(S[i], Sq); unpack4(g[2 * i], gq); unpack4(g[2 * i + 1], gq + 4);
+    }
+};
+__global__ void __launch_bounds__(256)
+denoise_regress_kernel(const float4* __restrict__ S, const float4* __restrict__ guide, int32_t W, int32_t H, const DenoiseSigma sg, float ridge, float4* __restrict__ F) {
+    const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
+#if !VR_REGRESS_GLOBAL_TAPS
+    __shared__ RegressTexel win[RegressWindow::kTexels];
+    const RegressWindow window = RegressWindow::of((int32_t)blockIdx.x, W);
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    stage_window(win, window, W, H, RegressTexel{ zero, zero, zero }, [&](int32_t i) { return RegressTexel{ S[i], guide[2 * i], guide[2 * i + 1] }; });
+#endif
+    if (q.px >= W || q.py >= H) return;
+    float f[4];
+#if VR_REGRESS_GLOBAL_TAPS
+    regress_pixel(RegressGlobalDev{ S, guide, q.py * W + q.px, W }, W, H, q.px, q.py, sg, ridge, f);
+#else
+    regress_pixel(RegressWindowDev{ win, window.at(q.px, q.py) }, W, H, q.px, q.py, sg, ridge, f);
+#endif
+    F[q.py * W + q.px] = pack4(f);
+}
+void launch_denoise_regress(const float* S, const float* guide, int32_t W, int32_t H, const DenoiseSigma& sg, float ridge, float* F, hipStream_t stream) {
+    if (W <= 0 || H <= 0) return;
+    hipLaunchKernelGGL(denoise_regress_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(S),
+                       reinterpret_cast<const float4*>(guide), W, H, sg, ridge, reinterpret_cast<float4*>(F));
 }
 
 // The upsampling of vr_upsample.h: one workgroup per 16 x 16 tile of the HI frame, F = hi / lo per axis at compile time (the window's size and the divisions

@@ -8,14 +8,14 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
+               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
                "expected_skip", "expected_stats")
 _READ_ONLY_INT_FIELDS = ("n_grid_frames", "last_launches", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
                          "kernel_wide", "adaptive_rounds", "seed_table_samples", "seed_table_fills")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
                  "tf_window_left": 1, "tf_window_width": 1, "cam_pos": 3, "cam_dir": 3, "cam_up": 3, "cam_fov": 1,
-                 "volume_transform": 16, "denoise_sigma": 5, "denoise_alpha": 1, "denoise_reject": 1}
+                 "volume_transform": 16, "denoise_sigma": 5, "denoise_alpha": 1, "denoise_reject": 1, "denoise_ridge": 1}
 
 
 def _f32(a):
@@ -291,7 +291,9 @@ class Renderer:
     # ---- denoiser ----
     def denoise(self, sync=True):
         """The a-trous filter of the current frame (include/volren_amd.h vr_denoise): needs `variance = 1` for all its samples and a render_features
-        since the last resize; `denoise_iterations` / `denoise_sigma` set it up."""
+        since the last resize; `denoise_iterations` / `denoise_sigma` set it up.  `denoise_filter = 1` (default 0; needs `denoise_layers = 1`; a change drops
+        the history) runs one 11 x 11 pass of weighted local regression on the scattered layer in the iterations' place (csrc/vr_regress.h); `denoise_ridge`
+        is the ridge on its seven slopes, 0 (the default: zero order) or in [2^-20, 2^20]."""
         _lib.check(self._L.vr_denoise(self._h))
         if sync:
             self.synchronize()
@@ -626,6 +628,13 @@ class ShardedRenderer:
     denoise_layers = _part0("denoise_layers", True,
         """Whether denoise() / denoise_temporal() filter the scattered layer alone and put the analytic background back (Renderer.denoise_layers): part 0's
         field, which holds the gathered frame and guide and runs it; setting it sets every part's.""")
+
+    denoise_filter = _part0("denoise_filter", True,
+        """Whether one pass of local regression takes the place of the a-trous iterations (Renderer.denoise, csrc/vr_regress.h): part 0's field, which holds
+        the gathered frame and guide and runs the filter; setting it sets every part's.""")
+
+    denoise_ridge = _part0("denoise_ridge", True,
+        """The ridge of that regression, 0 (zero order) or in [2^-20, 2^20]: part 0's field; setting it sets every part's.""")
 
     def denoised_layer(self):
         return self.parts[0].denoised_layer()
