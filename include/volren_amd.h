@@ -478,6 +478,37 @@ int vr_math_sweep(int fn, uint32_t first, long long count, float b, float* out);
  * 4 texel, 5 sky, 6 light sample, 7 transfer function) in compile-time form `form`, on the scene as the renderer's next launch would read it.  in: 4 32-bit words per
  * item; out: 1, 1, 1, 1, 3, 3, 7, 4 floats per item; host arrays.  VR_ERR_RUNTIME for a form the scene cannot serve (the message says why). */
 int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, long long n);
+/* test hook: ONE launcher of the image-space kernels (volren_amd/csrc/vr_device.h, section vr_filters.hip) on host arrays of the caller's.  The arrays of
+ * `in` go up into fresh device buffers, the stage's launch_* runs once on the renderer's stream, the call waits, and the arrays of `out` come back.  No buffer,
+ * flag or history of the renderer changes; the renderer gives its device and stream, and to the two scene-bound stages (resolve, upsample) its scene.
+ * W x H: the frame (upsample: the LO frame; the outputs are f W x f H).  in: 6 pointers, out: 5 pointers, NULL where the stage has none or an optional one is
+ * left out; params: 40 floats -- [0..4] sigma (colour, normal, depth, coverage, albedo), [5] an integer i0, [6] a float x, [7] tau, [8] an integer i1,
+ * [9..21] the current camera, [22..34] the history's (pos 3, cam_transform 9 column-major, cam_z), the rest 0.  float arrays of 4 bytes, counts and ids int32.
+ *   stage                 launcher                 in                                                            params               out
+ *   0 prepare             launch_denoise_prepare   moments S W*H*4, features W*H*8, [counts, one per tile]       i0 = n, x = vscale   v W*H, guide W*H*8
+ *   1 atrous              launch_denoise_atrous    colour W*H*4, v W*H, guide W*H*8                              i0 = step, sigma     colour W*H*4, [v W*H]
+ *   2 temporal            launch_denoise_temporal  colour, v, guide, [hist colour W*H*4, hist record W*H*4,      x = alpha, tau,      colour, record W*H*4 each, v W*H,
+ *                                                  [hist moments W*H*4]]                                         i1 = same_cam, both  [moments W*H*4], [scratch W*H*4 =
+ *                                                                                                                cameras, sigma       (T, N_h, z2, has)]
+ *       out[3] set: the moments form (vr_moments.h; in[5] with a history); tau > 0: the rejection form, out[4] must be set; else the plain pass
+ *   3 resolve             launch_resolve           fb W*H*4, features W*H*8                                      i0 = rays            B, Pq, out W*H*4 each
+ *   4 split               launch_layers_split      y W*H*4, B W*H*4, features W*H*8                                                   S W*H*4
+ *   5 merge               launch_layers_merge      F W*H*4, B W*H*4, features W*H*8                                                   out, L W*H*4 each
+ *   6 regress             launch_denoise_regress   S W*H*4, guide W*H*8                                          x = ridge, sigma     F W*H*4
+ *   7 upsample            launch_upsample          lo layer W*H*4, lo guide W*H*8, hi features fW*fH*8           i0 = rays, i1 = f,   out, L fW*fH*4 each
+ *                                                                                                                sigma
+ *   8 adaptive error      launch_adaptive_error    fb W*H*4, moments W*H*4, tile ids i0, counts i0               i0 = the tiles       e_t i0
+ * Stages 3 and 7 read the scene as the renderer's next launch would (7: with the resolution f W x f H, as vr_upsample forms it) and need W x H to be the
+ * renderer's resolution.  Everything that can be checked without a device is checked before the device is looked for: VR_ERR_ARG for a NULL renderer or array,
+ * an unknown stage, W, H outside 1..4096, step outside 1..2^20, rays outside 1..4, f outside 2..4, n < 1, a tile id outside the frame, tau < 0, a parameter
+ * that is not finite, the moments and the rejection form together, a history given in part; and, with a device, for a W x H that is not the renderer's in stages 3 and 7.
+ * The values INSIDE the arrays are the caller's business: tests/filter_cases.py holds the catalogue the suite runs (frames of 64 x 48 at most, built to the edges
+ * of what the product's own passes can hand these kernels), and every case of it passes the host build of its stage, range-checked, in
+ * tests/test_filter_cases_host.py before tests/test_gpu_filter_probe.py runs it on a device. */
+#define VR_FILTER_PROBE_IN 6
+#define VR_FILTER_PROBE_OUT 5
+#define VR_FILTER_PROBE_PARAMS 40
+int vr_filter_probe(vr_renderer* r, int stage, int W, int H, const void* const* in, float* const* out, const float* params);
 /* voldata::Volume::to_brick_grid + BrickGrid serialisation: encode a dense float grid (x fastest) and write it as a .brick
  * container (SURVEY.md 2.3 layout); transform may be NULL (identity).  Host only, needs no device. */
 int vr_write_brick_from_dense(const float* voxels, int nx, int ny, int nz, const float* transform, const char* path);

@@ -54,6 +54,14 @@ def regress(S, guide, ridge, sigma=hk_denoise.DEFAULT_SIGMA):
     return F
 
 
+def dropped(S, guide, ridge, sigma=hk_denoise.DEFAULT_SIGMA):
+    """regress() with the header's own counter: (F, int32 [H][W]: how many columns regress_solve dropped at each pixel, -1 where the pixel never reaches the solve)"""
+    h, w = S.shape[:2]
+    F, n = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32)
+    lib().hk_regress_dropped(w, h, _p(_f32(S, (h, w, 4))), _p(_f32(guide, (h, w, 8))), _p(np.asarray(sigma, np.float32)), C.c_float(float(ridge)), _p(F), _p(n))
+    return F, n
+
+
 def solve(A, b, floor):
     """Host build of regress_solve: A [8][8] (upper triangle), b [8][3] -> beta_0 [3]."""
     out = np.zeros(3, np.float32)
@@ -132,21 +140,54 @@ def spec_sums(S, guide, sigma=hk_denoise.DEFAULT_SIGMA):
     return A, b
 
 
-def spec(S, guide, ridge, sigma=hk_denoise.DEFAULT_SIGMA):
-    """float64 F [H][W][4]: kappa_p = 0 -> 0; A_00 <= 2^-20 -> rgb 0; ridge 0 -> b_0 / A_00; else beta_0 of (A + ridge A_00 diag(0, 1, .. 1)) beta = b.  In exact
-    arithmetic no pivot falls below the ridge, so no column is dropped."""
+PIVOT_SHARE = 2.0 ** -12
+
+
+def spec_solve(M, b, floor):
+    """float64 beta_0 [..., 3] of M beta = b (M [..., 8][8] symmetric, ridged; b [..., 8][3]) by the header's elimination in the order 0 .. 7: column k > 0 is kept
+    iff its pivot d_k > floor and d_k > 2^-12 a_k, a_k = M_kk before the elimination; a dropped column's coefficient is 0 and the others are fitted without it.
+    -> (beta_0, share [..., 8] = d_k / a_k, kept [..., 8])"""
+    M, b = np.array(M, np.float64), np.array(b, np.float64)
+    n = TERMS
+    a = np.stack([M[..., k, k] for k in range(n)], axis=-1)
+    d, kept = np.zeros_like(a), np.ones(a.shape, bool)
+    with np.errstate(all="ignore"):
+        for k in range(n):
+            d[..., k] = M[..., k, k]
+            if k:
+                kept[..., k] = (d[..., k] > floor) & (d[..., k] > PIVOT_SHARE * a[..., k])
+            for i in range(k + 1, n):
+                l = np.where(kept[..., k], M[..., k, i] / d[..., k], 0.0)
+                for j in range(i, n):
+                    M[..., i, j] = M[..., i, j] - l * M[..., k, j]
+                b[..., i, :] = b[..., i, :] - l[..., None] * b[..., k, :]
+                M[..., k, i] = l
+        beta = np.zeros_like(b)
+        for k in range(n - 1, -1, -1):
+            v = b[..., k, :] / d[..., k, None]
+            for i in range(k + 1, n):
+                v = v - M[..., k, i, None] * beta[..., i, :]
+            beta[..., k, :] = np.where(kept[..., k, None], v, 0.0)
+        return beta[..., 0, :], d / a, kept
+
+
+def spec(S, guide, ridge, sigma=hk_denoise.DEFAULT_SIGMA, detail=False):
+    """float64 F [H][W][4]: kappa_p = 0 -> 0; A_00 <= 2^-20 -> rgb 0; ridge 0 -> b_0 / A_00; else beta_0 of (A + ridge A_00 diag(0, 1, .. 1)) beta = b by
+    spec_solve.  In exact arithmetic no pivot falls below the ridge, so the floor drops nothing; a column that keeps no more than 2^-12 of its own diagonal is
+    dropped.  detail: -> (F, share [H][W][8], kept [H][W][8]) -- a pixel with a share near 2^-12 may decide otherwise in float32."""
     A, b = spec_sums(S, guide, sigma)
     kp = np.asarray(guide, np.float64)[..., 3]
     a00 = A[..., 0, 0]
     live = (kp != 0) & (a00 > MIN_WEIGHT)
     safe = np.where(live, a00, 1.0)
+    share, kept = np.ones(a00.shape + (TERMS,)), np.ones(a00.shape + (TERMS,), bool)
     if ridge == 0:
         Ct = b[..., 0, :] / safe[..., None]
     else:
         M = A + (float(ridge) * safe)[..., None, None] * np.diag([0.0] + [1.0] * (TERMS - 1))
         M = np.where(live[..., None, None], M, np.eye(TERMS))
-        Ct = np.linalg.solve(M, b)[..., 0, :]
+        Ct, share, kept = spec_solve(M, b, PIVOT_FLOOR * float(ridge) * safe)
     F = np.zeros(S.shape[:2] + (4,))
     F[..., :3] = np.where(live[..., None], kp[..., None] * Ct, 0.0)
     F[..., 3] = kp
-    return F
+    return (F, share, kept) if detail else F

@@ -41,6 +41,17 @@ void hk_regress_solve(const float* A, const float* b, float floor, float* Ct) {
     regress_solve(a, r, floor, Ct);
 }
 
+// the filter once more, with the header's own counter: dropped = W*H, how many columns regress_solve dropped at each pixel, -1 where the pixel never reaches the
+// solve (kappa_p = 0, A_00 at or below the smallest weight, or ridge 0)
+void hk_regress_dropped(int W, int H, const float* S, const float* guide, const float* sigma, float ridge, float* F, int32_t* dropped) {
+    const DenoiseSigma sg{ sigma[0], sigma[1], sigma[2], sigma[3], sigma[4] };
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const size_t i = (size_t)y * W + x;
+            regress_pixel(HostSrc{ S, guide, W, x, y }, W, H, x, y, sg, ridge, F + 4 * i, dropped + i);
+        }
+}
+
 // (radius, terms, smallest weight, smallest depth, pivot floor, smallest ridge, largest ridge, default ridge)
 void hk_regress_constants(float* out) {
     out[0] = (float)kRegressRadius; out[1] = (float)kRegressTerms; out[2] = kRegressMinWeight; out[3] = kRegressMinDepth; out[4] = kRegressPivotFloor;

@@ -56,6 +56,49 @@ def test_no_device_fails_loudly():
     assert lib.vr_probe(C.c_void_p(1), 0, 2, words, out, 1) == 2 and b"no HIP device" in lib.vr_last_error()      # (the handle is not touched before the device check)
     assert lib.vr_probe(None, 0, 2, words, out, 1) == 3                                       # VR_ERR_ARG: there is no renderer to probe without a device ...
     assert lib.vr_probe(C.c_void_p(1), 0, 2, None, out, 1) == 3 and lib.vr_probe(C.c_void_p(1), 0, 2, words, out, -1) == 3      # ... and the arguments are checked first
+    # vr_filter_probe: the same order -- the renderer, the arguments, the device; the handle is not touched before the device check
+    a = (C.c_float * (4 * 4 * 8))()
+    ids = (C.c_int32 * 1)(0)
+    ins = (C.c_void_p * 6)(C.addressof(a), C.addressof(a), C.addressof(a), None, None, None)
+    outs = (C.c_void_p * 5)(C.addressof(a), C.addressof(a), C.addressof(a), None, None)
+    par = (C.c_float * 40)()
+    par[5] = 1.0
+    for stage in (0, 1, 2, 3, 4, 5, 6):
+        assert lib.vr_filter_probe(C.c_void_p(1), stage, 4, 4, ins, outs, par) == 2 and b"no HIP device" in lib.vr_last_error(), stage
+    assert lib.vr_filter_probe(None, 1, 4, 4, ins, outs, par) == 3 and b"null renderer" in lib.vr_last_error()
+    assert lib.vr_filter_probe(C.c_void_p(1), 9, 4, 4, ins, outs, par) == 3 and lib.vr_filter_probe(C.c_void_p(1), -1, 4, 4, ins, outs, par) == 3
+    assert lib.vr_filter_probe(C.c_void_p(1), 1, 0, 4, ins, outs, par) == 3 and lib.vr_filter_probe(C.c_void_p(1), 1, 4, 4097, ins, outs, par) == 3
+    assert lib.vr_filter_probe(C.c_void_p(1), 1, 4, 4, None, outs, par) == 3 and lib.vr_filter_probe(C.c_void_p(1), 1, 4, 4, ins, None, par) == 3
+    assert lib.vr_filter_probe(C.c_void_p(1), 1, 4, 4, ins, outs, None) == 3
+    assert lib.vr_filter_probe(C.c_void_p(1), 8, 4, 4, ins, outs, par) == 3 and b"required input" in lib.vr_last_error()      # the adaptive error needs four arrays
+    ins[2] = ins[3] = C.addressof(ids)
+    assert lib.vr_filter_probe(C.c_void_p(1), 8, 4, 4, ins, outs, par) == 2
+    ids[0] = 1
+    assert lib.vr_filter_probe(C.c_void_p(1), 8, 4, 4, ins, outs, par) == 3 and b"tile id" in lib.vr_last_error()           # a 4 x 4 frame has one tile
+    ins[2], ins[3] = C.addressof(a), None
+    par[5] = 0.0
+    assert lib.vr_filter_probe(C.c_void_p(1), 1, 4, 4, ins, outs, par) == 3 and b"step" in lib.vr_last_error()
+    assert lib.vr_filter_probe(C.c_void_p(1), 0, 4, 4, ins, outs, par) == 3 and lib.vr_filter_probe(C.c_void_p(1), 3, 4, 4, ins, outs, par) == 3
+    par[5] = 2.5
+    assert lib.vr_filter_probe(C.c_void_p(1), 1, 4, 4, ins, outs, par) == 3 and b"whole" in lib.vr_last_error()
+    par[5], par[8] = 2.0, 5.0
+    assert lib.vr_filter_probe(C.c_void_p(1), 7, 4, 4, ins, outs, par) == 3 and b"f must" in lib.vr_last_error()
+    par[8] = 0.0
+    par[7] = 3.0                                                                                 # rejection: the scratch read-back must be asked for ...
+    assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3 and b"scratch" in lib.vr_last_error()
+    outs[4] = C.addressof(a)
+    assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 2
+    outs[3] = C.addressof(a)                                                                     # ... and does not go with the moments form
+    assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3 and b"do not go together" in lib.vr_last_error()
+    outs[3] = outs[4] = None
+    par[7] = -1.0
+    assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3
+    par[7] = 0.0
+    ins[3] = C.addressof(a)                                                                      # half a history
+    assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3 and b"history" in lib.vr_last_error()
+    ins[3] = None
+    par[20] = float("nan")
+    assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3 and b"not finite" in lib.vr_last_error()
     hs = C.c_void_p()
     devs = (C.c_int * 2)(0, 0)
     assert lib.vr_sharded_create(C.byref(hs), devs, 2, 64, 64) == 2 and not hs.value      # the sharded renderer has no CPU path either

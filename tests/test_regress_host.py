@@ -29,6 +29,7 @@ def test_the_constants_are_the_headers():
 
 # ---- 1: the host build is the header ------------------------------------------------------------------------------------------------------------------
 # largest |host - float64 statement| of F.rgb per channel over both frame sizes, recorded from the host build; asserted at 4x
+# (tests/test_filter_cases_host.py holds crafted frames of larger values to these too, times magnitude / the magnitude measured here: its _scaled)
 # (ridge 0, ridge 1)
 RECORDED = {"c2": ((1.96e-7, 2.14e-7, 1.71e-7), (2.58e-7, 2.55e-7, 1.76e-7)),
             "c3env": ((2.56e-8, 2.21e-8, 3.32e-8), (2.60e-8, 2.57e-8, 4.31e-8)),

@@ -61,6 +61,7 @@ _SIGNATURES = {
     **_sig([ci, vp, vp, vp, ci], "vr_math_probe"),
     **_sig([ci, C.c_uint32, ll, cf, vp], "vr_math_sweep"),
     **_sig([vp, ci, ci, vp, vp, ll], "vr_probe"),
+    **_sig([vp, ci, ci, ci, vp, vp, vp], "vr_filter_probe"),
     **_sig([vp, ci, ci, ci, vp, cs], "vr_write_brick_from_dense"),
     **_sig([vp, ci, ci, ci, cf, cf, vp, cs], "vr_write_dense"),
     **_sig([vp, ci, ci, ci, vp, vp, vp], "vr_encode_dense_stats"),

@@ -839,6 +839,53 @@ int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, lon
     return guard([&] { use_device(r); r->impl.probe(what, form, static_cast<const uint32_t*>(in), out, (size_t)n); });
 }
 
+// test hook: one launcher of the image-space kernels on host arrays (include/volren_amd.h).  What needs no device is checked first; nullptr = the arguments are fine
+static const char* filter_probe_error(int stage, int W, int H, const void* const* in, float* const* out, const float* p) {
+    if (stage < 0 || stage > 8) return "vr_filter_probe: unknown stage";
+    if (W < 1 || H < 1 || W > 4096 || H > 4096) return "vr_filter_probe: W and H must be in 1..4096";
+    if (!in || !out || !p) return "vr_filter_probe: null argument";
+    static const int need_in[9] = { 2, 3, 3, 2, 3, 3, 2, 3, 4 }, need_out[9] = { 2, 1, 3, 3, 1, 2, 1, 2, 1 };      // the arrays a stage cannot do without: the first of each list
+    for (int k = 0; k < need_in[stage]; ++k) if (!in[k]) return "vr_filter_probe: a required input array is null";
+    for (int k = 0; k < need_out[stage]; ++k) if (!out[k]) return "vr_filter_probe: a required output array is null";
+    for (int k = 0; k < VR_FILTER_PROBE_PARAMS; ++k) if (!std::isfinite(p[k])) return "vr_filter_probe: a parameter is not finite";
+    const float i0 = p[5], i1 = p[8];
+    if (i0 != std::floor(i0) || i1 != std::floor(i1)) return "vr_filter_probe: an integer parameter is not whole";
+    switch (stage) {
+    case 0: if (i0 < 1.0f || i0 > 0x1p30f) return "vr_filter_probe: prepare needs 1 <= n <= 2^30"; break;
+    case 1: if (i0 < 1.0f || i0 > 0x1p20f) return "vr_filter_probe: atrous needs 1 <= step <= 2^20"; break;
+    case 2: {
+        const bool have = in[3] != nullptr, moments = out[3] != nullptr;
+        if (p[7] < 0.0f) return "vr_filter_probe: tau must be >= 0";
+        if (moments && p[7] > 0.0f) return "vr_filter_probe: the moments form and the rejection form do not go together";
+        if ((in[4] != nullptr) != have || (in[5] != nullptr) != (have && moments)) return "vr_filter_probe: the history's arrays are not all set or all null";
+        if ((p[7] > 0.0f) != (out[4] != nullptr)) return "vr_filter_probe: the scratch read-back goes with tau > 0, and only with it";
+        break;
+    }
+    case 3: if (i0 < 1.0f || i0 > (float)vr::kExpectedMaxRays) return "vr_filter_probe: rays must be in 1..4"; break;
+    case 7:
+        if (i0 < 1.0f || i0 > (float)vr::kExpectedMaxRays) return "vr_filter_probe: rays must be in 1..4";
+        if (i1 < (float)vr::kUpsampleMinFactor || i1 > (float)vr::kUpsampleMaxFactor) return "vr_filter_probe: f must be in 2..4";
+        break;
+    case 8: {
+        if (i0 < 1.0f || i0 > 65536.0f) return "vr_filter_probe: the number of tiles must be in 1..65536";
+        const int32_t* ids = static_cast<const int32_t*>(in[2]);
+        const int32_t tiles = vr::tile_count(W, H);
+        for (int32_t k = 0; k < (int32_t)i0; ++k) if (ids[k] < 0 || ids[k] >= tiles) return "vr_filter_probe: a tile id outside the frame";
+        break;
+    }
+    default: break;
+    }
+    return nullptr;
+}
+int vr_filter_probe(vr_renderer* r, int stage, int W, int H, const void* const* in, float* const* out, const float* params) {
+    NEED(r);
+    if (const char* why = filter_probe_error(stage, W, H, in, out, params)) return fail(VR_ERR_ARG, why);
+    NEED_DEVICE();
+    if ((stage == 3 || stage == 7) && (W != r->impl.resolution.x || H != r->impl.resolution.y))
+        return fail(VR_ERR_ARG, "vr_filter_probe: resolve and upsample read the renderer's scene and need W x H to be its resolution");
+    return guard([&] { use_device(r); r->impl.filter_probe(stage, W, H, in, out, params); });
+}
+
 int vr_write_brick_from_dense(const float* voxels, int nx, int ny, int nz, const float* transform, const char* path) {
     if (!voxels || !path || nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_ARG, "bad arguments");
     return guard([&] {

@@ -1017,6 +1017,115 @@ void RendererHIP::probe(int what, int form, const uint32_t* in, float* out, size
     VR_HIP(hipStreamSynchronize(stream));
 }
 
+// Test hook (include/volren_amd.h vr_filter_probe).  Every array goes through a DeviceBuffer of this call's own; nothing of sized_ is read or written.  The two
+// scene-bound stages take the scene as run_resolve and upsample take it.
+void RendererHIP::filter_probe(int stage, int W, int H, const void* const* in, float* const* out, const float* params) {
+    flush_pending();
+    const size_t px = (size_t)W * (size_t)H, F4 = sizeof(float);
+    const DenoiseSigma sg{ params[0], params[1], params[2], params[3], params[4] };
+    const int32_t i0 = (int32_t)params[5], i1 = (int32_t)params[8];
+    const float x = params[6], tau = params[7];
+    std::vector<std::unique_ptr<DeviceBuffer>> held;
+    auto fresh = [&](size_t bytes) { held.push_back(std::make_unique<DeviceBuffer>(bytes)); return held.back().get(); };
+    auto up = [&](const void* src, size_t bytes) -> DeviceBuffer* {       // nullptr stays nullptr
+        if (!src) return nullptr;
+        DeviceBuffer* b = fresh(bytes);
+        b->upload(src, bytes, stream);
+        return b;
+    };
+    auto fl = [](DeviceBuffer* b) { return b ? b->as<float>() : nullptr; };
+    struct Back { DeviceBuffer* b; float* to; size_t bytes; };
+    std::vector<Back> back;
+    auto down = [&](float* to, size_t bytes) -> DeviceBuffer* {           // an output: zeroed, so that a word the launch leaves alone reads 0
+        if (!to) return nullptr;
+        DeviceBuffer* b = fresh(bytes);
+        VR_HIP(hipMemsetAsync(b->get(), 0, bytes, stream));
+        back.push_back({ b, to, bytes });
+        return b;
+    };
+    switch (stage) {
+    case 0: {
+        const size_t tiles = (size_t)tile_count(W, H);
+        DeviceBuffer *m = up(in[0], px * 4 * F4), *f = up(in[1], px * 8 * F4), *c = up(in[2], tiles * sizeof(int32_t));
+        DeviceBuffer *v = down(out[0], px * F4), *g = down(out[1], px * 8 * F4);
+        launch_denoise_prepare(fl(m), fl(f), W, H, i0, x, c ? c->as<int32_t>() : nullptr, fl(v), fl(g), stream);
+        break;
+    }
+    case 1: {
+        DeviceBuffer *c = up(in[0], px * 4 * F4), *v = up(in[1], px * F4), *g = up(in[2], px * 8 * F4);
+        DeviceBuffer *oc = down(out[0], px * 4 * F4), *ov = down(out[1], px * F4);
+        launch_denoise_atrous(fl(c), fl(v), fl(g), W, H, i0, sg, fl(oc), fl(ov), stream);
+        break;
+    }
+    case 2: {
+        TemporalPass t;
+        DeviceBuffer* v = up(in[1], px * F4);                            // read and written in place, as dn_var[0] is
+        back.push_back({ v, out[2], px * F4 });
+        t.color = fl(up(in[0], px * 4 * F4)); t.v = fl(v); t.guide = fl(up(in[2], px * 8 * F4));
+        t.hist_color = fl(up(in[3], px * 4 * F4)); t.hist_record = fl(up(in[4], px * 4 * F4)); t.hist_moments = fl(up(in[5], px * 4 * F4));
+        t.same_cam = i1 != 0;
+        memcpy(&t.cur, params + 9, 13 * F4); memcpy(&t.prev, params + 22, 13 * F4);
+        t.W = W; t.H = H; t.alpha = x; t.tau = tau; t.sigma = sg;
+        t.out_color = fl(down(out[0], px * 4 * F4)); t.out_record = fl(down(out[1], px * 4 * F4)); t.out_moments = fl(down(out[3], px * 4 * F4));
+        if (tau > 0.0f) {
+            DeviceBuffer* scratch = fresh(px * 8 * F4);
+            VR_HIP(hipMemsetAsync(scratch->get(), 0, px * 8 * F4, stream));
+            t.scratch = scratch->as<float>();
+        }
+        launch_denoise_temporal(t, stream);
+        if (tau > 0.0f) {
+            VR_HIP(hipGetLastError());
+            VR_HIP(hipMemcpyAsync(out[4], t.scratch + px * 4, px * 4 * F4, hipMemcpyDeviceToHost, stream));
+        }
+        break;
+    }
+    case 3: {
+        LaunchInputs li;
+        capture(li);
+        DeviceBuffer *fb = up(in[0], px * 4 * F4), *f = up(in[1], px * 8 * F4);
+        DeviceBuffer *B = down(out[0], px * 4 * F4), *Pq = down(out[1], px * 4 * F4), *y = down(out[2], px * 4 * F4);
+        launch_resolve(li.P, fl(fb), fl(f), i0, fl(B), fl(Pq), fl(y), stream);
+        break;
+    }
+    case 4: {
+        DeviceBuffer *y = up(in[0], px * 4 * F4), *B = up(in[1], px * 4 * F4), *f = up(in[2], px * 8 * F4);
+        launch_layers_split(fl(y), fl(B), fl(f), W, H, fl(down(out[0], px * 4 * F4)), stream);
+        break;
+    }
+    case 5: {
+        DeviceBuffer *Fq = up(in[0], px * 4 * F4), *B = up(in[1], px * 4 * F4), *f = up(in[2], px * 8 * F4);
+        DeviceBuffer *o = down(out[0], px * 4 * F4), *L = down(out[1], px * 4 * F4);
+        launch_layers_merge(fl(Fq), fl(B), fl(f), W, H, fl(o), fl(L), stream);
+        break;
+    }
+    case 6: {
+        DeviceBuffer *S = up(in[0], px * 4 * F4), *g = up(in[1], px * 8 * F4);
+        launch_denoise_regress(fl(S), fl(g), W, H, sg, x, fl(down(out[0], px * 4 * F4)), stream);
+        break;
+    }
+    case 7: {
+        const int32_t f = i1;
+        const size_t hi = px * (size_t)f * (size_t)f;
+        SceneParams P;
+        feature_scene(P);
+        P.u.resolution[0] = f * W; P.u.resolution[1] = f * H;
+        DeviceBuffer *l = up(in[0], px * 4 * F4), *g = up(in[1], px * 8 * F4), *hf = up(in[2], hi * 8 * F4);
+        DeviceBuffer *o = down(out[0], hi * 4 * F4), *L = down(out[1], hi * 4 * F4);
+        launch_upsample(P, fl(l), fl(g), W, H, f, fl(hf), i0, sg, fl(o), fl(L), stream);
+        break;
+    }
+    case 8: {
+        DeviceBuffer *fb = up(in[0], px * 4 * F4), *m = up(in[1], px * 4 * F4), *t = up(in[2], (size_t)i0 * sizeof(int32_t)), *c = up(in[3], (size_t)i0 * sizeof(int32_t));
+        launch_adaptive_error(fl(fb), fl(m), t->as<int32_t>(), c->as<int32_t>(), i0, W, H, fl(down(out[0], (size_t)i0 * F4)), stream);
+        break;
+    }
+    default: throw std::invalid_argument("filter_probe: unknown stage");
+    }
+    VR_HIP(hipGetLastError());
+    for (const Back& b : back) b.b->download(b.to, b.bytes, stream);
+    VR_HIP(hipStreamSynchronize(stream));
+}
+
 // the common body of the download_* of whole buffers: the refusal comes before the flush
 void RendererHIP::download_whole(const DeviceBufferPtr& b, float* out, const char* absent) {
     if (!b) throw std::runtime_error(absent);

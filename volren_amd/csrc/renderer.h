@@ -215,6 +215,10 @@ struct RendererHIP {
     // probe_kernel on the SceneParams the next launch would get -- after capture() (float atlas) and update_majorants, with the paired atlas where a kernel reads it.
     // Throws for a form the scene cannot serve.  Synchronous; touches no framebuffer.
     void probe(int what, int form, const uint32_t* in, float* out, size_t n);
+    // test hook (include/volren_amd.h vr_filter_probe: the stages, the arrays and the parameter block): one launch_* of vr_device.h's vr_filters.hip section on
+    // host arrays, through fresh device buffers on this renderer's stream.  The arguments are checked by the caller (capi.cpp).  Synchronous; touches no buffer,
+    // flag or history of the renderer.
+    void filter_probe(int stage, int W, int H, const void* const* in, float* const* out, const float* params);
     void download_features(float* out);
     void download_variance(float* rgba);
     // Denoiser (vr_denoise.h).  denoise(): the a-trous filter of the current frame, guided by the variance and the last feature pass, into its own W*H*4

@@ -27,11 +27,18 @@
 // A_00 <= 2^-20:  no covered tap, F_p = (0, 0, 0, kappa_p).  Otherwise
 //   lambda == 0:  Ct = b_0 / A_00                                                   zero order: the normalised weighted mean, no solve
 //   lambda > 0:   rl = lambda * A_00;  A_ii = A_ii + rl for i = 1..7;  floor = 2^-20 * rl; then the LDL^T elimination of regress_solve in the order 0, 1, .. 7:
-//     pivot k: d_k = A_kk; column k is KEPT if k == 0 or d_k > floor (a NaN pivot: dropped); r_k = 1 / d_k;
+//     a_k = A_kk as it stands before the elimination (ridge included), k = 1..7
+//     pivot k: d_k = A_kk; column k is KEPT if k == 0 or (d_k > floor and d_k > 2^-12 a_k) (a NaN pivot: dropped); r_k = 1 / d_k;
 //       for i = k+1..7: l = kept ? A_ki * r_k : 0;  A_ij = A_ij - l * A_kj for j = i..7;  b_ic = b_ic - l * b_kc;  then A_ki = l
 //     back, k = 7..0: beta_kc = kept ? (b_kc * r_k - A_k,k+1 * beta_k+1,c - ... - A_k7 * beta_7c, subtracted in that order) : 0
-//     Ct = beta_0.  In exact arithmetic every pivot after the first is >= rl (a sum of squares plus the ridge), so a dropped column is one that rounding
-//     emptied; its coefficient is 0 and the others are fitted without it.
+//     Ct = beta_0.  In exact arithmetic every pivot after the first is >= rl (a sum of squares plus the ridge), so the floor drops only a column that rounding
+//     emptied.  The second test is about a column that rounding did NOT empty but left meaningless: d_k is what remains of a_k after up to seven subtractions,
+//     known to some ten 2^-24 a_k (a_k is a sum over up to 121 taps) and no better, and a kept column moves Ct by about that times a_k / d_k of the
+//     window mean -- a regressor that sits far from 0
+//     over the whole window and hardly varies in it (depth 0 at the pixel, so rd = 2^20, over a flat neighbourhood) once gave pivots of either sign and of any size
+//     above the floor, and a Ct off by more than the layer's whole range.  A column that keeps less than 2^-12 of its own diagonal is therefore dropped as well: a
+//     kept column then costs at most some ten 2^-12 relative.  With regressors of size s the share is at least lambda / (s^2 + lambda): for unit normals, albedos
+//     and relative depths, s <= 2, a lambda >= 2^-10 keeps every pivot above the test by the ridge alone, and the test changes nothing.  A dropped column's coefficient is 0 and the others are fitted without it.
 //   F_p.rgb = kappa_p * Ct;   F_p.a = kappa_p
 // The unchanged merge (vr_layers.h) then has F.a = kappa_p: its ratio is kappa_p / kappa_p = 1 where kappa_p > 2^-20 and not taken below, so L.rgb = F.rgb and
 // out = max_(G + L.rgb, 0).  EVERY pixel with kappa_p = 0 comes out as B bit for bit, next to the volume and far from it: F = 0, G = 1 * B, B >= 0.  (The
@@ -55,21 +62,25 @@ constexpr int32_t kRegressTerms = 8;                   // the intercept, depth, 
 constexpr float kRegressMinWeight = 0x1p-20f;          // the smallest coverage of a tap that counts, and the smallest A_00 the pixel divides by
 constexpr float kRegressMinDepth = 0x1p-20f;           // the smallest depth the depth regressor is scaled by
 constexpr float kRegressPivotFloor = 0x1p-20f;         // a pivot not above this times lambda A_00 drops its column
+constexpr float kRegressPivotShare = 0x1p-12f;         // ... and so does one not above this times the column's own diagonal before the elimination
 constexpr float kRegressRidgeMin = 0x1p-20f, kRegressRidgeMax = 0x1p20f;      // the accepted range of "denoise_ridge" besides 0
 // zero order: in the sweep of {0, 0.01, 0.1, 1, 10} over five scenes at 2..64 spp no lambda > 0 beats it on the mean (tests/test_regress_host.py)
 constexpr float kRegressDefaultRidge = 0.0f;
 
 VR_HD bool regress_ridge_ok(float v) { return v == 0.0f || (v >= kRegressRidgeMin && v <= kRegressRidgeMax); }
 
-// beta_0 of the ridged normal equations: A the upper triangle (A[i][j], i <= j; the rest is not read), b the right-hand sides, both destroyed
-VR_HD void regress_solve(float A[kRegressTerms][kRegressTerms], float b[kRegressTerms][3], float floor, float Ct[3]) {
+// beta_0 of the ridged normal equations: A the upper triangle (A[i][j], i <= j; the rest is not read), b the right-hand sides, both destroyed.
+// dropped (tests): receives the number of columns that were not kept
+VR_HD void regress_solve(float A[kRegressTerms][kRegressTerms], float b[kRegressTerms][3], float floor, float Ct[3], int32_t* dropped = nullptr) {
     constexpr int32_t n = kRegressTerms;
     bool kept[n];
-    float r[n];
+    float r[n], share[n];
+#pragma unroll
+    for (int32_t k = 0; k < n; ++k) share[k] = kRegressPivotShare * A[k][k];
 #pragma unroll
     for (int32_t k = 0; k < n; ++k) {
         const float d = A[k][k];
-        kept[k] = k == 0 || d > floor;
+        kept[k] = k == 0 || (d > floor && d > share[k]);
         r[k] = 1.0f / d;
 #pragma unroll
         for (int32_t i = k + 1; i < n; ++i) {
@@ -93,13 +104,17 @@ VR_HD void regress_solve(float A[kRegressTerms][kRegressTerms], float b[kRegress
         }
     }
     for (int32_t c = 0; c < 3; ++c) Ct[c] = beta[0][c];
+    if (dropped) {
+        *dropped = 0;
+        for (int32_t k = 0; k < n; ++k) *dropped += kept[k] ? 0 : 1;
+    }
 }
 
 // The filter at pixel (px, py) of a W x H frame.  Src answers, for (px + dx, py + dy) inside the frame only, |dx|, |dy| <= kRegressRadius,
 //   void tap(int32_t dx, int32_t dy, float S[4], float g[8]) const      the texel of S and the guide there
-// -> F, what the merge reads.
+// -> F, what the merge reads.  dropped (tests): receives the number of columns regress_solve dropped, -1 where the pixel never reaches it.
 template <class Src>
-VR_HD void regress_pixel(const Src& src, int32_t W, int32_t H, int32_t px, int32_t py, const DenoiseSigma& sg, float ridge, float F[4]) {
+VR_HD void regress_pixel(const Src& src, int32_t W, int32_t H, int32_t px, int32_t py, const DenoiseSigma& sg, float ridge, float F[4], int32_t* dropped = nullptr) {
     constexpr int32_t n = kRegressTerms, R = kRegressRadius;
     // s(d) = exp(-d^2 / 12.5), d = -5..5, rounded to float32
     const float s[2 * R + 1] = { 0.135335283f, 0.278037300f, 0.486752256f, 0.726149037f, 0.923116346f, 1.0f, 0.923116346f, 0.726149037f, 0.486752256f, 0.278037300f, 0.135335283f };
@@ -107,6 +122,7 @@ VR_HD void regress_pixel(const Src& src, int32_t W, int32_t H, int32_t px, int32
     src.tap(0, 0, Sp, gp);
     const float kp = gp[3];
     F[0] = 0.0f; F[1] = 0.0f; F[2] = 0.0f; F[3] = kp;
+    if (dropped) *dropped = -1;
     if (kp == 0.0f) { F[3] = 0.0f; return; }
     const float rd = 1.0f / max_(gp[7], kRegressMinDepth);
     float A[n][n], b[n][3];
@@ -152,7 +168,7 @@ VR_HD void regress_pixel(const Src& src, int32_t W, int32_t H, int32_t px, int32
         const float rl = ridge * A[0][0];
 #pragma unroll
         for (int32_t i = 1; i < n; ++i) A[i][i] = A[i][i] + rl;
-        regress_solve(A, b, kRegressPivotFloor * rl, Ct);
+        regress_solve(A, b, kRegressPivotFloor * rl, Ct, dropped);
     }
     F[0] = kp * Ct[0]; F[1] = kp * Ct[1]; F[2] = kp * Ct[2];
 }

@@ -246,6 +246,41 @@ class Renderer:
         _lib.check(self._L.vr_probe(self._h, int(what), int(form), items.ctypes.data, out.ctypes.data, items.shape[0]))
         return out
 
+    FILTER_STAGES = ("prepare", "atrous", "temporal", "resolve", "split", "merge", "regress", "upsample", "adaptive_error")
+
+    def filter_probe(self, stage, w, h, inputs, outputs, sigma=(4.0, 0.5, 0.1, 0.25, 0.2), i0=0, x=0.0, tau=0.0, i1=0, cur=None, prev=None):
+        """Test hook (include/volren_amd.h vr_filter_probe): one launcher of the image-space kernels on host arrays.  stage: a name of FILTER_STAGES or its number;
+        inputs: up to 6 arrays in the stage's order, float32 (counts and tile ids int32), None where one is left out; outputs: up to 5 shapes in the stage's order,
+        None likewise; the rest is the parameter block (cur, prev: cameras of 13 float32).  Returns the outputs as float32 arrays, None where none was asked for.
+        Nothing of the renderer changes."""
+        stage = self.FILTER_STAGES.index(stage) if isinstance(stage, str) else int(stage)
+        keep = []
+        for a in inputs:
+            if a is not None:
+                a = np.ascontiguousarray(a)
+                assert a.dtype in (np.float32, np.int32), "inputs: float32, or int32 for counts and tile ids"
+            keep.append(a)
+        outs = [None if s is None else np.zeros(s, np.float32) for s in outputs]
+        # the sizes the library will read and write (words of 4 bytes): the header's table
+        px, hi, tiles, n = int(w) * int(h), int(w) * int(h) * int(i1) ** 2, ((int(w) + 15) // 16) * ((int(h) + 15) // 16), int(i0)
+        want_in = ((4 * px, 8 * px, tiles), (4 * px, px, 8 * px), (4 * px, px, 8 * px, 4 * px, 4 * px, 4 * px), (4 * px, 8 * px), (4 * px, 4 * px, 8 * px),
+                   (4 * px, 4 * px, 8 * px), (4 * px, 8 * px), (4 * px, 8 * px, 8 * hi), (4 * px, 4 * px, n, n))[stage]
+        want_out = ((px, 8 * px), (4 * px, px), (4 * px, 4 * px, px, 4 * px, 4 * px), (4 * px,) * 3, (4 * px,), (4 * px,) * 2, (4 * px,), (4 * hi,) * 2, (n,))[stage]
+        assert len(keep) <= len(want_in) and len(outs) <= len(want_out), "more arrays than the stage has"
+        assert all(a is None or a.size == k for a, k in zip(keep, want_in)), "an input array is not of the stage's size"
+        assert all(o is None or o.size == k for o, k in zip(outs, want_out)), "an output array is not of the stage's size"
+        pin = (C.c_void_p * 6)(*([None if a is None else a.ctypes.data for a in keep] + [None] * (6 - len(keep))))
+        pout = (C.c_void_p * 5)(*([None if o is None else o.ctypes.data for o in outs] + [None] * (5 - len(outs))))
+        p = np.zeros(40, np.float32)
+        p[0:5] = sigma
+        p[5], p[6], p[7], p[8] = i0, x, tau, i1
+        if cur is not None:
+            p[9:22] = cur
+        if prev is not None:
+            p[22:35] = prev
+        _lib.check(self._L.vr_filter_probe(self._h, stage, int(w), int(h), pin, pout, p.ctypes.data))
+        return outs
+
     # ---- denoiser data ----
     def render_features(self, spp, sync=True):
         """First-scatter features of samples 1..spp of every pixel (include/volren_amd.h vr_render_features), computed afresh."""
