@@ -344,7 +344,10 @@ int vr_denoised_layer(vr_renderer* r, float* rgba_out);
  *     so the silhouette ramp and the sky are the hi frame's own, and a hi pixel with kappa_p = 0 is B_p bit for bit.  The arithmetic is specified operation
  *     by operation in volren_amd/csrc/vr_upsample.h and reproducible bit for bit.  Asynchronous on the renderer's stream, and a flush point like vr_denoise.
  *     VR_ERR_ARG for a factor outside 2..4 or rays outside 1..4.  VR_ERR, before anything is launched, when vr_denoised_layer would be refused (no denoise call
- *     with "denoise_layers" = 1 since the last resize) or a tile subset is set.  The first call allocates the hi buffers; vr_resize drops them, and so does a
+ *     with "denoise_layers" = 1 since the last resize) or a tile subset is set; and, with words of its own ("the last denoise ran with denoise_layers = 0"),
+ *     when the last vr_denoise / vr_denoise_temporal that ran did so with "denoise_layers" = 0: the lo guide is the one that call prepared, so it no longer
+ *     belongs to the layer -- vr_denoised_layer stays readable, vr_upsampled* keep what they held, and a call with "denoise_layers" = 1 makes vr_upsample
+ *     available again (a refused denoise call changes nothing of this).  The first call allocates the hi buffers; vr_resize drops them, and so does a
  *     call with another factor.  The hi guide is marched when the call is made: the camera and the scene are the caller's to keep as they were at the denoise
  *     call.  The framebuffer, vr_features, vr_denoised, vr_denoised_layer and the history are left as they were.  There is no history at the hi size.
  *     Sharded renderers: after vr_sharded_denoise part 0 holds the gathered frame, guide and layer, and vr_upsample on vr_sharded_part(s, 0) is the call -- one

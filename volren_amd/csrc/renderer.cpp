@@ -1223,6 +1223,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         frame = sized_.ly_split.get();
     }
     DeviceBuffer* const result = layers ? sized_.ly_filtered.get() : sized_.denoised.get();
+    sized_.layer_guided = false;                      // the guide is this call's from here on; a call with layers pairs it with its layer below
     launch_denoise_prepare(sized_.moments->as<float>(), sized_.features->as<float>(), W, H, sample, vscale, counts, sized_.dn_var[0]->as<float>(), sized_.dn_guide->as<float>(), stream);
     VR_HIP(hipGetLastError());
     const DenoiseSigma sg = sigma();
@@ -1268,6 +1269,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         launch_layers_merge(result->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.denoised->as<float>(), sized_.layer->as<float>(), stream);
         VR_HIP(hipGetLastError());
         sized_.layer_valid = true;
+        sized_.layer_guided = true;
         sized_.layer_gathered = whole_frame_gathered;
     }
 }
@@ -1342,6 +1344,8 @@ void RendererHIP::upsample(int factor, int rays) {
     if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("upsample: rays must be 1.." + std::to_string(kExpectedMaxRays));
     flush_pending();
     if (!sized_.layer_valid) throw std::runtime_error("upsample: no denoise with denoise_layers = 1 since the last resize (its layer is what the call upsamples)");
+    if (!sized_.layer_guided)
+        throw std::runtime_error("upsample: the last denoise ran with denoise_layers = 0 and its guide has replaced the layer's (denoise with denoise_layers = 1 again; denoised_layer stays readable)");
     if (!tiles_host_.empty() && !sized_.layer_gathered) throw std::runtime_error("upsample: a tile subset is set (set_tiles); the call rebuilds whole frames only");
     const int32_t w = resolution.x, h = resolution.y, W = factor * w, H = factor * h;
     const size_t px = (size_t)W * (size_t)H;

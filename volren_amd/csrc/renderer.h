@@ -393,7 +393,8 @@ private:
         DeviceBufferPtr rs_bg, rs_part, resolved;      // resolve(): B, P and the resolved frame, W*H*4 each
         DeviceBufferPtr ly_split, ly_filtered, layer;  // denoise() with denoise_layers = 1: S, F and the layer L, W*H*4 each (vr_layers.h)
         bool layer_valid = false;                      // `layer` holds the layer of a finished call's merge
-        bool layer_gathered = false;                   // ... of a gathered whole frame (part 0 of a ShardedRenderer): the renderer's tile subset is no obstacle to upsample()
+        bool layer_guided = false;                     // ... and dn_guide is still that call's: no denoise without layers has overwritten it since (upsample() pairs the two)
+        bool layer_gathered = false;                  // ... of a gathered whole frame (part 0 of a ShardedRenderer): the renderer's tile subset is no obstacle to upsample()
         DeviceBufferPtr up_features, up_out, up_layer; // upsample(): the hi feature buffer (W*H*8), the hi frame and the hi layer (W*H*4 each), W x H = up_factor x the frame
         int up_factor = 0;                             // the factor they were allocated and last filled for (0: none)
         DeviceBufferPtr dn_guide, dn_var[2], dn_color[2];  // denoise(): guide W*H*8, variance ping-pong W*H, colour ping-pong W*H*4

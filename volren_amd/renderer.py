@@ -395,7 +395,8 @@ class Renderer:
         """Rebuild the frame at `factor` (2..4) times this renderer's size per axis from the layer of the last denoise() / denoise_temporal() with
         `denoise_layers = 1`, under an expected-value guide of `rays` (1..4) rays per axis marched at the large size (include/volren_amd.h vr_upsample,
         csrc/vr_upsample.h).  Asynchronous.  Keep the camera and the scene as they were at the denoise call.  Refused without such a layer since the last
-        resize, or with a tile subset set.  Results: upsampled(), upsampled_layer(), upsampled_features()."""
+        resize, after a denoise() / denoise_temporal() with `denoise_layers = 0` (its guide has replaced the layer's) until one with 1 has run again, or with a
+        tile subset set.  Results: upsampled(), upsampled_layer(), upsampled_features()."""
         _lib.check(self._L.vr_upsample(self._h, int(factor), int(rays)))
 
     def upsampled_size(self):
