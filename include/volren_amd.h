@@ -481,6 +481,11 @@ int vr_math_sweep(int fn, uint32_t first, long long count, float b, float* out);
  * 4 texel, 5 sky, 6 light sample, 7 transfer function) in compile-time form `form`, on the scene as the renderer's next launch would read it.  in: 4 32-bit words per
  * item; out: 1, 1, 1, 1, 3, 3, 7, 4 floats per item; host arrays.  VR_ERR_RUNTIME for a form the scene cannot serve (the message says why). */
 int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, long long n);
+/* test hook: unit-test probe of the per-path layer (volren_amd/csrc/vr_path_probe.h): n items of `kind` (0 RNG, 1 camera ray, 2 box clip, 3 phase function and
+ * MIS weight, 4 DDA step, 5 one whole segment of the hot pair, bounded) in form `form` (DDA step: 0 general, 1 CLEAN; segment: the compiled instance 0..6), on the
+ * scene as the renderer's next launch would read it.  in: 8, 4, 6, 9, 7, 8 32-bit words per item; out: 5, 4, 3, 5, 1, 14 32-bit words per item (floats as their bits);
+ * host arrays, at most 2^24 items.  VR_ERR_RUNTIME for a form the scene cannot serve -- an instance the scene's launch would not run -- with the reason. */
+int vr_path_probe(vr_renderer* r, int kind, int form, const void* in, void* out, long long n);
 /* test hook: ONE launcher of the image-space kernels (volren_amd/csrc/vr_device.h, section vr_filters.hip) on host arrays of the caller's.  The arrays of
  * `in` go up into fresh device buffers, the stage's launch_* runs once on the renderer's stream, the call waits, and the arrays of `out` come back.  No buffer,
  * flag or history of the renderer changes; the renderer gives its device and stream, and to the two scene-bound stages (resolve, upsample) its scene.

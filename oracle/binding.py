@@ -130,6 +130,11 @@ def lib():
     for name in ("trilinear", "majorant", "sky", "tf"):
         getattr(L, "orc_batch_" + name).argtypes = [C.POINTER(Params), C.POINTER(Scene), C.c_void_p, C.c_void_p, c_i64]
     L.orc_batch_light.argtypes = [C.POINTER(Params), C.POINTER(Scene), C.c_void_p, C.c_void_p, C.c_void_p, c_i64]
+    for name in ("rng", "phase", "dda_step"):
+        getattr(L, "orc_batch_" + name).argtypes = [C.c_void_p, C.c_void_p, c_i64]
+    for name in ("camera", "box"):
+        getattr(L, "orc_batch_" + name).argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, c_i64]
+    L.orc_batch_segment.argtypes = [C.POINTER(Params), C.POINTER(Scene), C.c_void_p, C.c_void_p, c_i64]
     L.orc_math.argtypes = [c_i, c_f, c_f]
     L.orc_math.restype = c_f
     L.orc_num_threads.restype = c_i
@@ -446,6 +451,35 @@ class OracleRenderer:
             if texel:
                 return out, tx
         else:
+            fn(C.byref(p), C.byref(s), items.ctypes.data, out.ctypes.data, n)
+        return out
+
+    # --- the per-path layer (orc_batch_rng ... orc_batch_segment): the item layouts of volren_amd/csrc/vr_path_probe.h ---
+    PATH_PROBES = ("rng", "camera", "box", "phase", "dda_step", "segment")
+    PATH_IN_WORDS = (8, 4, 6, 9, 7, 8)
+    PATH_OUT_WORDS = (5, 4, 3, 5, 1, 13)
+    @staticmethod
+    def segment_budget():
+        """ORC_SEGMENT_BUDGET, read from volren_oracle.h: the header is the one place that states it"""
+        import re
+        with open(os.path.join(_HERE, "volren_oracle.h")) as f:
+            return int(re.search(r"#define\s+ORC_SEGMENT_BUDGET\s+(\d+)", f.read()).group(1))
+
+    def path_probe(self, kind, items):
+        """items: [n][PATH_IN_WORDS[kind]] 32-bit words; returns [n][PATH_OUT_WORDS[kind]] uint32 (floats as their bits).  The segment loops are bounded."""
+        items = np.ascontiguousarray(items)
+        assert items.ndim == 2 and items.shape[1] == self.PATH_IN_WORDS[kind] and items.dtype.itemsize == 4
+        name = self.PATH_PROBES[kind]
+        n = items.shape[0]
+        out = np.zeros((n, self.PATH_OUT_WORDS[kind]), np.uint32)
+        fn = getattr(lib(), "orc_batch_" + name)
+        if name in ("rng", "phase", "dda_step"):
+            fn(items.ctypes.data, out.ctypes.data, n)
+        elif name in ("camera", "box"):
+            p = self.params()
+            fn(C.byref(p), items.ctypes.data, out.ctypes.data, n)
+        else:
+            p, s = self.params(), self.scene()
             fn(C.byref(p), C.byref(s), items.ctypes.data, out.ctypes.data, n)
         return out
 

@@ -385,41 +385,60 @@ static inline float collision_density(ctx_t* c, v3 ip, uint32_t* seed, float rgb
     return lookup_density_stochastic(c, ip, seed);
 }
 
+#define MIP_START 3.0f
+#define MIP_SPEED_UP 0.25f
+#define MIP_SPEED_DOWN 2.0f
+
 /* ------------------------------------------------------------------ */
 /* global-majorant null-collision methods  ref: common.glsl:333-394 (compiled out in the reference: USE_DDA) */
-static float transmittance_global(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed) {
+/* What orc_batch_segment asks of the four trackers below: a bound on the loop's iterations and the state the loop ends in.  NULL: the trackers as the
+ * reference states them, unbounded (every other caller).  status: see volren_oracle.h; the caller presets a missed box (status 0, t 0, tau 0, mipq 12, Tr 1). */
+typedef struct { int32_t budget, status, mipq; float t, tau, Tr; uint32_t n_coll; float col[3]; } seg_probe;
+static inline void seg_end(seg_probe* pr, int32_t status, float t, float tau, float mip, float Tr) {
+    if (!pr) return;
+    pr->status = status; pr->t = t; pr->tau = tau; pr->mipq = (int32_t)(mip * 4.0f); pr->Tr = Tr;
+}
+
+static float transmittance_global(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed, seg_probe* pr) {
     const orc_params* p = c->p;
     float near, far;
     if (!intersect_box(wpos, wdir, p->vol_bb_min, p->vol_bb_max, &near, &far)) return 1.0f;
     const v3 ipos = mat4point(p->vol_density_inv_transform, wpos);
     const v3 idir = mat4dir(p->vol_density_inv_transform, wdir);
     float t = near - om_log(1.0f - rng(seed)) * p->vol_inv_majorant, Tr = 1.0f;
+    int32_t it = 0;
     while (t < far) {
+        if (pr && it++ >= pr->budget) { seg_end(pr, 3, t, 0.0f, MIP_START, Tr); return Tr; }
         float rgba[4];
         const float d = collision_density(c, v3axpy(ipos, t, idir), seed, rgba);
         c->c.n_coll_tr++;
+        if (pr) pr->n_coll++;
         Tr *= 1.0f - d * p->vol_inv_majorant;
         if (Tr < 0.1f) {
             const float prob = 1.0f - Tr;
-            if (rng(seed) < prob) return 0.0f;
+            if (rng(seed) < prob) { seg_end(pr, 2, t, 0.0f, MIP_START, 0.0f); return 0.0f; }
             Tr /= 1.0f - prob;
         }
         t -= om_log(1.0f - rng(seed)) * p->vol_inv_majorant;
     }
+    seg_end(pr, 1, t, 0.0f, MIP_START, Tr);
     return Tr;
 }
-static int sample_volume_global(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* throughput, v3* Le, uint32_t* seed) {
+static int sample_volume_global(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* throughput, v3* Le, uint32_t* seed, seg_probe* pr) {
     const orc_params* p = c->p;
     float near, far;
     if (!intersect_box(wpos, wdir, p->vol_bb_min, p->vol_bb_max, &near, &far)) return 0;
     const v3 ipos = mat4point(p->vol_density_inv_transform, wpos);
     const v3 idir = mat4dir(p->vol_density_inv_transform, wdir);
     float t = near - om_log(1.0f - rng(seed)) * p->vol_inv_majorant;
+    int32_t it = 0;
     while (t < far) {
+        if (pr && it++ >= pr->budget) { seg_end(pr, 3, t, 0.0f, MIP_START, 1.0f); *tout = t; return 0; }
         float rgba[4];
         const v3 ip = v3axpy(ipos, t, idir);
         const float d = collision_density(c, ip, seed, rgba);
         c->c.n_coll_sv++;
+        if (pr) pr->n_coll++;
         const float P_real = d * p->vol_inv_majorant;
         const v3 em = lookup_emission(c, ip, seed);
         const v3 one_m_alb = V3(1.0f - p->vol_albedo[0], 1.0f - p->vol_albedo[1], 1.0f - p->vol_albedo[2]);
@@ -428,20 +447,19 @@ static int sample_volume_global(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* thr
             if (p->use_tf) *throughput = v3mul(*throughput, V3(rgba[0] * p->vol_albedo[0], rgba[1] * p->vol_albedo[1], rgba[2] * p->vol_albedo[2]));
             else           *throughput = v3mul(*throughput, V3(p->vol_albedo[0], p->vol_albedo[1], p->vol_albedo[2]));
             *tout = t;
+            seg_end(pr, 2, t, 0.0f, MIP_START, 1.0f);
+            if (pr && p->use_tf) { pr->col[0] = rgba[0]; pr->col[1] = rgba[1]; pr->col[2] = rgba[2]; }
             return 1;
         }
         t -= om_log(1.0f - rng(seed)) * p->vol_inv_majorant;
     }
     *tout = t;
+    seg_end(pr, 1, t, 0.0f, MIP_START, 1.0f);
     return 0;
 }
 
 /* ------------------------------------------------------------------ */
 /* DDA  ref: common.glsl:399-409 */
-#define MIP_START 3.0f
-#define MIP_SPEED_UP 0.25f
-#define MIP_SPEED_DOWN 2.0f
-
 static float stepDDA(v3 pos, v3 inv_dir, int mip) {
     const float dim = (float)(8 << mip);
     const float idim = 1.0f / dim;
@@ -465,7 +483,7 @@ static inline float dda_majorant(ctx_t* c, v3 curr, int mip) {
 }
 
 /* ref: common.glsl:412-455 */
-static float transmittanceDDA(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed) {
+static float transmittanceDDA(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed, seg_probe* pr) {
     const orc_params* p = c->p;
     float near, far;
     if (!intersect_box(wpos, wdir, p->vol_bb_min, p->vol_bb_max, &near, &far)) return 1.0f;
@@ -473,7 +491,9 @@ static float transmittanceDDA(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed) {
     const v3 idir = mat4dir(p->vol_density_inv_transform, wdir);
     const v3 ri = V3(1.0f / idir.x, 1.0f / idir.y, 1.0f / idir.z);
     float t = near + 1e-6f, Tr = 1.0f, tau = -om_log(1.0f - rng(seed)), mip = MIP_START;
+    int32_t it = 0;
     while (t < far) {
+        if (pr && it++ >= pr->budget) { seg_end(pr, 3, t, tau, mip, Tr); return Tr; }
         const v3 curr = v3axpy(ipos, t, idir);
         const int m = om_round_half_even(mip);
         const float majorant = dda_majorant(c, curr, m);
@@ -488,22 +508,24 @@ static float transmittanceDDA(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed) {
         float rgba[4];
         const float d = collision_density(c, v3axpy(ipos, t, idir), seed, rgba);
         c->c.n_coll_tr++;
+        if (pr) pr->n_coll++;
         if (rng(seed) * majorant < d) {
             Tr *= om_max(0.0f, 1.0f - p->vol_majorant / majorant);
             if (Tr < 0.1f) {
                 const float prob = 1.0f - Tr;
-                if (rng(seed) < prob) return 0.0f;
+                if (rng(seed) < prob) { seg_end(pr, 2, t, tau, mip, 0.0f); return 0.0f; }
                 Tr /= 1.0f - prob;
             }
         }
         tau = -om_log(1.0f - rng(seed));
         mip = om_max(0.0f, mip - MIP_SPEED_DOWN);
     }
+    seg_end(pr, 1, t, tau, mip, Tr);
     return Tr;
 }
 
 /* ref: common.glsl:458-501 */
-static int sample_volumeDDA(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* throughput, v3* Le, uint32_t* seed, int* hit_box) {
+static int sample_volumeDDA(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* throughput, v3* Le, uint32_t* seed, int* hit_box, seg_probe* pr) {
     const orc_params* p = c->p;
     float near, far;
     *hit_box = 0;
@@ -514,7 +536,9 @@ static int sample_volumeDDA(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* through
     const v3 ri = V3(1.0f / idir.x, 1.0f / idir.y, 1.0f / idir.z);
     float t = near + 1e-6f;
     float tau = -om_log(1.0f - rng(seed)), mip = MIP_START;
+    int32_t it = 0;
     while (t < far) {
+        if (pr && it++ >= pr->budget) { seg_end(pr, 3, t, tau, mip, 1.0f); *tout = t; return 0; }
         const v3 curr = v3axpy(ipos, t, idir);
         const int m = om_round_half_even(mip);
         const float majorant = dda_majorant(c, curr, m);
@@ -530,6 +554,7 @@ static int sample_volumeDDA(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* through
         const v3 ip = v3axpy(ipos, t, idir);
         const float d = collision_density(c, ip, seed, rgba);
         c->c.n_coll_sv++;
+        if (pr) pr->n_coll++;
         /* Le += throughput * (1 - albedo) * emission * d * vol_inv_majorant (global inverse majorant: reference quirk) */
         const v3 em = lookup_emission(c, ip, seed);
         const v3 one_m_alb = V3(1.0f - p->vol_albedo[0], 1.0f - p->vol_albedo[1], 1.0f - p->vol_albedo[2]);
@@ -538,12 +563,15 @@ static int sample_volumeDDA(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* through
             *throughput = v3mul(*throughput, V3(p->vol_albedo[0], p->vol_albedo[1], p->vol_albedo[2]));
             if (p->use_tf) *throughput = v3mul(*throughput, V3(rgba[0], rgba[1], rgba[2]));
             *tout = t;
+            seg_end(pr, 2, t, tau, mip, 1.0f);
+            if (pr && p->use_tf) { pr->col[0] = rgba[0]; pr->col[1] = rgba[1]; pr->col[2] = rgba[2]; }
             return 1;
         }
         tau = -om_log(1.0f - rng(seed));
         mip = om_max(0.0f, mip - MIP_SPEED_DOWN);
     }
     *tout = t;
+    seg_end(pr, 1, t, tau, mip, 1.0f);
     return 0;
 }
 
@@ -561,7 +589,7 @@ int orc_sample_volume(const orc_params* p, const orc_scene* s, const float pos[3
     v3 thr = V3(1, 1, 1), Le = V3(0, 0, 0);
     float t = 0.0f;
     int hit = 0;
-    const int real = sample_volumeDDA(&c, V3(pos[0], pos[1], pos[2]), V3(dir[0], dir[1], dir[2]), &t, &thr, &Le, seed, &hit);
+    const int real = sample_volumeDDA(&c, V3(pos[0], pos[1], pos[2]), V3(dir[0], dir[1], dir[2]), &t, &thr, &Le, seed, &hit, NULL);
     out[0] = t; out[1] = thr.x; out[2] = thr.y; out[3] = thr.z;
     return real;
 }
@@ -569,7 +597,7 @@ int orc_sample_volume(const orc_params* p, const orc_scene* s, const float pos[3
 float orc_transmittance(const orc_params* p, const orc_scene* s, const float pos[3], const float dir[3], uint32_t* seed) {
     ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s;
     v3 P = V3(pos[0], pos[1], pos[2]), D = V3(dir[0], dir[1], dir[2]);
-    return p->integrator == 0 ? transmittanceDDA(&c, P, D, seed) : transmittance_global(&c, P, D, seed);
+    return p->integrator == 0 ? transmittanceDDA(&c, P, D, seed, NULL) : transmittance_global(&c, P, D, seed, NULL);
 }
 
 /* ------------------------------------------------------------------ */
@@ -648,9 +676,9 @@ static void trace_path(ctx_t* c, v3 pos, v3 dir, uint32_t* seed, float out[4]) {
     for (;;) {
         int hit_box = 1, real;
         float rm_pdf;
-        if (p->integrator == 0)      real = sample_volumeDDA(c, pos, dir, &t, &throughput, &L, seed, &hit_box);
+        if (p->integrator == 0)      real = sample_volumeDDA(c, pos, dir, &t, &throughput, &L, seed, &hit_box, NULL);
         else if (p->integrator == 3) real = sample_volume_raymarch(c, pos, dir, &t, &throughput, &rm_pdf, seed, &hit_box);
-        else                         real = sample_volume_global(c, pos, dir, &t, &throughput, &L, seed);
+        else                         real = sample_volume_global(c, pos, dir, &t, &throughput, &L, seed, NULL);
         if (n_paths == 0 && !hit_box) c->c.n_primary_miss++;
         if (!real) break;
         pos = v3axpy(pos, t, dir);
@@ -662,8 +690,8 @@ static void trace_path(ctx_t* c, v3 pos, v3 dir, uint32_t* seed, float out[4]) {
         if (le_pdf[3] > 0.0f) {
             f_p = orc_phase_hg(dot3(v3neg(dir), w_i), p->vol_phase_g);
             const float mis_weight = p->show_environment > 0 ? power_heuristic(le_pdf[3], f_p) : 1.0f;
-            const float Tr = p->integrator == 0 ? transmittanceDDA(c, pos, w_i, seed)
-                           : (p->integrator == 3 ? transmittance_raymarch(c, pos, w_i, seed) : transmittance_global(c, pos, w_i, seed));
+            const float Tr = p->integrator == 0 ? transmittanceDDA(c, pos, w_i, seed, NULL)
+                           : (p->integrator == 3 ? transmittance_raymarch(c, pos, w_i, seed) : transmittance_global(c, pos, w_i, seed, NULL));
             /* L += throughput * mis_weight * f_p * Tr * Le_pdf.rgb / Le_pdf.w */
             v3 a = v3scale(v3scale(v3scale(throughput, mis_weight), f_p), Tr);
             a = v3mul(a, V3(le_pdf[0], le_pdf[1], le_pdf[2]));
@@ -891,6 +919,74 @@ void orc_batch_light(const orc_params* p, const orc_scene* s, const uint32_t* in
 }
 void orc_batch_tf(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n) {
     ORC_BATCH(ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s; tf_lookup(&c, word_f(w[0]), out + 4 * i);)
+}
+
+/* the per-path layer (volren_oracle.h): words in, words out */
+static inline uint32_t f_word(float f) { uint32_t w; memcpy(&w, &f, 4); return w; }
+#define ORC_BATCH_W(NIN, NOUT, BODY) \
+    _Pragma("omp parallel for schedule(static)") \
+    for (int64_t i = 0; i < n; ++i) { const uint32_t* w = in + (NIN) * i; uint32_t* o = out + (NOUT) * i; BODY }
+
+void orc_batch_rng(const uint32_t* in, uint32_t* out, int64_t n) {
+    ORC_BATCH_W(8, 5,
+        uint32_t s = w[0];
+        o[0] = f_word(orc_rng(&s)); o[1] = s;
+        uint32_t s9 = w[0];
+        for (int k = 0; k < 9; ++k) (void)orc_rng(&s9);
+        o[2] = s9;
+        o[3] = orc_tea(w[1], w[2], 32);
+        /* pixel_sample: GLSL int arithmetic wraps */
+        o[4] = orc_tea(w[3] * ((uint32_t)w[6] * (uint32_t)w[4] + (uint32_t)w[5]), w[7], 32);)
+}
+void orc_batch_camera(const orc_params* p, const uint32_t* in, uint32_t* out, int64_t n) {
+    const int W = p->resolution[0]; const int H = p->resolution[1];
+    ORC_BATCH_W(4, 4,
+        const int x = (int32_t)w[0]; const int y = (int32_t)w[1];
+        uint32_t seed = orc_tea((uint32_t)p->seed * ((uint32_t)y * (uint32_t)W + (uint32_t)x), w[2], 32);
+        const float jx = rng(&seed); const float jy = rng(&seed);
+        const v3 d = view_dir(p, x, y, W, H, jx, jy);
+        o[0] = f_word(d.x); o[1] = f_word(d.y); o[2] = f_word(d.z); o[3] = seed;)
+}
+void orc_batch_box(const orc_params* p, const uint32_t* in, uint32_t* out, int64_t n) {
+    ORC_BATCH_W(6, 3,
+        float near; float far;
+        o[0] = (uint32_t)intersect_box(V3(word_f(w[0]), word_f(w[1]), word_f(w[2])), V3(word_f(w[3]), word_f(w[4]), word_f(w[5])), p->vol_bb_min, p->vol_bb_max, &near, &far);
+        o[1] = f_word(near); o[2] = f_word(far);)
+}
+void orc_batch_phase(const uint32_t* in, uint32_t* out, int64_t n) {
+    ORC_BATCH_W(9, 5,
+        o[0] = f_word(orc_phase_hg(word_f(w[0]), word_f(w[1])));
+        const v3 d = sample_phase_hg(V3(word_f(w[2]), word_f(w[3]), word_f(w[4])), word_f(w[1]), word_f(w[5]), word_f(w[6]));
+        o[1] = f_word(d.x); o[2] = f_word(d.y); o[3] = f_word(d.z);
+        o[4] = f_word(power_heuristic(word_f(w[7]), word_f(w[8])));)
+}
+void orc_batch_dda_step(const uint32_t* in, uint32_t* out, int64_t n) {
+    ORC_BATCH_W(7, 1,
+        o[0] = f_word(stepDDA(V3(word_f(w[0]), word_f(w[1]), word_f(w[2])), V3(word_f(w[3]), word_f(w[4]), word_f(w[5])), (int32_t)w[6]));)
+}
+void orc_batch_segment(const orc_params* p, const orc_scene* s, const uint32_t* in, uint32_t* out, int64_t n) {
+    _Pragma("omp parallel for schedule(dynamic, 64)")
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t* w = in + 8 * i; uint32_t* o = out + 13 * i;
+        ctx_t c; memset(&c, 0, sizeof c); c.p = p; c.s = s;
+        const v3 pos = V3(word_f(w[0]), word_f(w[1]), word_f(w[2])); const v3 dir = V3(word_f(w[3]), word_f(w[4]), word_f(w[5]));
+        uint32_t seed = w[6];
+        seg_probe pr; memset(&pr, 0, sizeof pr);
+        pr.budget = ORC_SEGMENT_BUDGET; pr.mipq = 12; pr.Tr = 1.0f;
+        v3 thr = V3(1, 1, 1); v3 Le = V3(0, 0, 0);
+        float t = 0.0f; int hit = 0;
+        if (w[7] == 0u) {
+            if (p->integrator == 0) (void)sample_volumeDDA(&c, pos, dir, &t, &thr, &Le, &seed, &hit, &pr);
+            else (void)sample_volume_global(&c, pos, dir, &t, &thr, &Le, &seed, &pr);
+        } else {
+            if (p->integrator == 0) (void)transmittanceDDA(&c, pos, dir, &seed, &pr);
+            else (void)transmittance_global(&c, pos, dir, &seed, &pr);
+        }
+        o[0] = (uint32_t)pr.status; o[1] = f_word(pr.t); o[2] = f_word(pr.tau); o[3] = (uint32_t)pr.mipq; o[4] = seed; o[5] = pr.n_coll; o[6] = f_word(pr.Tr);
+        o[7] = f_word(pr.col[0]); o[8] = f_word(pr.col[1]); o[9] = f_word(pr.col[2]);
+        if (!(p->has_emission && s->emission)) Le = V3(0, 0, 0);      /* nothing was gathered: (throughput * 0) * d is NaN for a d that is not finite */
+        o[10] = f_word(Le.x); o[11] = f_word(Le.y); o[12] = f_word(Le.z);
+    }
 }
 
 /* ------------------------------------------------------------------ */

@@ -168,6 +168,28 @@ void     orc_batch_texel(const orc_scene* s, const uint32_t* in, float* out, int
 void     orc_batch_sky(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
 void     orc_batch_light(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int32_t* texel, int64_t n);
 void     orc_batch_tf(const orc_params* p, const orc_scene* s, const uint32_t* in, float* out, int64_t n);
+
+/* Batch forms of the per-path layer (OpenMP over items), for tests/test_path_probes_host.py and tests/test_gpu_path_probes.py: the item layouts of
+ * volren_amd/csrc/vr_path_probe.h, 32-bit words in and out (floats as their bits, integers as they are).
+ *   rng      in 8: state, v0, v1, seed, W, px, py, smp       out 5: rng(state), state after, state after nine draws, orc_tea(v0, v1, 32), the path seed
+ *   camera   in 4: px, py, smp, -                            out 4: pixel_sample's direction (two jitter draws, view_dir), the RNG state after the two draws
+ *   box      in 6: pos, dir                                  out 3: hit, near, far
+ *   phase    in 9: cos, g, dir, r0, r1, a, b                 out 5: phase_hg(cos, g), sample_phase_hg(dir, g, r0, r1), power_heuristic(a, b)
+ *   dda_step in 7: p, 1 / dir, mip                           out 1: stepDDA
+ *   segment  in 8: pos, dir, RNG state, kind (0 sample_volume, 1 transmittance), by the tracker p->integrator selects (0 DDA, otherwise the global-majorant
+ *            pair), with the loop bounded by ORC_SEGMENT_BUDGET iterations
+ *            out 13: status (0 missed the box, 1 the segment ended without a real collision -- kind 1: the ray left the box --, 2 real collision -- kind 1: the
+ *            roulette ended the ray --, 3 budget exhausted), t, tau, the DDA level in quarter steps (a ray that misses: 0, 0, 12; the global pair: tau 0, level 12),
+ *            the RNG state after, the number of tentative collisions, Tr (kind 0: 1), the colour of the real collision under a LUT (otherwise 0, 0, 0), the
+ *            radiance Le gathered with throughput 1 (kind 0 with an emission grid; otherwise 0, 0, 0)
+ * The single-item entry points above run the same loops without a bound. */
+#define ORC_SEGMENT_BUDGET 4096
+void     orc_batch_rng(const uint32_t* in, uint32_t* out, int64_t n);
+void     orc_batch_camera(const orc_params* p, const uint32_t* in, uint32_t* out, int64_t n);
+void     orc_batch_box(const orc_params* p, const uint32_t* in, uint32_t* out, int64_t n);
+void     orc_batch_phase(const uint32_t* in, uint32_t* out, int64_t n);
+void     orc_batch_dda_step(const uint32_t* in, uint32_t* out, int64_t n);
+void     orc_batch_segment(const orc_params* p, const orc_scene* s, const uint32_t* in, uint32_t* out, int64_t n);
 float    orc_math(int32_t fn, float a, float b);   /* 0 log 1 sin 2 cos 3 tan 4 acos 5 atan2 6 exp 7 pow 8 asin */
 int32_t  orc_num_threads(void);
 /* the product's math probe table (volren_amd/csrc/vr_math_probe.h, codes 0..37 without 12 and 17) from oracle_math.h; operands and results as bit

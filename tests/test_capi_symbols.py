@@ -56,6 +56,10 @@ def test_no_device_fails_loudly():
     assert lib.vr_probe(C.c_void_p(1), 0, 2, words, out, 1) == 2 and b"no HIP device" in lib.vr_last_error()      # (the handle is not touched before the device check)
     assert lib.vr_probe(None, 0, 2, words, out, 1) == 3                                       # VR_ERR_ARG: there is no renderer to probe without a device ...
     assert lib.vr_probe(C.c_void_p(1), 0, 2, None, out, 1) == 3 and lib.vr_probe(C.c_void_p(1), 0, 2, words, out, -1) == 3      # ... and the arguments are checked first
+    words8, out14 = (C.c_uint32 * 8)(), (C.c_uint32 * 14)()
+    assert lib.vr_path_probe(C.c_void_p(1), 5, 6, words8, out14, 1) == 2 and b"no HIP device" in lib.vr_last_error()
+    assert lib.vr_path_probe(None, 5, 6, words8, out14, 1) == 3 and lib.vr_path_probe(C.c_void_p(1), 5, 6, None, out14, 1) == 3
+    assert lib.vr_path_probe(C.c_void_p(1), 5, 6, words8, None, 1) == 3 and lib.vr_path_probe(C.c_void_p(1), 5, 6, words8, out14, -1) == 3
     # vr_filter_probe: the same order -- the renderer, the arguments, the device; the handle is not touched before the device check
     a = (C.c_float * (4 * 4 * 8))()
     ids = (C.c_int32 * 1)(0)

@@ -60,7 +60,7 @@ _SIGNATURES = {
     **_sig([ll], "vr_test_alloc_cap_mb"),
     **_sig([ci, vp, vp, vp, ci], "vr_math_probe"),
     **_sig([ci, C.c_uint32, ll, cf, vp], "vr_math_sweep"),
-    **_sig([vp, ci, ci, vp, vp, ll], "vr_probe"),
+    **_sig([vp, ci, ci, vp, vp, ll], "vr_probe vr_path_probe"),
     **_sig([vp, ci, ci, ci, vp, vp, vp], "vr_filter_probe"),
     **_sig([vp, ci, ci, ci, vp, cs], "vr_write_brick_from_dense"),
     **_sig([vp, ci, ci, ci, cf, cf, vp, cs], "vr_write_dense"),

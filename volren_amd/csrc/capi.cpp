@@ -839,6 +839,13 @@ int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, lon
     return guard([&] { use_device(r); r->impl.probe(what, form, static_cast<const uint32_t*>(in), out, (size_t)n); });
 }
 
+int vr_path_probe(vr_renderer* r, int kind, int form, const void* in, void* out, long long n) {
+    NEED(r);
+    if (!in || !out || n < 0) return fail(VR_ERR_ARG, "bad arguments");
+    NEED_DEVICE();
+    return guard([&] { use_device(r); r->impl.path_probe(kind, form, static_cast<const uint32_t*>(in), static_cast<uint32_t*>(out), (size_t)n); });
+}
+
 // test hook: one launcher of the image-space kernels on host arrays (include/volren_amd.h).  What needs no device is checked first; nullptr = the arguments are fine
 static const char* filter_probe_error(int stage, int W, int H, const void* const* in, float* const* out, const float* p) {
     if (stage < 0 || stage > 8) return "vr_filter_probe: unknown stage";

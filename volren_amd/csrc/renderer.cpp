@@ -13,6 +13,7 @@
 #include "vr_adaptive.h"
 #include "vr_device.h"
 #include "vr_math.h"
+#include "vr_path_probe.h"
 #include "vr_probe.h"
 #include "vr_upsample.h"
 
@@ -1012,6 +1013,28 @@ void RendererHIP::probe(int what, int form, const uint32_t* in, float* out, size
     DeviceBuffer din(in_bytes), dout(out_bytes);
     din.upload(in, in_bytes, stream);
     launch_probe(P, what, form, din.as<uint32_t>(), dout.as<float>(), (uint32_t)n, stream);
+    VR_HIP(hipGetLastError());
+    dout.download(out, out_bytes, stream);
+    VR_HIP(hipStreamSynchronize(stream));
+}
+
+// Test hook (vr_path_probe.h): the scene as probe() takes it.  The instance is judged on the views the launch would get (the paired ones where they exist).
+void RendererHIP::path_probe(int kind, int form, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!in || !out) throw std::runtime_error("path_probe: null array");
+    if (n > (size_t)1 << 24) throw std::runtime_error("path_probe: more than 2^24 items");
+    flush_pending();
+    LaunchInputs li;
+    capture(li);
+    update_majorants(li, density_grids.at(li.frame));
+    SceneParams P = li.P;
+    if (const char* why = path_probe_form_error(P, kind, form)) throw std::runtime_error(std::string("path_probe: this scene cannot serve that form: ") + why);
+    if (const char* why = path_probe_items_error(P, kind, form, in, n)) throw std::runtime_error(std::string("path_probe: bad item: ") + why);
+    if (!(kind == PATH_SEGMENT && (form == 4 || form == 5))) unpair_views(P, li.frame);
+    if (n == 0) return;
+    const size_t in_bytes = n * (size_t)path_probe_in_words(kind) * sizeof(uint32_t), out_bytes = n * (size_t)path_probe_out_words(kind) * sizeof(uint32_t);
+    DeviceBuffer din(in_bytes), dout(out_bytes);
+    din.upload(in, in_bytes, stream);
+    launch_path_probe(P, kind, form, din.as<uint32_t>(), dout.as<uint32_t>(), (uint32_t)n, stream);
     VR_HIP(hipGetLastError());
     dout.download(out, out_bytes, stream);
     VR_HIP(hipStreamSynchronize(stream));

@@ -215,6 +215,9 @@ struct RendererHIP {
     // probe_kernel on the SceneParams the next launch would get -- after capture() (float atlas) and update_majorants, with the paired atlas where a kernel reads it.
     // Throws for a form the scene cannot serve.  Synchronous; touches no framebuffer.
     void probe(int what, int form, const uint32_t* in, float* out, size_t n);
+    // test hook (vr_path_probe.h): the same for the per-path layer -- n items of path_probe_in_words(kind) words in, path_probe_out_words(kind) words out.  A segment
+    // form is a compiled instance: the paired-atlas instances (4, 5) read the paired views, every other form the grids' own atlases.
+    void path_probe(int kind, int form, const uint32_t* in, uint32_t* out, size_t n);
     // test hook (include/volren_amd.h vr_filter_probe: the stages, the arrays and the parameter block): one launch_* of vr_device.h's vr_filters.hip section on
     // host arrays, through fresh device buffers on this renderer's stream.  The arguments are checked by the caller (capi.cpp).  Synchronous; touches no buffer,
     // flag or history of the renderer.

@@ -166,5 +166,7 @@ void launch_math_sweep(int32_t fn, uint32_t first, float b, float* out, int32_t 
 void launch_fast_math_sweep(int32_t fn, uint32_t first, float* out, int32_t n, hipStream_t stream);
 // unit-test probe of the scene-data lookups (vr_probe.h, vr_probe.hip): n items of 4 words in, probe_out_words(what) floats out
 void launch_probe(const SceneParams& P, int32_t what, int32_t form, const uint32_t* in, float* out, uint32_t n, hipStream_t stream);
+// unit-test probe of the per-path layer (vr_path_probe.h, vr_probe.hip): n items of path_probe_in_words(kind) words in, path_probe_out_words(kind) words out
+void launch_path_probe(const SceneParams& P, int32_t kind, int32_t form, const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t stream);
 
 }  // namespace vr

@@ -246,6 +246,18 @@ class Renderer:
         _lib.check(self._L.vr_probe(self._h, int(what), int(form), items.ctypes.data, out.ctypes.data, items.shape[0]))
         return out
 
+    PATH_IN_WORDS = (8, 4, 6, 9, 7, 8)            # RNG, camera ray, box clip, phase / MIS, DDA step, segment
+    PATH_OUT_WORDS = (5, 4, 3, 5, 1, 14)
+
+    def path_probe(self, kind, form, items):
+        """Test hook (include/volren_amd.h vr_path_probe, volren_amd/csrc/vr_path_probe.h): `items` is [n][PATH_IN_WORDS[kind]] 32-bit words; returns
+        [n][PATH_OUT_WORDS[kind]] uint32 (floats as their bits) from the device's own per-path code in form `form` (a segment: the compiled instance)."""
+        items = np.ascontiguousarray(items)
+        assert items.ndim == 2 and items.shape[1] == self.PATH_IN_WORDS[int(kind)] and items.dtype.itemsize == 4, "items: [n][words] 32-bit words"
+        out = np.zeros((items.shape[0], self.PATH_OUT_WORDS[int(kind)]), np.uint32)
+        _lib.check(self._L.vr_path_probe(self._h, int(kind), int(form), items.ctypes.data, out.ctypes.data, items.shape[0]))
+        return out
+
     FILTER_STAGES = ("prepare", "atrous", "temporal", "resolve", "split", "merge", "regress", "upsample", "adaptive_error")
 
     def filter_probe(self, stage, w, h, inputs, outputs, sigma=(4.0, 0.5, 0.1, 0.25, 0.2), i0=0, x=0.0, tau=0.0, i1=0, cur=None, prev=None):
