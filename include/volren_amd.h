@@ -108,12 +108,21 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     large; 0 = split by the sample pool alone.  Results never depend on the split)
  *     "order_tiles" (a launch works through its tiles costliest first -- longest chord of the pixel rays through the volume's box -- so that short
  *     paths are what is left when its work queue runs empty: 0 = never (raster order), 1 = when a tile subset is set (vr_set_tiles / a sharded
- *     renderer's parts; default), 2 = always.  Results never depend on the order) (int);  "tonemap_exposure" "tonemap_gamma" "albedo"(3) "phase" "density_scale"
+ *     renderer's parts; default), 2 = always.  Results never depend on the order)
+ *     "sky_tiles" (0 / 1, default 1.  A 16x16 tile is CLEAR when no camera ray of any of its pixels, for any jitter, can hit the volume's box: its pixel
+ *     rectangle, grown by one pixel on every side, lies apart from the projection of the box's eight corners, all of them in front of the camera -- decided on
+ *     the host from camera, box and frame size alone; no tile is clear with the camera inside the box or a corner behind or near the camera plane.  Every sample of
+ *     a clear tile is the environment behind it (black with "show_environment" 0), alpha 0.  With 1 those tiles are rendered by one thread per pixel and the
+ *     path tracer and its sample pool see only the others; "order_tiles" orders those.  Where a vr_render is cut into sub-launches ("sample_pool_mb",
+ *     "launch_target_ms") does not move: both go on counting every tile.  A view without clear tiles is launched exactly as with 0.  The split is OFF, whatever the value, while vr_sched_stats counts (every sample passes through the instrumented kernels), with "fast_math" 1 and
+ *     with "integrator" 2 or 3.  Results never depend on it: the frames are the same bits.  A camera ray of a clear tile that does hit the box -- a bug of the
+ *     classification -- is reported by vr_synchronize like a tripped watchdog, in words of its own) (int);  "tonemap_exposure" "tonemap_gamma" "albedo"(3) "phase" "density_scale"
  *     "emission_scale" "vol_clip_min"(3) "vol_clip_max"(3) "env_strength" "env_transform"(9) "env_rot"(1, degrees about +y,
  *     main.cpp:382) "tf_window_left" "tf_window_width" "cam_pos"(3) "cam_dir"(3) "cam_up"(3) "cam_fov" "volume_transform"(16)
  *     "denoise_sigma"(5: the edge-stopping widths of vr_denoise for colour, normal, depth, coverage, albedo; each in [2^-60, 2^60], about
  *     [8.7e-19, 1.15e18]: VR_ERR otherwise, the old values kept; default 4, 0.5, 0.1, 0.25, 0.2) (float) */
-/* read-only through vr_get_int: "seed_table_samples" (samples 1 .. this of every pixel have their seeds in the table now; 0 = no table) and "seed_table_fills"
+/* read-only through vr_get_int: "last_sky_tiles" (the clear tiles of the last submit -- the last vr_render / flushed vr_trace run, or the last group of a
+ *     vr_render_adaptive: what "sky_tiles" kept out of the path tracer there; 0 when that submit was not split);  "seed_table_samples" (samples 1 .. this of every pixel have their seeds in the table now; 0 = no table) and "seed_table_fills"
  *     (fill launches of this renderer so far: a frame that repeats the last one's seed, size and samples adds none);  "kernel_variant" (the compiled path-tracing kernel the next launch uses: 0 brick grid, 1 dense fp16 grid, 2 / 4 brick grid +
  *     emission grid, 3 everything decided at run time -- correct for every scene, up to an order of magnitude slower) and "kernel_variant_reason" (what sent the
  *     scene to variant 3, a mask: 1 integrator != 0, 2 the environment's warp table has thresholds below 2^-76 ("env_div_safe" = 0), 4 density scale outside

@@ -125,6 +125,8 @@ const IntParam kIntParams[] = {
     { "expected_skip", VR_INT(expected_skip), 0, 1, "expected_skip: 0 (march every step) or 1 (drop the steps of empty space by the clear-distance table)" },
     { "expected_stats", VR_INT(expected_stats), 0, 1, "expected_stats: 0 (off) or 1 (the expected-value passes count their work)" },
     { "order_tiles", VR_INT(order_tiles), 0, 2, "order_tiles: 0 (never), 1 (tile subsets), 2 (always)" },
+    { "sky_tiles", VR_INT(sky_tiles), 0, 1, "sky_tiles: 0 (every tile through the path tracer) or 1 (tiles whose camera rays cannot hit the volume's box are rendered apart)" },
+    { "last_sky_tiles", VR_READ_ONLY(R.last_sky_tiles) },
     { "grid_frame_counter", VR_GET(R.volume ? (int)R.volume->grid_frame_counter : 0), set_grid_frame, VR_ANY },
     { "n_grid_frames", VR_READ_ONLY(R.volume ? (int)R.volume->n_grid_frames() : 0) },
     { "last_launches", VR_READ_ONLY(R.last_launches) },

@@ -15,6 +15,7 @@
 #include "vr_math.h"
 #include "vr_path_probe.h"
 #include "vr_probe.h"
+#include "vr_sky_tiles.h"
 #include "vr_upsample.h"
 
 namespace vr {
@@ -496,14 +497,47 @@ std::vector<int32_t> RendererHIP::costliest_first(const SceneParams& P, const st
     return ordered;
 }
 
-const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) {
+uint64_t RendererHIP::tile_order_key(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const {
     const Uniforms& u = P.u;
     uint64_t key = kFnv1aStart;
     auto mix = [&key](const void* p, size_t nbytes) { key = fnv1a(p, nbytes, key); };
     mix(u.cam_pos, sizeof u.cam_pos); mix(u.cam_transform, sizeof u.cam_transform); mix(&P.cam_z, sizeof P.cam_z);
     mix(u.vol_bb_min, sizeof u.vol_bb_min); mix(u.vol_bb_max, sizeof u.vol_bb_max); mix(u.resolution, sizeof u.resolution); mix(&n_tiles, sizeof n_tiles);
     if (!ids.empty()) mix(ids.data(), ids.size() * sizeof(int32_t));
+    return key ? key : 1;
+}
+
+// Clear tiles (vr_sky_tiles.h) are no work for the path scheduler: split_tiles takes them out of a submit's list.  What costliest_first says about order
+// applies to the march tiles that stay.  The classification reads what tile_order's key hashes and nothing else, so the device list -- and the answer "no
+// clear tile", which needs none -- is cached under that key.
+RendererHIP::SplitTiles RendererHIP::split_tiles(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles, bool ordered) {
+    const int tag = ordered ? 2 : 1;
+    uint64_t key = fnv1a(&tag, sizeof tag, tile_order_key(P, ids, n_tiles));
     key = key ? key : 1;
+    if (split_key_ != key) {
+        std::vector<int32_t> march, sky;
+        sky_split_tiles(P, ids, n_tiles, march, sky);
+        if (!sky.empty()) {
+            if (ordered && !march.empty()) march = costliest_first(P, march, (int)march.size());
+            march.insert(march.end(), sky.begin(), sky.end());
+            ensure_buffer(split_dev_, march.size() * sizeof(int32_t));
+            split_dev_->upload(march.data(), march.size() * sizeof(int32_t), stream);
+        }
+        split_n_sky_ = (int)sky.size();
+        split_key_ = key;
+    }
+    SplitTiles s;
+    if (split_n_sky_ > 0) {
+        s.n_sky = split_n_sky_;
+        s.n_march = n_tiles - split_n_sky_;
+        s.march = split_dev_->as<int32_t>();
+        s.sky = s.march + s.n_march;
+    }
+    return s;
+}
+
+const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) {
+    const uint64_t key = tile_order_key(P, ids, n_tiles);
     if (order_dev_ && order_key_ == key && order_dev_->size_bytes() == (size_t)n_tiles * sizeof(int32_t)) return order_dev_->as<int32_t>();
     const std::vector<int32_t> ordered = costliest_first(P, ids, n_tiles);
     ensure_buffer(order_dev_, ordered.size() * sizeof(int32_t));
@@ -514,7 +548,7 @@ const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<i
 
 bool RendererHIP::LaunchInputs::same_launch_as(const LaunchInputs& o) const {
     return memcmp(&P, &o.P, sizeof P) == 0 && frame == o.frame && maj == o.maj && tuning == o.tuning && order_tiles == o.order_tiles && launch_target_ms == o.launch_target_ms &&
-           fast_math == o.fast_math && variance == o.variance && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
+           fast_math == o.fast_math && variance == o.variance && sky_tiles == o.sky_tiles && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
 }
 
 // What a launch reads from the renderer's public, freely mutable state -- taken when trace() / render() is CALLED (the reference issues its dispatch at that
@@ -567,7 +601,7 @@ void RendererHIP::capture(LaunchInputs& in) {
     in.maj.frame = in.frame;
     in.maj.blocked = in.P.density.maj_blocked;
     in.tuning = tuning;
-    in.order_tiles = order_tiles; in.launch_target_ms = launch_target_ms; in.fast_math = fast_math ? 1 : 0; in.variance = variance != 0 ? 1 : 0;
+    in.order_tiles = order_tiles; in.launch_target_ms = launch_target_ms; in.fast_math = fast_math ? 1 : 0; in.variance = variance != 0 ? 1 : 0; in.sky_tiles = sky_tiles != 0 ? 1 : 0;
     in.sample_pool_bytes = sample_pool_bytes;
     in.stream = stream;
     in.env = environment; in.tf = transferfunc;
@@ -593,6 +627,14 @@ void RendererHIP::submit_tile_set(const LaunchInputs& in, int first, int n) {
     if (n <= 0) return;
     const int n_tiles = tile_set_size();
     const bool ordered = in.order_tiles >= 2 || (in.order_tiles == 1 && tiles_dev_);
+    const SplitTiles split = in.splits_sky() ? split_tiles(in.P, tiles_dev_ ? tiles_host_ : std::vector<int32_t>(), n_tiles, ordered) : SplitTiles{};
+    if (split.n_sky > 0) {                                       // the march tiles to the path tracer, the clear ones to the sky kernel
+        const int per_launch = prepare_submit(in, first, n, split.n_march, split.n_sky);
+        open_timing_window(in.stream);
+        submit(in, first, n, split.march, split.n_march, per_launch, split.sky, split.n_sky);
+        close_timing_window(in.stream);
+        return;
+    }
     const int32_t* tiles = ordered ? tile_order(in.P, tiles_host_, n_tiles) : (tiles_dev_ ? tiles_dev_->as<int32_t>() : nullptr);
     const int per_launch = prepare_submit(in, first, n, n_tiles);      // (a throw here leaves the last call's window as it is)
     open_timing_window(in.stream);
@@ -609,13 +651,16 @@ void RendererHIP::close_timing_window(hipStream_t s) { VR_HIP(hipEventRecord(ev1
 
 // What a submit needs in place before its launches: the majorant table, the sample pool, the workspace and the moments; and the rate of the last sub-launch
 // enqueued, read while the window that goes still holds its events.  Returns the samples of one sub-launch as the pool allows.
-int RendererHIP::prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles) {
+int RendererHIP::prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles, int n_sky) {
     if (n <= 0) return 0;
     hipStream_t stream = in.stream;                              // (shadows the member: the launch goes where it was recorded for)
     update_majorants(in, density_grids.at(in.frame));
     // per-sample radiances live in a device pool; split the request so that one sub-launch fits the pool
-    int per_launch = std::min(samples_per_launch(in, n_tiles), n);
-    for (;;) {                                                   // a pool that does not fit the free HBM: halve the sub-launch, never fail for it
+    // (n_sky: clear tiles split off the submit.  They put nothing into the pool, so the pool is allocated for the n_tiles march tiles alone; the samples of a
+    // sub-launch stay what sample_pool_bytes gives the WHOLE tile set, so that the split moves no sub-launch boundary a caller has sized by that budget.
+    // n_tiles == 0: every tile is clear -- the sky kernel needs neither pool nor workspace, and takes the samples in one launch)
+    int per_launch = n_tiles > 0 ? std::min(samples_per_launch(in, n_tiles + n_sky), n) : n;
+    for (; n_tiles > 0;) {                                       // a pool that does not fit the free HBM: halve the sub-launch, never fail for it
         const size_t need = pathtrace_pool_floats(in.tuning, n_tiles, per_launch) * sizeof(float);
         if (pool_ && pool_->size_bytes() >= need) break;
         if (pool_) { VR_HIP(hipStreamSynchronize(stream)); pool_.reset(); }
@@ -627,14 +672,14 @@ int RendererHIP::prepare_submit(const LaunchInputs& in, int first, int n, int n_
             if (per_launch > 32) per_launch -= per_launch % 32;
         }
     }
-    if (!workspace_) {
+    if (!workspace_ && n_tiles > 0) {
         workspace_ = make_device_buffer(pathtrace_workspace_floats() * sizeof(float));
         // test hook: no path may depend on what its cold line held before the path wrote it (tests/test_gpu_parity.py)
         if (const char* e = std::getenv("VR_TEST_POISON_WORKSPACE"); e && *e == '1') VR_HIP(hipMemsetAsync(workspace_->get(), 0xFF, workspace_->size_bytes(), stream));
     }
     // test hook, value 2: NaN patterns in the workspace AND the sample pool before EVERY submit -- a frame must not depend on what an earlier frame (of this or of
     // another mode's kernels) left in either (tests/tools_determinism.py, test_frames_are_reproducible_on_every_compiled_instance)
-    if (const char* e = std::getenv("VR_TEST_POISON_WORKSPACE"); e && *e == '2') {
+    if (const char* e = std::getenv("VR_TEST_POISON_WORKSPACE"); e && *e == '2' && n_tiles > 0) {
         VR_HIP(hipMemsetAsync(workspace_->get(), 0xFF, workspace_->size_bytes(), stream));
         VR_HIP(hipMemsetAsync(pool_->get(), 0xFF, pool_->size_bytes(), stream));
     }
@@ -648,8 +693,9 @@ int RendererHIP::prepare_submit(const LaunchInputs& in, int first, int n, int n_
     return per_launch;
 }
 
-void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch) {
+void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch, const int32_t* sky, int n_sky) {
     const SceneParams& P = in.P;
+    last_sky_tiles = n_sky;
     hipStream_t stream = in.stream;
     const PathtraceKernel kernel = in.kernel();
     const bool pt_kernel = kernel.item_integrator == 0;          // launch_pathtrace records the events around the path-tracing kernel only
@@ -657,7 +703,8 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     // finished sub-launch; when there is none for the current settings and the request is large, a short probe launch measures it first (one
     // synchronisation, once per change of settings).  A plan can still be off -- the rate is a property of the scene AND the view -- which costs nothing
     // but the bound: the kernel's watchdog watches progress, not duration (vr_pathtrace.h).
-    const double px_samples = (double)n_tiles * 256.0;                          // samples per spp of this launch
+    const double px_samples = (double)(n_tiles + n_sky) * 256.0;                // samples per spp of this launch: the clear tiles' too -- the events whose time gives the
+                                                                                 // rate span the path-tracing kernel AND the sky kernel, and the plan divides by the same count
     const uint64_t key = [&] {
         uint64_t h = kFnv1aStart;
         auto mix = [&h](const void* p, size_t nbytes) { h = fnv1a(p, nbytes, h); };
@@ -687,7 +734,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     }
     float* moments = in.variance ? sized_.moments->as<float>() : nullptr;
     for (int done = 0; done < n;) {
-        ++last_launches;
+        if (n_tiles > 0) ++last_launches;
         const int m = probe > 0 ? probe : std::min(per_launch, n - done);
         hipEvent_t eb = nullptr, ee = nullptr;
         if (pt_kernel) {
@@ -697,8 +744,8 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
         }
         int seed_samples = 0;
         const uint32_t* seed_table = kernel.reads_seed_table ? seed_table_for(P, first + done, m, stream, &seed_samples) : nullptr;
-        launch_pathtrace(in.tuning, P, color->as<float>(), pool_->as<float>(), workspace_->as<float>(), status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m, status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments,
-                         seed_table, seed_samples);
+        launch_pathtrace(in.tuning, P, color->as<float>(), n_tiles > 0 ? pool_->as<float>() : nullptr, n_tiles > 0 ? workspace_->as<float>() : nullptr, status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m,
+                         status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments, seed_table, seed_samples, sky, n_sky);
         VR_HIP(hipGetLastError());
         done += m;
         if (pt_kernel) { rate_pending_samples_ = px_samples * (double)m; rate_pending_key_ = key; }
@@ -1484,24 +1531,30 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
     if (set.empty()) { set.resize((size_t)n_all); for (int t = 0; t < n_all; ++t) set[(size_t)t] = t; }
     ensure_buffer_at_least(sized_.adaptive_lists, (size_t)n_all * 2 * sizeof(int32_t));
     ensure_buffer_at_least(sized_.adaptive_err, (size_t)n_all * sizeof(float));
-    const bool ordered = in.order_tiles >= 1;
+    const bool ordered = in.order_tiles >= 1, split = in.splits_sky();
     open_timing_window(in.stream);                    // one window over all the call's submits
     adaptive_rounds = 0;
     // every group of `ids` from its count n to to(n), as one submit each
     auto launch_groups = [&](const std::vector<int32_t>& ids, const auto& to) {
         const auto groups = adaptive_groups(ids, tile_n_);
         std::vector<int32_t> packed;
+        std::vector<int> n_sky;                       // per group: its clear tiles, which lie behind its march tiles in `packed`
         for (const auto& g : groups) {
-            const std::vector<int32_t> o = ordered ? costliest_first(in.P, g.second, (int)g.second.size()) : g.second;
-            packed.insert(packed.end(), o.begin(), o.end());
+            std::vector<int32_t> march = g.second, sky;
+            if (split) sky_split_tiles(in.P, g.second, (int)g.second.size(), march, sky);
+            if (ordered && !march.empty()) march = costliest_first(in.P, march, (int)march.size());
+            packed.insert(packed.end(), march.begin(), march.end());
+            packed.insert(packed.end(), sky.begin(), sky.end());
+            n_sky.push_back((int)sky.size());
         }
         if (packed.empty()) return;
         sized_.adaptive_lists->upload(packed.data(), packed.size() * sizeof(int32_t), in.stream);
-        size_t off = 0;
+        size_t off = 0, k = 0;
         for (const auto& g : groups) {
             const int32_t n = g.first, next = to(n);
-            const int n_tiles = (int)g.second.size();
-            submit(in, n, next - n, sized_.adaptive_lists->as<int32_t>() + off, n_tiles, prepare_submit(in, n, next - n, n_tiles));
+            const int n_clear = n_sky[k++], n_tiles = (int)g.second.size() - n_clear;      // the march tiles
+            const int32_t* list = sized_.adaptive_lists->as<int32_t>() + off;
+            submit(in, n, next - n, list, n_tiles, prepare_submit(in, n, next - n, n_tiles, n_clear), n_clear > 0 ? list + n_tiles : nullptr, n_clear);
             for (int32_t t : g.second) tile_n_[(size_t)t] = next;
             off += g.second.size();
         }
@@ -1546,13 +1599,14 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
 
 void RendererHIP::check_watchdog() {
     const uint32_t st = watchdog_status();
+    if (st & kSkyHitStatus) throw std::runtime_error("sky tiles: a camera ray of a tile classified clear hit the volume's box (vr_sky_tiles.h sky_tile_clear is wrong for this view); the pixels concerned stopped at that sample. Render with sky_tiles 0");
     if (st & kFeatureLostStatus) throw std::runtime_error("feature pass: a camera segment exceeded its step budget (vr_render_features); the pixels concerned cover only their samples before it");
     if (st != 0) throw std::runtime_error("path-tracing kernel watchdog tripped (a wavefront exceeded its step budget)");
 }
 
 uint32_t RendererHIP::watchdog_status() {
     // bit 0: a wavefront gave up (iteration / shader-clock budget), bit 1: a path ended in an impossible state, bit 2 (kFeatureLostStatus): a feature
-    // sample's tracker exceeded its step budget.
+    // sample's tracker exceeded its step budget, bit 3 (kSkyHitStatus): a camera ray of a tile classified clear hit the box.
     // Read-and-clear, so that one bad launch does not poison the renderer.
     flush_pending();
     uint32_t s = 0;

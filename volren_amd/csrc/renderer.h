@@ -161,6 +161,13 @@ struct RendererHIP {
                                                       // (not bit-reproducible; without a transfer function within 1e-3 relative L2 of the default --
                                                       // with one bound the renderer refuses it: DESIGN.md 3)
     PathtraceTuning tuning = default_tuning();        // scheduler thresholds, work-unit size, statistics buffer of THIS renderer's launches
+    int sky_tiles = 1;                                // 1: a submit's CLEAR tiles -- 16x16 tiles no camera ray of which can hit the volume's box (vr_sky_tiles.h), whose samples
+                                                      // are all (environment, alpha 0) -- are rendered by one thread per pixel (vr_launch.hip sky_kernel) instead of going through the
+                                                      // path scheduler and the sample pool; the path tracer gets the other tiles.  The split depends on camera, box and frame size alone;
+                                                      // a view without clear tiles is launched as with 0.  Off, whatever this says, while the instrumented kernels are on (sched_stats:
+                                                      // every sample passes through them), in the tolerance mode (fast_math: its frames belong to that build's arithmetic) and for the
+                                                      // item integrators (2, 3).  Results never depend on it
+    int last_sky_tiles = 0;                           // clear tiles of the last submit (0: it was not split)
     int last_launches = 0;                            // path-tracing sub-launches of the last trace()/render()/render_adaptive()
     int adaptive_rounds = 0;                          // error evaluations (rounds) of the last render_adaptive()
     int launch_target_ms = 2000;                      // a sub-launch is planned to take at most this long, from the rate the renderer measured on its last launch (a short
@@ -339,7 +346,7 @@ private:
         MajKey maj;
         size_t frame = 0;
         PathtraceTuning tuning;
-        int order_tiles = 0, launch_target_ms = 0, fast_math = 0, variance = 0;
+        int order_tiles = 0, launch_target_ms = 0, fast_math = 0, variance = 0, sky_tiles = 0;
         size_t sample_pool_bytes = 0;
         hipStream_t stream = nullptr;
         std::shared_ptr<Environment> env;
@@ -347,13 +354,18 @@ private:
         DeviceBufferPtr keep[5];               // envmap, impmap, env_cdf, lut, compact envmap
         bool same_launch_as(const LaunchInputs& o) const;
         PathtraceKernel kernel() const { return pathtrace_kernel_of(P, tuning.wide_addressing != 0, tuning.stats != nullptr); }      // the kernel that serves the launch (vr_variant.h)
+        // the launch's clear tiles are split off (RendererHIP::sky_tiles says when not)
+        bool splits_sky() const { return sky_tiles != 0 && tuning.stats == nullptr && fast_math == 0 && kernel().item_integrator == 0; }
     };
     void capture(LaunchInputs& in);            // validates, builds the decoded float atlas when a LUT needs it, fills `in` from the current fields
     // samples first+1 .. first+n of the `n_tiles` tiles of the device list `tiles` in that order (nullptr: the whole frame in raster order), inside the
     // timing window its caller opened, per_launch samples at a time: what prepare_submit returned for the same arguments, after it brought the majorant table, the
     // pool, the workspace and the moments up to date -- outside the window of render() / trace(), which spans the sub-launches alone
-    int prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles);
-    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch);
+    // With clear tiles split off (sky, n_sky: their device list), tiles / n_tiles are the MARCH tiles alone: the pool's allocation sees only those, and every
+    // sub-launch's sample window is followed by the sky kernel over the clear ones; the samples of a sub-launch stay what the pool's budget gives the whole tile set, and
+    // the rate plan counts all the submit's samples over the time of both kernels (the split moves no sub-launch boundary a caller has sized).  n_tiles == 0 (every tile clear): no pool, no workspace, no path-tracing launch.
+    int prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles, int n_sky = 0);
+    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch, const int32_t* sky = nullptr, int n_sky = 0);
     void submit_tile_set(const LaunchInputs& in, int first, int n);      // prepare, then one window around a submit over the renderer's tile set (set_tiles), ordered as order_tiles says
     void open_timing_window(hipStream_t s), close_timing_window(hipStream_t s);      // of one call: last_launches, last_kernel_ms, last_pathtrace_ms
     int tile_set_size() const;                 // tiles of the renderer's tile set: the listed ones, or all of the frame
@@ -369,6 +381,14 @@ private:
     uint64_t order_key_ = 0;
     std::vector<int32_t> costliest_first(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const;
     const int32_t* tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles);
+    uint64_t tile_order_key(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const;      // (camera, box, frame size, tile list)
+    // The same tiles divided by vr_sky_tiles.h sky_split_tiles: the march tiles (costliest first if `ordered`, else in the list's order) and the clear ones, as one
+    // device list [march | sky] cached under tile_order's key (with `ordered`).  n_sky == 0: the list was not built -- the caller launches as without the split.
+    struct SplitTiles { const int32_t* march = nullptr; int n_march = 0; const int32_t* sky = nullptr; int n_sky = 0; };
+    SplitTiles split_tiles(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles, bool ordered);
+    DeviceBufferPtr split_dev_;
+    uint64_t split_key_ = 0;
+    int split_n_sky_ = 0;
     // adaptive sampling: samples behind each raster tile, meaningful while `sample` == tile_n_sample_ (ragged()); the denoiser's device copy: sized_.tile_n_dev
     std::vector<int32_t> tile_n_;
     int tile_n_sample_ = -1;

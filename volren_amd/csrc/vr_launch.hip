@@ -6,6 +6,8 @@
 // Radiance per (pixel, sample) goes to a sample pool; accumulate_kernel folds it into the RGBA32F running mean in sample
 // order, which makes the result bit-identical to the reference's one-dispatch-per-sample loop (renderer.cpp:138-140,
 // pathtracer_brick.glsl:36).  MFMA is not used: there is no dense contraction on this path.
+// The tiles of a launch that no camera ray can hit the volume's box from (vr_sky_tiles.h) never enter that path: sky_kernel renders them, one thread per
+// pixel, straight into the running mean.
 //
 // Also here: the integrators that run one thread per (pixel, sample) item -- direct volume rendering (common.glsl:571-591)
 // and ray marching --, which fill the same sample pool, and the denoiser's feature pass.
@@ -43,9 +45,22 @@ item_kernel(const SceneParams P, float* __restrict__ sbuf, const LaunchDesc D) {
     reinterpret_cast<float4*>(sbuf)[wu.base + item] = pack4(L);
 }
 
-// Running mean over the samples of one launch, in sample order (pathtracer_brick.glsl:36): one workgroup per listed tile (tiles == nullptr: all
-// tiles), one thread per pixel.  The mean is accumulate_sample's arithmetic (vr_trace.h).  MOMENTS (variance = 1): also the per-channel second
-// moments, Welford in the running-mean form, S_k = M2_k / k, in a W*H*4 buffer beside the colour.
+// One sample folded into a pixel's running mean (pathtracer_brick.glsl:36; accumulate_sample's arithmetic, vr_trace.h) as sample number `current_sample` (1-based).
+// MOMENTS (variance = 1): also into the per-channel second moments, Welford in the running-mean form, S_k = M2_k / k.  The one statement of the mean on the
+// device: accumulate_kernel and sky_kernel both fold through it.
+template <bool MOMENTS>
+__device__ __forceinline__ void fold_sample(float acc[4], float S[4], const float L[4], int32_t current_sample) {
+    const float a = 1.0f / (float)current_sample;
+    for (int32_t c = 0; c < 4; ++c) {
+        const float x = sanitize(L[c]);
+        const float mu = acc[c], mu1 = mix_(mu, x, a);
+        if (MOMENTS) S[c] = mix_(S[c], (x - mu) * (x - mu1), a);
+        acc[c] = mu1;
+    }
+}
+
+// Running mean over the samples of one launch, in sample order: one workgroup per listed tile (tiles == nullptr: all tiles), one thread per pixel, every
+// sample folded by fold_sample.  MOMENTS: the second moments in a W*H*4 buffer beside the colour.
 template <bool MOMENTS>
 __global__ void __launch_bounds__(256)
 accumulate_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, float* __restrict__ moments, const int32_t* __restrict__ tiles, int32_t n_tiles,
@@ -64,16 +79,45 @@ accumulate_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, float*
         const int32_t chunk = k / spu, sl = k - chunk * spu;
         float L[4];
         unpack4(sb[pool_slot<size_t>((size_t)chunk, n_tiles, (size_t)blockIdx.x, (uint32_t)q.sub, spu, (size_t)sl, (uint32_t)q.lane)], L);
-        const float a = 1.0f / (float)(first_sample + k);
-        for (int32_t c = 0; c < 4; ++c) {
-            const float x = sanitize(L[c]);
-            const float mu = acc[c], mu1 = mix_(mu, x, a);
-            if (MOMENTS) S[c] = mix_(S[c], (x - mu) * (x - mu1), a);
-            acc[c] = mu1;
-        }
+        fold_sample<MOMENTS>(acc, S, L, first_sample + k);
     }
     *texel = pack4(acc);
     if (MOMENTS) *mtexel = pack4(S);
+}
+
+// The clear tiles of a launch (vr_sky_tiles.h: no camera ray of theirs can hit the volume's box): one workgroup per listed tile, one thread per pixel, laid out
+// like accumulate_kernel.  Every sample of the launch's window is a primary miss -- sky_sample (vr_trace.h), its seed from the launch's seed table where that
+// covers the sample number, hashed otherwise -- and is folded into the running mean as it is made, in sample order: no scheduler, no sample pool, and the lanes
+// of a wavefront fetch neighbouring texels of the environment.  Starts from the framebuffer's texel when first_sample > 1.
+// A ray that does hit the box means the classifier called a tile clear that is not: the pixel stops there and the kernel sets kSkyHitStatus in the renderer's
+// status word (RendererHIP::check_watchdog throws).  A tripwire for a bug, never a fallback.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256)
+sky_kernel(const SceneParams P, float* __restrict__ fb, float* __restrict__ moments, const int32_t* __restrict__ tiles, int32_t first_sample, int32_t n_samples,
+           const SeedTable seeds, uint32_t* __restrict__ status) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const TilePixel q = wave_tiled_pixel(tiles[blockIdx.x], threadIdx.x, W);
+    if (q.px >= W || q.py >= H) return;
+    float4* texel = reinterpret_cast<float4*>(fb) + (size_t)q.py * W + q.px;
+    float4* mtexel = MOMENTS ? reinterpret_cast<float4*>(moments) + (size_t)q.py * W + q.px : nullptr;
+    float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, S[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if (first_sample > 1) {
+        unpack4(*texel, acc);
+        if (MOMENTS) unpack4(*mtexel, S);
+    }
+    bool hit = false;
+    for (int32_t k = 0; k < n_samples; ++k) {
+        const int32_t smp = first_sample + k;
+        uint32_t seed;
+        if (seeds.table != nullptr && smp - 1 < seeds.cap) seed = seeds.table[seed_table_index<uint32_t>((uint32_t)(smp - 1), seeds.n_tiles, (uint32_t)q.tile, (uint32_t)q.sub, (uint32_t)q.lane)];
+        else seed = path_seed((uint32_t)P.u.seed, W, q.px, q.py, smp);
+        float L[4];
+        if (!sky_sample(P, q.px, q.py, seed, L)) { hit = true; break; }
+        fold_sample<MOMENTS>(acc, S, L, smp);
+    }
+    *texel = pack4(acc);
+    if (MOMENTS) *mtexel = pack4(S);
+    if (hit) atomicOr(status, kSkyHitStatus);
 }
 
 // Denoiser features (vr_trace.h feature_pixel): one thread per pixel of the renderer's tiles (tiles == nullptr: all tiles), all `spp` samples in a loop,
@@ -230,8 +274,24 @@ size_t pathtrace_workspace_floats() { return kColdMainFloats + (size_t)kMaxWorkg
 
 void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
                       int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math, hipEvent_t ev_kernel_begin, hipEvent_t ev_kernel_end,
-                      float* moments, const uint32_t* seed_table, int32_t seed_samples) {
-    if (n_tiles <= 0 || n_samples <= 0) return;
+                      float* moments, const uint32_t* seed_table, int32_t seed_samples, const int32_t* sky_tiles, int32_t n_sky_tiles) {
+    if (n_samples <= 0 || (n_tiles <= 0 && n_sky_tiles <= 0)) return;
+    SeedTable seeds;
+    seeds.table = seed_samples > 0 ? seed_table : nullptr;
+    seeds.cap = seed_samples;
+    seeds.n_tiles = tile_count(P.u.resolution[0], P.u.resolution[1]);
+    // the clear tiles of the launch, behind the path-tracing kernel on the same stream and inside the same pair of events
+    auto launch_sky = [&] {
+        if (n_sky_tiles <= 0) return;
+        const auto sky = moments ? sky_kernel<true> : sky_kernel<false>;
+        hipLaunchKernelGGL(sky, dim3((unsigned)n_sky_tiles), dim3(256), 0, stream, P, fb, moments, sky_tiles, first_sample, n_samples, seeds, status);
+    };
+    if (n_tiles <= 0) {                             // every tile of the launch is clear: no path-tracing kernel, no sample pool
+        if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
+        launch_sky();
+        if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
+        return;
+    }
     SchedParams S;
     for (int i = 0; i < ST_COUNT; ++i) S.thr[i] = T.thr[i];
     LaunchDesc D;
@@ -248,10 +308,6 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
     D.chunks = (uint32_t)chunks;
     D.seg_len = (D.n_units + kQueueSegments - 1u) / kQueueSegments;
     D.unit_counter = unit_counter;
-    SeedTable seeds;
-    seeds.table = seed_samples > 0 ? seed_table : nullptr;
-    seeds.cap = seed_samples;
-    seeds.n_tiles = tile_count(P.u.resolution[0], P.u.resolution[1]);
     S.max_iters = kMaxIdleIters;
     // lanes that must stand at a tentative collision before the collision code runs while others still march (vr_pathtrace.h):
     // measured optimum 24 (smoke.brick +0.5 %, dense +0.7 %, sparse + emission +2...3.5 %), 32 with a transfer function, whose
@@ -266,10 +322,12 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
         const uint64_t items = (uint64_t)D.n_units * (uint64_t)(D.spu * 64);
         const auto integrate = K.item_integrator == 2 ? item_kernel<2> : item_kernel<3>;
         hipLaunchKernelGGL(integrate, dim3((unsigned)((items + 255) / 256)), block, 0, stream, P, sample_pool, D);
+        launch_sky();                               // (the renderer splits no launch of these integrators)
     } else {
         (void)hipMemsetAsync(unit_counter, 0, kQueueSegments * sizeof(uint32_t), stream);
         if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
         kPtInstance[mode][K.instance].launch(tf, stats, grid.x, stream, &P, sample_pool, workspace, &D, &S, status, T.stats, &seeds);
+        launch_sky();
         if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);
     }
     const auto accumulate = moments ? accumulate_kernel<true> : accumulate_kernel<false>;

@@ -1039,6 +1039,25 @@ VR_HD void first_resume(Hot& h, const SceneParams& P) {
     h.Tr = 1.0f;
 }
 
+// The primary-miss sample stated once: sample `seed` (the table's entry or path_seed, as do_new takes it) of pixel (px, py), when its camera ray misses the
+// volume's box -- jitter, direction and box test as do_new / begin_segment do them, the radiance as do_escape writes it for a `first` path (L = 0, throughput 1,
+// no scattering: mis = 1, alpha 0).  Returns false, with nothing produced, when the ray HITS the box: the sample is the path tracer's then.  No path state, no
+// scheduler, no sample pool: what the kernel of the clear tiles runs per sample (vr_launch.hip sky_kernel; vr_sky_tiles.h says which tiles those are).
+VR_HD bool sky_sample(const SceneParams& P, int32_t px, int32_t py, uint32_t seed, float out[4]) {
+    const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const float jx = rng(seed), jy = rng(seed);
+    const float fx = (((float)px + jx) - (float)W * 0.5f) / (float)H;
+    const float fy = (((float)py + jy) - (float)H * 0.5f) / (float)H;
+    const v3 dir = normalize(mat3_mul(P.u.cam_transform, normalize(v3{ fx, fy, P.cam_z })));
+    const v3 pos = v3{ P.u.cam_pos[0], P.u.cam_pos[1], P.u.cam_pos[2] };
+    float tnear, tfar;
+    if (intersect_box(pos, dir, P.u.vol_bb_min, P.u.vol_bb_max, tnear, tfar)) return false;
+    v3 L = v3{ 0.0f, 0.0f, 0.0f };
+    if (P.u.show_environment > 0) L = L + (v3{ 1.0f, 1.0f, 1.0f } * 1.0f) * lookup_environment(P, dir);      // do_escape's L + (thr * mis) * Le
+    out[0] = L.x; out[1] = L.y; out[2] = L.z; out[3] = 0.0f;
+    return true;
+}
+
 // Loop body of both DDA trackers up to the collision test (common.glsl:422-435, 469-482), two iterations at a time and
 // in two phases.  march_prep does everything that needs no memory -- positions, DDA levels, step lengths of this iteration AND
 // of the following ones, each taken as if its predecessors neither collide nor leave the box (step lengths do not depend on the
