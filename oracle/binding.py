@@ -57,7 +57,7 @@ class Scene(C.Structure):
 
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "n_dda_sv", "n_dda_tr", "n_coll_sv", "n_coll_tr",
-                                           "n_nee", "n_esc", "n_primary_miss", "n_tf_lookup")]
+                                           "n_nee", "n_esc", "n_primary_miss", "n_tf_lookup", "n_ended")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}

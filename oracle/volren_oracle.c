@@ -424,10 +424,12 @@ static float transmittance_global(ctx_t* c, v3 wpos, v3 wdir, uint32_t* seed, se
     seg_end(pr, 1, t, 0.0f, MIP_START, Tr);
     return Tr;
 }
-static int sample_volume_global(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* throughput, v3* Le, uint32_t* seed, seg_probe* pr) {
+static int sample_volume_global(ctx_t* c, v3 wpos, v3 wdir, float* tout, v3* throughput, v3* Le, uint32_t* seed, int* hit_box, seg_probe* pr) {
     const orc_params* p = c->p;
     float near, far;
+    *hit_box = 0;
     if (!intersect_box(wpos, wdir, p->vol_bb_min, p->vol_bb_max, &near, &far)) return 0;
+    *hit_box = 1;
     const v3 ipos = mat4point(p->vol_density_inv_transform, wpos);
     const v3 idir = mat4dir(p->vol_density_inv_transform, wdir);
     float t = near - om_log(1.0f - rng(seed)) * p->vol_inv_majorant;
@@ -678,7 +680,7 @@ static void trace_path(ctx_t* c, v3 pos, v3 dir, uint32_t* seed, float out[4]) {
         float rm_pdf;
         if (p->integrator == 0)      real = sample_volumeDDA(c, pos, dir, &t, &throughput, &L, seed, &hit_box, NULL);
         else if (p->integrator == 3) real = sample_volume_raymarch(c, pos, dir, &t, &throughput, &rm_pdf, seed, &hit_box);
-        else                         real = sample_volume_global(c, pos, dir, &t, &throughput, &L, seed, NULL);
+        else                         real = sample_volume_global(c, pos, dir, &t, &throughput, &L, seed, &hit_box, NULL);
         if (n_paths == 0 && !hit_box) c->c.n_primary_miss++;
         if (!real) break;
         pos = v3axpy(pos, t, dir);
@@ -715,6 +717,7 @@ static void trace_path(ctx_t* c, v3 pos, v3 dir, uint32_t* seed, float out[4]) {
         L = v3add(L, v3mul(v3scale(throughput, mis_weight), Le));
         c->c.n_esc++;
     }
+    if (!free_path) c->c.n_ended++;
     out[0] = L.x; out[1] = L.y; out[2] = L.z;
     out[3] = n_paths > 0 ? 1.0f : 0.0f;     /* clamp(n_paths, 0.f, 1.f) */
 }
@@ -772,6 +775,7 @@ static void counters_add(orc_counters* a, const orc_counters* b) {
     a->samples += b->samples; a->n_dda_sv += b->n_dda_sv; a->n_dda_tr += b->n_dda_tr;
     a->n_coll_sv += b->n_coll_sv; a->n_coll_tr += b->n_coll_tr; a->n_nee += b->n_nee;
     a->n_esc += b->n_esc; a->n_primary_miss += b->n_primary_miss; a->n_tf_lookup += b->n_tf_lookup;
+    a->n_ended += b->n_ended;
 }
 
 int32_t orc_num_threads(void) {
@@ -977,7 +981,7 @@ void orc_batch_segment(const orc_params* p, const orc_scene* s, const uint32_t* 
         float t = 0.0f; int hit = 0;
         if (w[7] == 0u) {
             if (p->integrator == 0) (void)sample_volumeDDA(&c, pos, dir, &t, &thr, &Le, &seed, &hit, &pr);
-            else (void)sample_volume_global(&c, pos, dir, &t, &thr, &Le, &seed, &pr);
+            else (void)sample_volume_global(&c, pos, dir, &t, &thr, &Le, &seed, &hit, &pr);
         } else {
             if (p->integrator == 0) (void)transmittanceDDA(&c, pos, dir, &seed, &pr);
             else (void)transmittance_global(&c, pos, dir, &seed, &pr);

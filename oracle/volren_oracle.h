@@ -93,6 +93,7 @@ typedef struct {
     uint64_t n_esc;                    /* escaped paths that fetch the environment */
     uint64_t n_primary_miss;           /* camera rays that miss the clip box */
     uint64_t n_tf_lookup;              /* tf_lookup calls (on-chip traffic) */
+    uint64_t n_ended;                  /* paths that end with free_path == 0: the bounce cap or the roulette (samples - n_ended leave the volume) */
 } orc_counters;
 
 /* ---- loaders ---- */

@@ -49,6 +49,7 @@ def lib(fast_tap=False):
     if fast_tap not in _libs:
         L = C.CDLL(build(fast_tap=fast_tap))
         L.hk_render.restype = C.c_longlong
+        L.hk_render_tiles.restype = C.c_longlong
         L.hk_math.restype = C.c_float
         L.hk_math.argtypes = [C.c_int, C.c_float, C.c_float]
         _libs[fast_tap] = L
@@ -58,7 +59,11 @@ def lib(fast_tap=False):
 # The forms of the lane code the harness compiles: exactly the 14 configurations the device ships (host_kernel.cpp FormCfg, vr_pathtrace.hip Cfg), in the
 # order of the product's instances (vr_variant.h PathtraceKernel::instance; form = 2 * instance + tf): (kernel variant, 64-bit gather addresses, transfer function)
 FORMS = tuple((variant, wide, tf) for variant, wide in ((0, False), (0, True), (1, False), (1, True), (2, True), (4, True), (3, True)) for tf in (False, True))
-COUNTERS = ("steps", "clean_march", "clean_collide", "general_march", "general_collide")
+# host_kernel.cpp g_form_steps: the first five as they always were; then the lane steps by the state they were entered in -- what the device's instrumented
+# instances count as the lanes of a block --, the transitions that end a path or an item, and what relates a march pass to the reference's DDA iterations
+COUNTERS = ("steps", "clean_march", "clean_collide", "general_march", "general_collide",
+            "new", "march", "collide", "nee", "postnee", "escape",
+            "ended", "outside", "new_escape", "primary_miss", "march_dda", "march_empty", "shadow_segments")
 HS_MAJ_BLOCKED = 1            # host_scene.h
 
 
@@ -98,4 +103,27 @@ def render(orc_renderer, spp, rect=None, fb=None, first_sample=1, fast_tap=False
                         orc_renderer.impmap.ctypes.data_as(C.c_void_p), 512,
                         fb.ctypes.data_as(C.c_void_p), x0, y0, x1, y1, first_sample, spp, 1 if wide else 0, HS_MAJ_BLOCKED if blocked else 0)
     assert steps >= 0
+    return fb, steps
+
+
+def render_tiles(orc_renderer, spp, tiles=None, fb=None, first_sample=1, fast_tap=False, wide=False, blocked=False):
+    """The same scene walked as the device walks a launch (host_kernel.cpp hk_render_tiles): every item of every listed 16x16 tile (raster ids, row 0 = bottom;
+    None: all tiles of the frame), the items outside a ragged frame included.  Returns (frame, lane steps)."""
+    L = lib(fast_tap)
+    p = orc_renderer.params()
+    assert C.sizeof(p) == L.hk_uniforms_size(), (C.sizeof(p), L.hk_uniforms_size())
+    dd = grid_desc(orc_renderer.density)
+    ed = grid_desc(orc_renderer.emission) if orc_renderer.emission is not None else None
+    if fb is None:
+        fb = np.zeros((orc_renderer.h, orc_renderer.w, 4), np.float32)
+    t = np.ascontiguousarray(tiles, np.int32) if tiles is not None else None
+    env = orc_renderer.env_tex
+    lut = orc_renderer.lut
+    steps = L.hk_render_tiles(C.byref(p), C.byref(dd), C.byref(ed) if ed is not None else None,
+                              lut.ctypes.data_as(C.c_void_p) if lut is not None else None,
+                              env.ctypes.data_as(C.c_void_p), env.shape[1], env.shape[0],
+                              orc_renderer.impmap.ctypes.data_as(C.c_void_p), 512,
+                              fb.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p) if t is not None else None, int(t.size) if t is not None else 0,
+                              first_sample, spp, 1 if wide else 0, HS_MAJ_BLOCKED if blocked else 0)
+    assert steps >= 0, steps
     return fb, steps

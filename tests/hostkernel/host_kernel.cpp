@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../volren_amd/csrc/vr_variant.h"
+#include "../../volren_amd/csrc/vr_tiles.h"
 #include "host_scene.h"
 
 using namespace vr;
@@ -42,7 +43,7 @@ static void trace_access(const Hot& h, const SceneParams& P) {
 // form = 2 * slot + (transfer function ? 1 : 0); slots = the product's instances (vr_variant.h PathtraceKernel::instance): 0 variant 0 with 32-bit gather offsets, 1 variant 0 with 64-bit addresses ("wide"), 2 and 3 the same for variant 1,
 // 4 variant 2, 5 variant 4, 6 variant 3 (the last three always form 64-bit addresses).  What stays out is what only the device's scheduler has: the emission
 // state cached in the hot registers (collide_finish's CACHED) and the LDS stores.
-enum { HK_SLOTS = 7, HK_FORMS = 2 * HK_SLOTS, HK_COUNTERS = 5 };
+enum { HK_SLOTS = 7, HK_FORMS = 2 * HK_SLOTS, HK_COUNTERS = 18 };
 template <int SLOT, bool TF> struct FormCfg;
 template <bool TF> struct FormCfg<0, TF> { using type = TraceCfg<TF, 0, 0, 0, 0, true>; };
 template <bool TF> struct FormCfg<1, TF> { using type = TraceCfg<TF, 0, 0, 0, 0, false>; };
@@ -52,7 +53,15 @@ template <bool TF> struct FormCfg<4, TF> { using type = TraceCfg<TF, 0, 1, 0, 0,
 template <bool TF> struct FormCfg<5, TF> { using type = TraceCfg<TF, 0, 1, 0, 1, false>; };
 template <bool TF> struct FormCfg<6, TF> { using type = TraceCfg<TF, 2, 2, 2, 2, false>; };
 // per form since the last hk_form_steps(reset): [0] lane steps, then the steps of the hot pair by the segment's kind, counted before each lane_step from seg_clean(l)
-// and l.state: [1] march on a clean segment, [2] collide on a clean one, [3] march on a segment that is not clean (the general forms), [4] collide on such a one
+// and l.state: [1] march on a clean segment, [2] collide on a clean one, [3] march on a segment that is not clean (the general forms), [4] collide on such a one.
+// Then what the device scheduler's instrumented instances count per block (vr_pathtrace.h VR_STAT: the lanes a block ran for), here per path and so whatever the
+// scheduler: lane steps by the state they were ENTERED in, counted before the step -- [5] NEW (only a step that takes an item: the harness's own last step of a
+// lane, NEW -> DONE, is no item), [6] MARCH (one pass of up to two DDA iterations, as on the device), [7] COLLIDE, [8] NEE, [9] POSTNEE, [10] ESCAPE -- and the
+// transitions that end a path or an item, counted after it: [11] POSTNEE -> NEW (bounce cap or roulette), [12] NEW -> NEW (the item's pixel lies outside a ragged
+// frame), [13] NEW -> ESCAPE (the camera segment ends before it begins), [14] those of [13] whose camera ray misses the volume's box (the others, global-majorant
+// trackers only, hit it and draw a free flight beyond it).  [15] the DDA iterations the march passes of [6] went through and [16] the passes among them that went
+// through none (entered with t >= far), both read off march_prep / march_load as march_finish reads them; [17] NEE steps that start a shadow segment
+enum { HC_NEW = 5, HC_MARCH, HC_COLLIDE, HC_NEE, HC_POSTNEE, HC_ESCAPE, HC_ENDED, HC_OUTSIDE, HC_NEW_ESCAPE, HC_PRIMARY_MISS, HC_DDA, HC_MARCH_EMPTY, HC_SHADOW };
 static unsigned long long g_form_steps[HK_FORMS][HK_COUNTERS] = {};
 
 struct ColdHost {
@@ -78,6 +87,59 @@ static void build_lane_scene(HostScene& S, const Uniforms* up, const hk_grid_des
     }
 }
 
+// DDA iterations of the march pass lane_step is about to run for `l` (0, 1 or 2): march_finish's own tests on march_prep's and march_load's values
+template <class K>
+static int march_pass_iterations(const Hot& l, const SceneParams& P) {
+    MarchIO io;
+    if (seg_clean(l)) march_prep<K::dense, K::majb, true>(l, P, io); else march_prep<K::dense, K::majb, false>(l, P, io);
+    if (!io.go1) return 0;
+    march_load<K::tf, K::a32>(P, io);
+    const float tau = l.tau - majorant_value<K::tf>(P, io.maj1) * io.dt1;
+    return (tau > 0.0f && io.go2) ? 2 : 1;
+}
+
+// one work unit on 64 lanes advanced round-robin: exercises the item hand-out in a different order than the GPU does
+template <class K>
+static bool run_unit(const SceneParams& P, unsigned long long* count, const WorkUnit& wu, long long& steps) {
+    Hot lanes[64];
+    ColdHost cold[64] = {};
+    FirstStash stash[64] = {};
+    for (auto& l : lanes) hot_init(l);
+    uint32_t next_item = 0;
+    bool live = true;
+    while (live) {
+        live = false;
+        for (int i = 0; i < 64; ++i) {
+            Hot& l = lanes[i];
+            if (l.state == ST_DONE) continue;
+            live = true;
+            if (l.state == ST_NEW) for (float& v : cold[i].v) v = nan_();         // a new path must not depend on what its cold line held
+            if (l.state == ST_MARCH || l.state == ST_COLLIDE) {
+                if (g_trace) trace_access(l, P);
+                ++count[(seg_clean(l) ? 1 : 3) + (l.state == ST_COLLIDE ? 1 : 0)];
+            }
+            const int32_t st = l.state;
+            if (st == ST_MARCH) { const int it = march_pass_iterations<K>(l, P); count[HC_DDA] += (unsigned)it; if (it == 0) ++count[HC_MARCH_EMPTY]; }
+            const bool took_item = st == ST_NEW && next_item < (uint32_t)wu.n_items;
+            if (took_item) ++count[HC_NEW];
+            else if (st >= ST_MARCH && st <= ST_ESCAPE) ++count[HC_MARCH + (st - ST_MARCH)];
+            lane_step<K>(l, cold[i], P, wu, next_item, stash[i]);
+            if (st == ST_POSTNEE && l.state == ST_NEW) ++count[HC_ENDED];
+            if (took_item && l.state == ST_NEW) ++count[HC_OUTSIDE];
+            if (took_item && l.state == ST_ESCAPE) {
+                ++count[HC_NEW_ESCAPE];
+                // a ray that misses the box leaves a `first` path (do_new), whose direction is in the stash; the box test is begin_segment's
+                float tn, tf;
+                if (l.first && !intersect_box(v3{ P.u.cam_pos[0], P.u.cam_pos[1], P.u.cam_pos[2] }, stash[i].dir, P.u.vol_bb_min, P.u.vol_bb_max, tn, tf)) ++count[HC_PRIMARY_MISS];
+            }
+            if (st == ST_NEE && l.shadow) ++count[HC_SHADOW];
+            ++count[0];
+            if (++steps > (1ll << 40)) return false;
+        }
+    }
+    return true;
+}
+
 // wave-sized work units exactly like the HIP kernel: 8x8 tile x chunk of samples -> sample buffer -> running mean
 template <class K>
 static long long render_units(const SceneParams& P, int form, float* fb, int x0, int y0, int x1, int y1, int first_sample, int n_samples) {
@@ -94,32 +156,39 @@ static long long render_units(const SceneParams& P, int form, float* fb, int x0,
                 wu.px0 = tx; wu.py0 = ty; wu.first_sample = first_sample + c0;
                 const int sc = (n_samples - c0) < spu ? (n_samples - c0) : spu;
                 wu.n_items = sc * 64; wu.base = 0u; wu.out = sbuf.data();
-                // 64 lanes advanced round-robin: exercises the item hand-out in a different order than the GPU does
-                Hot lanes[64];
-                ColdHost cold[64] = {};
-                FirstStash stash[64] = {};
-                for (auto& l : lanes) hot_init(l);
-                uint32_t next_item = 0;
-                bool live = true;
-                while (live) {
-                    live = false;
-                    for (int i = 0; i < 64; ++i) {
-                        Hot& l = lanes[i];
-                        if (l.state == ST_DONE) continue;
-                        live = true;
-                        if (l.state == ST_NEW) for (float& v : cold[i].v) v = nan_();         // a new path must not depend on what its cold line held
-                        if (l.state == ST_MARCH || l.state == ST_COLLIDE) {
-                            if (g_trace) trace_access(l, P);
-                            ++count[(seg_clean(l) ? 1 : 3) + (l.state == ST_COLLIDE ? 1 : 0)];
-                        }
-                        lane_step<K>(l, cold[i], P, wu, next_item, stash[i]);
-                        ++count[0];
-                        if (++steps > (1ll << 40)) return -1;
-                    }
-                }
+                if (!run_unit<K>(P, count, wu, steps)) return -1;
                 for (int p = 0; p < 64; ++p) {
                     const int x = tx + (p & 7), y = ty + (p >> 3);
                     if (x < x0 || x >= x1 || y < y0 || y >= y1 || x >= W || y >= H) continue;
+                    float* px = fb + 4 * ((size_t)y * W + x);
+                    for (int k = 0; k < sc; ++k) accumulate_sample(px, &sbuf[4 * ((size_t)k * 64 + p)], first_sample + c0 + k);
+                }
+            }
+    return steps;
+}
+
+// The device's items for a tile list (vr_pathtrace.h make_unit): every listed 16x16 tile's four 8x8 sub-tiles, each in chunks of `spu` samples, 64 items per sample
+// -- the items whose pixel lies outside a ragged frame included, as the device's NEW batches take them (tiles == nullptr: tiles 0 .. n_tiles - 1)
+template <class K>
+static long long render_tiles(const SceneParams& P, int form, float* fb, const int32_t* tiles, int n_tiles, int first_sample, int n_samples, int spu) {
+    const Uniforms& u = P.u;
+    const int W = u.resolution[0], H = u.resolution[1];
+    long long steps = 0;
+    unsigned long long* count = g_form_steps[form];
+    if (spu > n_samples) spu = n_samples;
+    std::vector<float> sbuf((size_t)spu * 64 * 4);
+    for (int slot = 0; slot < n_tiles; ++slot)
+        for (uint32_t sub = 0; sub < 4u; ++sub)
+            for (int c0 = 0; c0 < n_samples; c0 += spu) {
+                const TilePixel q = wave_tiled_pixel(tiles ? tiles[slot] : slot, sub * 64u, W);
+                WorkUnit wu;
+                wu.px0 = q.px; wu.py0 = q.py; wu.first_sample = first_sample + c0;
+                const int sc = (n_samples - c0) < spu ? (n_samples - c0) : spu;
+                wu.n_items = sc * 64; wu.base = 0u; wu.out = sbuf.data();
+                if (!run_unit<K>(P, count, wu, steps)) return -1;
+                for (int p = 0; p < 64; ++p) {
+                    const int x = q.px + (p & 7), y = q.py + (p >> 3);
+                    if (x >= W || y >= H) continue;
                     float* px = fb + 4 * ((size_t)y * W + x);
                     for (int k = 0; k < sc; ++k) accumulate_sample(px, &sbuf[4 * ((size_t)k * 64 + p)], first_sample + c0 + k);
                 }
@@ -166,6 +235,29 @@ long long hk_render(const Uniforms* up, const hk_grid_desc* density, const hk_gr
 #define HK_FORM(SLOT) \
     case 2 * SLOT: return render_units<FormCfg<SLOT, false>::type>(P, form, fb, x0, y0, x1, y1, first_sample, n_samples); \
     case 2 * SLOT + 1: return render_units<FormCfg<SLOT, true>::type>(P, form, fb, x0, y0, x1, y1, first_sample, n_samples);
+    HK_FORM(0) HK_FORM(1) HK_FORM(2) HK_FORM(3) HK_FORM(4) HK_FORM(5) HK_FORM(6)
+#undef HK_FORM
+    default: return -1;
+    }
+}
+
+// The same scene and form rule, walked as the device walks a launch: the items of the `n_tiles` listed 16x16 tiles (raster ids, row 0 = bottom; tiles == nullptr:
+// every tile of the frame), in work units of the serving kernel's own size.  Path-tracing forms only (-2 for the item integrators, which have no scheduler).
+long long hk_render_tiles(const Uniforms* up, const hk_grid_desc* density, const hk_grid_desc* emission, const float* lut,
+                          const float* env_rgb, int env_w, int env_h, const float* impmap, int imp_dim,
+                          float* fb, const int32_t* tiles, int n_tiles, int first_sample, int n_samples, int force_wide, int flags) {
+    HostScene S;
+    build_lane_scene(S, up, density, emission, lut, env_rgb, env_w, env_h, impmap, imp_dim, flags);
+    const SceneParams& P = S.P;
+    const PathtraceKernel kernel = pathtrace_kernel_of(P, force_wide != 0, false);
+    if (kernel.item_integrator != 0) return -2;
+    if (n_samples <= 0) return 0;
+    if (!tiles) n_tiles = tile_count(P.u.resolution[0], P.u.resolution[1]);
+    const int form = 2 * kernel.instance + (P.u.use_tf ? 1 : 0);
+    switch (form) {
+#define HK_FORM(SLOT) \
+    case 2 * SLOT: return render_tiles<FormCfg<SLOT, false>::type>(P, form, fb, tiles, n_tiles, first_sample, n_samples, kernel.samples_per_unit); \
+    case 2 * SLOT + 1: return render_tiles<FormCfg<SLOT, true>::type>(P, form, fb, tiles, n_tiles, first_sample, n_samples, kernel.samples_per_unit);
     HK_FORM(0) HK_FORM(1) HK_FORM(2) HK_FORM(3) HK_FORM(4) HK_FORM(5) HK_FORM(6)
 #undef HK_FORM
     default: return -1;

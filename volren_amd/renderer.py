@@ -508,6 +508,7 @@ class Renderer:
         d["cycles"] = {n: int(out[18 + i]) for i, n in enumerate(STATE_NAMES)}     # shader-clock ticks inside each state's block
         d["wave_cycles"] = int(out[25])                                            # summed lifetime of all wavefronts
         d["occupancy"] = {n: int(out[26 + i]) / max(1, int(out[16])) for i, n in enumerate(("marching", "ready", "nee", "postnee", "escape", "free"))}
+        d["raw"] = [int(v) for v in out]                                           # the 32 words as the kernels summed them (csrc/vr_pathtrace.h lds_stat)
         return d
 
     def wave_timeline(self, n_waves=8192):
