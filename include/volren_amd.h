@@ -116,13 +116,21 @@ int vr_set_transferfunc(vr_renderer* r, const float* rgba, int n);
  *     path tracer and its sample pool see only the others; "order_tiles" orders those.  Where a vr_render is cut into sub-launches ("sample_pool_mb",
  *     "launch_target_ms") does not move: both go on counting every tile.  A view without clear tiles is launched exactly as with 0.  The split is OFF, whatever the value, while vr_sched_stats counts (every sample passes through the instrumented kernels), with "fast_math" 1 and
  *     with "integrator" 2 or 3.  Results never depend on it: the frames are the same bits.  A camera ray of a clear tile that does hit the box -- a bug of the
- *     classification -- is reported by vr_synchronize like a tripped watchdog, in words of its own) (int);  "tonemap_exposure" "tonemap_gamma" "albedo"(3) "phase" "density_scale"
+ *     classification -- is reported by vr_synchronize like a tripped watchdog, in words of its own)
+ *     "see_through_tiles" (0 / 1, default 1.  A tile is SEE-THROUGH when rays of it surely cross the box (its rectangle, SHRUNK by one pixel, meets the box's projection) and no camera ray of its pixels can come within reach of a density tap
+ *     of an 8^3-voxel cell of the density grid whose range allows density > 0: its rays cross the box, but no real collision can happen on them, so every sample
+ *     of it is the environment, alpha 0, as well.  Decided on the host from the grid's range table -- every live cell grown by 3.5 voxels, projected, its
+ *     rectangle grown by one pixel.  Where "sky_tiles" splits a submit, such tiles go to the same per-pixel kernel, without its box test.  None for "integrator"
+ *     other than 0 or 1, with an emission grid or a transfer function bound, a density scale that is negative or not finite, the camera inside the box, a live
+ *     cell behind or beside the camera, a NaN in the range table, or a float grid (encoded on the device: the host holds no table).  Results never depend on it)
+ *     (int);  "tonemap_exposure" "tonemap_gamma" "albedo"(3) "phase" "density_scale"
  *     "emission_scale" "vol_clip_min"(3) "vol_clip_max"(3) "env_strength" "env_transform"(9) "env_rot"(1, degrees about +y,
  *     main.cpp:382) "tf_window_left" "tf_window_width" "cam_pos"(3) "cam_dir"(3) "cam_up"(3) "cam_fov" "volume_transform"(16)
  *     "denoise_sigma"(5: the edge-stopping widths of vr_denoise for colour, normal, depth, coverage, albedo; each in [2^-60, 2^60], about
  *     [8.7e-19, 1.15e18]: VR_ERR otherwise, the old values kept; default 4, 0.5, 0.1, 0.25, 0.2) (float) */
 /* read-only through vr_get_int: "last_sky_tiles" (the clear tiles of the last submit -- the last vr_render / flushed vr_trace run, or the last group of a
- *     vr_render_adaptive: what "sky_tiles" kept out of the path tracer there; 0 when that submit was not split);  "seed_table_samples" (samples 1 .. this of every pixel have their seeds in the table now; 0 = no table) and "seed_table_fills"
+ *     vr_render_adaptive: what "sky_tiles" kept out of the path tracer there; 0 when that submit was not split) and "last_see_through_tiles" (the same for the
+ *     see-through tiles; "last_sky_tiles" counts the clear ones only);  "seed_table_samples" (samples 1 .. this of every pixel have their seeds in the table now; 0 = no table) and "seed_table_fills"
  *     (fill launches of this renderer so far: a frame that repeats the last one's seed, size and samples adds none);  "kernel_variant" (the compiled path-tracing kernel the next launch uses: 0 brick grid, 1 dense fp16 grid, 2 / 4 brick grid +
  *     emission grid, 3 everything decided at run time -- correct for every scene, up to an order of magnitude slower) and "kernel_variant_reason" (what sent the
  *     scene to variant 3, a mask: 1 integrator != 0, 2 the environment's warp table has thresholds below 2^-76 ("env_div_safe" = 0), 4 density scale outside

@@ -127,6 +127,8 @@ const IntParam kIntParams[] = {
     { "order_tiles", VR_INT(order_tiles), 0, 2, "order_tiles: 0 (never), 1 (tile subsets), 2 (always)" },
     { "sky_tiles", VR_INT(sky_tiles), 0, 1, "sky_tiles: 0 (every tile through the path tracer) or 1 (tiles whose camera rays cannot hit the volume's box are rendered apart)" },
     { "last_sky_tiles", VR_READ_ONLY(R.last_sky_tiles) },
+    { "see_through_tiles", VR_INT(see_through_tiles), 0, 1, "see_through_tiles: 0 or 1 (where the clear tiles are rendered apart, so are the tiles whose camera rays cross the box without reaching a voxel with density)" },
+    { "last_see_through_tiles", VR_READ_ONLY(R.last_see_through_tiles) },
     { "grid_frame_counter", VR_GET(R.volume ? (int)R.volume->grid_frame_counter : 0), set_grid_frame, VR_ANY },
     { "n_grid_frames", VR_READ_ONLY(R.volume ? (int)R.volume->n_grid_frames() : 0) },
     { "last_launches", VR_READ_ONLY(R.last_launches) },

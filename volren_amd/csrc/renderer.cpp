@@ -83,11 +83,18 @@ void RendererHIP::commit() {
     emission_grids.clear();
     majorant_emission = 0.f;
     maj_key_ = MajKey{};
+    ++commit_version_;                                            // a cached tile split belongs to the volume it was made from
     std::cout << "Preparing brick grids for HIP..." << std::endl;
     std::vector<size_t> with_emission;                              // frames that have an emission grid (index into both vectors' tails)
     for (const auto& frame : volume->grids) {
         Volume::GridPtr density_grid = frame.at("density");       // throws std::out_of_range like the reference
         density_grids.push_back(grid_to_device(density_grid));
+        // the see-through tiles (vr_sky_tiles.h) go by the range table of the host grid the device copy was made from: a brick grid's or a dense fp16 grid's own;
+        // a float grid is encoded on the device (or into a temporary brick grid) and the host holds no table of it
+        if (auto bg = std::dynamic_pointer_cast<BrickGrid>(density_grid))
+            density_grids.back().live_cells = std::make_shared<const SkyLiveCells>(sky_live_cells(bg->range.data.data(), (int32_t)bg->range.stride.x, (int32_t)bg->range.stride.y, (int32_t)bg->range.stride.z));
+        else if (auto dg = std::dynamic_pointer_cast<DenseGridF16>(density_grid))
+            density_grids.back().live_cells = std::make_shared<const SkyLiveCells>(sky_live_cells(dg->range.data.data(), (int32_t)dg->range.stride.x, (int32_t)dg->range.stride.y, (int32_t)dg->range.stride.z));
         Volume::GridPtr emission_grid;
         for (const char* name : { "flame", "flames", "temperature" }) {
             auto it = frame.find(name);
@@ -507,29 +514,50 @@ uint64_t RendererHIP::tile_order_key(const SceneParams& P, const std::vector<int
     return key ? key : 1;
 }
 
-// Clear tiles (vr_sky_tiles.h) are no work for the path scheduler: split_tiles takes them out of a submit's list.  What costliest_first says about order
-// applies to the march tiles that stay.  The classification reads what tile_order's key hashes and nothing else, so the device list -- and the answer "no
-// clear tile", which needs none -- is cached under that key.
-RendererHIP::SplitTiles RendererHIP::split_tiles(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles, bool ordered) {
+// The three-way split (vr_sky_tiles.h sky_split_tiles3) with the live cells of the launch's density grid -- or with none, which leaves the see-through class
+// empty and the other two what sky_split_tiles gives: when the class is switched off, or the host holds no range table of the grid.
+void RendererHIP::split_three(const LaunchInputs& in, const std::vector<int32_t>& ids, int n_tiles, std::vector<int32_t>& march, std::vector<int32_t>& clear, std::vector<int32_t>& see) const {
+    static const SkyLiveCells none;
+    const std::shared_ptr<const SkyLiveCells>& held = density_grids.at(in.frame).live_cells;
+    sky_split_tiles3(in.P, in.see_through_tiles != 0 && held ? *held : none, ids, n_tiles, march, clear, see);
+}
+
+// Clear and see-through tiles (vr_sky_tiles.h) are no work for the path scheduler: split_tiles takes them out of a submit's list.  What costliest_first says about
+// order applies to the march tiles that stay.  The clear class reads what tile_order's key hashes and nothing else; the see-through class also reads the density
+// grid's live cells (the grid frame of one committed volume), its switch, the index-to-world transform and the uniforms its fallbacks look at.  The device list --
+// and the answer "nothing to split off", which needs none -- is cached under the key of all of that.
+RendererHIP::SplitTiles RendererHIP::split_tiles(const LaunchInputs& in, const std::vector<int32_t>& ids, int n_tiles, bool ordered) {
+    const SceneParams& P = in.P;
     const int tag = ordered ? 2 : 1;
     uint64_t key = fnv1a(&tag, sizeof tag, tile_order_key(P, ids, n_tiles));
+    {
+        const Uniforms& u = P.u;
+        const uint64_t frame = in.frame, version = commit_version_;
+        auto mix = [&key](const void* p, size_t nbytes) { key = fnv1a(p, nbytes, key); };
+        mix(&frame, sizeof frame); mix(&version, sizeof version); mix(&in.see_through_tiles, sizeof in.see_through_tiles);
+        mix(u.vol_density_transform, sizeof u.vol_density_transform); mix(&u.vol_density_scale, sizeof u.vol_density_scale);
+        mix(&u.integrator, sizeof u.integrator); mix(&u.has_emission, sizeof u.has_emission); mix(&u.use_tf, sizeof u.use_tf);
+    }
     key = key ? key : 1;
     if (split_key_ != key) {
-        std::vector<int32_t> march, sky;
-        sky_split_tiles(P, ids, n_tiles, march, sky);
-        if (!sky.empty()) {
+        std::vector<int32_t> march, clear, see;
+        split_three(in, ids, n_tiles, march, clear, see);
+        if (!clear.empty() || !see.empty()) {
             if (ordered && !march.empty()) march = costliest_first(P, march, (int)march.size());
-            march.insert(march.end(), sky.begin(), sky.end());
+            march.insert(march.end(), clear.begin(), clear.end());
+            march.insert(march.end(), see.begin(), see.end());
             ensure_buffer(split_dev_, march.size() * sizeof(int32_t));
             split_dev_->upload(march.data(), march.size() * sizeof(int32_t), stream);
         }
-        split_n_sky_ = (int)sky.size();
+        split_n_sky_ = (int)clear.size();
+        split_n_see_ = (int)see.size();
         split_key_ = key;
     }
     SplitTiles s;
-    if (split_n_sky_ > 0) {
+    if (split_n_sky_ + split_n_see_ > 0) {
         s.n_sky = split_n_sky_;
-        s.n_march = n_tiles - split_n_sky_;
+        s.n_see = split_n_see_;
+        s.n_march = n_tiles - split_n_sky_ - split_n_see_;
         s.march = split_dev_->as<int32_t>();
         s.sky = s.march + s.n_march;
     }
@@ -548,7 +576,7 @@ const int32_t* RendererHIP::tile_order(const SceneParams& P, const std::vector<i
 
 bool RendererHIP::LaunchInputs::same_launch_as(const LaunchInputs& o) const {
     return memcmp(&P, &o.P, sizeof P) == 0 && frame == o.frame && maj == o.maj && tuning == o.tuning && order_tiles == o.order_tiles && launch_target_ms == o.launch_target_ms &&
-           fast_math == o.fast_math && variance == o.variance && sky_tiles == o.sky_tiles && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
+           fast_math == o.fast_math && variance == o.variance && sky_tiles == o.sky_tiles && see_through_tiles == o.see_through_tiles && sample_pool_bytes == o.sample_pool_bytes && stream == o.stream;
 }
 
 // What a launch reads from the renderer's public, freely mutable state -- taken when trace() / render() is CALLED (the reference issues its dispatch at that
@@ -602,6 +630,7 @@ void RendererHIP::capture(LaunchInputs& in) {
     in.maj.blocked = in.P.density.maj_blocked;
     in.tuning = tuning;
     in.order_tiles = order_tiles; in.launch_target_ms = launch_target_ms; in.fast_math = fast_math ? 1 : 0; in.variance = variance != 0 ? 1 : 0; in.sky_tiles = sky_tiles != 0 ? 1 : 0;
+    in.see_through_tiles = see_through_tiles != 0 ? 1 : 0;
     in.sample_pool_bytes = sample_pool_bytes;
     in.stream = stream;
     in.env = environment; in.tf = transferfunc;
@@ -627,11 +656,11 @@ void RendererHIP::submit_tile_set(const LaunchInputs& in, int first, int n) {
     if (n <= 0) return;
     const int n_tiles = tile_set_size();
     const bool ordered = in.order_tiles >= 2 || (in.order_tiles == 1 && tiles_dev_);
-    const SplitTiles split = in.splits_sky() ? split_tiles(in.P, tiles_dev_ ? tiles_host_ : std::vector<int32_t>(), n_tiles, ordered) : SplitTiles{};
-    if (split.n_sky > 0) {                                       // the march tiles to the path tracer, the clear ones to the sky kernel
-        const int per_launch = prepare_submit(in, first, n, split.n_march, split.n_sky);
+    const SplitTiles split = in.splits_sky() ? split_tiles(in, tiles_dev_ ? tiles_host_ : std::vector<int32_t>(), n_tiles, ordered) : SplitTiles{};
+    if (split.n_sky + split.n_see > 0) {                         // the march tiles to the path tracer, the clear and the see-through ones to the sky kernel
+        const int per_launch = prepare_submit(in, first, n, split.n_march, split.n_sky + split.n_see);
         open_timing_window(in.stream);
-        submit(in, first, n, split.march, split.n_march, per_launch, split.sky, split.n_sky);
+        submit(in, first, n, split.march, split.n_march, per_launch, split.sky, split.n_sky, split.n_see);
         close_timing_window(in.stream);
         return;
     }
@@ -693,9 +722,10 @@ int RendererHIP::prepare_submit(const LaunchInputs& in, int first, int n, int n_
     return per_launch;
 }
 
-void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch, const int32_t* sky, int n_sky) {
+void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch, const int32_t* sky, int n_sky, int n_see) {
     const SceneParams& P = in.P;
     last_sky_tiles = n_sky;
+    last_see_through_tiles = n_see;
     hipStream_t stream = in.stream;
     const PathtraceKernel kernel = in.kernel();
     const bool pt_kernel = kernel.item_integrator == 0;          // launch_pathtrace records the events around the path-tracing kernel only
@@ -703,7 +733,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
     // finished sub-launch; when there is none for the current settings and the request is large, a short probe launch measures it first (one
     // synchronisation, once per change of settings).  A plan can still be off -- the rate is a property of the scene AND the view -- which costs nothing
     // but the bound: the kernel's watchdog watches progress, not duration (vr_pathtrace.h).
-    const double px_samples = (double)(n_tiles + n_sky) * 256.0;                // samples per spp of this launch: the clear tiles' too -- the events whose time gives the
+    const double px_samples = (double)(n_tiles + n_sky + n_see) * 256.0;        // samples per spp of this launch: the clear and see-through tiles' too -- the events whose time gives the
                                                                                  // rate span the path-tracing kernel AND the sky kernel, and the plan divides by the same count
     const uint64_t key = [&] {
         uint64_t h = kFnv1aStart;
@@ -745,7 +775,7 @@ void RendererHIP::submit(const LaunchInputs& in, int first, int n, const int32_t
         int seed_samples = 0;
         const uint32_t* seed_table = kernel.reads_seed_table ? seed_table_for(P, first + done, m, stream, &seed_samples) : nullptr;
         launch_pathtrace(in.tuning, P, color->as<float>(), n_tiles > 0 ? pool_->as<float>() : nullptr, n_tiles > 0 ? workspace_->as<float>() : nullptr, status_->as<uint32_t>() + 1, tiles, n_tiles, first + 1 + done, m,
-                         status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments, seed_table, seed_samples, sky, n_sky);
+                         status_->as<uint32_t>(), stream, in.fast_math != 0, eb, ee, moments, seed_table, seed_samples, sky, n_sky, n_see);
         VR_HIP(hipGetLastError());
         done += m;
         if (pt_kernel) { rate_pending_samples_ = px_samples * (double)m; rate_pending_key_ = key; }
@@ -1538,23 +1568,26 @@ void RendererHIP::render_adaptive(int min_spp, int max_spp, float threshold) {
     auto launch_groups = [&](const std::vector<int32_t>& ids, const auto& to) {
         const auto groups = adaptive_groups(ids, tile_n_);
         std::vector<int32_t> packed;
-        std::vector<int> n_sky;                       // per group: its clear tiles, which lie behind its march tiles in `packed`
+        std::vector<int> n_sky, n_see;                // per group: its clear and its see-through tiles, which lie in that order behind its march tiles in `packed`
         for (const auto& g : groups) {
-            std::vector<int32_t> march = g.second, sky;
-            if (split) sky_split_tiles(in.P, g.second, (int)g.second.size(), march, sky);
+            std::vector<int32_t> march = g.second, sky, see;
+            if (split) split_three(in, g.second, (int)g.second.size(), march, sky, see);
             if (ordered && !march.empty()) march = costliest_first(in.P, march, (int)march.size());
             packed.insert(packed.end(), march.begin(), march.end());
             packed.insert(packed.end(), sky.begin(), sky.end());
+            packed.insert(packed.end(), see.begin(), see.end());
             n_sky.push_back((int)sky.size());
+            n_see.push_back((int)see.size());
         }
         if (packed.empty()) return;
         sized_.adaptive_lists->upload(packed.data(), packed.size() * sizeof(int32_t), in.stream);
         size_t off = 0, k = 0;
         for (const auto& g : groups) {
             const int32_t n = g.first, next = to(n);
-            const int n_clear = n_sky[k++], n_tiles = (int)g.second.size() - n_clear;      // the march tiles
+            const int n_clear = n_sky[k], n_through = n_see[k], n_tiles = (int)g.second.size() - n_clear - n_through;      // the march tiles
+            ++k;
             const int32_t* list = sized_.adaptive_lists->as<int32_t>() + off;
-            submit(in, n, next - n, list, n_tiles, prepare_submit(in, n, next - n, n_tiles, n_clear), n_clear > 0 ? list + n_tiles : nullptr, n_clear);
+            submit(in, n, next - n, list, n_tiles, prepare_submit(in, n, next - n, n_tiles, n_clear + n_through), n_clear + n_through > 0 ? list + n_tiles : nullptr, n_clear, n_through);
             for (int32_t t : g.second) tile_n_[(size_t)t] = next;
             off += g.second.size();
         }

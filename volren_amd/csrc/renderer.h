@@ -29,6 +29,8 @@
 
 namespace vr {
 
+struct SkyLiveCells;                       // vr_sky_tiles.h (host only)
+
 // stand-in for cppgl's camera (pos/dir/up/fov_degree are what the renderer reads: renderer.cpp:93-95)
 struct Camera {
     vec3 pos{ 1.f, 0.f, 1.f };                 // main.cpp:458
@@ -62,6 +64,8 @@ struct BrickGridHIP {
     int32_t mshift[3] = { 3, 3, 3 };       // padded power-of-two extent of `majorant` (vr_scene.h)
     size_t n_active = 0;                   // bricks whose voxels matter (range not a single value): what the choice of the majorant layout looks at
     bool maj_blocked = false;              // commit()'s choice for this grid: majorant levels 0-1 in 4x4x4-cell blocks (vr_scene.h majorant_cell_index)
+    std::shared_ptr<const SkyLiveCells> live_cells;   // which cells of the host grid's range table can hold density > 0 (vr_sky_tiles.h), for the see-through tiles of a
+                                           // density grid; null for a grid whose table the host does not hold (encoded on the device): no see-through tile then
     mat4 transform;
 };
 
@@ -168,6 +172,12 @@ struct RendererHIP {
                                                       // every sample passes through them), in the tolerance mode (fast_math: its frames belong to that build's arithmetic) and for the
                                                       // item integrators (2, 3).  Results never depend on it
     int last_sky_tiles = 0;                           // clear tiles of the last submit (0: it was not split)
+    int see_through_tiles = 1;                        // 1: where the clear tiles are split off (sky_tiles says where), so are a submit's SEE-THROUGH tiles -- tiles whose rays surely cross the
+                                                      // box but cannot come within tap reach of a cell of the density grid that holds density > 0 (vr_sky_tiles.h): every sample of
+                                                      // theirs is (environment, alpha 0) as well, and the same kernel renders them without the box test.  Only for integrators 0 and 1
+                                                      // without emission grid and transfer function, a finite density scale >= 0 and a grid whose range table the host holds; a view
+                                                      // without such tiles is launched as with 0.  Results never depend on it
+    int last_see_through_tiles = 0;                   // see-through tiles of the last submit (last_sky_tiles counts the clear ones only)
     int last_launches = 0;                            // path-tracing sub-launches of the last trace()/render()/render_adaptive()
     int adaptive_rounds = 0;                          // error evaluations (rounds) of the last render_adaptive()
     int launch_target_ms = 2000;                      // a sub-launch is planned to take at most this long, from the rate the renderer measured on its last launch (a short
@@ -346,7 +356,7 @@ private:
         MajKey maj;
         size_t frame = 0;
         PathtraceTuning tuning;
-        int order_tiles = 0, launch_target_ms = 0, fast_math = 0, variance = 0, sky_tiles = 0;
+        int order_tiles = 0, launch_target_ms = 0, fast_math = 0, variance = 0, sky_tiles = 0, see_through_tiles = 0;
         size_t sample_pool_bytes = 0;
         hipStream_t stream = nullptr;
         std::shared_ptr<Environment> env;
@@ -364,8 +374,9 @@ private:
     // With clear tiles split off (sky, n_sky: their device list), tiles / n_tiles are the MARCH tiles alone: the pool's allocation sees only those, and every
     // sub-launch's sample window is followed by the sky kernel over the clear ones; the samples of a sub-launch stay what the pool's budget gives the whole tile set, and
     // the rate plan counts all the submit's samples over the time of both kernels (the split moves no sub-launch boundary a caller has sized).  n_tiles == 0 (every tile clear): no pool, no workspace, no path-tracing launch.
+    // See-through tiles (n_see) follow the clear ones in `sky` and are treated like them; prepare_submit's n_sky counts both classes.
     int prepare_submit(const LaunchInputs& in, int first, int n, int n_tiles, int n_sky = 0);
-    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch, const int32_t* sky = nullptr, int n_sky = 0);
+    void submit(const LaunchInputs& in, int first, int n, const int32_t* tiles, int n_tiles, int per_launch, const int32_t* sky = nullptr, int n_sky = 0, int n_see = 0);
     void submit_tile_set(const LaunchInputs& in, int first, int n);      // prepare, then one window around a submit over the renderer's tile set (set_tiles), ordered as order_tiles says
     void open_timing_window(hipStream_t s), close_timing_window(hipStream_t s);      // of one call: last_launches, last_kernel_ms, last_pathtrace_ms
     int tile_set_size() const;                 // tiles of the renderer's tile set: the listed ones, or all of the frame
@@ -382,13 +393,18 @@ private:
     std::vector<int32_t> costliest_first(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const;
     const int32_t* tile_order(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles);
     uint64_t tile_order_key(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles) const;      // (camera, box, frame size, tile list)
-    // The same tiles divided by vr_sky_tiles.h sky_split_tiles: the march tiles (costliest first if `ordered`, else in the list's order) and the clear ones, as one
-    // device list [march | sky] cached under tile_order's key (with `ordered`).  n_sky == 0: the list was not built -- the caller launches as without the split.
-    struct SplitTiles { const int32_t* march = nullptr; int n_march = 0; const int32_t* sky = nullptr; int n_sky = 0; };
-    SplitTiles split_tiles(const SceneParams& P, const std::vector<int32_t>& ids, int n_tiles, bool ordered);
+    // The same tiles divided by vr_sky_tiles.h sky_split_tiles3: the march tiles (costliest first if `ordered`, else in the list's order), the clear ones and the
+    // see-through ones, as one device list [march | clear | see-through] cached under tile_order's key with `ordered` and with what the see-through class reads
+    // besides: the grid frame, the version of the committed volume, the class switch and the uniforms its fallbacks look at.  n_sky + n_see == 0: the list was not
+    // built -- the caller launches as without the split.
+    struct SplitTiles { const int32_t* march = nullptr; int n_march = 0; const int32_t* sky = nullptr; int n_sky = 0, n_see = 0; };
+    SplitTiles split_tiles(const LaunchInputs& in, const std::vector<int32_t>& ids, int n_tiles, bool ordered);
+    // the one three-way split of a submit's list: the grid's live cells when the see-through class is on for `in`, the clear tiles alone otherwise
+    void split_three(const LaunchInputs& in, const std::vector<int32_t>& ids, int n_tiles, std::vector<int32_t>& march, std::vector<int32_t>& clear, std::vector<int32_t>& see) const;
     DeviceBufferPtr split_dev_;
     uint64_t split_key_ = 0;
-    int split_n_sky_ = 0;
+    int split_n_sky_ = 0, split_n_see_ = 0;
+    uint64_t commit_version_ = 0;              // counts commit(): the live cells a cached split was made from belong to one committed volume
     // adaptive sampling: samples behind each raster tile, meaningful while `sample` == tile_n_sample_ (ragged()); the denoiser's device copy: sized_.tile_n_dev
     std::vector<int32_t> tile_n_;
     int tile_n_sample_ = -1;

@@ -47,8 +47,9 @@ void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb,
                       // optional: the launch's CLEAR tiles (vr_sky_tiles.h; a device list, disjoint from `tiles`), whose samples of the same window sky_kernel
                       // renders into fb (and moments) without scheduler or pool, after the path-tracing kernel on the same stream and inside the same pair of
                       // events; it reads the same seed table.  n_tiles may be 0 then: no path-tracing kernel is launched and sample_pool, workspace and
-                      // unit_counter are not touched.  A camera ray of theirs that hits the box sets kSkyHitStatus in status[0]
-                      const int32_t* sky_tiles = nullptr, int32_t n_sky_tiles = 0);
+                      // unit_counter are not touched.  A camera ray of theirs that hits the box sets kSkyHitStatus in status[0].
+                      // n_see_tiles: the launch's SEE-THROUGH tiles, which follow the clear ones in sky_tiles and are rendered by the same launch without the box test
+                      const int32_t* sky_tiles = nullptr, int32_t n_sky_tiles = 0, int32_t n_see_tiles = 0);
 constexpr uint32_t kSkyHitStatus = 8u;
 // Denoiser features of samples 1..spp for every pixel of the listed tiles (tiles == nullptr: all n_tiles of the frame): out = W*H*8 floats,
 // (albedo.rgb, coverage, normal.xyz, depth) per pixel, row 0 at the bottom (vr_trace.h feature_pixel).  Pixels of other tiles are not written.

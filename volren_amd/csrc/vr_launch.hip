@@ -6,8 +6,8 @@
 // Radiance per (pixel, sample) goes to a sample pool; accumulate_kernel folds it into the RGBA32F running mean in sample
 // order, which makes the result bit-identical to the reference's one-dispatch-per-sample loop (renderer.cpp:138-140,
 // pathtracer_brick.glsl:36).  MFMA is not used: there is no dense contraction on this path.
-// The tiles of a launch that no camera ray can hit the volume's box from (vr_sky_tiles.h) never enter that path: sky_kernel renders them, one thread per
-// pixel, straight into the running mean.
+// The tiles of a launch that no camera ray can hit the volume's box from, and those whose rays cross the box but cannot reach a voxel with density (vr_sky_tiles.h:
+// clear and see-through tiles), never enter that path: sky_kernel renders them, one thread per pixel, straight into the running mean.
 //
 // Also here: the integrators that run one thread per (pixel, sample) item -- direct volume rendering (common.glsl:571-591)
 // and ray marching --, which fill the same sample pool, and the denoiser's feature pass.
@@ -91,11 +91,14 @@ accumulate_kernel(const float* __restrict__ sbuf, float* __restrict__ fb, float*
 // of a wavefront fetch neighbouring texels of the environment.  Starts from the framebuffer's texel when first_sample > 1.
 // A ray that does hit the box means the classifier called a tile clear that is not: the pixel stops there and the kernel sets kSkyHitStatus in the renderer's
 // status word (RendererHIP::check_watchdog throws).  A tripwire for a bug, never a fallback.
+// The list is [clear | see-through]: the workgroups from n_clear on serve SEE-THROUGH tiles (vr_sky_tiles.h: rays that cross the box without a voxel with density
+// in tap reach), whose samples are the same sky_sample without the box test -- hit or miss, the sample is the sky's; there is no tripwire to set for them.
 template <bool MOMENTS>
 __global__ void __launch_bounds__(256)
-sky_kernel(const SceneParams P, float* __restrict__ fb, float* __restrict__ moments, const int32_t* __restrict__ tiles, int32_t first_sample, int32_t n_samples,
-           const SeedTable seeds, uint32_t* __restrict__ status) {
+sky_kernel(const SceneParams P, float* __restrict__ fb, float* __restrict__ moments, const int32_t* __restrict__ tiles, int32_t n_clear, int32_t first_sample,
+           int32_t n_samples, const SeedTable seeds, uint32_t* __restrict__ status) {
     const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
+    const bool box_test = (int32_t)blockIdx.x < n_clear;                      // uniform over the workgroup
     const TilePixel q = wave_tiled_pixel(tiles[blockIdx.x], threadIdx.x, W);
     if (q.px >= W || q.py >= H) return;
     float4* texel = reinterpret_cast<float4*>(fb) + (size_t)q.py * W + q.px;
@@ -112,7 +115,7 @@ sky_kernel(const SceneParams P, float* __restrict__ fb, float* __restrict__ mome
         if (seeds.table != nullptr && smp - 1 < seeds.cap) seed = seeds.table[seed_table_index<uint32_t>((uint32_t)(smp - 1), seeds.n_tiles, (uint32_t)q.tile, (uint32_t)q.sub, (uint32_t)q.lane)];
         else seed = path_seed((uint32_t)P.u.seed, W, q.px, q.py, smp);
         float L[4];
-        if (!sky_sample(P, q.px, q.py, seed, L)) { hit = true; break; }
+        if (!sky_sample(P, q.px, q.py, seed, L, box_test)) { hit = true; break; }
         fold_sample<MOMENTS>(acc, S, L, smp);
     }
     *texel = pack4(acc);
@@ -274,19 +277,19 @@ size_t pathtrace_workspace_floats() { return kColdMainFloats + (size_t)kMaxWorkg
 
 void launch_pathtrace(const PathtraceTuning& T, const SceneParams& P, float* fb, float* sample_pool, float* workspace, uint32_t* unit_counter, const int32_t* tiles, int32_t n_tiles,
                       int32_t first_sample, int32_t n_samples, uint32_t* status, hipStream_t stream, bool fast_math, hipEvent_t ev_kernel_begin, hipEvent_t ev_kernel_end,
-                      float* moments, const uint32_t* seed_table, int32_t seed_samples, const int32_t* sky_tiles, int32_t n_sky_tiles) {
-    if (n_samples <= 0 || (n_tiles <= 0 && n_sky_tiles <= 0)) return;
+                      float* moments, const uint32_t* seed_table, int32_t seed_samples, const int32_t* sky_tiles, int32_t n_sky_tiles, int32_t n_see_tiles) {
+    if (n_samples <= 0 || (n_tiles <= 0 && n_sky_tiles + n_see_tiles <= 0)) return;
     SeedTable seeds;
     seeds.table = seed_samples > 0 ? seed_table : nullptr;
     seeds.cap = seed_samples;
     seeds.n_tiles = tile_count(P.u.resolution[0], P.u.resolution[1]);
-    // the clear tiles of the launch, behind the path-tracing kernel on the same stream and inside the same pair of events
+    // the clear and the see-through tiles of the launch, in one launch behind the path-tracing kernel on the same stream and inside the same pair of events
     auto launch_sky = [&] {
-        if (n_sky_tiles <= 0) return;
+        if (n_sky_tiles + n_see_tiles <= 0) return;
         const auto sky = moments ? sky_kernel<true> : sky_kernel<false>;
-        hipLaunchKernelGGL(sky, dim3((unsigned)n_sky_tiles), dim3(256), 0, stream, P, fb, moments, sky_tiles, first_sample, n_samples, seeds, status);
+        hipLaunchKernelGGL(sky, dim3((unsigned)(n_sky_tiles + n_see_tiles)), dim3(256), 0, stream, P, fb, moments, sky_tiles, n_sky_tiles, first_sample, n_samples, seeds, status);
     };
-    if (n_tiles <= 0) {                             // every tile of the launch is clear: no path-tracing kernel, no sample pool
+    if (n_tiles <= 0) {                             // every tile of the launch is clear or see-through: no path-tracing kernel, no sample pool
         if (ev_kernel_begin) (void)hipEventRecord(ev_kernel_begin, stream);
         launch_sky();
         if (ev_kernel_end) (void)hipEventRecord(ev_kernel_end, stream);

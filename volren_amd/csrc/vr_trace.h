@@ -1043,7 +1043,9 @@ VR_HD void first_resume(Hot& h, const SceneParams& P) {
 // volume's box -- jitter, direction and box test as do_new / begin_segment do them, the radiance as do_escape writes it for a `first` path (L = 0, throughput 1,
 // no scattering: mis = 1, alpha 0).  Returns false, with nothing produced, when the ray HITS the box: the sample is the path tracer's then.  No path state, no
 // scheduler, no sample pool: what the kernel of the clear tiles runs per sample (vr_launch.hip sky_kernel; vr_sky_tiles.h says which tiles those are).
-VR_HD bool sky_sample(const SceneParams& P, int32_t px, int32_t py, uint32_t seed, float out[4]) {
+// box_test = false: the sample of a SEE-THROUGH tile (vr_sky_tiles.h) -- its ray may cross the box, but no real collision can happen on it, so the path tracer
+// would leave the camera segment with the same L = 0, throughput 1, mis = 1 and write the same value: hit or miss, the sample is the sky's.  Always true then.
+VR_HD bool sky_sample(const SceneParams& P, int32_t px, int32_t py, uint32_t seed, float out[4], bool box_test = true) {
     const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
     const float jx = rng(seed), jy = rng(seed);
     const float fx = (((float)px + jx) - (float)W * 0.5f) / (float)H;
@@ -1051,7 +1053,7 @@ VR_HD bool sky_sample(const SceneParams& P, int32_t px, int32_t py, uint32_t see
     const v3 dir = normalize(mat3_mul(P.u.cam_transform, normalize(v3{ fx, fy, P.cam_z })));
     const v3 pos = v3{ P.u.cam_pos[0], P.u.cam_pos[1], P.u.cam_pos[2] };
     float tnear, tfar;
-    if (intersect_box(pos, dir, P.u.vol_bb_min, P.u.vol_bb_max, tnear, tfar)) return false;
+    if (box_test && intersect_box(pos, dir, P.u.vol_bb_min, P.u.vol_bb_max, tnear, tfar)) return false;
     v3 L = v3{ 0.0f, 0.0f, 0.0f };
     if (P.u.show_environment > 0) L = L + (v3{ 1.0f, 1.0f, 1.0f } * 1.0f) * lookup_environment(P, dir);      // do_escape's L + (thr * mis) * Le
     out[0] = L.x; out[1] = L.y; out[2] = L.z; out[3] = 0.0f;

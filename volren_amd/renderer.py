@@ -9,8 +9,8 @@ from . import _lib
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
                "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
-               "expected_skip", "expected_stats", "sky_tiles")
-_READ_ONLY_INT_FIELDS = ("n_grid_frames", "last_launches", "last_sky_tiles", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
+               "expected_skip", "expected_stats", "sky_tiles", "see_through_tiles")
+_READ_ONLY_INT_FIELDS = ("n_grid_frames", "last_launches", "last_sky_tiles", "last_see_through_tiles", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
                          "kernel_wide", "adaptive_rounds", "seed_table_samples", "seed_table_fills")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
                  "emission_scale": 1, "vol_clip_min": 3, "vol_clip_max": 3, "env_strength": 1, "env_transform": 9,
