@@ -209,6 +209,17 @@ int vr_framebuffer_device(vr_renderer* r, void** device_ptr);
  *     waits and writes the last pass's totals: out[0] sub-rays marched, [1] steps reached (dropped ones included), [2] steps that fetched their
  *     corners, [3] reads of the table; VR_ERR when "expected_stats" was off for that pass.  vr_expected_clear_table (test hook) writes the table of
  *     the current density grid, built if need be, x fastest, and its extent in cells; out may be NULL (the extent alone).
+ *     The field: vr_set_int "expected_field" 0 (the default) marches the trilinear density as above; 1 marches the field the path tracer decides
+ *     its collisions on (other values VR_ERR).  Without a transfer function that is the separable cubic B-spline of the voxels -- the mean of the
+ *     tracker's stochastic tricubic tap: 64 taps a step, floor(p - 0.5) - 1 .. + 2 per axis, value and gradient from the same taps
+ *     (volren_amd/csrc/vr_cubic.h) -- and the coverage is then the one the framebuffer's alpha converges to: the trilinear march lies 4e-4 below it
+ *     on smoke.brick and 6e-3 on a dense 64^3 grid, the cubic one within sampling noise at 4096 spp.  With a transfer function the tracker itself
+ *     looks up the trilinear field, and 1 gives the same bits as 0.  The cubic march skips empty space by a table of its own, of reach 2 (the
+ *     cell's box grown by two voxels, 12^3), built and cached like the other; vr_expected_clear_table returns the table the current setting marches
+ *     with, and the frame is the same bits with "expected_skip" 0 and 1.  It costs 3 to 4 times the trilinear pass, and 2 x 2 cubic rays cost more
+ *     than the 16-spp stochastic pass (profiles/r22_expected_cubic.txt).  The setting acts on every expected-value pass -- tile subsets, the parts
+ *     of a sharded renderer, vr_upsample's pass at the large size -- and changing it drops no temporal history: the next pass is simply another
+ *     guide.
  *     vr_features waits and writes W*H*8 floats (albedo.rgb, coverage, normal.xyz, depth), row 0 at the bottom; VR_ERR before the first
  *     vr_render_features since the last resize.
  *     vr_variance waits and writes W*H*4 floats: the unbiased per-channel variance of the samples 1..n behind the framebuffer (0 for n = 1),
@@ -327,7 +338,7 @@ int vr_resolve_background(vr_renderer* r, float* rgba_out);
  *     under vr_denoise_temporal the history (vr_denoise_history) holds the layer S blended over the frames, not the composite, so a turning camera
  *     does not drag old sky along behind the volume.  Whatever vr_resolve refuses these calls refuse then, before anything is launched, besides their
  *     own refusals: it needs vr_render_features_expected with rays >= 2 as the last feature pass.  Without a transfer function kappa lies about
- *     0.0004 below the path tracer's coverage, and that bias stays, as with vr_resolve.  README.md has the measured errors, among them the case that
+ *     0.0004 below the path tracer's coverage, and that bias stays, as with vr_resolve, unless "expected_field" is 1.  README.md has the measured errors, among them the case that
  *     loses.  vr_sharded_denoise / vr_sharded_denoise_temporal honour part 0's setting, bit for bit one device's result.
  *     vr_denoised_layer waits and writes L of the last such call, W*H*4 floats, linear, row 0 at the bottom: the scattered light premultiplied by the
  *     exact coverage, alpha = kappa; composite it over any background B' as (1 - a) B' + rgb.  VR_ERR before the first vr_denoise or
@@ -495,8 +506,8 @@ int vr_math_probe(int fn, const float* a, const float* b, float* out, int n);
  * fn: volren_amd/csrc/vr_math_probe.h (17 has no sweep form); 100..103: the tolerance-mode forms of neg_log_1m (of the draw (first + i) 2^-24), sincos_ (sine, cosine), unorm8 (of (first + i) & 255) */
 int vr_math_sweep(int fn, uint32_t first, long long count, float b, float* out);
 /* test hook: unit-test probe of the scene-data lookups (volren_amd/csrc/vr_probe.h): n items of probe `what` (0 voxel, 1 trilinear, 2 majorant, 3 importance,
- * 4 texel, 5 sky, 6 light sample, 7 transfer function) in compile-time form `form`, on the scene as the renderer's next launch would read it.  in: 4 32-bit words per
- * item; out: 1, 1, 1, 1, 3, 3, 7, 4 floats per item; host arrays.  VR_ERR_RUNTIME for a form the scene cannot serve (the message says why). */
+ * 4 texel, 5 sky, 6 light sample, 7 transfer function, 8 cubic B-spline lookup: value and gradient) in compile-time form `form`, on the scene as the renderer's next
+ * launch would read it.  in: 4 32-bit words per item; out: 1, 1, 1, 1, 3, 3, 7, 4, 4 floats per item; host arrays.  VR_ERR_RUNTIME for a form the scene cannot serve (the message says why). */
 int vr_probe(vr_renderer* r, int what, int form, const void* in, float* out, long long n);
 /* test hook: unit-test probe of the per-path layer (volren_amd/csrc/vr_path_probe.h): n items of `kind` (0 RNG, 1 camera ray, 2 box clip, 3 phase function and
  * MIS weight, 4 DDA step, 5 one whole segment of the hot pair, bounded) in form `form` (DDA step: 0 general, 1 CLEAN; segment: the compiled instance 0..6), on the

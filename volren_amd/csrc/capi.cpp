@@ -123,6 +123,7 @@ const IntParam kIntParams[] = {
     { "seed_table_fills", VR_READ_ONLY(R.seed_table_fills()) },
     { "launch_target_ms", VR_INT(launch_target_ms), 0, INT_MAX, "launch_target_ms must be >= 0 (0 = no sizing by time)" },
     { "expected_skip", VR_INT(expected_skip), 0, 1, "expected_skip: 0 (march every step) or 1 (drop the steps of empty space by the clear-distance table)" },
+    { "expected_field", VR_INT(expected_field), 0, 1, "expected_field: 0 (march the trilinear field) or 1 (the tracker's field: without a LUT the cubic B-spline field)" },
     { "expected_stats", VR_INT(expected_stats), 0, 1, "expected_stats: 0 (off) or 1 (the expected-value passes count their work)" },
     { "order_tiles", VR_INT(order_tiles), 0, 2, "order_tiles: 0 (never), 1 (tile subsets), 2 (always)" },
     { "sky_tiles", VR_INT(sky_tiles), 0, 1, "sky_tiles: 0 (every tile through the path tracer) or 1 (tiles whose camera rays cannot hit the volume's box are rendered apart)" },

@@ -25,6 +25,8 @@
 // written; refused alone.
 // --expected-skip 0|1 with --expected-features: whether that pass skips empty space by the clear-distance table (default 1; the frame is the same either
 // way; refused without --expected-features).
+// --expected-field 0|1 with --expected-features: which field that pass marches -- 0 the trilinear one (default), 1 the tracker's (without a LUT the cubic
+// B-spline field of vr_cubic.h; with one the trilinear field, the same frame); refused without --expected-features.
 // Addition: --adaptive T renders every frame with adaptive sampling per 16x16 tile (render_adaptive(min(16, spp), spp, T): vr_adaptive.h) and logs
 // the mean samples per pixel; combines with --denoise (one device only).
 //
@@ -141,7 +143,7 @@ static void parse_cmd(int argc, char** argv) {
         } else if (arg == "--vol_crop_min") { renderer->vol_clip_min.x = a.nextf(); renderer->vol_clip_min.y = a.nextf(); renderer->vol_clip_min.z = a.nextf(); }
         else if (arg == "--vol_crop_max") { renderer->vol_clip_max.x = a.nextf(); renderer->vol_clip_max.y = a.nextf(); renderer->vol_clip_max.z = a.nextf(); }
         else if (arg == "--seed") renderer->seed = a.nexti();                        // addition
-        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject" || arg == "--expected-features" || arg == "--expected-skip") a.next();  // consumed earlier
+        else if (arg == "--device" || arg == "--gpus" || arg == "--devices" || arg == "--adaptive" || arg == "--denoise-reject" || arg == "--expected-features" || arg == "--expected-skip" || arg == "--expected-field") a.next();  // consumed earlier
         else if (fs::is_regular_file(arg) || fs::is_directory(arg)) handle_path(arg);
     }
 }
@@ -186,6 +188,7 @@ int main(int argc, char** argv) {
     float threshold = 0.f, reject = 0.f;      // reject: --denoise-reject, the history rejection threshold of --denoise-temporal (0 = off)
     int expected_rays = 0;      // --expected-features N: the denoise flags take their guide from render_features_expected(N) instead of render_features(min(spp, 16))
     int expected_skip = -1;     // --expected-skip 0|1 (with --expected-features): whether that pass drops the steps of empty space (same frame either way); -1: the renderer's default
+    int expected_field = -1;    // --expected-field 0|1 (with --expected-features): the field that pass marches, 1 = the tracker's; -1: the renderer's default
     bool resolve = false;       // --resolve (with --expected-features N >= 2): the control variate on the expected coverage, alone or in front of the filter
     bool layers = false;        // --denoise-layers (with a denoise flag and --expected-features N >= 2): the filter runs on the scattered layer alone ("denoise_layers" = 1, vr_layers.h)
     int filter = -1;            // --denoise-filter 0|1 (with --denoise-layers): one pass of local regression in the iterations' place (vr_regress.h); -1: not given
@@ -234,6 +237,11 @@ int main(int argc, char** argv) {
                 const std::string v = argv[++i];
                 if (v != "0" && v != "1") throw std::runtime_error("--expected-skip: 0 (march every step) or 1 (skip empty space)");
                 expected_skip = v == "1" ? 1 : 0;
+            } else if (arg == "--expected-field") {
+                if (i + 1 >= argc) throw std::runtime_error("missing value after --expected-field");
+                const std::string v = argv[++i];
+                if (v != "0" && v != "1") throw std::runtime_error("--expected-field: 0 (the trilinear field) or 1 (the tracker's field)");
+                expected_field = v == "1" ? 1 : 0;
             } else if (arg == "--adaptive") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --adaptive");
                 adaptive = true;
@@ -251,6 +259,7 @@ int main(int argc, char** argv) {
         if (upsample > 0 && !layers) throw std::runtime_error("--upsample needs --denoise-layers: the filtered scattered layer is what it upsamples");
         if (expected_rays > 0 && !denoise && !resolve) throw std::runtime_error("--expected-features needs --denoise, --denoise-temporal or --resolve: it chooses the guide of their filter");
         if (expected_skip >= 0 && expected_rays == 0) throw std::runtime_error("--expected-skip needs --expected-features: it is a setting of that pass");
+        if (expected_field >= 0 && expected_rays == 0) throw std::runtime_error("--expected-field needs --expected-features: it is a setting of that pass");
         if (moments && !temporal) throw std::runtime_error("--denoise-moments needs --denoise-temporal: the moments live in the history that only that call keeps");
         if (moments && reject > 0.f) throw std::runtime_error("--denoise-moments and --denoise-reject do not go together: the rejection statistic needs the frames' sample variance");
         if (adaptive && (gpus > 0 || devices.size() > 1))
@@ -290,6 +299,7 @@ int main(int argc, char** argv) {
             if (filter >= 0) renderer->set_denoise_filter(filter);
             if (ridge >= 0.f) renderer->set_denoise_ridge(ridge);
             if (expected_skip >= 0) renderer->expected_skip = expected_skip;
+            if (expected_field >= 0) renderer->expected_field = expected_field;
             parts.push_back(renderer);
         }
         renderer = parts[0];                            // holds the whole frame after the gather

@@ -1024,7 +1024,8 @@ void RendererHIP::render_features_expected(int rays) {
 
 void RendererHIP::launch_expected(const SceneParams& P, const int32_t* tiles, int n_tiles, int rays, float* out) {
     ClearTable clear = { nullptr, { 0, 0, 0 } };
-    if (expected_skip) clear = clear_table_of(density_grids.at(volume->grid_frame_counter), P.density);
+    const bool cubic = expected_field != 0 && !P.u.use_tf;       // the tracker's field: under a LUT the trilinear one (vr_expected.h)
+    if (expected_skip) clear = clear_table_of(density_grids.at(volume->grid_frame_counter), P.density, cubic ? 2 : 1);
     expected_stats_valid_ = false;
     unsigned long long* counters = nullptr;
     if (expected_stats) {
@@ -1032,26 +1033,27 @@ void RendererHIP::launch_expected(const SceneParams& P, const int32_t* tiles, in
         VR_HIP(hipMemsetAsync(expected_stats_->get(), 0, expected_stats_->size_bytes(), stream));
         counters = expected_stats_->as<unsigned long long>();
     }
-    launch_features_expected(P, tiles, n_tiles, rays, out, stream, &clear, counters);
+    launch_features_expected(P, tiles, n_tiles, rays, out, stream, &clear, counters, cubic);
     VR_HIP(hipGetLastError());
     expected_stats_valid_ = counters != nullptr;
 }
 
 // The clear-distance table of a density grid (vr_clear.h), made by the first pass that asks for it: the table lives with the grid's device arrays, so
 // commit() -- which every change of the volume goes through -- leaves the new grids without one, and each frame of an animation keeps its own.
-ClearTable RendererHIP::clear_table_of(BrickGridHIP& g, const GridView& view) {
+ClearTable RendererHIP::clear_table_of(BrickGridHIP& g, const GridView& view, int reach) {
     ClearTable t;
     clear_cells(view, t.n);
     const size_t cells = (size_t)t.n[0] * (size_t)t.n[1] * (size_t)t.n[2];
-    if (!g.clear_table && cells > 0) {
+    DeviceBufferPtr& cached = g.clear_table[reach == 2 ? 1 : 0];        // one table per grid and reach
+    if (!cached && cells > 0) {
         auto table = make_device_buffer(cells);
         DeviceBuffer scratch(cells);
-        launch_clear_table(view, table->as<uint8_t>(), scratch.as<uint8_t>(), stream);
+        launch_clear_table(view, table->as<uint8_t>(), scratch.as<uint8_t>(), stream, reach == 2 ? 2 : 1);
         VR_HIP(hipGetLastError());
         VR_HIP(hipStreamSynchronize(stream));                   // the scratch half goes with this scope
-        g.clear_table = table;
+        cached = table;
     }
-    t.d = g.clear_table ? g.clear_table->as<uint8_t>() : nullptr;
+    t.d = cached ? cached->as<uint8_t>() : nullptr;
     return t;
 }
 
@@ -1067,9 +1069,11 @@ void RendererHIP::expected_clear_table(uint8_t* out, int cells[3]) {
     LaunchInputs in;
     capture(in);                                                 // the scene as the pass reads it (the decoded float atlas under a transfer function)
     BrickGridHIP& g = density_grids.at(in.frame);
-    const ClearTable t = clear_table_of(g, make_view(g, false, in.P.density.maj_blocked != 0));
+    const int reach = expected_field != 0 && !in.P.u.use_tf ? 2 : 1;      // the table the current setting marches with (launch_expected)
+    const ClearTable t = clear_table_of(g, make_view(g, false, in.P.density.maj_blocked != 0), reach);
     for (int i = 0; i < 3; ++i) cells[i] = t.n[i];
-    if (out && g.clear_table) g.clear_table->download(out, g.clear_table->size_bytes(), stream);
+    const DeviceBufferPtr& table = g.clear_table[reach - 1];
+    if (out && table) table->download(out, table->size_bytes(), stream);
 }
 
 // Test hook (vr_probe.h).  The scene as the next launch reads it: capture() and the majorant table as submit() / render_features() bring them up to date.  A PAIR form

@@ -52,8 +52,8 @@ struct BrickGridHIP {
     bool atlas_f32_failed = false; // its allocation failed once: not retried until commit() or a tf_float_atlas toggle (the byte atlas serves)
     DeviceBufferPtr atlas_paired;  // this grid's voxels interleaved with those of the frame's other grid (density + emission grids of one brick layout: vr_scene.h);
                                    // one buffer, held by both grids of the frame; built by commit()
-    DeviceBufferPtr clear_table;   // clear-distance table (vr_clear.h), one byte per cell, built by the first expected-value pass that reads this grid; a grid
-                                   // that commit() uploads anew starts without one
+    DeviceBufferPtr clear_table[2];// clear-distance tables (vr_clear.h) of reach 1 and 2, one byte per cell, each built by the first expected-value pass that
+                                   // marches this grid with it; a grid that commit() uploads anew starts without them
     DeviceBufferPtr dense;         // dense fp16 voxels in 4x4x4 blocks (DenseGridF16), then bricks/atlas are empty
     int32_t dim[3] = { 0, 0, 0 };
     int32_t dblk[2] = { 0, 0 };            // 4x4x4 blocks per axis (x, y) of the dense layout
@@ -222,8 +222,13 @@ struct RendererHIP {
     // instrumented twin of the kernel; expected_stats_read waits and returns the last pass's totals (sub-rays marched, steps reached, steps that fetched
     // their corners, table reads), and throws when that pass did not count.  expected_clear_table: test hook, the current density grid's table (built if
     // need be) and its extent in cells; out may be null.
+    // expected_field = 1: every expected-value pass (this one, a tile subset's, upsample()'s) marches the field the tracker decides its collisions on: without a
+    // LUT the cubic B-spline field of vr_cubic.h (64 taps a step; the clear-distance table of reach 2), with a LUT the trilinear one -- the same bits as 0, the
+    // default, which marches the trilinear field always.  Changing it drops no temporal history: the next pass is simply another guide.  expected_clear_table
+    // returns the table the current setting marches with.
     void render_features(int spp);
     void render_features_expected(int rays);
+    int expected_field = 0;
     int expected_skip = 1;
     int expected_stats = 0;
     void expected_stats_read(uint64_t out[4]);
@@ -455,7 +460,7 @@ private:
     DenoiseSigma sigma() const { return { denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] }; }      // denoise_sigma as the kernels take it
     DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
     bool expected_stats_valid_ = false;                // ... which that pass filled
-    ClearTable clear_table_of(BrickGridHIP& g, const GridView& view);      // the grid's table, built on `stream` if it has none
+    ClearTable clear_table_of(BrickGridHIP& g, const GridView& view, int reach);      // the grid's table of that reach (1 or 2), built on `stream` if it has none
     void check_moments(const char* who);               // throws unless the moments cover samples 1..sample (of every tile, on a ragged frame)
     void run_denoise(const char* who, bool temporal, bool whole_frame_gathered = false);  // the body of both; whole_frame_gathered: part 0 of a ShardedRenderer,
                                                        // whose moments and features hold every part's tiles (gather_guides) -- the tile subset is no obstacle then

@@ -9,6 +9,9 @@
 //   Clear     cell (cx, cy, cz) is clear when every voxel of [8 cx - 1, 8 cx + 8] x [8 cy - 1, 8 cy + 8] x [8 cz - 1, 8 cz + 8] -- its box grown by one
 //             voxel on each side, 10^3 voxels -- has the bit pattern of +0.0f.  -0 and NaN are not +0.  The eight corners of a trilinear lookup at a
 //             point of the cell, floor(p - 0.5) and one more per axis, lie in that box.
+//   Reach     the table above has reach 1, what a trilinear lookup reads.  The table of reach 2 grows the box by two voxels on each side instead,
+//             [8 c - 2, 8 c + 9] per axis, 12^3 voxels: what the 64 taps of the cubic lookup (vr_cubic.h: floor(p - 0.5) - 1 .. + 2 per axis) read at a
+//             point of the cell.  Everything else is the same text; a grid keeps one table per reach.
 //   Distance  d = min(255, max(|dx|, |dy|, |dz|) to the nearest cell that is not clear): 0 for a cell that is not clear, 255 for a grid without one.
 // Built in two stages: the marking pass writes 0 or 255 per cell (clear_box_bits over the box), then one pass per axis replaces each byte by
 // min over the cells c' of its row along that axis of max(|c - c'|, byte(c')) (clear_axis_pass): max distributes over min, and so does the cap.
@@ -19,7 +22,8 @@
 namespace vr {
 
 constexpr uint32_t kClearMax = 255u;
-constexpr int32_t kClearBoxVoxels = 1000;           // 10^3
+constexpr int32_t kClearBoxVoxels = 1000;           // 10^3: reach 1
+constexpr int32_t kClearReaches = 2;                // reach 1 (trilinear) and 2 (cubic)
 
 // (ClearTable, what the march gets, and clear_cells, the table's extent: vr_scene.h)
 
@@ -30,12 +34,14 @@ VR_HD uint32_t clear_voxel_bits(const GridView& g, int32_t x, int32_t y, int32_t
     if (!g.dense && g.atlas_f32) return f2u(g.atlas_f32[(size_t)a.cell * 512u + a.off]);
     return f2u(tap_value(g, tap_load(g, a), true));
 }
-// the OR of the bits of voxels first, first + stride, ... (< 1000, x fastest) of the grown box of cell (cx, cy, cz): 0 over the whole box = clear
-VR_HD uint32_t clear_box_bits(const GridView& g, int32_t cx, int32_t cy, int32_t cz, int32_t first, int32_t stride) {
+// the OR of the bits of voxels first, first + stride, ... (< (8 + 2 reach)^3, x fastest) of the box of cell (cx, cy, cz) grown by `reach` voxels (1 or 2): 0 over
+// the whole box = clear
+VR_HD uint32_t clear_box_bits(const GridView& g, int32_t cx, int32_t cy, int32_t cz, int32_t first, int32_t stride, int32_t reach = 1) {
+    const int32_t side = 8 + 2 * reach, slab = side * side;
     uint32_t acc = 0u;
-    for (int32_t i = first; i < kClearBoxVoxels; i += stride) {
-        const int32_t k = i / 100, j = (i - 100 * k) / 10;
-        acc |= clear_voxel_bits(g, 8 * cx - 1 + (i - 100 * k - 10 * j), 8 * cy - 1 + j, 8 * cz - 1 + k);
+    for (int32_t i = first; i < slab * side; i += stride) {
+        const int32_t k = i / slab, j = (i - slab * k) / side;
+        acc |= clear_voxel_bits(g, 8 * cx - reach + (i - slab * k - side * j), 8 * cy - reach + j, 8 * cz - reach + k);
     }
     return acc;
 }

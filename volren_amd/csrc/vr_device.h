@@ -60,10 +60,11 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
 // expected_pixel), rays in 1..kExpectedMaxRays.  Bounded by construction: no status word.
 // clear: the clear-distance table of P.density (launch_clear_table), by which the march drops the steps of empty space -- same bits; nullptr, or a table without
 // bytes: every step runs.  stats: 4 device counters that the launch ADDS to, in the instrumented twin of the kernel (sub-rays marched, steps reached, steps
-// that fetched their corners, reads of the table); nullptr: the plain kernel.
+// that fetched their corners, reads of the table); nullptr: the plain kernel.  cubic: march the tracker's field -- without a LUT the cubic B-spline field of
+// vr_cubic.h, and clear must then be the table of reach 2; with a LUT the trilinear field, the same launch as without the flag.
 constexpr int32_t kExpectedMaxRays = 4;
 void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream,
-                              const ClearTable* clear = nullptr, unsigned long long* stats = nullptr);
+                              const ClearTable* clear = nullptr, unsigned long long* stats = nullptr, bool cubic = false);
 // which compiled kernel instance serves a scene, why, and whether it reads a seed table: vr_variant.h pathtrace_kernel_of
 // fast_math: the opt-in tolerance-mode kernels (hardware transcendentals, reciprocal division; vr_math.h VR_FAST_MATH); the default
 // kernels are bit-identical to the CPU oracle
@@ -158,7 +159,8 @@ void launch_pair_atlas(const uint8_t* atlas_density, const uint8_t* atlas_emissi
 // decoded float atlas (one float per atlas byte: rmin + unorm8(b) * rdiff of its brick), used by transfer-function renders
 void launch_decode_atlas(const float* rng, const uint8_t* atlas, float* out, size_t n_records, hipStream_t stream);
 // Clear-distance table of the grid behind view g (vr_clear.h): table and scratch hold one byte per cell of clear_cells(g) each (vr_scene.h); the result is in table.
-void launch_clear_table(const GridView& g, uint8_t* table, uint8_t* scratch, hipStream_t stream);
+// reach: 1 (the trilinear lookup's table) or 2 (the cubic lookup's)
+void launch_clear_table(const GridView& g, uint8_t* table, uint8_t* scratch, hipStream_t stream, int32_t reach = 1);
 // Path-seed table (vr_tiles.h seed_table_index): the entries of the 0-based sample numbers [s_begin, s_end) of every pixel of the W x H frame's tiles, each
 // vr_trace.h path_seed(seed, W, px, py, s + 1) -- what do_new hashes for that sample.  table holds s_end * tile_count(W, H) * 256 entries at least.
 void launch_seed_fill(uint32_t* table, uint32_t seed, int32_t W, int32_t H, int32_t s_begin, int32_t s_end, hipStream_t stream);

@@ -20,7 +20,12 @@
 //             vol_density_scale * raw and a = vol_albedo; with one, tf_lookup(P, (vol_density_scale * raw) * vol_inv_majorant, rgba), sigma = rgba[3] *
 //             vol_majorant, a = vol_albedo * rgba.rgb.  A step with !(sigma > 0) -- NaN included -- contributes nothing and leaves T as it is.
 //             Without a LUT the tracker of feature_sample decides its collisions on the stochastic-tricubic (B-spline) field, about a voxel smoother
-//             than the trilinear one marched here: the two passes agree up to that difference.
+//             than the trilinear one marched here: the two passes agree up to that difference (coverage: 4e-4 on smoke.brick, 6e-3 on a dense 64^3
+//             grid), which CUBIC removes.
+//   CUBIC     (without a LUT; with one the tracker itself looks up the trilinear field, and CUBIC changes nothing.)  The Density line reads raw =
+//             the cubic B-spline field of vr_cubic.h (cubic_lookup: 64 taps, fl - 1 .. fl + 2 per axis, fl = floor(ip - 0.5)) instead, the mean of
+//             the tracker's stochastic tap, and the Normal line takes g from the same lookup -- the same 64 values, no further loads -- through the
+//             same transpose(Minv3), normalise and negate.  Everything else is the text as it stands.
 //   Weights   e = exp_(-(sigma * h)), w = T * (1 - e), then T = T * e.  The sub-ray ends when T <= 2^-10 (kExpectedMinT): what is left of it is
 //             below the precision the filter's edge weights resolve.
 //   Normal    g = trilinear_gradient of the same eight corners (vr_trace.h; no further loads), n^ = -normalize(transpose(Minv3) g) in
@@ -31,7 +36,7 @@
 // The emission grid, the integrator setting and the majorant table play no part.
 //
 // Empty space (SKIP, with the clear-distance table of vr_clear.h; without one the march is the text above, step by step).  A step whose eight corners
-// are all +0 has raw = +0 whatever its weights, so its sigma is the value s0 of the Density line at raw = +0.0f; when !(s0 > 0) -- always without a LUT:
+// are all +0 (CUBIC: whose 64 taps are all +0) has raw = +0 whatever its weights, so its sigma is the value s0 of the Density line at raw = +0.0f; when !(s0 > 0) -- always without a LUT:
 // vol_density_scale * (+0) is +-0 or NaN; with one unless the LUT's alpha at density 0 is positive -- such a step contributes nothing and may be
 // dropped with its loads.  s0 is evaluated once per pixel; when it is > 0 the pixel marches every step.  Otherwise step k, before it loads anything,
 // reads the byte d of the cell that holds its midpoint ip, cell floor(ip / 8) per axis:
@@ -42,11 +47,15 @@
 //           and the table is read again where that lands.  The eighth of a cell per cell is the margin against rounding, which is why a sub-ray
 //           leaps only while max |ipos_i| + tfar max |idir_i| < 2^16 (kExpectedLeapBound): there a midpoint is computed to within 0.02 voxels.
 //           Every other sub-ray -- m capped at kExpectedMaxSteps, or coordinates beyond that bound -- drops one step at a time.
+// CUBIC marches with the table of reach 2 (vr_clear.h): ip in [8 c, 8 c + 8) gives fl in [8 c - 1, 8 c + 7], taps in [8 c - 2, 8 c + 9], the cell's box grown by
+// two voxels.  A clear cell gives 64 taps of +0, a sum of products with +0 -- raw = +0, or NaN under weights that are not finite --, hence !(sigma > 0); the leap
+// argument holds unchanged.
 // The frame is the same bits with and without the table.  ExpectedRayInfo::steps stays the step index the sub-ray reached, dropped steps included
 // (a leap past the last step ends at m).
 #pragma once
 
 #include "vr_clear.h"
+#include "vr_cubic.h"
 #include "vr_trace.h"
 
 namespace vr {
@@ -83,6 +92,12 @@ VR_HD float expected_sigma(const SceneParams& P, v3 ip, v3 alb, TriIO& io, v3& a
     }
     return sigma;
 }
+// CUBIC's Density line (no LUT): sigma of the step at ip, the gradient of the same 64 taps in g
+VR_HD float expected_sigma_cubic(const SceneParams& P, v3 ip, v3& g) {
+    float raw;
+    cubic_lookup(P.density, ip, raw, g);
+    return P.u.vol_density_scale * raw;
+}
 // the same line at raw = +0.0f: the sigma of every step whose eight corners are +0
 template <bool TF>
 VR_HD float expected_sigma_of_zero(const SceneParams& P) {
@@ -97,10 +112,12 @@ VR_HD float expected_sigma_of_zero(const SceneParams& P) {
 }
 
 // SKIP: with clear (its table not null) and skip (the pixel's !(expected_sigma_of_zero > 0)) steps in clear cells are dropped; WORK: work counts;
-// AUDIT (host only, with WORK): every dropped step is evaluated all the same and counted in work->audit when its sigma > 0
-template <bool TF, bool INFO = false, bool SKIP = false, bool WORK = false, bool AUDIT = false>
+// AUDIT (host only, with WORK): every dropped step is evaluated all the same and counted in work->audit when its sigma > 0; CUBIC: the cubic B-spline
+// field (without a LUT; clear must then be the table of reach 2)
+template <bool TF, bool INFO = false, bool SKIP = false, bool WORK = false, bool AUDIT = false, bool CUBIC = false>
 VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t i, int32_t j, int32_t n, ExpectedSums& S, ExpectedRayInfo* info = nullptr,
                            const ClearTable* clear = nullptr, bool skip = false, ExpectedWork* work = nullptr) {
+    constexpr bool CB = CUBIC && !TF;
     const Uniforms& u = P.u;
     const int32_t W = u.resolution[0], H = u.resolution[1];
     if (INFO) { info->m = 0; info->steps = 0; info->T = 1.0f; }
@@ -133,7 +150,7 @@ VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t
         const float t = tnear + ((float)k + 0.5f) * h;
         const v3 ip = axpy(ipos, t, idir);
         TriIO io;
-        v3 a;
+        v3 a = alb, g;
         if (SKIP && skip) {
             // (One loop over fetched and dropped steps alike: neighbouring rays cross the same cells nearly in lockstep, so a wavefront mostly drops or fetches as
             // one.  A loop of its own that runs each lane ahead to its next fetching step measured slower: profiles/r12_expected_skip.txt.)
@@ -146,19 +163,20 @@ VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t
                     const int32_t more = leap ? 7 * ((int32_t)d - 1) : 0;
                     if (AUDIT)
                         for (int32_t kk = k; kk <= k + more && kk < m; ++kk)
-                            if (expected_sigma<TF>(P, axpy(ipos, tnear + ((float)kk + 0.5f) * h, idir), alb, io, a) > 0.0f) ++work->audit;
+                            if ((CB ? expected_sigma_cubic(P, axpy(ipos, tnear + ((float)kk + 0.5f) * h, idir), g)
+                                    : expected_sigma<TF>(P, axpy(ipos, tnear + ((float)kk + 0.5f) * h, idir), alb, io, a)) > 0.0f) ++work->audit;
                     k += more;
                     continue;
                 }
             }
         }
         if (WORK) ++work->fetched;
-        const float sigma = expected_sigma<TF>(P, ip, alb, io, a);
+        const float sigma = CB ? expected_sigma_cubic(P, ip, g) : expected_sigma<TF>(P, ip, alb, io, a);
         if (!(sigma > 0.0f)) continue;
         const float e = exp_(-(sigma * h));
         const float w = T * (1.0f - e);
         T = T * e;
-        const v3 g = trilinear_gradient(P.density, io);
+        if (!CB) g = trilinear_gradient(P.density, io);
         const v3 nn = v3{ (mi[0] * g.x + mi[1] * g.y) + mi[2] * g.z, (mi[4] * g.x + mi[5] * g.y) + mi[6] * g.z, (mi[8] * g.x + mi[9] * g.y) + mi[10] * g.z };
         const v3 nh = (nn.x == 0.0f && nn.y == 0.0f && nn.z == 0.0f) ? v3{ 0, 0, 0 } : -normalize(nn);
         S.K += w;
@@ -173,14 +191,14 @@ VR_HD void expected_subray(const SceneParams& P, int32_t px, int32_t py, int32_t
 }
 
 // info (INFO only): n * n entries, sub-ray j * n + i
-template <bool TF, bool INFO = false, bool SKIP = false, bool WORK = false, bool AUDIT = false>
+template <bool TF, bool INFO = false, bool SKIP = false, bool WORK = false, bool AUDIT = false, bool CUBIC = false>
 VR_HD void expected_pixel(const SceneParams& P, int32_t px, int32_t py, int32_t n, float out[8], ExpectedRayInfo* info = nullptr,
                           const ClearTable* clear = nullptr, ExpectedWork* work = nullptr) {
     ExpectedSums S;
     S.K = 0.0f; S.D = 0.0f; S.A = v3{ 0, 0, 0 }; S.N = v3{ 0, 0, 0 };
     const bool skip = SKIP && clear && clear->d && !(expected_sigma_of_zero<TF>(P) > 0.0f);
     for (int32_t j = 0; j < n; ++j)
-        for (int32_t i = 0; i < n; ++i) expected_subray<TF, INFO, SKIP, WORK, AUDIT>(P, px, py, i, j, n, S, INFO ? info + (j * n + i) : nullptr, clear, skip, work);
+        for (int32_t i = 0; i < n; ++i) expected_subray<TF, INFO, SKIP, WORK, AUDIT, CUBIC>(P, px, py, i, j, n, S, INFO ? info + (j * n + i) : nullptr, clear, skip, work);
     for (int32_t c = 0; c < 8; ++c) out[c] = 0.0f;
     if (!(S.K > 0.0f)) return;
     out[0] = S.A.x / S.K; out[1] = S.A.y / S.K; out[2] = S.A.z / S.K; out[3] = S.K / (float)(n * n);

@@ -151,7 +151,9 @@ void launch_features(const SceneParams& P, const int32_t* tiles, int32_t n_tiles
 // SKIP: the instance that reads the clear-distance table `clear` (vr_expected.h: steps in clear cells are dropped with their loads, same bits); the table is an
 // argument of this kernel alone.  STATS: the instrumented twin: every lane counts (ExpectedWork), the wavefront sums, and its lanes 0..3 add one total each to
 // stats[0..3] in one atomic instruction.  No lane leaves before that sum.
-template <bool TF, bool SKIP, bool STATS>
+// CUBIC (without a LUT only): the instances that march the tracker's cubic B-spline field (vr_cubic.h: 64 taps a step in at most 2 x 2 x 2 cells, whose indices and
+// decode ranges are formed once per step); `clear` is then the table of reach 2.
+template <bool TF, bool SKIP, bool STATS, bool CUBIC = false>
 __global__ void __launch_bounds__(256)
 features_expected_kernel(const SceneParams P, const int32_t* __restrict__ tiles, int32_t rays, float* __restrict__ out, const ClearTable clear,
                          unsigned long long* __restrict__ stats) {
@@ -162,7 +164,7 @@ features_expected_kernel(const SceneParams P, const int32_t* __restrict__ tiles,
     ExpectedWork work = { 0u, 0u, 0u, 0u, 0u };
     if (live) {
         float f[8];
-        expected_pixel<TF, false, SKIP, STATS>(P, q.px, q.py, rays, f, nullptr, SKIP ? &clear : nullptr, STATS ? &work : nullptr);
+        expected_pixel<TF, false, SKIP, STATS, false, CUBIC>(P, q.px, q.py, rays, f, nullptr, SKIP ? &clear : nullptr, STATS ? &work : nullptr);
         float4* o = reinterpret_cast<float4*>(out) + 2u * ((size_t)q.py * W + q.px);
         o[0] = pack4(f);
         o[1] = pack4(f + 4);
@@ -177,14 +179,19 @@ features_expected_kernel(const SceneParams P, const int32_t* __restrict__ tiles,
     }
 }
 void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_t n_tiles, int32_t rays, float* out, hipStream_t stream,
-                              const ClearTable* clear, unsigned long long* stats) {
+                              const ClearTable* clear, unsigned long long* stats, bool cubic) {
     if (n_tiles <= 0 || rays < 1 || rays > kExpectedMaxRays) return;
     const bool skip = clear && clear->d;
     const ClearTable C = skip ? *clear : ClearTable{ nullptr, { 0, 0, 0 } };
     const bool tf = P.u.use_tf != 0;
     const dim3 grid((unsigned)n_tiles), block(256);
 #define VR_EXPECTED_LAUNCH(TF, SKIP, STATS) hipLaunchKernelGGL((features_expected_kernel<TF, SKIP, STATS>), grid, block, 0, stream, P, tiles, rays, out, C, stats)
-    if (stats) {
+    if (cubic && !tf) {                             // under a LUT the tracker's field is the trilinear one: the instances below
+#define VR_EXPECTED_CUBIC(SKIP, STATS) hipLaunchKernelGGL((features_expected_kernel<false, SKIP, STATS, true>), grid, block, 0, stream, P, tiles, rays, out, C, stats)
+        if (stats) { if (skip) VR_EXPECTED_CUBIC(true, true); else VR_EXPECTED_CUBIC(false, true); }
+        else { if (skip) VR_EXPECTED_CUBIC(true, false); else VR_EXPECTED_CUBIC(false, false); }
+#undef VR_EXPECTED_CUBIC
+    } else if (stats) {
         if (skip) { if (tf) VR_EXPECTED_LAUNCH(true, true, true); else VR_EXPECTED_LAUNCH(false, true, true); }
         else { if (tf) VR_EXPECTED_LAUNCH(true, false, true); else VR_EXPECTED_LAUNCH(false, false, true); }
     } else {

@@ -25,7 +25,7 @@
 // and the pixel is B + the filtered (y - B): the filtered frame, as without the setting.  A caller composites L over any background B' as (1 - L.a) B' + L.rgb.
 // Nothing is sanitised: a NaN in F makes the pixel NaN (max_(NaN, 0) is NaN).
 //
-// What it inherits.  kappa is the march's coverage: without a transfer function the tracker's lies about 0.0004 above it (vr_resolve.h), and that bias stays.
+// What it inherits.  kappa is the march's coverage: without a transfer function the tracker's lies about 0.0004 above it (vr_resolve.h), and that bias stays unless the pass marched the tracker's own field ("expected_field" 1).
 // It needs what resolve() needs: an expected-value pass of rays >= 2, the whole frame, integrator != 2.
 #pragma once
 

@@ -19,24 +19,28 @@
 //   PROBE_SKY       direction x, y, z (float), -      r, g, b                    0
 //   PROBE_LIGHT     r0, r1 (float), -, -              w_i, Le, pdf (7)           0 sample_environment<true, true> (needs env_div_safe), 1 <false, false>
 //   PROBE_TF        density (float), -, -, -          r, g, b, a                 0 (needs a LUT)
+//   PROBE_CUBIC     grid, x, y, z (float, index       value, gx, gy, gz          DENSE: 0 | 1 | 2.  vr_cubic.h cubic_lookup: the raw cubic B-spline value (no
+//                   space)                            (voxel units)              density scale) and its gradient, from the byte atlas or the fp16 voxels
 //
 // probe_form_error says why a scene cannot serve a form (nullptr: it can); probe_items_error checks what would index outside a table.
 #pragma once
 
+#include "vr_cubic.h"
 #include "vr_trace.h"
 
 namespace vr {
 
-enum ProbeWhat { PROBE_VOXEL = 0, PROBE_TRILINEAR, PROBE_MAJORANT, PROBE_IMPORTANCE, PROBE_TEXEL, PROBE_SKY, PROBE_LIGHT, PROBE_TF, PROBE_COUNT };
+enum ProbeWhat { PROBE_VOXEL = 0, PROBE_TRILINEAR, PROBE_MAJORANT, PROBE_IMPORTANCE, PROBE_TEXEL, PROBE_SKY, PROBE_LIGHT, PROBE_TF, PROBE_CUBIC, PROBE_COUNT };
 constexpr int32_t kProbeInWords = 4;
 VR_HD int32_t probe_out_words(int32_t what) {
-    return what == PROBE_LIGHT ? 7 : (what == PROBE_TF ? 4 : ((what == PROBE_TEXEL || what == PROBE_SKY) ? 3 : 1));
+    return what == PROBE_LIGHT ? 7 : ((what == PROBE_TF || what == PROBE_CUBIC) ? 4 : ((what == PROBE_TEXEL || what == PROBE_SKY) ? 3 : 1));
 }
 
 struct ProbeForm { int32_t dense, pair, majb, f32; bool tf, clean; };
 inline ProbeForm probe_decode_form(int32_t what, int32_t form) {
     ProbeForm f{ 0, 0, 0, 0, false, false };
     if (what == PROBE_VOXEL) { f.dense = form % 3; f.pair = form / 3; }
+    else if (what == PROBE_CUBIC) f.dense = form % 3;
     else if (what == PROBE_TRILINEAR) { f.dense = form % 3; f.pair = (form / 3) % 2; f.f32 = form / 6; }
     else if (what == PROBE_MAJORANT) { f.tf = (form & 1) != 0; f.dense = (form >> 1) % 3; f.majb = (form / 6) % 3; f.clean = form / 18 != 0; }
     return f;
@@ -79,6 +83,11 @@ inline const char* probe_form_error(const SceneParams& P, int32_t what, int32_t 
     case PROBE_TF:
         if (form != 0) return "form out of range";
         return P.u.use_tf ? nullptr : "no transfer function bound";
+    case PROBE_CUBIC:
+        if (form >= 3) return "form out of range";
+        if (f.dense == 0 && dense_grid) return "DENSE = 0 form on a dense density grid";
+        if (f.dense == 1 && !dense_grid) return "DENSE = 1 form on a brick density grid";
+        return nullptr;
     }
     return "unknown probe";
 }
@@ -88,7 +97,12 @@ inline const char* probe_items_error(const SceneParams& P, int32_t what, int32_t
     const ProbeForm f = probe_decode_form(what, form);
     for (size_t i = 0; i < n; ++i) {
         const uint32_t* w = in + kProbeInWords * i;
-        if (what == PROBE_VOXEL || what == PROBE_TRILINEAR) {
+        if (what == PROBE_CUBIC) {
+            if (w[0] > 1u) return "grid must be 0 (density) or 1 (emission)";
+            if (w[0] == 1u && !P.u.has_emission) return "no emission grid";
+            if (w[0] == 1u && f.dense == 1) return "only the density grid has a compiled-in dense form";
+            if (w[0] == 1u && f.dense == 0 && P.emission.dense) return "DENSE = 0 form on a dense emission grid";
+        } else if (what == PROBE_VOXEL || what == PROBE_TRILINEAR) {
             if (w[0] > 1u) return "grid must be 0 (density) or 1 (emission)";
             if (w[0] == 1u && !P.u.has_emission) return "no emission grid";
             if (f.pair != 0 && w[0] != (what == PROBE_VOXEL ? (uint32_t)f.pair - 1u : 0u)) return "PAIR 1 reads the density grid, PAIR 2 the emission grid";
@@ -193,6 +207,20 @@ VR_HD void probe_item(const SceneParams& P, int32_t what, int32_t form, const ui
         break;
     }
     case PROBE_TF: tf_lookup(P, fx, out); break;
+    case PROBE_CUBIC: {
+        const GridView& g = w[0] ? P.emission : P.density;
+        const v3 p{ u2f(w[1]), u2f(w[2]), u2f(w[3]) };
+        v3 gr{ 0.0f, 0.0f, 0.0f };
+        out[0] = nan_();
+        switch (form) {
+        case 0: cubic_lookup<0>(g, p, out[0], gr); break;
+        case 1: cubic_lookup<1>(g, p, out[0], gr); break;
+        case 2: cubic_lookup<2>(g, p, out[0], gr); break;
+        default: break;
+        }
+        out[1] = gr.x; out[2] = gr.y; out[3] = gr.z;
+        break;
+    }
     default: break;
     }
 }

@@ -29,7 +29,8 @@
 // What the estimator assumes.  E[y] = E[x] + beta (E[kappa^] - kappa) for a fixed beta: y is unbiased wherever the path tracer's tracker collides with
 // the probability the march integrates.  Under a transfer function it does: the tracker decides its collisions on the very field -- trilinear density
 // through the LUT -- that expected_pixel marches.  Without one the tracker uses the stochastic-tricubic (B-spline) field, about a voxel smoother; the two
-// coverages differ by about 0.002 on average, and y carries beta times that difference as bias.  beta itself is estimated from the frame (C~), which
+// coverages differ by about 0.002 on average, and y carries beta times that difference as bias -- unless the pass marched that field itself
+// ("expected_field" 1: vr_expected.h CUBIC), where the coverages agree to within sampling noise.  beta itself is estimated from the frame (C~), which
 // couples it to kappa^: a second-order bias that shrinks with the 49 pixels pooled and with the sample count.  With an emission grid the estimator stays
 // valid -- emission before the first collision is part of x and of B's complement alike -- but beta is no longer the optimal coefficient.  The direct
 // volume rendering integrator (2) writes an opacity into alpha, not a hit indicator: the renderer refuses it.  kappa from one ray per pixel is the

@@ -262,14 +262,14 @@ void launch_majorants(const SceneParams& P, const uint32_t* range_words_all_mips
 
 // ---------------------------------------------------------------------------------------------------
 // Clear-distance table of a density grid (vr_clear.h), built at the first expected-value pass that reads the grid.
-//   1. clear_mark_kernel : one wavefront per cell, the 1000 voxels of its grown box spread over the lanes; 255 when all of them are +0, else 0
+//   1. clear_mark_kernel : one wavefront per cell, the 10^3 (reach 1) or 12^3 (reach 2) voxels of its grown box spread over the lanes; 255 when all of them are +0, else 0
 //   2. clear_axis_kernel : one thread per cell, once per axis (x, y, z), each from one buffer into the other
 __global__ void __launch_bounds__(256)
-clear_mark_kernel(const GridView g, int32_t n0, int32_t n1, int32_t n2, uint8_t* __restrict__ out) {
+clear_mark_kernel(const GridView g, int32_t n0, int32_t n1, int32_t n2, int32_t reach, uint8_t* __restrict__ out) {
     const uint32_t cell = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (cell >= (uint32_t)n0 * (uint32_t)n1 * (uint32_t)n2) return;                    // the whole wavefront
     const int32_t cx = (int32_t)(cell % (uint32_t)n0), cy = (int32_t)((cell / (uint32_t)n0) % (uint32_t)n1), cz = (int32_t)(cell / ((uint32_t)n0 * (uint32_t)n1));
-    const uint32_t bits = clear_box_bits(g, cx, cy, cz, (int32_t)lane, 64);
+    const uint32_t bits = clear_box_bits(g, cx, cy, cz, (int32_t)lane, 64, reach);
     const bool any = __ballot(bits != 0u) != 0ull;
     if (lane == 0u) out[cell] = any ? (uint8_t)0 : (uint8_t)kClearMax;
 }
@@ -281,12 +281,12 @@ clear_axis_kernel(const uint8_t* __restrict__ in, int32_t n0, int32_t n1, int32_
     const int32_t cx = (int32_t)(cell % (uint32_t)n0), cy = (int32_t)((cell / (uint32_t)n0) % (uint32_t)n1), cz = (int32_t)(cell / ((uint32_t)n0 * (uint32_t)n1));
     out[cell] = (uint8_t)clear_axis_pass(in, n, axis, cx, cy, cz);
 }
-void launch_clear_table(const GridView& g, uint8_t* table, uint8_t* scratch, hipStream_t stream) {
+void launch_clear_table(const GridView& g, uint8_t* table, uint8_t* scratch, hipStream_t stream, int32_t reach) {
     int32_t n[3];
     clear_cells(g, n);
     const uint32_t cells = (uint32_t)n[0] * (uint32_t)n[1] * (uint32_t)n[2];
     if (cells == 0u) return;
-    hipLaunchKernelGGL(clear_mark_kernel, dim3((cells + 3u) / 4u), dim3(256), 0, stream, g, n[0], n[1], n[2], scratch);
+    hipLaunchKernelGGL(clear_mark_kernel, dim3((cells + 3u) / 4u), dim3(256), 0, stream, g, n[0], n[1], n[2], reach == 2 ? 2 : 1, scratch);
     const dim3 grid((cells + 255u) / 256u);
     hipLaunchKernelGGL(clear_axis_kernel, grid, dim3(256), 0, stream, scratch, n[0], n[1], n[2], 0, table);
     hipLaunchKernelGGL(clear_axis_kernel, grid, dim3(256), 0, stream, table, n[0], n[1], n[2], 1, scratch);

@@ -9,7 +9,7 @@ from . import _lib
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
                "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
-               "expected_skip", "expected_stats", "sky_tiles", "see_through_tiles")
+               "expected_skip", "expected_field", "expected_stats", "sky_tiles", "see_through_tiles")
 _READ_ONLY_INT_FIELDS = ("n_grid_frames", "last_launches", "last_sky_tiles", "last_see_through_tiles", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
                          "kernel_wide", "adaptive_rounds", "seed_table_samples", "seed_table_fills")
 _FLOAT_FIELDS = {"tonemap_exposure": 1, "tonemap_gamma": 1, "albedo": 3, "phase": 1, "density_scale": 1,
@@ -235,7 +235,7 @@ class Renderer:
         return self.framebuffer()[..., :3].copy()
 
     # ---- test hook ----
-    PROBE_OUT_WORDS = (1, 1, 1, 1, 3, 3, 7, 4)      # voxel, trilinear, majorant, importance, texel, sky, light sample, transfer function
+    PROBE_OUT_WORDS = (1, 1, 1, 1, 3, 3, 7, 4, 4)   # voxel, trilinear, majorant, importance, texel, sky, light sample, transfer function, cubic (value, gradient)
 
     def probe(self, what, form, items):
         """Test hook (include/volren_amd.h vr_probe, volren_amd/csrc/vr_probe.h): `items` is [n][4] 32-bit words (int32, uint32 or float32 -- the bits are passed
@@ -302,7 +302,8 @@ class Renderer:
 
     def render_features_expected(self, rays=2, sync=True):
         """The expected values of the same features from rays x rays deterministic ray marches per pixel, rays in 1..4 (include/volren_amd.h
-        vr_render_features_expected): no noise, no dependence on spp or seed; fills the buffer features() and the denoiser read."""
+        vr_render_features_expected): no noise, no dependence on spp or seed; fills the buffer features() and the denoiser read.
+        `expected_field = 1` marches the field the tracker decides its collisions on (without a LUT the cubic B-spline field) instead of the trilinear one."""
         _lib.check(self._L.vr_render_features_expected(self._h, int(rays)))
         if sync:
             self.synchronize()
@@ -320,7 +321,8 @@ class Renderer:
         return dict(zip(("rays", "steps", "fetched", "reads"), (int(v) for v in out)))
 
     def expected_clear_table(self):
-        """Test hook (vr_expected_clear_table): the clear-distance table of the current density grid, uint8 [cz][cy][cx], built if need be."""
+        """Test hook (vr_expected_clear_table): the clear-distance table of the current density grid that the current `expected_field` marches with,
+        uint8 [cz][cy][cx], built if need be."""
         n = (C.c_int * 3)()
         _lib.check(self._L.vr_expected_clear_table(self._h, None, n))
         out = np.empty((n[2], n[1], n[0]), np.uint8)
@@ -621,6 +623,8 @@ class ShardedRenderer:
     expected_skip = _part0("expected_skip", True,
         """Whether the parts' expected-value passes drop the steps of empty space (Renderer.expected_skip): part 0's field; setting it sets every part's.
         Every part builds the clear-distance table of its own copy of the grid.""")
+    expected_field = _part0("expected_field", True,
+        """The field the parts' expected-value passes march (Renderer.expected_field: 0 trilinear, 1 the tracker's): part 0's field; setting it sets every part's.""")
 
     def gather_guides(self):
         """Every part's moments and features of its tiles into `parts[0]` (vr_sharded_gather_guides): one exchange, asynchronous."""

@@ -403,7 +403,7 @@ def set_context(width=None, height=None, device=None):
 _SCALARS = ("sample", "sppx", "bounces", "seed", "tonemap_exposure", "tonemap_gamma", "tonemapping", "show_environment",
             "phase", "density_scale", "emission_scale", "cam_fov")
 _VEC3S = ("albedo", "vol_clip_min", "vol_clip_max", "cam_pos", "cam_dir", "cam_up")
-_PASS_THROUGH = ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "denoise_ridge", "expected_skip")      # this build's own fields: the inner renderer's, as they are
+_PASS_THROUGH = ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "denoise_ridge", "expected_skip", "expected_field")      # this build's own fields: the inner renderer's, as they are
 
 
 class Renderer:
@@ -539,7 +539,8 @@ class Renderer:
 
     def render_features_expected(self, rays=2):
         """The same features as expected values: rays x rays deterministic ray marches per pixel (1..4), noise-free and independent of `seed`.
-        `expected_skip` (default 1) lets the march drop the steps of empty space; 0 runs every step, to the same bits."""
+        `expected_skip` (default 1) lets the march drop the steps of empty space; 0 runs every step, to the same bits.  `expected_field` = 1 marches the
+        field the path tracer decides its collisions on (without a transfer function the cubic B-spline field) instead of the trilinear one (0, the default)."""
         self._r.render_features_expected(int(rays))
 
     def feature_data(self):
