@@ -356,7 +356,22 @@ int vr_resolve_background(vr_renderer* r, float* rgba_out);
  *         F.rgb = kappa_p beta_0, F.a = kappa_p; lambda = 0 is zero order, beta_0 = sum(w c) / sum(w), and the default (README.md has the sweep that chose it)
  *     and F = 0 where kappa_p = 0 or sum(w) <= 2^-20, so every pixel without coverage comes out as B bit for bit.  The arithmetic is specified operation
  *     by operation in volren_amd/csrc/vr_regress.h and reproducible bit for bit; vr_upsample, the history and vr_sharded_denoise (part 0's settings) take
- *     it as they take the a-trous's result. */
+ *     it as they take the a-trous's result.
+ *     Albedo demodulation: vr_set_int / vr_get_int "denoise_demodulate" (0 or 1; default 0, and then every launch, allocation and result is what it is
+ *     without this paragraph; anything else is VR_ERR, the old value kept; a call that changes the value drops the history).  Every scattered sample is
+ *     a_1 R, the first collision's albedo times everything after it; under a transfer function a_1 holds the colour texture and R is smooth, and the
+ *     expected-value pass gives the pixel's mean a_1 without noise (words 0..2 of the feature buffer).  With 1 -- and "denoise_layers" = 1: without it
+ *     vr_denoise and vr_denoise_temporal are VR_ERR before anything is launched -- per pixel and channel
+ *         d = kappa > 0 ? max(albedo, 2^-6) : 1
+ *         S.rgb = (y.rgb - G) / d, and the variance the filter reads is that of the divided layer: (sum_c w_c sqrt(var_c) / d_c)^2 / n
+ *         the filter ("denoise_filter" 0 or 1), the temporal blend with rejection or moments and the history: unchanged, on the divided layer
+ *         L.rgb = (the merge's L.rgb) d;  out.rgb = max(G + L.rgb, 0)
+ *     so vr_denoised_layer keeps its meaning, and a pixel with kappa = 0 comes out as it does without the setting, bit for bit.  vr_upsample with the setting
+ *     1 at its call divides every lo texel by the d of the lo guide before its taps and multiplies the hi layer by the d of the hi guide, whatever produced
+ *     the lo layer.  A channel whose albedo lies below the floor keeps at most 2^-6 of its neighbours' irradiance as bias; light that carries no a_1 (an
+ *     emission grid's) is divided all the same, amplified by at most 64 before the filter.  With the setting on, a wide "denoise_sigma" albedo value (README.md
+ *     has the tables) lets the filter cross the colour edges that d has taken out: a gain for frames of a few spp, a loss at 64.  The arithmetic is specified operation by operation in
+ *     volren_amd/csrc/vr_demod.h and reproducible bit for bit; vr_sharded_denoise takes part 0's setting. */
 int vr_denoised_layer(vr_renderer* r, float* rgba_out);
 /* --- the denoised scattered layer upsampled under a full-resolution guide (no reference counterpart).
  *     kappa and B of (1 - kappa) B + kappa C are functions of the camera ray alone and cost no path-tracing sample at any resolution; C is smooth after the

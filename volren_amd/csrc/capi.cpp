@@ -100,6 +100,7 @@ const IntParam kIntParams[] = {
     { "denoise_resolve", VR_GET(R.denoise_resolve), VR_SET(R.set_denoise_resolve(v)), VR_ANY },
     { "denoise_layers", VR_GET(R.denoise_layers), VR_SET(R.set_denoise_layers(v)), VR_ANY },
     { "denoise_filter", VR_GET(R.denoise_filter), VR_SET(R.set_denoise_filter(v)), VR_ANY },
+    { "denoise_demodulate", VR_GET(R.denoise_demodulate), VR_SET(R.set_denoise_demodulate(v)), VR_ANY },
     { "coalesce_trace", VR_GET(R.coalesce_trace ? 1 : 0), VR_SET(R.flush_pending(); R.coalesce_trace = v != 0), VR_ANY },
     { "majorant_layout", VR_INT(majorant_layout), -1, 1, "majorant_layout: -1 (per grid, chosen at commit), 0 (linear), 1 (4x4x4-cell blocks)" },
     { "majorant_blocked", VR_READ_ONLY(next_launch(R).density.maj_blocked) },

@@ -20,6 +20,8 @@
 // background is put back afterwards ("denoise_layers" = 1, vr_layers.h); refused without them.
 // --denoise-filter 0|1 and --denoise-ridge X with --denoise-layers: 1 runs one pass of local regression on the scattered layer in the place of the a-trous
 // iterations ("denoise_filter" = 1, vr_regress.h), X is the ridge on its slopes ("denoise_ridge": 0 = zero order, or in [2^-20, 2^20]); refused without it.
+// --denoise-demodulate with --denoise-layers: the scattered layer is divided by the guide's albedo in front of the filter and multiplied back behind it
+// ("denoise_demodulate" = 1, vr_demod.h), and so is the layer --upsample rebuilds; refused without it.
 // --upsample F (2..4) with --denoise-layers (and so with a denoise flag and --expected-features N): the frame is rendered and filtered at -w x -h, its layer is
 // rebuilt at F times that size per axis under an expected-value guide of N rays at the large size (vr_upsample.h), and the tonemapped F w x F h frame is
 // written; refused alone.
@@ -105,7 +107,7 @@ static void parse_cmd(int argc, char** argv) {
     Args a{ argc, argv, 0 };
     for (a.i = 1; a.i < argc; ++a.i) {
         const std::string arg = argv[a.i];
-        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments" || arg == "--denoise-layers" || arg == "--resolve") {      // --denoise*, --adaptive: main()
+        if (arg == "--render" || arg == "--denoise" || arg == "--denoise-temporal" || arg == "--denoise-moments" || arg == "--denoise-layers" || arg == "--denoise-demodulate" || arg == "--resolve") {      // --denoise*, --adaptive: main()
         } else if (arg == "-w" || arg == "-h" || arg == "--title" || arg == "--major" || arg == "--minor" || arg == "--swap" || arg == "--font" || arg == "--fontsize") {
             a.next();                                           // consumed by the context set-up pass
         } else if (arg == "--upsample" || arg == "--denoise-filter" || arg == "--denoise-ridge") {
@@ -191,6 +193,7 @@ int main(int argc, char** argv) {
     int expected_field = -1;    // --expected-field 0|1 (with --expected-features): the field that pass marches, 1 = the tracker's; -1: the renderer's default
     bool resolve = false;       // --resolve (with --expected-features N >= 2): the control variate on the expected coverage, alone or in front of the filter
     bool layers = false;        // --denoise-layers (with a denoise flag and --expected-features N >= 2): the filter runs on the scattered layer alone ("denoise_layers" = 1, vr_layers.h)
+    bool demodulate = false;    // --denoise-demodulate (with --denoise-layers): the layer is filtered divided by the guide's albedo ("denoise_demodulate" = 1, vr_demod.h)
     int filter = -1;            // --denoise-filter 0|1 (with --denoise-layers): one pass of local regression in the iterations' place (vr_regress.h); -1: not given
     float ridge = -1.f;         // --denoise-ridge X (with --denoise-layers): the ridge of that regression; -1: not given, the renderer's default
     int upsample = 0;           // --upsample F (with --denoise-layers): the frame written is F times -w x -h, rebuilt from the filtered layer (vr_upsample.h); 0: off
@@ -208,6 +211,7 @@ int main(int argc, char** argv) {
             else if (arg == "--denoise-temporal") denoise = temporal = true;
             else if (arg == "--denoise-moments") moments = true;
             else if (arg == "--denoise-layers") layers = true;
+            else if (arg == "--denoise-demodulate") demodulate = true;
             else if (arg == "--resolve") resolve = true;
             else if (arg == "--denoise-reject") {
                 if (i + 1 >= argc) throw std::runtime_error("missing value after --denoise-reject");
@@ -254,6 +258,7 @@ int main(int argc, char** argv) {
         if (resolve && expected_rays < 2) throw std::runtime_error("--resolve needs --expected-features N with N >= 2: one ray gives the coverage of the pixel's centre, not of its area");
         if (layers && !denoise) throw std::runtime_error("--denoise-layers needs --denoise or --denoise-temporal: it is a setting of their filter");
         if (layers && expected_rays < 2) throw std::runtime_error("--denoise-layers needs --expected-features N with N >= 2: the expected coverage of that pass splits the frame into background and scattered layer");
+        if (demodulate && !layers) throw std::runtime_error("--denoise-demodulate needs --denoise-layers: the albedo divides the scattered layer");
         if (filter >= 0 && !layers) throw std::runtime_error("--denoise-filter needs --denoise-layers: the regression is defined on the scattered layer");
         if (ridge >= 0.f && !layers) throw std::runtime_error("--denoise-ridge needs --denoise-layers: it is a setting of the regression on the scattered layer");
         if (upsample > 0 && !layers) throw std::runtime_error("--upsample needs --denoise-layers: the filtered scattered layer is what it upsamples");
@@ -296,6 +301,7 @@ int main(int argc, char** argv) {
             renderer->denoise_moments = moments ? 1 : 0;
             renderer->denoise_resolve = resolve && denoise ? 1 : 0;
             renderer->denoise_layers = layers ? 1 : 0;
+            renderer->denoise_demodulate = demodulate ? 1 : 0;
             if (filter >= 0) renderer->set_denoise_filter(filter);
             if (ridge >= 0.f) renderer->set_denoise_ridge(ridge);
             if (expected_skip >= 0) renderer->expected_skip = expected_skip;

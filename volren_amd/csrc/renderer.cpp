@@ -1268,8 +1268,10 @@ void RendererHIP::download_variance(float* rgba) {
 // from the new history's colour and variance instead.  layers (denoise_layers, vr_layers.h): the frame all of this reads is the resolved frame's
 // scattered layer S (resolve, then a split), the last iteration writes a buffer F of its own, and a merge writes `denoised` and the layer from F.
 // regress (denoise_filter, vr_regress.h; with layers only): one kernel from what iteration 0 would read to F takes the iterations' place.
+// demod (denoise_demodulate, vr_demod.h; with layers only): split, prepare and merge run their DEMOD instances; the launches and buffers are the same.
 // Every buffer the call needs is allocated before its first launch, so a failed allocation
 // leaves the last result and the history as they were.
+static const char* const kDemodulateRange = "denoise_demodulate: 0 (the filter reads the scattered layer as it is) or 1 (divided by the guide's albedo, multiplied back afterwards; needs denoise_layers = 1)";
 void RendererHIP::denoise() { run_denoise("denoise", false); }
 void RendererHIP::denoise_temporal() { run_denoise("denoise_temporal", true); }
 
@@ -1288,6 +1290,9 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     const bool regress = denoise_filter != 0;         // vr_regress.h: one pass of local regression in the place of the iterations
     if (regress && !layers) throw std::runtime_error(me + "denoise_filter = 1 needs denoise_layers = 1: the regression is defined on the scattered layer S with S.a = the expected coverage");
     if (regress && !regress_ridge_ok(denoise_ridge)) throw std::runtime_error(me + "denoise_ridge must be 0 (zero order) or in [2^-20, 2^20]");
+    if (denoise_demodulate != 0 && denoise_demodulate != 1) throw std::runtime_error(me + kDemodulateRange);
+    const bool demod = denoise_demodulate != 0;       // vr_demod.h: the DEMOD instances of split, prepare and merge
+    if (demod && !layers) throw std::runtime_error(me + "denoise_demodulate = 1 needs denoise_layers = 1: the albedo divides the scattered layer S, not a frame with the background in it");
     const int32_t* counts = nullptr;                  // a ragged frame: every tile's own count (uploaded here: waits for the frame)
     if (ragged()) {
         for (int32_t c : tile_n_)
@@ -1303,8 +1308,8 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     const size_t px = (size_t)W * H;
     Sized::History& hist = sized_.hist;
     // a history without moment records cannot continue one with them, nor the other way round (denoise_moments set as a field, past set_denoise_moments);
-    // nor one of composites one of layers (denoise_layers set as a field, past set_denoise_layers)
-    if (temporal && hist.cur >= 0 && ((hist.moments[hist.cur] != nullptr) != (denoise_moments != 0) || hist.layers != layers)) drop_history();
+    // nor one of composites one of layers, nor a demodulated layer a plain one (denoise_layers, denoise_demodulate set as fields, past their setters)
+    if (temporal && hist.cur >= 0 && ((hist.moments[hist.cur] != nullptr) != (denoise_moments != 0) || hist.layers != layers || hist.demod != demod)) drop_history();
     const int to = hist.cur < 0 ? 0 : 1 - hist.cur;      // the half of the history pair this call writes
     const bool reject = temporal && denoise_reject > 0.0f;      // vr_temporal.h steps 2a, 3a: the fetch / resolve pair instead of the one kernel
     const bool moments = temporal && denoise_moments != 0;      // vr_moments.h: the temporal kernel with the moment records, then the variance kernel
@@ -1322,13 +1327,13 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
     if (denoise_resolve != 0 || layers) run_resolve();      // vr_resolve.h: the filter starts from y, with the frame's own variance
     const DeviceBuffer* frame = denoise_resolve != 0 ? sized_.resolved.get() : color.get();
     if (layers) {                                     // ... or from y's scattered layer S; the last iteration then writes F, and the merge writes `denoised` and the layer
-        launch_layers_split(sized_.resolved->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.ly_split->as<float>(), stream);
+        launch_layers_split(sized_.resolved->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.ly_split->as<float>(), stream, demod);
         VR_HIP(hipGetLastError());
         frame = sized_.ly_split.get();
     }
     DeviceBuffer* const result = layers ? sized_.ly_filtered.get() : sized_.denoised.get();
     sized_.layer_guided = false;                      // the guide is this call's from here on; a call with layers pairs it with its layer below
-    launch_denoise_prepare(sized_.moments->as<float>(), sized_.features->as<float>(), W, H, sample, vscale, counts, sized_.dn_var[0]->as<float>(), sized_.dn_guide->as<float>(), stream);
+    launch_denoise_prepare(sized_.moments->as<float>(), sized_.features->as<float>(), W, H, sample, vscale, counts, sized_.dn_var[0]->as<float>(), sized_.dn_guide->as<float>(), stream, demod);
     VR_HIP(hipGetLastError());
     const DenoiseSigma sg = sigma();
     const DeviceBuffer* first = frame;                // what iteration 0 reads
@@ -1354,7 +1359,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         launch_denoise_temporal(t, stream);
         VR_HIP(hipGetLastError());
         sized_.reject_stat = reject;
-        hist.cur = to; hist.cam = cur; hist.layers = layers;
+        hist.cur = to; hist.cam = cur; hist.layers = layers; hist.demod = demod;
         first = hist.color[to].get();
     }
     if (N == 0) VR_HIP(hipMemcpyAsync(result->get(), first->get(), first->size_bytes(), hipMemcpyDeviceToDevice, stream));
@@ -1370,7 +1375,7 @@ void RendererHIP::run_denoise(const char* who, bool temporal, bool whole_frame_g
         VR_HIP(hipGetLastError());
     }
     if (layers) {
-        launch_layers_merge(result->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.denoised->as<float>(), sized_.layer->as<float>(), stream);
+        launch_layers_merge(result->as<float>(), sized_.rs_bg->as<float>(), sized_.features->as<float>(), W, H, sized_.denoised->as<float>(), sized_.layer->as<float>(), stream, demod);
         VR_HIP(hipGetLastError());
         sized_.layer_valid = true;
         sized_.layer_guided = true;
@@ -1401,6 +1406,7 @@ void RendererHIP::set_denoise_ridge(float v) {
     if (!regress_ridge_ok(v)) throw std::runtime_error("denoise_ridge must be 0 (zero order) or in [2^-20, 2^20]");
     denoise_ridge = v;
 }
+void RendererHIP::set_denoise_demodulate(int v) { set_history_switch(denoise_demodulate, v, kDemodulateRange); }
 void RendererHIP::set_denoise_layers(int v) {
     set_history_switch(denoise_layers, v, "denoise_layers: 0 (the filter runs on the frame) or 1 (on the scattered layer, the background of the expected coverage put back afterwards)");
 }
@@ -1446,6 +1452,7 @@ void RendererHIP::download_denoised_layer(float* rgba) {
 void RendererHIP::upsample(int factor, int rays) {
     if (factor < kUpsampleMinFactor || factor > kUpsampleMaxFactor) throw std::runtime_error("upsample: factor must be 2..4");
     if (rays < 1 || rays > kExpectedMaxRays) throw std::runtime_error("upsample: rays must be 1.." + std::to_string(kExpectedMaxRays));
+    if (denoise_demodulate != 0 && denoise_demodulate != 1) throw std::runtime_error(std::string("upsample: ") + kDemodulateRange);
     flush_pending();
     if (!sized_.layer_valid) throw std::runtime_error("upsample: no denoise with denoise_layers = 1 since the last resize (its layer is what the call upsamples)");
     if (!sized_.layer_guided)
@@ -1464,7 +1471,7 @@ void RendererHIP::upsample(int factor, int rays) {
     launch_expected(P, nullptr, tile_count(W, H), rays, sized_.up_features->as<float>());
     const DenoiseSigma sg = sigma();
     launch_upsample(P, sized_.layer->as<float>(), sized_.dn_guide->as<float>(), w, h, factor, sized_.up_features->as<float>(), rays, sg, sized_.up_out->as<float>(),
-                    sized_.up_layer->as<float>(), stream);
+                    sized_.up_layer->as<float>(), stream, denoise_demodulate != 0);      // vr_demod.h: the lo layer demodulated inside the kernel, whatever produced it
     VR_HIP(hipGetLastError());
     sized_.up_factor = factor;
 }

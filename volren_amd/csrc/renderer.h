@@ -299,6 +299,14 @@ struct RendererHIP {
     int denoise_filter = 0;
     void set_denoise_ridge(float v);
     float denoise_ridge = kRegressDefaultRidge;
+    // Albedo demodulation (vr_demod.h).  denoise_demodulate = 1: with denoise_layers = 1, the split divides the scattered layer by the albedo of the feature buffer
+    // (floored at 2^-6, 1 where the coverage is 0), prepare divides the channels' standard deviations alike, the filter -- iterations or regression, the temporal
+    // pass with rejection or moments -- runs on the quotient, the history holds it, and the merge multiplies back: the DEMOD instances of the same kernels, no
+    // launch and no buffer more.  The layer keeps its meaning.  upsample() with the setting 1 at its call demodulates the lo layer by the lo guide inside its kernel
+    // and remodulates by the hi guide, whatever produced the layer.  Without denoise_layers = 1 denoise() and denoise_temporal() throw before anything is launched
+    // (0 is today's calls exactly).  set_denoise_demodulate: 0 or 1, throws otherwise; a change drops the history.
+    void set_denoise_demodulate(int v);
+    int denoise_demodulate = 0;
     // The layer upsampled under a full-resolution guide (vr_upsample.h).  upsample(factor, rays): the frame at factor x the renderer's size per axis, rebuilt from
     // the layer of the last denoise() / denoise_temporal() with denoise_layers = 1 and an expected-value pass of `rays` rays per axis at that size, which the call
     // marches into a buffer of its own with the scene and camera as they are now -- the caller keeps them as they were at the denoise call.  expected_skip and
@@ -451,12 +459,13 @@ private:
             DeviceBufferPtr moments[2];                // with denoise_moments = 1 the W*H*4 moment records (m1, m2, E, S); the current half exists iff the history has them
             int cur = -1;                              // the half that holds the history (-1: none)
             bool layers = false;                       // it holds the scattered layer (denoise_layers = 1), not the composite
+            bool demod = false;                        // ... divided by the albedo (denoise_demodulate = 1)
             TemporalCamera cam{};                      // the camera of the frame that wrote it
         } hist;
     } sized_;
     void download_whole(const DeviceBufferPtr& b, float* out, const char* absent);      // throws `absent` when b is null; else flushes and copies all of b
     void run_resolve();                                       // resolve()'s launches, after check_resolve
-    void set_history_switch(int& field, int v, const char* refusal);      // the body of set_denoise_moments / _resolve / _layers / _filter, each with its own refusal
+    void set_history_switch(int& field, int v, const char* refusal);      // the body of set_denoise_moments / _resolve / _layers / _filter / _demodulate, each with its own refusal
     DenoiseSigma sigma() const { return { denoise_sigma[0], denoise_sigma[1], denoise_sigma[2], denoise_sigma[3], denoise_sigma[4] }; }      // denoise_sigma as the kernels take it
     DeviceBufferPtr expected_stats_;                   // 4 counters of the last render_features_expected with expected_stats on
     bool expected_stats_valid_ = false;                // ... which that pass filled

@@ -382,6 +382,9 @@ void ShardedRenderer::run_denoise(const char* who, bool temporal) {
     // ... and its filter ("denoise_filter", vr_regress.h) runs on the gathered frame there: refused here, before the exchange launches anything
     if (parts_[0]->denoise_filter != 0 && parts_[0]->denoise_layers == 0)
         throw std::runtime_error(std::string("ShardedRenderer::") + who + ": denoise_filter = 1 needs denoise_layers = 1: the regression is defined on the scattered layer S with S.a = the expected coverage");
+    // ... and so does its demodulation ("denoise_demodulate", vr_demod.h)
+    if (parts_[0]->denoise_demodulate != 0 && parts_[0]->denoise_layers == 0)
+        throw std::runtime_error(std::string("ShardedRenderer::") + who + ": denoise_demodulate = 1 needs denoise_layers = 1: the albedo divides the scattered layer S, not a frame with the background in it");
     exchange_guides();
     VR_HIP(hipSetDevice(devices_[0]));
     parts_[0]->run_denoise(who, temporal, transport_ != "none");

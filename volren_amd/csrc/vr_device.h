@@ -74,8 +74,10 @@ void launch_features_expected(const SceneParams& P, const int32_t* tiles, int32_
 // atrous: one iteration of step `step` from (cin W*H*4, vin W*H, guide) into cout (W*H*4) and vout (W*H; nullptr: not written); the
 // inputs and outputs must not overlap.
 // counts: one sample count per raster tile (a frame of adaptive sampling), which replaces n and vscale per pixel; nullptr = the scalars.
+// demod, here and on the split, the merge and the upsampling below ("denoise_demodulate" = 1, vr_demod.h): the kernel's DEMOD instance, which divides the layer and
+// its standard deviation by the albedo of the same features, or multiplies it back; the arguments are the same.
 void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, const int32_t* counts, float* v, float* guide,
-                            hipStream_t stream);
+                            hipStream_t stream, bool demod = false);
 void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
                            float* cout, float* vout, hipStream_t stream);
 // Temporal accumulation (vr_temporal.h), between prepare and the iterations, described by one struct.  The plain pass blends (color W*H*4, v W*H, guide
@@ -108,8 +110,8 @@ void launch_resolve(const SceneParams& P, const float* fb, const float* features
 // The layered filter of vr_layers.h on whole W x H frames.  split: y (W*H*4, the resolved frame), B (W*H*4, launch_resolve's) and the coverage word of features
 // (W*H*8) -> S (W*H*4: the scattered layer, alpha = the coverage), which the denoiser's kernels read in the frame's place.  merge: F (W*H*4, their output), B and
 // features -> out (W*H*4: the frame with the background back) and L (W*H*4: the layer).  One kernel each; outputs must not overlap inputs.
-void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream);
-void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream);
+void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream, bool demod = false);
+void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream, bool demod = false);
 // The one-pass regression of vr_regress.h on a whole W x H frame, in the place of the a-trous iterations: S (W*H*4: what iteration 0 would read, alpha = the
 // coverage) and guide (W*H*8: launch_denoise_prepare's) -> F (W*H*4, what launch_layers_merge reads).  One kernel; F must not overlap the inputs.
 void launch_denoise_regress(const float* S, const float* guide, int32_t W, int32_t H, const DenoiseSigma& sg, float ridge, float* F, hipStream_t stream);
@@ -117,7 +119,7 @@ void launch_denoise_regress(const float* S, const float* guide, int32_t W, int32
 // lo_guide (w*h*8: launch_denoise_prepare's guide), hi_features (W*H*8: an expected-value pass at the hi resolution, `rays` rays per axis) -> out (W*H*4: the hi
 // frame) and L (W*H*4: the hi layer).  One kernel; outputs must not overlap inputs.
 void launch_upsample(const SceneParams& P, const float* lo_layer, const float* lo_guide, int32_t w, int32_t h, int32_t f, const float* hi_features, int32_t rays,
-                     const DenoiseSigma& sg, float* out, float* L, hipStream_t stream);
+                     const DenoiseSigma& sg, float* out, float* L, hipStream_t stream, bool demod = false);
 // Adaptive sampling (vr_adaptive.h): out[k] = e_t of raster tile tiles[k] holding counts[k] samples, k < n_tiles, from the W*H*4 framebuffer
 // and the W*H*4 moments (device arrays, ids in range).
 void launch_adaptive_error(const float* fb, const float* moments, const int32_t* tiles, const int32_t* counts, int32_t n_tiles, int32_t W, int32_t H, float* out,

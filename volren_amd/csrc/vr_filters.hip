@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "vr_adaptive.h"
+#include "vr_demod.h"
 #include "vr_denoise.h"
 #include "vr_device.h"
 #include "vr_layers.h"
@@ -32,7 +33,9 @@ struct DenoiseSrcDev : GuideDev {
 };
 // prepare: moments S (W*H*4, Welford's M2 / n) -> the unbiased variance var = S * vscale exactly as vr_variance forms it (0 for n = 1), then
 // the variance of the mean's luminance v (W*H) and the guide (W*H*8) from the features.  counts (a frame of adaptive sampling: one count per
-// raster tile) replaces the scalar n and vscale with the tile's own, formed as the host forms vscale; nullptr = the scalars
+// raster tile) replaces the scalar n and vscale with the tile's own, formed as the host forms vscale; nullptr = the scalars.  DEMOD ("denoise_demodulate" = 1):
+// v is vr_demod.h's, the variance of the layer divided by the albedo the pixel's features already hold in registers: three divisions more, no load more
+template <bool DEMOD>
 __global__ void __launch_bounds__(256)
 denoise_prepare_kernel(const float4* __restrict__ moments, const float4* __restrict__ features, int32_t W, int32_t H, int32_t n_all, float vscale_all,
                        const int32_t* __restrict__ counts, float* __restrict__ v, float4* __restrict__ guide) {
@@ -47,7 +50,8 @@ denoise_prepare_kernel(const float4* __restrict__ moments, const float4* __restr
     float f[8], g[8];
     unpack4(fa, f); unpack4(fb, f + 4);
     denoise_guide(f, g);
-    v[i] = denoise_mean_variance(var, n);
+    if constexpr (DEMOD) v[i] = demod_mean_variance(var, f, n);
+    else v[i] = denoise_mean_variance(var, n);
     guide[2 * i] = pack4(g);
     guide[2 * i + 1] = pack4(g + 4);
 }
@@ -65,10 +69,10 @@ denoise_atrous_kernel(const float4* __restrict__ cin, const float* __restrict__ 
     if (vout) vout[i] = ov;
 }
 void launch_denoise_prepare(const float* moments, const float* features, int32_t W, int32_t H, int32_t n, float vscale, const int32_t* counts, float* v, float* guide,
-                            hipStream_t stream) {
+                            hipStream_t stream, bool demod) {
     if (W <= 0 || H <= 0) return;
-    hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(moments),
-                       reinterpret_cast<const float4*>(features), W, H, n, vscale, counts, v, reinterpret_cast<float4*>(guide));
+    hipLaunchKernelGGL((demod ? denoise_prepare_kernel<true> : denoise_prepare_kernel<false>), dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream,
+                       reinterpret_cast<const float4*>(moments), reinterpret_cast<const float4*>(features), W, H, n, vscale, counts, v, reinterpret_cast<float4*>(guide));
 }
 void launch_denoise_atrous(const float* cin, const float* vin, const float* guide, int32_t W, int32_t H, int32_t step, const DenoiseSigma& sg,
                            float* cout, float* vout, hipStream_t stream) {
@@ -279,7 +283,9 @@ void launch_resolve(const SceneParams& P, const float* fb, const float* features
 
 // The layered filter of vr_layers.h: split in front of the denoiser's kernels, merge behind them.  One thread per pixel, dwordx4 loads and stores, no LDS, no
 // atomics.  split reads the pixel's texels of the resolved frame and of B and the first float4 of its features (the coverage word) and writes S: 64 B a pixel.
-// merge reads the filter's output, B and the same float4 and writes the frame and the layer: 80 B a pixel.
+// merge reads the filter's output, B and the same float4 and writes the frame and the layer: 80 B a pixel.  DEMOD ("denoise_demodulate" = 1): vr_demod.h's split
+// and merge, whose divisor comes from the albedo words of that float4 -- the same bytes, three divisions (split) or three multiplies (merge) more.
+template <bool DEMOD>
 __global__ void __launch_bounds__(256)
 layers_split_kernel(const float4* __restrict__ y, const float4* __restrict__ B, const float4* __restrict__ features, int32_t W, int32_t H, float4* __restrict__ S) {
     const TilePixel q = wave_tiled_pixel((int32_t)blockIdx.x, threadIdx.x, W);
@@ -288,9 +294,16 @@ layers_split_kernel(const float4* __restrict__ y, const float4* __restrict__ B, 
     float yy[4], b[4], s[4];
     unpack4(y[i], yy);
     unpack4(B[i], b);
-    layers_split_pixel(yy, b, features[2 * i].w, s);
+    if constexpr (DEMOD) {
+        float ak[4];
+        unpack4(features[2 * i], ak);
+        demod_split_pixel(yy, b, ak, s);
+    } else {
+        layers_split_pixel(yy, b, features[2 * i].w, s);
+    }
     S[i] = pack4(s);
 }
+template <bool DEMOD>
 __global__ void __launch_bounds__(256)
 layers_merge_kernel(const float4* __restrict__ F, const float4* __restrict__ B, const float4* __restrict__ features, int32_t W, int32_t H, float4* __restrict__ out,
                     float4* __restrict__ L) {
@@ -300,18 +313,24 @@ layers_merge_kernel(const float4* __restrict__ F, const float4* __restrict__ B, 
     float f[4], b[4], l[4], o[4];
     unpack4(F[i], f);
     unpack4(B[i], b);
-    layers_merge_pixel(f, b, features[2 * i].w, l, o);
+    if constexpr (DEMOD) {
+        float ak[4];
+        unpack4(features[2 * i], ak);
+        demod_merge_pixel(f, b, ak, l, o);
+    } else {
+        layers_merge_pixel(f, b, features[2 * i].w, l, o);
+    }
     out[i] = pack4(o);
     L[i] = pack4(l);
 }
-void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream) {
+void launch_layers_split(const float* y, const float* B, const float* features, int32_t W, int32_t H, float* S, hipStream_t stream, bool demod) {
     if (W <= 0 || H <= 0) return;
-    hipLaunchKernelGGL(layers_split_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(y),
+    hipLaunchKernelGGL((demod ? layers_split_kernel<true> : layers_split_kernel<false>), dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(y),
                        reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(features), W, H, reinterpret_cast<float4*>(S));
 }
-void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream) {
+void launch_layers_merge(const float* F, const float* B, const float* features, int32_t W, int32_t H, float* out, float* L, hipStream_t stream, bool demod) {
     if (W <= 0 || H <= 0) return;
-    hipLaunchKernelGGL(layers_merge_kernel, dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(F),
+    hipLaunchKernelGGL((demod ? layers_merge_kernel<true> : layers_merge_kernel<false>), dim3((unsigned)tile_count(W, H)), dim3(256), 0, stream, reinterpret_cast<const float4*>(F),
                        reinterpret_cast<const float4*>(B), reinterpret_cast<const float4*>(features), W, H, reinterpret_cast<float4*>(out),
                        reinterpret_cast<float4*>(L));
 }
@@ -376,7 +395,9 @@ void launch_denoise_regress(const float* S, const float* guide, int32_t W, int32
 // and texels off the lo frame hold a record no tap reads (the lane code skips such taps by their coordinates).  Then a pixel reads the two float4 of its hi
 // features, forms its guide and B_p (rays x rays environment lookups, none with the environment hidden), runs its 16 taps from LDS and writes out and L, one
 // dwordx4 each.  VR_UPSAMPLE_GLOBAL_TAPS = 1 builds the form whose taps read the three float4 from global memory instead (no LDS, no barrier): measured, not
-// shipped.  No atomics, no scratch.
+// shipped.  No atomics, no scratch.  DEMOD ("denoise_demodulate" = 1, vr_demod.h): a lo record's layer is divided by the divisor of its own guide
+// once, when it is staged -- the record's three float4 are in the staging thread's registers then, so the window holds the demodulated layer at the same size and
+// the 16 taps read it as they do today -- and the pixel's hi layer is multiplied by the divisor of its hi features, which it has loaded for its guide.
 #ifndef VR_UPSAMPLE_GLOBAL_TAPS
 #define VR_UPSAMPLE_GLOBAL_TAPS 0
 #endif
@@ -399,7 +420,7 @@ struct UpsampleGlobalDev {
         unpack4(L[i], Lq); unpack4(g[2 * i], gq); unpack4(g[2 * i + 1], gq + 4);
     }
 };
-template <int32_t F>
+template <int32_t F, bool DEMOD>
 __global__ void __launch_bounds__(256)
 upsample_kernel(const SceneParams P, const float4* __restrict__ lo_layer, const float4* __restrict__ lo_guide, int32_t w, int32_t h,
                 const float4* __restrict__ hi_features, int32_t rays, const DenoiseSigma sg, float4* __restrict__ out, float4* __restrict__ L) {
@@ -410,7 +431,16 @@ upsample_kernel(const SceneParams P, const float4* __restrict__ lo_layer, const 
     __shared__ UpsampleTexel win[Window::kTexels];
     const Window window = Window::of((int32_t)blockIdx.x, W);
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    stage_window(win, window, w, h, UpsampleTexel{ zero, zero, zero }, [&](int32_t i) { return UpsampleTexel{ lo_layer[i], lo_guide[2 * i], lo_guide[2 * i + 1] }; });
+    stage_window(win, window, w, h, UpsampleTexel{ zero, zero, zero }, [&](int32_t i) {
+        UpsampleTexel t{ lo_layer[i], lo_guide[2 * i], lo_guide[2 * i + 1] };
+        if constexpr (DEMOD) {
+            float lq[4], ak[4];
+            unpack4(t.L, lq); unpack4(t.ga, ak);
+            demod_tap(lq, ak);
+            t.L = pack4(lq);
+        }
+        return t;
+    });
 #endif
     if (q.px >= W || q.py >= H) return;
     const int32_t i = q.py * W + q.px;
@@ -420,20 +450,22 @@ upsample_kernel(const SceneParams P, const float4* __restrict__ lo_layer, const 
     const v3 b = resolve_background(P, q.px, q.py, rays);
     B[0] = b.x; B[1] = b.y; B[2] = b.z; B[3] = 0.0f;
 #if VR_UPSAMPLE_GLOBAL_TAPS
-    upsample_pixel(UpsampleGlobalDev{ lo_layer, lo_guide, w }, w, h, F, q.px, q.py, gp, B, sg, l, o);
+    if constexpr (DEMOD) demod_upsample_pixel(DemodTaps<UpsampleGlobalDev>{ { lo_layer, lo_guide, w } }, w, h, F, q.px, q.py, gp, B, sg, l, o);
+    else upsample_pixel(UpsampleGlobalDev{ lo_layer, lo_guide, w }, w, h, F, q.px, q.py, gp, B, sg, l, o);
 #else
-    upsample_pixel(UpsampleWindowDev<F>{ win, window }, w, h, F, q.px, q.py, gp, B, sg, l, o);
+    if constexpr (DEMOD) demod_upsample_pixel(UpsampleWindowDev<F>{ win, window }, w, h, F, q.px, q.py, gp, B, sg, l, o);
+    else upsample_pixel(UpsampleWindowDev<F>{ win, window }, w, h, F, q.px, q.py, gp, B, sg, l, o);
 #endif
     out[i] = pack4(o);
     L[i] = pack4(l);
 }
 void launch_upsample(const SceneParams& P, const float* lo_layer, const float* lo_guide, int32_t w, int32_t h, int32_t f, const float* hi_features, int32_t rays,
-                     const DenoiseSigma& sg, float* out, float* L, hipStream_t stream) {
+                     const DenoiseSigma& sg, float* out, float* L, hipStream_t stream, bool demod) {
     const int32_t W = P.u.resolution[0], H = P.u.resolution[1];
     if (f < kUpsampleMinFactor || f > kUpsampleMaxFactor || W != f * w || H != f * h) throw std::invalid_argument("launch_upsample: the hi frame is not f times the lo frame, f in 2..4");
     if (w <= 0 || h <= 0 || rays < 1) return;
     const dim3 grid((unsigned)tile_count(W, H)), block(256);
-#define VR_UPSAMPLE_LAUNCH(F) hipLaunchKernelGGL(upsample_kernel<F>, grid, block, 0, stream, P, reinterpret_cast<const float4*>(lo_layer), reinterpret_cast<const float4*>(lo_guide), \
+#define VR_UPSAMPLE_LAUNCH(F) hipLaunchKernelGGL((demod ? upsample_kernel<F, true> : upsample_kernel<F, false>), grid, block, 0, stream, P, reinterpret_cast<const float4*>(lo_layer), reinterpret_cast<const float4*>(lo_guide), \
                                                  w, h, reinterpret_cast<const float4*>(hi_features), rays, sg, reinterpret_cast<float4*>(out), reinterpret_cast<float4*>(L))
     if (f == 2) VR_UPSAMPLE_LAUNCH(2); else if (f == 3) VR_UPSAMPLE_LAUNCH(3); else VR_UPSAMPLE_LAUNCH(4);
 #undef VR_UPSAMPLE_LAUNCH

@@ -8,7 +8,7 @@ from . import _lib
 
 _INT_FIELDS = ("sample", "sppx", "seed", "bounces", "show_environment", "tonemapping", "integrator", "grid_frame_counter",
                "sample_pool_mb", "gpu_encoder", "fast_math", "tf_float_atlas", "launch_target_ms", "order_tiles", "coalesce_trace", "majorant_layout",
-               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
+               "variance", "denoise_iterations", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "denoise_demodulate", "wide_addressing", "seed_table_mb", "seed_table_max_samples",
                "expected_skip", "expected_field", "expected_stats", "sky_tiles", "see_through_tiles")
 _READ_ONLY_INT_FIELDS = ("n_grid_frames", "last_launches", "last_sky_tiles", "last_see_through_tiles", "pending_samples", "majorant_blocked", "env_div_safe", "env_compact", "kernel_variant", "kernel_variant_reason",
                          "kernel_wide", "adaptive_rounds", "seed_table_samples", "seed_table_fills")
@@ -342,7 +342,9 @@ class Renderer:
         """The a-trous filter of the current frame (include/volren_amd.h vr_denoise): needs `variance = 1` for all its samples and a render_features
         since the last resize; `denoise_iterations` / `denoise_sigma` set it up.  `denoise_filter = 1` (default 0; needs `denoise_layers = 1`; a change drops
         the history) runs one 11 x 11 pass of weighted local regression on the scattered layer in the iterations' place (csrc/vr_regress.h); `denoise_ridge`
-        is the ridge on its seven slopes, 0 (the default: zero order) or in [2^-20, 2^20]."""
+        is the ridge on its seven slopes, 0 (the default: zero order) or in [2^-20, 2^20].  `denoise_demodulate = 1` (default 0; needs
+        `denoise_layers = 1`; a change drops the history) divides the scattered layer by the guide's albedo in front of either filter and multiplies it back
+        behind it (csrc/vr_demod.h); upsample() then demodulates the layer it rebuilds as well."""
         _lib.check(self._L.vr_denoise(self._h))
         if sync:
             self.synchronize()
@@ -685,6 +687,10 @@ class ShardedRenderer:
     denoise_filter = _part0("denoise_filter", True,
         """Whether one pass of local regression takes the place of the a-trous iterations (Renderer.denoise, csrc/vr_regress.h): part 0's field, which holds
         the gathered frame and guide and runs the filter; setting it sets every part's.""")
+
+    denoise_demodulate = _part0("denoise_demodulate", True,
+        """Whether the scattered layer is filtered divided by the guide's albedo (Renderer.denoise, csrc/vr_demod.h): part 0's field, which holds the
+        gathered frame and guide and runs the filter; setting it sets every part's.""")
 
     denoise_ridge = _part0("denoise_ridge", True,
         """The ridge of that regression, 0 (zero order) or in [2^-20, 2^20]: part 0's field; setting it sets every part's.""")

@@ -403,7 +403,7 @@ def set_context(width=None, height=None, device=None):
 _SCALARS = ("sample", "sppx", "bounces", "seed", "tonemap_exposure", "tonemap_gamma", "tonemapping", "show_environment",
             "phase", "density_scale", "emission_scale", "cam_fov")
 _VEC3S = ("albedo", "vol_clip_min", "vol_clip_max", "cam_pos", "cam_dir", "cam_up")
-_PASS_THROUGH = ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "denoise_ridge", "expected_skip", "expected_field")      # this build's own fields: the inner renderer's, as they are
+_PASS_THROUGH = ("denoise_reject", "denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "denoise_ridge", "denoise_demodulate", "expected_skip", "expected_field")      # this build's own fields: the inner renderer's, as they are
 
 
 class Renderer:
@@ -598,7 +598,8 @@ class Renderer:
         needs render_features_expected with rays >= 2), in fbo_data()'s shape: the filtered scattered light premultiplied by the exact coverage, alpha =
         the coverage (volren_amd.Renderer.denoised_layer).  With the setting on the filter runs on that layer alone and the analytic background is put
         back afterwards: denoised_data() is the composite.  `denoise_filter = 1` on top of it (default 0; a change drops the history) runs one pass of local
-        regression in the place of the a-trous iterations, `denoise_ridge` its ridge, 0 or in [2^-20, 2^20] (volren_amd.Renderer.denoise)."""
+        regression in the place of the a-trous iterations, `denoise_ridge` its ridge, 0 or in [2^-20, 2^20]; `denoise_demodulate = 1` (default 0; a change drops the
+        history) divides the layer by the guide's albedo in front of the filter and multiplies it back behind it (volren_amd.Renderer.denoise)."""
         return self._r.denoised_layer().reshape(self._r.width, self._r.height, 4)
 
     def upsample(self, factor=2, rays=2):
