@@ -534,7 +534,7 @@ int vr_path_probe(vr_renderer* r, int kind, int form, const void* in, void* out,
  * flag or history of the renderer changes; the renderer gives its device and stream, and to the two scene-bound stages (resolve, upsample) its scene.
  * W x H: the frame (upsample: the LO frame; the outputs are f W x f H).  in: 6 pointers, out: 5 pointers, NULL where the stage has none or an optional one is
  * left out; params: 40 floats -- [0..4] sigma (colour, normal, depth, coverage, albedo), [5] an integer i0, [6] a float x, [7] tau, [8] an integer i1,
- * [9..21] the current camera, [22..34] the history's (pos 3, cam_transform 9 column-major, cam_z), the rest 0.  float arrays of 4 bytes, counts and ids int32.
+ * [9..21] the current camera, [22..34] the history's (pos 3, cam_transform 9 column-major, cam_z), [35] an integer demod, the rest 0.  float arrays of 4 bytes, counts and ids int32.
  *   stage                 launcher                 in                                                            params               out
  *   0 prepare             launch_denoise_prepare   moments S W*H*4, features W*H*8, [counts, one per tile]       i0 = n, x = vscale   v W*H, guide W*H*8
  *   1 atrous              launch_denoise_atrous    colour W*H*4, v W*H, guide W*H*8                              i0 = step, sigma     colour W*H*4, [v W*H]
@@ -549,10 +549,12 @@ int vr_path_probe(vr_renderer* r, int kind, int form, const void* in, void* out,
  *   7 upsample            launch_upsample          lo layer W*H*4, lo guide W*H*8, hi features fW*fH*8           i0 = rays, i1 = f,   out, L fW*fH*4 each
  *                                                                                                                sigma
  *   8 adaptive error      launch_adaptive_error    fb W*H*4, moments W*H*4, tile ids i0, counts i0               i0 = the tiles       e_t i0
+ * demod (0 or 1; default 0, and then every launch is what it is without this line): 1 runs the stage's DEMOD instance ("denoise_demodulate" = 1,
+ * volren_amd/csrc/vr_demod.h) in stages 0, 4, 5 and 7, which read the albedo in words 0..2 of their features (7: of the lo guide and of the hi features).
  * Stages 3 and 7 read the scene as the renderer's next launch would (7: with the resolution f W x f H, as vr_upsample forms it) and need W x H to be the
  * renderer's resolution.  Everything that can be checked without a device is checked before the device is looked for: VR_ERR_ARG for a NULL renderer or array,
  * an unknown stage, W, H outside 1..4096, step outside 1..2^20, rays outside 1..4, f outside 2..4, n < 1, a tile id outside the frame, tau < 0, a parameter
- * that is not finite, the moments and the rejection form together, a history given in part; and, with a device, for a W x H that is not the renderer's in stages 3 and 7.
+ * that is not finite, a demod other than 0 or 1, demod = 1 at a stage other than 0, 4, 5 or 7, the moments and the rejection form together, a history given in part; and, with a device, for a W x H that is not the renderer's in stages 3 and 7.
  * The values INSIDE the arrays are the caller's business: tests/filter_cases.py holds the catalogue the suite runs (frames of 64 x 48 at most, built to the edges
  * of what the product's own passes can hand these kernels), and every case of it passes the host build of its stage, range-checked, in
  * tests/test_filter_cases_host.py before tests/test_gpu_filter_probe.py runs it on a device. */

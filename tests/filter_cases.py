@@ -5,15 +5,21 @@ conditions; tests/test_gpu_filter_probe.py compares device() with host() bit for
 TEST HARNESS ONLY.
 
 Every case is deterministic and inside what the product's own passes can hand these kernels: coverage in [0, 1], depth finite and >= 0, albedo finite, normals
-finite (not necessarily unit, possibly zero), colour and moments >= 0.  The exceptions carry nonfinite = True and are of three kinds only: inf moments from
-overflow in prepare (and the inf v behind it), a NaN or inf colour texel in atrous, regress and temporal, a NaN moment in the adaptive error.  No case puts a
-non-finite value into a feature, a guide, a camera or a history record: those feed index arithmetic.
+finite (not necessarily unit, possibly zero), colour and moments >= 0.  The exceptions carry nonfinite = True and are of four kinds only: inf moments from
+overflow in prepare (and the inf v behind it), a NaN or inf colour texel in atrous, regress and temporal, a NaN moment in the adaptive error, and -- in the
+group "demod", in the DEMOD instances of split, prepare and merge alone -- a NaN or +inf albedo word of the features (and a quotient or product of finite words
+that overflows).  Those three stages are per-pixel and index nothing by the albedo.  No such word goes into upsample, a guide input, a camera or a history record,
+and no other case puts a non-finite value into a feature: those feed the edge weights and the index arithmetic.
+
+The group "demod" (par["demod"] = 1: vr_filter_probe's params[35], hk_demod on the host) draws its albedo words per channel from ALBEDOS -- zeros of both signs,
+a subnormal, the floor 2^-6 and its two neighbours, values above 1, a negative one -- and its coverage from KAPPAS, and keeps the albedo where the coverage is 0.
 
 Frames: 47x33 (test_denoise_host.hostile's size: 3 x 3 tiles, ragged on both axes); 33x31, 17x16, 1x37 and 37x1 where the stage reads neighbours or stages a
 window; nothing holds more pixels than 64x48."""
 import numpy as np
 
 import hk_adaptive as ha
+import hk_demod as hd
 import hk_denoise
 import hk_layers as hl
 import hk_moments as hm
@@ -33,7 +39,7 @@ STAGES = ("prepare", "atrous", "temporal", "resolve", "split", "merge", "regress
 
 class Case:
     """stage, name, frame size, the input arrays (inp) and the parameters (par).  scene: the scene-bound stages' scene name (test_resolve_host._oracle's names).
-    nonfinite: the case holds one of the three sanctioned non-finite inputs.  ill: why the float64 statement does not apply, or None."""
+    nonfinite: the case holds one of the four sanctioned non-finite inputs.  ill: why the float64 statement does not apply, or None."""
 
     def __init__(self, stage, name, w, h, inp, par=None, scene=None, nonfinite=False, ill=None):
         assert stage in STAGES and w * h <= MAX_PIXELS
@@ -94,12 +100,15 @@ def _prepare_host(c):
         if counts is None:
             var = S * variance_scale(n) if n >= 2 else np.zeros_like(S)
             v, g = hk_denoise.prepare(f32(var), feat, n)
+            n_px = n
         else:
             n_px = ha.per_pixel(counts, c.w, c.h)
             scale = np.array([variance_scale(int(k)) for k in counts.reshape(-1)], np.float32).reshape(counts.shape)
             scale_px = np.repeat(np.repeat(scale, 16, axis=0), 16, axis=1)[:c.h, :c.w]
             var = np.where((n_px >= 2)[..., None], S * scale_px[..., None], np.float32(0.0))
             v, g = ha.prepare(f32(var), feat, n_px)
+        if c.par.get("demod"):                           # the variance of the divided layer; the guide stays prepare's
+            v = hd.variance(f32(var), feat, n_px)
     return {"v": v, "guide": g}
 
 
@@ -107,7 +116,7 @@ def _prepare_device(r, c):
     n = c.par["n"]
     counts = c.inp.get("counts")
     v, g = r.filter_probe("prepare", c.w, c.h, [c.inp["S"], c.inp["feat"], None if counts is None else np.ascontiguousarray(counts.reshape(-1), np.int32)],
-                          [(c.h, c.w), (c.h, c.w, 8)], i0=n, x=variance_scale(n))
+                          [(c.h, c.w), (c.h, c.w, 8)], i0=n, x=variance_scale(n), demod=bool(c.par.get("demod")))
     return {"v": v, "guide": g}
 
 
@@ -385,20 +394,27 @@ def layers_cases():
 
 
 def _split_host(c):
-    return {"S": hl.split(c.inp["y"], c.inp["B"], np.ascontiguousarray(c.inp["feat"][..., 3]))}
+    with np.errstate(all="ignore"):
+        if c.par.get("demod"):
+            return {"S": hd.split(c.inp["y"], c.inp["B"], c.inp["feat"])}
+        return {"S": hl.split(c.inp["y"], c.inp["B"], np.ascontiguousarray(c.inp["feat"][..., 3]))}
 
 
 def _split_device(r, c):
-    return {"S": r.filter_probe("split", c.w, c.h, [c.inp["y"], c.inp["B"], c.inp["feat"]], [(c.h, c.w, 4)])[0]}
+    return {"S": r.filter_probe("split", c.w, c.h, [c.inp["y"], c.inp["B"], c.inp["feat"]], [(c.h, c.w, 4)], demod=bool(c.par.get("demod")))[0]}
 
 
 def _merge_host(c):
-    out, L = hl.merge(c.inp["F"], c.inp["B"], np.ascontiguousarray(c.inp["feat"][..., 3]))
+    with np.errstate(all="ignore"):
+        if c.par.get("demod"):
+            out, L = hd.merge(c.inp["F"], c.inp["B"], c.inp["feat"])
+        else:
+            out, L = hl.merge(c.inp["F"], c.inp["B"], np.ascontiguousarray(c.inp["feat"][..., 3]))
     return {"out": out, "L": L}
 
 
 def _merge_device(r, c):
-    out, L = r.filter_probe("merge", c.w, c.h, [c.inp["F"], c.inp["B"], c.inp["feat"]], [(c.h, c.w, 4)] * 2)
+    out, L = r.filter_probe("merge", c.w, c.h, [c.inp["F"], c.inp["B"], c.inp["feat"]], [(c.h, c.w, 4)] * 2, demod=bool(c.par.get("demod")))
     return {"out": out, "L": L}
 
 
@@ -482,6 +498,35 @@ def _regress_device(r, c):
 UPSAMPLE_SHAPES = (((1, 37), (2, 3, 4)), ((37, 1), (2, 3, 4)), ((17, 16), (2, 3)), ((12, 20), (2, 3)), ((12, 12), (4,)))
 
 
+def _upsample_case(scene, w, h, f, demod=False):
+    """demod: the albedo words of the lo and of the hi features drawn per channel from ALBEDOS (under the hi checkerboard the lo pixel's own), kept where the
+    coverage is 0"""
+    rng = np.random.default_rng(8000 + 100 * f + 7 * w + h)
+    lo_feat = frame(w, h, seed=19)[2]
+    hi = frame(f * w, f * h, seed=23)[2]
+    if demod:
+        arng = np.random.default_rng(8500 + 100 * f + 7 * w + h)
+        lo_feat[..., 0:3] = arng.choice(ALBEDOS, (h, w, 3))
+        hi[..., 0:3] = arng.choice(ALBEDOS, (f * h, f * w, 3))
+    glo = hu.guide(lo_feat)
+    L = f32(rng.uniform(0.0, 1.0, (h, w, 4)))
+    L[..., 3] = glo[..., 3]
+    L[..., :3] *= L[..., 3:4]                 # premultiplied, as the merge leaves it
+    rep = np.repeat(np.repeat(lo_feat, f, axis=0), f, axis=1)      # the lo features under every hi pixel: a hi guide equal to a lo tap's bit for bit
+    y, x = np.mgrid[0:f * h, 0:f * w]
+    hi = np.where(((x // 4 + y // 4) % 2 == 0)[..., None], rep, hi)
+    flip = rng.random((f * h, f * w)) < 0.15                       # hi coverage 0 where lo is covered, and the reverse
+    hi[..., 3] = np.where(flip, np.where(rep[..., 3] > 0, 0.0, 0.625), hi[..., 3])
+    albedo = hi[..., 0:3].copy()
+    hi[hi[..., 3] == 0] = 0.0
+    if demod:
+        hi[..., 0:3] = albedo
+    par = {"f": f, "rays": 2, "sigma": SIGMA}
+    if demod:
+        par["demod"] = 1
+    return Case("upsample", "%s%s-%dx%d-f%d" % ("demod-" if demod else "", scene, w, h, f), w, h, {"L": L, "glo": glo, "feat_hi": f32(hi)}, par, scene=scene)
+
+
 def upsample_cases():
     out = []
     for scene in ("c2", "c3env"):
@@ -489,34 +534,22 @@ def upsample_cases():
             for f in factors:
                 if scene == "c3env" and (w, h) != (17, 16):
                     continue
-                rng = np.random.default_rng(8000 + 100 * f + 7 * w + h)
-                lo_feat = frame(w, h, seed=19)[2]
-                glo = hu.guide(lo_feat)
-                L = f32(rng.uniform(0.0, 1.0, (h, w, 4)))
-                L[..., 3] = glo[..., 3]
-                L[..., :3] *= L[..., 3:4]                 # premultiplied, as the merge leaves it
-                hi = frame(f * w, f * h, seed=23)[2]
-                rep = np.repeat(np.repeat(lo_feat, f, axis=0), f, axis=1)      # the lo features under every hi pixel: a hi guide equal to a lo tap's bit for bit
-                y, x = np.mgrid[0:f * h, 0:f * w]
-                hi = np.where(((x // 4 + y // 4) % 2 == 0)[..., None], rep, hi)
-                flip = rng.random((f * h, f * w)) < 0.15                       # hi coverage 0 where lo is covered, and the reverse
-                hi[..., 3] = np.where(flip, np.where(rep[..., 3] > 0, 0.0, 0.625), hi[..., 3])
-                hi[hi[..., 3] == 0] = 0.0
-                out.append(Case("upsample", "%s-%dx%d-f%d" % (scene, w, h, f), w, h, {"L": L, "glo": glo, "feat_hi": f32(hi)}, {"f": f, "rays": 2, "sigma": SIGMA}, scene=scene))
+                out.append(_upsample_case(scene, w, h, f))
     return out
 
 
 def _upsample_host(c):
     f = c.par["f"]
     B, _ = hr.prepare(oracle(c.scene, f * c.w, f * c.h), c.par["rays"], np.zeros((f * c.h, f * c.w, 4), np.float32))
-    out, L = hu.upsample(c.inp["L"], c.inp["glo"], hu.guide(c.inp["feat_hi"]), B, f, c.par["sigma"])
+    up = (lambda *a: hd.upsample(*a, staged=False)) if c.par.get("demod") else hu.upsample
+    out, L = up(c.inp["L"], c.inp["glo"], hu.guide(c.inp["feat_hi"]), B, f, c.par["sigma"])
     return {"out": out, "L": L}
 
 
 def _upsample_device(r, c):
     f = c.par["f"]
     hi = (f * c.h, f * c.w, 4)
-    out, L = r.filter_probe("upsample", c.w, c.h, [c.inp["L"], c.inp["glo"], c.inp["feat_hi"]], [hi, hi], sigma=c.par["sigma"], i0=c.par["rays"], i1=f)
+    out, L = r.filter_probe("upsample", c.w, c.h, [c.inp["L"], c.inp["glo"], c.inp["feat_hi"]], [hi, hi], sigma=c.par["sigma"], i0=c.par["rays"], i1=f, demod=bool(c.par.get("demod")))
     return {"out": out, "L": L}
 
 
@@ -552,15 +585,91 @@ def _adaptive_device(r, c):
     return {"e": r.filter_probe("adaptive_error", c.w, c.h, [c.inp["fb"], c.inp["S"], c.inp["tiles"], c.inp["counts"]], [(n,)], i0=n)[0]}
 
 
+# ---- the DEMOD instances of prepare, split, merge and upsample (vr_demod.h; par["demod"] = 1) -----------------------------------------------------------------
+_FLOOR = np.float32(2.0 ** -6)
+# per channel: nothing, a signed nothing, a subnormal, below the floor, the floats around the floor, ordinary, 1 and the float above it, above 1, far above, negative
+ALBEDOS = np.array([0.0, -0.0, 1e-40, 2.0 ** -7, np.nextafter(_FLOOR, np.float32(0)), _FLOOR, np.nextafter(_FLOOR, np.float32(1)), 0.5, 1.0,
+                    np.nextafter(np.float32(1), np.float32(2)), 4.0, 1e5, -0.25], np.float32)
+
+
+def demod_features(seed, w=W0, h=H0):
+    """the hostile features with the coverage drawn from KAPPAS and every albedo word from ALBEDOS -- on the pixels without coverage too: d = 1 has to ignore them"""
+    rng = np.random.default_rng(seed)
+    feat = frame(w, h)[2]
+    feat[..., 3] = rng.choice(KAPPAS, (h, w))
+    feat[..., 0:3] = rng.choice(ALBEDOS, (h, w, 3))
+    return feat
+
+
+def poisoned(feat):
+    """the fourth non-finite kind: one albedo channel NaN on some pixels and +inf on others, covered and uncovered ones among both.  -> (features, NaN mask
+    [H][W][3], inf mask [H][W][3])"""
+    h, w = feat.shape[:2]
+    y, x = np.mgrid[0:h, 0:w]
+    ch = (x + y) % 3
+    nan_px, inf_px = (x % 5 == 1) & (y % 4 == 2), (x % 5 == 3) & (y % 4 == 0)
+    is_nan, is_inf = (nan_px[..., None] & (ch[..., None] == np.arange(3))), (inf_px[..., None] & (ch[..., None] == np.arange(3)))
+    out = feat.copy()
+    out[..., 0:3] = np.where(is_nan, np.float32(np.nan), np.where(is_inf, np.float32(np.inf), feat[..., 0:3]))
+    return out, is_nan, is_inf
+
+
+def demod_cases():
+    rng = np.random.default_rng(6500)
+    par = {"demod": 1}
+    out = []
+    kap, lev = (c for c in layers_cases() if c.stage == "split")
+    # -- split
+    feat = demod_features(6501)
+    y = kap.inp["y"].copy()
+    y[..., 3] = feat[..., 3]
+    out.append(Case("split", "demod-albedos", W0, H0, {"y": y, "B": kap.inp["B"], "feat": feat}, par))
+    out.append(Case("split", "demod-levels", W0, H0, {"y": lev.inp["y"], "B": lev.inp["B"], "feat": demod_features(6502)}, par))
+    # no background, so S = y / d: 1e-36 .. 1e-38 over 1e5 in the left half of the frame lands in the subnormal range, where the division's result is denormalised
+    sub = demod_features(6503)
+    sub[:, : W0 // 2, 0:3] = np.float32(1e5)
+    tiny = f32(rng.choice(np.array([1e-36, 1e-37, 1e-38], np.float32), (H0, W0, 4)))
+    tiny[..., 3] = sub[..., 3]
+    out.append(Case("split", "demod-subnormal-quotient", W0, H0, {"y": tiny, "B": np.zeros_like(tiny), "feat": sub}, par))
+    huge = f32(rng.choice(np.array([3e38, 1e30, 1.0], np.float32), (H0, W0, 4)))         # 3e38 over the floor overflows, over 4 and 1e5 it does not
+    huge[..., 3] = feat[..., 3]
+    out.append(Case("split", "demod-overflow-quotient", W0, H0, {"y": huge, "B": np.zeros_like(huge), "feat": feat}, par, nonfinite=True))
+    bad, _, _ = poisoned(feat)
+    out.append(Case("split", "demod-nan-inf-albedo", W0, H0, {"y": y, "B": kap.inp["B"], "feat": bad}, par, nonfinite=True))
+    # -- prepare
+    pfeat = demod_features(6504)
+    for c in prepare_cases():
+        if c.name == "tiny-n1048576":
+            continue
+        out.append(Case("prepare", "demod-" + c.name, W0, H0, dict(c.inp, feat=pfeat), dict(c.par, demod=1), nonfinite=c.nonfinite))
+    hostile_counts = next(c for c in prepare_cases() if c.name == "counts")
+    out.append(Case("prepare", "demod-nan-inf-albedo", W0, H0, dict(hostile_counts.inp, feat=poisoned(pfeat)[0]), dict(hostile_counts.par, demod=1), nonfinite=True))
+    # -- merge, on the demodulated S
+    S = hd.split(y, kap.inp["B"], feat)
+    other = S.copy()
+    other[..., 3] = rng.choice(KAPPAS, (H0, W0))
+    out.append(Case("merge", "demod-alpha-differs", W0, H0, {"F": other, "B": kap.inp["B"], "feat": feat}, par))
+    out.append(Case("merge", "demod-alpha-is-kappa", W0, H0, {"F": S, "B": kap.inp["B"], "feat": feat}, par))
+    big = S.copy()
+    big[..., :3] = f32(rng.choice(np.array([1e34, 1.0, -1e34, 1e-3], np.float32), (H0, W0, 3)))      # 1e34 times 1e5 overflows, times 4 it does not
+    out.append(Case("merge", "demod-overflow", W0, H0, {"F": big, "B": kap.inp["B"], "feat": feat}, par, nonfinite=True))
+    out.append(Case("merge", "demod-nan-inf-albedo", W0, H0, {"F": other, "B": kap.inp["B"], "feat": bad}, par, nonfinite=True))
+    # -- upsample: no non-finite word here, the guides feed the edge weights of every tap
+    for scene, (w, h), factors in (("c3env", (17, 16), (2, 3)), ("c2", (1, 37), (2, 3, 4)), ("c2", (37, 1), (2, 3, 4)), ("c2", (12, 12), (4,))):
+        for f in factors:
+            out.append(_upsample_case(scene, w, h, f, demod=True))
+    return out
+
+
 # ---- the catalogue ----------------------------------------------------------------------------------------------------------------------------------------
-_HOST = {"prepare": _prepare_host, "atrous": _atrous_host, "temporal": _temporal_host, "resolve": _resolve_host, "split": _split_host, "merge": _merge_host,
+_HOST ={"prepare": _prepare_host, "atrous": _atrous_host, "temporal": _temporal_host, "resolve": _resolve_host, "split": _split_host, "merge": _merge_host,
          "regress": _regress_host, "upsample": _upsample_host, "adaptive_error": _adaptive_host}
 _DEVICE = {"prepare": _prepare_device, "atrous": _atrous_device, "temporal": _temporal_device, "resolve": _resolve_device, "split": _split_device,
            "merge": _merge_device, "regress": _regress_device, "upsample": _upsample_device, "adaptive_error": _adaptive_device}
 # the groups the two test files parametrise over: the three temporal forms apart, split and merge together
 GROUPS = {"prepare": prepare_cases, "atrous": atrous_cases, "temporal-plain": lambda: temporal_cases("plain"), "temporal-reject": lambda: temporal_cases("reject"),
           "temporal-moments": lambda: temporal_cases("moments"), "resolve": resolve_cases, "layers": layers_cases, "regress": regress_cases,
-          "upsample": upsample_cases, "adaptive_error": adaptive_cases}
+          "upsample": upsample_cases, "adaptive_error": adaptive_cases, "demod": demod_cases}
 _CASES, _RESULTS = {}, {}
 
 

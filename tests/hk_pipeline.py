@@ -1,7 +1,7 @@
 """One host model of the image-space state of a renderer (include/volren_amd.h): which frame a denoise call starts from, what it leaves in
 `denoised`, the layer, the history, the statistic, the resolved frame and the upsampled frames, which setting drops the history, and what every refused call
 says and leaves behind.  The arithmetic is the host builds' (hk_denoise, hk_adaptive, hk_temporal, hk_moments, hk_resolve, hk_layers, hk_regress,
-hk_upsample); nothing of the path tracer is stated here: a frame, its variance, its features and its sample counts are inputs (new_frame).  Plus the two
+hk_upsample, hk_demod); nothing of the path tracer is stated here: a frame, its variance, its features and its sample counts are inputs (new_frame).  Plus the two
 generators the tests of the pipeline share: a greedy all-pairs array over the denoiser's settings and random call sequences.  TEST HARNESS ONLY.
 
 Written from the header's text, not from RendererHIP::run_denoise.  Where several refusals apply at once the header ranks none of them: Refused carries every
@@ -12,6 +12,7 @@ import numpy as np
 
 import hk_adaptive
 import hk_common
+import hk_demod
 import hk_denoise
 import hk_layers
 import hk_moments
@@ -29,7 +30,8 @@ REFUSALS = {
     "moments_reject": "do not go together",
     "not_expected": "was not last filled by render_features_expected",
     "one_ray": "rays >= 2 is needed",
-    "filter_layers": "needs denoise_layers = 1",
+    "filter_layers": "denoise_filter = 1 needs denoise_layers = 1",
+    "demod_layers": "denoise_demodulate = 1 needs denoise_layers = 1",
     "empty_tile": "a tile of the frame holds no samples",
     "no_layer": "no denoise with denoise_layers = 1 since the last resize",
     "stale_guide": "the last denoise ran with denoise_layers = 0",
@@ -40,9 +42,9 @@ REFUSALS = {
     "no_resolve": "no resolve since the last resize",
     "no_upsample": "no upsample since the last resize",
 }
-CALL_REFUSALS = ("tiles", "no_features", "no_samples", "moments_cover", "moments_reject", "not_expected", "one_ray", "filter_layers", "empty_tile", "no_layer",
-                 "stale_guide")
-SWITCHES = ("denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter")      # 0 or 1; a change drops the history
+CALL_REFUSALS = ("tiles", "no_features", "no_samples", "moments_cover", "moments_reject", "not_expected", "one_ray", "filter_layers", "demod_layers", "empty_tile",
+                 "no_layer", "stale_guide")
+SWITCHES = ("denoise_moments", "denoise_resolve", "denoise_layers", "denoise_filter", "denoise_demodulate")      # 0 or 1; a change drops the history
 DROP_RULES = tuple("switch:" + s for s in SWITCHES) + ("history_reset", "resize", "mismatch")
 SIGMA2 = (2.0, 3.0, 0.3, 0.5, 0.5)
 
@@ -97,9 +99,10 @@ class OracleScene:
     def resolved(self, rays, fb, feat):
         return hk_resolve.resolved(self.lo(), rays, fb, feat)
 
-    def upsampled(self, layer, feat_lo, f, rays, sigma):
-        """-> (out, L, hi features)"""
-        return hk_upsample.chain(layer, feat_lo, self._at(f * self.w, f * self.h), rays, f, sigma)[:3]
+    def upsampled(self, layer, feat_lo, f, rays, sigma, demod=False):
+        """-> (out, L, hi features); demod: "denoise_demodulate" at the call"""
+        chain = hk_demod.chain if demod else hk_upsample.chain
+        return chain(layer, feat_lo, self._at(f * self.w, f * self.h), rays, f, sigma)[:3]
 
 
 class BlankScene:
@@ -119,7 +122,7 @@ class BlankScene:
         y[..., 3] = feat[..., 3]
         return y, np.zeros_like(y)
 
-    def upsampled(self, layer, feat_lo, f, rays, sigma):
+    def upsampled(self, layer, feat_lo, f, rays, sigma, demod=False):
         H, W = f * self.h, f * self.w
         return np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32), np.zeros((H, W, 8), np.float32)
 
@@ -128,7 +131,7 @@ class BlankScene:
 class Model:
     def __init__(self, scene, w, h):
         self.scene = scene
-        self.denoise_moments = self.denoise_resolve = self.denoise_layers = self.denoise_filter = 0
+        self.denoise_moments = self.denoise_resolve = self.denoise_layers = self.denoise_filter = self.denoise_demodulate = 0
         self.denoise_reject = self.denoise_ridge = 0.0
         self.denoise_iterations, self.denoise_alpha, self.denoise_sigma = 5, 0.1, hk_denoise.DEFAULT_SIGMA
         self.tiles = False                            # a tile subset is set (kept across a resize)
@@ -140,7 +143,7 @@ class Model:
         self.w, self.h = int(w), int(h)
         self.fb = self.var = self.feat = self.camera = None
         self.pass_kind, self.rays, self.n = "none", 0, None       # n: keeps the caller's count across a resize (new_frame says what it is)
-        self.hist = None                              # dict(cam, c, rec, mom | None, layers)
+        self.hist = None                              # dict(cam, c, rec, mom | None, layers, demod)
         self.guide_feat = None                        # the features behind the last guide
         self.guide_of_layer = False                   # ... and that guide is the layer's
         self._denoised = self._layer = self._stat = self._resolved = self._bg = self._up = None
@@ -214,6 +217,7 @@ class Model:
     def _denoise(self, who, temporal):
         self.log.append(("op", who))
         layers, regress, moments = bool(self.denoise_layers), bool(self.denoise_filter), temporal and bool(self.denoise_moments)
+        demod = bool(self.denoise_demodulate)
         reject = self.denoise_reject if temporal else 0.0
         no = []
         if self.tiles:
@@ -230,6 +234,8 @@ class Model:
             no += [k for k in self._resolve_refusals() if k not in no]
         if regress and not layers:
             no.append("filter_layers")
+        if demod and not layers:
+            no.append("demod_layers")
         if self.ragged() and (self.n < 1).any():
             no.append("empty_tile")
         self._refuse(who, no)
@@ -239,13 +245,16 @@ class Model:
         if self.denoise_resolve or layers:             # vr_resolve first, whatever denoise_resolve says with layers
             y, B = self.scene.resolved(self.rays, fb, feat)
             self._resolved, self._bg = y, B
-            frame = hk_layers.split(y, B, kappa) if layers else y
+            frame = (hk_demod.split(y, B, feat) if demod else hk_layers.split(y, B, kappa)) if layers else y
         if self.ragged():
             v, g = hk_adaptive.prepare(var, feat, hk_adaptive.per_pixel(self.n, self.w, self.h))
         else:
             v, g = hk_denoise.prepare(var, feat, self.n)
+        if demod:                                      # the variance of the divided layer, every pixel with its own tile's count; the guide stays prepare's
+            v = hk_demod.variance(var, feat, hk_adaptive.per_pixel(self.n, self.w, self.h) if self.ragged() else self.n)
         if temporal:
-            if self.hist is not None and ((self.hist["mom"] is not None) != moments or self.hist["layers"] != layers):
+            if self.hist is not None and ((self.hist["mom"] is not None) != moments or self.hist["layers"] != layers or
+                                          self.hist["demod"] != demod):
                 self._drop("mismatch")                # one kind of history cannot continue the other
             h = self.hist
             if moments:
@@ -255,7 +264,7 @@ class Model:
                 (c, rec, stat), mom = hk_temporal.step_reject(self.camera, frame, v, g[..., 3], g[..., 7], self.denoise_alpha, reject, h and (h["cam"], h["c"], h["rec"])), None
             else:
                 (c, rec), stat, mom = hk_temporal.step(self.camera, frame, v, g[..., 3], g[..., 7], self.denoise_alpha, h and (h["cam"], h["c"], h["rec"])), None, None
-            self.hist = dict(cam=self.camera.copy(), c=c, rec=rec, mom=mom, layers=layers)
+            self.hist = dict(cam=self.camera.copy(), c=c, rec=rec, mom=mom, layers=layers, demod=demod)
             self._stat = stat                         # T of the last denoise_temporal, or none
             frame, v = c, np.ascontiguousarray(rec[..., 0])
         if regress:
@@ -265,7 +274,7 @@ class Model:
             for k in range(N):
                 F, v = hk_denoise.atrous(F, v, g, 1 << k, sigma)
         if layers:
-            self._denoised, self._layer = hk_layers.merge(F, B, kappa)
+            self._denoised, self._layer = hk_demod.merge(F, B, feat) if demod else hk_layers.merge(F, B, kappa)
         else:
             self._denoised = np.array(F, np.float32)
         self.guide_feat, self.guide_of_layer = feat, layers
@@ -285,7 +294,10 @@ class Model:
         if self.tiles:
             no.append("tiles")
         self._refuse("upsample", no)
-        self._up = (int(f),) + tuple(self.scene.upsampled(self._layer, self.guide_feat, int(f), int(rays), self.denoise_sigma))
+        demod = bool(self.denoise_demodulate)          # read at the call, whatever made the layer
+        if demod:
+            self.log.append(("op", "upsample_demod"))
+        self._up = (int(f),) + tuple(self.scene.upsampled(self._layer, self.guide_feat, int(f), int(rays), self.denoise_sigma, demod))
 
     def resize(self, w, h):
         self.log.append(("op", "resize"))
@@ -386,13 +398,13 @@ def unchanged(before, after):
 
 # ---- the all-pairs array -------------------------------------------------------------------------------------------------------------------------------------
 FACTORS = (("call", ("denoise", "denoise_temporal")), ("moments", (0, 1)), ("reject", (0.0, 3.0)), ("resolve", (0, 1)), ("layers", (0, 1)), ("filter", (0, 1)),
-           ("ridge", (0.0, 1.0)), ("iterations", (0, 1, 2, 3, 5)), ("frame", ("uniform", "ragged")), ("features", ("stochastic", "expected")),
+           ("demodulate", (0, 1)), ("ridge", (0.0, 1.0)), ("iterations", (0, 1, 2, 3, 5)), ("frame", ("uniform", "ragged")), ("features", ("stochastic", "expected")),
            ("camera", ("fixed", "orbit")), ("shape", ((33, 31), (17, 16), (1, 37))))
 NAMES = tuple(n for n, _ in FACTORS)
 # what the product refuses: each a set of (factor, value) that no accepted row holds together
 FORBIDDEN = ((("filter", 1), ("layers", 0)), (("layers", 1), ("features", "stochastic")), (("resolve", 1), ("features", "stochastic")),
-             (("call", "denoise_temporal"), ("moments", 1), ("reject", 3.0)))
-FORBIDDEN_KINDS = ("filter_layers", "not_expected", "not_expected", "moments_reject")
+             (("call", "denoise_temporal"), ("moments", 1), ("reject", 3.0)), (("demodulate", 1), ("layers", 0)))
+FORBIDDEN_KINDS = ("filter_layers", "not_expected", "not_expected", "moments_reject", "demod_layers")
 
 
 def row_dict(row):
@@ -450,16 +462,31 @@ def covering_array():
     return accepted, refusals
 
 
-PIVOT = dict(call="denoise_temporal", moments=0, reject=3.0, resolve=1, layers=1, filter=0, ridge=0.0, iterations=3, frame="uniform", features="expected",
+PIVOT = dict(call="denoise_temporal", moments=0, reject=3.0, resolve=1, layers=1, filter=0, demodulate=0, ridge=0.0, iterations=3, frame="uniform", features="expected",
              camera="orbit", shape=(33, 31))
 
 
 def factor_pairs():
     """Per factor two accepted rows that differ in that factor alone, at a pivot where the factor is live: everything on, and per factor what it needs --
     no rejection next to the moments, the regression next to the ridge, no layers next to the resolve, no resolve and no layers next to a stochastic pass, iterations 2 against 3."""
+    return _pairs_at(PIVOT, NAMES)
+
+
+DEMODULATED = ("call", "moments", "reject", "filter", "ridge", "iterations", "frame", "camera", "shape")
+
+
+def factor_pairs_demodulated():
+    """The same at the pivot with "demodulate" 1, for every factor that stays accepted there with layers 1 (the resolve runs whatever its switch says, a
+    stochastic pass and no layers are refused): the history, the rejection, the moments, the regression and the counts of a ragged frame on the divided layer."""
+    return _pairs_at(dict(PIVOT, demodulate=1), DEMODULATED)
+
+
+def _pairs_at(pivot, names):
     out = {}
     for name, values in FACTORS:
-        base = dict(PIVOT)
+        if name not in names:
+            continue
+        base = dict(pivot)
         a, b = values[0], values[1]
         if name == "moments":
             base["reject"] = 0.0
@@ -478,21 +505,23 @@ def factor_pairs():
 
 
 # ---- random call sequences -----------------------------------------------------------------------------------------------------------------------------------
-SEEDS = (31, 32, 33, 34, 35, 36, 37, 38, 39, 40)               # replaced until test_pipeline_model_host.py counted every kind twice
+SEEDS = (41, 42, 43, 44, 45, 59, 149, 156, 175, 351)             # replaced until test_pipeline_model_host.py counted every kind twice
 LENGTH = 25
 SIZES = ((33, 31), (17, 16))
-OP_KINDS = ("set", "frame", "features", "denoise", "denoise_temporal", "history_reset", "resolve", "upsample", "resize", "tiles")
+OP_KINDS = ("set", "frame", "features", "denoise", "denoise_temporal", "history_reset", "resolve", "upsample", "upsample_demod", "resize", "tiles")
+# (upsample_demod: an upsample that ran with "denoise_demodulate" = 1 at its call, logged besides "upsample")
 
 
 REPAIRS = {"tiles": ("tiles", ()), "no_features": ("features", "expected", 2), "not_expected": ("features", "expected", 2), "one_ray": ("features", "expected", 2),
            "no_samples": ("frame", "uniform"), "moments_cover": ("frame", "uniform"), "empty_tile": ("frame", "uniform"), "moments_reject": ("set", "denoise_reject", 0.0),
-           "filter_layers": ("set", "denoise_layers", 1), "no_layer": ("set", "denoise_layers", 1), "stale_guide": ("denoise",)}
+           "filter_layers": ("set", "denoise_layers", 1), "demod_layers": ("set", "denoise_layers", 1), "no_layer": ("set", "denoise_layers", 1), "stale_guide": ("denoise",)}
 
 
 def sequence(seed, length=LENGTH):
     """About `length` operations drawn by numpy's Mersenne twister of `seed`; every one is a call the header defines.  Drawn one by one and blindly, most calls
     would be refused for the same two reasons and few histories would live long enough to be dropped.  So the draw is of short motifs -- one blind operation; a
-    run of temporal frames; a switch flipped between two temporal calls; a reset; a resize; a temporal call without rejection after one with it; each refusal's own preparation -- whose parameters, order and
+    run of temporal frames; a switch flipped between two temporal calls; a reset; a resize; a temporal call without rejection after one with it; a layer upsampled under the other
+    value of "denoise_demodulate" than the one that made it; each refusal's own preparation -- whose parameters, order and
     neighbours are random, and it runs a Model over a StubTracer alongside: `call` answers a refusal with the call that lifts its first reason and tries again,
     so that the refusal, the repair and the accepted call all stand in the sequence.  A motif that has begun is finished, repairs included: a sequence has length .. length + 10
     operations."""
@@ -588,6 +617,19 @@ def sequence(seed, length=LENGTH):
         emit(("set", "denoise_layers", pick((0, 0, 1))))
         call(("denoise",))
 
+    def demod_layers():
+        emit(("set", "denoise_demodulate", 1))
+        emit(("set", "denoise_layers", pick((0, 0, 1))))
+        call(("denoise",))
+
+    def demod_upsample():
+        made_with = pick((0, 1))                      # the layer made under one value of the setting, upsampled under the other: the call's value counts
+        emit(("set", "denoise_layers", 1))
+        emit(("set", "denoise_demodulate", made_with))
+        call(pick((("denoise",), ("denoise_temporal",))))
+        emit(("set", "denoise_demodulate", 1 - made_with))
+        emit(("upsample", pick((2, 3)), 2))
+
     def tiles():
         emit(("tiles", (0, 1)))
         emit(pick((("denoise",), ("resolve",), ("upsample", 2, 2), ("frame", "uniform"))))
@@ -597,7 +639,8 @@ def sequence(seed, length=LENGTH):
         emit(("features", "stochastic", 2))
         emit(pick((("denoise",), ("denoise_temporal",), ("resolve",))))
 
-    motifs = (blind, blind, blind, blind, temporal_run, flip, flip, reset, resize, moments_reject, statistic_goes, one_ray, empty_tile, stale_guide, filter_layers, tiles, stochastic)
+    motifs = (blind, blind, blind, blind, temporal_run, flip, flip, reset, resize, moments_reject, statistic_goes, one_ray, empty_tile, stale_guide, filter_layers, demod_layers,
+              demod_upsample, tiles, stochastic)
     while len(ops) < length:
         pick(motifs)()
     return ops

@@ -101,6 +101,15 @@ def test_no_device_fails_loudly():
     ins[3] = C.addressof(a)                                                                      # half a history
     assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3 and b"history" in lib.vr_last_error()
     ins[3] = None
+    par[5], par[35] = 1.0, 1.0                                                                   # demod: 0 or 1, and 1 only where a DEMOD instance exists
+    for stage in (0, 4, 5):
+        assert lib.vr_filter_probe(C.c_void_p(1), stage, 4, 4, ins, outs, par) == 2 and b"no HIP device" in lib.vr_last_error(), stage
+    for stage in (1, 2, 3, 6):
+        assert lib.vr_filter_probe(C.c_void_p(1), stage, 4, 4, ins, outs, par) == 3 and b"demod = 1 goes with" in lib.vr_last_error(), stage
+    for bad in (2.0, -1.0, 0.5):
+        par[35] = bad
+        assert lib.vr_filter_probe(C.c_void_p(1), 4, 4, 4, ins, outs, par) == 3 and b"demod must be 0 or 1" in lib.vr_last_error(), bad
+    par[5], par[35] = 2.0, 0.0
     par[20] = float("nan")
     assert lib.vr_filter_probe(C.c_void_p(1), 2, 4, 4, ins, outs, par) == 3 and b"not finite" in lib.vr_last_error()
     hs = C.c_void_p()

@@ -3,12 +3,15 @@ and hk_moments offer it -- held to the stage's float64 statement at the toleranc
 running: how many pixels have a history, were rejected, took one, two or four taps, dropped a column.  tests/test_gpu_filter_probe.py then compares the kernels with
 these same host results bit for bit; no case reaches a device before it passes here.
 
-Non-finite cases are not compared with float64; they are held to the containment the headers state."""
+Non-finite cases are not compared with float64; they are held to the containment the headers state.  The group "demod" (the DEMOD instances of vr_demod.h) is
+held to hk_demod's float64 statements at bounds derived from the header's operation counts, not recorded ones; its overflow cases are compared on their finite
+words, and its NaN and inf albedo words must stay in their own channel."""
 import numpy as np
 import pytest
 
 import filter_cases as fc
 import hk_adaptive as ha
+import hk_demod as hd
 import hk_denoise
 import hk_layers as hl
 import hk_moments as hm
@@ -61,7 +64,10 @@ def test_the_catalogue_holds_what_the_kernels_may_be_handed():
                 if a is None:
                     continue
                 if key in ("feat", "guide", "glo", "feat_hi"):
-                    assert np.isfinite(a).all() and (a[..., 3] >= 0).all() and (a[..., 3] <= 1).all() and (a[..., 7] >= 0).all(), (c.id, key)
+                    fourth = key == "feat" and c.nonfinite and c.par.get("demod") == 1 and c.stage in ("prepare", "split", "merge")
+                    if fourth:                           # the fourth kind: a NaN or +inf albedo word of a per-pixel DEMOD stage, and no other word of the features
+                        assert group == "demod" and not np.isneginf(a).any()
+                    assert np.isfinite(a[..., 3:] if fourth else a).all() and (a[..., 3] >= 0).all() and (a[..., 3] <= 1).all() and (a[..., 7] >= 0).all(), (c.id, key)
                 elif key == "hist":
                     assert np.isfinite(a[0]).all() and np.isfinite(a[2]).all() and (a[2][..., 1] >= 0).all() and (a[2][..., 3] >= 0).all(), c.id
                     assert all(np.isfinite(p).all() for p in a[1:]), c.id
@@ -488,6 +494,308 @@ def test_upsample(name):
     assert near.mean() <= 0.01
     assert np.abs(o - so)[~near][:, :3].max() <= _recorded(test_upsample_host.RECORDED, 0) and np.abs(Lh - sl)[~near][:, :3].max() <= _recorded(test_upsample_host.RECORDED, 1)
     assert (De > hu.MIN_WEIGHT).any() and ((De <= hu.MIN_WEIGHT) & (ghi[..., 3] > 0)).any() or min(c.w, c.h) == 1      # both tiers
+
+
+# ---- the DEMOD instances (vr_demod.h) -----------------------------------------------------------------------------------------------------------------------
+# Every bound below is derived, not recorded: per output word, the number of float32 roundings in vr_demod.h's statement of it, times 2^-24, times the float64 sum
+# of the magnitudes of the statement's terms at that pixel (divided or multiplied by d as the statement is), plus 2^-149 for a result in the subnormal range.
+#   split    S = (y - (1 - kappa) B) / d: 1 - kappa, its product with B, the difference, the quotient                       4 roundings of (|y| + |1 - kappa| |B|) / d
+#   merge    L = (F (kappa / F.a)) d: the ratio, two products                                                              3 roundings of |F| (kappa / F.a) d
+#            out = max_(G + L, 0): G's two, L's three, the sum (max_ moves nothing apart)                                  6 roundings of |G| + |L|
+#   v        test_demod_host.py's 2^-21, relative, per pixel
+#   upsample _upsample_bound below
+U = 2.0 ** -24
+TINY = 2.0 ** -149
+FLT_MAX = float(np.finfo(np.float32).max)
+_WORST = {}                                              # stage -> (the largest |host - float64| / bound over the finite cases run so far, the case)
+
+
+def _note(stage, case, err, bound):
+    ratio = float((err / bound).max())
+    if ratio > _WORST.get(stage, (0.0, None))[0]:
+        _WORST[stage] = (ratio, case.id)
+    print("%-34s worst |host - float64| %.3e, %.3f of its derived bound (%.3e there)" % (case.id, float(err.max()), ratio, float(bound.reshape(-1)[np.argmax(err / bound)])))
+    return ratio
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same_or_nan(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return bool(((_bits(a) == _bits(b)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def _census(feats):
+    """how many covered pixels hold each value of ALBEDOS (bit for bit: the two zeros apart) in some channel, over the feature buffers of a case"""
+    return [sum(int(((_bits(f[..., 0:3]) == _bits(a)).any(axis=-1) & (f[..., 3] > 0)).sum()) for f in feats) for a in fc.ALBEDOS]
+
+
+def _plain_twin(c):
+    """the case with demod 0, through the catalogue's own dispatch"""
+    return fc._HOST[c.stage](fc.Case(c.stage, c.name + "-plain", c.w, c.h, c.inp, dict(c.par, demod=0), scene=c.scene, nonfinite=c.nonfinite))
+
+
+def _upsample_bound(L, glo, ghi, f, sigma):
+    """The derived bound of the demodulated upsampling's hi layer and of vr_upsample.h's C before it, per word: -> (bound of L_p.rgb [H][W][3], D_e, D_s).
+    The statement is a ratio of two sums over up to 16 taps, C = sum w_q c_q / sum w_q kappa_q with c_q = L_q.rgb / d_q, then L_p = (kappa_p C) d_p.
+    Values: the tap's division, its product with the weight, at most 16 additions; the same for the denominator's product and additions; the quotient, the
+    product with kappa_p, the product with d_p: 38 roundings of M = sum w_q |c_q| / D (times kappa_p d_p).
+    Weights: a relative error delta_q of w_q moves C by at most delta_q w_q (|c_q| + |C|) / D -- it is in the numerator and in the denominator.  delta_q in
+    roundings: the spline factor b(a) is at most 9 operations on intermediates of up to 13/6 against a result of 1/6 or more (b_1, b_2; b_0 and b_3 are
+    products), 117, and a = r / 2f is one rounding that (1 - a)^3 amplifies by 3a / (1 - a) <= 15 at a = 5/6 (r / 4 and r / 8 are exact): 132 per axis, 265 for
+    s = b_x b_y.  Where both coverages are positive e = w_n w_d w_a follows (two products, and one for s e): w_d = exp_(-x_d), x_d of 4 roundings, and
+    w_a = exp_(-x_a), x_a of 7 (three differences, their squares, two sums, sigma^2, the quotient): an argument's relative error k comes out as k x, and exp_
+    itself is good to 2; w_n = pow_(dot, sigma_n) = exp_(sigma_n log_(dot)): the dot product of two guides' normals is 5 roundings of magnitude 1 against dot,
+    6 sigma_n / dot with the clamp, then 3 x_n for the logarithm's product and 2.  A dot below 6 x 2^-24 has no relative bound: there w_n is anywhere in
+    [0, (12 x 2^-24)^sigma_n], an absolute error of the weight.  Every weight and every product of the sums may besides underflow: 2^-149 absolutely each."""
+    L, glo, ghi = (np.asarray(a, np.float64) for a in (L, glo, ghi))
+    sn, sd, sa = (float(np.float32(sigma[i])) for i in (1, 2, 4))
+    h, w = L.shape[:2]
+    H, W = f * h, f * w
+    dlo, dhi = hd.spec_divisor(glo), hd.spec_divisor(ghi)
+    c = L[..., :3] / dlo
+    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    x0, y0 = np.floor_divide(2 * xs + 1 - f, 2 * f), np.floor_divide(2 * ys + 1 - f, 2 * f)
+    bx = hu.spec_spline((2 * xs + 1 - f - 2 * f * x0) / (2.0 * f))
+    by = hu.spec_spline((2 * ys + 1 - f - 2 * f * y0) / (2.0 * f))
+    zero3 = np.zeros((H, W, 3))
+    acc = {t: dict(N=zero3.copy(), M=zero3.copy(), D=np.zeros((H, W)), E=zero3.copy(), Ew=np.zeros((H, W)), A=zero3.copy()) for t in ("e", "s")}
+    for j in range(4):
+        for i in range(4):
+            lx, ly = x0 - 1 + i, y0 - 1 + j
+            ok = (lx >= 0) & (lx < w) & (ly >= 0) & (ly < h)
+            cx, cy = np.clip(lx, 0, w - 1), np.clip(ly, 0, h - 1)
+            gq, cq, kq = glo[cy, cx], c[cy, cx], L[cy, cx][..., 3]
+            s = np.where(ok, bx[..., i] * by[..., j], 0.0)
+            both = (ghi[..., 3] > 0) & (gq[..., 3] > 0)
+            flat = ~ghi[..., 4:7].any(axis=-1) | ~gq[..., 4:7].any(axis=-1)
+            dot = np.clip((ghi[..., 4:7] * gq[..., 4:7]).sum(axis=-1), 0.0, 1.0)
+            loose = both & ~flat & (dot < 6 * U)
+            with np.errstate(divide="ignore"):
+                xn = np.where(flat | loose, 0.0, -sn * np.log(np.where(dot > 0, dot, 1.0)))
+            xd = np.abs(ghi[..., 7] - gq[..., 7]) / (sd * np.maximum(ghi[..., 7], gq[..., 7]) + float(np.float32(1e-6)))
+            da = ghi[..., 0:3] - gq[..., 0:3]
+            xa = (da * da).sum(axis=-1) / (sa * sa)
+            delta_e = 3 + np.where(flat | loose, 0.0, 6 * sn / np.where(dot > 0, dot, 1.0) + 3 * xn + 2) + (4 * xd + 2) + (7 * xa + 2)
+            e = hu.spec_edge(ghi, gq, sigma)
+            for t, wq, delta, absolute in (("e", s * e, 265 + np.where(both, delta_e, 0.0), np.where(loose, s * (12 * U) ** sn, 0.0) + TINY), ("s", s, 265.0, TINY)):
+                a = acc[t]
+                a["N"] += wq[..., None] * cq
+                a["M"] += wq[..., None] * np.abs(cq)
+                a["D"] += wq * kq
+                a["E"] += ((delta * U * wq + absolute) * ok)[..., None] * np.abs(cq)      # the weight's error against the tap's value ...
+                a["Ew"] += (delta * U * wq + absolute) * ok                                  # ... and against C
+                a["A"] += TINY * ok[..., None]
+    De, Ds = acc["e"]["D"], acc["s"]["D"]
+    first, second = De > hu.MIN_WEIGHT, Ds > hu.MIN_WEIGHT
+    bound = zero3.copy()
+    for t, take in (("e", first), ("s", second & ~first)):
+        a = acc[t]
+        D = np.where(take, a["D"], 1.0)[..., None]
+        C = np.abs(a["N"]) / D
+        b = (38 * U * a["M"] + a["E"] + a["Ew"][..., None] * C + a["A"] * (1.0 + C)) / D
+        bound = np.where(take[..., None], b, bound)
+    k = ghi[..., 3]
+    return bound * (k[..., None] * dhi) + TINY, De, Ds
+
+
+@pytest.mark.parametrize("case_id", [c.id for c in fc.cases("demod")])
+def test_demod(case_id):
+    c = next(x for x in fc.cases("demod") if x.id == case_id)
+    out = fc.host(c)
+    poisoned = c.name.endswith("nan-inf-albedo")
+    assert c.par["demod"] == 1 and (c.nonfinite or all(np.isfinite(a).all() for a in out.values())), c.id
+    feats = [c.inp["glo"], c.inp["feat_hi"]] if c.stage == "upsample" else [c.inp["feat"]]
+    census = _census(feats)
+    assert min(census) >= 8, (c.id, census)                                      # every value of ALBEDOS on covered pixels
+    # with demod 0 the catalogue runs the plain host function, on these inputs too
+    plain = _plain_twin(c)
+    with np.errstate(all="ignore"):
+        if c.stage == "split":
+            direct = {"S": hl.split(c.inp["y"], c.inp["B"], np.ascontiguousarray(c.inp["feat"][..., 3]))}
+        elif c.stage == "merge":
+            direct = dict(zip(("out", "L"), hl.merge(c.inp["F"], c.inp["B"], np.ascontiguousarray(c.inp["feat"][..., 3]))))
+        elif c.stage == "prepare":
+            direct = fc._prepare_host(fc.Case("prepare", "direct", c.w, c.h, c.inp, {"n": c.par["n"]}))
+        else:
+            f = c.par["f"]
+            ghi = hu.guide(c.inp["feat_hi"])
+            B, _ = hr.prepare(fc.oracle(c.scene, f * c.w, f * c.h), c.par["rays"], np.zeros((f * c.h, f * c.w, 4), np.float32))
+            direct = dict(zip(("out", "L"), hu.upsample(c.inp["L"], c.inp["glo"], ghi, B, f, c.par["sigma"])))
+    assert set(plain) == set(direct) == set(out) and all(_same_or_nan(plain[k], direct[k]) for k in plain), c.id
+    # pixels without coverage hold albedo words and come out as the plain stage's, bit for bit
+    fo = feats[-1]
+    bare = (fo[..., 3] == 0) & (fo[..., 0:3] != 0).any(axis=-1)
+    assert bare.sum() >= 8 and all(_same_or_nan(out[k][bare], plain[k][bare]) for k in out), (c.id, int(bare.sum()))
+    if c.stage != "upsample" and c.par.get("n") != 1:
+        assert any(not _same_or_nan(out[k], plain[k]) for k in out if k != "guide"), c.id
+    _DEMOD_CHECKS[c.stage](c, out, plain, poisoned)
+
+
+def _poison(c, twin_name):
+    """a poisoned case: (the features before the poison's host outputs, NaN mask, inf mask, covered)"""
+    twin = next(x for x in fc.cases("demod") if x.name == twin_name)
+    feat = c.inp["feat"]
+    is_nan, is_inf = np.isnan(feat[..., 0:3]), np.isposinf(feat[..., 0:3])
+    covered = feat[..., 3] > 0
+    assert np.isfinite(feat[..., 3:]).all() and not np.isneginf(feat).any()
+    for m in (is_nan, is_inf):                                                   # on covered and on uncovered pixels, one channel of a pixel at most
+        assert (m.sum(axis=-1) <= 1).all() and (m.any(axis=-1) & covered).sum() >= 8 and (m.any(axis=-1) & ~covered).sum() >= 4, c.id
+    return twin, is_nan, is_inf, covered
+
+
+def _demod_split(c, out, plain, poisoned):
+    S, y, B, feat = out["S"], c.inp["y"], c.inp["B"], c.inp["feat"]
+    kappa = feat[..., 3]
+    assert _same(S[..., 3], kappa)
+    if poisoned:
+        twin, is_nan, is_inf, covered = _poison(c, "demod-albedos")
+        clean = fc.host(twin)["S"][..., :3]
+        hit = (is_nan | is_inf) & covered[..., None]
+        assert np.isnan(S[..., :3][is_nan & covered[..., None]]).all() and not np.isnan(S[..., :3][~(is_nan & covered[..., None])]).any()      # that channel, and no other
+        assert (S[..., :3][is_inf & covered[..., None]] == 0).all()              # an infinite albedo divides to 0
+        assert _same(S[..., :3][~hit], clean[~hit])
+        return
+    with np.errstate(all="ignore"):
+        want = hd.spec_split(y, B, feat)[..., :3]
+        d = hd.spec_divisor(feat)
+        bound = 4 * U * (np.abs(y[..., :3].astype(np.float64)) + np.abs((1.0 - kappa.astype(np.float64))[..., None] * B[..., :3])) / d + TINY
+    fin = np.isfinite(S[..., :3])
+    if c.nonfinite:                                                              # the quotient overflows: inf exactly where the float64 quotient leaves float32, by its sign
+        over = np.abs(want) > FLT_MAX * (1 + 2 * U)
+        assert not np.isnan(S).any() and over.sum() > 100 and fin.sum() > 100 and np.array_equal(~fin, over) and (np.sign(S[..., :3][over]) == np.sign(want[over])).all()
+    else:
+        assert fin.all()
+    err = np.abs(S[..., :3] - want)
+    assert _note("split", c, err[fin], bound[fin]) <= 1.0, c.id
+    if c.name == "demod-subnormal-quotient":
+        sub = (S[..., :3] != 0) & (np.abs(S[..., :3]) < SUBNORMAL)
+        assert (sub & (feat[..., 0:3] == np.float32(1e5))).sum() >= 32 and (np.abs(y[..., :3]) >= SUBNORMAL * 0.8).all(), int(sub.sum())      # not flushed
+    elif not c.nonfinite:
+        assert (S[..., :3] < 0).mean() > 0.1 and (S[..., :3] > 0).mean() > 0.1   # signed
+
+
+def _demod_prepare(c, out, plain, poisoned):
+    v, g = out["v"], out["guide"]
+    S, feat, counts, n = c.inp["S"], c.inp["feat"], c.inp.get("counts"), c.par["n"]
+    n_px = np.full((c.h, c.w), n) if counts is None else ha.per_pixel(counts, c.w, c.h)
+    assert _same_or_nan(g, plain["guide"])                                       # the guide stays prepare's
+    with np.errstate(all="ignore"):
+        scale = np.where(n_px >= 2, n_px / np.maximum(n_px - 1.0, 1.0), 0.0).astype(np.float32)
+        var = np.where((n_px >= 2)[..., None], S * scale[..., None], np.float32(0.0))
+        want = hd.spec_variance(var, feat, n_px)
+        s2 = want * n_px                                                         # the statement squares before it divides: (s * s) / float(n)
+    if poisoned:
+        twin, is_nan, is_inf, covered = _poison(c, "demod-counts")
+        nan_px = (is_nan & covered[..., None]).any(axis=-1)
+        assert np.isnan(v[nan_px]).all() and np.isfinite(v[~nan_px]).all()       # NaN albedo, covered: a NaN v there and nowhere else (var = 0 too: 0 / NaN)
+        clean = fc.host(twin)
+        assert _same(v[~covered], plain["v"][~covered])
+        untouched = ~((is_nan | is_inf).any(axis=-1) & covered)
+        assert _same(v[untouched], clean["v"][untouched])
+        words = np.ones(g.shape, bool)
+        words[..., 0:3] = ~(is_nan | is_inf)
+        assert _same(g[words], clean["guide"][words])                            # the guide copies the word, and no other word moves
+        inf_px = (is_inf & covered[..., None]).any(axis=-1) & (n_px >= 2)        # an infinite albedo: that channel's share is 0
+        assert np.abs(v[inf_px] - want[inf_px]).max() <= 2.0 ** -21 * want[inf_px].max() and (v[inf_px] < clean["v"][inf_px]).any()
+        return
+    assert (v[n_px < 2] == 0).all() and (n_px < 2).any() == (n == 1 or counts is not None)      # n = 1: var = 0 and v = 0
+    fin = np.isfinite(v)
+    if c.nonfinite:
+        with np.errstate(all="ignore"):
+            over = np.isinf(var[..., :3]).any(axis=-1) | (s2 > FLT_MAX * (1 - 2.0 ** -20))
+            sure = np.isinf(var[..., :3]).any(axis=-1) | (s2 > FLT_MAX * (1 + 2.0 ** -20))
+        assert not np.isnan(v).any() and np.isposinf(v[~fin]).all() and sure.sum() > 100 and fin.sum() > 100
+        assert (~fin)[sure].all() and over[~fin].all()                           # inf where the variance or the square leaves float32, and nowhere else
+    else:
+        assert fin.all()
+    with np.errstate(invalid="ignore"):
+        err, bound = np.abs(v - want)[fin], (2.0 ** -21 * want + TINY)[fin]
+    assert _note("prepare", c, err, bound) <= 1.0, c.id
+    covered = feat[..., 3] > 0
+    assert n == 1 or not _same(v[covered], plain["v"][covered])
+    if c.name == "demod-tiny-n2":
+        assert ((v > 0) & (v < SUBNORMAL)).sum() > 100, c.id
+    if counts is not None:
+        assert (counts == 1).any() and (n_px == 1).sum() > 100 and (v[(n_px >= 2) & covered] > 0).sum() > 100
+
+
+def _demod_merge(c, out, plain, poisoned):
+    o, L, F, B, feat = out["out"], out["L"], c.inp["F"], c.inp["B"], c.inp["feat"]
+    kappa = feat[..., 3]
+    assert _same(o[..., 3], kappa) and _same(L[..., 3], kappa)
+    if poisoned:
+        twin, is_nan, is_inf, covered = _poison(c, "demod-alpha-differs")
+        clean = fc.host(twin)
+        nan_w = is_nan & covered[..., None]
+        hit = (is_nan | is_inf) & covered[..., None]
+        for a, b in ((o, clean["out"]), (L, clean["L"])):
+            assert np.isnan(a[..., :3][nan_w]).all() and not np.isnan(a[..., :3][~hit]).any() and _same(a[..., :3][~hit], b[..., :3][~hit])
+        inf_w = is_inf & covered[..., None]
+        assert not np.isfinite(L[..., :3][inf_w]).any()                          # F d: inf by F's sign, NaN where F is 0
+        return
+    with np.errstate(all="ignore"):
+        so, sl = hd.spec_merge(F, B, feat)
+        G = np.abs((1.0 - kappa.astype(np.float64))[..., None] * B[..., :3])
+        bl = 3 * U * np.abs(sl[..., :3]) + TINY
+        bo = 6 * U * (G + np.abs(sl[..., :3])) + TINY
+    fl, fo = np.isfinite(L[..., :3]), np.isfinite(o[..., :3])
+    if c.nonfinite:                                                              # the remodulation overflows
+        over = np.abs(sl[..., :3]) > FLT_MAX * (1 + 4 * U)
+        assert not np.isnan(L).any() and not np.isnan(o).any() and over.sum() > 100 and fl.sum() > 100
+        assert (~fl)[over].all() and (np.abs(sl[..., :3])[~fl] > FLT_MAX * (1 - 4 * U)).all()
+        assert (np.sign(L[..., :3][over]) == np.sign(sl[..., :3][over])).all() and (o[..., :3][over & (sl[..., :3] < 0)] == 0).all() and np.isposinf(o[..., :3][over & (sl[..., :3] > 0)]).all()
+    else:
+        assert fl.all() and fo.all()
+    assert (o[..., :3] >= 0).all()
+    assert _note("merge", c, np.abs(L[..., :3] - sl[..., :3])[fl], bl[fl]) <= 1.0 and _note("merge", c, np.abs(o[..., :3] - so[..., :3])[fo & fl], bo[fo & fl]) <= 1.0, c.id
+    if c.name == "demod-alpha-is-kappa":
+        assert _same(F[..., 3], kappa)
+    elif c.name == "demod-alpha-differs":
+        assert ((F[..., 3] <= hl.MIN_WEIGHT) & (kappa > 0)).sum() > 100 and ((F[..., 3] > hl.MIN_WEIGHT) & (F[..., 3] != kappa)).sum() > 100
+
+
+def _demod_upsample(c, out, plain, poisoned):
+    f = c.par["f"]
+    L, glo = c.inp["L"], c.inp["glo"]
+    ghi = hu.guide(c.inp["feat_hi"])
+    B, _ = hr.prepare(fc.oracle(c.scene, f * c.w, f * c.h), c.par["rays"], np.zeros((f * c.h, f * c.w, 4), np.float32))
+    o, Lh = out["out"], out["L"]
+    assert np.isfinite(c.inp["feat_hi"]).all() and np.isfinite(glo).all() and np.isfinite(L).all()      # no non-finite word goes into this stage
+    assert (o[..., :3] >= 0).all() and _same(o[..., 3], ghi[..., 3]) and _same(Lh[..., 3], ghi[..., 3])
+    so2, sl2 = hd.upsample(L, glo, ghi, B, f, c.par["sigma"], staged=True)       # the kernel's window holds the same values
+    assert _same(o, so2) and _same(Lh, sl2)
+    rep = np.repeat(np.repeat(glo, f, axis=0), f, axis=1)
+    equal = (ghi.view(np.uint32) == rep.view(np.uint32)).all(axis=-1) & (ghi[..., 3] > 0)
+    assert equal.sum() >= 5, (c.id, int(equal.sum()))                            # the existing checkerboard: a hi guide equal to the lo tap's under it
+    none = ghi[..., 3] == 0
+    assert _same(o[none][:, :3], B[none][:, :3]) and not Lh[none].any()
+    so, sl = hd.spec_upsample(L, glo, ghi, B, f, c.par["sigma"])
+    bound, De, Ds = _upsample_bound(L, glo, ghi, f, c.par["sigma"])
+    near = (np.abs(De - hu.MIN_WEIGHT) < 1e-3 * hu.MIN_WEIGHT) | (np.abs(Ds - hu.MIN_WEIGHT) < 1e-3 * hu.MIN_WEIGHT)
+    assert near.mean() <= 0.01, (c.id, float(near.mean()))                       # the float64 statement alone stays inside the cap
+    k = ghi[..., 3].astype(np.float64)
+    G = np.abs((1.0 - k)[..., None] * B[..., :3])
+    bo = bound + 3 * U * (G + np.abs(sl[..., :3])) + TINY                        # G's two roundings and the sum's
+    assert _note("upsample", c, np.abs(Lh[..., :3] - sl[..., :3])[~near], bound[~near]) <= 1.0 and _note("upsample", c, np.abs(o[..., :3] - so[..., :3])[~near], bo[~near]) <= 1.0, c.id
+    covered = ghi[..., 3] > 0
+    assert not _same(Lh[covered], plain["L"][covered])
+    assert ((De > hu.MIN_WEIGHT) & covered).any() and ((De <= hu.MIN_WEIGHT) & (Ds > hu.MIN_WEIGHT) & covered).any()      # both tiers
+
+
+_DEMOD_CHECKS = {"split": _demod_split, "prepare": _demod_prepare, "merge": _demod_merge, "upsample": _demod_upsample}
+
+
+def test_demod_worst_errors_are_printed():
+    """per stage, the worst host-against-float64 error of the finite words of the group as a share of its derived bound (collected by test_demod above)"""
+    if not _WORST:
+        for c in fc.cases("demod"):
+            test_demod(c.id)
+    for stage in ("split", "prepare", "merge", "upsample"):
+        print("demod %-8s worst error / derived bound %.3f (%s)" % ((stage,) + _WORST[stage]))
+        assert _WORST[stage][0] <= 1.0
 
 
 # ---- adaptive error ---------------------------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,10 @@
 """GPU: every image-space kernel of vr_filters.hip, one launcher at a time through vr_filter_probe, on the crafted frames of tests/filter_cases.py against the
 host build of the same header, bit for bit -- the frames tests/test_filter_cases_host.py holds to the float64 statements on the CPU first: zero and over-unit
 normals, depth 0, colours from 1e-6 to 1e5, subnormal and overflowing variances, reprojections onto the frame's edge and behind the camera, histories of 2^20
-frames, singular regression windows, NaN and inf texels.  Then two chains in which the device is fed its own outputs stage by stage, and vr_denoise on a rendered
-frame reproduced by the probe's prepare and atrous from the renderer's read-backs: the hook runs the product's launches."""
+frames, singular regression windows, NaN and inf texels; and, with demod = 1, the DEMOD instances of vr_demod.h on albedo words at and around the floor, above 1,
+negative, subnormal, NaN and inf.  Then three chains in which the device is fed its own outputs stage by stage (the third demodulated), and vr_denoise on a
+rendered frame reproduced by the probe's prepare and atrous from the renderer's read-backs -- and, demodulated, on a ragged frame through split, prepare with
+counts, atrous and merge: the hook runs the product's launches."""
 import numpy as np
 import pytest
 
@@ -146,6 +148,109 @@ def test_the_regression_chain_fed_its_own_outputs():
     bad = _compare(end, du, qu)
     assert not bad, "\n".join(bad)
     assert np.isfinite(qu["out"]).all() and np.abs(qu["L"][..., :3]).max() > 1e-3 and not _same(qm["out"], fb)
+
+
+def test_the_demodulated_chain_fed_its_own_outputs():
+    """the regression chain again on c3env at 17x16, upsampled by 2, with demod = 1 in split, prepare, merge and upsample and the albedo words of the lo features
+    drawn from the catalogue's finite ALBEDOS (the hi features are the catalogue's demodulated upsample case's): the history, the regression and the taps read the
+    divided layer the device's own split wrote, and the end equals the host chain bit for bit"""
+    w, h, f = 17, 16, 2
+    rc = next(x for x in fc.cases("resolve") if (x.scene, x.w, x.h) == ("c2", w, h))                 # (its frame and coverage, under c3env's sky)
+    uc = next(x for x in fc.cases("demod") if x.stage == "upsample" and (x.scene, x.w, x.h, x.par["f"]) == ("c3env", w, h, f))
+    _, S0, _ = fc.frame(w, h, seed=13)
+    fb, feat = rc.inp["fb"], rc.inp["feat"].copy()
+    feat[..., 0:3] = np.random.default_rng(78).choice(fc.ALBEDOS, (h, w, 3))
+    demod = {"demod": 1}
+    r = _hip("c3env", w, h)
+    d, q = _chain_step(r, "resolve", "demod-chain", w, h, {"fb": fb, "feat": feat}, {"fb": fb, "feat": feat}, rc.par, scene="c3env")
+    ds, qs = _chain_step(r, "split", "demod-chain", w, h, {"y": d["y"], "B": d["B"], "feat": feat}, {"y": q["y"], "B": q["B"], "feat": feat}, demod)
+    dp, qp = _chain_step(r, "prepare", "demod-chain", w, h, {"S": S0, "feat": feat}, {"S": S0, "feat": feat}, {"n": 4, "demod": 1})
+    cur = fc.orbit_camera(11.0, height=0.3)
+    hist = fc.history(np.random.default_rng(77), cur, fc.orbit_camera(10.0, height=0.25), np.ascontiguousarray(qp["guide"][..., 3]), np.ascontiguousarray(qp["guide"][..., 7]), w, h, False)
+    par = {"cur": fc.f32(cur), "alpha": 0.1, "tau": 0.0, "form": "plain", "sigma": fc.SIGMA}
+    dt, qt = _chain_step(r, "temporal", "demod-chain", w, h, {"color": ds["S"], "v": dp["v"], "guide": dp["guide"], "hist": hist},
+                         {"color": qs["S"], "v": qp["v"], "guide": qp["guide"], "hist": hist}, par)
+    assert (qt["record"][..., 1] > 1).sum() > 20
+    par = {"ridge": 0.01, "sigma": fc.SIGMA}
+    dr, qr = _chain_step(r, "regress", "demod-chain", w, h, {"S": dt["color"], "guide": dp["guide"]}, {"S": qt["color"], "guide": qp["guide"]}, par)
+    dm, qm = _chain_step(r, "merge", "demod-chain", w, h, {"F": dr["F"], "B": d["B"], "feat": feat}, {"F": qr["F"], "B": q["B"], "feat": feat}, demod)
+    du, qu = _chain_step(r, "upsample", "demod-chain", w, h, {"L": dm["L"], "glo": dp["guide"], "feat_hi": uc.inp["feat_hi"]},
+                         {"L": qm["L"], "glo": qp["guide"], "feat_hi": uc.inp["feat_hi"]}, uc.par, scene="c3env")
+    r.close()
+    end = fc.Case("upsample", "demod-chain-end", w, h, {})
+    bad = _compare(end, du, qu) + _compare(end, dm, qm)
+    assert not bad, "\n".join(bad)
+    assert uc.par["demod"] == 1 and np.isfinite(qu["out"]).all() and np.abs(qu["L"][..., :3]).max() > 1e-3
+    plain = fc._HOST["merge"](fc.Case("merge", "plain", w, h, {"F": qr["F"], "B": q["B"], "feat": feat}))
+    assert not _same(qm["L"], plain["L"]) and not _same(qs["S"], fc._HOST["split"](fc.Case("split", "plain", w, h, {"y": q["y"], "B": q["B"], "feat": feat}))["S"])
+
+
+def _moments_behind(var, n_px):
+    """vr_variance is the moments times float(n) / float(n - 1) of the pixel's tile, and prepare with counts forms that very product again: moments that give
+    the read-back's words bit for bit, by division and a search over the quotient's neighbours (the true moments are among them or give the same product)"""
+    scale = np.array([[fc.variance_scale(int(n)) for n in row] for row in n_px], np.float32)[..., None]
+    m = (var / scale).astype(np.float32)
+    found = (m * scale).astype(np.float32) == var
+    for towards in (np.inf, -np.inf):
+        cand = m.copy()
+        for _ in range(2):
+            cand = np.nextafter(cand, np.float32(towards))
+            hit = ~found & ((cand * scale).astype(np.float32) == var)
+            m, found = np.where(hit, cand, m), found | hit
+    assert found.all(), int((~found).sum())
+    return m
+
+
+def test_the_probe_reproduces_a_demodulated_vr_denoise_of_a_ragged_frame():
+    """c3env at 33x31 after render_adaptive(2, 8, a threshold between the tiles' errors): vr_denoise with denoise_layers and denoise_demodulate, then the probe's
+    split, prepare with the renderer's tile_samples() as counts, five a-trous steps and merge, all with demod = 1, fed vr_resolved, vr_resolve_background,
+    vr_variance and vr_features: vr_denoised and vr_denoised_layer bit for bit.  denoise_prepare_kernel<true> reads counts[q.tile] here and nowhere else."""
+    import hk_adaptive
+    w, h = 33, 31
+    r = _hip("c3env", w, h)
+    r.variance = 1
+    r.render(2)
+    e = np.unique(r.tile_error())
+    e = e[np.isfinite(e)]
+    r.render_adaptive(2, 8, float(0.5 * (e[len(e) // 2 - 1] + e[len(e) // 2])))
+    counts = r.tile_samples()
+    assert len(np.unique(counts)) >= 2 and counts.min() >= 2
+    r.render_features_expected(2)
+    r.denoise_layers = 1
+    r.denoise_demodulate = 1
+    r.denoise()
+    want, want_layer = r.denoised(), r.denoised_layer()
+    y, B, var, feat = r.resolved(), r.resolve_background(), r.variance(), r.features()
+    n_px = hk_adaptive.per_pixel(counts, w, h)
+    px = (h, w, 4)
+    S = r.filter_probe("split", w, h, [y, B, feat], [px], demod=True)[0]
+    n = int(counts.max())
+    v, g = r.filter_probe("prepare", w, h, [_moments_behind(var, n_px), feat, np.ascontiguousarray(counts.reshape(-1), np.int32)], [(h, w), (h, w, 8)], i0=n,
+                          x=fc.variance_scale(n), demod=True)
+    sigma = tuple(r.denoise_sigma)
+    assert r.denoise_iterations == 5
+    c = S
+    for k in range(5):
+        c, v = r.filter_probe("atrous", w, h, [c, v, g], [px, (h, w) if k < 4 else None], sigma=sigma, i0=1 << k)
+    out, L = r.filter_probe("merge", w, h, [c, B, feat], [px, px], demod=True)
+    assert _same(out, want) and _same(L, want_layer) and not _same(want, r.framebuffer())
+    plain = r.filter_probe("merge", w, h, [c, B, feat], [px, px])[1]
+    assert not _same(plain, want_layer)                                          # (and the plain instances do not give it)
+    assert _same(r.denoised(), want) and _same(r.denoised_layer(), want_layer)
+    r.close()
+
+
+def test_demod_is_refused_outside_0_and_1_and_at_a_stage_without_a_demod_instance():
+    r = _hip("c2", 16, 16)
+    z4, z8, z1 = np.zeros((16, 16, 4), np.float32), np.zeros((16, 16, 8), np.float32), np.zeros((16, 16), np.float32)
+    with pytest.raises(volren_amd.VolrenError, match="demod must be 0 or 1"):
+        r.filter_probe("split", 16, 16, [z4, z4, z8], [(16, 16, 4)], demod=2)
+    with pytest.raises(volren_amd.VolrenError, match="demod = 1 goes with prepare, split, merge and upsample only"):
+        r.filter_probe("atrous", 16, 16, [z4, z1, z8], [(16, 16, 4), (16, 16)], i0=1, demod=True)
+    with pytest.raises(volren_amd.VolrenError, match="demod = 1 goes with prepare, split, merge and upsample only"):
+        r.filter_probe("regress", 16, 16, [z4, z8], [(16, 16, 4)], demod=True)
+    assert not r.filter_probe("split", 16, 16, [z4, z4, z8], [(16, 16, 4)], demod=True)[0].any()      # and the renderer still answers
+    r.close()
 
 
 def test_the_probe_reproduces_vr_denoise_from_the_renderers_read_backs():

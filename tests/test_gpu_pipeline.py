@@ -2,7 +2,7 @@
 refusal leaves behind) against one host model of that state (tests/hk_pipeline.py, itself held to the existing replays by tests/test_pipeline_model_host.py):
 (a) an all-pairs array over the denoiser's settings, frames, feature passes, cameras and shapes, three frames per row, every read-back after every frame bit for
 bit, and a refusal row per combination the product refuses; (b) committed random call sequences, every read-back or the refusal after every operation; (c) the
-rule of include/volren_amd.h on vr_upsample after a denoise call without layers; (d) the rows and one sequence a ShardedRenderer of three logical parts can
+rule of include/volren_amd.h on vr_upsample after a denoise call without layers, and its rule that vr_upsample reads "denoise_demodulate" at the call; (d) the rows and one sequence a ShardedRenderer of three logical parts can
 express.  The kernels themselves are tests/test_gpu_filter_probe.py's subject; nothing here has a tolerance."""
 import functools
 
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 NAME, SPP, RAYS = "c3env", 3, 2
 ACCEPTED, REFUSED = hp.covering_array()
 SETTINGS = (("denoise_moments", "moments"), ("denoise_reject", "reject"), ("denoise_resolve", "resolve"), ("denoise_layers", "layers"), ("denoise_filter", "filter"),
-            ("denoise_ridge", "ridge"), ("denoise_iterations", "iterations"))
+            ("denoise_demodulate", "demodulate"), ("denoise_ridge", "ridge"), ("denoise_iterations", "iterations"))
 
 
 def _id(row):
@@ -143,10 +143,14 @@ def test_a_refused_row_says_why_and_leaves_every_read_back(row):
     r.close()
 
 
-@pytest.mark.parametrize("factor", hp.NAMES)
+@pytest.mark.parametrize("factor", hp.NAMES + tuple("demodulated-" + n for n in hp.DEMODULATED))
 def test_every_factor_changes_the_result(factor):
-    """two accepted rows that differ in the factor alone (hk_pipeline.factor_pairs: iterations 2 against 3): some read-back differs"""
-    a, b = (_run_row(row) for row in hp.factor_pairs()[factor])
+    """two accepted rows that differ in the factor alone (hk_pipeline.factor_pairs: iterations 2 against 3): some read-back differs.  demodulated-*: the same
+    at the pivot with "denoise_demodulate" = 1 (hk_pipeline.factor_pairs_demodulated)"""
+    pairs = hp.factor_pairs()
+    if factor.startswith("demodulated-"):
+        factor, pairs = factor[len("demodulated-"):], hp.factor_pairs_demodulated()
+    a, b = (_run_row(row) for row in pairs[factor])
     differ = [n for n in hp.READERS if isinstance(a[n], Exception) != isinstance(b[n], Exception) or
               (not isinstance(a[n], Exception) and not hp.same_value(a[n], b[n]))]
     print(factor, differ)
@@ -253,6 +257,32 @@ def test_upsample_is_refused_once_a_denoise_without_layers_has_replaced_the_guid
     r.close()
 
 
+def test_upsample_reads_denoise_demodulate_at_its_call_and_a_flip_between_two_temporal_calls_drops_the_history():
+    """include/volren_amd.h, "Albedo demodulation": a layer made with the setting 0, upsampled with it at 1 (the lo layer is divided inside the call) and at 0
+    again (the plain call's picture: the first upsample's, had it run); then two temporal calls with the setting flipped in between -- the second starts a
+    history of its own -- and two more under the new value, which continue it.  Every read-back against the model after every operation."""
+    w, h = hp.SIZES[0]
+    r, scene = _renderer(w, h), hp.OracleScene(NAME, w, h)
+    m = hp.Model(scene, w, h)
+    tracer = _Tracer(r, scene)
+    _run_sequence([("frame", "uniform", 7, 0.0), ("features", "expected", 2), ("set", "denoise_layers", 1), ("set", "denoise_demodulate", 0), ("denoise",),
+                   ("upsample", 2, 2)], r, m, tracer, "made without")
+    plain, layer = r.upsampled(), r.denoised_layer()
+    _run_sequence([("set", "denoise_demodulate", 1), ("upsample", 2, 2)], r, m, tracer, "upsampled with")
+    assert not _same(r.upsampled(), plain) and _same(r.denoised_layer(), layer)
+    _run_sequence([("set", "denoise_demodulate", 0), ("upsample", 2, 2)], r, m, tracer, "upsampled without")
+    assert _same(r.upsampled(), plain)
+    _run_sequence([("denoise_temporal",), ("frame", "uniform", 8, 1.0), ("features", "expected", 2), ("denoise_temporal",)], r, m, tracer, "temporal without")
+    assert (r.denoise_history()[2] == 2).sum() > 50
+    _run_sequence([("set", "denoise_demodulate", 1), ("frame", "uniform", 9, 2.0), ("features", "expected", 2), ("denoise_temporal",)], r, m, tracer, "flipped")
+    assert (r.denoise_history()[2] == 1).all()                # a history of its own
+    _run_sequence([("frame", "uniform", 10, 3.0), ("features", "expected", 2), ("denoise_temporal",), ("upsample", 2, 2)], r, m, tracer, "temporal with")
+    assert (r.denoise_history()[2] == 2).sum() > 50
+    count = hp.tally([m.log])
+    assert count[("drop", "switch:denoise_demodulate")] == 1 and count[("op", "upsample_demod")] == 2 and not any(k[0] == "refused" for k in count)
+    r.close()
+
+
 def test_the_statistic_is_the_last_temporal_calls():
     """vr_denoise_reject_stat after unrelated later calls: kept across vr_denoise, a history reset and a change of a switch, the next temporal call's own after
     one with rejection, and refused after a temporal call without"""
@@ -310,6 +340,7 @@ def _sharded_inputs(s, kind, rays):
 
 
 SHARDED_ROWS = [row for row in ACCEPTED if hp.row_dict(row)["frame"] == "uniform"]
+SHARDED_ROWS += [row for row in hp.factor_pairs_demodulated()["moments"] if row not in SHARDED_ROWS]      # the divided layer's history, plain and under the moments
 
 
 @pytest.mark.parametrize("row", SHARDED_ROWS, ids=_id)

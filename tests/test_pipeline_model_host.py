@@ -1,6 +1,6 @@
 """CPU: the host model of the renderer's image-space state (tests/hk_pipeline.py) held to what exists, before tests/test_gpu_pipeline.py lets it judge the
 product: with one switch on at a time its three-frame sequences are the existing replays' (hk_temporal.Replay, hk_moments.Replay, hk_layers.Replay and layered,
-hk_regress.Replay, hk_resolve.resolved, hk_upsample.chain) bit for bit; the all-pairs array holds every pair the product accepts and every combination it
+hk_regress.Replay, hk_resolve.resolved, hk_upsample.chain; with "denoise_demodulate" on top of the layers hk_demod.layered, Replay and chain) bit for bit; the all-pairs array holds every pair the product accepts and every combination it
 refuses; and the committed seeds' call sequences fire every kind of operation, every rule that drops the history and every refusal at least twice.  The counts
 are printed.  No device is touched.
 
@@ -9,6 +9,8 @@ with a seed and a camera per frame, plus the host build of the expected-value pa
 import numpy as np
 import pytest
 
+import hk_adaptive
+import hk_demod
 import hk_denoise
 import hk_expected
 import hk_features
@@ -140,6 +142,87 @@ def test_upsample_by_two_is_the_host_chain(name):
         assert _same(m.upsampled(), out) and _same(m.upsampled_layer(), Lh) and _same(m.upsampled_features(), fh), i
 
 
+@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("ridge", (None, 0.0, 1.0))
+def test_demodulated_layers_are_the_demodulated_call(name, ridge):
+    """denoise_layers and denoise_demodulate on; ridge None: the a-trous iterations on the divided layer, otherwise the regression.  vr_denoise is
+    hk_demod.layered, vr_denoise_temporal hk_demod.Replay (with a ridge too) over the three frames."""
+    m, scene, frames = _model(name, denoise_layers=1, denoise_demodulate=1, **({} if ridge is None else {"denoise_filter": 1, "denoise_ridge": ridge}))
+    replay = hk_demod.Replay(ridge=ridge)
+    for i in range(FRAMES):
+        fb, var, feat, cam = _feed(m, scene, frames, i, True)
+        y, B = hk_resolve.resolved(scene.lo(), RAYS, fb, feat)
+        m.denoise()
+        out, L = hk_demod.layered(y, B, var, feat, SPP, ridge=ridge)[:2]
+        assert _same(m.denoised(), out) and _same(m.denoised_layer(), L), i
+        if name == "c3env":                                   # (under the LUT the divided layer filters differently)
+            assert not _same(out, hk_layers.layered(y, B, var, feat, SPP)[0] if ridge is None else hk_regress.layered(y, B, feat, ridge)[0])
+        m.denoise_temporal()
+        want = replay.frame(cam, y, B, var, feat, SPP, 0.1)
+        assert all(_same(a, b) for a, b in zip(m.denoise_history() + (m.denoised(), m.denoised_layer()), want)), i
+        assert _same(m.resolved(), y) and _same(m.resolve_background(), B)
+    assert (m.denoise_history()[2] >= 2).mean() > 0.5
+
+
+@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("form", ("plain", "tau3", "moments"))
+def test_the_demodulated_history_is_the_demodulated_replay(name, form):
+    """the temporal pass on the divided layer: plain, with rejection (the statistic too), with the moments (the moment records too)"""
+    tau = 3.0 if form == "tau3" else 0.0
+    m, scene, frames = _model(name, denoise_layers=1, denoise_demodulate=1, denoise_reject=tau, denoise_moments=int(form == "moments"))
+    replay = hk_demod.Replay(moments=form == "moments")
+    for i in range(FRAMES):
+        fb, var, feat, cam = _feed(m, scene, frames, i, True)
+        y, B = hk_resolve.resolved(scene.lo(), RAYS, fb, feat)
+        m.denoise_temporal()
+        want = replay.frame(cam, y, B, var, feat, SPP, 0.1, tau=tau)
+        assert all(_same(a, b) for a, b in zip(m.denoise_history() + (m.denoised(), m.denoised_layer()), want)), i
+        if form == "tau3":
+            assert _same(m.denoise_reject_stat(), replay.stat)
+        if form == "moments":
+            assert _same(m.denoise_history_moments(), replay.hist[3])
+    assert (m.denoise_history()[2] >= 2).mean() > 0.5
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_a_ragged_demodulated_frame_takes_each_tiles_own_count(name):
+    """synthetic per-tile counts of 2 and 8 by turns over the 3 x 2 tiles: hk_demod.layered on hk_adaptive.per_pixel of them, and not the call of either count"""
+    m, scene, frames = _model(name, denoise_layers=1, denoise_demodulate=1)
+    fb, var, feat, cam = _feed(m, scene, frames, 0, True)
+    ty, tx = hk_adaptive.tiles_of(W, H)
+    counts = np.array([(2, 8)[t & 1] for t in range(ty * tx)], np.int32)
+    m.new_frame(fb, var, feat, "expected", RAYS, counts, cam)
+    assert m.ragged()
+    y, B = hk_resolve.resolved(scene.lo(), RAYS, fb, feat)
+    m.denoise()
+    out, L = hk_demod.layered(y, B, var, feat, hk_adaptive.per_pixel(counts, W, H))[:2]
+    assert _same(m.denoised(), out) and _same(m.denoised_layer(), L)
+    assert not _same(out, hk_demod.layered(y, B, var, feat, 2)[0]) and not _same(out, hk_demod.layered(y, B, var, feat, 8)[0])
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_upsample_reads_the_setting_at_its_call(name):
+    """by 2: hk_demod.chain with the setting 1 at the call and hk_upsample.chain with 0, on a layer made with it and on one made without"""
+    for made_with in (1, 0):
+        m, scene, frames = _model(name, denoise_layers=1, denoise_demodulate=made_with)
+        for i in range(FRAMES):
+            fb, var, feat, cam = _feed(m, scene, frames, i, True)
+            m.denoise()
+            layer = m.denoised_layer()
+            for at_call in (1, 0):
+                m.set("denoise_demodulate", at_call)
+                m.upsample(2, RAYS)
+                chain = hk_demod.chain if at_call else hk_upsample.chain
+                out, Lh, fh, _ = chain(layer, feat, scene._at(2 * W, 2 * H), RAYS, 2)
+                assert m.upsampled_size() == (2 * W, 2 * H)
+                assert _same(m.upsampled(), out) and _same(m.upsampled_layer(), Lh) and _same(m.upsampled_features(), fh), (made_with, at_call, i)
+                assert _same(m.denoised_layer(), layer)
+            if name == "c3env":                               # (under the LUT the two calls differ)
+                assert not _same(out, hk_demod.chain(layer, feat, scene._at(2 * W, 2 * H), RAYS, 2)[0])
+            m.set("denoise_demodulate", made_with)
+    assert hp.tally([m.log])[("op", "upsample_demod")] == FRAMES
+
+
 def test_a_refused_call_leaves_the_model_as_it_was_and_the_rule_on_the_stale_guide():
     """every refusal in turn on a model that holds every read-back; and the sequence of the header's rule: after a denoise without layers the upsample is refused
     with words of its own, the layer stays readable, and a denoise with layers makes the call available again"""
@@ -157,12 +240,18 @@ def test_a_refused_call_leaves_the_model_as_it_was_and_the_rule_on_the_stale_gui
                                  (lambda: m.set_tiles(()), None, None),
                                  (lambda: _feed(m, scene, frames, 0, False), m.denoise_temporal, "was not last filled by render_features_expected"),
                                  (lambda: _feed(m, scene, frames, 0, False), m.resolve, "was not last filled by render_features_expected"),
-                                 (lambda: _feed(m, scene, frames, 0, True), None, None)):
+                                 (lambda: _feed(m, scene, frames, 0, True), None, None),
+                                 (lambda: (m.set("denoise_layers", 0), m.set("denoise_demodulate", 1)), m.denoise, "denoise_demodulate = 1 needs denoise_layers = 1"),
+                                 (lambda: None, m.denoise_temporal, "denoise_demodulate = 1 needs denoise_layers = 1"),
+                                 (lambda: (m.set("denoise_demodulate", 0), m.set("denoise_filter", 1)), m.denoise, "denoise_filter = 1 needs denoise_layers = 1"),
+                                 (lambda: (m.set("denoise_filter", 0), m.set("denoise_layers", 1)), None, None)):
         prepare()
         if call is not None:
             with pytest.raises(hp.Refused, match=words):
                 call()
         assert hp.unchanged(before, hp.read_all(m, hp.Refused)) == []
+    assert hp.tally([m.log])[("refused", "demod_layers")] == 2 and hp.tally([m.log])[("refused", "filter_layers")] == 1      # neither message is the other's kind
+    assert hp.REFUSALS["filter_layers"] not in hp.REFUSALS["demod_layers"] and hp.REFUSALS["demod_layers"] not in hp.REFUSALS["filter_layers"]
     m.set("denoise_layers", 0)
     layer = m.denoised_layer()
     m.denoise()
@@ -194,6 +283,14 @@ def test_the_array_holds_every_accepted_pair_and_every_refused_combination():
     assert (hp.covering_array()[0], hp.covering_array()[1]) == (accepted, refusals)      # deterministic
     for name, (a, b) in hp.factor_pairs().items():
         assert [n for n, x, y in zip(hp.NAMES, a, b) if x != y] == [name]
+    assert set(hp.factor_pairs()) == set(hp.NAMES) and all(hp.row_dict(r)["demodulate"] == 0 for n, p in hp.factor_pairs().items() if n != "demodulate" for r in p)
+    assert set(hp.factor_pairs_demodulated()) == set(hp.DEMODULATED)
+    for name, (a, b) in hp.factor_pairs_demodulated().items():
+        assert [n for n, x, y in zip(hp.NAMES, a, b) if x != y] == [name] and not hp.violated(a) and not hp.violated(b)
+        assert all(hp.row_dict(r)["demodulate"] == 1 and hp.row_dict(r)["layers"] == 1 for r in (a, b))
+    with_setting = [hp.row_dict(r) for r in accepted if hp.row_dict(r)["demodulate"] == 1]
+    assert len(with_setting) >= 4 and any(d["frame"] == "ragged" for d in with_setting) and all(d["layers"] == 1 for d in with_setting)
+    assert any(hp.row_dict(r)["demodulate"] == 1 and hp.row_dict(r)["layers"] == 0 for r in refusals)
     print("all-pairs array: %d accepted rows, %d refusal rows, %d pairs held, %d pairs forbidden" % (len(accepted), len(refusals), len(held), len(forbidden)))
     assert len(accepted) <= 24 and len(refusals) <= 8
 

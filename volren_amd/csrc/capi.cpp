@@ -863,6 +863,8 @@ static const char* filter_probe_error(int stage, int W, int H, const void* const
     for (int k = 0; k < VR_FILTER_PROBE_PARAMS; ++k) if (!std::isfinite(p[k])) return "vr_filter_probe: a parameter is not finite";
     const float i0 = p[5], i1 = p[8];
     if (i0 != std::floor(i0) || i1 != std::floor(i1)) return "vr_filter_probe: an integer parameter is not whole";
+    if (p[35] != 0.0f && p[35] != 1.0f) return "vr_filter_probe: demod must be 0 or 1";
+    if (p[35] != 0.0f && stage != 0 && stage != 4 && stage != 5 && stage != 7) return "vr_filter_probe: demod = 1 goes with prepare, split, merge and upsample only";
     switch (stage) {
     case 0: if (i0 < 1.0f || i0 > 0x1p30f) return "vr_filter_probe: prepare needs 1 <= n <= 2^30"; break;
     case 1: if (i0 < 1.0f || i0 > 0x1p20f) return "vr_filter_probe: atrous needs 1 <= step <= 2^20"; break;

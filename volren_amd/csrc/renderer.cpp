@@ -1129,6 +1129,7 @@ void RendererHIP::filter_probe(int stage, int W, int H, const void* const* in, f
     const DenoiseSigma sg{ params[0], params[1], params[2], params[3], params[4] };
     const int32_t i0 = (int32_t)params[5], i1 = (int32_t)params[8];
     const float x = params[6], tau = params[7];
+    const bool demod = params[35] != 0.0f;            // vr_demod.h: the DEMOD instance of prepare, split, merge and upsample
     std::vector<std::unique_ptr<DeviceBuffer>> held;
     auto fresh = [&](size_t bytes) { held.push_back(std::make_unique<DeviceBuffer>(bytes)); return held.back().get(); };
     auto up = [&](const void* src, size_t bytes) -> DeviceBuffer* {       // nullptr stays nullptr
@@ -1152,7 +1153,7 @@ void RendererHIP::filter_probe(int stage, int W, int H, const void* const* in, f
         const size_t tiles = (size_t)tile_count(W, H);
         DeviceBuffer *m = up(in[0], px * 4 * F4), *f = up(in[1], px * 8 * F4), *c = up(in[2], tiles * sizeof(int32_t));
         DeviceBuffer *v = down(out[0], px * F4), *g = down(out[1], px * 8 * F4);
-        launch_denoise_prepare(fl(m), fl(f), W, H, i0, x, c ? c->as<int32_t>() : nullptr, fl(v), fl(g), stream);
+        launch_denoise_prepare(fl(m), fl(f), W, H, i0, x, c ? c->as<int32_t>() : nullptr, fl(v), fl(g), stream, demod);
         break;
     }
     case 1: {
@@ -1193,13 +1194,13 @@ void RendererHIP::filter_probe(int stage, int W, int H, const void* const* in, f
     }
     case 4: {
         DeviceBuffer *y = up(in[0], px * 4 * F4), *B = up(in[1], px * 4 * F4), *f = up(in[2], px * 8 * F4);
-        launch_layers_split(fl(y), fl(B), fl(f), W, H, fl(down(out[0], px * 4 * F4)), stream);
+        launch_layers_split(fl(y), fl(B), fl(f), W, H, fl(down(out[0], px * 4 * F4)), stream, demod);
         break;
     }
     case 5: {
         DeviceBuffer *Fq = up(in[0], px * 4 * F4), *B = up(in[1], px * 4 * F4), *f = up(in[2], px * 8 * F4);
         DeviceBuffer *o = down(out[0], px * 4 * F4), *L = down(out[1], px * 4 * F4);
-        launch_layers_merge(fl(Fq), fl(B), fl(f), W, H, fl(o), fl(L), stream);
+        launch_layers_merge(fl(Fq), fl(B), fl(f), W, H, fl(o), fl(L), stream, demod);
         break;
     }
     case 6: {
@@ -1215,7 +1216,7 @@ void RendererHIP::filter_probe(int stage, int W, int H, const void* const* in, f
         P.u.resolution[0] = f * W; P.u.resolution[1] = f * H;
         DeviceBuffer *l = up(in[0], px * 4 * F4), *g = up(in[1], px * 8 * F4), *hf = up(in[2], hi * 8 * F4);
         DeviceBuffer *o = down(out[0], hi * 4 * F4), *L = down(out[1], hi * 4 * F4);
-        launch_upsample(P, fl(l), fl(g), W, H, f, fl(hf), i0, sg, fl(o), fl(L), stream);
+        launch_upsample(P, fl(l), fl(g), W, H, f, fl(hf), i0, sg, fl(o), fl(L), stream, demod);
         break;
     }
     case 8: {

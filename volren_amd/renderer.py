@@ -260,10 +260,10 @@ class Renderer:
 
     FILTER_STAGES = ("prepare", "atrous", "temporal", "resolve", "split", "merge", "regress", "upsample", "adaptive_error")
 
-    def filter_probe(self, stage, w, h, inputs, outputs, sigma=(4.0, 0.5, 0.1, 0.25, 0.2), i0=0, x=0.0, tau=0.0, i1=0, cur=None, prev=None):
+    def filter_probe(self, stage, w, h, inputs, outputs, sigma=(4.0, 0.5, 0.1, 0.25, 0.2), i0=0, x=0.0, tau=0.0, i1=0, cur=None, prev=None, demod=False):
         """Test hook (include/volren_amd.h vr_filter_probe): one launcher of the image-space kernels on host arrays.  stage: a name of FILTER_STAGES or its number;
         inputs: up to 6 arrays in the stage's order, float32 (counts and tile ids int32), None where one is left out; outputs: up to 5 shapes in the stage's order,
-        None likewise; the rest is the parameter block (cur, prev: cameras of 13 float32).  Returns the outputs as float32 arrays, None where none was asked for.
+        None likewise; the rest is the parameter block (cur, prev: cameras of 13 float32; demod: the DEMOD instance of prepare, split, merge, upsample).  Returns the outputs as float32 arrays, None where none was asked for.
         Nothing of the renderer changes."""
         stage = self.FILTER_STAGES.index(stage) if isinstance(stage, str) else int(stage)
         keep = []
@@ -290,6 +290,7 @@ class Renderer:
             p[9:22] = cur
         if prev is not None:
             p[22:35] = prev
+        p[35] = int(demod)
         _lib.check(self._L.vr_filter_probe(self._h, stage, int(w), int(h), pin, pout, p.ctypes.data))
         return outs
 
